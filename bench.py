@@ -11,11 +11,15 @@ runs the same per-GPU workload on its own frames); torch.distributed is used onl
 timing barrier and the max-over-ranks reduction.  `python bench.py --gpus N` launches its own
 N ranks (one per GPU, torch.distributed.run on 127.0.0.1) when it is not already running under
 torchrun, and REFUSES (non-zero exit) when fewer than N GPUs are visible: the printed `n_gpus`
-is always the number of GPUs that were measured.  N > 1 lines carry the same `roofline` and
-`cpu_baseline` objects plus the SHARDED host scopes (all ranks reading one 4:2:0 file / their own
+is always the number of GPUs that were measured.  With --full, N > 1 lines carry the same `roofline`
+and `cpu_baseline` objects plus the SHARDED host scopes (all ranks reading one 4:2:0 file / their own
 host memory at the same time: where host DRAM and PCIe contention decide).
 
-Prints ONE JSON line on rank 0 (contract in the task statement) with two extra objects:
+Prints ONE JSON line on rank 0: the headline (`metric`, `value`, `unit`, `ms_per_step`, `dtype` ...)
+and `config`.  A plain run does only that: set-up, warm-up, the --steps timed steps, the line.
+--dump-outputs DIR also writes what the last timed step computed as DIR/<name>.npy.  --full adds
+every side measurement and check (stage breakdown, opt-in plans, host scopes, other configs,
+latency, parity vs the oracle) and, among others, these two objects:
   roofline      dominant kernel = FC1 (77.6 % of the MACs): algorithmic FLOP / HIP-event
                 kernel time vs the fp32-MFMA peak of MI355X_MICROARCH.md (157.3 TFLOP/s)
   cpu_baseline  the CPU oracle (a port of the reference's TF-CPU path; TensorFlow itself
@@ -59,16 +63,21 @@ def synth_luma(width, height, frames, seed):
     import numpy as np
     rng = np.random.default_rng(seed)
     out = np.empty((frames, height, width), dtype=np.uint8)
-    yy, xx = np.mgrid[0:height, 0:width]
+    yy, xx = np.ogrid[0:height, 0:width]
     kind = ((yy // 256) + (xx // 256)) % 4
-    grad = ((yy * 3 + xx * 2) // 8) % 256
-    flat = (((yy // 16) * 31 + (xx // 16) * 17) % 200 + 20)
+    is_grad, is_blur, is_flat = kind == 0, kind == 1, kind == 2
+    grad = (((yy * 3 + xx * 2) // 8) % 256).astype(np.uint8)
+    flat = (((yy // 16) * 31 + (xx // 16) * 17) % 200 + 20).astype(np.uint8)
     for f in range(frames):
         noise = rng.integers(0, 256, size=(height, width), dtype=np.uint8)
         blur = noise.astype(np.uint16)
         blur = (blur + np.roll(blur, 1, 0) + np.roll(blur, 1, 1) + np.roll(np.roll(blur, 1, 0), 1, 1)) // 4
-        frame = np.where(kind == 0, (grad + f) % 256, np.where(kind == 1, blur, np.where(kind == 2, flat, noise)))
-        out[f] = frame.astype(np.uint8)
+        # the four macro-tile kinds written in place, in 8 bits (uint8 addition wraps: (grad + f) % 256)
+        frame = out[f]
+        frame[...] = noise
+        np.copyto(frame, flat, where=is_flat)
+        np.copyto(frame, blur, where=is_blur, casting="unsafe")
+        np.add(grad, np.uint8(f % 256), out=frame, where=is_grad)
     return out
 
 
@@ -85,12 +94,20 @@ def main():
     ap.add_argument("--no-fast-plan", action="store_true", help="skip the further timed regions (opt-in FC1 / trunk plans on the 16-bit matrix pipe), reported as `fast_plan*`")
     ap.add_argument("--no-other-configs", action="store_true", help="skip the short driver-timed regions of the other BASELINE configs (`other_configs`)")
     ap.add_argument("--fast-plans", default="2,3", help="which opt-in plans get a timed region (profiling runs: --fast-plans 3)")
+    ap.add_argument("--full", action="store_true",
+                    help="also run every side measurement and check (stage breakdown, roofline, box calibration, opt-in plans, host scopes, "
+                         "CPU baselines, other configs, latency, parity vs the oracle); the --no-* options above prune it.  Without it "
+                         "the run is set-up, warm-up, the timed steps and the headline line")
+    ap.add_argument("--dump-outputs", metavar="DIR",
+                    help="write what the last timed step computed as DIR/<name>.npy (float32; rank 0's frames when --gpus > 1)")
     args = ap.parse_args()
 
     import numpy as np
     import torch  # first: both torch and libethcnn bind libamdhip64.so.7 -> one HIP runtime in the process
     if args.gpus < 1:
         raise SystemExit("bench.py: --gpus must be >= 1")
+    if args.steps < 1 or args.warmup < 0:
+        raise SystemExit("bench.py: --steps must be >= 1 and --warmup >= 0")
     if not torch.cuda.is_available():
         raise SystemExit("bench.py needs a GPU (libethcnn has no CPU fallback)")
     if "WORLD_SIZE" not in os.environ and args.gpus > 1:
@@ -168,6 +185,8 @@ def main():
         for _ in range(8):
             step()
         ctx.synchronize()
+    if ldp:
+        ldp_frame[0] = 0  # the warm-up and timed steps walk the same frames and recurrent states in every run
     for _ in range(args.warmup):
         step()
     ctx.synchronize()
@@ -182,17 +201,28 @@ def main():
     t1 = time.perf_counter()
     elapsed = t1 - t0
     st = ctx.stage_times()
-    # per-stage breakdown: a short extra run OUTSIDE the timed region (an event pair per launch costs stream time, so it
-    # is kept out of `value`), with the pass pipeline OFF: with it on the CTU-load stage of step i+1 runs beside FC1 of step i
-    # (throttled to one block per CU on purpose) and the stage intervals overlap
-    ctx.set_pass_pipeline(False)
-    ctx.set_profiling(2)
-    ctx.reset_stage_times()
-    for _ in range(3):
-        step()
-    st_all = ctx.stage_times()
     ctx.set_profiling(0)
-    ctx.set_pass_pipeline(True)  # (the library's default; it reads no environment switch for it -- ADVICE r04)
+    if args.dump_outputs and rank == 0:
+        # what a caller of the timed path receives from its last step: the gated probabilities of every CTU of the step
+        # (21 per CTU; c4, the largest, is 17.8 MB) and, for the LDP step, the recurrent state it hands to the next frame
+        dump = {"probabilities": d_out.download(np.float32, ctus_per_step * 21).reshape(ctus_per_step, 21)}
+        if ldp:
+            dump["lstm_state"] = d_state[ldp_frame[0] & 1].download(np.float32, nctu * 896).reshape(nctu, 896)
+        os.makedirs(args.dump_outputs, exist_ok=True)
+        for name, arr in dump.items():
+            np.save(os.path.join(args.dump_outputs, name + ".npy"), arr)
+    if args.full:
+        # per-stage breakdown: a short extra run OUTSIDE the timed region (an event pair per launch costs stream time, so it
+        # is kept out of `value`), with the pass pipeline OFF: with it on the CTU-load stage of step i+1 runs beside FC1 of step i
+        # (throttled to one block per CU on purpose) and the stage intervals overlap
+        ctx.set_pass_pipeline(False)
+        ctx.set_profiling(2)
+        ctx.reset_stage_times()
+        for _ in range(3):
+            step()
+        st_all = ctx.stage_times()
+        ctx.set_profiling(0)
+        ctx.set_pass_pipeline(True)  # (the library's default; it reads no environment switch for it -- ADVICE r04)
     if dist is not None:
         tt = torch.tensor([elapsed], dtype=torch.float64, device="cuda" if backend == "nccl" else "cpu")
         dist.all_reduce(tt, op=dist.ReduceOp.MAX)
@@ -200,14 +230,14 @@ def main():
 
     # collective side measurements (every rank takes part; never `value`): the sharded host scopes at N > 1
     sharded = None
-    if dist is not None and not ldp and not args.no_host_scopes:
+    if args.full and dist is not None and not ldp and not args.no_host_scopes:
         sharded = host_scopes_sharded(ctx, luma, W, H, NF, QP, rank, world, dist, backend, barrier)
 
     # FC1 plans 1 / 2 ("fast": split operands on the 16-bit matrix pipe, ethcnn_set_fc1_plan) -- further timed regions of the same K
     # steps under the same barriers, reported beside the headline as `fast_plan` (bf16 x 3) and `fast_plan_fp16x2`, never as
     # `value`: their results agree with the exact plan to ~1e-6 but are not bit-identical to the oracle
     fast = {}
-    if not ldp and not args.no_fast_plan:
+    if args.full and not ldp and not args.no_fast_plan:
         exact_out = d_out.download(np.float32, ctus_per_step * 21).reshape(-1, 21) if rank == 0 else None
         for plan in [int(p) for p in args.fast_plans.split(",") if p]:
             ctx.set_profiling(0)
@@ -281,13 +311,6 @@ def main():
     if rank == 0:
         total_ctus = ctus_per_step * args.steps * world
         value = total_ctus / elapsed
-        # level 1 times the FC1 stage of every 3rd pass of the timed region; the rate uses the CTUs of exactly those passes
-        fc1_ms = st["ms"]["fc1"] / max(1, st["timed"]["fc1"])
-        ctus_per_launch = st["timed_ctus"]["fc1"] / max(1, st["timed"]["fc1"])
-        fc1_tflops = FC1_FLOP_PER_CTU * st["timed_ctus"]["fc1"] / (st["ms"]["fc1"] * 1e-3) / 1e12 if st["ms"]["fc1"] > 0 else 0.0
-        tile_ms = st_all["ms"]["tile"] / max(1, st_all["timed"]["tile"])
-        tile_gbps = 4096.0 * st_all["timed_ctus"]["tile"] / (st_all["ms"]["tile"] * 1e-3) / 1e9 if st_all["ms"]["tile"] > 0 else 0.0
-        kernel_ms = sum(st_all["ms"].values()) / 3.0
         result = {
             "metric": "CTUs/sec (ETH-CNN inference)", "value": value, "unit": "CTU/s", "n_gpus": world,
             "steps": args.steps, "warmup": args.warmup, "ms_per_step": elapsed / args.steps * 1e3,
@@ -299,6 +322,16 @@ def main():
                        "one_rank_per_device": os.environ.get("BENCH_FORCE_DEVICE") is None,  # False only under the one-GPU test hook
                        "rendezvous_backend": backend if world > 1 else None,
                        "device": ctx.device_name, "host_affinity": numa, "host_fill_threads_per_rank": ctx.host_threads},
+        }
+    if rank == 0 and args.full:
+        # level 1 times the FC1 stage of every 3rd pass of the timed region; the rate uses the CTUs of exactly those passes
+        fc1_ms = st["ms"]["fc1"] / max(1, st["timed"]["fc1"])
+        ctus_per_launch = st["timed_ctus"]["fc1"] / max(1, st["timed"]["fc1"])
+        fc1_tflops = FC1_FLOP_PER_CTU * st["timed_ctus"]["fc1"] / (st["ms"]["fc1"] * 1e-3) / 1e12 if st["ms"]["fc1"] > 0 else 0.0
+        tile_ms = st_all["ms"]["tile"] / max(1, st_all["timed"]["tile"])
+        tile_gbps = 4096.0 * st_all["timed_ctus"]["tile"] / (st_all["ms"]["tile"] * 1e-3) / 1e9 if st_all["ms"]["tile"] > 0 else 0.0
+        kernel_ms = sum(st_all["ms"].values()) / 3.0
+        result.update({
             "roofline": {"kernel": FC1_KERNEL_NOTE,
                          "bound": "mfma", "achieved": fc1_tflops, "peak": PEAK_F32_MFMA_TFLOPS, "unit": "TFLOP/s",
                          "frac": fc1_tflops / PEAK_F32_MFMA_TFLOPS, **pmc_traffic(args.workload),
@@ -322,7 +355,7 @@ def main():
                                "counter_bytes_per_ctu": ctu_load_counters(args.workload, ctus_per_step),
                                "form": "k0_tile_slab on a side stream beside FC1 of the previous step; the form folded into the trunk "
                                        "(no slab records, no side stream) was measured 3.5 % slower per step (profiles/r04_tile_fold.txt)"},
-        }
+        })
         # box calibration, right behind the timed region (same clocks, same temperature): what THIS GPU sustains in pure
         # exact-fp32 MFMAs.  Boxes of one pool differ by several per cent (round 3 saw 39.4 - 42.0 M CTU/s from the same code);
         # frac_of_box_mfma_rate is the fraction that does not move with the box
@@ -395,6 +428,7 @@ def main():
             result["parity_first_frame_bit_exact"] = first_frame_parity(ctx, d_out, luma, W, H, QP, nctu)
             if world == 1 and not args.no_cpu_baseline:
                 result["decision_stability"] = decision_stability(ctx, luma, W, H, QP)
+    if rank == 0:
         print(json.dumps(result))
         sys.stdout.flush()
     d_in.free()

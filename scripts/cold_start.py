@@ -3,7 +3,7 @@
 process start, imports, HIP runtime init, context, checkpoint, first launch, compute, exit.  The reference quotes "1~10 s" for its
 TensorFlow start-up (README.md:124).  Measured here per config and per launcher, 1 / 2 / 8 workers on the one visible GPU:
 
-    python scripts/cold_start.py [reps]      -> gpurun_out/cold_start.txt  (profiles/r06_cold_start.txt)
+    python scripts/cold_start.py [reps]      -> bench_out/cold_start.txt  (profiles/r06_cold_start.txt)
 
 C1 768x512 x 1 (96 CTUs), C2 1920x1080 x 50, C4's 1/8 share 4928x3264 x 54.  Launchers: the Python host mirror (one process; workers =
 threads inside the library), the same with a PROCESS per worker (ETHCNN_SHARD_PROCESSES=1, round 5's form), the native C tool.  Every
@@ -72,8 +72,8 @@ def main():
         os.remove(yuv)
     text = "\n".join(out)
     print(text)
-    os.makedirs(os.path.join(ROOT, "gpurun_out"), exist_ok=True)
-    open(os.path.join(ROOT, "gpurun_out", "cold_start.txt"), "w").write(text + "\n")
+    os.makedirs(os.path.join(ROOT, "bench_out"), exist_ok=True)
+    open(os.path.join(ROOT, "bench_out", "cold_start.txt"), "w").write(text + "\n")
 
 
 if __name__ == "__main__":

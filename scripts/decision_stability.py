@@ -3,7 +3,7 @@
 (3840x2160 x 50 frames, QP 22/27/32/37) with both synthetic head gains through the HIP path, against the
 literal-TF-order fp32 evaluation (oracle mode 1) and the float64 restatement.  Counts the outputs within
 1e-6 / 1e-5 / 1e-4 of every threshold the reference ships and the thresholded decisions that differ.
-Run on the GPU box: python scripts/decision_stability.py [frames] > gpurun_out/decision_stability.json"""
+Run on the GPU box: python scripts/decision_stability.py [frames] > bench_out/decision_stability.json"""
 import importlib
 import json
 import os

@@ -4,11 +4,11 @@
 # against the shipped lean form (agent-scope accesses + s_waitcnt vmcnt(0), no cache maintenance): correctness of the fenced build on the
 # tests of those paths, then latency A/B/A/B at 96 / 510 / 2040 CTUs (device-resident pictures) and per LDP frame.
 set -u
-mkdir -p gpurun_out
+mkdir -p bench_out
 REPO=$PWD
 FENCE=$REPO/hevc-complexity-reduction_amd/lib_fence/libethcnn.so
 [ -s $FENCE ] || bash scripts/build_variant.sh fence -DETHCNN_FULL_FENCE
-OUT=gpurun_out/handoff_fence_ab.txt
+OUT=bench_out/handoff_fence_ab.txt
 {
 echo "# scripts/gpu_fence_ab.sh: lean = shipped library; fence = the same sources with -DETHCNN_FULL_FENCE (buffer_wbl2 sc1 before every announcing"
 echo "# atomic's s_waitcnt, buffer_inv sc1 behind every consumer's flag read / completer's ticket)"

@@ -1,7 +1,7 @@
 #!/bin/bash
 # PMC passes for one bench configuration: WL, env knobs inherited. Output summary per kernel.
 set -u
-mkdir -p gpurun_out
+mkdir -p bench_out
 export TMPDIR=/tmp
 REPO=$PWD
 WL=${WL:-c3}
@@ -10,13 +10,13 @@ cd /tmp
 i=0
 for pmc in "SQ_VALU_MFMA_BUSY_CYCLES SQ_BUSY_CYCLES GRBM_GUI_ACTIVE SQ_WAVES" "SQ_WAVE_CYCLES SQ_WAIT_ANY SQ_WAIT_INST_ANY SQ_ACTIVE_INST_ANY SQ_ACTIVE_INST_LDS SQ_WAIT_INST_LDS SQ_ACTIVE_INST_VMEM SQ_ACTIVE_INST_VALU" "SQ_LDS_BANK_CONFLICT SQ_LDS_IDX_ACTIVE SQ_LDS_ADDR_CONFLICT SQ_INSTS_LDS SQ_INSTS_VALU SQ_INSTS_VMEM_RD SQ_INSTS_SALU SQ_INSTS_MFMA" "TCC_HIT_sum TCC_MISS_sum TCC_REQ_sum TCC_EA0_RDREQ_sum" "FETCH_SIZE" "WRITE_SIZE"; do
   i=$((i+1))
-  rocprofv3 --pmc $pmc --kernel-trace --output-format csv -d $REPO/gpurun_out/${TAG}_$i -o p -- python $REPO/bench.py --workload $WL --no-cpu-baseline --no-host-scopes --steps 3 --warmup 1 > $REPO/gpurun_out/${TAG}_$i.log 2>&1 || tail -3 $REPO/gpurun_out/${TAG}_$i.log
+  rocprofv3 --pmc $pmc --kernel-trace --output-format csv -d $REPO/bench_out/${TAG}_$i -o p -- python $REPO/bench.py --full --workload $WL --no-cpu-baseline --no-host-scopes --steps 3 --warmup 1 > $REPO/bench_out/${TAG}_$i.log 2>&1 || tail -3 $REPO/bench_out/${TAG}_$i.log
 done
 cd $REPO
 python - <<PY
 import csv, glob, collections
 tot=collections.defaultdict(dict)
-for f in sorted(glob.glob("gpurun_out/${TAG}_*/**/*counter_collection.csv", recursive=True)):
+for f in sorted(glob.glob("bench_out/${TAG}_*/**/*counter_collection.csv", recursive=True)):
     agg=collections.defaultdict(lambda: collections.defaultdict(float)); cnt=collections.Counter()
     for r in csv.DictReader(open(f)):
         k=r["Kernel_Name"]

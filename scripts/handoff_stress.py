@@ -1,7 +1,7 @@
 """Stress of the hand-offs inside a launch (profiles/r06_handoff_fence_ab.txt: the full LLVM release / acquire sequence
 costs 20 us of a 43 us 1080p call, so the lean form ships -- agent-scope accesses + s_waitcnt, no cache maintenance -- and THIS is its test).
 
-    LAUNCHES=100000 python scripts/handoff_stress.py      -> gpurun_out/handoff_stress.txt
+    LAUNCHES=100000 python scripts/handoff_stress.py      -> bench_out/handoff_stress.txt
 
 The single-launch small pass and the LDP frame launches run back to back on ONE context, i.e. on the SAME workspace and sync areas,
 with DIFFERENT data every launch (K pictures cycled with a stride coprime to K, three geometries that move the buffers' layout), every
@@ -135,8 +135,8 @@ def main():
     out.append("handoff stress: %d single-launch passes, %d LDP steps (%d launches of a dataflow kernel in all) in %.1f s beside %d C3-sized exact passes and %d x 128 MB "
                "of copies on the same GPU: %d mismatches" % (n_ai, n_ldp, n_ai + 2 * n_ldp, dt, hog_steps[0], hog_steps[1], bad_ai + bad_ldp))
     print(out[-1])
-    os.makedirs(os.path.join(ROOT, "gpurun_out"), exist_ok=True)
-    open(os.path.join(ROOT, "gpurun_out", "handoff_stress.txt"), "a").write("\n".join(out) + "\n")
+    os.makedirs(os.path.join(ROOT, "bench_out"), exist_ok=True)
+    open(os.path.join(ROOT, "bench_out", "handoff_stress.txt"), "a").write("\n".join(out) + "\n")
     c.close()
     return 1 if bad_ai + bad_ldp else 0
 

@@ -4,7 +4,7 @@ UNCHANGED HM encoder (/root/reference/HM-16.5_Test_AI/bin/TAppEncoderStatic) a c
 and reports the bitstream md5.  HM's hook (TAppEncCfg.cpp:2317-2321) runs
 `python video_to_cu_depth.py <yuv> <w> <h> <qp>` in its cwd; with no GPU here that command is
 satisfied by a replay shim that installs a cu_depth.dat produced earlier (on the GPU box by the
-real launcher -> gpurun_out/hm/, or by the CPU oracle) -- what is checked is that HM consumes
+real launcher -> bench_out/hm/, or by the CPU oracle) -- what is checked is that HM consumes
 the file layout and that GPU-made and oracle-made files drive identical bitstreams.
 
 usage: hm_bitstream_check.py <seq.yuv> <w> <h> <qp> <frames> <cu_depth_a.dat> [<cu_depth_b.dat> ...]

@@ -1,6 +1,6 @@
 #!/usr/bin/env python
 """Runs HERE (build container).  The reference's prebuilt, UNCHANGED HM encoder replays the
-cu_depth.dat that the in-process build produced on the GPU box (gpurun_out/hm_inprocess/) with the
+cu_depth.dat that the in-process build produced on the GPU box (bench_out/hm_inprocess/) with the
 same configuration file, and the two bitstreams are compared: the in-process hook
 drives HM to the same bitstream as the reference's file hand-off."""
 import hashlib
@@ -12,7 +12,7 @@ import tempfile
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 HM_BIN = "/root/reference/HM-16.5_Test_AI/bin"
-src = os.path.join(ROOT, "gpurun_out", "hm_inprocess")
+src = os.path.join(ROOT, "bench_out", "hm_inprocess")
 d = tempfile.mkdtemp(prefix="hm_")
 shutil.copy(os.path.join(src, "cu_depth.dat"), os.path.join(d, "replay_cu_depth.dat"))
 open(os.path.join(d, "Thr_info.txt"), "w").write("0.5 0.5 0.5 0.5 0.5 0.5\n")
@@ -21,7 +21,7 @@ open(os.path.join(d, "video_to_cu_depth.py"), "w").write(
 exe = os.path.join(d, "TAppEncoderStatic")
 shutil.copy(os.path.join(HM_BIN, "TAppEncoderStatic"), exe)
 os.chmod(exe, 0o755)
-yuv = os.path.join(ROOT, "gpurun_out", "hm", "seq.yuv")
+yuv = os.path.join(ROOT, "bench_out", "hm", "seq.yuv")
 r = subprocess.run([exe, "-c", os.path.join(ROOT, "scripts", "hm_intra_test.cfg"), "-i", yuv, "-wdt", "416", "-hgt", "240",
                     "-fr", "30", "-f", "4", "-q", "32", "-b", "str.bin", "-o", ""], cwd=d, capture_output=True, text=True)
 if r.returncode != 0:

@@ -1,5 +1,5 @@
 #!/usr/bin/env python
-"""GPU box: writes gpurun_out/hm/{seq.yuv, cu_depth_gpu.dat, cu_depth_oracle.dat} for
+"""GPU box: writes bench_out/hm/{seq.yuv, cu_depth_gpu.dat, cu_depth_oracle.dat} for
 scripts/hm_bitstream_check.py (which runs where the HM binary lives).  cu_depth_gpu.dat is
 produced by the real drop-in launcher exactly as HM's hook would run it."""
 import os
@@ -15,7 +15,7 @@ import bench  # noqa: E402
 import ethcnn_np as oracle  # noqa: E402
 
 w, h, frames, qp, seed, gain = 416, 240, 4, 32, 9, 8.0
-out = os.path.join(ROOT, "gpurun_out", "hm")
+out = os.path.join(ROOT, "bench_out", "hm")
 os.makedirs(out, exist_ok=True)
 luma = bench.synth_luma(w, h, frames, 1)
 yuv = np.concatenate([np.concatenate([luma[f].reshape(-1), np.full(w * h // 2, 128, np.uint8)]) for f in range(frames)])

@@ -1,6 +1,6 @@
 """Joules per TFLOP of gfx950's matrix instructions by shape / type on random operands (round 6; plan 3 is bound by the socket's power cap).
 
-    python scripts/mfma_energy.py [seconds per kind]   -> gpurun_out/mfma_energy.txt (profiles/r06_mfma_energy.txt)
+    python scripts/mfma_energy.py [seconds per kind]   -> bench_out/mfma_energy.txt (profiles/r06_mfma_energy.txt)
 
 scripts/ubench/mfma_energy.hip loops one instruction (3 waves per SIMD, 4 independent accumulators, operands that change every iteration) while
 this script samples the socket's power and shader clock (hwmon, 20 ms); steady state = the busy samples' median."""
@@ -44,8 +44,8 @@ def main():
         mhz = sorted(r[1] for r in tail)[len(tail) // 2]
         lines.append("%-52s %10.1f %8.0f %8.0f %12.3f %14.3f" % (name, tf, w, mhz, w / tf if tf else 0, (w - idle) / tf if tf else 0))
         print(lines[-1], flush=True)
-    os.makedirs(os.path.join(ROOT, "gpurun_out"), exist_ok=True)
-    open(os.path.join(ROOT, "gpurun_out", "mfma_energy.txt"), "w").write("\n".join(lines) + "\n")
+    os.makedirs(os.path.join(ROOT, "bench_out"), exist_ok=True)
+    open(os.path.join(ROOT, "bench_out", "mfma_energy.txt"), "w").write("\n".join(lines) + "\n")
 
 
 if __name__ == "__main__":

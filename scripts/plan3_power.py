@@ -1,6 +1,6 @@
 """Why plan 3's trunk and FC1 are not overlapped: the experiment and the numbers.
 
-    python scripts/plan3_power.py [seconds per setting]     -> gpurun_out/plan3_overlap.txt (profiles/r06_plan3_overlap.txt)
+    python scripts/plan3_power.py [seconds per setting]     -> bench_out/plan3_overlap.txt (profiles/r06_plan3_overlap.txt)
 
 1. Socket power and shader clock (hwmon, 20 ms samples, steady state) of a C3 step looped under plan 3 and plan 0, and of EACH STAGE of
    plan 3 looped alone (experiments build, ETHCNN_STAGE_ONLY): which stages sit at the 1400 W cap, what a step costs in joules.
@@ -138,8 +138,8 @@ def main():
             res[label] = r[1:]
         print(lines[-1], flush=True)
     text = "\n".join(lines)
-    os.makedirs(os.path.join(ROOT, "gpurun_out"), exist_ok=True)
-    open(os.path.join(ROOT, "gpurun_out", "plan3_overlap.txt"), "w").write(text + "\n")
+    os.makedirs(os.path.join(ROOT, "bench_out"), exist_ok=True)
+    open(os.path.join(ROOT, "bench_out", "plan3_overlap.txt"), "w").write(text + "\n")
 
 
 if __name__ == "__main__":

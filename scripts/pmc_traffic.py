@@ -6,9 +6,9 @@ visited the other configs (three grid sizes in one average).  Here every row is 
     python scripts/pmc_traffic.py collect <workload> <dir of the FETCH_SIZE pass> <dir of the WRITE_SIZE pass>
 
 reads the two counter_collection.csv files of `bench.py --workload <wl> --no-other-configs ...` runs (scripts/gpu_step_traffic.sh),
-writes gpurun_out/traffic_by_kernel_grid_<wl>.csv (one row per kernel x grid: dispatches, FETCH_SIZE / WRITE_SIZE averages as
+writes bench_out/traffic_by_kernel_grid_<wl>.csv (one row per kernel x grid: dispatches, FETCH_SIZE / WRITE_SIZE averages as
 reported in KB, bytes = FETCH x 2 x 1024 + WRITE x 1024 -- the gfx950 correction of MI355X_MICROARCH.md) and merges the per-step sums
-of every plan into gpurun_out/step_traffic.json:  <wl>, <wl>_plan2, <wl>_plan3 -> per_kernel {"kernel @grid": {...}}, bytes_per_step,
+of every plan into bench_out/step_traffic.json:  <wl>, <wl>_plan2, <wl>_plan3 -> per_kernel {"kernel @grid": {...}}, bytes_per_step,
 fc1_bytes_per_launch (= the FC1 rows of that step: what bench.py prints as roofline.traffic AND finds again under
 hbm.per_kernel_bytes -- the same numbers by construction, asserted in tests/test_gpu_bench_contract.py).
 
@@ -67,17 +67,17 @@ def collect(wl, dir_fetch, dir_write):
         w_kb = wr[k][0] / wr[k][1] if k in wr and wr[k][1] else 0.0
         rows[k] = {"dispatches": max(fe.get(k, [0, 0])[1], wr.get(k, [0, 0])[1]), "fetch_kb": f_kb, "write_kb": w_kb,
                    "fetch_bytes": int(f_kb * 1024 * 2), "write_bytes": int(w_kb * 1024)}
-    os.makedirs(os.path.join(ROOT, "gpurun_out"), exist_ok=True)
-    csv_path = os.path.join(ROOT, "gpurun_out", "traffic_by_kernel_grid_%s.csv" % wl)
+    os.makedirs(os.path.join(ROOT, "bench_out"), exist_ok=True)
+    csv_path = os.path.join(ROOT, "bench_out", "traffic_by_kernel_grid_%s.csv" % wl)
     with open(csv_path, "w") as f:
-        f.write("# rocprofv3 --pmc FETCH_SIZE / --pmc WRITE_SIZE (separate passes, --kernel-trace only) of `python bench.py --workload %s "
+        f.write("# rocprofv3 --pmc FETCH_SIZE / --pmc WRITE_SIZE (separate passes, --kernel-trace only) of `python bench.py --full --workload %s "
                 "--no-cpu-baseline --no-host-scopes --no-other-configs --fast-plans 2,3 --steps 3 --warmup 1` (scripts/gpu_step_traffic.sh).\n"
                 "# One row per kernel AND grid size; *_kb = per-dispatch average as reported; bytes = FETCH_SIZE x 2 x 1024 + WRITE_SIZE x 1024 "
                 "(gfx950: FETCH_SIZE under-counts wide reads by 2, MI355X_MICROARCH.md).\n" % wl)
         f.write("workload,kernel,grid_size,dispatches,fetch_size_kb_avg,write_size_kb_avg,bytes_per_dispatch\n")
         for (k, g), r in rows.items():
             f.write('%s,"%s",%d,%d,%.3f,%.3f,%d\n' % (wl, k, g, r["dispatches"], r["fetch_kb"], r["write_kb"], r["fetch_bytes"] + r["write_bytes"]))
-    out_path = os.path.join(ROOT, "gpurun_out", "step_traffic.json")
+    out_path = os.path.join(ROOT, "bench_out", "step_traffic.json")
     try:
         out = json.load(open(out_path))
     except Exception:
@@ -86,7 +86,7 @@ def collect(wl, dir_fetch, dir_write):
     if out.get("kernel_source_stamp") != stamp:
         out = {}
     out["kernel_source_stamp"] = stamp
-    out["source"] = ("rocprofv3 --pmc FETCH_SIZE / --pmc WRITE_SIZE passes (kernel trace only) of `python bench.py --workload <wl> --no-cpu-baseline "
+    out["source"] = ("rocprofv3 --pmc FETCH_SIZE / --pmc WRITE_SIZE passes (kernel trace only) of `python bench.py --full --workload <wl> --no-cpu-baseline "
                      "--no-host-scopes --no-other-configs --fast-plans 2,3 --steps 3 --warmup 1` (scripts/gpu_step_traffic.sh -> scripts/pmc_traffic.py): "
                      "per-dispatch averages per kernel AND grid size (profiles/*traffic_by_kernel_grid_<wl>.csv), summed over the dispatches of one "
                      "step of the plan; FETCH_SIZE x2 (gfx950 correction)")

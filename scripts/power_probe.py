@@ -26,7 +26,7 @@ except Exception as exc:
     print("PCI lookup failed:", exc)
 cap = rd((mine or hw[0]) + "/power1_cap")
 print("cap W:", cap and cap / 1e6, " job's GPU:", mine or "unknown (the busiest of %d is taken)" % len(hw))
-p = subprocess.Popen([sys.executable, "bench.py", "--no-cpu-baseline", "--no-host-scopes", "--steps", steps], stdout=open("gpurun_out/power_bench.json", "w"), stderr=subprocess.DEVNULL)
+p = subprocess.Popen([sys.executable, "bench.py", "--full", "--no-cpu-baseline", "--no-host-scopes", "--steps", steps], stdout=open("bench_out/power_bench.json", "w"), stderr=subprocess.DEVNULL)
 t0 = time.time()
 rows = []
 while p.poll() is None:

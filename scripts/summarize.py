@@ -1,5 +1,5 @@
 import json, sys, glob
-for f in sorted(glob.glob(sys.argv[1] if len(sys.argv) > 1 else "gpurun_out/v*.json")):
+for f in sorted(glob.glob(sys.argv[1] if len(sys.argv) > 1 else "bench_out/v*.json")):
     try:
         d = json.load(open(f))
         box = d["roofline"].get("box_mfma_tflops")

@@ -4,7 +4,6 @@ import os
 import numpy as np
 import pytest
 
-from conftest import REFERENCE, have_reference
 from tfckpt_writer import crc32c, mask, write_bundle
 
 HERE = os.path.dirname(os.path.abspath(__file__))
@@ -41,10 +40,9 @@ def test_crc32c(pkg):
         assert pkg.ethcnn.crc32c_masked(b) == mask(crc32c(b))
 
 
-@pytest.mark.skipif(not have_reference(), reason="needs /root/reference (build container only)")
 def test_real_lstm_data_crcs(pkg):
-    """The one real weight blob in the reference: every tensor's stored crc32c matches."""
-    prefix = os.path.join(REFERENCE, "HM-16.5_Test_LDP", "bin", "model_LDP_200000_qp32.dat")
+    """The one real weight blob in the reference (copied as a fixture): every tensor's stored crc32c matches."""
+    prefix = os.path.join(HERE, "golden", "model_LDP_200000_qp32.dat")
     data = open(prefix + ".data-00000-of-00001", "rb").read()
     ents = pkg.ethcnn.read_ckpt_index(prefix + ".index")
     assert len(ents) == 18 and sum(e[5] for e in ents) == len(data) == 3040312
@@ -52,12 +50,12 @@ def test_real_lstm_data_crcs(pkg):
         assert pkg.ethcnn.crc32c_masked(data[off:off + size]) == crc, name
 
 
-@pytest.mark.skipif(not have_reference(), reason="needs /root/reference (build container only)")
 def test_all_reference_indexes_share_the_layout(pkg, oracle):
+    """Every ETH-CNN checkpoint index the reference ships (the four HM AI models, the four training runs, the LDP CNN;
+    copied as fixtures with '~' spelled '_') holds the one tensor table."""
     import glob
-    paths = glob.glob(os.path.join(REFERENCE, "HM-16.5_Test_AI", "bin", "*.index")) + \
-        glob.glob(os.path.join(REFERENCE, "ETH-CNN_Training_AI", "Models", "*.index")) + \
-        [os.path.join(REFERENCE, "HM-16.5_Test_LDP", "bin", "model_LDP_2000000_qp22~37.dat.index")]
+    paths = sorted(glob.glob(os.path.join(HERE, "golden", "ckpt_index", "*.index")))
+    assert len(paths) == 9
     seen = 0
     for p in paths:
         if not os.path.exists(p):

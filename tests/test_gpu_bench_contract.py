@@ -2,8 +2,9 @@
 
   * `python bench.py --gpus 2` on a 1-GPU box must exit non-zero with a clear message -- never a line whose n_gpus is not what ran;
   * the N > 1 control flow (self-launch through torch.distributed.run, barriers, max-over-ranks, sharded host scopes, rank-0 JSON
-    with `roofline` + `cpu_baseline`) is exercised by two ranks sharing GPU 0 over gloo through the PLAIN command (test hooks
-    BENCH_FORCE_DEVICE / BENCH_DIST_BACKEND; RCCL refuses two ranks on one device).  The numbers of that run mean nothing."""
+    with `roofline` + `cpu_baseline` under --full) is exercised by two ranks sharing GPU 0 over gloo through the command itself, not torchrun (test hooks
+    BENCH_FORCE_DEVICE / BENCH_DIST_BACKEND; RCCL refuses two ranks on one device).  The numbers of that run mean nothing;
+  * a plain run (no --full) prints the headline line only, and --dump-outputs writes what its last timed step computed."""
 import json
 import os
 import subprocess
@@ -39,7 +40,7 @@ def test_world_size_mismatch_is_refused():
 
 def test_two_ranks_through_the_plain_command():
     r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "2", "--workload", "c2", "--steps", "3", "--warmup", "1",
-                        "--ramp-ms", "20", "--cpu-seconds", "2"], capture_output=True, text=True,
+                        "--ramp-ms", "20", "--cpu-seconds", "2", "--full"], capture_output=True, text=True,
                        env=_env(BENCH_FORCE_DEVICE="0", BENCH_DIST_BACKEND="gloo"), timeout=900, cwd=ROOT)
     assert r.returncode == 0, r.stderr[-2000:]
     lines = [l for l in r.stdout.splitlines() if l.startswith("{")]
@@ -74,12 +75,12 @@ def test_box_calibration_is_a_plausible_mfma_rate(pkg):
 
 
 def test_one_gpu_line_states_the_north_star_ratio_and_the_fast_plans():
-    """The default (N = 1) line on a short C2 run: contract keys, `roofline` + `cpu_baseline`, the north star's ratio
+    """The --full (N = 1) line on a short C2 run: contract keys, `roofline` + `cpu_baseline`, the north star's ratio
     (`vs_baseline` = S3 GPU / S3 oracle port, `vs_tf_cpu_proxy`, `north_star_10x`, each naming scope / cores / kind "port"),
     and the two opt-in plans reported BESIDE the exact headline (`fast_plan_fp16x2`, `fast_plan_fp16x2_trunk`) -- the headline
     itself stays dtype f32 and bit-exact."""
     r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--workload", "c2", "--steps", "4", "--warmup", "1", "--ramp-ms", "20",
-                        "--cpu-seconds", "3"], capture_output=True, text=True, env=_env(), timeout=900, cwd=ROOT)
+                        "--cpu-seconds", "3", "--full"], capture_output=True, text=True, env=_env(), timeout=900, cwd=ROOT)
     assert r.returncode == 0, r.stderr[-2000:]
     lines = [l for l in r.stdout.splitlines() if l.startswith("{")]
     assert len(lines) == 1
@@ -127,3 +128,46 @@ def test_one_gpu_line_states_the_north_star_ratio_and_the_fast_plans():
     h2h = d["single_picture_latency"]["host_to_host"]
     for name in ("1920x1080", "3840x2160"):
         assert 20.0 < h2h[name]["page_locked"] < 2000.0 and 20.0 < h2h[name]["pageable"] < 4000.0, h2h
+
+
+def _plain(tmp_path, tag, *args):
+    out = tmp_path / tag
+    r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "1", "--ramp-ms", "20", "--dump-outputs", str(out)] + list(args),
+                       capture_output=True, text=True, env=_env(), timeout=600, cwd=ROOT)
+    assert r.returncode == 0, r.stderr[-2000:]
+    lines = [l for l in r.stdout.splitlines() if l.startswith("{")]
+    assert len(lines) == 1, r.stdout[-2000:]
+    return json.loads(lines[0]), out
+
+
+def test_plain_line_is_the_headline_and_dumps_the_last_step(tmp_path, oracle):
+    """No --full: the contract keys and nothing measured beside them; --steps sets the timed steps; the dumped probabilities
+    are the whole last step (every CTU of the 50 frames), and its first frame is bit-exact vs the oracle"""
+    d, out = _plain(tmp_path, "c2", "--workload", "c2", "--steps", "3", "--warmup", "1")
+    for k in ("metric", "value", "unit", "higher_is_better", "dtype", "ms_per_step", "n_gpus", "steps", "config"):
+        assert k in d, k
+    assert d["steps"] == 3 and d["dtype"] == "f32" and d["higher_is_better"] is True and d["unit"] == "CTU/s"
+    assert abs(d["value"] - d["config"]["ctus_per_step_per_gpu"] / (d["ms_per_step"] * 1e-3)) < 1e-6 * d["value"]
+    for k in ("roofline", "cpu_baseline", "host_scopes", "other_configs", "fast_plan_fp16x2", "stages_ms_per_step"):
+        assert k not in d, k
+    assert sorted(os.listdir(out)) == ["probabilities.npy"]
+    import numpy as np
+    import bench
+    got = np.load(out / "probabilities.npy")
+    w, h = 1920, 1080
+    nctu = ((w + 63) // 64) * ((h + 63) // 64)
+    assert got.dtype == np.float32 and got.shape == (nctu * 50, 21)
+    luma = bench.synth_luma(w, h, 1, seed=0xE7C00000 + 2)
+    want = oracle.predict_frames(oracle.synth_blob(1, 8.0), luma, w, h, 1, 32, 0.5, 0.5, mode=0)
+    assert np.array_equal(got[:nctu].view(np.uint32), want.view(np.uint32))
+
+
+def test_dumped_ldp_step_repeats_run_to_run(tmp_path):
+    """The LDP step (recurrent state in HBM) walks the same frames in every run: two runs with the same arguments dump the
+    same probabilities and the same state"""
+    import numpy as np
+    runs = [_plain(tmp_path, "run%d" % i, "--workload", "c5", "--steps", "20", "--warmup", "5")[1] for i in range(2)]
+    for name, shape in (("probabilities", (510, 21)), ("lstm_state", (510, 896))):
+        a, b = (np.load(r / (name + ".npy")) for r in runs)
+        assert a.shape == shape and a.dtype == np.float32
+        assert np.array_equal(a.view(np.uint32), b.view(np.uint32)), name

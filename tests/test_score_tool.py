@@ -1,14 +1,12 @@
 """CPU: tools/score_cu_depth.py (label / accuracy tooling): the vectorized score equals a
 literal per-sample restatement of the reference's get_class_matrices (train_CNN_CTU64.py:103-137), and the
-label reader accepts the reference's own AI_Info files when they are present."""
+label reader accepts the reference's own AI_Info files (tests/golden/ai_info)."""
 import glob
 import importlib.util
 import os
 
 import numpy as np
-import pytest
 
-from conftest import have_reference
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 spec = importlib.util.spec_from_file_location("score_cu_depth", os.path.join(ROOT, "tools", "score_cu_depth.py"))
@@ -63,9 +61,9 @@ def test_label_layout_round_trip(tmp_path):
     assert np.array_equal(per_ctu[1 * 6 + 2 * 2 + 1].reshape(4, 4), lab[1, 8:12, 4:8])
 
 
-@pytest.mark.skipif(not have_reference(), reason="needs /root/reference/AI_Info")
 def test_reads_the_reference_label_files():
-    files = sorted(glob.glob("/root/reference/AI_Info/*_768x512_*_CUDepth.dat"))
+    """the reference's own AI_Info label files of the 768x512 sequence (QP 22 / 27 / 32 / 37, copied as fixtures)"""
+    files = sorted(glob.glob(os.path.join(os.path.dirname(os.path.abspath(__file__)), "golden", "ai_info", "*_768x512_*_CUDepth.dat")))
     assert files
     for f in files[:4]:
         lab = sc.read_labels(f, 768, 512)
