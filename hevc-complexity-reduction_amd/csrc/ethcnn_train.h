@@ -1,0 +1,86 @@
+// ethcnn_train.h -- shared between the training kernels (ethcnn_train_kernels.hip) and their host side (ethcnn_train.cpp).
+//
+// One training step of ETH-CNN (All-Intra; ETH-CNN_Training_AI/net_CTU64.py:94-196) at batch B is 8 launches on the
+// context's stream, in this order:
+//   1 k_train_trunk_fwd   one block per sample: draw / read the sample index and QP, 4096 luma bytes -> the three pooled, mean-removed
+//                         branch images, conv1..3 + leaky-ReLU; keeps images and conv1 outputs (per-sample trunk record) and writes the
+//                         2688 features (+ a ones column) = F_aug [B][2689]
+//   2 k_train_gemm        FC1 forward: F [B,2688] x W1 [2688,448] (the three heads' tensors as three group members), MFMA 32x32x2 f32
+//   3 k_train_heads_fwd   one block per sample: FC1 bias + leaky + dropout, FC2 / FC3 of the three heads, sigmoid
+//   4 k_train_loss        one block: the batch-global label counts, the loss / accuracy lists, dL/dlogit per sample
+//   5 k_train_heads_bwd   one block per sample: dlogit -> dZ2 -> dZ1 (through the dropout masks and the leaky-ReLUs)
+//   6 k_train_gemm        one grouped launch: dF = dZ1 x W1^T (K split over the three heads' tensors) and the nine FC weight / bias
+//                         gradients X_aug^T x dZ (bias = the ones row), written in blob layout
+//   7 k_train_trunk_bwd   one block per sample: dF -> the 18 conv tensors' per-sample gradient partials
+//   8 k_train_update      every parameter: conv gradients summed over the batch in sample order, then the momentum update
+// Determinism: no atomics; every sum has one owner thread and a fixed order (MFMA chains run k in order), so the same inputs give the
+// same bits on every run.
+#pragma once
+#include <cstdint>
+
+namespace ethcnn {
+namespace train {
+
+constexpr int kRec = 4992;        // bytes per training record (input_data.py:16): 4096 luma, 64 pad, 52 x 16 label bytes
+constexpr int kLabelBase = 4160;  // label row of QP q at kLabelBase + 16 q (input_data.py:104)
+constexpr int kTF = 2688, kLdF = 2689, kTV = 448, kT2 = 336, kTOut = 21;
+constexpr int kConvFloats = 14808;  // the 18 conv tensors lie at blob floats [0, 14808) (sorted keys "Variable*")
+constexpr int kTrunkRec = 10752;    // per-sample trunk record: images S 4096 | M 1024 | L 256, conv1 S 4096 | M 1024 | L 256
+constexpr int kMaxGemm = 12;
+
+// counter-based RNG (documented in include/ethcnn.h, regenerated in numpy by the tests)
+__host__ __device__ inline uint64_t mix64(uint64_t z) {
+    z += 0x9E3779B97F4A7C15ull;
+    z = (z ^ (z >> 30)) * 0xBF58476D1CE4E5B9ull;
+    z = (z ^ (z >> 27)) * 0x94D049BB133111EBull;
+    return z ^ (z >> 31);
+}
+__host__ __device__ inline uint64_t draw(uint64_t seed, uint64_t stream, uint64_t step, uint64_t slot, uint64_t unit) {
+    return mix64(mix64(mix64(seed ^ (stream * 0xD1B54A32D192ED03ull)) ^ step) ^ ((slot << 12) | unit));
+}
+enum { kStreamIndex = 1, kStreamQp = 2, kStreamDropout = 3 };
+
+// C[m][n] = sum_k A(m,k) B(k,n); A(m,k) = A[m sam + k sak]; B(k,n) = Bs[s][(k - kseg[s]) sbk[s] + n sbn[s]] for the last segment s with
+// kseg[s] <= k (segment starts are multiples of 32); rows m < msplit go to C[m ldc + n], rows m >= msplit to C2[(m - msplit) ldc + n].
+struct GemmDesc {
+    int M, N, K, nseg;
+    const float* A;
+    long sam, sak;
+    const float* B[3];
+    long sbk[3], sbn[3];
+    int kseg[3];
+    float* C;
+    float* C2;
+    long ldc;
+    int msplit, tiles_n, tile_begin;
+};
+struct GemmGroup {
+    GemmDesc d[kMaxGemm];
+    int n, tiles;
+};
+
+// blob float offsets of the tensors the kernels touch (from kTensors, filled on the host)
+struct NetOffsets {
+    int convw[3][3], convb[3][3];  // [branch S, M, L][layer 1..3]
+    int w1[3], b1[3], w2[3], b2[3], w3[3], b3[3];  // heads 64, 32, 16
+};
+
+struct StepArgs {
+    const uint8_t* data;  // records
+    long nrec;
+    const int32_t* idx_in;  // explicit indices (NULL: drawn)
+    const int32_t* qp_in;   // explicit QPs (NULL: drawn from qps)
+    int qps[52];
+    int nqps;
+    int qp_fixed;  // >= 0: every sample at this QP (evaluation)
+    uint64_t seed, step;
+    int dropout;
+    int32_t* idx_out;
+    int32_t* qp_out;
+    float* labels;  // [B][16] depths
+    float* trunk;   // [B][kTrunkRec]
+    float* F;       // [B][kLdF]
+};
+
+}  // namespace train
+}  // namespace ethcnn

@@ -9,7 +9,8 @@
 //        key ""  -> BundleHeaderProto ; other keys -> BundleEntryProto
 //   <prefix>.data-00000-of-00001   raw little-endian tensors back to back
 //
-// TensorFlow is not a dependency: the table and the two protobuf messages are decoded here.
+// TensorFlow is not a dependency: the table and the two protobuf messages are decoded here, and written by
+// ckpt_write_blob (the trainer's checkpoints, in the same format).
 #include <cstdio>
 #include <cstring>
 #include <string>
@@ -266,6 +267,106 @@ int ckpt_load_table(const char* prefix, const TensorDesc* table, int ntensors, f
     return 0;
 }
 
+// ------------------------------------------------------------------------ writer ----
+// BundleWriter's layout: one data block (header entry "" + the 36 sorted keys, restart interval 16, shared key prefixes), an empty
+// metaindex block, an index block with one handle, the 48-byte footer.  The .data file is the blob itself (kTensors' offsets are
+// its tensors back to back); both files are written to a temp name and renamed.
+static void put_varint(std::string& o, uint64_t v) {
+    while (v >= 0x80) { o.push_back((char)(uint8_t)(v | 0x80)); v >>= 7; }
+    o.push_back((char)(uint8_t)v);
+}
+static void put_fixed32(std::string& o, uint32_t v) { o.append((const char*)&v, 4); }
+
+static std::string table_block(const std::vector<std::pair<std::string, std::string>>& entries) {
+    std::string out, prev;
+    std::vector<uint32_t> restarts;
+    for (size_t i = 0; i < entries.size(); ++i) {
+        const std::string& k = entries[i].first;
+        size_t shared = 0;
+        if (i % 16 == 0) restarts.push_back((uint32_t)out.size());
+        else
+            while (shared < k.size() && shared < prev.size() && k[shared] == prev[shared]) ++shared;
+        put_varint(out, shared);
+        put_varint(out, k.size() - shared);
+        put_varint(out, entries[i].second.size());
+        out.append(k, shared, std::string::npos);
+        out += entries[i].second;
+        prev = k;
+    }
+    if (restarts.empty()) restarts.push_back(0);
+    for (uint32_t r : restarts) put_fixed32(out, r);
+    put_fixed32(out, (uint32_t)restarts.size());
+    return out;
+}
+// block + trailer (type 0 = uncompressed, masked crc32c over block + type); returns the block's handle
+static void append_block(std::string& file, const std::string& blk, uint64_t& off, uint64_t& size) {
+    off = file.size();
+    size = blk.size();
+    file += blk;
+    file.push_back('\0');
+    put_fixed32(file, crc32c_mask(crc32c(file.data() + off, blk.size() + 1)));
+}
+
+static bool write_replace(const std::string& path, const void* data, size_t n, std::string& why) {
+    const std::string tmp = path + ".tmp";
+    FILE* f = std::fopen(tmp.c_str(), "wb");
+    if (!f) { why = "cannot create " + tmp; return false; }
+    const bool ok = (n == 0 || std::fwrite(data, 1, n, f) == n) && std::fflush(f) == 0;
+    if (std::fclose(f) != 0 || !ok) { std::remove(tmp.c_str()); why = "cannot write " + tmp; return false; }
+    if (std::rename(tmp.c_str(), path.c_str()) != 0) { std::remove(tmp.c_str()); why = "cannot rename " + tmp; return false; }
+    return true;
+}
+
+int ckpt_write_blob(const char* prefix, const float* blob, char* err, size_t errcap) {
+    std::vector<std::pair<std::string, std::string>> entries;
+    entries.emplace_back(std::string(), std::string("\x08\x01\x1a\x02\x08\x01", 6));  // BundleHeaderProto{num_shards 1, version{producer 1}}
+    for (int t = 0; t < kNumTensors; ++t) {
+        const TensorDesc& d = kTensors[t];
+        std::string shape;
+        for (int i = 0; i < d.rank; ++i) {
+            std::string dim;
+            dim.push_back('\x08');
+            put_varint(dim, (uint64_t)d.shape[i]);
+            shape.push_back('\x12');
+            put_varint(shape, dim.size());
+            shape += dim;
+        }
+        const size_t nbytes = d.count() * 4;
+        std::string v("\x08\x01", 2);  // dtype DT_FLOAT
+        v.push_back('\x12');
+        put_varint(v, shape.size());
+        v += shape;
+        if (d.offset_bytes) { v.push_back('\x20'); put_varint(v, d.offset_bytes); }
+        v.push_back('\x28');
+        put_varint(v, nbytes);
+        v.push_back('\x35');
+        put_fixed32(v, crc32c_mask(crc32c((const uint8_t*)blob + d.offset_bytes, nbytes)));
+        entries.emplace_back(d.name, v);
+    }
+    std::string file;
+    uint64_t doff, dsize, moff, msize, ioff, isize;
+    append_block(file, table_block(entries), doff, dsize);
+    append_block(file, table_block({}), moff, msize);
+    std::string handle;
+    put_varint(handle, doff);
+    put_varint(handle, dsize);
+    append_block(file, table_block({{std::string(kTensors[kNumTensors - 1].name) + "\xff", handle}}), ioff, isize);
+    std::string footer;
+    put_varint(footer, moff);
+    put_varint(footer, msize);
+    put_varint(footer, ioff);
+    put_varint(footer, isize);
+    footer.resize(40, '\0');
+    const uint64_t magic = 0xdb4775248b80fb57ull;
+    footer.append((const char*)&magic, 8);
+    file += footer;
+    std::string why;
+    const std::string p(prefix);
+    if (!write_replace(p + ".data-00000-of-00001", blob, kBlobFloats * 4, why) || !write_replace(p + ".index", file.data(), file.size(), why))
+        return fail(err, errcap, ETHCNN_ERR_IO, why);
+    return 0;
+}
+
 }  // namespace ethcnn
 
 extern "C" int ethcnn_ckpt_read_index(const char* index_path, ethcnn_ckpt_entry* entries, int cap, int* n_out,
@@ -282,4 +383,8 @@ extern "C" int ethcnn_ckpt_read_blob(const char* prefix, float* blob_out, size_t
 extern "C" int ethcnn_ckpt_read_lstm_blob(const char* prefix, float* blob_out, size_t nfloats, char* err, size_t errcap) {
     if (!prefix || !blob_out || nfloats != ethcnn::kLstmBlobFloats) return ETHCNN_ERR_ARG;
     return ethcnn::ckpt_load_table(prefix, ethcnn::kLstmTensors, ethcnn::kNumLstmTensors, blob_out, err, errcap);
+}
+extern "C" int ethcnn_ckpt_write_blob(const char* prefix, const float* blob, size_t nfloats, char* err, size_t errcap) {
+    if (!prefix || !*prefix || !blob || nfloats != ethcnn::kBlobFloats) return ETHCNN_ERR_ARG;
+    return ethcnn::ckpt_write_blob(prefix, blob, err, errcap);
 }

@@ -6,6 +6,7 @@ is usable, construction raises.
 """
 import ctypes
 import os
+import weakref
 
 import numpy as np
 
@@ -125,6 +126,20 @@ SIGNATURES = {
     "ethcnn_crc32c_masked": (ctypes.c_uint32, [_vp, _sz]),
     "ethcnn_host_thread_budget": (_i, [_i, _i]),
     "ethcnn_host_threads": (_i, [_vp]),
+    "ethcnn_ckpt_write_blob": (_i, [_cp, _fp, _sz, ctypes.c_char_p, _sz]),
+    "ethcnn_train_create": (_i, [_vp, ctypes.c_void_p, ctypes.POINTER(_vp)]),
+    "ethcnn_train_destroy": (None, [_vp]),
+    "ethcnn_train_init_weights": (_i, [_vp, ctypes.c_uint64]),
+    "ethcnn_train_set_blob": (_i, [_vp, _fp, _fp, _sz]),
+    "ethcnn_train_get_blob": (_i, [_vp, _fp, _fp, _sz]),
+    "ethcnn_train_set_samples": (_i, [_vp, _i, _vp, _sz]),
+    "ethcnn_train_set_qps": (_i, [_vp, ctypes.POINTER(ctypes.c_int), _i]),
+    "ethcnn_train_run": (_i, [_vp, ctypes.c_int64, ctypes.c_int64]),
+    "ethcnn_train_last_stats": (_i, [_vp, _fp, _fp]),
+    "ethcnn_train_step_indices": (_i, [_vp, ctypes.c_int64, ctypes.POINTER(ctypes.c_int32), ctypes.POINTER(ctypes.c_int), _i, _fp, _fp]),
+    "ethcnn_train_evaluate": (_i, [_vp, _i, ctypes.POINTER(ctypes.c_int32), ctypes.c_int64, _i, _fp, _fp, _fp]),
+    "ethcnn_train_debug_fetch": (_i, [_vp, _i, _fp, _sz]),
+    "ethcnn_train_last_error": (_cp, [_vp]),
 }
 
 _lib = None
@@ -196,6 +211,15 @@ def read_ckpt_lstm_blob(prefix):
     return out
 
 
+def write_ckpt_blob(prefix, blob):
+    """float32[BLOB_FLOATS] -> <prefix>.index + <prefix>.data-00000-of-00001 (TF-V2 bundle, host only)"""
+    blob = np.ascontiguousarray(blob, dtype=np.float32)
+    err = ctypes.create_string_buffer(400)
+    rc = load_library().ethcnn_ckpt_write_blob(os.fsencode(prefix), blob.ctypes.data_as(_fp), blob.size, err, 400)
+    if rc:
+        raise EthCnnError(rc, err.value.decode("utf-8", "replace") or "ethcnn_ckpt_write_blob: bad arguments")
+
+
 def read_ckpt_blob(prefix):
     """TF-V2 bundle -> float32[BLOB_FLOATS] in checkpoint layout (crc32c-checked, host only)."""
     out = np.empty(BLOB_FLOATS, dtype=np.float32)
@@ -265,6 +289,8 @@ class EthCnn(object):
 
     def close(self):
         if getattr(self, "h", None):
+            for t in list(getattr(self, "_trainers", ())):  # a trainer lives on this context: it goes first
+                t.close()
             self.free_host_buffers()
             self.lib.ethcnn_destroy(self.h)
             self.h = None
@@ -586,4 +612,119 @@ class EthCnn(object):
     def debug_fetch(self, which, n):
         out = np.empty((n, _DBG_WIDTH[which]), dtype=np.float32)
         self._chk(self.lib.ethcnn_debug_fetch(self.h, which, out.ctypes.data_as(_fp), out.size))
+        return out
+
+
+# ---------------------------------------------------------------------------------------------------------------- training ---
+TRAIN_REC = 4992  # bytes per training-sample record (4096 luma, 64 pad, 52 x 16 label bytes)
+SET_TRAIN, SET_VALID = 0, 1
+TDBG_GRADS, TDBG_MASK_FC1, TDBG_MASK_FC2, TDBG_PROBS, TDBG_INDICES, TDBG_ACCUM = range(6)
+
+
+class TrainOptions(ctypes.Structure):
+    _fields_ = [("batch", ctypes.c_int), ("lr_init", ctypes.c_float), ("momentum", ctypes.c_float), ("decay_rate", ctypes.c_float),
+                ("decay_steps", ctypes.c_int64), ("dropout", ctypes.c_int), ("seed", ctypes.c_uint64), ("reserved", ctypes.c_int * 8)]
+
+
+class Trainer(object):
+    """ETH-CNN (All-Intra) training on the GPU of an EthCnn context (include/ethcnn.h "training").  Defaults are the reference's
+    (train_CNN_CTU64.py:36-47): batch 64, lr 0.01 decayed by 0.3163 every 250000 steps, momentum 0.9, dropout on."""
+
+    def __init__(self, ctx, batch=64, lr=0.01, momentum=0.9, decay_rate=0.3163, decay_steps=250000, dropout=True, seed=0):
+        self.ctx, self.lib, self.batch = ctx, ctx.lib, int(batch)
+        o = TrainOptions(int(batch), float(lr), float(momentum), float(decay_rate), int(decay_steps), 1 if dropout else 0,
+                         int(seed) & (2 ** 64 - 1))
+        h = ctypes.c_void_p()
+        rc = self.lib.ethcnn_train_create(ctx.h, ctypes.byref(o), ctypes.byref(h))
+        if rc:
+            raise EthCnnError(rc, self.lib.ethcnn_last_error(ctx.h).decode())
+        self.h = h
+        if not hasattr(ctx, "_trainers"):
+            ctx._trainers = weakref.WeakSet()
+        ctx._trainers.add(self)
+
+    def _chk(self, rc):
+        if rc:
+            raise EthCnnError(rc, self.lib.ethcnn_train_last_error(self.h).decode())
+
+    def close(self):
+        if getattr(self, "h", None):
+            self.lib.ethcnn_train_destroy(self.h)
+            self.h = None
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+    def __enter__(self):
+        return self
+
+    def __exit__(self, *a):
+        self.close()
+
+    def init_weights(self, seed):
+        self._chk(self.lib.ethcnn_train_init_weights(self.h, int(seed) & (2 ** 64 - 1)))
+
+    def set_blob(self, blob, accum=None):
+        blob = np.ascontiguousarray(blob, dtype=np.float32)
+        acc = None if accum is None else np.ascontiguousarray(accum, dtype=np.float32)
+        if acc is not None and acc.size != blob.size:
+            raise ValueError("accumulators and blob differ in size")
+        self._chk(self.lib.ethcnn_train_set_blob(self.h, blob.ctypes.data_as(_fp), None if acc is None else acc.ctypes.data_as(_fp),
+                                                 blob.size))
+
+    def get_blob(self, with_accum=False):
+        blob = np.empty(BLOB_FLOATS, dtype=np.float32)
+        acc = np.empty(BLOB_FLOATS, dtype=np.float32) if with_accum else None
+        self._chk(self.lib.ethcnn_train_get_blob(self.h, blob.ctypes.data_as(_fp), None if acc is None else acc.ctypes.data_as(_fp),
+                                                 BLOB_FLOATS))
+        return (blob, acc) if with_accum else blob
+
+    def set_samples(self, which, records):
+        """records: bytes / uint8 array of whole 4992-byte records (one sample file of the reference's Extract_Data)"""
+        buf = np.frombuffer(records, dtype=np.uint8) if isinstance(records, (bytes, bytearray)) else np.ascontiguousarray(records, np.uint8)
+        self._chk(self.lib.ethcnn_train_set_samples(self.h, int(which), buf.ctypes.data if buf.size else None, buf.size))
+
+    def set_qps(self, qps):
+        arr = (ctypes.c_int * len(qps))(*[int(q) for q in qps])
+        self._chk(self.lib.ethcnn_train_set_qps(self.h, arr, len(qps)))
+
+    def run(self, first_step, nsteps):
+        """enqueue steps first_step .. first_step + nsteps - 1 (device-drawn batches); returns at once"""
+        self._chk(self.lib.ethcnn_train_run(self.h, int(first_step), int(nsteps)))
+
+    def last_stats(self):
+        """(loss_list, accuracy_list) of the last step enqueued (waits for it)"""
+        l3, a3 = np.zeros(3, np.float32), np.zeros(3, np.float32)
+        self._chk(self.lib.ethcnn_train_last_stats(self.h, l3.ctypes.data_as(_fp), a3.ctypes.data_as(_fp)))
+        return l3, a3
+
+    def step_indices(self, step, idx, qps):
+        idx = np.ascontiguousarray(idx, dtype=np.int32)
+        qps = np.ascontiguousarray(np.broadcast_to(np.asarray(qps, dtype=np.int32), idx.shape))
+        l3, a3 = np.zeros(3, np.float32), np.zeros(3, np.float32)
+        self._chk(self.lib.ethcnn_train_step_indices(self.h, int(step), idx.ctypes.data_as(ctypes.POINTER(ctypes.c_int32)),
+                                                     qps.ctypes.data_as(ctypes.POINTER(ctypes.c_int)), idx.size,
+                                                     l3.ctypes.data_as(_fp), a3.ctypes.data_as(_fp)))
+        return l3, a3
+
+    def evaluate(self, which, qp, idx=None, n=None, want_probs=False):
+        """(loss_list, accuracy_list[, probs [n,21]]) of ONE forward batch over the samples idx (or 0 .. n-1)"""
+        if idx is not None:
+            idx = np.ascontiguousarray(idx, dtype=np.int32)
+            n = idx.size
+        probs = np.empty((int(n), NOUT), dtype=np.float32) if want_probs else None
+        l3, a3 = np.zeros(3, np.float32), np.zeros(3, np.float32)
+        self._chk(self.lib.ethcnn_train_evaluate(self.h, int(which), None if idx is None else idx.ctypes.data_as(ctypes.POINTER(ctypes.c_int32)),
+                                                 int(n), int(qp), l3.ctypes.data_as(_fp), a3.ctypes.data_as(_fp),
+                                                 None if probs is None else probs.ctypes.data_as(_fp)))
+        return (l3, a3, probs) if want_probs else (l3, a3)
+
+    def debug_fetch(self, which):
+        n = {TDBG_GRADS: BLOB_FLOATS, TDBG_ACCUM: BLOB_FLOATS, TDBG_MASK_FC1: self.batch * NVEC, TDBG_MASK_FC2: self.batch * NFC2,
+             TDBG_PROBS: self.batch * NOUT, TDBG_INDICES: self.batch * 2}[which]
+        out = np.empty(n, dtype=np.float32)
+        self._chk(self.lib.ethcnn_train_debug_fetch(self.h, int(which), out.ctypes.data_as(_fp), n))
         return out

@@ -1,0 +1,167 @@
+"""Train ETH-CNN (All-Intra) on the GPU: the driver of ETH-CNN_Training_AI/train_CNN_CTU64.py:316-399, with
+command-line flags in place of its module constants.  Every step runs in the library's training kernels (Trainer,
+include/ethcnn.h "training"); this file only schedules, evaluates, logs and saves.
+
+    python train_CNN_CTU64.py --train AI_Train_2446725.dat_shuffled --valid AI_Valid_143925.dat_shuffled --model-type 3
+    python train_CNN_CTU64.py ... --iters 1000000 --export-ai .   # also writes model_2000000_qp30~35.dat for video_to_cu_depth.py
+
+Sample files: the reference's Extract_Data output (4992-byte records), uploaded once into HBM.  Like the reference it evaluates
+every 1000 steps on 5000 random samples of each set (no dropout), appends to Models/loss_accuracy_list.dat (first line: total
+iterations, then 19 columns per evaluation, CRLF), saves Models/model_<time>_<step>_<name>.dat every 50000 steps and
+Models/model.dat at the end.  --reload resumes from Models/model.dat and that log.  Resume choice: the reference's Saver keeps only
+the 36 trainable variables (train_CNN_CTU64.py:293), so its momentum accumulators restart at zero on reload; this driver does the
+same (the library can resume them exactly, ethcnn_train_set_blob with accumulators, but the checkpoint format has no place for them).
+Plotting is not ported.
+"""
+import argparse
+import importlib
+import math
+import os
+import sys
+import time
+
+import numpy as np
+
+_HERE = os.path.dirname(os.path.abspath(__file__))
+_ROOT = os.path.dirname(_HERE)
+if _ROOT not in sys.path:
+    sys.path.insert(0, _ROOT)
+sys.path.insert(0, os.path.join(_ROOT, "tools"))
+
+REC = 4992
+# input_data.py:39-55: MODEL_TYPE -> (MODEL_NAME, SELECT_QP_LIST)
+MODEL_TYPES = {1: ("qp22", [22]), 2: ("qp27", [27]), 3: ("qp32", [32]), 4: ("qp37", [37])}
+ITER_TIMES_PER_EVALUATE, ITER_TIMES_PER_SAVE, ITER_TIMES_PER_PRINT = 1000, 50000, 100
+NUM_EVAL = 5000
+
+
+def get_time_str():
+    return time.strftime("%Y%m%d_%H%M%S", time.localtime(time.time()))
+
+
+def get_tendency_2x2(m):  # train_CNN_CTU64.py:140-148
+    if m[0][1] == 0 and m[1][0] == 0:
+        return 0
+    elif m[0][1] == 0 or m[1][1] == 0:
+        return -100
+    elif m[1][0] == 0 or m[0][0] == 0:
+        return 100
+    return -math.log10((m[0][0] / m[0][1]) / (m[1][1] / m[1][0]))
+
+
+def load_records(path):
+    data = np.memmap(path, dtype=np.uint8, mode="r")
+    if data.size == 0 or data.size % REC:
+        raise SystemExit("%s: %d bytes is not a whole number of %d-byte samples" % (path, data.size, REC))
+    return data
+
+
+def parse_args(argv):
+    ap = argparse.ArgumentParser(description=__doc__.split("\n\n")[0])
+    ap.add_argument("--train", required=True, help="training sample file (4992-byte records)")
+    ap.add_argument("--valid", required=True, help="validation sample file")
+    g = ap.add_mutually_exclusive_group()
+    g.add_argument("--model-type", type=int, choices=sorted(MODEL_TYPES), default=1)
+    g.add_argument("--qp", type=int, help="train one QP (model name qp<QP>)")
+    ap.add_argument("--iters", type=int, default=1000000)
+    ap.add_argument("--batch", type=int, default=64)
+    ap.add_argument("--lr", type=float, default=0.01)
+    ap.add_argument("--decay-steps", type=int, default=250000)
+    ap.add_argument("--decay-rate", type=float, default=0.3163)
+    ap.add_argument("--momentum", type=float, default=0.9)
+    ap.add_argument("--seed", type=int, default=0, help="batches, dropout masks and the initial weights")
+    ap.add_argument("--no-dropout", action="store_true")
+    ap.add_argument("--reload", action="store_true", help="resume from <models>/model.dat and its loss_accuracy_list.dat")
+    ap.add_argument("--models", default="Models")
+    ap.add_argument("--export-ai", metavar="DIR", help="also write the final weights as video_to_cu_depth.py's model file in DIR")
+    ap.add_argument("--device", type=int, default=0)
+    return ap.parse_args(argv)
+
+
+def main(argv=None):
+    a = parse_args(argv)
+    pkg = importlib.import_module("hevc-complexity-reduction_amd")
+    import score_cu_depth
+    if a.qp is not None:
+        if not 0 <= a.qp <= 51:
+            raise SystemExit("--qp must be in 0..51")
+        name, qps = "qp%d" % a.qp, [a.qp]
+    else:
+        name, qps = MODEL_TYPES[a.model_type]
+    train, valid = load_records(a.train), load_records(a.valid)
+    ntrain, nvalid = train.size // REC, valid.size // REC
+    os.makedirs(a.models, exist_ok=True)
+    ctx = pkg.EthCnn(device=a.device)
+    tr = pkg.Trainer(ctx, batch=a.batch, lr=a.lr, momentum=a.momentum, decay_rate=a.decay_rate, decay_steps=a.decay_steps,
+                     dropout=not a.no_dropout, seed=a.seed)
+    tr.set_samples(pkg.ethcnn.SET_TRAIN, train)
+    tr.set_samples(pkg.ethcnn.SET_VALID, valid)
+    tr.set_qps(qps)
+    log = os.path.join(a.models, "loss_accuracy_list.dat")
+    rows = []
+    if a.reload:
+        tr.set_blob(pkg.ethcnn.read_ckpt_blob(os.path.join(a.models, "model.dat")))  # accumulators: zeros, as the reference's restore
+        with open(log) as f:
+            iter_times_last = int(f.readline())
+            rows = [ln.rstrip("\r\n") for ln in f if ln.strip()]
+    else:
+        tr.init_weights(a.seed)
+        iter_times_last = 0
+    print("iter_times_last = %d" % iter_times_last)
+    eval_rng = np.random.default_rng(a.seed + iter_times_last + 1)
+
+    def labels_of(data, idx):
+        recs = np.asarray(data).reshape(-1, REC)
+        return recs[idx, 4160 + 16 * qps[0]: 4176 + 16 * qps[0]]
+
+    def evaluate_loss_accuracy(step, lr):  # train_CNN_CTU64.py:213-250
+        out = []
+        for which, data, n in ((pkg.ethcnn.SET_TRAIN, train, ntrain), (pkg.ethcnn.SET_VALID, valid, nvalid)):
+            idx = eval_rng.integers(0, n, min(NUM_EVAL, n))
+            l3, a3, probs = tr.evaluate(which, qps[0], idx=idx, want_probs=True)
+            ms = score_cu_depth.class_matrices(labels_of(data, idx), probs)
+            out.append((l3, a3, [get_tendency_2x2(m) for m in ms]))
+        (tl, ta, tt), (vl, va, vt) = out
+        print("%s step %d: loss=[[%.3f %.3f %.3f] [%.3f %.3f %.3f]], accu=[[%.3f %.3f %.3f] [%.3f %.3f %.3f]], lr=%g"
+              % ((get_time_str(), step) + tuple(tl) + tuple(vl) + tuple(ta) + tuple(va) + (lr,)))
+        print("tendency = [[%.3f, %.3f, %.3f] [%.3f, %.3f, %.3f]]" % (tuple(tt) + tuple(vt)))
+        rows.append("%d  " % step + "  ".join("%g" % v for v in list(tl) + list(vl) + list(ta) + list(va) + list(tt) + list(vt)))
+
+    def lr_at(step):
+        return a.lr * a.decay_rate ** (step // a.decay_steps)
+
+    if not a.reload:
+        evaluate_loss_accuracy(iter_times_last, a.lr)
+    step = iter_times_last
+    end = iter_times_last + a.iters
+    while step < end:
+        # enqueue up to the next evaluation / save / print point without reading anything back
+        nxt = min(end, (step // ITER_TIMES_PER_PRINT + 1) * ITER_TIMES_PER_PRINT)
+        tr.run(step + 1, nxt - step)
+        step = nxt
+        if step % ITER_TIMES_PER_EVALUATE == 0:
+            evaluate_loss_accuracy(step, lr_at(step))
+        elif step % ITER_TIMES_PER_PRINT == 0:
+            tr.last_stats()
+            print("%s  step %d" % (get_time_str(), step))
+        if step % ITER_TIMES_PER_SAVE == 0:
+            pkg.ethcnn.write_ckpt_blob(os.path.join(a.models, "model_%s_%d_%s.dat" % (get_time_str(), step, name)), tr.get_blob())
+    blob = tr.get_blob()
+    with open(log, "w", newline="") as f:
+        f.write("%d\r\n" % end)
+        for r in rows:
+            f.write(r + "\r\n")
+    if end % ITER_TIMES_PER_SAVE != 0:
+        pkg.ethcnn.write_ckpt_blob(os.path.join(a.models, "model_%s_%d_%s.dat" % (get_time_str(), end, name)), blob)
+    pkg.ethcnn.write_ckpt_blob(os.path.join(a.models, "model.dat"), blob)
+    if a.export_ai:
+        target = os.path.join(a.export_ai, pkg.ethcnn.model_name_for_qp(qps[0]))
+        pkg.ethcnn.write_ckpt_blob(target, blob)
+        print("exported %s" % target)
+    tr.close()
+    ctx.close()
+    return 0
+
+
+if __name__ == "__main__":
+    sys.exit(main())

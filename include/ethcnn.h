@@ -347,6 +347,68 @@ uint32_t ethcnn_crc32c_masked(const void* data, size_t nbytes);
 int ethcnn_ckpt_read_blob(const char* prefix, float* blob_out, size_t nfloats, char* err, size_t errcap);
 int ethcnn_ckpt_read_lstm_blob(const char* prefix, float* blob_out, size_t nfloats, char* err, size_t errcap);
 
+
+/* TF-V2 bundle WRITER (tf.train.Saver's format, BundleWriter layout): blob -> <prefix>.index + <prefix>.data-00000-of-00001, each
+ * written to a temp file and renamed.  What ethcnn_load_checkpoint and both launchers restore.  No context / device needed. */
+int ethcnn_ckpt_write_blob(const char* prefix, const float* blob, size_t nfloats, char* err, size_t errcap);
+
+/* ---- training (All-Intra ETH-CNN; ETH-CNN_Training_AI/net_CTU64.py:94-206 + train_CNN_CTU64.py:36-47).
+ *      A trainer is bound to a context: its device and its stream.  Everything a step computes runs in hand-written gfx950 kernels
+ *      (exact fp32; csrc/ethcnn_train.h lists the 8 launches of a step).  Deterministic: same weights, data, seed and calls ->
+ *      bit-identical weights.
+ *   Samples: the reference's record format (input_data.py:16,92-116), 4992 bytes = 4096 luma + 64 pad + 52 x 16 label bytes; the
+ *      label row of QP q is at byte 4160 + 16 q.  Set 0 = training, 1 = validation; uploaded once, resident in HBM.
+ *   Batches drawn on the device (ethcnn_train_run), with mix(z) = splitmix64's output function
+ *      (z += 0x9E3779B97F4A7C15; z = (z ^ z >> 30) * 0xBF58476D1CE4E5B9; z = (z ^ z >> 27) * 0x94D049BB133111EB; z ^ z >> 31) and
+ *      draw(stream, step, slot, unit) = mix(mix(mix(seed ^ stream * 0xD1B54A32D192ED03) ^ step) ^ (slot << 12 | unit)) (uint64):
+ *        sample index of batch slot b   = (draw(1, step, b, 0) >> 32) * n_train >> 32      (uniform, with replacement)
+ *        QP of batch slot b             = qps[(draw(2, step, b, 0) >> 32) * nqps >> 32]
+ *        dropout keep of unit u         = (draw(3, step, b, u) >> 40) * 2^-24 < keep   (float compare; u = 0..447 FC1 in head order
+ *                                         64|32|16 with keep 0.5, u = 448 + 0..335 FC2 with keep 0.8; kept values scaled by 1 / keep)
+ *      `step` is the 1-based global step, which also sets the learning rate: lr_init * decay_rate ^ floor(step / decay_steps).
+ *   Optimiser: MomentumOptimizer without Nesterov, accum = momentum * accum + grad; w -= lr * accum.  The blob (key order, as in the
+ *      checkpoints) is the master copy of the weights. */
+typedef struct ethcnn_trainer ethcnn_trainer;
+typedef struct ethcnn_train_options {
+    int batch;           /* samples per step (reference: 64)                                   */
+    float lr_init;       /* 0.01                                                               */
+    float momentum;      /* 0.9                                                                */
+    float decay_rate;    /* 0.3163                                                             */
+    int64_t decay_steps; /* 250000                                                             */
+    int dropout;         /* 1: isdrop = 1 in training steps (evaluation never drops)           */
+    uint64_t seed;       /* the draw() seed of batches and dropout masks                       */
+    int reserved[8];
+} ethcnn_train_options;
+enum { ETHCNN_TRAIN_SET_TRAIN = 0, ETHCNN_TRAIN_SET_VALID = 1 };
+enum {
+    ETHCNN_TRAIN_DBG_GRADS = 0,     /* [1288210] gradient of the last step, blob layout                        */
+    ETHCNN_TRAIN_DBG_MASK_FC1 = 1,  /* [batch][448] dropout keep (0 / 1) of the last step, heads 64|32|16      */
+    ETHCNN_TRAIN_DBG_MASK_FC2 = 2,  /* [batch][336]                                                            */
+    ETHCNN_TRAIN_DBG_PROBS = 3,     /* [batch][21] probabilities of the last step                              */
+    ETHCNN_TRAIN_DBG_INDICES = 4,   /* [batch][2] (sample index, QP) of the last step, as floats               */
+    ETHCNN_TRAIN_DBG_ACCUM = 5      /* [1288210] momentum accumulators                                         */
+};
+int ethcnn_train_create(ethcnn_ctx* ctx, const ethcnn_train_options* opt, ethcnn_trainer** out);
+void ethcnn_train_destroy(ethcnn_trainer* tr); /* before ethcnn_destroy of its context */
+/* tf.truncated_normal(stddev 0.1) weights (|x| <= 0.2, redrawn beyond), tf.constant(0.01) biases (net_CTU64.py:37-43); our RNG, seeded;
+ * accumulators zeroed */
+int ethcnn_train_init_weights(ethcnn_trainer* tr, uint64_t seed);
+int ethcnn_train_set_blob(ethcnn_trainer* tr, const float* blob, const float* accum /* NULL = zeros */, size_t nfloats);
+int ethcnn_train_get_blob(ethcnn_trainer* tr, float* blob, float* accum /* may be NULL */, size_t nfloats);
+int ethcnn_train_set_samples(ethcnn_trainer* tr, int set, const uint8_t* records, size_t nbytes); /* ERR_FORMAT: nbytes % 4992 != 0 */
+int ethcnn_train_set_qps(ethcnn_trainer* tr, const int* qps, int nqps);                           /* SELECT_QP_LIST, 0..51 */
+/* steps first_step .. first_step + nsteps - 1 with device-drawn batches; asynchronous (nothing read back) */
+int ethcnn_train_run(ethcnn_trainer* tr, int64_t first_step, int64_t nsteps);
+/* loss_list / accuracy_list (64, 32, 16) of the last step enqueued; waits for it */
+int ethcnn_train_last_stats(ethcnn_trainer* tr, float loss3[3], float acc3[3]);
+/* one step on an explicit batch of n == batch training samples (tests); synchronous */
+int ethcnn_train_step_indices(ethcnn_trainer* tr, int64_t step, const int32_t* idx, const int* qp, int n, float loss3[3], float acc3[3]);
+/* forward only (no dropout) over n samples of a set at one QP (idx NULL: samples 0 .. n-1); the loss and accuracy lists are those of
+ * ONE batch of all n samples (train_CNN_CTU64.py's 5000-sample sess.run), not a mean over pieces.  probs [n][21] may be NULL. */
+int ethcnn_train_evaluate(ethcnn_trainer* tr, int set, const int32_t* idx, int64_t n, int qp, float loss3[3], float acc3[3], float* probs);
+int ethcnn_train_debug_fetch(ethcnn_trainer* tr, int which, float* out, size_t nfloats);
+const char* ethcnn_train_last_error(const ethcnn_trainer* tr);
+
 #ifdef __cplusplus
 }
 #endif

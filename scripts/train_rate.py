@@ -1,0 +1,96 @@
+"""Training-step rate of the GPU trainer (include/ethcnn.h "training") and the float64 torch-CPU restatement as a baseline.
+
+    python scripts/train_rate.py [--steps 2000] [--cpu-steps 5] [--out profiles/train_rate.json]
+
+Per batch size: `--warmup` steps, then `--steps` device-drawn steps enqueued back to back inside one synchronised host-clock window
+(no read-back inside it) -> us per step and samples/s.  The CPU baseline runs tests/train_ref.py (float64 autograd, torch's own CPU
+kernels) on the same batch size; its thread count is torch's default unless --cpu-threads is given.  Data: seeded synthetic records.
+"""
+import argparse
+import importlib
+import json
+import os
+import subprocess
+import sys
+import time
+
+import numpy as np
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+sys.path.insert(0, ROOT)
+sys.path.insert(0, os.path.join(ROOT, "tests"))
+import train_data  # noqa: E402
+
+LAUNCHES_PER_STEP = 8  # csrc/ethcnn_train.h
+FC1_FLOP_PER_SAMPLE = 2 * 2688 * 448 * 3  # forward + the two backward GEMMs of FC1
+
+
+def gpu_rate(pkg, ctx, batch, data, warmup, steps):
+    t = pkg.Trainer(ctx, batch=batch, seed=1)
+    t.set_samples(0, data)
+    t.set_qps([32])
+    t.init_weights(1)
+    t.run(1, warmup)
+    t.last_stats()
+    t0 = time.perf_counter()
+    t.run(warmup + 1, steps)
+    t.last_stats()
+    dt = time.perf_counter() - t0
+    t.close()
+    return dt / steps * 1e6
+
+
+def cpu_rate(batch, data, steps, threads):
+    import torch
+    import train_ref
+    if threads:
+        torch.set_num_threads(threads)
+    blob = np.random.default_rng(0).standard_normal(1288210) * 0.05
+    idx = np.arange(batch) % (len(data) // 4992)
+    luma, lab = train_ref.parse_records(data, idx, 32)
+    train_ref.loss_and_grad(blob, luma, lab, 32)
+    t0 = time.perf_counter()
+    for _ in range(steps):
+        train_ref.loss_and_grad(blob, luma, lab, 32)
+    return (time.perf_counter() - t0) / steps * 1e6, torch.get_num_threads()
+
+
+def main():
+    ap = argparse.ArgumentParser()
+    ap.add_argument("--steps", type=int, default=2000)
+    ap.add_argument("--warmup", type=int, default=200)
+    ap.add_argument("--batches", default="64,256,1024")
+    ap.add_argument("--cpu-steps", type=int, default=5)
+    ap.add_argument("--cpu-threads", type=int, default=0)
+    ap.add_argument("--out", default="")
+    a = ap.parse_args()
+    pkg = importlib.import_module("hevc-complexity-reduction_amd")
+    data = train_data.make_records(4096, seed=1)
+    ctx = pkg.EthCnn(device=0)
+    res = {"launches_per_step": LAUNCHES_PER_STEP, "device": ctx.device_name, "gpu": {}}
+    for b in [int(x) for x in a.batches.split(",")]:
+        us = gpu_rate(pkg, ctx, b, data, a.warmup, a.steps)
+        res["gpu"][str(b)] = {"us_per_step": round(us, 2), "samples_per_s": round(b / us * 1e6),
+                              "fc1_tflops": round(FC1_FLOP_PER_SAMPLE * b / us * 1e-6, 3)}
+        print("batch %5d: %9.1f us/step  %10.0f samples/s" % (b, us, b / us * 1e6), flush=True)
+    ctx.close()
+    us64 = res["gpu"].get("64", {}).get("us_per_step")
+    if us64:
+        res["projected_1M_iterations_h"] = round(us64 * 1e6 / 3.6e9, 3)  # the reference's schedule: 1 M steps at batch 64
+    if a.cpu_steps:
+        cus, thr = cpu_rate(64, data, a.cpu_steps, a.cpu_threads)
+        res["cpu_torch_float64"] = {"batch": 64, "us_per_step": round(cus), "threads": thr}
+        print("cpu torch float64 batch 64: %.0f us/step (%d threads)" % (cus, thr))
+    try:
+        res["commit"] = subprocess.check_output(["git", "-C", ROOT, "rev-parse", "--short", "HEAD"], stderr=subprocess.DEVNULL).decode().strip()
+    except Exception:
+        res["commit"] = "unknown"
+    line = json.dumps(res)
+    print(line)
+    if a.out:
+        with open(a.out, "w") as f:
+            f.write(line + "\n")
+
+
+if __name__ == "__main__":
+    main()
