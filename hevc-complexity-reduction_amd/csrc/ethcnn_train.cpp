@@ -1,5 +1,6 @@
 // ethcnn_train.cpp -- host side of the trainer (include/ethcnn.h "training"): buffers, the GEMM descriptor tables, the step and
 // evaluation sequences (kernels: ethcnn_train_kernels.hip, launch order: ethcnn_train.h).
+#include <algorithm>
 #include <cmath>
 #include <new>
 #include <cstring>
@@ -11,16 +12,18 @@
 
 namespace ethcnn {
 namespace train {
-void launch_trunk_fwd(hipStream_t s, int nb, const StepArgs& a, const float* W, const NetOffsets& o);
+void launch_trunk_fwd(hipStream_t s, int nb, const StepArgs& a, const float* W, const NetOffsets& o, int net);
 void launch_gemm(hipStream_t s, const GemmGroup* d_grp, int tiles);
 void launch_heads_fwd(hipStream_t s, int nb, const float* Z1, float* A1, float* M1, float* H1, float* A2, float* M2, float* H2,
-                      float* P, const int32_t* qp, const float* W, const NetOffsets& o, uint64_t seed, uint64_t step, int dropout);
+                      float* P, const int32_t* qp, const float* W, const NetOffsets& o, uint64_t seed, uint64_t step, int dropout, int net);
 void launch_loss(hipStream_t s, const float* P, const float* lab, int n, float* stats, float* dZ);
 void launch_heads_bwd(hipStream_t s, int nb, const float* dZ3, const float* A1, const float* M1, const float* A2, const float* M2,
                       float* dZ2, float* dZ1, const float* W, const NetOffsets& o, int dropout);
 void launch_trunk_bwd(hipStream_t s, int nb, const float* trunk, const float* F, const float* dF, const float* W, const NetOffsets& o,
                       float* part);
-void launch_update(hipStream_t s, float* W, float* acc, float* grad, const float* part, int nb, float lr, float momentum, long n);
+void launch_update(hipStream_t s, float* W, float* acc, float* grad, const float* part, int nb, float lr, float momentum, long n,
+                   const TuneMask& mask);
+void launch_check_slots(hipStream_t s, const uint8_t* data, long nrec, uint32_t want, long* first_bad, int nblocks);
 }  // namespace train
 }  // namespace ethcnn
 
@@ -63,6 +66,10 @@ struct ethcnn_trainer {
     int64_t nrec[2] = {0, 0};
     int qps[52] = {0};
     int nqps = 0;
+    int net = kNetAi, tune = 0;  // ethcnn_train_options.net / .tune
+    TuneMask mask{};             // the tensors tune 1..3 optimises (n == 0: all)
+    int slot_of_qp[2][52];       // LDP, per set: the slot of each of its four QPs, -1 elsewhere
+    int slot_qps[2][4] = {{0}};
     std::vector<void*> allocs;
 };
 
@@ -120,17 +127,21 @@ static GemmGroup fc1_group(const ethcnn_trainer* t, int m) {
 }
 
 // dF = dZ1 x W1^T (K = 448 over the three heads' tensors) and the nine FC weight / bias gradients X_aug^T x dZ, written into grad
+// (tune 1..3: only the tuned head's three GEMMs; the conv gradients have no reader, so dF is not formed)
 static GemmGroup bwd_group(const ethcnn_trainer* t, int m) {
     GemmGroup g{};
-    GemmDesc f{};
-    f.M = m; f.N = kTF; f.K = kTV; f.nseg = 3;
-    f.A = t->dZ1; f.sam = kTV; f.sak = 1;
-    for (int h = 0; h < 3; ++h) {
-        f.B[h] = t->W + t->o.w1[h]; f.sbk[h] = 1; f.sbn[h] = kHN1[h]; f.kseg[h] = kHOff1[h];
+    if (!t->tune) {
+        GemmDesc f{};
+        f.M = m; f.N = kTF; f.K = kTV; f.nseg = 3;
+        f.A = t->dZ1; f.sam = kTV; f.sak = 1;
+        for (int h = 0; h < 3; ++h) {
+            f.B[h] = t->W + t->o.w1[h]; f.sbk[h] = 1; f.sbn[h] = kHN1[h]; f.kseg[h] = kHOff1[h];
+        }
+        f.C = t->dF; f.ldc = kTF;
+        add_desc(g, f);
     }
-    f.C = t->dF; f.ldc = kTF;
-    add_desc(g, f);
     for (int h = 0; h < 3; ++h) {
+        if (t->tune && h != t->tune - 1) continue;
         GemmDesc d{};  // dW1 | db1: rows 0..2687 from F, row 2688 = the ones column
         d.M = kLdF; d.N = kHN1[h]; d.K = m; d.msplit = kTF;
         d.A = t->F; d.sam = 1; d.sak = kLdF;
@@ -170,6 +181,7 @@ static void enqueue_forward(ethcnn_trainer* t, int set, int nb, const int32_t* d
     std::memcpy(a.qps, t->qps, sizeof a.qps);
     a.nqps = t->nqps;
     a.qp_fixed = qp_fixed;
+    std::memcpy(a.slot_of_qp, t->slot_of_qp[set], sizeof a.slot_of_qp);
     a.seed = t->opt.seed;
     a.step = step;
     a.dropout = dropout;
@@ -178,9 +190,9 @@ static void enqueue_forward(ethcnn_trainer* t, int set, int nb, const int32_t* d
     a.labels = lab;
     a.trunk = t->trunk;
     a.F = t->F;
-    launch_trunk_fwd(s, nb, a, t->W, t->o);
+    launch_trunk_fwd(s, nb, a, t->W, t->o, t->net);
     launch_gemm(s, grp, tiles);
-    launch_heads_fwd(s, nb, t->Z1, t->A1, t->M1, t->H1, t->A2, t->M2, t->H2, P, t->qp, t->W, t->o, t->opt.seed, step, dropout);
+    launch_heads_fwd(s, nb, t->Z1, t->A1, t->M1, t->H1, t->A2, t->M2, t->H2, P, t->qp, t->W, t->o, t->opt.seed, step, dropout, t->net);
 }
 
 static int enqueue_step(ethcnn_trainer* t, int64_t step, bool explicit_batch) {
@@ -192,8 +204,8 @@ static int enqueue_step(ethcnn_trainer* t, int64_t step, bool explicit_batch) {
     launch_loss(s, t->P, t->lab, t->B, t->stats, t->dZ3);
     launch_heads_bwd(s, t->B, t->dZ3, t->A1, t->M1, t->A2, t->M2, t->dZ2, t->dZ1, t->W, t->o, dropout);
     launch_gemm(s, t->g_bwd, t->t_bwd);
-    launch_trunk_bwd(s, t->B, t->trunk, t->F, t->dF, t->W, t->o, t->part);
-    launch_update(s, t->W, t->acc, t->grad, t->part, t->B, lr_at(t, step), t->opt.momentum, (long)kBlobFloats);
+    if (!t->tune) launch_trunk_bwd(s, t->B, t->trunk, t->F, t->dF, t->W, t->o, t->part);
+    launch_update(s, t->W, t->acc, t->grad, t->part, t->B, lr_at(t, step), t->opt.momentum, (long)kBlobFloats, t->mask);
     TCHK(t, hipGetLastError());
     return 0;
 }
@@ -222,6 +234,9 @@ extern "C" int ethcnn_train_create(ethcnn_ctx* c, const ethcnn_train_options* op
     if (opt->decay_steps <= 0) return set_err(c, ETHCNN_ERR_ARG, "decay_steps must be positive");
     if (!std::isfinite(opt->lr_init) || !std::isfinite(opt->momentum) || !std::isfinite(opt->decay_rate))
         return set_err(c, ETHCNN_ERR_ARG, "non-finite optimiser option");
+    if (opt->net != ETHCNN_TRAIN_NET_AI && opt->net != ETHCNN_TRAIN_NET_LDP)
+        return set_err(c, ETHCNN_ERR_ARG, "net must be %d (All-Intra) or %d (LDP), got %d", ETHCNN_TRAIN_NET_AI, ETHCNN_TRAIN_NET_LDP, opt->net);
+    if (opt->tune < 0 || opt->tune > 3) return set_err(c, ETHCNN_ERR_ARG, "tune must be in 0..3, got %d", opt->tune);
     if (hipSetDevice(c->device) != hipSuccess) return set_err(c, ETHCNN_ERR_DEVICE, "hipSetDevice(%d) failed", c->device);
     ethcnn_trainer* t = new (std::nothrow) ethcnn_trainer;
     if (!t) return set_err(c, ETHCNN_ERR_NOMEM, "out of memory");
@@ -229,6 +244,10 @@ extern "C" int ethcnn_train_create(ethcnn_ctx* c, const ethcnn_train_options* op
     t->opt = *opt;
     t->B = opt->batch;
     t->cap = std::max(t->B, kEvalChunk);
+    t->net = opt->net;
+    t->tune = opt->tune;
+    for (int s = 0; s < 2; ++s)
+        for (int q = 0; q < 52; ++q) t->slot_of_qp[s][q] = -1;
     for (int br = 0; br < 3; ++br) {  // conv variables in creation order L, M, S (net_CTU64.py:122-138): Variable_{6 br' + 2 l}
         const int bc = br == 0 ? 2 : (br == 1 ? 1 : 0);
         for (int l = 0; l < 3; ++l) {
@@ -250,6 +269,16 @@ extern "C" int ethcnn_train_create(ethcnn_ctx* c, const ethcnn_train_options* op
         std::snprintf(n, sizeof n, "h_fc2__%s__b", tag); t->o.b2[h] = tensor_off(n);
         std::snprintf(n, sizeof n, "y_conv_flat__%s__w", tag); t->o.w3[h] = tensor_off(n);
         std::snprintf(n, sizeof n, "y_conv_flat__%s__b", tag); t->o.b3[h] = tensor_off(n);
+    }
+    if (t->tune) {  // PARTLY_TUNING_MODE (net_CTU64.py:200-209): the six tensors whose names hold __64__ / __32__ / __16__
+        const int h = t->tune - 1, n1 = kHN1[h], n2 = kHN2[h], n3 = kHN3[h];
+        const int off[6] = {t->o.w1[h], t->o.b1[h], t->o.w2[h], t->o.b2[h], t->o.w3[h], t->o.b3[h]};
+        const int cnt[6] = {kTF * n1, n1, (n1 + 1) * n2, n2, (n2 + 1) * n3, n3};
+        for (int i = 0; i < 6; ++i) {
+            t->mask.lo[i] = off[i];
+            t->mask.hi[i] = (long)off[i] + cnt[i];
+        }
+        t->mask.n = 6;
     }
     const size_t R = (size_t)t->cap;
     int rc = 0;
@@ -336,7 +365,8 @@ extern "C" int ethcnn_train_init_weights(ethcnn_trainer* t, uint64_t seed) {
         const TensorDesc& d = kTensors[i];
         float* out = blob.data() + d.offset_bytes / 4;
         uint64_t state = mix64(seed ^ (0xA0761D6478BD642Full * (uint64_t)(i + 1)));
-        for (size_t k = 0; k < d.count(); ++k) out[k] = d.rank == 1 ? 0.01f : (float)(0.1 * trunc_normal(state));
+        const bool constant_bias = d.rank == 1 && t->net == ETHCNN_TRAIN_NET_AI;  // LDP: bias_variable is truncated normal too
+        for (size_t k = 0; k < d.count(); ++k) out[k] = constant_bias ? 0.01f : (float)(0.1 * trunc_normal(state));
     }
     return ethcnn_train_set_blob(t, blob.data(), nullptr, kBlobFloats);
 }
@@ -368,8 +398,18 @@ extern "C" int ethcnn_train_set_samples(ethcnn_trainer* t, int set, const uint8_
     if (!t) return ETHCNN_ERR_ARG;
     if (set != 0 && set != 1) return terr(t, ETHCNN_ERR_ARG, "set must be 0 (train) or 1 (valid), got %d", set);
     if (!rec || nbytes == 0) return terr(t, ETHCNN_ERR_ARG, "no sample records");
-    if (nbytes % kRec) return terr(t, ETHCNN_ERR_FORMAT, "%zu bytes is not a whole number of %d-byte records", nbytes, kRec);
-    if (nbytes / kRec > 0x7fffffffull) return terr(t, ETHCNN_ERR_ARG, "more than 2^31 - 1 records");
+    const int rb = t->net == ETHCNN_TRAIN_NET_LDP ? kRecLdp : kRec;
+    if (nbytes % rb) return terr(t, ETHCNN_ERR_FORMAT, "%zu bytes is not a whole number of %d-byte records", nbytes, rb);
+    if (nbytes / rb > 0x7fffffffull) return terr(t, ETHCNN_ERR_ARG, "more than 2^31 - 1 records");
+    int sq[4] = {0, 0, 0, 0};
+    if (t->net == ETHCNN_TRAIN_NET_LDP) {  // record 0's slot QPs: four distinct values in 0..51
+        for (int q = 0; q < 4; ++q) {
+            sq[q] = rec[kSlotBase + kSlotBytes * q];
+            if (sq[q] > 51) return terr(t, ETHCNN_ERR_FORMAT, "record 0: slot %d holds QP %d, outside 0..51", q, sq[q]);
+            for (int k = 0; k < q; ++k)
+                if (sq[k] == sq[q]) return terr(t, ETHCNN_ERR_FORMAT, "record 0: slots %d and %d both hold QP %d", k, q, sq[q]);
+        }
+    }
     TCHK(t, hipSetDevice(t->c->device));
     TCHK(t, hipStreamSynchronize(t->c->stream));
     if (t->data[set]) {
@@ -386,8 +426,43 @@ extern "C" int ethcnn_train_set_samples(ethcnn_trainer* t, int set, const uint8_
         (void)hipFree(p);
         return terr(t, ETHCNN_ERR_DEVICE, "sample upload failed");
     }
+    const int64_t n = (int64_t)(nbytes / rb);
+    if (t->net == ETHCNN_TRAIN_NET_LDP) {  // every record carries record 0's slot QPs (one pass on the device)
+        const int nblk = (int)std::min<int64_t>(1024, (n + 255) / 256);
+        long* d_bad = nullptr;
+        std::vector<long> bad((size_t)nblk);
+        const uint32_t want = (uint32_t)sq[0] | (uint32_t)sq[1] << 8 | (uint32_t)sq[2] << 16 | (uint32_t)sq[3] << 24;
+        hipError_t e = hipMalloc(&d_bad, sizeof(long) * nblk);
+        if (e == hipSuccess) {
+            launch_check_slots(t->c->stream, (const uint8_t*)p, (long)n, want, d_bad, nblk);
+            e = hipGetLastError();
+        }
+        if (e == hipSuccess) e = hipMemcpyAsync(bad.data(), d_bad, sizeof(long) * nblk, hipMemcpyDeviceToHost, t->c->stream);
+        if (e == hipSuccess) e = hipStreamSynchronize(t->c->stream);
+        (void)hipFree(d_bad);
+        if (e != hipSuccess) {
+            (void)hipFree(p);
+            return terr(t, ETHCNN_ERR_DEVICE, "sample check: %s", hipGetErrorString(e));
+        }
+        const long first = *std::min_element(bad.begin(), bad.end());
+        if (first < n) {
+            (void)hipFree(p);
+            const uint8_t* r = rec + (size_t)first * kRecLdp + kSlotBase;
+            return terr(t, ETHCNN_ERR_FORMAT, "record %ld: slot QPs %d %d %d %d differ from record 0's %d %d %d %d", first, r[0],
+                        r[kSlotBytes], r[2 * kSlotBytes], r[3 * kSlotBytes], sq[0], sq[1], sq[2], sq[3]);
+        }
+        for (int q = 0; q < 52; ++q) t->slot_of_qp[set][q] = -1;
+        for (int q = 0; q < 4; ++q) {
+            t->slot_qps[set][q] = sq[q];
+            t->slot_of_qp[set][sq[q]] = q;
+        }
+        if (set == ETHCNN_TRAIN_SET_TRAIN) {  // the QP list defaults to the four slots (every MODEL_TYPE trains on all of them)
+            std::memcpy(t->qps, sq, sizeof sq);
+            t->nqps = 4;
+        }
+    }
     t->data[set] = (uint8_t*)p;
-    t->nrec[set] = (int64_t)(nbytes / kRec);
+    t->nrec[set] = n;
     return 0;
 }
 
@@ -396,6 +471,12 @@ extern "C" int ethcnn_train_set_qps(ethcnn_trainer* t, const int* qps, int n) {
     if (!qps || n <= 0 || n > 52) return terr(t, ETHCNN_ERR_ARG, "the QP list must hold 1..52 entries");
     for (int i = 0; i < n; ++i)
         if (qps[i] < 0 || qps[i] > 51) return terr(t, ETHCNN_ERR_ARG, "QP %d outside 0..51", qps[i]);
+    if (t->net == ETHCNN_TRAIN_NET_LDP) {
+        if (!t->data[ETHCNN_TRAIN_SET_TRAIN]) return terr(t, ETHCNN_ERR_ARG, "LDP: upload the training samples before the QP list");
+        for (int i = 0; i < n; ++i)
+            if (t->slot_of_qp[ETHCNN_TRAIN_SET_TRAIN][qps[i]] < 0)
+                return terr(t, ETHCNN_ERR_ARG, "QP %d is not a slot QP of the training samples", qps[i]);
+    }
     std::memcpy(t->qps, qps, sizeof(int) * n);
     t->nqps = n;
     return 0;
@@ -426,6 +507,8 @@ extern "C" int ethcnn_train_step_indices(ethcnn_trainer* t, int64_t step, const 
     for (int i = 0; i < n; ++i) {
         if (idx[i] < 0 || idx[i] >= t->nrec[0]) return terr(t, ETHCNN_ERR_ARG, "sample index %d outside 0..%lld", idx[i], (long long)t->nrec[0] - 1);
         if (qp[i] < 0 || qp[i] > 51) return terr(t, ETHCNN_ERR_ARG, "QP %d outside 0..51", qp[i]);
+        if (t->net == ETHCNN_TRAIN_NET_LDP && t->slot_of_qp[ETHCNN_TRAIN_SET_TRAIN][qp[i]] < 0)
+            return terr(t, ETHCNN_ERR_ARG, "QP %d is not a slot QP of the training samples", qp[i]);
     }
     TCHK(t, hipSetDevice(t->c->device));
     hipStream_t s = t->c->stream;
@@ -441,7 +524,10 @@ extern "C" int ethcnn_train_evaluate(ethcnn_trainer* t, int set, const int32_t* 
     if (!t) return ETHCNN_ERR_ARG;
     if (set != 0 && set != 1) return terr(t, ETHCNN_ERR_ARG, "set must be 0 (train) or 1 (valid), got %d", set);
     if (!t->data[set]) return terr(t, ETHCNN_ERR_ARG, "no samples in set %d", set);
-    if (qp < 0 || qp > 51) return terr(t, ETHCNN_ERR_ARG, "QP %d outside 0..51", qp);
+    const bool ldp = t->net == ETHCNN_TRAIN_NET_LDP;
+    if (!(qp >= 0 && qp <= 51) && !(ldp && qp == -1))
+        return terr(t, ETHCNN_ERR_ARG, ldp ? "QP %d is neither a slot QP nor -1" : "QP %d outside 0..51", qp);
+    if (ldp && qp >= 0 && t->slot_of_qp[set][qp] < 0) return terr(t, ETHCNN_ERR_ARG, "QP %d is not a slot QP of set %d", qp, set);
     if (n <= 0 || n > 0x7fffffffll || (!idx && n > t->nrec[set])) return terr(t, ETHCNN_ERR_ARG, "bad sample count %lld", (long long)n);
     if (idx)
         for (int64_t i = 0; i < n; ++i)
@@ -455,18 +541,25 @@ extern "C" int ethcnn_train_evaluate(ethcnn_trainer* t, int set, const int32_t* 
         for (int64_t i = 0; i < n; ++i) ids[(size_t)i] = (int32_t)i;
         idx = ids.data();
     }
+    std::vector<int32_t> mixed;  // qp == -1: sample i at the slot draw(2, 0, i, 0) picks among the four
+    if (qp < 0) {
+        mixed.resize((size_t)n);
+        for (int64_t i = 0; i < n; ++i)
+            mixed[(size_t)i] = t->slot_qps[set][((draw(t->opt.seed, kStreamQp, 0, (uint64_t)i, 0) >> 32) * 4ull) >> 32];
+    }
     float *Pn = nullptr, *Ln = nullptr;
-    int32_t* In = nullptr;
+    int32_t *In = nullptr, *Qn = nullptr;
     if (hipMalloc(&Pn, (size_t)n * kTOut * 4) != hipSuccess || hipMalloc(&Ln, (size_t)n * 16 * 4) != hipSuccess ||
-        hipMalloc(&In, (size_t)n * 4) != hipSuccess) {
+        hipMalloc(&In, (size_t)n * 4) != hipSuccess || (qp < 0 && hipMalloc(&Qn, (size_t)n * 4) != hipSuccess)) {
         (void)hipGetLastError();
-        (void)hipFree(Pn); (void)hipFree(Ln); (void)hipFree(In);
+        (void)hipFree(Pn); (void)hipFree(Ln); (void)hipFree(In); (void)hipFree(Qn);
         return terr(t, ETHCNN_ERR_NOMEM, "cannot allocate the evaluation buffers of %lld samples", (long long)n);
     }
     hipError_t e = hipMemcpyAsync(In, idx, (size_t)n * 4, hipMemcpyHostToDevice, s);
+    if (e == hipSuccess && Qn) e = hipMemcpyAsync(Qn, mixed.data(), (size_t)n * 4, hipMemcpyHostToDevice, s);
     for (int64_t c0 = 0; e == hipSuccess && c0 < n; c0 += t->cap) {
         const int nb = (int)std::min<int64_t>(t->cap, n - c0);
-        enqueue_forward(t, set, nb, In + c0, nullptr, qp, 0, 0, Pn + c0 * kTOut, Ln + c0 * 16, t->g_eval, t->t_eval);
+        enqueue_forward(t, set, nb, In + c0, Qn ? Qn + c0 : nullptr, qp, 0, 0, Pn + c0 * kTOut, Ln + c0 * 16, t->g_eval, t->t_eval);
         e = hipGetLastError();
     }
     if (e == hipSuccess) {
@@ -476,7 +569,7 @@ extern "C" int ethcnn_train_evaluate(ethcnn_trainer* t, int set, const int32_t* 
     }
     if (e == hipSuccess && probs) e = hipMemcpyAsync(probs, Pn, (size_t)n * kTOut * 4, hipMemcpyDeviceToHost, s);
     if (e == hipSuccess) e = hipStreamSynchronize(s);
-    (void)hipFree(Pn); (void)hipFree(Ln); (void)hipFree(In);
+    (void)hipFree(Pn); (void)hipFree(Ln); (void)hipFree(In); (void)hipFree(Qn);
     if (e != hipSuccess) return terr(t, ETHCNN_ERR_DEVICE, "evaluation: %s", hipGetErrorString(e));
     return read_stats(t, loss3, acc3);
 }
@@ -493,6 +586,7 @@ extern "C" int ethcnn_train_debug_fetch(ethcnn_trainer* t, int which, float* out
         case ETHCNN_TRAIN_DBG_MASK_FC2: src = t->M2; need = (size_t)t->B * kT2; break;
         case ETHCNN_TRAIN_DBG_PROBS: src = t->P; need = (size_t)t->B * kTOut; break;
         case ETHCNN_TRAIN_DBG_INDICES: need = (size_t)t->B * 2; break;
+        case ETHCNN_TRAIN_DBG_H1: src = t->A1; need = (size_t)t->B * kTV; break;
         default: return terr(t, ETHCNN_ERR_ARG, "unknown debug buffer %d", which);
     }
     if (!out || nfloats != need) return terr(t, ETHCNN_ERR_ARG, "debug buffer %d holds %zu floats", which, need);

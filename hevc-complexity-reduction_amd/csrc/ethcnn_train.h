@@ -13,6 +13,11 @@
 //                         gradients X_aug^T x dZ (bias = the ones row), written in blob layout
 //   7 k_train_trunk_bwd   one block per sample: dF -> the 18 conv tensors' per-sample gradient partials
 //   8 k_train_update      every parameter: conv gradients summed over the batch in sample order, then the momentum update
+// Low-Delay-P residual net (ETH-CNN_Training_LDP/net_CTU64.py:94-209): the same chain, with launches 1 and 3 instantiated for kNetLdp
+// (16516-byte records, the sample's slot, residual scaling, the 0.18 QP feature).  With a tuning mode 1..3 (PARTLY_TUNING_MODE: only
+// one head's six FC tensors are optimised) the conv gradients have no reader, so a step is 7 launches: launch 6 holds only the tuned
+// head's three weight / bias GEMMs (no dF = dZ1 W1^T), launch 7 (trunk backward) is skipped, and launch 8 leaves every other tensor
+// and its accumulator untouched.
 // Determinism: no atomics; every sum has one owner thread and a fixed order (MFMA chains run k in order), so the same inputs give the
 // same bits on every run.
 #pragma once
@@ -23,6 +28,9 @@ namespace train {
 
 constexpr int kRec = 4992;        // bytes per training record (input_data.py:16): 4096 luma, 64 pad, 52 x 16 label bytes
 constexpr int kLabelBase = 4160;  // label row of QP q at kLabelBase + 16 q (input_data.py:104)
+constexpr int kRecLdp = 16516;    // LDP record (input_data.py:48-50): 64 header bytes, then 4 slots of [qp | 16 labels | 4096 residual]
+constexpr int kSlotBase = 64, kSlotBytes = 4113;
+enum { kNetAi = 0, kNetLdp = 1 };  // ETHCNN_TRAIN_NET_AI / _LDP
 constexpr int kTF = 2688, kLdF = 2689, kTV = 448, kT2 = 336, kTOut = 21;
 constexpr int kConvFloats = 14808;  // the 18 conv tensors lie at blob floats [0, 14808) (sorted keys "Variable*")
 constexpr int kTrunkRec = 10752;    // per-sample trunk record: images S 4096 | M 1024 | L 256, conv1 S 4096 | M 1024 | L 256
@@ -73,6 +81,7 @@ struct StepArgs {
     int qps[52];
     int nqps;
     int qp_fixed;  // >= 0: every sample at this QP (evaluation)
+    int slot_of_qp[52];  // LDP: the record slot holding QP q (the set's four slot QPs; -1 elsewhere)
     uint64_t seed, step;
     int dropout;
     int32_t* idx_out;
@@ -80,6 +89,12 @@ struct StepArgs {
     float* labels;  // [B][16] depths
     float* trunk;   // [B][kTrunkRec]
     float* F;       // [B][kLdF]
+};
+
+// the parameter ranges [lo, hi) (blob floats) the update optimises; n == 0: all of them
+struct TuneMask {
+    long lo[6], hi[6];
+    int n;
 };
 
 }  // namespace train

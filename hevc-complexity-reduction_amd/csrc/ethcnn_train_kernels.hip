@@ -27,6 +27,9 @@ __device__ inline float keep_mask(uint64_t seed, uint64_t step, int slot, int un
 }
 
 // ------------------------------------------------------------------------------------------------------------ trunk forward ---
+// NET = kNetAi: a 4992-byte record, luma * (1/255), the label row of QP q at 4160 + 16 q.  NET = kNetLdp: a 16516-byte record, the
+// slot of QP q (a.slot_of_qp) holds [qp | 16 labels | 4096 residual bytes] at 64 + 4113 slot, residual (x - 128) / 255 * 10.
+template <int NET>
 __global__ __launch_bounds__(256) void k_train_trunk_fwd(StepArgs a, const float* __restrict__ W, NetOffsets o) {
     __shared__ float rec[kTrunkRec];  // images then conv1 outputs (trunk record layout)
     __shared__ float feat[kTF];
@@ -47,10 +50,17 @@ __global__ __launch_bounds__(256) void k_train_trunk_fwd(StepArgs a, const float
         a.qp_out[b] = q;
     }
     __syncthreads();
-    const uint8_t* r = a.data + (int64_t)sidx * kRec;
-    if (t < 16) a.labels[b * 16 + t] = (float)r[kLabelBase + 16 * sqp + t];
-    const float inv255 = (float)(1.0 / 255.0);  // tf.scalar_mul(1.0 / 255.0, x)
-    for (int p = t; p < 4096; p += 256) rec[p] = (float)r[p] * inv255;
+    if (NET == kNetAi) {
+        const uint8_t* r = a.data + (int64_t)sidx * kRec;
+        if (t < 16) a.labels[b * 16 + t] = (float)r[kLabelBase + 16 * sqp + t];
+        const float inv255 = (float)(1.0 / 255.0);  // tf.scalar_mul(1.0 / 255.0, x)
+        for (int p = t; p < 4096; p += 256) rec[p] = (float)r[p] * inv255;
+    } else {
+        // the slot base is odd (64 + 4113 slot), so the residual at +17 has no alignment: byte loads only
+        const uint8_t* r = a.data + (int64_t)sidx * kRecLdp + kSlotBase + (int64_t)kSlotBytes * a.slot_of_qp[sqp];
+        if (t < 16) a.labels[b * 16 + t] = (float)r[1 + t];
+        for (int p = t; p < 4096; p += 256) rec[p] = (((float)r[17 + p] - 128.f) / 255.f) * 10.f;  // net_CTU64.py:102, in TF's order
+    }
     __syncthreads();
     // aver_pool(x, 2) / aver_pool(x, 4) (net_CTU64.py:131,125)
     for (int p = t; p < 1024 + 256; p += 256) {
@@ -181,11 +191,13 @@ struct HeadBufs {
     const int32_t* qp;
 };
 
+template <int NET>
 __global__ __launch_bounds__(256) void k_train_heads_fwd(HeadBufs h, const float* __restrict__ W, NetOffsets o, uint64_t seed,
                                                           uint64_t step, int dropout) {
     __shared__ float h1[kLdH1], h2[kLdH2];
     const int b = blockIdx.x, t = threadIdx.x;
-    const float qpf = (float)h.qp[b] * (float)(1.0 / 51.0);  // tf.scalar_mul(1 / 51.0, qp)
+    const float qpf = NET == kNetAi ? (float)h.qp[b] * (float)(1.0 / 51.0)   // tf.scalar_mul(1 / 51.0, qp)
+                                    : ((float)h.qp[b] / 51.f) * 0.18f;       // LDP net_CTU64.py:103
     for (int u = t; u < kTV; u += 256) {
         const int hd = head_of(u, kHOff1), j = u - kHOff1[hd];
         const float av = lrelu(h.Z1[(long)b * kTV + u] + W[o.b1[hd] + j]);
@@ -441,10 +453,17 @@ __global__ __launch_bounds__(256) void k_train_trunk_bwd(const float* __restrict
 
 // ------------------------------------------------------------------------------------------------------------ update ---
 // MomentumOptimizer (use_nesterov=False): accum = accum * momentum + grad; var -= lr * accum.  Conv gradients: sum of the
-// per-sample partials in sample order.
+// per-sample partials in sample order.  mask.n > 0 (PARTLY_TUNING_MODE 1..3): only the blob ranges [lo, hi) are optimised; every
+// other weight and its accumulator is left untouched (not even rewritten).
 __global__ __launch_bounds__(256) void k_train_update(float* __restrict__ W, float* __restrict__ acc, float* __restrict__ grad,
-                                                       const float* __restrict__ part, int nb, float lr, float momentum, long n) {
+                                                       const float* __restrict__ part, int nb, float lr, float momentum, long n,
+                                                       TuneMask mask) {
     for (long j = (long)blockIdx.x * 256 + threadIdx.x; j < n; j += (long)gridDim.x * 256) {
+        if (mask.n) {
+            bool on = false;
+            for (int r = 0; r < mask.n; ++r) on = on || (j >= mask.lo[r] && j < mask.hi[r]);
+            if (!on) continue;
+        }
         float g;
         if (j < kConvFloats) {
             g = 0.f;
@@ -459,17 +478,42 @@ __global__ __launch_bounds__(256) void k_train_update(float* __restrict__ W, flo
     }
 }
 
+// ------------------------------------------------------------------------------------------------------------ LDP set check ---
+// first record (per block, over a contiguous range of records) whose four slot QP bytes differ from `want` (record 0's, packed
+// little-endian); nrec when there is none.  A min over the block in LDS, no atomics: the host takes the min over the blocks.
+__global__ __launch_bounds__(256) void k_train_check_slots(const uint8_t* __restrict__ data, long nrec, uint32_t want,
+                                                            long* __restrict__ first_bad) {
+    __shared__ long red[256];
+    const long per = (nrec + gridDim.x - 1) / gridDim.x, r0 = (long)blockIdx.x * per, r1 = min(nrec, r0 + per);
+    long bad = nrec;
+    for (long i = r0 + threadIdx.x; i < r1 && bad == nrec; i += 256) {
+        const uint8_t* r = data + i * kRecLdp + kSlotBase;
+        uint32_t got = 0;
+        for (int q = 0; q < 4; ++q) got |= (uint32_t)r[(long)kSlotBytes * q] << (8 * q);
+        if (got != want) bad = i;
+    }
+    red[threadIdx.x] = bad;
+    __syncthreads();
+    for (int w = 128; w > 0; w >>= 1) {
+        if ((int)threadIdx.x < w) red[threadIdx.x] = min(red[threadIdx.x], red[threadIdx.x + w]);
+        __syncthreads();
+    }
+    if (threadIdx.x == 0) first_bad[blockIdx.x] = red[0];
+}
+
 // ------------------------------------------------------------------------------------------------------------ launchers ---
-void launch_trunk_fwd(hipStream_t s, int nb, const StepArgs& a, const float* W, const NetOffsets& o) {
-    hipLaunchKernelGGL(k_train_trunk_fwd, dim3(nb), dim3(256), 0, s, a, W, o);
+void launch_trunk_fwd(hipStream_t s, int nb, const StepArgs& a, const float* W, const NetOffsets& o, int net) {
+    if (net == kNetLdp) hipLaunchKernelGGL(k_train_trunk_fwd<kNetLdp>, dim3(nb), dim3(256), 0, s, a, W, o);
+    else hipLaunchKernelGGL(k_train_trunk_fwd<kNetAi>, dim3(nb), dim3(256), 0, s, a, W, o);
 }
 void launch_gemm(hipStream_t s, const GemmGroup* d_grp, int tiles) {
     hipLaunchKernelGGL(k_train_gemm, dim3(tiles), dim3(256), 0, s, d_grp);
 }
 void launch_heads_fwd(hipStream_t s, int nb, const float* Z1, float* A1, float* M1, float* H1, float* A2, float* M2, float* H2,
-                      float* P, const int32_t* qp, const float* W, const NetOffsets& o, uint64_t seed, uint64_t step, int dropout) {
+                      float* P, const int32_t* qp, const float* W, const NetOffsets& o, uint64_t seed, uint64_t step, int dropout, int net) {
     HeadBufs h{Z1, A1, M1, H1, A2, M2, H2, P, qp};
-    hipLaunchKernelGGL(k_train_heads_fwd, dim3(nb), dim3(256), 0, s, h, W, o, seed, step, dropout);
+    if (net == kNetLdp) hipLaunchKernelGGL(k_train_heads_fwd<kNetLdp>, dim3(nb), dim3(256), 0, s, h, W, o, seed, step, dropout);
+    else hipLaunchKernelGGL(k_train_heads_fwd<kNetAi>, dim3(nb), dim3(256), 0, s, h, W, o, seed, step, dropout);
 }
 void launch_loss(hipStream_t s, const float* P, const float* lab, int n, float* stats, float* dZ) {
     hipLaunchKernelGGL(k_train_loss, dim3(1), dim3(256), 0, s, P, lab, n, stats, dZ);
@@ -483,8 +527,12 @@ void launch_trunk_bwd(hipStream_t s, int nb, const float* trunk, const float* F,
                       float* part) {
     hipLaunchKernelGGL(k_train_trunk_bwd, dim3(nb), dim3(256), 0, s, trunk, F, dF, W, o, part);
 }
-void launch_update(hipStream_t s, float* W, float* acc, float* grad, const float* part, int nb, float lr, float momentum, long n) {
-    hipLaunchKernelGGL(k_train_update, dim3(1024), dim3(256), 0, s, W, acc, grad, part, nb, lr, momentum, n);
+void launch_update(hipStream_t s, float* W, float* acc, float* grad, const float* part, int nb, float lr, float momentum, long n,
+                   const TuneMask& mask) {
+    hipLaunchKernelGGL(k_train_update, dim3(1024), dim3(256), 0, s, W, acc, grad, part, nb, lr, momentum, n, mask);
+}
+void launch_check_slots(hipStream_t s, const uint8_t* data, long nrec, uint32_t want, long* first_bad, int nblocks) {
+    hipLaunchKernelGGL(k_train_check_slots, dim3(nblocks), dim3(256), 0, s, data, nrec, want, first_bad);
 }
 
 }  // namespace train

@@ -617,23 +617,46 @@ class EthCnn(object):
 
 # ---------------------------------------------------------------------------------------------------------------- training ---
 TRAIN_REC = 4992  # bytes per training-sample record (4096 luma, 64 pad, 52 x 16 label bytes)
+LDP_REC = 16516   # bytes per LDP record: 64 header bytes, then 4 slots of [QP byte | 16 label bytes | 4096 residual bytes]
+LDP_SLOT_BASE, LDP_SLOT_BYTES = 64, 4113
 SET_TRAIN, SET_VALID = 0, 1
-TDBG_GRADS, TDBG_MASK_FC1, TDBG_MASK_FC2, TDBG_PROBS, TDBG_INDICES, TDBG_ACCUM = range(6)
+TRAIN_NET_AI, TRAIN_NET_LDP = 0, 1
+TDBG_GRADS, TDBG_MASK_FC1, TDBG_MASK_FC2, TDBG_PROBS, TDBG_INDICES, TDBG_ACCUM, TDBG_H1 = range(7)
+_M64 = (1 << 64) - 1
+
+
+def _mix64(z):
+    z = (z + 0x9E3779B97F4A7C15) & _M64
+    z = ((z ^ (z >> 30)) * 0xBF58476D1CE4E5B9) & _M64
+    z = ((z ^ (z >> 27)) * 0x94D049BB133111EB) & _M64
+    return z ^ (z >> 31)
+
+
+def mixed_eval_slots(seed, n):
+    """slot (0..3) of sample i = 0 .. n-1 in an LDP evaluation at qp = -1: (draw(2, 0, i, 0) >> 32) * 4 >> 32 (include/ethcnn.h)"""
+    base = _mix64(_mix64((int(seed) ^ 2 * 0xD1B54A32D192ED03) & _M64) ^ 0)  # draw(2, step 0, ...) up to its last mix
+    return np.array([(_mix64(base ^ (i << 12)) >> 32) * 4 >> 32 for i in range(int(n))], dtype=np.int64)
 
 
 class TrainOptions(ctypes.Structure):
     _fields_ = [("batch", ctypes.c_int), ("lr_init", ctypes.c_float), ("momentum", ctypes.c_float), ("decay_rate", ctypes.c_float),
-                ("decay_steps", ctypes.c_int64), ("dropout", ctypes.c_int), ("seed", ctypes.c_uint64), ("reserved", ctypes.c_int * 8)]
+                ("decay_steps", ctypes.c_int64), ("dropout", ctypes.c_int), ("seed", ctypes.c_uint64), ("net", ctypes.c_int),
+                ("tune", ctypes.c_int), ("reserved", ctypes.c_int * 6)]
 
 
 class Trainer(object):
-    """ETH-CNN (All-Intra) training on the GPU of an EthCnn context (include/ethcnn.h "training").  Defaults are the reference's
-    (train_CNN_CTU64.py:36-47): batch 64, lr 0.01 decayed by 0.3163 every 250000 steps, momentum 0.9, dropout on."""
+    """ETH-CNN training on the GPU of an EthCnn context (include/ethcnn.h "training").  Defaults are the reference's
+    (train_CNN_CTU64.py:36-47): batch 64, lr 0.01 decayed by 0.3163 every 250000 steps, momentum 0.9, dropout on.
+    net="ai": the All-Intra net on 4992-byte records; net="ldp": the Low-Delay-P residual net on 16516-byte records
+    (train_resi_CNN_CTU64.py).  tune: PARTLY_TUNING_MODE, 0 = every tensor, 1 / 2 / 3 = only head 64 / 32 / 16."""
 
-    def __init__(self, ctx, batch=64, lr=0.01, momentum=0.9, decay_rate=0.3163, decay_steps=250000, dropout=True, seed=0):
-        self.ctx, self.lib, self.batch = ctx, ctx.lib, int(batch)
+    def __init__(self, ctx, batch=64, lr=0.01, momentum=0.9, decay_rate=0.3163, decay_steps=250000, dropout=True, seed=0, net="ai",
+                 tune=0):
+        self.ctx, self.lib, self.batch, self.seed = ctx, ctx.lib, int(batch), int(seed) & (2 ** 64 - 1)
+        nets = {"ai": TRAIN_NET_AI, "ldp": TRAIN_NET_LDP}
+        self.net = net
         o = TrainOptions(int(batch), float(lr), float(momentum), float(decay_rate), int(decay_steps), 1 if dropout else 0,
-                         int(seed) & (2 ** 64 - 1))
+                         int(seed) & (2 ** 64 - 1), nets[net] if net in nets else int(net), int(tune))
         h = ctypes.c_void_p()
         rc = self.lib.ethcnn_train_create(ctx.h, ctypes.byref(o), ctypes.byref(h))
         if rc:
@@ -683,7 +706,8 @@ class Trainer(object):
         return (blob, acc) if with_accum else blob
 
     def set_samples(self, which, records):
-        """records: bytes / uint8 array of whole 4992-byte records (one sample file of the reference's Extract_Data)"""
+        """records: bytes / uint8 array of whole 4992-byte records (LDP: 16516-byte records), one sample file of the reference's
+        Extract_Data"""
         buf = np.frombuffer(records, dtype=np.uint8) if isinstance(records, (bytes, bytearray)) else np.ascontiguousarray(records, np.uint8)
         self._chk(self.lib.ethcnn_train_set_samples(self.h, int(which), buf.ctypes.data if buf.size else None, buf.size))
 
@@ -711,7 +735,8 @@ class Trainer(object):
         return l3, a3
 
     def evaluate(self, which, qp, idx=None, n=None, want_probs=False):
-        """(loss_list, accuracy_list[, probs [n,21]]) of ONE forward batch over the samples idx (or 0 .. n-1)"""
+        """(loss_list, accuracy_list[, probs [n,21]]) of ONE forward batch over the samples idx (or 0 .. n-1); LDP: qp = -1 puts
+        sample i at slot mixed_eval_slots(seed, n)[i]"""
         if idx is not None:
             idx = np.ascontiguousarray(idx, dtype=np.int32)
             n = idx.size
@@ -724,7 +749,7 @@ class Trainer(object):
 
     def debug_fetch(self, which):
         n = {TDBG_GRADS: BLOB_FLOATS, TDBG_ACCUM: BLOB_FLOATS, TDBG_MASK_FC1: self.batch * NVEC, TDBG_MASK_FC2: self.batch * NFC2,
-             TDBG_PROBS: self.batch * NOUT, TDBG_INDICES: self.batch * 2}[which]
+             TDBG_PROBS: self.batch * NOUT, TDBG_INDICES: self.batch * 2, TDBG_H1: self.batch * NVEC}[which]
         out = np.empty(n, dtype=np.float32)
         self._chk(self.lib.ethcnn_train_debug_fetch(self.h, int(which), out.ctypes.data_as(_fp), n))
         return out

@@ -49,54 +49,17 @@ def get_tendency_2x2(m):  # train_CNN_CTU64.py:140-148
     return -math.log10((m[0][0] / m[0][1]) / (m[1][1] / m[1][0]))
 
 
-def load_records(path):
+def load_records(path, rec=REC):
     data = np.memmap(path, dtype=np.uint8, mode="r")
-    if data.size == 0 or data.size % REC:
-        raise SystemExit("%s: %d bytes is not a whole number of %d-byte samples" % (path, data.size, REC))
+    if data.size == 0 or data.size % rec:
+        raise SystemExit("%s: %d bytes is not a whole number of %d-byte samples" % (path, data.size, rec))
     return data
 
 
-def parse_args(argv):
-    ap = argparse.ArgumentParser(description=__doc__.split("\n\n")[0])
-    ap.add_argument("--train", required=True, help="training sample file (4992-byte records)")
-    ap.add_argument("--valid", required=True, help="validation sample file")
-    g = ap.add_mutually_exclusive_group()
-    g.add_argument("--model-type", type=int, choices=sorted(MODEL_TYPES), default=1)
-    g.add_argument("--qp", type=int, help="train one QP (model name qp<QP>)")
-    ap.add_argument("--iters", type=int, default=1000000)
-    ap.add_argument("--batch", type=int, default=64)
-    ap.add_argument("--lr", type=float, default=0.01)
-    ap.add_argument("--decay-steps", type=int, default=250000)
-    ap.add_argument("--decay-rate", type=float, default=0.3163)
-    ap.add_argument("--momentum", type=float, default=0.9)
-    ap.add_argument("--seed", type=int, default=0, help="batches, dropout masks and the initial weights")
-    ap.add_argument("--no-dropout", action="store_true")
-    ap.add_argument("--reload", action="store_true", help="resume from <models>/model.dat and its loss_accuracy_list.dat")
-    ap.add_argument("--models", default="Models")
-    ap.add_argument("--export-ai", metavar="DIR", help="also write the final weights as video_to_cu_depth.py's model file in DIR")
-    ap.add_argument("--device", type=int, default=0)
-    return ap.parse_args(argv)
-
-
-def main(argv=None):
-    a = parse_args(argv)
-    pkg = importlib.import_module("hevc-complexity-reduction_amd")
+def train_loop(a, pkg, tr, name, ntrain, nvalid, evaluate, export=None):
+    """train_CNN_CTU64.py:296-399 (shared with train_resi_CNN_CTU64.py): reload, evaluate every 1000 steps (evaluate(which, idx) ->
+    loss list, accuracy list, probabilities, labels of one batch), the log, periodic and final checkpoints, the optional export."""
     import score_cu_depth
-    if a.qp is not None:
-        if not 0 <= a.qp <= 51:
-            raise SystemExit("--qp must be in 0..51")
-        name, qps = "qp%d" % a.qp, [a.qp]
-    else:
-        name, qps = MODEL_TYPES[a.model_type]
-    train, valid = load_records(a.train), load_records(a.valid)
-    ntrain, nvalid = train.size // REC, valid.size // REC
-    os.makedirs(a.models, exist_ok=True)
-    ctx = pkg.EthCnn(device=a.device)
-    tr = pkg.Trainer(ctx, batch=a.batch, lr=a.lr, momentum=a.momentum, decay_rate=a.decay_rate, decay_steps=a.decay_steps,
-                     dropout=not a.no_dropout, seed=a.seed)
-    tr.set_samples(pkg.ethcnn.SET_TRAIN, train)
-    tr.set_samples(pkg.ethcnn.SET_VALID, valid)
-    tr.set_qps(qps)
     log = os.path.join(a.models, "loss_accuracy_list.dat")
     rows = []
     if a.reload:
@@ -110,16 +73,12 @@ def main(argv=None):
     print("iter_times_last = %d" % iter_times_last)
     eval_rng = np.random.default_rng(a.seed + iter_times_last + 1)
 
-    def labels_of(data, idx):
-        recs = np.asarray(data).reshape(-1, REC)
-        return recs[idx, 4160 + 16 * qps[0]: 4176 + 16 * qps[0]]
-
     def evaluate_loss_accuracy(step, lr):  # train_CNN_CTU64.py:213-250
         out = []
-        for which, data, n in ((pkg.ethcnn.SET_TRAIN, train, ntrain), (pkg.ethcnn.SET_VALID, valid, nvalid)):
+        for which, n in ((pkg.ethcnn.SET_TRAIN, ntrain), (pkg.ethcnn.SET_VALID, nvalid)):
             idx = eval_rng.integers(0, n, min(NUM_EVAL, n))
-            l3, a3, probs = tr.evaluate(which, qps[0], idx=idx, want_probs=True)
-            ms = score_cu_depth.class_matrices(labels_of(data, idx), probs)
+            l3, a3, probs, labels = evaluate(which, idx)
+            ms = score_cu_depth.class_matrices(labels, probs)
             out.append((l3, a3, [get_tendency_2x2(m) for m in ms]))
         (tl, ta, tt), (vl, va, vt) = out
         print("%s step %d: loss=[[%.3f %.3f %.3f] [%.3f %.3f %.3f]], accu=[[%.3f %.3f %.3f] [%.3f %.3f %.3f]], lr=%g"
@@ -154,10 +113,59 @@ def main(argv=None):
     if end % ITER_TIMES_PER_SAVE != 0:
         pkg.ethcnn.write_ckpt_blob(os.path.join(a.models, "model_%s_%d_%s.dat" % (get_time_str(), end, name)), blob)
     pkg.ethcnn.write_ckpt_blob(os.path.join(a.models, "model.dat"), blob)
-    if a.export_ai:
-        target = os.path.join(a.export_ai, pkg.ethcnn.model_name_for_qp(qps[0]))
-        pkg.ethcnn.write_ckpt_blob(target, blob)
-        print("exported %s" % target)
+    if export:
+        pkg.ethcnn.write_ckpt_blob(export, blob)
+        print("exported %s" % export)
+
+
+def parse_args(argv):
+    ap = argparse.ArgumentParser(description=__doc__.split("\n\n")[0])
+    ap.add_argument("--train", required=True, help="training sample file (4992-byte records)")
+    ap.add_argument("--valid", required=True, help="validation sample file")
+    g = ap.add_mutually_exclusive_group()
+    g.add_argument("--model-type", type=int, choices=sorted(MODEL_TYPES), default=1)
+    g.add_argument("--qp", type=int, help="train one QP (model name qp<QP>)")
+    ap.add_argument("--iters", type=int, default=1000000)
+    ap.add_argument("--batch", type=int, default=64)
+    ap.add_argument("--lr", type=float, default=0.01)
+    ap.add_argument("--decay-steps", type=int, default=250000)
+    ap.add_argument("--decay-rate", type=float, default=0.3163)
+    ap.add_argument("--momentum", type=float, default=0.9)
+    ap.add_argument("--seed", type=int, default=0, help="batches, dropout masks and the initial weights")
+    ap.add_argument("--no-dropout", action="store_true")
+    ap.add_argument("--reload", action="store_true", help="resume from <models>/model.dat and its loss_accuracy_list.dat")
+    ap.add_argument("--models", default="Models")
+    ap.add_argument("--export-ai", metavar="DIR", help="also write the final weights as video_to_cu_depth.py's model file in DIR")
+    ap.add_argument("--device", type=int, default=0)
+    return ap.parse_args(argv)
+
+
+def main(argv=None):
+    a = parse_args(argv)
+    pkg = importlib.import_module("hevc-complexity-reduction_amd")
+    if a.qp is not None:
+        if not 0 <= a.qp <= 51:
+            raise SystemExit("--qp must be in 0..51")
+        name, qps = "qp%d" % a.qp, [a.qp]
+    else:
+        name, qps = MODEL_TYPES[a.model_type]
+    train, valid = load_records(a.train), load_records(a.valid)
+    ntrain, nvalid = train.size // REC, valid.size // REC
+    os.makedirs(a.models, exist_ok=True)
+    ctx = pkg.EthCnn(device=a.device)
+    tr = pkg.Trainer(ctx, batch=a.batch, lr=a.lr, momentum=a.momentum, decay_rate=a.decay_rate, decay_steps=a.decay_steps,
+                     dropout=not a.no_dropout, seed=a.seed)
+    tr.set_samples(pkg.ethcnn.SET_TRAIN, train)
+    tr.set_samples(pkg.ethcnn.SET_VALID, valid)
+    tr.set_qps(qps)
+
+    def evaluate(which, idx):  # one ONE-batch evaluation at the model's QP -> (loss, accuracy, probs, labels)
+        data = train if which == pkg.ethcnn.SET_TRAIN else valid
+        l3, a3, probs = tr.evaluate(which, qps[0], idx=idx, want_probs=True)
+        return l3, a3, probs, np.asarray(data).reshape(-1, REC)[idx, 4160 + 16 * qps[0]: 4176 + 16 * qps[0]]
+
+    export = os.path.join(a.export_ai, pkg.ethcnn.model_name_for_qp(qps[0])) if a.export_ai else None
+    train_loop(a, pkg, tr, name, ntrain, nvalid, evaluate, export)
     tr.close()
     ctx.close()
     return 0

@@ -1,0 +1,84 @@
+"""Train the Low-Delay-P residual ETH-CNN on the GPU: the driver of ETH-CNN_Training_LDP/train_resi_CNN_CTU64.py:283-399, with
+command-line flags in place of its module constants.  Every step runs in the library's training kernels (Trainer(net="ldp"),
+include/ethcnn.h "training"); this file only schedules, evaluates, logs and saves, through train_CNN_CTU64.py's loop.
+
+    python train_resi_CNN_CTU64.py --train LDP_Train_9011161.dat_shuffled --valid LDP_Valid_1057660.dat_shuffled
+    python train_resi_CNN_CTU64.py ... --export-ldp HM-16.5_Test_LDP/bin   # model_LDP_2000000_qp22~37.dat for the LDP daemon
+
+Sample files: the reference's Extract_Data LDP output (16516-byte records: a 64-byte header, then four QP slots of [QP | 16 depths |
+4096 residual bytes]), memory-mapped and uploaded once into HBM.  Every step draws each sample's slot uniformly among the four
+(input_data.py:119-130; every MODEL_TYPE trains on all four, MODEL_TYPE only names the model).  Evaluation every 1000 steps on 5000
+random samples of each set, each at a slot drawn per sample (the reference's mixed-QP parts; ethcnn_train_evaluate at qp = -1).
+Log, checkpoints and --reload as train_CNN_CTU64.py (accumulators restart at zero on reload, as the reference's Saver).
+--partly-tuning-mode 1 / 2 / 3 optimises only head 64 / 32 / 16 (net_CTU64.py:200-209); checkpoints hold all 36 tensors.
+Plotting is not ported.
+"""
+import argparse
+import importlib
+import os
+import sys
+
+import numpy as np
+
+_HERE = os.path.dirname(os.path.abspath(__file__))
+if _HERE not in sys.path:
+    sys.path.insert(0, _HERE)
+import train_CNN_CTU64 as ai  # noqa: E402  (also puts the repository root and tools/ on sys.path)
+
+REC = 16516
+SLOT_BASE, SLOT_BYTES = 64, 4113
+# input_data.py:54-74: MODEL_TYPE -> MODEL_NAME (SELECT_QP_LIST is never read by get_data_set)
+MODEL_TYPES = {0: "qp22~37", 1: "qp22", 2: "qp27", 3: "qp32", 4: "qp37"}
+EXPORT_NAME = "model_LDP_2000000_qp22~37.dat"  # resi_to_cu_depth_LDP.py:158-159
+
+
+def parse_args(argv):
+    ap = argparse.ArgumentParser(description=__doc__.split("\n\n")[0])
+    ap.add_argument("--train", required=True, help="training sample file (16516-byte records)")
+    ap.add_argument("--valid", required=True, help="validation sample file")
+    ap.add_argument("--model-type", type=int, choices=sorted(MODEL_TYPES), default=0)
+    ap.add_argument("--partly-tuning-mode", type=int, choices=(0, 1, 2, 3), default=0)
+    ap.add_argument("--iters", type=int, default=1000000)
+    ap.add_argument("--batch", type=int, default=64)
+    ap.add_argument("--lr", type=float, default=0.01)
+    ap.add_argument("--decay-steps", type=int, default=250000)
+    ap.add_argument("--decay-rate", type=float, default=0.3163)
+    ap.add_argument("--momentum", type=float, default=0.9)
+    ap.add_argument("--seed", type=int, default=0, help="batches, slots, dropout masks and the initial weights")
+    ap.add_argument("--no-dropout", action="store_true")
+    ap.add_argument("--reload", action="store_true", help="resume from <models>/model.dat and its loss_accuracy_list.dat")
+    ap.add_argument("--models", default="Models")
+    ap.add_argument("--export-ldp", metavar="DIR", help="also write the final weights as the LDP daemon's %s in DIR" % EXPORT_NAME)
+    ap.add_argument("--device", type=int, default=0)
+    return ap.parse_args(argv)
+
+
+def main(argv=None):
+    a = parse_args(argv)
+    pkg = importlib.import_module("hevc-complexity-reduction_amd")
+    name = MODEL_TYPES[a.model_type]
+    train, valid = ai.load_records(a.train, REC), ai.load_records(a.valid, REC)
+    ntrain, nvalid = train.size // REC, valid.size // REC
+    os.makedirs(a.models, exist_ok=True)
+    ctx = pkg.EthCnn(device=a.device)
+    tr = pkg.Trainer(ctx, batch=a.batch, lr=a.lr, momentum=a.momentum, decay_rate=a.decay_rate, decay_steps=a.decay_steps,
+                     dropout=not a.no_dropout, seed=a.seed, net="ldp", tune=a.partly_tuning_mode)
+    tr.set_samples(pkg.ethcnn.SET_TRAIN, train)  # the QP list becomes the four slot QPs
+    tr.set_samples(pkg.ethcnn.SET_VALID, valid)
+
+    def evaluate(which, idx):  # ONE batch, each sample at its drawn slot -> (loss, accuracy, probs, labels)
+        data = np.asarray(train if which == pkg.ethcnn.SET_TRAIN else valid).reshape(-1, REC)
+        l3, a3, probs = tr.evaluate(which, -1, idx=idx, want_probs=True)
+        lab0 = SLOT_BASE + SLOT_BYTES * pkg.ethcnn.mixed_eval_slots(a.seed, len(idx)) + 1
+        labels = data[np.asarray(idx)[:, None], lab0[:, None] + np.arange(16)]
+        return l3, a3, probs, labels
+
+    export = os.path.join(a.export_ldp, EXPORT_NAME) if a.export_ldp else None
+    ai.train_loop(a, pkg, tr, name, ntrain, nvalid, evaluate, export)
+    tr.close()
+    ctx.close()
+    return 0
+
+
+if __name__ == "__main__":
+    sys.exit(main())

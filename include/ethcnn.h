@@ -352,7 +352,8 @@ int ethcnn_ckpt_read_lstm_blob(const char* prefix, float* blob_out, size_t nfloa
  * written to a temp file and renamed.  What ethcnn_load_checkpoint and both launchers restore.  No context / device needed. */
 int ethcnn_ckpt_write_blob(const char* prefix, const float* blob, size_t nfloats, char* err, size_t errcap);
 
-/* ---- training (All-Intra ETH-CNN; ETH-CNN_Training_AI/net_CTU64.py:94-206 + train_CNN_CTU64.py:36-47).
+/* ---- training (All-Intra ETH-CNN; ETH-CNN_Training_AI/net_CTU64.py:94-206 + train_CNN_CTU64.py:36-47; the Low-Delay-P
+ *      residual CNN as a variant, see "net = ETHCNN_TRAIN_NET_LDP" below).
  *      A trainer is bound to a context: its device and its stream.  Everything a step computes runs in hand-written gfx950 kernels
  *      (exact fp32; csrc/ethcnn_train.h lists the 8 launches of a step).  Deterministic: same weights, data, seed and calls ->
  *      bit-identical weights.
@@ -367,7 +368,23 @@ int ethcnn_ckpt_write_blob(const char* prefix, const float* blob, size_t nfloats
  *                                         64|32|16 with keep 0.5, u = 448 + 0..335 FC2 with keep 0.8; kept values scaled by 1 / keep)
  *      `step` is the 1-based global step, which also sets the learning rate: lr_init * decay_rate ^ floor(step / decay_steps).
  *   Optimiser: MomentumOptimizer without Nesterov, accum = momentum * accum + grad; w -= lr * accum.  The blob (key order, as in the
- *      checkpoints) is the master copy of the weights. */
+ *      checkpoints) is the master copy of the weights.
+ *   net = ETHCNN_TRAIN_NET_LDP: the Low-Delay-P residual CNN (ETH-CNN_Training_LDP/net_CTU64.py:94-209, train_resi_CNN_CTU64.py),
+ *      whose checkpoint is model_LDP_2000000_qp22~37.dat.  Same graph, loss, labels, dropout and schedule; it differs in:
+ *        records: 16516 bytes (input_data.py:48-50) = 64 header bytes, then 4 slots of 4113 bytes = [QP byte | 16 label bytes |
+ *          4096 residual bytes] at 64 + 4113 s.  ethcnn_train_set_samples returns ERR_FORMAT if nbytes % 16516 != 0, or if any record's
+ *          four slot QP bytes differ from record 0's (four distinct values in 0..51; the message names the first such record).
+ *        QPs: a sample at QP q reads the slot whose QP byte is q (its labels and residual).  Uploading the training set sets the QP
+ *          list to its four slot QPs (the reference trains every MODEL_TYPE on all four); ethcnn_train_set_qps may choose a subset
+ *          (single-QP training), any other QP is ERR_ARG, as it is in explicit batches and in evaluation.  The device-drawn QP uses
+ *          the formula above, so a uniform draw over the four slots is input_data.py:119-130's numpy.random.choice(4).
+ *        input scaling: x = (x - 128) / 255 * 10 and the FC2 / FC3 QP feature qp / 51 * 0.18 (fp32, in that order).
+ *        initial biases: truncated normal sigma 0.1 like the weights (net_CTU64.py:38-40).
+ *        evaluation at qp = -1 (LDP only): sample i of the n evaluated is at the slot draw(2, 0, i, 0) picks,
+ *          slot = (draw(2, 0, i, 0) >> 32) * 4 >> 32 -- the reference's mixed-QP 5000-sample evaluation.
+ *   tune 1..3 (PARTLY_TUNING_MODE, net_CTU64.py:200-209; either net): only the six FC tensors of head 64 / 32 / 16 are optimised;
+ *      every other weight and its momentum accumulator stay bit-identical.  Such a step skips the trunk backward, and
+ *      ETHCNN_TRAIN_DBG_GRADS holds the tuned head's tensors only (the others keep whatever was there).  Checkpoints hold all 36. */
 typedef struct ethcnn_trainer ethcnn_trainer;
 typedef struct ethcnn_train_options {
     int batch;           /* samples per step (reference: 64)                                   */
@@ -377,8 +394,11 @@ typedef struct ethcnn_train_options {
     int64_t decay_steps; /* 250000                                                             */
     int dropout;         /* 1: isdrop = 1 in training steps (evaluation never drops)           */
     uint64_t seed;       /* the draw() seed of batches and dropout masks                       */
-    int reserved[8];
+    int net;             /* ETHCNN_TRAIN_NET_AI (0) or ETHCNN_TRAIN_NET_LDP (1); else ERR_ARG   */
+    int tune;            /* PARTLY_TUNING_MODE 0..3: 0 all tensors, 1/2/3 only head 64/32/16   */
+    int reserved[6];
 } ethcnn_train_options;
+enum { ETHCNN_TRAIN_NET_AI = 0, ETHCNN_TRAIN_NET_LDP = 1 };
 enum { ETHCNN_TRAIN_SET_TRAIN = 0, ETHCNN_TRAIN_SET_VALID = 1 };
 enum {
     ETHCNN_TRAIN_DBG_GRADS = 0,     /* [1288210] gradient of the last step, blob layout                        */
@@ -386,17 +406,18 @@ enum {
     ETHCNN_TRAIN_DBG_MASK_FC2 = 2,  /* [batch][336]                                                            */
     ETHCNN_TRAIN_DBG_PROBS = 3,     /* [batch][21] probabilities of the last step                              */
     ETHCNN_TRAIN_DBG_INDICES = 4,   /* [batch][2] (sample index, QP) of the last step, as floats               */
-    ETHCNN_TRAIN_DBG_ACCUM = 5      /* [1288210] momentum accumulators                                         */
+    ETHCNN_TRAIN_DBG_ACCUM = 5,     /* [1288210] momentum accumulators                                         */
+    ETHCNN_TRAIN_DBG_H1 = 6         /* [batch][448] leaky-ReLU FC1 outputs of the last step, before dropout    */
 };
 int ethcnn_train_create(ethcnn_ctx* ctx, const ethcnn_train_options* opt, ethcnn_trainer** out);
 void ethcnn_train_destroy(ethcnn_trainer* tr); /* before ethcnn_destroy of its context */
-/* tf.truncated_normal(stddev 0.1) weights (|x| <= 0.2, redrawn beyond), tf.constant(0.01) biases (net_CTU64.py:37-43); our RNG, seeded;
- * accumulators zeroed */
+/* tf.truncated_normal(stddev 0.1) weights (|x| <= 0.2, redrawn beyond), tf.constant(0.01) biases (net_CTU64.py:37-43; LDP: biases
+ * truncated normal too, from the same generator); our RNG, seeded; accumulators zeroed */
 int ethcnn_train_init_weights(ethcnn_trainer* tr, uint64_t seed);
 int ethcnn_train_set_blob(ethcnn_trainer* tr, const float* blob, const float* accum /* NULL = zeros */, size_t nfloats);
 int ethcnn_train_get_blob(ethcnn_trainer* tr, float* blob, float* accum /* may be NULL */, size_t nfloats);
-int ethcnn_train_set_samples(ethcnn_trainer* tr, int set, const uint8_t* records, size_t nbytes); /* ERR_FORMAT: nbytes % 4992 != 0 */
-int ethcnn_train_set_qps(ethcnn_trainer* tr, const int* qps, int nqps);                           /* SELECT_QP_LIST, 0..51 */
+int ethcnn_train_set_samples(ethcnn_trainer* tr, int set, const uint8_t* records, size_t nbytes); /* ERR_FORMAT: nbytes % 4992 (LDP 16516) */
+int ethcnn_train_set_qps(ethcnn_trainer* tr, const int* qps, int nqps);                           /* SELECT_QP_LIST, 0..51 (LDP: slot QPs) */
 /* steps first_step .. first_step + nsteps - 1 with device-drawn batches; asynchronous (nothing read back) */
 int ethcnn_train_run(ethcnn_trainer* tr, int64_t first_step, int64_t nsteps);
 /* loss_list / accuracy_list (64, 32, 16) of the last step enqueued; waits for it */
@@ -404,7 +425,8 @@ int ethcnn_train_last_stats(ethcnn_trainer* tr, float loss3[3], float acc3[3]);
 /* one step on an explicit batch of n == batch training samples (tests); synchronous */
 int ethcnn_train_step_indices(ethcnn_trainer* tr, int64_t step, const int32_t* idx, const int* qp, int n, float loss3[3], float acc3[3]);
 /* forward only (no dropout) over n samples of a set at one QP (idx NULL: samples 0 .. n-1); the loss and accuracy lists are those of
- * ONE batch of all n samples (train_CNN_CTU64.py's 5000-sample sess.run), not a mean over pieces.  probs [n][21] may be NULL. */
+ * ONE batch of all n samples (train_CNN_CTU64.py's 5000-sample sess.run), not a mean over pieces.  probs [n][21] may be NULL.
+ * LDP: qp is a slot QP of the set, or -1 for the per-sample slot draw above. */
 int ethcnn_train_evaluate(ethcnn_trainer* tr, int set, const int32_t* idx, int64_t n, int qp, float loss3[3], float acc3[3], float* probs);
 int ethcnn_train_debug_fetch(ethcnn_trainer* tr, int which, float* out, size_t nfloats);
 const char* ethcnn_train_last_error(const ethcnn_trainer* tr);

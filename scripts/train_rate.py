@@ -1,10 +1,13 @@
 """Training-step rate of the GPU trainer (include/ethcnn.h "training") and the float64 torch-CPU restatement as a baseline.
 
     python scripts/train_rate.py [--steps 2000] [--cpu-steps 5] [--out profiles/train_rate.json]
+    python scripts/train_rate.py --net ldp --tune 0,1 [--cpu-steps 0] [--out profiles/train_rate_ldp.json]
 
 Per batch size: `--warmup` steps, then `--steps` device-drawn steps enqueued back to back inside one synchronised host-clock window
 (no read-back inside it) -> us per step and samples/s.  The CPU baseline runs tests/train_ref.py (float64 autograd, torch's own CPU
 kernels) on the same batch size; its thread count is torch's default unless --cpu-threads is given.  Data: seeded synthetic records.
+--net ldp: the Low-Delay-P residual net on 16516-byte records (every step over the four slots); --tune: PARTLY_TUNING_MODE values,
+one timing row set each (1..3 skip the trunk backward: 7 launches).
 """
 import argparse
 import importlib
@@ -20,15 +23,17 @@ ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, ROOT)
 sys.path.insert(0, os.path.join(ROOT, "tests"))
 import train_data  # noqa: E402
+import train_data_ldp  # noqa: E402
 
 LAUNCHES_PER_STEP = 8  # csrc/ethcnn_train.h
 FC1_FLOP_PER_SAMPLE = 2 * 2688 * 448 * 3  # forward + the two backward GEMMs of FC1
 
 
-def gpu_rate(pkg, ctx, batch, data, warmup, steps):
-    t = pkg.Trainer(ctx, batch=batch, seed=1)
+def gpu_rate(pkg, ctx, batch, data, warmup, steps, net="ai", tune=0):
+    t = pkg.Trainer(ctx, batch=batch, seed=1, net=net, tune=tune)
     t.set_samples(0, data)
-    t.set_qps([32])
+    if net == "ai":
+        t.set_qps([32])  # LDP: the four slot QPs
     t.init_weights(1)
     t.run(1, warmup)
     t.last_stats()
@@ -63,8 +68,12 @@ def main():
     ap.add_argument("--cpu-steps", type=int, default=5)
     ap.add_argument("--cpu-threads", type=int, default=0)
     ap.add_argument("--out", default="")
+    ap.add_argument("--net", choices=("ai", "ldp"), default="ai")
+    ap.add_argument("--tune", default="0", help="comma-separated tuning modes (each a row set)")
     a = ap.parse_args()
     pkg = importlib.import_module("hevc-complexity-reduction_amd")
+    if a.net == "ldp":
+        return main_ldp(a, pkg)
     data = train_data.make_records(4096, seed=1)
     ctx = pkg.EthCnn(device=0)
     res = {"launches_per_step": LAUNCHES_PER_STEP, "device": ctx.device_name, "gpu": {}}
@@ -85,6 +94,24 @@ def main():
         res["commit"] = subprocess.check_output(["git", "-C", ROOT, "rev-parse", "--short", "HEAD"], stderr=subprocess.DEVNULL).decode().strip()
     except Exception:
         res["commit"] = "unknown"
+    line = json.dumps(res)
+    print(line)
+    if a.out:
+        with open(a.out, "w") as f:
+            f.write(line + "\n")
+
+
+def main_ldp(a, pkg):
+    data = train_data_ldp.make_records(4096, seed=1)
+    ctx = pkg.EthCnn(device=0)
+    res = {"net": "ldp", "device": ctx.device_name, "gpu": {}}
+    for tune in [int(x) for x in a.tune.split(",")]:
+        rows = res["gpu"]["tune%d" % tune] = {"launches_per_step": LAUNCHES_PER_STEP - (1 if tune else 0)}
+        for b in [int(x) for x in a.batches.split(",")]:
+            us = gpu_rate(pkg, ctx, b, data, a.warmup, a.steps, "ldp", tune)
+            rows[str(b)] = {"us_per_step": round(us, 2), "samples_per_s": round(b / us * 1e6)}
+            print("ldp tune %d batch %5d: %9.1f us/step  %10.0f samples/s" % (tune, b, us, b / us * 1e6), flush=True)
+    ctx.close()
     line = json.dumps(res)
     print(line)
     if a.out:
