@@ -265,6 +265,7 @@ int ckpt_read_index(const char* index_path, CkptEntry* entries, int cap, int* n_
 int ckpt_load_blob(const char* prefix, float* blob_out /*[kBlobFloats]*/, char* err, size_t errcap);
 int ckpt_load_table(const char* prefix, const TensorDesc* table, int ntensors, float* blob_out, char* err, size_t errcap);
 int ckpt_write_blob(const char* prefix, const float* blob /*[kBlobFloats]*/, char* err, size_t errcap);  // BundleWriter format
+int ckpt_write_table(const char* prefix, const TensorDesc* table, int ntensors, const float* blob, size_t nfloats, char* err, size_t errcap);
 uint32_t crc32c(const void* data, size_t n);
 uint32_t crc32c_mask(uint32_t crc);
 

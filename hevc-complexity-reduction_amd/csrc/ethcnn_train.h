@@ -23,6 +23,8 @@
 #pragma once
 #include <cstdint>
 
+#include <hip/hip_runtime_api.h>
+
 namespace ethcnn {
 namespace train {
 
@@ -96,6 +98,10 @@ struct TuneMask {
     long lo[6], hi[6];
     int n;
 };
+
+// launchers other trainers share (ethcnn_train_kernels.hip); the ETH-LSTM trainer uses both unchanged
+void launch_gemm(hipStream_t s, const GemmGroup* d_grp, int tiles);
+void launch_loss(hipStream_t s, const float* P, const float* lab, int n, float* stats, float* dZ);
 
 }  // namespace train
 }  // namespace ethcnn

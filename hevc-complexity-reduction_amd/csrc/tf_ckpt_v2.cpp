@@ -268,7 +268,7 @@ int ckpt_load_table(const char* prefix, const TensorDesc* table, int ntensors, f
 }
 
 // ------------------------------------------------------------------------ writer ----
-// BundleWriter's layout: one data block (header entry "" + the 36 sorted keys, restart interval 16, shared key prefixes), an empty
+// BundleWriter's layout: one data block (header entry "" + the sorted keys of a tensor table (36 CNN / 18 LSTM), restart interval 16, shared key prefixes), an empty
 // metaindex block, an index block with one handle, the 48-byte footer.  The .data file is the blob itself (kTensors' offsets are
 // its tensors back to back); both files are written to a temp name and renamed.
 static void put_varint(std::string& o, uint64_t v) {
@@ -317,11 +317,12 @@ static bool write_replace(const std::string& path, const void* data, size_t n, s
     return true;
 }
 
-int ckpt_write_blob(const char* prefix, const float* blob, char* err, size_t errcap) {
+int ckpt_write_table(const char* prefix, const TensorDesc* table, int ntensors, const float* blob, size_t nfloats,
+                            char* err, size_t errcap) {
     std::vector<std::pair<std::string, std::string>> entries;
     entries.emplace_back(std::string(), std::string("\x08\x01\x1a\x02\x08\x01", 6));  // BundleHeaderProto{num_shards 1, version{producer 1}}
-    for (int t = 0; t < kNumTensors; ++t) {
-        const TensorDesc& d = kTensors[t];
+    for (int t = 0; t < ntensors; ++t) {
+        const TensorDesc& d = table[t];
         std::string shape;
         for (int i = 0; i < d.rank; ++i) {
             std::string dim;
@@ -350,7 +351,7 @@ int ckpt_write_blob(const char* prefix, const float* blob, char* err, size_t err
     std::string handle;
     put_varint(handle, doff);
     put_varint(handle, dsize);
-    append_block(file, table_block({{std::string(kTensors[kNumTensors - 1].name) + "\xff", handle}}), ioff, isize);
+    append_block(file, table_block({{std::string(table[ntensors - 1].name) + "\xff", handle}}), ioff, isize);
     std::string footer;
     put_varint(footer, moff);
     put_varint(footer, msize);
@@ -362,9 +363,13 @@ int ckpt_write_blob(const char* prefix, const float* blob, char* err, size_t err
     file += footer;
     std::string why;
     const std::string p(prefix);
-    if (!write_replace(p + ".data-00000-of-00001", blob, kBlobFloats * 4, why) || !write_replace(p + ".index", file.data(), file.size(), why))
+    if (!write_replace(p + ".data-00000-of-00001", blob, nfloats * 4, why) || !write_replace(p + ".index", file.data(), file.size(), why))
         return fail(err, errcap, ETHCNN_ERR_IO, why);
     return 0;
+}
+
+int ckpt_write_blob(const char* prefix, const float* blob, char* err, size_t errcap) {
+    return ckpt_write_table(prefix, kTensors, kNumTensors, blob, kBlobFloats, err, errcap);
 }
 
 }  // namespace ethcnn
@@ -387,4 +392,8 @@ extern "C" int ethcnn_ckpt_read_lstm_blob(const char* prefix, float* blob_out, s
 extern "C" int ethcnn_ckpt_write_blob(const char* prefix, const float* blob, size_t nfloats, char* err, size_t errcap) {
     if (!prefix || !*prefix || !blob || nfloats != ethcnn::kBlobFloats) return ETHCNN_ERR_ARG;
     return ethcnn::ckpt_write_blob(prefix, blob, err, errcap);
+}
+extern "C" int ethcnn_ckpt_write_lstm_blob(const char* prefix, const float* blob, size_t nfloats, char* err, size_t errcap) {
+    if (!prefix || !*prefix || !blob || nfloats != ethcnn::kLstmBlobFloats) return ETHCNN_ERR_ARG;
+    return ethcnn::ckpt_write_table(prefix, ethcnn::kLstmTensors, ethcnn::kNumLstmTensors, blob, nfloats, err, errcap);
 }

@@ -140,6 +140,22 @@ SIGNATURES = {
     "ethcnn_train_evaluate": (_i, [_vp, _i, ctypes.POINTER(ctypes.c_int32), ctypes.c_int64, _i, _fp, _fp, _fp]),
     "ethcnn_train_debug_fetch": (_i, [_vp, _i, _fp, _sz]),
     "ethcnn_train_last_error": (_cp, [_vp]),
+    "ethcnn_ckpt_write_lstm_blob": (_i, [_cp, _fp, _sz, ctypes.c_char_p, _sz]),
+    "ethcnn_lstm_train_create": (_i, [_vp, ctypes.c_void_p, ctypes.POINTER(_vp)]),
+    "ethcnn_lstm_train_destroy": (None, [_vp]),
+    "ethcnn_lstm_train_init_weights": (_i, [_vp, ctypes.c_uint64]),
+    "ethcnn_lstm_train_set_blob": (_i, [_vp, _fp, _fp, _sz]),
+    "ethcnn_lstm_train_get_blob": (_i, [_vp, _fp, _fp, _sz]),
+    "ethcnn_lstm_train_set_qps": (_i, [_vp, ctypes.POINTER(ctypes.c_int), _i]),
+    "ethcnn_lstm_train_set_samples": (_i, [_vp, _i, _vp, _sz]),
+    "ethcnn_lstm_train_num_samples": (ctypes.c_int64, [_vp, _i]),
+    "ethcnn_lstm_train_run": (_i, [_vp, ctypes.c_int64, ctypes.c_int64]),
+    "ethcnn_lstm_train_last_stats": (_i, [_vp, _fp, _fp]),
+    "ethcnn_lstm_train_step_indices": (_i, [_vp, ctypes.c_int64, ctypes.POINTER(ctypes.c_int32), _i, _fp, _fp]),
+    "ethcnn_lstm_train_evaluate": (_i, [_vp, _i, ctypes.POINTER(ctypes.c_int32), ctypes.c_int64, _fp, _fp, _fp]),
+    "ethcnn_lstm_train_debug_fetch": (_i, [_vp, _i, _fp, _sz]),
+    "ethcnn_lstm_train_debug_rows": (ctypes.c_int64, [_vp]),
+    "ethcnn_lstm_train_last_error": (_cp, [_vp]),
 }
 
 _lib = None
@@ -218,6 +234,15 @@ def write_ckpt_blob(prefix, blob):
     rc = load_library().ethcnn_ckpt_write_blob(os.fsencode(prefix), blob.ctypes.data_as(_fp), blob.size, err, 400)
     if rc:
         raise EthCnnError(rc, err.value.decode("utf-8", "replace") or "ethcnn_ckpt_write_blob: bad arguments")
+
+
+def write_ckpt_lstm_blob(prefix, blob):
+    """float32[LSTM_BLOB_FLOATS] -> the ETH-LSTM TF-V2 bundle ethcnn_load_lstm_checkpoint restores (host only)"""
+    blob = np.ascontiguousarray(blob, dtype=np.float32)
+    err = ctypes.create_string_buffer(400)
+    rc = load_library().ethcnn_ckpt_write_lstm_blob(os.fsencode(prefix), blob.ctypes.data_as(_fp), blob.size, err, 400)
+    if rc:
+        raise EthCnnError(rc, err.value.decode("utf-8", "replace") or "ethcnn_ckpt_write_lstm_blob: bad arguments")
 
 
 def read_ckpt_blob(prefix):
@@ -752,4 +777,137 @@ class Trainer(object):
              TDBG_PROBS: self.batch * NOUT, TDBG_INDICES: self.batch * 2, TDBG_H1: self.batch * NVEC}[which]
         out = np.empty(n, dtype=np.float32)
         self._chk(self.lib.ethcnn_train_debug_fetch(self.h, int(which), out.ctypes.data_as(_fp), n))
+        return out
+
+
+# ------------------------------------------------------------------------------------------------------- ETH-LSTM training ---
+LSTM_SAMPLE_BYTES = 37264  # 64 info bytes + 20 slots of 465 float32 [qp | 16 labels | 448 vector]
+LSTM_STEPS, LSTM_SLOT_FLOATS = 20, 465
+(LDBG_GRADS, LDBG_NORM, LDBG_ACCUM, LDBG_MASK_H, LDBG_MASK_FC2, LDBG_PROBS, LDBG_INDICES, LDBG_STATE_C, LDBG_STATE_H) = range(9)
+
+
+class LstmTrainOptions(ctypes.Structure):
+    _fields_ = [("batch", ctypes.c_int), ("lr_init", ctypes.c_float), ("momentum", ctypes.c_float), ("decay_rate", ctypes.c_float),
+                ("decay_steps", ctypes.c_int64), ("dropout", ctypes.c_int), ("seed", ctypes.c_uint64), ("qp_scale", ctypes.c_float),
+                ("clip_norm", ctypes.c_float), ("reserved", ctypes.c_int * 6)]
+
+
+def lstm_select_qp(records, qps):
+    """indices of the 37264-byte samples whose slot-0 QP is in qps (SELECT_QP_LIST, input_data.py:126-134): what
+    LstmTrainer.set_samples keeps after set_qps(qps), in this order"""
+    raw = np.frombuffer(records, dtype=np.uint8) if isinstance(records, (bytes, bytearray)) else np.asarray(records, np.uint8)
+    q0 = np.ascontiguousarray(raw.reshape(-1, LSTM_SAMPLE_BYTES)[:, 64:68]).view(np.float32)[:, 0]
+    return np.arange(q0.size) if not len(qps) else np.flatnonzero(np.isin(q0, np.asarray(qps, np.float32)))
+
+
+class LstmTrainer(object):
+    """ETH-LSTM training on the GPU of an EthCnn context (include/ethcnn.h "ETH-LSTM training").  Defaults are the reference's
+    (train_LSTM_CTU64.py:42-52): batch 64, lr 0.1 decayed by 0.3163 every 25000 steps, momentum 0.9, global-norm clip 5, dropout on.
+    qp_scale: 1.0 is the training script as shipped; 0.18 trains a model for lstm_step / the LDP daemons."""
+
+    def __init__(self, ctx, batch=64, lr=0.1, momentum=0.9, decay_rate=0.3163, decay_steps=25000, dropout=True, seed=0, qp_scale=1.0,
+                 clip_norm=5.0):
+        self.ctx, self.lib, self.batch, self.seed = ctx, ctx.lib, int(batch), int(seed) & (2 ** 64 - 1)
+        o = LstmTrainOptions(int(batch), float(lr), float(momentum), float(decay_rate), int(decay_steps), 1 if dropout else 0,
+                             self.seed, float(qp_scale), float(clip_norm))
+        h = ctypes.c_void_p()
+        rc = self.lib.ethcnn_lstm_train_create(ctx.h, ctypes.byref(o), ctypes.byref(h))
+        if rc:
+            raise EthCnnError(rc, self.lib.ethcnn_last_error(ctx.h).decode())
+        self.h = h
+        if not hasattr(ctx, "_trainers"):
+            ctx._trainers = weakref.WeakSet()
+        ctx._trainers.add(self)
+
+    def _chk(self, rc):
+        if rc:
+            raise EthCnnError(rc, self.lib.ethcnn_lstm_train_last_error(self.h).decode())
+
+    def close(self):
+        if getattr(self, "h", None):
+            self.lib.ethcnn_lstm_train_destroy(self.h)
+            self.h = None
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+    def __enter__(self):
+        return self
+
+    def __exit__(self, *a):
+        self.close()
+
+    def init_weights(self, seed):
+        self._chk(self.lib.ethcnn_lstm_train_init_weights(self.h, int(seed) & (2 ** 64 - 1)))
+
+    def set_blob(self, blob, accum=None):
+        blob = np.ascontiguousarray(blob, dtype=np.float32)
+        acc = None if accum is None else np.ascontiguousarray(accum, dtype=np.float32)
+        if acc is not None and acc.size != blob.size:
+            raise ValueError("accumulators and blob differ in size")
+        self._chk(self.lib.ethcnn_lstm_train_set_blob(self.h, blob.ctypes.data_as(_fp),
+                                                      None if acc is None else acc.ctypes.data_as(_fp), blob.size))
+
+    def get_blob(self, with_accum=False):
+        blob = np.empty(LSTM_BLOB_FLOATS, dtype=np.float32)
+        acc = np.empty(LSTM_BLOB_FLOATS, dtype=np.float32) if with_accum else None
+        self._chk(self.lib.ethcnn_lstm_train_get_blob(self.h, blob.ctypes.data_as(_fp),
+                                                      None if acc is None else acc.ctypes.data_as(_fp), LSTM_BLOB_FLOATS))
+        return (blob, acc) if with_accum else blob
+
+    def set_qps(self, qps):
+        """SELECT_QP_LIST for the uploads that follow ([] keeps every sample)"""
+        arr = (ctypes.c_int * max(1, len(qps)))(*[int(q) for q in qps])
+        self._chk(self.lib.ethcnn_lstm_train_set_qps(self.h, arr, len(qps)))
+
+    def set_samples(self, which, records):
+        """records: bytes / uint8 array of whole 37264-byte samples (get_LSTM_input.py's output); returns the number kept"""
+        buf = np.frombuffer(records, dtype=np.uint8) if isinstance(records, (bytes, bytearray)) else np.ascontiguousarray(records, np.uint8)
+        self._chk(self.lib.ethcnn_lstm_train_set_samples(self.h, int(which), buf.ctypes.data if buf.size else None, buf.size))
+        return self.num_samples(which)
+
+    def num_samples(self, which):
+        return int(self.lib.ethcnn_lstm_train_num_samples(self.h, int(which)))
+
+    def run(self, first_step, nsteps):
+        """enqueue steps first_step .. first_step + nsteps - 1 (device-drawn batches); returns at once"""
+        self._chk(self.lib.ethcnn_lstm_train_run(self.h, int(first_step), int(nsteps)))
+
+    def last_stats(self):
+        l3, a3 = np.zeros(3, np.float32), np.zeros(3, np.float32)
+        self._chk(self.lib.ethcnn_lstm_train_last_stats(self.h, l3.ctypes.data_as(_fp), a3.ctypes.data_as(_fp)))
+        return l3, a3
+
+    def step_indices(self, step, idx):
+        idx = np.ascontiguousarray(idx, dtype=np.int32)
+        l3, a3 = np.zeros(3, np.float32), np.zeros(3, np.float32)
+        self._chk(self.lib.ethcnn_lstm_train_step_indices(self.h, int(step), idx.ctypes.data_as(ctypes.POINTER(ctypes.c_int32)), idx.size,
+                                                          l3.ctypes.data_as(_fp), a3.ctypes.data_as(_fp)))
+        return l3, a3
+
+    def evaluate(self, which, idx=None, n=None, want_probs=False):
+        """(loss_list, accuracy_list[, probs [20 n, 21]]) of ONE forward batch over the samples idx (or 0 .. n-1); rows 20 i + p"""
+        if idx is not None:
+            idx = np.ascontiguousarray(idx, dtype=np.int32)
+            n = idx.size
+        if n is None:
+            raise ValueError("evaluate needs idx or n")
+        probs = np.empty((int(n) * LSTM_STEPS, NOUT), dtype=np.float32) if want_probs else None
+        l3, a3 = np.zeros(3, np.float32), np.zeros(3, np.float32)
+        self._chk(self.lib.ethcnn_lstm_train_evaluate(self.h, int(which),
+                                                      None if idx is None else idx.ctypes.data_as(ctypes.POINTER(ctypes.c_int32)), int(n),
+                                                      l3.ctypes.data_as(_fp), a3.ctypes.data_as(_fp),
+                                                      None if probs is None else probs.ctypes.data_as(_fp)))
+        return (l3, a3, probs) if want_probs else (l3, a3)
+
+    def debug_fetch(self, which):
+        rows = int(self.lib.ethcnn_lstm_train_debug_rows(self.h))  # of the last step / the last piece of the last evaluation
+        n = {LDBG_GRADS: LSTM_BLOB_FLOATS, LDBG_ACCUM: LSTM_BLOB_FLOATS, LDBG_NORM: 1, LDBG_MASK_H: rows * NVEC,
+             LDBG_MASK_FC2: rows * NFC2, LDBG_PROBS: self.batch * LSTM_STEPS * NOUT, LDBG_INDICES: rows // LSTM_STEPS,
+             LDBG_STATE_C: rows * NVEC, LDBG_STATE_H: rows * NVEC}.get(which, 1)
+        out = np.empty(n, dtype=np.float32)
+        self._chk(self.lib.ethcnn_lstm_train_debug_fetch(self.h, int(which), out.ctypes.data_as(_fp), n))
         return out

@@ -56,14 +56,17 @@ def load_records(path, rec=REC):
     return data
 
 
-def train_loop(a, pkg, tr, name, ntrain, nvalid, evaluate, export=None):
-    """train_CNN_CTU64.py:296-399 (shared with train_resi_CNN_CTU64.py): reload, evaluate every 1000 steps (evaluate(which, idx) ->
-    loss list, accuracy list, probabilities, labels of one batch), the log, periodic and final checkpoints, the optional export."""
+def train_loop(a, pkg, tr, name, ntrain, nvalid, evaluate, export=None, num_eval=NUM_EVAL, save_every=ITER_TIMES_PER_SAVE, ckpt_io=None):
+    """train_CNN_CTU64.py:296-399 (shared with train_resi_CNN_CTU64.py and train_LSTM_CTU64.py): reload, evaluate every 1000 steps
+    (evaluate(which, idx) -> loss list, accuracy list, probabilities, labels of one batch), the log, periodic and final checkpoints,
+    the optional export.  num_eval / save_every / ckpt_io = (read, write): the LSTM driver's 10000 samples, 10000 steps and
+    18-tensor bundle; the defaults are the CNN drivers'."""
     import score_cu_depth
+    read_ckpt, write_ckpt = ckpt_io or (pkg.ethcnn.read_ckpt_blob, pkg.ethcnn.write_ckpt_blob)
     log = os.path.join(a.models, "loss_accuracy_list.dat")
     rows = []
     if a.reload:
-        tr.set_blob(pkg.ethcnn.read_ckpt_blob(os.path.join(a.models, "model.dat")))  # accumulators: zeros, as the reference's restore
+        tr.set_blob(read_ckpt(os.path.join(a.models, "model.dat")))  # accumulators: zeros, as the reference's restore
         with open(log) as f:
             iter_times_last = int(f.readline())
             rows = [ln.rstrip("\r\n") for ln in f if ln.strip()]
@@ -76,7 +79,7 @@ def train_loop(a, pkg, tr, name, ntrain, nvalid, evaluate, export=None):
     def evaluate_loss_accuracy(step, lr):  # train_CNN_CTU64.py:213-250
         out = []
         for which, n in ((pkg.ethcnn.SET_TRAIN, ntrain), (pkg.ethcnn.SET_VALID, nvalid)):
-            idx = eval_rng.integers(0, n, min(NUM_EVAL, n))
+            idx = eval_rng.integers(0, n, min(num_eval, n))
             l3, a3, probs, labels = evaluate(which, idx)
             ms = score_cu_depth.class_matrices(labels, probs)
             out.append((l3, a3, [get_tendency_2x2(m) for m in ms]))
@@ -103,18 +106,18 @@ def train_loop(a, pkg, tr, name, ntrain, nvalid, evaluate, export=None):
         elif step % ITER_TIMES_PER_PRINT == 0:
             tr.last_stats()
             print("%s  step %d" % (get_time_str(), step))
-        if step % ITER_TIMES_PER_SAVE == 0:
-            pkg.ethcnn.write_ckpt_blob(os.path.join(a.models, "model_%s_%d_%s.dat" % (get_time_str(), step, name)), tr.get_blob())
+        if step % save_every == 0:
+            write_ckpt(os.path.join(a.models, "model_%s_%d_%s.dat" % (get_time_str(), step, name)), tr.get_blob())
     blob = tr.get_blob()
     with open(log, "w", newline="") as f:
         f.write("%d\r\n" % end)
         for r in rows:
             f.write(r + "\r\n")
-    if end % ITER_TIMES_PER_SAVE != 0:
-        pkg.ethcnn.write_ckpt_blob(os.path.join(a.models, "model_%s_%d_%s.dat" % (get_time_str(), end, name)), blob)
-    pkg.ethcnn.write_ckpt_blob(os.path.join(a.models, "model.dat"), blob)
+    if end % save_every != 0:
+        write_ckpt(os.path.join(a.models, "model_%s_%d_%s.dat" % (get_time_str(), end, name)), blob)
+    write_ckpt(os.path.join(a.models, "model.dat"), blob)
     if export:
-        pkg.ethcnn.write_ckpt_blob(export, blob)
+        write_ckpt(export, blob)
         print("exported %s" % export)
 
 

@@ -1,0 +1,94 @@
+"""Train ETH-LSTM (Low-Delay-P, one model per QP) on the GPU: the driver of ETH-LSTM_Training_LDP/train_LSTM_CTU64.py:283-431, with
+command-line flags in place of its module constants.  Every step runs in the library's LSTM training kernels (LstmTrainer,
+include/ethcnn.h "ETH-LSTM training"); this file only schedules, evaluates, logs and saves, through train_CNN_CTU64.py's loop.
+
+    python train_LSTM_CTU64.py --train LDP_Train.dat_lstm_4qps_shuffled --valid LDP_Valid.dat_lstm_4qps_shuffled --qp 32
+    python train_LSTM_CTU64.py ... --qp 32 --qp-scale 0.18 --export-lstm HM-16.5_Test_LDP/bin   # model_LDP_200000_qp32.dat
+
+Sample files: get_LSTM_input.py's output (37264-byte samples: 64 info bytes + 20 slots of [qp | 16 labels | 448-vector] float32).
+--qp keeps the samples whose slot-0 QP is that value (SELECT_QP_LIST, input_data.py:41-61,126-134; --model-type 1..4 = QP 22 / 27 /
+32 / 37); they are uploaded once into HBM.  Like the reference: batch 64, lr 0.1 x 0.3163 every 25000 steps, momentum 0.9, gradients
+clipped to global norm 5, 200000 steps; every 1000 steps an evaluation (no dropout) on 10000 random samples of each set as ONE batch
+(NUM_TRAIN_PART / NUM_VALID_PART), with the class matrices and tendency of train_LSTM_CTU64.py:68-133 over its 20 x 10000 rows, one
+19-column line in Models/loss_accuracy_list.dat, a checkpoint every 10000 steps and Models/model.dat at the end.  --reload resumes
+from Models/model.dat and that log (momentum accumulators restart at zero, as the reference's Saver restore).
+--qp-scale: the QP feature is qp / 51 * qp_scale.  1.0 is the training script as shipped; the deployed one-step graph (lstm_step,
+both LDP daemons) computes qp / 51 * 0.18, so train with --qp-scale 0.18 for a model meant for them.
+Not ported: the per-QP evaluation report (log_*.dat), the periodic swap of the in-memory training part (all samples are resident),
+plotting.
+"""
+import argparse
+import importlib
+import os
+import sys
+
+import numpy as np
+
+_HERE = os.path.dirname(os.path.abspath(__file__))
+if _HERE not in sys.path:
+    sys.path.insert(0, _HERE)
+import train_CNN_CTU64 as ai  # noqa: E402  (also puts the repository root and tools/ on sys.path)
+
+REC, STEPS, SLOT = 37264, 20, 465
+MODEL_TYPES = {1: 22, 2: 27, 3: 32, 4: 37}  # input_data.py:41-61
+NUM_PART, ITER_TIMES_PER_SAVE = 10000, 10000  # train_LSTM_CTU64.py:57-58,64
+
+
+def parse_args(argv):
+    ap = argparse.ArgumentParser(description=__doc__.split("\n\n")[0])
+    ap.add_argument("--train", required=True, help="training sample file (37264-byte samples)")
+    ap.add_argument("--valid", required=True, help="validation sample file")
+    g = ap.add_mutually_exclusive_group()
+    g.add_argument("--model-type", type=int, choices=sorted(MODEL_TYPES), default=1)
+    g.add_argument("--qp", type=int, help="train the model of one QP (model name qp<QP>)")
+    ap.add_argument("--qp-scale", type=float, default=1.0, help="1.0: the training script as shipped; 0.18: a model for the daemons")
+    ap.add_argument("--iters", type=int, default=200000)
+    ap.add_argument("--batch", type=int, default=64)
+    ap.add_argument("--lr", type=float, default=0.1)
+    ap.add_argument("--decay-steps", type=int, default=25000)
+    ap.add_argument("--decay-rate", type=float, default=0.3163)
+    ap.add_argument("--momentum", type=float, default=0.9)
+    ap.add_argument("--clip-norm", type=float, default=5.0, help="MAX_GRAD_NORM; 0 = no clip")
+    ap.add_argument("--seed", type=int, default=0, help="batches, dropout masks and the initial weights")
+    ap.add_argument("--no-dropout", action="store_true")
+    ap.add_argument("--reload", action="store_true", help="resume from <models>/model.dat and its loss_accuracy_list.dat")
+    ap.add_argument("--models", default="Models")
+    ap.add_argument("--export-lstm", metavar="DIR", help="also write the final weights as the daemons' model_LDP_200000_qp<QP>.dat in DIR")
+    ap.add_argument("--device", type=int, default=0)
+    return ap.parse_args(argv)
+
+
+def main(argv=None):
+    a = parse_args(argv)
+    pkg = importlib.import_module("hevc-complexity-reduction_amd")
+    qp = a.qp if a.qp is not None else MODEL_TYPES[a.model_type]
+    if not 0 <= qp <= 51:
+        raise SystemExit("--qp must be in 0..51")
+    name = "qp%d" % qp
+    train, valid = ai.load_records(a.train, REC), ai.load_records(a.valid, REC)
+    os.makedirs(a.models, exist_ok=True)
+    ctx = pkg.EthCnn(device=a.device)
+    tr = pkg.LstmTrainer(ctx, batch=a.batch, lr=a.lr, momentum=a.momentum, decay_rate=a.decay_rate, decay_steps=a.decay_steps,
+                         dropout=not a.no_dropout, seed=a.seed, qp_scale=a.qp_scale, clip_norm=a.clip_norm)
+    tr.set_qps([qp])
+    ntrain = tr.set_samples(pkg.ethcnn.SET_TRAIN, train)
+    nvalid = tr.set_samples(pkg.ethcnn.SET_VALID, valid)
+    kept = {pkg.ethcnn.SET_TRAIN: pkg.ethcnn.lstm_select_qp(train, [qp]), pkg.ethcnn.SET_VALID: pkg.ethcnn.lstm_select_qp(valid, [qp])}
+    print("QP %d: %d of %d training and %d of %d validation samples" % (qp, ntrain, train.size // REC, nvalid, valid.size // REC))
+
+    def evaluate(which, idx):  # ONE batch of len(idx) samples -> (loss, accuracy, probs [20 n, 21], labels [20 n, 16])
+        data = np.asarray(train if which == pkg.ethcnn.SET_TRAIN else valid).reshape(-1, REC)
+        l3, a3, probs = tr.evaluate(which, idx=idx, want_probs=True)
+        rows = np.ascontiguousarray(data[kept[which][np.asarray(idx)], 64:]).view(np.float32).reshape(len(idx), STEPS, SLOT)
+        return l3, a3, probs, rows[:, :, 1:17].reshape(-1, 16)
+
+    export = os.path.join(a.export_lstm, pkg.ethcnn.lstm_model_name_for_qp(qp)) if a.export_lstm else None
+    ai.train_loop(a, pkg, tr, name, ntrain, nvalid, evaluate, export, num_eval=NUM_PART, save_every=ITER_TIMES_PER_SAVE,
+                  ckpt_io=(pkg.ethcnn.read_ckpt_lstm_blob, pkg.ethcnn.write_ckpt_lstm_blob))
+    tr.close()
+    ctx.close()
+    return 0
+
+
+if __name__ == "__main__":
+    sys.exit(main())

@@ -351,6 +351,8 @@ int ethcnn_ckpt_read_lstm_blob(const char* prefix, float* blob_out, size_t nfloa
 /* TF-V2 bundle WRITER (tf.train.Saver's format, BundleWriter layout): blob -> <prefix>.index + <prefix>.data-00000-of-00001, each
  * written to a temp file and renamed.  What ethcnn_load_checkpoint and both launchers restore.  No context / device needed. */
 int ethcnn_ckpt_write_blob(const char* prefix, const float* blob, size_t nfloats, char* err, size_t errcap);
+/* the same writer over the 18-tensor ETH-LSTM table (ETHCNN_LSTM_BLOB_FLOATS floats): what ethcnn_load_lstm_checkpoint restores */
+int ethcnn_ckpt_write_lstm_blob(const char* prefix, const float* blob, size_t nfloats, char* err, size_t errcap);
 
 /* ---- training (All-Intra ETH-CNN; ETH-CNN_Training_AI/net_CTU64.py:94-206 + train_CNN_CTU64.py:36-47; the Low-Delay-P
  *      residual CNN as a variant, see "net = ETHCNN_TRAIN_NET_LDP" below).
@@ -430,6 +432,90 @@ int ethcnn_train_step_indices(ethcnn_trainer* tr, int64_t step, const int32_t* i
 int ethcnn_train_evaluate(ethcnn_trainer* tr, int set, const int32_t* idx, int64_t n, int qp, float loss3[3], float acc3[3], float* probs);
 int ethcnn_train_debug_fetch(ethcnn_trainer* tr, int which, float* out, size_t nfloats);
 const char* ethcnn_train_last_error(const ethcnn_trainer* tr);
+
+/* ---- ETH-LSTM training (ETH-LSTM_Training_LDP/net_CTU64.py:85-276, input_data.py:88-147, train_LSTM_CTU64.py:42-52): the 20-step
+ *      unrolled LSTM of the Low-Delay-P path with back-propagation through time, one model per QP (model_LDP_200000_qp<QP>.dat).
+ *      Mirrors ethcnn_train_* one to one; bound to a context (its device and stream); hand-written gfx950 kernels, exact fp32,
+ *      deterministic (csrc/ethcnn_lstm_train.h lists the 10 launches of a step).  The blob is the 18-tensor LSTM table
+ *      (ETHCNN_LSTM_BLOB_FLOATS floats, key order), the master copy of the weights.
+ *   Samples: 37264 bytes = 64 info bytes + 20 time slots of 465 float32 [qp | 16 depth labels | 448-vector of the residual CNN]
+ *      (input_data.py:94-108).  Slot 0 is the current frame, slot k frame i - k; i_frame is the little-endian u32 at info byte 10 and
+ *      i_frame_in_GOP[k] = (i_frame - k) mod 4 (non-negative, as numpy.mod; so a GOP value outside 0..3 cannot arise, and a sample
+ *      with i_frame < 19, which get_LSTM_input.py never writes, is accepted with positions wrapped below frame 0).
+ *      ethcnn_lstm_train_set_samples returns ERR_FORMAT if nbytes % 37264 != 0, or (one pass
+ *      on the device) if a kept sample has a QP that is not an integer in 0..51, a label that is not an integer in 0..3 or a non-finite
+ *      vector element.  ethcnn_lstm_train_set_qps BEFORE an upload selects by QP (SELECT_QP_LIST, input_data.py:126-134): only the
+ *      samples whose slot-0 QP is in the list are kept, in file order, and sample indices count the kept ones (n = 0: keep all).
+ *   Graph as shipped: three cells (hidden 64 / 128 / 256 on vector columns [0,64) / [64,192) / [192,448); forget_bias 1, cell_clip 5,
+ *      gates i, j, f, o, zero initial state) consume slot 19 first and slot 0 last; the prediction of slot p is the one computed when
+ *      slot p was the input.  The external features are NOT reversed: the heads of the step that reads slot p get the QP and the GOP
+ *      one-hot of slot 19 - p (net_CTU64.py:125 indexes both lists by the unrolled step).  This is how the shipped models were
+ *      trained; it is transcribed, not corrected.  Heads: fc2([h, qp, onehot4]) leaky-ReLU(0.2), fc3([h2, qp, onehot4]) sigmoid.
+ *      Rows of every per-row output: r = 20 b + p (sample b of the batch, slot p).  Labels, class-balanced loss with counts over all
+ *      20 x batch rows, accuracy: net_CTU64.py:160-176, 220-233, 263-271.
+ *   qp_scale: the QP feature is qp / 51 * qp_scale.  0 means 1.0, the training script as shipped (net_CTU64.py:149).  The deployed
+ *      one-step graph -- ethcnn_lstm_step_device and both LDP daemons -- uses qp / 51 * 0.18, so a model meant for them is trained
+ *      with qp_scale = 0.18; one trained with 1.0 sees a shifted feature there.
+ *   Dropout (training steps with dropout = 1 only): keep 0.5 on the cell OUTPUT fed to fc2 (the h carried in the state is not
+ *      dropped), keep 0.8 on fc2's output; kept values scaled by 1 / keep.
+ *   RNG: draw() of "training" above with three more streams:
+ *        sample index of batch slot b  = (draw(4, step, b, 0) >> 32) * n_train >> 32            (next_batch_random: with replacement)
+ *        keep of unit u of row r       = (draw(5, step, r, u) >> 40) * 2^-24 < keep   (u = 0..447 cell outputs 64|32|16, keep 0.5;
+ *                                        u = 448 + 0..335 fc2 outputs, keep 0.8)
+ *        initial weight k of tensor t  = (2 * (draw(6, t, 0, k) >> 11) * 2^-53 - 1) * limit  (t: index in the table, key order)
+ *      limit: tf.get_variable's default glorot_uniform, sqrt(6 / (fan_in + fan_out)) for the six matrices and three LSTM kernels,
+ *      sqrt(3 / n) for the six fc biases (1-D [n]: fan_in = fan_out = n); the LSTM biases start at zero.
+ *   Optimiser: gradients of loss_16 + loss_32 + loss_64, tf.clip_by_global_norm(., clip_norm) (scale = clip * min(1 / norm,
+ *      1 / clip); clip_norm 0: no clip), MomentumOptimizer, lr = lr_init * decay_rate ^ floor(step / decay_steps).  The cell clip's
+ *      gradient is zero where c was clipped.  The global norm is summed in a fixed two-level order (512 ranges, then their sums). */
+typedef struct ethcnn_lstm_trainer ethcnn_lstm_trainer;
+typedef struct ethcnn_lstm_train_options {
+    int batch;           /* samples per step (reference: 64), 1..4096                          */
+    float lr_init;       /* 0.1                                                                */
+    float momentum;      /* 0.9                                                                */
+    float decay_rate;    /* 0.3163                                                             */
+    int64_t decay_steps; /* 25000                                                              */
+    int dropout;         /* 1: isdrop = 1 in training steps (evaluation never drops)           */
+    uint64_t seed;       /* the draw() seed of batches and dropout masks                       */
+    float qp_scale;      /* 0 = 1.0 (as shipped); 0.18 for a model the daemons will run        */
+    float clip_norm;     /* MAX_GRAD_NORM = 5; 0 = no clip                                     */
+    int reserved[6];
+} ethcnn_lstm_train_options;
+#define ETHCNN_LSTM_SAMPLE_BYTES 37264
+enum {
+    ETHCNN_LSTM_DBG_GRADS = 0,    /* [760078] gradient of the last step BEFORE the clip, blob layout                        */
+    ETHCNN_LSTM_DBG_NORM = 1,     /* [1] its global norm                                                                    */
+    ETHCNN_LSTM_DBG_ACCUM = 2,    /* [760078] momentum accumulators                                                         */
+    ETHCNN_LSTM_DBG_MASK_H = 3,   /* [rows][448] keep (0 / 1) of the cell outputs, last step                                */
+    ETHCNN_LSTM_DBG_MASK_FC2 = 4, /* [rows][336]                                                                            */
+    ETHCNN_LSTM_DBG_PROBS = 5,    /* [20 batch][21] probabilities of the last step                                          */
+    ETHCNN_LSTM_DBG_INDICES = 6,  /* [rows / 20] sample indices, as floats                                                  */
+    ETHCNN_LSTM_DBG_STATE_C = 7,  /* [rows][448] c (after the clip) computed with slot p as the input, cells 64|32|16        */
+    ETHCNN_LSTM_DBG_STATE_H = 8   /* [rows][448] h (not dropped)                                                            */
+};  /* rows = 20 x the samples of the last step, or of the last piece (<= max(batch, 256) samples) of the last evaluation:
+     ethcnn_lstm_train_debug_rows */
+int ethcnn_lstm_train_create(ethcnn_ctx* ctx, const ethcnn_lstm_train_options* opt, ethcnn_lstm_trainer** out);
+void ethcnn_lstm_train_destroy(ethcnn_lstm_trainer* tr); /* before ethcnn_destroy of its context */
+int ethcnn_lstm_train_init_weights(ethcnn_lstm_trainer* tr, uint64_t seed); /* accumulators zeroed */
+int ethcnn_lstm_train_set_blob(ethcnn_lstm_trainer* tr, const float* blob, const float* accum /* NULL = zeros */, size_t nfloats);
+int ethcnn_lstm_train_get_blob(ethcnn_lstm_trainer* tr, float* blob, float* accum /* may be NULL */, size_t nfloats);
+int ethcnn_lstm_train_set_qps(ethcnn_lstm_trainer* tr, const int* qps, int nqps); /* applies to the uploads that follow */
+int ethcnn_lstm_train_set_samples(ethcnn_lstm_trainer* tr, int set, const uint8_t* records, size_t nbytes);
+int64_t ethcnn_lstm_train_num_samples(const ethcnn_lstm_trainer* tr, int set); /* kept samples of a set */
+/* steps first_step .. first_step + nsteps - 1 with device-drawn batches; asynchronous (nothing read back) */
+int ethcnn_lstm_train_run(ethcnn_lstm_trainer* tr, int64_t first_step, int64_t nsteps);
+int ethcnn_lstm_train_last_stats(ethcnn_lstm_trainer* tr, float loss3[3], float acc3[3]);
+/* one step on an explicit batch of n == batch training samples (tests); synchronous */
+int ethcnn_lstm_train_step_indices(ethcnn_lstm_trainer* tr, int64_t step, const int32_t* idx, int n, float loss3[3], float acc3[3]);
+/* forward only (no dropout, no update) over n samples of a set (idx NULL: samples 0 .. n-1); the loss and accuracy lists are those
+ * of ONE batch of all n samples (train_LSTM_CTU64.py's NUM_TRAIN_PART = 10000 sess.run): the balanced loss divides by batch-global
+ * counts, so a mean over pieces would be another number.  probs [20 n][21] may be NULL.  Meant for a call every 1000 steps, not
+ * for a tight loop: each call allocates and frees its three [20 n] device arrays, and every piece's projection GEMM runs over the
+ * full max(batch, 256) x 20 rows (rows past a short piece hold an earlier batch's vectors; they are computed and never read). */
+int ethcnn_lstm_train_evaluate(ethcnn_lstm_trainer* tr, int set, const int32_t* idx, int64_t n, float loss3[3], float acc3[3], float* probs);
+int ethcnn_lstm_train_debug_fetch(ethcnn_lstm_trainer* tr, int which, float* out, size_t nfloats);
+int64_t ethcnn_lstm_train_debug_rows(const ethcnn_lstm_trainer* tr); /* `rows` of the per-row debug buffers right now */
+const char* ethcnn_lstm_train_last_error(const ethcnn_lstm_trainer* tr);
 
 #ifdef __cplusplus
 }
