@@ -302,6 +302,8 @@ std::vector<Pass> plan_passes(int nctu, int nframes, int max_ctus);
 void free_staging(ethcnn_ctx* c);
 int ensure_staging(ethcnn_ctx* c, size_t in_bytes, size_t out_bytes, int nbufs = 1);
 bool in_pinned(const ethcnn_ctx* c, const void* p, size_t bytes);
+HostPool* host_pool(ethcnn_ctx* c);  // the context's fill threads (created on first use)
+int pinned_pread(int fd, uint8_t* dst, size_t want, off_t off);  // file bytes -> page-locked memory; 0 or ETHCNN_ERR_IO
 
 struct StageTimer {
     ethcnn_ctx* c;

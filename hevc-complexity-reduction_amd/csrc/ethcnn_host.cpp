@@ -79,7 +79,7 @@ static int local_workers() {
     return 1;
 }
 
-static HostPool* host_pool(ethcnn_ctx* c) {
+HostPool* host_pool(ethcnn_ctx* c) {
     if (!c->pool) {
         // (shard_workers: this context is one of several workers of ONE process -- ethcnn_predict_yuv_file_sharded -- on top of
         // whatever other predictor processes share the node)
@@ -119,6 +119,32 @@ static void nt_copy(uint8_t* dst, const uint8_t* src, size_t n) {
     if (i < n) std::memcpy(dst + i, src + i, n - i);
     _mm_sfence();
 #endif
+}
+
+// `want` bytes of a file at `off` into page-locked staging memory.  pread lands in a cache-resident bounce buffer and goes on to the
+// pinned memory with non-temporal stores (nt_copy): pread straight into the staging buffer writes its lines through the cache
+// (read-for-ownership + write back) beside the DMA engine.  ETHCNN_FILE_IO=direct keeps the single-copy form.  (A read-only mapping of
+// the file + nt_copy, one copy and no syscalls, was measured at HALF the rate: page faults.)
+int pinned_pread(int fd, uint8_t* d, size_t want, off_t off) {
+    static const bool bounce = [] { const char* e = dev_env("ETHCNN_FILE_IO"); return !(e && std::strcmp(e, "direct") == 0); }();
+    constexpr size_t kBounce = 128u << 10;
+    size_t got = 0;
+    if (bounce) {
+        alignas(64) static thread_local uint8_t tmp[kBounce];
+        while (got < want) {
+            const ssize_t r = pread(fd, tmp, std::min(kBounce, want - got), off + (off_t)got);
+            if (r <= 0) return ETHCNN_ERR_IO;
+            nt_copy(d + got, tmp, (size_t)r);
+            got += (size_t)r;
+        }
+        return 0;
+    }
+    while (got < want) {
+        const ssize_t r = pread(fd, d + got, want - got, off + (off_t)got);
+        if (r <= 0) return ETHCNN_ERR_IO;
+        got += (size_t)r;
+    }
+    return 0;
 }
 
 template <typename Fn>
@@ -492,35 +518,10 @@ static int yuv_frames(ethcnn_ctx* c, const char* yuv, int w, int h, int qp, cons
         return set_err(c, ETHCNN_ERR_IO, "cannot open %s for writing: %s", shard ? out_path : tmp.c_str(), std::strerror(errno));
     }
     const int fd = fileno(fin), ofd = fileno(fout);
-    // pread lands in a cache-resident bounce buffer and goes on to the pinned staging memory with non-temporal stores
-    // (nt_copy): pread straight into the staging buffer writes its lines through the cache (read-for-ownership + write
-    // back) beside the DMA engine.  ETHCNN_FILE_IO=direct keeps the single-copy form.  (A read-only mapping of the file
-    // + nt_copy, one copy and no syscalls, was measured at HALF the rate: page faults.)
-    static const bool bounce = [] { const char* e = dev_env("ETHCNN_FILE_IO"); return !(e && std::strcmp(e, "direct") == 0); }();
-    constexpr size_t kBounce = 128u << 10;
     auto fill = [&](uint8_t* dst, int g0, int nf) -> int {
         // luma only; chroma (w*h/2 bytes per frame) is never read (:47-48)
         const int rc = parallel_bands(c, nf, w, h, [&](int f, int r0, int rows) -> int {
-            size_t got = 0;
-            const size_t want = (size_t)w * rows;
-            const off_t off = (off_t)(f0 + g0 + f) * frame_bytes + (off_t)r0 * w;
-            uint8_t* d = dst + (size_t)f * w * h + (size_t)r0 * w;
-            if (bounce) {
-                alignas(64) static thread_local uint8_t tmp[kBounce];
-                while (got < want) {
-                    const ssize_t r = pread(fd, tmp, std::min(kBounce, want - got), off + (off_t)got);
-                    if (r <= 0) return ETHCNN_ERR_IO;
-                    nt_copy(d + got, tmp, (size_t)r);
-                    got += (size_t)r;
-                }
-                return 0;
-            }
-            while (got < want) {
-                const ssize_t r = pread(fd, d + got, want - got, off + (off_t)got);
-                if (r <= 0) return ETHCNN_ERR_IO;
-                got += (size_t)r;
-            }
-            return 0;
+            return pinned_pread(fd, dst + (size_t)f * w * h + (size_t)r0 * w, (size_t)w * rows, (off_t)(f0 + g0 + f) * frame_bytes + (off_t)r0 * w);
         });
         return rc ? set_err(c, rc, "short read in %s (frames %lld..%lld)", yuv, (long long)(f0 + g0), (long long)(f0 + g0 + nf - 1)) : 0;
     };

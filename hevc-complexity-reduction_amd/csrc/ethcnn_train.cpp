@@ -8,6 +8,7 @@
 #include <vector>
 
 #include "ethcnn_ctx.h"
+#include "ethcnn_samples.h"
 #include "ethcnn_train.h"
 
 namespace ethcnn {
@@ -394,6 +395,48 @@ extern "C" int ethcnn_train_get_blob(ethcnn_trainer* t, float* blob, float* accu
     return 0;
 }
 
+// the checks every record takes on the device, then the set's bookkeeping: `p` (n records in HBM) becomes set `set`.  LDP: every record
+// carries the slot QPs sq[4] (one pass on the device).  On failure `p` is left to the caller.
+static int install_samples(ethcnn_trainer* t, int set, uint8_t* p, int64_t n, const int sq[4]) {
+    if (t->net == ETHCNN_TRAIN_NET_LDP) {
+        const int nblk = (int)std::min<int64_t>(1024, (n + 255) / 256);
+        long* d_bad = nullptr;
+        std::vector<long> bad((size_t)nblk);
+        const uint32_t want = (uint32_t)sq[0] | (uint32_t)sq[1] << 8 | (uint32_t)sq[2] << 16 | (uint32_t)sq[3] << 24;
+        hipError_t e = hipMalloc(&d_bad, sizeof(long) * nblk);
+        if (e == hipSuccess) {
+            launch_check_slots(t->c->stream, p, (long)n, want, d_bad, nblk);
+            e = hipGetLastError();
+        }
+        if (e == hipSuccess) e = hipMemcpyAsync(bad.data(), d_bad, sizeof(long) * nblk, hipMemcpyDeviceToHost, t->c->stream);
+        if (e == hipSuccess) e = hipStreamSynchronize(t->c->stream);
+        (void)hipFree(d_bad);
+        if (e != hipSuccess) return terr(t, ETHCNN_ERR_DEVICE, "sample check: %s", hipGetErrorString(e));
+        const long first = *std::min_element(bad.begin(), bad.end());
+        if (first < n) {
+            uint8_t r[3 * kSlotBytes + 1] = {0};
+            (void)hipMemcpy(r, p + (size_t)first * kRecLdp + kSlotBase, sizeof r, hipMemcpyDeviceToHost);
+            return terr(t, ETHCNN_ERR_FORMAT, "record %ld: slot QPs %d %d %d %d differ from record 0's %d %d %d %d", first, r[0],
+                        r[kSlotBytes], r[2 * kSlotBytes], r[3 * kSlotBytes], sq[0], sq[1], sq[2], sq[3]);
+        }
+    }
+    if (t->data[set]) (void)hipFree(t->data[set]);
+    if (t->net == ETHCNN_TRAIN_NET_LDP) {
+        for (int q = 0; q < 52; ++q) t->slot_of_qp[set][q] = -1;
+        for (int q = 0; q < 4; ++q) {
+            t->slot_qps[set][q] = sq[q];
+            t->slot_of_qp[set][sq[q]] = q;
+        }
+        if (set == ETHCNN_TRAIN_SET_TRAIN) {  // the QP list defaults to the four slots (every MODEL_TYPE trains on all of them)
+            std::memcpy(t->qps, sq, sizeof(int) * 4);
+            t->nqps = 4;
+        }
+    }
+    t->data[set] = p;
+    t->nrec[set] = n;
+    return 0;
+}
+
 extern "C" int ethcnn_train_set_samples(ethcnn_trainer* t, int set, const uint8_t* rec, size_t nbytes) {
     if (!t) return ETHCNN_ERR_ARG;
     if (set != 0 && set != 1) return terr(t, ETHCNN_ERR_ARG, "set must be 0 (train) or 1 (valid), got %d", set);
@@ -426,43 +469,46 @@ extern "C" int ethcnn_train_set_samples(ethcnn_trainer* t, int set, const uint8_
         (void)hipFree(p);
         return terr(t, ETHCNN_ERR_DEVICE, "sample upload failed");
     }
-    const int64_t n = (int64_t)(nbytes / rb);
-    if (t->net == ETHCNN_TRAIN_NET_LDP) {  // every record carries record 0's slot QPs (one pass on the device)
-        const int nblk = (int)std::min<int64_t>(1024, (n + 255) / 256);
-        long* d_bad = nullptr;
-        std::vector<long> bad((size_t)nblk);
-        const uint32_t want = (uint32_t)sq[0] | (uint32_t)sq[1] << 8 | (uint32_t)sq[2] << 16 | (uint32_t)sq[3] << 24;
-        hipError_t e = hipMalloc(&d_bad, sizeof(long) * nblk);
-        if (e == hipSuccess) {
-            launch_check_slots(t->c->stream, (const uint8_t*)p, (long)n, want, d_bad, nblk);
-            e = hipGetLastError();
+    const int rc = install_samples(t, set, (uint8_t*)p, (int64_t)(nbytes / rb), sq);
+    if (rc) (void)hipFree(p);
+    return rc;
+}
+
+// the same from a sample set already in HBM (include/ethcnn.h "sample sets"): adopted (take) or copied device to device
+extern "C" int ethcnn_train_set_samples_from(ethcnn_trainer* t, int set, ethcnn_samples* sm, int take) {
+    if (!t) return ETHCNN_ERR_ARG;
+    if (set != 0 && set != 1) return terr(t, ETHCNN_ERR_ARG, "set must be 0 (train) or 1 (valid), got %d", set);
+    if (!sm || !sm->built || sm->count == 0) return terr(t, ETHCNN_ERR_ARG, "no sample records (the sample set is not built or empty)");
+    if (sm->c != t->c) return terr(t, ETHCNN_ERR_ARG, "the sample set and the trainer live on different contexts");
+    if (sm->kind != t->net)
+        return terr(t, ETHCNN_ERR_FORMAT, "a sample set of %d-byte records does not feed this trainer's net (%d-byte records)",
+                    sm->record_bytes(), t->net == ETHCNN_TRAIN_NET_LDP ? kRecLdp : kRec);
+    if (sm->count > 0x7fffffffll) return terr(t, ETHCNN_ERR_ARG, "more than 2^31 - 1 records");
+    TCHK(t, hipSetDevice(t->c->device));
+    TCHK(t, hipStreamSynchronize(t->c->stream));
+    const size_t nbytes = (size_t)sm->count * (size_t)sm->record_bytes();
+    uint8_t* p = sm->data;
+    if (!take) {
+        if (hipMalloc((void**)&p, nbytes) != hipSuccess) {
+            (void)hipGetLastError();
+            return terr(t, ETHCNN_ERR_NOMEM, "%zu bytes of samples do not fit in device memory", nbytes);
         }
-        if (e == hipSuccess) e = hipMemcpyAsync(bad.data(), d_bad, sizeof(long) * nblk, hipMemcpyDeviceToHost, t->c->stream);
-        if (e == hipSuccess) e = hipStreamSynchronize(t->c->stream);
-        (void)hipFree(d_bad);
-        if (e != hipSuccess) {
+        if (hipMemcpy(p, sm->data, nbytes, hipMemcpyDeviceToDevice) != hipSuccess) {
             (void)hipFree(p);
-            return terr(t, ETHCNN_ERR_DEVICE, "sample check: %s", hipGetErrorString(e));
-        }
-        const long first = *std::min_element(bad.begin(), bad.end());
-        if (first < n) {
-            (void)hipFree(p);
-            const uint8_t* r = rec + (size_t)first * kRecLdp + kSlotBase;
-            return terr(t, ETHCNN_ERR_FORMAT, "record %ld: slot QPs %d %d %d %d differ from record 0's %d %d %d %d", first, r[0],
-                        r[kSlotBytes], r[2 * kSlotBytes], r[3 * kSlotBytes], sq[0], sq[1], sq[2], sq[3]);
-        }
-        for (int q = 0; q < 52; ++q) t->slot_of_qp[set][q] = -1;
-        for (int q = 0; q < 4; ++q) {
-            t->slot_qps[set][q] = sq[q];
-            t->slot_of_qp[set][sq[q]] = q;
-        }
-        if (set == ETHCNN_TRAIN_SET_TRAIN) {  // the QP list defaults to the four slots (every MODEL_TYPE trains on all of them)
-            std::memcpy(t->qps, sq, sizeof sq);
-            t->nqps = 4;
+            return terr(t, ETHCNN_ERR_DEVICE, "sample copy failed");
         }
     }
-    t->data[set] = (uint8_t*)p;
-    t->nrec[set] = n;
+    const int rc = install_samples(t, set, p, sm->count, sm->qps);
+    if (rc) {
+        if (!take) (void)hipFree(p);
+        return rc;
+    }
+    if (take) {  // the trainer owns the buffer now; the set is empty (and may take sequences again)
+        sm->data = nullptr;
+        sm->count = 0;
+        sm->seqs.clear();
+        sm->built = false;
+    }
     return 0;
 }
 

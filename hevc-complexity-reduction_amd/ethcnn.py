@@ -24,6 +24,7 @@ _DBG_WIDTH = {DBG_FEATURES: NFEAT, DBG_FC1: NVEC, DBG_FC2: NFC2, DBG_LOGITS: NOU
 
 
 ERR_ROWS_TIMEOUT, ERR_PLAN_REFUSED = -7, -8  # include/ethcnn.h
+ERR_ARG, ERR_IO, ERR_FORMAT, ERR_DEVICE, ERR_NOMEM = -1, -2, -3, -4, -6
 
 
 def fast_plan_bound(blob, plan, lib=None):
@@ -156,6 +157,18 @@ SIGNATURES = {
     "ethcnn_lstm_train_debug_fetch": (_i, [_vp, _i, _fp, _sz]),
     "ethcnn_lstm_train_debug_rows": (ctypes.c_int64, [_vp]),
     "ethcnn_lstm_train_last_error": (_cp, [_vp]),
+    "ethcnn_samples_create": (_i, [_vp, _i, ctypes.POINTER(ctypes.c_int), _i, _i, ctypes.c_uint64, ctypes.POINTER(_vp)]),
+    "ethcnn_samples_destroy": (None, [_vp]),
+    "ethcnn_samples_last_error": (_cp, [_vp]),
+    "ethcnn_samples_add_sequence": (_i, [_vp, _i, _i, ctypes.POINTER(ctypes.c_char_p), _i, ctypes.POINTER(ctypes.c_char_p), _i]),
+    "ethcnn_samples_count": (ctypes.c_int64, [_vp]),
+    "ethcnn_samples_record_bytes": (_i, [_vp]),
+    "ethcnn_samples_build": (_i, [_vp]),
+    "ethcnn_samples_cut_device": (_i, [_vp, _i, ctypes.POINTER(ctypes.c_int), _i, _i, _i, _i, ctypes.POINTER(_vp), ctypes.POINTER(_pd),
+                                       ctypes.POINTER(_pd), ctypes.POINTER(_vp), _i, _i, _vp, ctypes.c_int64]),
+    "ethcnn_samples_read": (_i, [_vp, ctypes.c_int64, ctypes.c_int64, _i, ctypes.c_uint64, _vp]),
+    "ethcnn_samples_write": (_i, [_vp, _cp, _i, ctypes.c_uint64]),
+    "ethcnn_train_set_samples_from": (_i, [_vp, _i, _vp, _i]),
 }
 
 _lib = None
@@ -730,9 +743,13 @@ class Trainer(object):
                                                  BLOB_FLOATS))
         return (blob, acc) if with_accum else blob
 
-    def set_samples(self, which, records):
+    def set_samples(self, which, records, take=False):
         """records: bytes / uint8 array of whole 4992-byte records (LDP: 16516-byte records), one sample file of the reference's
-        Extract_Data"""
+        Extract_Data; or a built SampleSet, which stays in HBM (take=True: the trainer adopts its buffer and the set becomes empty,
+        else a device-to-device copy)"""
+        if isinstance(records, SampleSet):
+            self._chk(self.lib.ethcnn_train_set_samples_from(self.h, int(which), records.h, 1 if take else 0))
+            return
         buf = np.frombuffer(records, dtype=np.uint8) if isinstance(records, (bytes, bytearray)) else np.ascontiguousarray(records, np.uint8)
         self._chk(self.lib.ethcnn_train_set_samples(self.h, int(which), buf.ctypes.data if buf.size else None, buf.size))
 
@@ -778,6 +795,129 @@ class Trainer(object):
         out = np.empty(n, dtype=np.float32)
         self._chk(self.lib.ethcnn_train_debug_fetch(self.h, int(which), out.ctypes.data_as(_fp), n))
         return out
+
+
+# ------------------------------------------------------------------------------------------------------------ sample sets ---
+SAMPLES_AI, SAMPLES_INTER = 0, 1
+ORDER_ENCODE, ORDER_RA = 0, 1
+SAMPLE_BYTES = {SAMPLES_AI: 4992, SAMPLES_INTER: 16516}
+PERMUTE_STREAM = 7
+
+
+def _draw(seed, stream, step, slot, unit):
+    return _mix64(_mix64(_mix64((seed ^ stream * 0xD1B54A32D192ED03) & _M64) ^ step) ^ ((slot << 12 | unit) & _M64))
+
+
+def sample_permutation(seed, count):
+    """perm(0 .. count-1) of include/ethcnn.h "sample sets": shuffled record j is record perm[j]"""
+    seed, count = int(seed) & _M64, int(count)
+    half = 1
+    while 4 ** half < count:
+        half += 1
+    mask = (1 << half) - 1
+    out = np.empty(count, dtype=np.int64)
+    for j in range(count):
+        x = j
+        while True:
+            l, r = x >> half, x & mask
+            for rnd in range(4):
+                l, r = r, l ^ (_draw(seed, PERMUTE_STREAM, count, r, rnd) & mask)
+            x = l << half | r
+            if x < count:
+                break
+        out[j] = x
+    return out
+
+
+def cut_device(ctx, kind, qps, width, height, nframes, d_luma, pitch, frame_stride, d_labels, d_records, record_offset=0, frame_number=0,
+               seq_number=0):
+    """ethcnn_samples_cut_device: the cut kernel on frames in HBM.  d_luma / pitch / frame_stride: one entry (All-Intra) or four
+    (inter slots); d_labels: one device address per QP; all addresses as integers (DeviceBuffer.ptr.value plus an offset)."""
+    n, nq = len(d_luma), len(qps)
+    rc = ctx.lib.ethcnn_samples_cut_device(ctx.h, int(kind), (ctypes.c_int * nq)(*[int(q) for q in qps]), nq, int(width), int(height),
+                                           int(nframes), (_vp * n)(*[int(p) for p in d_luma]), (_pd * n)(*[int(p) for p in pitch]),
+                                           (_pd * n)(*[int(p) for p in frame_stride]), (_vp * nq)(*[int(p) for p in d_labels]),
+                                           int(frame_number), int(seq_number), int(d_records), int(record_offset))
+    if rc:
+        raise EthCnnError(rc, ctx.lib.ethcnn_last_error(ctx.h).decode())
+
+
+class SampleSet(object):
+    """The trainers' sample records, cut out of YUV and label files into HBM (include/ethcnn.h "sample sets").
+    kind "ai": 4992-byte records from one YUV and one *_CUDepth.dat per QP; kind "inter" (LDP / LDB / RA): 16516-byte records from four
+    residual YUVs and four label files, order="ra" for the Random-Access frame table.  ctx=None validates and counts only."""
+
+    def __init__(self, ctx, kind="ai", qps=(22, 27, 32, 37), order="encode", max_bytes=0, lib=None):
+        self.ctx, self.lib = ctx, (ctx.lib if ctx is not None else (lib or load_library()))
+        kinds, orders = {"ai": SAMPLES_AI, "inter": SAMPLES_INTER}, {"encode": ORDER_ENCODE, "ra": ORDER_RA}
+        self.kind = kinds[kind] if kind in kinds else int(kind)
+        self.qps = [int(q) for q in qps]
+        h = ctypes.c_void_p()
+        rc = self.lib.ethcnn_samples_create(ctx.h if ctx is not None else None, self.kind, (ctypes.c_int * len(self.qps))(*self.qps),
+                                            len(self.qps), orders[order] if order in orders else int(order), int(max_bytes), ctypes.byref(h))
+        if rc:
+            raise EthCnnError(rc, self.lib.ethcnn_last_error(ctx.h).decode() if ctx is not None else "bad sample-set arguments")
+        self.h = h
+        if ctx is not None:
+            if not hasattr(ctx, "_trainers"):
+                ctx._trainers = weakref.WeakSet()
+            ctx._trainers.add(self)  # closed with the context, before it
+
+    def _chk(self, rc):
+        if rc:
+            raise EthCnnError(rc, self.lib.ethcnn_samples_last_error(self.h).decode())
+
+    def close(self):
+        if getattr(self, "h", None):
+            self.lib.ethcnn_samples_destroy(self.h)
+            self.h = None
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+    def __enter__(self):
+        return self
+
+    def __exit__(self, *a):
+        self.close()
+
+    def add_sequence(self, width, height, yuv, labels):
+        """yuv: the YUV path (All-Intra) or the four residual paths; labels: one *_CUDepth.dat path per QP, in QP-list order"""
+        yuv = [yuv] if isinstance(yuv, (str, bytes, os.PathLike)) else list(yuv)
+        y = [os.fsencode(p) for p in yuv]
+        lab = [os.fsencode(p) for p in labels]
+        self._chk(self.lib.ethcnn_samples_add_sequence(self.h, int(width), int(height), (ctypes.c_char_p * len(y))(*y), len(y),
+                                                       (ctypes.c_char_p * len(lab))(*lab), len(lab)))
+
+    @property
+    def count(self):
+        return int(self.lib.ethcnn_samples_count(self.h))
+
+    def __len__(self):
+        return self.count
+
+    @property
+    def record_bytes(self):
+        return int(self.lib.ethcnn_samples_record_bytes(self.h))
+
+    def build(self):
+        self._chk(self.lib.ethcnn_samples_build(self.h))
+        return self
+
+    def read(self, first=0, n=None, seed=None):
+        """records [first, first + n) as a uint8 array [n, record_bytes]; seed: of the set permuted by that seed"""
+        n = self.count - first if n is None else int(n)
+        out = np.empty((n, self.record_bytes), dtype=np.uint8)
+        self._chk(self.lib.ethcnn_samples_read(self.h, int(first), n, 0 if seed is None else 1, 0 if seed is None else int(seed) & _M64,
+                                               out.ctypes.data if n else None))
+        return out
+
+    def write(self, path, seed=None):
+        """the set as a sample file; seed: the "_shuffled" form, permuted by that seed"""
+        self._chk(self.lib.ethcnn_samples_write(self.h, os.fsencode(path), 0 if seed is None else 1, 0 if seed is None else int(seed) & _M64))
 
 
 # ------------------------------------------------------------------------------------------------------- ETH-LSTM training ---

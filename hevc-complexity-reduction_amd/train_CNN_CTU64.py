@@ -27,6 +27,10 @@ _ROOT = os.path.dirname(_HERE)
 if _ROOT not in sys.path:
     sys.path.insert(0, _ROOT)
 sys.path.insert(0, os.path.join(_ROOT, "tools"))
+if _HERE not in sys.path:
+    sys.path.insert(0, _HERE)
+
+import sequence_table  # noqa: E402
 
 REC = 4992
 # input_data.py:39-55: MODEL_TYPE -> (MODEL_NAME, SELECT_QP_LIST)
@@ -123,8 +127,9 @@ def train_loop(a, pkg, tr, name, ntrain, nvalid, evaluate, export=None, num_eval
 
 def parse_args(argv):
     ap = argparse.ArgumentParser(description=__doc__.split("\n\n")[0])
-    ap.add_argument("--train", required=True, help="training sample file (4992-byte records)")
-    ap.add_argument("--valid", required=True, help="validation sample file")
+    ap.add_argument("--train", help="training sample file (4992-byte records)")
+    ap.add_argument("--valid", help="validation sample file")
+    sequence_table.add_video_args(ap)
     g = ap.add_mutually_exclusive_group()
     g.add_argument("--model-type", type=int, choices=sorted(MODEL_TYPES), default=1)
     g.add_argument("--qp", type=int, help="train one QP (model name qp<QP>)")
@@ -152,20 +157,34 @@ def main(argv=None):
         name, qps = "qp%d" % a.qp, [a.qp]
     else:
         name, qps = MODEL_TYPES[a.model_type]
-    train, valid = load_records(a.train), load_records(a.valid)
-    ntrain, nvalid = train.size // REC, valid.size // REC
+    sequence_table.check_source(a)
     os.makedirs(a.models, exist_ok=True)
     ctx = pkg.EthCnn(device=a.device)
     tr = pkg.Trainer(ctx, batch=a.batch, lr=a.lr, momentum=a.momentum, decay_rate=a.decay_rate, decay_steps=a.decay_steps,
                      dropout=not a.no_dropout, seed=a.seed)
-    tr.set_samples(pkg.ethcnn.SET_TRAIN, train)
-    tr.set_samples(pkg.ethcnn.SET_VALID, valid)
+    labels = {}  # set -> [samples, 16] depth bytes at the model's QP
+    if a.yuv_dir:  # both sets cut in HBM and adopted by the trainer: no sample file, no host copy of a record
+        di = sequence_table
+        for which, lst, key in ((pkg.ethcnn.SET_TRAIN, a.sequences, "train"), (pkg.ethcnn.SET_VALID, a.valid_sequences or a.sequences, "valid")):
+            rows = []
+            with pkg.SampleSet(ctx, "ai", qps) as sset:
+                for sname, w, h in di.select(lst, di.AI_INDEX, key):
+                    info = [di.info_file(a.info_dir, sname, q) for q in qps]
+                    sset.add_sequence(w, h, di.find_one(a.yuv_dir, sname + ".yuv"), info)
+                    rows.append(di.ctu_labels(info[0], w, h))
+                tr.set_samples(which, sset.build(), take=True)
+            labels[which] = np.concatenate(rows)
+    else:
+        for which, path in ((pkg.ethcnn.SET_TRAIN, a.train), (pkg.ethcnn.SET_VALID, a.valid)):
+            data = load_records(path)
+            tr.set_samples(which, data)
+            labels[which] = np.asarray(data).reshape(-1, REC)[:, 4160 + 16 * qps[0]: 4176 + 16 * qps[0]]
+    ntrain, nvalid = len(labels[pkg.ethcnn.SET_TRAIN]), len(labels[pkg.ethcnn.SET_VALID])
     tr.set_qps(qps)
 
     def evaluate(which, idx):  # one ONE-batch evaluation at the model's QP -> (loss, accuracy, probs, labels)
-        data = train if which == pkg.ethcnn.SET_TRAIN else valid
         l3, a3, probs = tr.evaluate(which, qps[0], idx=idx, want_probs=True)
-        return l3, a3, probs, np.asarray(data).reshape(-1, REC)[idx, 4160 + 16 * qps[0]: 4176 + 16 * qps[0]]
+        return l3, a3, probs, labels[which][idx]
 
     export = os.path.join(a.export_ai, pkg.ethcnn.model_name_for_qp(qps[0])) if a.export_ai else None
     train_loop(a, pkg, tr, name, ntrain, nvalid, evaluate, export)

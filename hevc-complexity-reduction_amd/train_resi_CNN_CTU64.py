@@ -24,6 +24,7 @@ _HERE = os.path.dirname(os.path.abspath(__file__))
 if _HERE not in sys.path:
     sys.path.insert(0, _HERE)
 import train_CNN_CTU64 as ai  # noqa: E402  (also puts the repository root and tools/ on sys.path)
+import sequence_table as di  # noqa: E402
 
 REC = 16516
 SLOT_BASE, SLOT_BYTES = 64, 4113
@@ -34,8 +35,10 @@ EXPORT_NAME = "model_LDP_2000000_qp22~37.dat"  # resi_to_cu_depth_LDP.py:158-159
 
 def parse_args(argv):
     ap = argparse.ArgumentParser(description=__doc__.split("\n\n")[0])
-    ap.add_argument("--train", required=True, help="training sample file (16516-byte records)")
-    ap.add_argument("--valid", required=True, help="validation sample file")
+    ap.add_argument("--train", help="training sample file (16516-byte records)")
+    ap.add_argument("--valid", help="validation sample file")
+    di.add_video_args(ap)
+    ap.add_argument("--qps", type=int, nargs=4, default=list(di.QP_LIST), help="with --yuv-dir: the four slot QPs")
     ap.add_argument("--model-type", type=int, choices=sorted(MODEL_TYPES), default=0)
     ap.add_argument("--partly-tuning-mode", type=int, choices=(0, 1, 2, 3), default=0)
     ap.add_argument("--iters", type=int, default=1000000)
@@ -57,21 +60,33 @@ def main(argv=None):
     a = parse_args(argv)
     pkg = importlib.import_module("hevc-complexity-reduction_amd")
     name = MODEL_TYPES[a.model_type]
-    train, valid = ai.load_records(a.train, REC), ai.load_records(a.valid, REC)
-    ntrain, nvalid = train.size // REC, valid.size // REC
+    di.check_source(a)
     os.makedirs(a.models, exist_ok=True)
     ctx = pkg.EthCnn(device=a.device)
     tr = pkg.Trainer(ctx, batch=a.batch, lr=a.lr, momentum=a.momentum, decay_rate=a.decay_rate, decay_steps=a.decay_steps,
                      dropout=not a.no_dropout, seed=a.seed, net="ldp", tune=a.partly_tuning_mode)
-    tr.set_samples(pkg.ethcnn.SET_TRAIN, train)  # the QP list becomes the four slot QPs
-    tr.set_samples(pkg.ethcnn.SET_VALID, valid)
+    labels = {}  # set -> [samples, 4 slots, 16] depth bytes
+    if a.yuv_dir:  # both sets cut in HBM and adopted by the trainer: no sample file, no host copy of a record
+        for which, lst, key in ((pkg.ethcnn.SET_TRAIN, a.sequences, "train"), (pkg.ethcnn.SET_VALID, a.valid_sequences or a.sequences, "valid")):
+            rows = []
+            with pkg.SampleSet(ctx, "inter", a.qps) as sset:
+                for sname, w, h in di.select(lst, di.INTER_INDEX, key):
+                    info = [di.info_file(a.info_dir, sname, q) for q in a.qps]
+                    sset.add_sequence(w, h, [di.resi_file(a.yuv_dir, sname, q) for q in a.qps], info)
+                    rows.append(np.stack([di.ctu_labels(p, w, h, first_frame=1) for p in info], axis=1))
+                tr.set_samples(which, sset.build(), take=True)  # the QP list becomes the four slot QPs
+            labels[which] = np.concatenate(rows)
+    else:
+        for which, path in ((pkg.ethcnn.SET_TRAIN, a.train), (pkg.ethcnn.SET_VALID, a.valid)):
+            data = ai.load_records(path, REC)
+            tr.set_samples(which, data)  # the QP list becomes the four slot QPs
+            slots = np.asarray(data).reshape(-1, REC)[:, SLOT_BASE:].reshape(-1, 4, SLOT_BYTES)
+            labels[which] = slots[:, :, 1:17]
+    ntrain, nvalid = len(labels[pkg.ethcnn.SET_TRAIN]), len(labels[pkg.ethcnn.SET_VALID])
 
     def evaluate(which, idx):  # ONE batch, each sample at its drawn slot -> (loss, accuracy, probs, labels)
-        data = np.asarray(train if which == pkg.ethcnn.SET_TRAIN else valid).reshape(-1, REC)
         l3, a3, probs = tr.evaluate(which, -1, idx=idx, want_probs=True)
-        lab0 = SLOT_BASE + SLOT_BYTES * pkg.ethcnn.mixed_eval_slots(a.seed, len(idx)) + 1
-        labels = data[np.asarray(idx)[:, None], lab0[:, None] + np.arange(16)]
-        return l3, a3, probs, labels
+        return l3, a3, probs, labels[which][np.asarray(idx), pkg.ethcnn.mixed_eval_slots(a.seed, len(idx))]
 
     export = os.path.join(a.export_ldp, EXPORT_NAME) if a.export_ldp else None
     ai.train_loop(a, pkg, tr, name, ntrain, nvalid, evaluate, export)

@@ -517,6 +517,66 @@ int ethcnn_lstm_train_debug_fetch(ethcnn_lstm_trainer* tr, int which, float* out
 int64_t ethcnn_lstm_train_debug_rows(const ethcnn_lstm_trainer* tr); /* `rows` of the per-row debug buffers right now */
 const char* ethcnn_lstm_train_last_error(const ethcnn_lstm_trainer* tr);
 
+/* ---- sample sets (Extract_Data/extract_data_AI.py:94-170, extract_data_LDP_LDB_RA.py:68-208): the trainers' sample records cut out of
+ *      YUV and label files into HBM, handed to a trainer there, or written as the reference's sample files, byte for byte.
+ *   Samples are the WHOLE 64 x 64 CTUs of a frame, (height / 64) x (width / 64) of them in raster order (the ragged right and bottom
+ *      edges are dropped, not padded); records follow in the order sequence (as added), frame, CTU.
+ *   Label files (*_CUDepth.dat): one byte per 16 x 16 block, (height / 16) x (width / 16) per frame, raster, frames in file order.
+ *   ETHCNN_SAMPLES_AI: the 4992-byte record of "training" above, every byte 255 except the luma at 0 and, for each QP q of the list,
+ *      the CTU's 4 x 4 depth bytes (raster) at 4160 + 16 q.  One YUV per sequence, one label file per QP, every frame of the file.
+ *   ETHCNN_SAMPLES_INTER (Low-Delay-P, Low-Delay-B, Random-Access): the 16516-byte record, every byte 255 except header byte 0 = 1,
+ *      2-3 width, 4-5 height, 10-13 frame number in encoding order, 14-15 CTU line, 16-17 CTU column, 18-19 the sequence's position in
+ *      the order of the add calls (little-endian), and slot s at 64 + 4113 s = [qps[s] | 16 depth bytes | 4096 residual bytes], the
+ *      residual from the s-th residual file.  Four QPs, four residual YUVs and four label files per sequence.  Frames 1 .. n-1 in
+ *      encoding order (the initial I-frame is skipped).  The frame READ from the files for frame i in encoding order is i itself
+ *      (ETHCNN_SAMPLES_ORDER_ENCODE: LDP, LDB) or, ETHCNN_SAMPLES_ORDER_RA, 1 + T[(i - 1) % 8] + 8 g with g = (i - 1) / 8 and T =
+ *      (7 3 1 0 2 5 4 6) without the entries >= min(n - 1 - 8 g, 8) -- the shortened table of a last GOP of fewer than 8 frames.
+ *   The permutation (shuffled reads and files): record j of the output is record perm(j) of the set, with, for count records,
+ *      h = the smallest integer >= 1 with 4^h >= count, mask = 2^h - 1, and draw() of "training" above on stream 7:
+ *        x = j; repeat { l = x >> h; r = x & mask; for round = 0..3: (l, r) = (r, l ^ (draw(7, count, r, round) & mask)); x = l << h | r }
+ *        until x < count; perm(j) = x
+ *      (a four-round Feistel network over 2 h bits, cycle-walked into [0, count): a bijection fixed by (seed, count), computed per
+ *      record; the reference's own shuffle is Python's unseeded random.sample and is not reproduced.)
+ *   A set belongs to a context (its device, stream and fill threads); ctx == NULL gives a set that validates and counts only. */
+typedef struct ethcnn_samples ethcnn_samples;
+enum { ETHCNN_SAMPLES_AI = 0, ETHCNN_SAMPLES_INTER = 1 };
+enum { ETHCNN_SAMPLES_ORDER_ENCODE = 0, ETHCNN_SAMPLES_ORDER_RA = 1 };
+/* qps: All-Intra 1..52 distinct QPs in 0..51; inter exactly four distinct, in slot order.  max_bytes: the largest set
+ * ethcnn_samples_build may allocate, 0 = no limit of its own. */
+int ethcnn_samples_create(ethcnn_ctx* ctx /* may be NULL */, int kind, const int* qps, int nqps, int frame_order, uint64_t max_bytes,
+                          ethcnn_samples** out);
+void ethcnn_samples_destroy(ethcnn_samples* set); /* before ethcnn_destroy of its context */
+const char* ethcnn_samples_last_error(const ethcnn_samples* set);
+/* Validates and counts, nothing more.  nyuv = 1 (All-Intra) or 4 (inter: the residual file of each slot), nlabels = the QP count, label
+ * paths in QP-list order.  ETHCNN_ERR_FORMAT, with the file named: width or height below 64 or not a multiple of 8, a YUV that is not a
+ * whole number of 4:2:0 frames, residual files of different frame counts, a label file whose size is not frames x (h / 16) x (w / 16).
+ * ETHCNN_ERR_IO: a file that cannot be examined. */
+int ethcnn_samples_add_sequence(ethcnn_samples* set, int width, int height, const char* const* yuv_paths, int nyuv,
+                                const char* const* label_paths, int nlabels);
+int64_t ethcnn_samples_count(const ethcnn_samples* set); /* records of the sequences added so far */
+int ethcnn_samples_record_bytes(const ethcnn_samples* set);
+/* One allocation of count x record_bytes in HBM (ETHCNN_ERR_NOMEM, with the byte count, when it does not fit or exceeds max_bytes;
+ * nothing is allocated then), filled sequence by sequence, a bounded number of frames at a time: luma and label planes are read by the
+ * context's fill threads into page-locked staging (chroma is never read), copied to HBM and cut into records by the kernel while the next
+ * frames are read.  Synchronous.  Once; sequences cannot be added afterwards. */
+int ethcnn_samples_build(ethcnn_samples* set);
+/* The kernel alone, on frames already in HBM: `nframes` frames of d_luma[p] (p = 0, or the four slots; `pitch[p]` bytes between rows,
+ * `frame_stride[p]` between frames) and of d_labels[q] (one per QP of the list, frames packed) become records record_offset .. of
+ * d_records (16-byte aligned, inter: 4-byte), frame f with frame number frame_number + f (inter header).  Any alignment of the luma
+ * pointers and pitches gives the same bytes (16-byte aligned ones take the wide loads).  Asynchronous on the context's stream. */
+int ethcnn_samples_cut_device(ethcnn_ctx* ctx, int kind, const int* qps, int nqps, int width, int height, int nframes,
+                              const uint8_t* const* d_luma, const ptrdiff_t* pitch, const ptrdiff_t* frame_stride,
+                              const uint8_t* const* d_labels, int frame_number, int seq_number, uint8_t* d_records, int64_t record_offset);
+/* records [first, first + n) of the built set (permuted != 0: of its permutation by `seed`) -> host memory */
+int ethcnn_samples_read(ethcnn_samples* set, int64_t first, int64_t n, int permuted, uint64_t seed, uint8_t* out);
+/* the whole set as a sample file (temp file + rename: never a partial file); permuted != 0: the "_shuffled" form */
+int ethcnn_samples_write(ethcnn_samples* set, const char* path, int permuted, uint64_t seed);
+/* A built set becomes set 0 / 1 of a trainer of the same context without leaving HBM.  ETHCNN_ERR_FORMAT when the kind does not match
+ * the trainer's net; for the LDP net the slot-QP pass of ethcnn_train_set_samples runs on the device copy and the QP list defaults to
+ * the four slots, as there.  take != 0: the trainer adopts the buffer and the set becomes empty (0 records, not built); else a
+ * device-to-device copy. */
+int ethcnn_train_set_samples_from(ethcnn_trainer* tr, int set_index, ethcnn_samples* set, int take);
+
 #ifdef __cplusplus
 }
 #endif
