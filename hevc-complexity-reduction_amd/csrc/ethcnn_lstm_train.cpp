@@ -10,6 +10,7 @@
 #include <vector>
 
 #include "ethcnn_ctx.h"
+#include "ethcnn_lstm_samples.h"
 #include "ethcnn_lstm_train.h"
 
 using namespace ethcnn::lstm_train;
@@ -340,6 +341,23 @@ extern "C" int ethcnn_lstm_train_set_qps(ethcnn_lstm_trainer* t, const int* qps,
     return 0;
 }
 
+// the pass every kept sample takes on the device (k_lstm_check): *first = the first sample that fails it, n when none does
+static hipError_t first_bad_sample(ethcnn_lstm_trainer* t, const uint8_t* p, size_t n, long* first) {
+    const int nblk = (int)std::min<size_t>(1024, n);
+    long* d_bad = nullptr;
+    std::vector<long> bad((size_t)nblk);
+    hipError_t e = hipMalloc(&d_bad, sizeof(long) * nblk);
+    if (e == hipSuccess) {
+        launch_check(t->c->stream, p, (long)n, d_bad, nblk);
+        e = hipGetLastError();
+    }
+    if (e == hipSuccess) e = hipMemcpyAsync(bad.data(), d_bad, sizeof(long) * nblk, hipMemcpyDeviceToHost, t->c->stream);
+    if (e == hipSuccess) e = hipStreamSynchronize(t->c->stream);
+    (void)hipFree(d_bad);
+    if (e == hipSuccess) *first = *std::min_element(bad.begin(), bad.end());
+    return e;
+}
+
 extern "C" int ethcnn_lstm_train_set_samples(ethcnn_lstm_trainer* t, int set, const uint8_t* rec, size_t nbytes) {
     if (!t) return ETHCNN_ERR_ARG;
     if (set != 0 && set != 1) return terr(t, ETHCNN_ERR_ARG, "set must be 0 (train) or 1 (valid), got %d", set);
@@ -373,22 +391,12 @@ extern "C" int ethcnn_lstm_train_set_samples(ethcnn_lstm_trainer* t, int set, co
         e = hipMemcpy((uint8_t*)p + j * kRecBytes, rec + keep[j] * kRecBytes, (k - j) * kRecBytes, hipMemcpyHostToDevice);
         j = k;
     }
-    const int nblk = (int)std::min<size_t>(1024, n);
-    long* d_bad = nullptr;
-    std::vector<long> bad((size_t)nblk);
-    if (e == hipSuccess) e = hipMalloc(&d_bad, sizeof(long) * nblk);
-    if (e == hipSuccess) {
-        launch_check(t->c->stream, (const uint8_t*)p, (long)n, d_bad, nblk);
-        e = hipGetLastError();
-    }
-    if (e == hipSuccess) e = hipMemcpyAsync(bad.data(), d_bad, sizeof(long) * nblk, hipMemcpyDeviceToHost, t->c->stream);
-    if (e == hipSuccess) e = hipStreamSynchronize(t->c->stream);
-    (void)hipFree(d_bad);
+    long first = 0;
+    if (e == hipSuccess) e = first_bad_sample(t, (const uint8_t*)p, n, &first);
     if (e != hipSuccess) {
         (void)hipFree(p);
         return terr(t, ETHCNN_ERR_DEVICE, "sample upload / check: %s", hipGetErrorString(e));
     }
-    const long first = *std::min_element(bad.begin(), bad.end());
     if (first < (long)n) {
         (void)hipFree(p);
         return terr(t, ETHCNN_ERR_FORMAT, "sample %zu: a QP outside 0..51, a label outside 0..3 or a non-finite vector element",
@@ -397,6 +405,88 @@ extern "C" int ethcnn_lstm_train_set_samples(ethcnn_lstm_trainer* t, int set, co
     if (t->data[set]) (void)hipFree(t->data[set]);
     t->data[set] = (uint8_t*)p;
     t->nrec[set] = (int64_t)n;
+    return 0;
+}
+
+// the same from an ETH-LSTM sample set already in HBM (include/ethcnn.h "ETH-LSTM sample sets"): the QP selection on the slot-0 QP
+// floats (the only bytes that leave HBM), then the buffer adopted (take, everything kept) or a compacting device-to-device copy
+extern "C" int ethcnn_lstm_train_set_samples_from(ethcnn_lstm_trainer* t, int set, ethcnn_lstm_samples* sm, int take) {
+    namespace ls = ethcnn::lstm_samples;
+    if (!t) return ETHCNN_ERR_ARG;
+    if (set != 0 && set != 1) return terr(t, ETHCNN_ERR_ARG, "set must be 0 (train) or 1 (valid), got %d", set);
+    if (!sm || !sm->built || sm->count == 0) return terr(t, ETHCNN_ERR_ARG, "no sample records (the sample set is not built or empty)");
+    if (sm->c != t->c) return terr(t, ETHCNN_ERR_ARG, "the sample set and the trainer live on different contexts");
+    const size_t nall = (size_t)sm->count;
+    hipStream_t s = t->c->stream;
+    TCHK(t, hipSetDevice(t->c->device));
+    TCHK(t, hipStreamSynchronize(s));
+    // SELECT_QP_LIST, as in ethcnn_lstm_train_set_samples
+    std::vector<int64_t> keep;
+    if (t->nqps) {
+        float* d_q = nullptr;
+        std::vector<float> q(nall);
+        hipError_t e = hipMalloc((void**)&d_q, nall * 4);
+        if (e == hipSuccess) {
+            ls::launch_qp0(s, sm->data, (long)nall, d_q);
+            e = hipGetLastError();
+        }
+        if (e == hipSuccess) e = hipMemcpyAsync(q.data(), d_q, nall * 4, hipMemcpyDeviceToHost, s);
+        if (e == hipSuccess) e = hipStreamSynchronize(s);
+        (void)hipFree(d_q);
+        if (e != hipSuccess) return terr(t, ETHCNN_ERR_DEVICE, "sample selection: %s", hipGetErrorString(e));
+        for (size_t i = 0; i < nall; ++i) {
+            bool on = false;
+            for (int k = 0; k < t->nqps && !on; ++k) on = q[i] == (float)t->qps[k];
+            if (on) keep.push_back((int64_t)i);
+        }
+        if (keep.empty()) return terr(t, ETHCNN_ERR_FORMAT, "none of the %zu samples has a selected QP", nall);
+    }
+    const bool all = !t->nqps || keep.size() == nall;
+    const size_t n = all ? nall : keep.size();
+    if (n > 0x7fffffffull / kSteps) return terr(t, ETHCNN_ERR_ARG, "too many samples");
+    uint8_t* p = sm->data;
+    const bool adopt = all && take;
+    if (!adopt) {
+        if (hipMalloc((void**)&p, n * kRecBytes) != hipSuccess) {
+            (void)hipGetLastError();
+            return terr(t, ETHCNN_ERR_NOMEM, "%zu bytes of samples do not fit in device memory", n * kRecBytes);
+        }
+        hipError_t e = hipSuccess;
+        int64_t* d_keep = nullptr;
+        if (all) {
+            e = hipMemcpyAsync(p, sm->data, n * kRecBytes, hipMemcpyDeviceToDevice, s);
+        } else {
+            e = hipMalloc((void**)&d_keep, n * 8);
+            if (e == hipSuccess) e = hipMemcpyAsync(d_keep, keep.data(), n * 8, hipMemcpyHostToDevice, s);
+            if (e == hipSuccess) {
+                ls::launch_compact(s, sm->data, d_keep, (long)n, p, t->c->cus > 0 ? t->c->cus : 256);
+                e = hipGetLastError();
+            }
+        }
+        if (e == hipSuccess) e = hipStreamSynchronize(s);
+        if (d_keep) (void)hipFree(d_keep);
+        if (e != hipSuccess) {
+            (void)hipFree(p);
+            return terr(t, ETHCNN_ERR_DEVICE, "sample copy: %s", hipGetErrorString(e));
+        }
+    }
+    long first = 0;
+    const hipError_t e = first_bad_sample(t, p, n, &first);
+    if (e != hipSuccess || first < (long)n) {
+        if (!adopt) (void)hipFree(p);
+        if (e != hipSuccess) return terr(t, ETHCNN_ERR_DEVICE, "sample check: %s", hipGetErrorString(e));
+        return terr(t, ETHCNN_ERR_FORMAT, "sample %lld: a QP outside 0..51, a label outside 0..3 or a non-finite vector element",
+                    (long long)(all ? (int64_t)first : keep[(size_t)first]));
+    }
+    if (t->data[set]) (void)hipFree(t->data[set]);
+    t->data[set] = p;
+    t->nrec[set] = (int64_t)n;
+    if (take) {  // the set is empty afterwards: its buffer is the trainer's now, or (after a compacting copy) is freed
+        if (!adopt) (void)hipFree(sm->data);
+        sm->data = nullptr;
+        sm->count = sm->skipped = 0;
+        sm->built = false;
+    }
     return 0;
 }
 

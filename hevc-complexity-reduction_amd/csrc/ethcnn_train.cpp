@@ -493,7 +493,10 @@ extern "C" int ethcnn_train_set_samples_from(ethcnn_trainer* t, int set, ethcnn_
             (void)hipGetLastError();
             return terr(t, ETHCNN_ERR_NOMEM, "%zu bytes of samples do not fit in device memory", nbytes);
         }
-        if (hipMemcpy(p, sm->data, nbytes, hipMemcpyDeviceToDevice) != hipSuccess) {
+        // (on the context's stream, which does not wait for the null stream: a device-to-device hipMemcpy there may still be
+        // running when the check below reads its destination)
+        if (hipMemcpyAsync(p, sm->data, nbytes, hipMemcpyDeviceToDevice, t->c->stream) != hipSuccess ||
+            hipStreamSynchronize(t->c->stream) != hipSuccess) {
             (void)hipFree(p);
             return terr(t, ETHCNN_ERR_DEVICE, "sample copy failed");
         }

@@ -24,7 +24,7 @@ _DBG_WIDTH = {DBG_FEATURES: NFEAT, DBG_FC1: NVEC, DBG_FC2: NFC2, DBG_LOGITS: NOU
 
 
 ERR_ROWS_TIMEOUT, ERR_PLAN_REFUSED = -7, -8  # include/ethcnn.h
-ERR_ARG, ERR_IO, ERR_FORMAT, ERR_DEVICE, ERR_NOMEM = -1, -2, -3, -4, -6
+ERR_ARG, ERR_IO, ERR_FORMAT, ERR_DEVICE, ERR_NOWEIGHTS, ERR_NOMEM = -1, -2, -3, -4, -5, -6
 
 
 def fast_plan_bound(blob, plan, lib=None):
@@ -169,6 +169,21 @@ SIGNATURES = {
     "ethcnn_samples_read": (_i, [_vp, ctypes.c_int64, ctypes.c_int64, _i, ctypes.c_uint64, _vp]),
     "ethcnn_samples_write": (_i, [_vp, _cp, _i, ctypes.c_uint64]),
     "ethcnn_train_set_samples_from": (_i, [_vp, _i, _vp, _i]),
+    "ethcnn_lstm_samples_plan": (_i, [_vp, _sz, ctypes.POINTER(ctypes.c_int64), ctypes.POINTER(ctypes.c_int64), ctypes.POINTER(ctypes.c_int64),
+                                      ctypes.POINTER(ctypes.c_int64)]),
+    "ethcnn_lstm_samples_create": (_i, [_vp, ctypes.POINTER(ctypes.c_int), _i, _i, ctypes.c_uint64, ctypes.POINTER(_vp)]),
+    "ethcnn_lstm_samples_destroy": (None, [_vp]),
+    "ethcnn_lstm_samples_last_error": (_cp, [_vp]),
+    "ethcnn_lstm_samples_build_from_set": (_i, [_vp, _vp]),
+    "ethcnn_lstm_samples_build_from_records": (_i, [_vp, _vp, _sz]),
+    "ethcnn_lstm_samples_count": (ctypes.c_int64, [_vp]),
+    "ethcnn_lstm_samples_skipped": (ctypes.c_int64, [_vp]),
+    "ethcnn_lstm_samples_read": (_i, [_vp, ctypes.c_int64, ctypes.c_int64, _vp]),
+    "ethcnn_lstm_samples_write": (_i, [_vp, _cp]),
+    "ethcnn_lstm_train_set_samples_from": (_i, [_vp, _i, _vp, _i]),
+    "ethcnn_bench_lstm_repack": (_i, [_vp, _vp, ctypes.c_int64, ctypes.c_int64, _i, _i, _vp]),
+    "ethcnn_bench_lstm_gather": (_i, [_vp, _vp, ctypes.c_int64, _vp, _vp, _vp, ctypes.c_int64, _i, _vp]),
+    "ethcnn_bench_copy": (_i, [_vp, _vp, _vp, _sz]),
 }
 
 _lib = None
@@ -1003,8 +1018,13 @@ class LstmTrainer(object):
         arr = (ctypes.c_int * max(1, len(qps)))(*[int(q) for q in qps])
         self._chk(self.lib.ethcnn_lstm_train_set_qps(self.h, arr, len(qps)))
 
-    def set_samples(self, which, records):
-        """records: bytes / uint8 array of whole 37264-byte samples (get_LSTM_input.py's output); returns the number kept"""
+    def set_samples(self, which, records, take=False):
+        """records: bytes / uint8 array of whole 37264-byte samples (get_LSTM_input.py's output), or a built LstmSampleSet, which
+        stays in HBM (take=True: the set is empty afterwards, and the trainer adopts its buffer when the QP selection keeps every
+        sample; else a device-to-device copy of the kept samples); returns the number kept"""
+        if isinstance(records, LstmSampleSet):
+            self._chk(self.lib.ethcnn_lstm_train_set_samples_from(self.h, int(which), records.h, 1 if take else 0))
+            return self.num_samples(which)
         buf = np.frombuffer(records, dtype=np.uint8) if isinstance(records, (bytes, bytearray)) else np.ascontiguousarray(records, np.uint8)
         self._chk(self.lib.ethcnn_lstm_train_set_samples(self.h, int(which), buf.ctypes.data if buf.size else None, buf.size))
         return self.num_samples(which)
@@ -1051,3 +1071,96 @@ class LstmTrainer(object):
         out = np.empty(n, dtype=np.float32)
         self._chk(self.lib.ethcnn_lstm_train_debug_fetch(self.h, int(which), out.ctypes.data_as(_fp), n))
         return out
+
+
+# ------------------------------------------------------------------------------------------------- ETH-LSTM sample sets ---
+LDP_RECORD_BYTES = 16516
+
+
+def lstm_samples_plan(records, lib=None):
+    """ethcnn_lstm_samples_plan on uint8 LDP records (host only): (heads [m], strides [m], skipped); time slot k of head j is record
+    heads[j] - k * strides[j]"""
+    lib = lib or load_library()
+    buf = np.frombuffer(records, dtype=np.uint8) if isinstance(records, (bytes, bytearray)) else np.ascontiguousarray(records, np.uint8)
+    n = buf.size // LDP_RECORD_BYTES
+    heads, strides = np.empty(max(n, 1), np.int64), np.empty(max(n, 1), np.int64)
+    m, skipped = ctypes.c_int64(), ctypes.c_int64()
+    p64 = ctypes.POINTER(ctypes.c_int64)
+    rc = lib.ethcnn_lstm_samples_plan(buf.ctypes.data if buf.size else None, buf.size, heads.ctypes.data_as(p64), strides.ctypes.data_as(p64),
+                                      ctypes.byref(m), ctypes.byref(skipped))
+    if rc:
+        raise EthCnnError(rc, "%d bytes is not a whole number of %d-byte records" % (buf.size, LDP_RECORD_BYTES))
+    return heads[:m.value].copy(), strides[:m.value].copy(), int(skipped.value)
+
+
+class LstmSampleSet(object):
+    """The ETH-LSTM trainer's 37264-byte samples, built in HBM from Low-Delay-P records with the residual CNN the context has loaded
+    (include/ethcnn.h "ETH-LSTM sample sets"): what get_LSTM_input.build_samples returns.  slots: the QP slots (0..3) to build, None =
+    all four; chunk_ctus: records per pass through the CNN (0 = default)."""
+
+    def __init__(self, ctx, slots=None, chunk_ctus=0, max_bytes=0):
+        self.ctx, self.lib = ctx, ctx.lib
+        sl = [] if slots is None else [int(q) for q in slots]
+        h = ctypes.c_void_p()
+        rc = self.lib.ethcnn_lstm_samples_create(ctx.h, (ctypes.c_int * max(1, len(sl)))(*sl), len(sl), int(chunk_ctus), int(max_bytes),
+                                                 ctypes.byref(h))
+        if rc:
+            raise EthCnnError(rc, self.lib.ethcnn_last_error(ctx.h).decode())
+        self.h = h
+        if not hasattr(ctx, "_trainers"):
+            ctx._trainers = weakref.WeakSet()
+        ctx._trainers.add(self)  # closed with the context, before it
+
+    def _chk(self, rc):
+        if rc:
+            raise EthCnnError(rc, self.lib.ethcnn_lstm_samples_last_error(self.h).decode())
+
+    def close(self):
+        if getattr(self, "h", None):
+            self.lib.ethcnn_lstm_samples_destroy(self.h)
+            self.h = None
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+    def __enter__(self):
+        return self
+
+    def __exit__(self, *a):
+        self.close()
+
+    def build_from(self, x):
+        """x: a built inter SampleSet (read in HBM, left as it is), a uint8 array / bytes of 16516-byte records, or the path of a
+        file of them"""
+        if isinstance(x, SampleSet):
+            self._chk(self.lib.ethcnn_lstm_samples_build_from_set(self.h, x.h))
+            return self
+        if isinstance(x, (str, os.PathLike)):
+            x = np.memmap(x, dtype=np.uint8, mode="r") if os.path.getsize(x) else np.empty(0, np.uint8)
+        buf = np.frombuffer(x, dtype=np.uint8) if isinstance(x, (bytes, bytearray)) else np.ascontiguousarray(x, np.uint8)
+        self._chk(self.lib.ethcnn_lstm_samples_build_from_records(self.h, buf.ctypes.data if buf.size else None, buf.size))
+        return self
+
+    @property
+    def count(self):
+        return int(self.lib.ethcnn_lstm_samples_count(self.h))
+
+    @property
+    def skipped(self):
+        return int(self.lib.ethcnn_lstm_samples_skipped(self.h))
+
+    def __len__(self):
+        return self.count
+
+    def read(self, first=0, n=None):
+        """samples [first, first + n) as a uint8 array [n, 37264]"""
+        n = self.count - first if n is None else int(n)
+        out = np.empty((n, LSTM_SAMPLE_BYTES), dtype=np.uint8)
+        self._chk(self.lib.ethcnn_lstm_samples_read(self.h, int(first), n, out.ctypes.data if n else None))
+        return out
+
+    def write(self, path):
+        self._chk(self.lib.ethcnn_lstm_samples_write(self.h, os.fsencode(path)))

@@ -6,7 +6,8 @@ ETH-LSTM_Training_LDP/get_LSTM_input.py, second stage of  ETH-CNN_Training_LDP -
 Input: 16516-byte LDP records (64 info bytes, then four QP slots of [QP byte | 16 depth bytes | 4096 residual bytes]); info bytes
 2-3 / 4-5 are the picture's width / height, 10-13 its frame number i_frame (little-endian).  --model is the residual CNN's checkpoint
 (train_resi_CNN_CTU64.py's model.dat or its --export-ldp file); its 448-vector h_fc1_64|32|16 of every slot's residual is computed
-on the GPU by EthCnn.resi_vectors, thousands of CTUs per call (tiled into one tall picture), not 100 at a time.
+on the GPU, thousands of CTUs per pass (tiled into one tall picture), not 100 at a time.  main builds the samples in HBM
+(LstmSampleSet, include/ethcnn.h "ETH-LSTM sample sets"); build_samples with gpu_vectors is the same definition on the host.
 
 Output <out>: 37264-byte samples = 64 info bytes + 20 time slots of 465 float32 [qp | 16 labels | 448 vector].  Definition: for each
 QP slot in turn, for each record r with i_frame >= 19 and i_frame % 10 == 0 (LSTM_OVERLAP_STRIDE), the record's info bytes with
@@ -104,9 +105,11 @@ def main(argv=None):
         raise SystemExit("%s: %d bytes is not a whole number of %d-byte records" % (a.input, data.size, REC_IN))
     ctx = pkg.EthCnn(device=a.device)
     ctx.load_checkpoint(a.model)
-    samples, skipped = build_samples(data, gpu_vectors(ctx))
+    with pkg.LstmSampleSet(ctx) as ls:  # build_samples(data, gpu_vectors(ctx)) with the records, vectors and samples in HBM
+        ls.build_from(data)
+        ls.write(a.out)
+        samples, skipped = ls.read(), ls.skipped
     ctx.close()
-    samples.tofile(a.out)
     shuffle_groups(samples, a.seed).tofile(a.out + "_shuffled")
     print("%d records -> %d samples (%d per QP); %d skipped (a reference before the start of the file)"
           % (data.size // REC_IN, len(samples), len(samples) // 4, skipped))

@@ -4,6 +4,7 @@ include/ethcnn.h "ETH-LSTM training"); this file only schedules, evaluates, logs
 
     python train_LSTM_CTU64.py --train LDP_Train.dat_lstm_4qps_shuffled --valid LDP_Valid.dat_lstm_4qps_shuffled --qp 32
     python train_LSTM_CTU64.py ... --qp 32 --qp-scale 0.18 --export-lstm HM-16.5_Test_LDP/bin   # model_LDP_200000_qp32.dat
+    python train_LSTM_CTU64.py --ldp-train LDP_Train.dat --ldp-valid LDP_Valid.dat --cnn-model Models/model.dat --qp 32
 
 Sample files: get_LSTM_input.py's output (37264-byte samples: 64 info bytes + 20 slots of [qp | 16 labels | 448-vector] float32).
 --qp keeps the samples whose slot-0 QP is that value (SELECT_QP_LIST, input_data.py:41-61,126-134; --model-type 1..4 = QP 22 / 27 /
@@ -14,6 +15,11 @@ clipped to global norm 5, 200000 steps; every 1000 steps an evaluation (no dropo
 from Models/model.dat and that log (momentum accumulators restart at zero, as the reference's Saver restore).
 --qp-scale: the QP feature is qp / 51 * qp_scale.  1.0 is the training script as shipped; the deployed one-step graph (lstm_step,
 both LDP daemons) computes qp / 51 * 0.18, so train with --qp-scale 0.18 for a model meant for them.
+--ldp-train / --ldp-valid / --cnn-model (instead of --train / --valid): the Low-Delay-P sample files (16516-byte records) themselves.
+The samples of --qp's slot alone are built in HBM with that residual CNN (LstmSampleSet: get_LSTM_input.py's samples, in its unshuffled
+order) and handed to the trainer there; no 37264-byte file is written or read.  The evaluation's labels come from the records.
+The slot of --qp, the slot QPs an error names and the "N of M samples" line are read from record 0; a file whose later records carry
+other QPs in that slot loses those samples to the trainer's own selection (M counts them, N does not).
 Not ported: the per-QP evaluation report (log_*.dat), the periodic swap of the in-memory training part (all samples are resident),
 plotting.
 """
@@ -36,8 +42,11 @@ NUM_PART, ITER_TIMES_PER_SAVE = 10000, 10000  # train_LSTM_CTU64.py:57-58,64
 
 def parse_args(argv):
     ap = argparse.ArgumentParser(description=__doc__.split("\n\n")[0])
-    ap.add_argument("--train", required=True, help="training sample file (37264-byte samples)")
-    ap.add_argument("--valid", required=True, help="validation sample file")
+    ap.add_argument("--train", help="training sample file (37264-byte samples)")
+    ap.add_argument("--valid", help="validation sample file")
+    ap.add_argument("--ldp-train", metavar="FILE", help="training LDP sample file (16516-byte records): samples built in HBM")
+    ap.add_argument("--ldp-valid", metavar="FILE", help="validation LDP sample file")
+    ap.add_argument("--cnn-model", metavar="PREFIX", help="residual CNN checkpoint for --ldp-train / --ldp-valid")
     g = ap.add_mutually_exclusive_group()
     g.add_argument("--model-type", type=int, choices=sorted(MODEL_TYPES), default=1)
     g.add_argument("--qp", type=int, help="train the model of one QP (model name qp<QP>)")
@@ -55,7 +64,39 @@ def parse_args(argv):
     ap.add_argument("--models", default="Models")
     ap.add_argument("--export-lstm", metavar="DIR", help="also write the final weights as the daemons' model_LDP_200000_qp<QP>.dat in DIR")
     ap.add_argument("--device", type=int, default=0)
-    return ap.parse_args(argv)
+    a = ap.parse_args(argv)
+    ldp = (a.ldp_train, a.ldp_valid, a.cnn_model)
+    if any(v is not None for v in ldp):
+        if a.train is not None or a.valid is not None:
+            ap.error("--ldp-train / --ldp-valid / --cnn-model cannot be combined with --train / --valid")
+        if any(v is None for v in ldp):
+            ap.error("--ldp-train, --ldp-valid and --cnn-model go together")
+    elif a.train is None or a.valid is None:
+        ap.error("the following arguments are required: --train, --valid (or --ldp-train, --ldp-valid, --cnn-model)")
+    return a
+
+
+def ldp_set(pkg, ctx, tr, which, path, qp):
+    """Builds the samples of one LDP file at QP `qp` in HBM and hands them to the trainer.  -> (kept, total, labels(idx) -> [20 n, 16])"""
+    E = pkg.ethcnn
+    rec = ai.load_records(path, E.LDP_RECORD_BYTES).reshape(-1, E.LDP_RECORD_BYTES)
+    slot_qps = [int(rec[0, 64 + 4113 * s]) for s in range(4)]
+    if qp not in slot_qps:
+        raise SystemExit("%s: QP %d is not one of the file's slot QPs %s" % (path, qp, " ".join(str(q) for q in slot_qps)))
+    o = 64 + 4113 * slot_qps.index(qp)
+    heads, strides, _ = E.lstm_samples_plan(rec)
+    with pkg.LstmSampleSet(ctx, slots=[slot_qps.index(qp)]) as ls:
+        ls.build_from(rec)
+        total = ls.count
+        kept = tr.set_samples(which, ls, take=True)
+    on = np.flatnonzero(rec[heads, o] == qp)  # the trainer's own selection (set_qps), on the slot-0 QP
+
+    def labels(idx):
+        j = on[np.asarray(idx)]
+        refs = heads[j][:, None] - np.arange(STEPS)[None, :] * strides[j][:, None]
+        return rec[refs.reshape(-1), o + 1: o + 17].astype(np.float32)
+
+    return kept, total, labels
 
 
 def main(argv=None):
@@ -65,18 +106,29 @@ def main(argv=None):
     if not 0 <= qp <= 51:
         raise SystemExit("--qp must be in 0..51")
     name = "qp%d" % qp
-    train, valid = ai.load_records(a.train, REC), ai.load_records(a.valid, REC)
+    from_ldp = a.ldp_train is not None
+    if not from_ldp:
+        train, valid = ai.load_records(a.train, REC), ai.load_records(a.valid, REC)
     os.makedirs(a.models, exist_ok=True)
     ctx = pkg.EthCnn(device=a.device)
     tr = pkg.LstmTrainer(ctx, batch=a.batch, lr=a.lr, momentum=a.momentum, decay_rate=a.decay_rate, decay_steps=a.decay_steps,
                          dropout=not a.no_dropout, seed=a.seed, qp_scale=a.qp_scale, clip_norm=a.clip_norm)
     tr.set_qps([qp])
-    ntrain = tr.set_samples(pkg.ethcnn.SET_TRAIN, train)
-    nvalid = tr.set_samples(pkg.ethcnn.SET_VALID, valid)
-    kept = {pkg.ethcnn.SET_TRAIN: pkg.ethcnn.lstm_select_qp(train, [qp]), pkg.ethcnn.SET_VALID: pkg.ethcnn.lstm_select_qp(valid, [qp])}
-    print("QP %d: %d of %d training and %d of %d validation samples" % (qp, ntrain, train.size // REC, nvalid, valid.size // REC))
+    if from_ldp:
+        ctx.load_checkpoint(a.cnn_model)
+        ntrain, alltrain, ltrain = ldp_set(pkg, ctx, tr, pkg.ethcnn.SET_TRAIN, a.ldp_train, qp)
+        nvalid, allvalid, lvalid = ldp_set(pkg, ctx, tr, pkg.ethcnn.SET_VALID, a.ldp_valid, qp)
+        print("QP %d: %d of %d training and %d of %d validation samples" % (qp, ntrain, alltrain, nvalid, allvalid))
+    else:
+        ntrain = tr.set_samples(pkg.ethcnn.SET_TRAIN, train)
+        nvalid = tr.set_samples(pkg.ethcnn.SET_VALID, valid)
+        kept = {pkg.ethcnn.SET_TRAIN: pkg.ethcnn.lstm_select_qp(train, [qp]), pkg.ethcnn.SET_VALID: pkg.ethcnn.lstm_select_qp(valid, [qp])}
+        print("QP %d: %d of %d training and %d of %d validation samples" % (qp, ntrain, train.size // REC, nvalid, valid.size // REC))
 
     def evaluate(which, idx):  # ONE batch of len(idx) samples -> (loss, accuracy, probs [20 n, 21], labels [20 n, 16])
+        if from_ldp:
+            l3, a3, probs = tr.evaluate(which, idx=idx, want_probs=True)
+            return l3, a3, probs, (ltrain if which == pkg.ethcnn.SET_TRAIN else lvalid)(idx)
         data = np.asarray(train if which == pkg.ethcnn.SET_TRAIN else valid).reshape(-1, REC)
         l3, a3, probs = tr.evaluate(which, idx=idx, want_probs=True)
         rows = np.ascontiguousarray(data[kept[which][np.asarray(idx)], 64:]).view(np.float32).reshape(len(idx), STEPS, SLOT)

@@ -577,6 +577,64 @@ int ethcnn_samples_write(ethcnn_samples* set, const char* path, int permuted, ui
  * device-to-device copy. */
 int ethcnn_train_set_samples_from(ethcnn_trainer* tr, int set_index, ethcnn_samples* set, int take);
 
+/* ---- ETH-LSTM sample sets (ETH-LSTM_Training_LDP/get_LSTM_input.py): the 37264-byte samples of "ETH-LSTM training" above, built in HBM
+ *      from 16516-byte Low-Delay-P records (an inter sample set that is resident there, or records in host memory) with the context's
+ *      residual CNN, handed to an LSTM trainer there, or written as the file get_LSTM_input.py writes, byte for byte.
+ *   Definition.  For each requested QP slot in ascending slot order, for each record r in file order whose i_frame (little-endian u32 at
+ *      info byte 10) is >= 19 and a multiple of 10: time slot k = 0..19 takes record r - k * (width / 64) * (height / 64) (integer
+ *      divisions; width = u16 at info byte 2, height = u16 at byte 4, both of r's OWN header).  A head whose slot-19 reference is
+ *      negative is skipped and counted.  No other check ties a reference to the head's sequence: a file that holds several sequences or
+ *      geometries gives what this rule gives.  The sample is r's 64 info bytes with byte 0 set to 19, then for every k 465 float32:
+ *      [QP byte | 16 label bytes | 448-vector] of the referenced record at that slot, the bytes converted to float, the vector what
+ *      ethcnn_resi_vectors* gives for the slot's 4096 residual bytes (a 64 x 64 picture) with the CNN the context has loaded -- the
+ *      same bits whichever picture shape and pass form compute it.  With m heads kept and the slots s_0 < s_1 < ..., sample
+ *      i m + j is head j at slot s_i.  The order is fixed by this rule alone (no atomics, no scheduling).
+ *   slots: the QP slots (0..3, distinct, any order) to build; nslots = 0: all four.  One LSTM model is trained per QP, so a caller who
+ *      trains one QP builds one slot, at a quarter of the work and memory.
+ *   chunk_ctus: records whose residuals go through the CNN per chunk; 0 = default (8192), else a multiple of 32 and at most the
+ *      context's max_ctus_per_pass.  max_bytes: the most device memory a build may allocate (samples + working buffers), 0 = no limit
+ *      of its own.
+ *   Memory of a build over n records with m heads: m x nslots x 37264 bytes of samples; working buffers, freed when the build returns:
+ *      one slot's vectors (n rounded up to 32, x 1792 bytes; reused by the next slot), one chunk's picture (4096 x the smaller of
+ *      chunk_ctus and n rounded up to 32), the plan (16 m) and, for records from host memory, their copy in HBM (n x 16516, uploaded in
+ *      pieces of 64 MB).  That sum is what max_bytes is held against and what ETHCNN_ERR_NOMEM reports, before any of it is allocated.
+ *      Outside the sum: a build from a set first holds 8 n bytes of record headers in HBM for the selection, freed before the check.
+ *   Errors: ETHCNN_ERR_NOWEIGHTS when the context has no CNN loaded; ETHCNN_ERR_FORMAT when nbytes is zero or not a whole number of
+ *      16516-byte records, or the set is of kind ETHCNN_SAMPLES_AI or not built; ETHCNN_ERR_ARG for bad slots or a bad chunk_ctus;
+ *      ETHCNN_ERR_NOMEM, with the byte count in the message, when the memory above exceeds max_bytes or does not fit -- nothing stays
+ *      allocated then, and the object may build again.  A build on a built set replaces its samples.  All offsets are 64-bit. */
+typedef struct ethcnn_lstm_samples ethcnn_lstm_samples;
+/* The selection alone, on the host (no context, no GPU): heads[j] = record index of the j-th head kept, strides[j] = its
+ * (width / 64) * (height / 64); both may be NULL, else they hold nbytes / 16516 entries.  ERR_FORMAT as above. */
+int ethcnn_lstm_samples_plan(const uint8_t* records, size_t nbytes, int64_t* heads, int64_t* strides, int64_t* nheads, int64_t* skipped);
+int ethcnn_lstm_samples_create(ethcnn_ctx* ctx, const int* slots, int nslots, int chunk_ctus, uint64_t max_bytes, ethcnn_lstm_samples** out);
+void ethcnn_lstm_samples_destroy(ethcnn_lstm_samples* set); /* before ethcnn_destroy of its context */
+const char* ethcnn_lstm_samples_last_error(const ethcnn_lstm_samples* set);
+/* from a built inter set of the same context, which is only read and stays as it is */
+int ethcnn_lstm_samples_build_from_set(ethcnn_lstm_samples* set, ethcnn_samples* inter_set);
+int ethcnn_lstm_samples_build_from_records(ethcnn_lstm_samples* set, const uint8_t* records, size_t nbytes); /* host memory */
+int64_t ethcnn_lstm_samples_count(const ethcnn_lstm_samples* set);   /* samples: heads kept x slots */
+int64_t ethcnn_lstm_samples_skipped(const ethcnn_lstm_samples* set); /* heads skipped (counted once, not per slot) */
+int ethcnn_lstm_samples_read(ethcnn_lstm_samples* set, int64_t first, int64_t n, uint8_t* out); /* samples [first, first + n) -> host */
+int ethcnn_lstm_samples_write(ethcnn_lstm_samples* set, const char* path); /* temp file + rename: never a partial file */
+/* A built set becomes set 0 / 1 of an LSTM trainer of the same context without leaving HBM, as if its bytes had gone through
+ * ethcnn_lstm_train_set_samples: the QP list of an earlier ethcnn_lstm_train_set_qps selects on the slot-0 QP (kept samples in order)
+ * and the same validation pass runs on the device.  When the selection keeps every sample and take != 0 the trainer adopts the buffer;
+ * else it gets a device-to-device copy of the kept samples.  take != 0: the set is empty afterwards (0 samples, not built). */
+int ethcnn_lstm_train_set_samples_from(ethcnn_lstm_trainer* tr, int set_index, ethcnn_lstm_samples* set, int take);
+/* MEASUREMENT ENTRIES, not part of the feature's interface: they exist for scripts/lstm_samples_rate.py, may change or go without
+ * notice, and nothing should be built on them.  All asynchronous on the context's stream.
+ * repack / gather: the two kernels alone, on buffers already in HBM.  repack: the residuals of records first .. first + n - 1 (of
+ * d_records' nrecords, 16-byte aligned) at `slot` -> d_picture, 2048 bytes a row, 64 rows per 32 records, record first + j at row
+ * 64 (j / 32), column 64 (j % 32), the rest of the last 32 zero: the picture ethcnn_resi_vectors_device takes.  gather: sample j of
+ * d_samples from head d_heads[j] with stride d_strides[j] (the caller's duty: every reference within 0 .. nrecords - 1) and the
+ * vectors d_vectors [nrecords][448] of that slot.
+ * copy: a float4 grid-stride copy (addresses and nbytes multiples of 16), the rate the byte-moving kernels are judged against. */
+int ethcnn_bench_lstm_repack(ethcnn_ctx* ctx, const uint8_t* d_records, int64_t nrecords, int64_t first, int n, int slot, uint8_t* d_picture);
+int ethcnn_bench_lstm_gather(ethcnn_ctx* ctx, const uint8_t* d_records, int64_t nrecords, const float* d_vectors, const int64_t* d_heads,
+                             const int64_t* d_strides, int64_t nheads, int slot, uint8_t* d_samples);
+int ethcnn_bench_copy(ethcnn_ctx* ctx, const void* d_src, void* d_dst, size_t nbytes);
+
 #ifdef __cplusplus
 }
 #endif
