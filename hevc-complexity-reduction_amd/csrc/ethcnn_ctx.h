@@ -3,7 +3,7 @@
 //   ethcnn_model.cpp    weights: upload, the 16-bit plans' images + their accuracy guard, LSTM bundle, introspection
 //   ethcnn_pass.cpp     one pass over CTUs in HBM (the kernel pipeline), the device entry point
 //   ethcnn_host.cpp     host / file entry points: staging ring, worker pool, latency path, streamed pictures, sharded file driver
-//   ethcnn_ldp.cpp      config #5: resi vectors, ETH-LSTM step, the per-frame LDP calls
+//   ethcnn_ldp.cpp      config #5: resi vectors, ETH-LSTM step, the per-frame LDP calls, the offline whole-sequence calls
 // Mirrors /root/reference/HM-16.5_Test_AI/bin/video_to_cu_depth.py (driver) around net_CNN.py (network).  There is no CPU
 // compute path in this library.
 #pragma once
@@ -165,6 +165,12 @@ struct ethcnn_ctx {
     int lstm_cap = 0;
     int state_cur = -1;           // d_state[state_cur] = (c, h) left by the last ethcnn_ldp_step; -1 = none
     int state_nctu = 0;
+    // config #5 offline (ethcnn_ldp_sequence*): the vectors [chunk][nctu][448] and, for the host / file entries, the probabilities
+    // [chunk][nctu][21] of one chunk of frames
+    float* seq_vec = nullptr;
+    float* seq_probs = nullptr;
+    size_t seq_vec_cap = 0, seq_probs_cap = 0;  // bytes
+    int seq_chunk = 0;                          // frames per chunk (ethcnn_ldp_set_sequence_chunk; 0 = default)
 
     Workspace ws;
     // Cross-pass software pipeline ("pass pipeline"): the tile stage of pass i+1 (HBM-bound, no MFMA) runs

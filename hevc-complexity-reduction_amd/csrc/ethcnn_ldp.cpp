@@ -1,5 +1,7 @@
-// ethcnn_ldp.cpp -- config #5: resi_cnn vectors, one ETH-LSTM step, the per-frame Low-Delay-P calls (resident state, streamed input)
+// ethcnn_ldp.cpp -- config #5: resi_cnn vectors, one ETH-LSTM step, the per-frame Low-Delay-P calls (resident state, streamed input),
+// and the offline calls over a whole residual sequence (at the end of the file)
 #include "ethcnn_ctx.h"
+#include "ethcnn_lstm_seq.h"
 
 // -------------------------------------------------------------- config #5 -----------
 extern "C" int ethcnn_resi_vectors_device(ethcnn_ctx* c, const uint8_t* d_luma, int w, int h, ptrdiff_t pitch, float* d_vec) {
@@ -308,4 +310,287 @@ extern "C" int ethcnn_ldp_predict_frame(ethcnn_ctx* c, const uint8_t* luma, int 
     if (rc) return rc;
     const int nctu = ((w + 63) / 64) * ((h + 63) / 64);
     return ethcnn_ldp_get_state(c, state_out, (size_t)nctu * 2 * kNVec);
+}
+
+// ------------------------------------------------- config #5 offline: a whole residual sequence -----------
+// The result of nframes successive ethcnn_ldp_step calls (frame t: i_frame = i_frame_first + t), computed the way an offline job
+// should be: the front-end of a chunk of frames in the big multi-launch passes, then ONE recurrence launch per run of frames that
+// carries its state on chip (ethcnn_lstm_seq.hip), then the gate post-pass.  Chunks only bound the memory: the state goes from one
+// chunk to the next through the resident buffer, and the results do not depend on the chunk size.
+static int64_t seq_default_chunk(int nctu) { return std::max<int64_t>(1, (int64_t)(256 << 20) / ((int64_t)nctu * kNVec * 4)); }  // 256 MB of vectors
+static int64_t seq_chunk_frames(int nctu, int64_t nframes, int chunk) {
+    return std::min<int64_t>(nframes, chunk > 0 ? (int64_t)chunk : seq_default_chunk(nctu));
+}
+
+extern "C" int64_t ethcnn_ldp_sequence_bytes(int w, int h, int nframes, int chunk_frames) {
+    if (w <= 0 || h <= 0 || nframes <= 0 || chunk_frames < 0) return ETHCNN_ERR_ARG;
+    const int64_t nctu = (int64_t)((w + 63) / 64) * ((h + 63) / 64), cap = (nctu + 15) / 16 * 16;
+    const int64_t F = seq_chunk_frames((int)nctu, nframes, chunk_frames);
+    // vectors + probabilities of a chunk, the two resident (c, h) buffers; no projection scratch (the recurrence runs the x half itself)
+    return F * nctu * kNVec * 4 + F * nctu * kNOut * 4 + 2 * cap * 2 * kNVec * 4;
+}
+
+extern "C" int ethcnn_ldp_set_sequence_chunk(ethcnn_ctx* c, int frames) {
+    if (!c) return ETHCNN_ERR_ARG;
+    if (frames < 0) return set_err(c, ETHCNN_ERR_ARG, "ethcnn_ldp_set_sequence_chunk: %d frames", frames);
+    c->seq_chunk = frames;
+    return ETHCNN_OK;
+}
+
+// checks shared by the three entries (nothing is allocated or enqueued before they pass); *in: the buffer that holds the state in
+// front of frame 0 (-1: zeros or the caller's own)
+static int seq_check(ethcnn_ctx* c, int w, int h, ptrdiff_t pitch, int64_t nframes, int i_first, bool have_state_in, int* in) {
+    if (c->ldp.open || c->ai.open) return set_err(c, ETHCNN_ERR_ARG, "ethcnn_ldp_sequence: a streamed call has not been ended");
+    if (w <= 0 || h <= 0 || pitch < w) return set_err(c, ETHCNN_ERR_ARG, "bad geometry");
+    if (nframes <= 0) return set_err(c, ETHCNN_ERR_ARG, "ethcnn_ldp_sequence: nframes must be positive");
+    if (i_first < 0) return set_err(c, ETHCNN_ERR_ARG, "ethcnn_ldp_sequence: i_frame_first must not be negative");
+    if (!c->have_weights) return set_err(c, ETHCNN_ERR_NOWEIGHTS, "no CNN weights loaded");
+    if (!c->have_lstm) return set_err(c, ETHCNN_ERR_NOWEIGHTS, "no LSTM weights loaded");
+    const int nctu = ((w + 63) / 64) * ((h + 63) / 64);
+    *in = -1;
+    if (i_first > 1 && !have_state_in) {
+        if (c->state_cur < 0 || c->state_nctu != nctu)
+            return set_err(c, ETHCNN_ERR_ARG, "ethcnn_ldp_step: frame %d needs the previous frame's state, but none is resident for %d CTUs", i_first, nctu);
+        *in = c->state_cur;
+    }
+    return ETHCNN_OK;
+}
+
+// buffers of a chunk of F frames; refuses with the whole sum (ethcnn_ldp_sequence_bytes) before it allocates what it cannot get
+static int seq_ensure(ethcnn_ctx* c, int w, int h, int64_t nframes, int64_t F, bool want_probs, int* in) {
+    const int nctu = ((w + 63) / 64) * ((h + 63) / 64);
+    const size_t vb = (size_t)F * nctu * kNVec * 4, pb = want_probs ? (size_t)F * nctu * kNOut * 4 : 0;
+    HIPCHK(c, hipSetDevice(c->device));
+    size_t grow = 0, back = 0;
+    if (vb > c->seq_vec_cap) grow += vb, back += c->seq_vec_cap;
+    if (pb > c->seq_probs_cap) grow += pb, back += c->seq_probs_cap;
+    if (nctu > c->lstm_cap) grow += (size_t)((nctu + 15) / 16 * 16) * (5 * kNVec + kNOut) * 4;
+    if (grow) {
+        size_t free_b = 0, total_b = 0;
+        HIPCHK(c, hipMemGetInfo(&free_b, &total_b));
+        if (grow > free_b + back)
+            return set_err(c, ETHCNN_ERR_NOMEM, "ethcnn_ldp_sequence: a chunk of %lld frames holds %lld bytes on the device (ethcnn_ldp_sequence_bytes); %zu are free",
+                           (long long)F, (long long)ethcnn_ldp_sequence_bytes(w, h, (int)std::min<int64_t>(nframes, INT32_MAX), (int)F), free_b + back);
+        HIPCHK(c, hipStreamSynchronize(c->stream));
+    }
+    if (vb > c->seq_vec_cap) {
+        if (c->seq_vec) (void)hipFree(c->seq_vec);
+        c->seq_vec = nullptr, c->seq_vec_cap = 0;
+        if (hipMalloc((void**)&c->seq_vec, vb) != hipSuccess) { (void)hipGetLastError(); return set_err(c, ETHCNN_ERR_NOMEM, "ethcnn_ldp_sequence: %zu bytes of vectors do not fit", vb); }
+        c->seq_vec_cap = vb;
+    }
+    if (pb > c->seq_probs_cap) {
+        if (c->seq_probs) (void)hipFree(c->seq_probs);
+        c->seq_probs = nullptr, c->seq_probs_cap = 0;
+        if (hipMalloc((void**)&c->seq_probs, pb) != hipSuccess) { (void)hipGetLastError(); return set_err(c, ETHCNN_ERR_NOMEM, "ethcnn_ldp_sequence: %zu bytes of probabilities do not fit", pb); }
+        c->seq_probs_cap = pb;
+    }
+    if (nctu > c->lstm_cap) {  // (seq_check has made sure that no resident state is needed then: it belongs to another CTU count)
+        c->state_cur = -1;
+        *in = -1;
+    }
+    return ensure_lstm_buffers(c, nctu);
+}
+
+// the residual vectors of nf frames: the throughput stages ethcnn_resi_vectors_device falls back to, over passes of whole frames
+static int seq_front(ethcnn_ctx* c, const uint8_t* d_luma, const FrameGeom& g, int nf, float* d_vec) {
+    int rc = ensure_workspace(c, (int)std::min<int64_t>((int64_t)g.nctu * nf, c->max_ctus), 1);
+    if (rc) return rc;
+    for (const Pass& p : plan_passes(g.nctu, nf, c->max_ctus)) {
+        { StageTimer t(c, ETHCNN_STAGE_TILE, p.n); launch_tile(d_luma, g, p.ctu0, p.n, c->ws, 0, c->stream); }
+        { StageTimer t(c, ETHCNN_STAGE_TRUNK); launch_trunk(c->ws, c->dw, p.n, true, c->stream); }
+        { StageTimer t(c, ETHCNN_STAGE_FC1, p.n); launch_fc1(c->ws, c->dw, p.n, d_vec + (size_t)p.ctu0 * kNVec, c->stream); }
+        HIPCHK(c, hipGetLastError());
+        c->times.ctus += p.n;
+        c->last_n = p.n;
+        c->last_parity = 0;
+    }
+    return ETHCNN_OK;
+}
+
+// recurrence + heads + gates of nf frames whose vectors are in d_vec.  *sin: the state in front of the first frame (null = zeros);
+// afterwards the state behind the last one, which is in `sout`.  The state is zeroed in front of every frame with i_frame <= 1, so
+// a run of frames that carries its state starts there.
+static int seq_recur(ethcnn_ctx* c, const float* d_vec, int nctu, int nf, int qp, int i0, const float** sin, float* sout, float* d_probs) {
+    for (int f = 0; f < nf;) {
+        const int i = i0 + f, run = (i <= 0) ? 1 : nf - f;
+        StageTimer t(c, ETHCNN_STAGE_HEADS, (long)nctu * run);
+        if (i <= 1) *sin = nullptr;
+        launch_lstm_seq(d_vec + (size_t)f * nctu * kNVec, *sin, sout, c->d_lstm, nctu, run, qp, i, d_probs + (size_t)f * nctu * kNOut, c->stream);
+        *sin = sout;
+        f += run;
+    }
+    { StageTimer tg(c, ETHCNN_STAGE_GATE); launch_lstm_seq_gates(d_probs, nctu, nf, c->thr1, c->thr2, c->stream); }
+    HIPCHK(c, hipGetLastError());
+    return ETHCNN_OK;
+}
+
+extern "C" int ethcnn_ldp_sequence_device(ethcnn_ctx* c, const uint8_t* d_luma, int w, int h, ptrdiff_t pitch, ptrdiff_t fstride, int nframes,
+                                          int qp, int i_first, const float* d_state_in, float* d_probs) {
+    if (!c || !d_luma || !d_probs) return c ? set_err(c, ETHCNN_ERR_ARG, "null pointer") : ETHCNN_ERR_ARG;
+    c->done_armed = 0;
+    int in = -1;
+    int rc = seq_check(c, w, h, pitch, nframes, i_first, d_state_in != nullptr, &in);
+    if (rc) return rc;
+    FrameGeom g;
+    rc = make_geom(c, w, h, pitch, fstride, &g);
+    if (rc) return rc;
+    const int64_t F = seq_chunk_frames(g.nctu, nframes, c->seq_chunk);
+    rc = seq_ensure(c, w, h, nframes, F, false, &in);
+    if (rc) return rc;
+    const int out = in >= 0 ? in : 0;  // the resident state is advanced in place: a block stores only its own columns (ethcnn_lstm_seq.h)
+    const float* sin = i_first > 1 ? (d_state_in ? d_state_in : c->d_state[in]) : nullptr;
+    c->state_cur = -1;  // until every frame has been enqueued
+    for (int64_t f0 = 0; f0 < nframes; f0 += F) {
+        const int nf = (int)std::min<int64_t>(F, nframes - f0);
+        rc = seq_front(c, d_luma + f0 * fstride, g, nf, c->seq_vec);
+        if (rc == 0) rc = seq_recur(c, c->seq_vec, g.nctu, nf, qp, i_first + (int)f0, &sin, c->d_state[out], d_probs + (size_t)f0 * g.nctu * kNOut);
+        if (rc) return rc;
+    }
+    c->state_cur = out;
+    c->state_nctu = g.nctu;
+    return serial_end(c);
+}
+
+// host / file entries: luma reaches the device in pieces of <= 64 MB through the context's staging ring (two of its buffers in turn),
+// each piece goes through the front-end at once; the probabilities of a chunk come back through the pinned output buffer.
+// fetch(dst, f, nf): frames [f, f + nf) of the sequence -> page-locked dst (null: `luma` is the caller's memory, copied from in place)
+template <typename Fetch, typename Sink>
+static int seq_host_run(ethcnn_ctx* c, const uint8_t* luma, int w, int h, ptrdiff_t pitch, ptrdiff_t fstride, int64_t nframes, int qp, int i_first,
+                        const float* state_in, Fetch fetch, Sink sink) {
+    int in = -1;
+    int rc = seq_check(c, w, h, pitch, nframes, i_first, state_in != nullptr, &in);
+    if (rc) return rc;
+    if (fstride < (ptrdiff_t)(h - 1) * pitch + w && nframes > 1) return set_err(c, ETHCNN_ERR_ARG, "ethcnn_ldp_sequence: frame stride %td is shorter than a frame", fstride);
+    c->done_armed = 0;
+    FrameGeom g;
+    rc = make_geom(c, w, h, pitch, fstride, &g);
+    if (rc) return rc;
+    const int64_t F = seq_chunk_frames(g.nctu, nframes, c->seq_chunk);
+    rc = seq_ensure(c, w, h, nframes, F, true, &in);
+    if (rc) return rc;
+    const size_t last = (size_t)(h - 1) * pitch + w;  // the meaningful bytes of the last frame of a piece
+    const int pf = (int)std::max<int64_t>(1, std::min<int64_t>(F, (int64_t)(64 << 20) / std::max<int64_t>(1, (int64_t)fstride)));
+    rc = ensure_staging(c, (size_t)(pf - 1) * fstride + last, (size_t)pf * g.nctu * kNOut * 4, 2);
+    if (rc) return rc;
+    const size_t sbytes = (size_t)g.nctu * 2 * kNVec * 4;
+    const float* sin = nullptr;
+    if (i_first > 1) {
+        if (state_in) {
+            in = 0;
+            HIPCHK(c, hipMemcpyAsync(c->d_state[0], state_in, sbytes, hipMemcpyHostToDevice, c->stream));
+        }
+        sin = c->d_state[in];
+    }
+    const int out = in >= 0 ? in : 0;
+    c->state_cur = -1;
+    bool used[2] = {false, false};
+    int piece = 0;
+    // a HIP failure inside the loops leaves through the common exit below (which waits until nothing reads the caller's memory)
+#define SEQCHK(call)                                                                                                   \
+    {                                                                                                                  \
+        const hipError_t e_ = (call);                                                                                  \
+        if (e_ != hipSuccess) { rc = set_err(c, ETHCNN_ERR_DEVICE, "%s failed: %s", #call, hipGetErrorString(e_)); break; } \
+    }
+    for (int64_t f0 = 0; f0 < nframes && rc == 0; f0 += F) {
+        const int nf = (int)std::min<int64_t>(F, nframes - f0);
+        for (int p0 = 0; p0 < nf && rc == 0; p0 += pf, ++piece) {
+            const int np = std::min(pf, nf - p0), b = piece & 1;
+            const size_t bytes = (size_t)(np - 1) * fstride + last;
+            if (used[b]) SEQCHK(hipEventSynchronize(c->ev_in[b]));  // the piece before last has left this buffer pair
+            const uint8_t* src = luma ? luma + (f0 + p0) * fstride : c->h_in[b];
+            if (!luma) rc = fetch(c->h_in[b], f0 + p0, np);
+            if (rc) break;
+            SEQCHK(hipMemcpyAsync(c->d_in[b], src, bytes, hipMemcpyHostToDevice, c->stream));
+            rc = seq_front(c, c->d_in[b], g, np, c->seq_vec + (size_t)p0 * g.nctu * kNVec);
+            if (rc) break;
+            SEQCHK(hipEventRecord(c->ev_in[b], c->stream));
+            used[b] = true;
+        }
+        if (rc == 0) rc = seq_recur(c, c->seq_vec, g.nctu, nf, qp, i_first + (int)f0, &sin, c->d_state[out], c->seq_probs);
+        if (rc == 0) rc = sink(c->seq_probs, f0, nf, pf);
+    }
+#undef SEQCHK
+    if (rc == 0 && hipStreamSynchronize(c->stream) != hipSuccess) rc = set_err(c, ETHCNN_ERR_DEVICE, "hipStreamSynchronize failed");
+    if (rc) {
+        // nothing still reads the caller's memory when the error is returned; the resident state was being advanced in place and
+        // is dropped (state_cur stays -1): the next call with i_frame > 1 has to bring its state
+        (void)hipStreamSynchronize(c->stream);
+        c->err += " (the resident LDP state was dropped)";
+        return rc;
+    }
+    c->state_cur = out;
+    c->state_nctu = g.nctu;
+    return serial_end(c);
+}
+
+extern "C" int ethcnn_ldp_sequence(ethcnn_ctx* c, const uint8_t* luma, int w, int h, ptrdiff_t pitch, ptrdiff_t fstride, int nframes, int qp,
+                                   int i_first, const float* state_in, float* probs) {
+    if (!c || !luma || !probs) return c ? set_err(c, ETHCNN_ERR_ARG, "null pointer") : ETHCNN_ERR_ARG;
+    const size_t fb = (size_t)(w > 0 && h > 0 ? ((w + 63) / 64) * ((h + 63) / 64) : 0) * kNOut * 4;
+    auto sink = [&](const float* d, int64_t f0, int nf, int) -> int {
+        HIPCHK(c, hipMemcpyAsync((char*)probs + (size_t)f0 * fb, d, (size_t)nf * fb, hipMemcpyDeviceToHost, c->stream));
+        HIPCHK(c, hipStreamSynchronize(c->stream));  // (the next chunk overwrites d)
+        return 0;
+    };
+    return seq_host_run(c, luma, w, h, pitch, fstride, nframes, qp, i_first, state_in, [](uint8_t*, int64_t, int) { return 0; }, sink);
+}
+
+extern "C" int ethcnn_ldp_predict_yuv_file(ethcnn_ctx* c, const char* yuv, int w, int h, int qp, const char* out_path, int64_t f_begin, int64_t f_end) {
+    if (!c || !yuv || !out_path) return c ? set_err(c, ETHCNN_ERR_ARG, "null path") : ETHCNN_ERR_ARG;
+    if (w <= 0 || h <= 0) return set_err(c, ETHCNN_ERR_ARG, "bad frame size %dx%d", w, h);
+    struct stat st;
+    if (stat(yuv, &st) != 0) return set_err(c, ETHCNN_ERR_IO, "cannot stat %s: %s", yuv, std::strerror(errno));
+    const int64_t frame_bytes = (int64_t)w * h * 3 / 2;
+    if (frame_bytes == 0 || st.st_size % frame_bytes != 0)
+        return set_err(c, ETHCNN_ERR_FORMAT, "%s: size %lld is not a multiple of the %dx%d 4:2:0 frame size %lld", yuv, (long long)st.st_size, w, h, (long long)frame_bytes);
+    const int64_t total = st.st_size / frame_bytes;
+    if (f_begin == 0)  // frame k of the file is POC k (extract_data_LDP_LDB_RA.py:192 skips it as well)
+        return set_err(c, ETHCNN_ERR_ARG, "ethcnn_ldp_predict_yuv_file: frame 0 is the intra picture (POC 0) and has no residual: begin at frame 1");
+    if (f_begin < 0 || f_end <= f_begin || f_end > total || f_end > INT32_MAX)
+        return set_err(c, ETHCNN_ERR_ARG, "frame range [%lld,%lld) outside 1..%lld", (long long)f_begin, (long long)f_end, (long long)total);
+    const int nctu = ((w + 63) / 64) * ((h + 63) / 64);
+    int in = -1;
+    int rc = seq_check(c, w, h, w, f_end - f_begin, (int)f_begin, false, &in);  // (before any file is created)
+    if (rc) return rc;
+    FILE* fin = std::fopen(yuv, "rb");
+    if (!fin) return set_err(c, ETHCNN_ERR_IO, "cannot open %s: %s", yuv, std::strerror(errno));
+    const std::string tmp = std::string(out_path) + ".tmp." + std::to_string((long)getpid());
+    FILE* fout = std::fopen(tmp.c_str(), "wb");
+    if (!fout) {
+        std::fclose(fin);
+        return set_err(c, ETHCNN_ERR_IO, "cannot open %s for writing: %s", tmp.c_str(), std::strerror(errno));
+    }
+    const int fd = fileno(fin), ofd = fileno(fout);
+    const size_t plane = (size_t)w * h, fb = (size_t)nctu * kNOut * 4;
+    auto fetch = [&](uint8_t* dst, int64_t f, int nf) -> int {  // luma only: the chroma planes are never read
+        const int bands = (int)std::max<size_t>(1, std::min<size_t>((size_t)std::min(h, 32), plane / (512u << 10)));
+        const std::function<int(int)> unit = [&](int u) -> int {
+            const int k = u / bands, b = u % bands;
+            const int r0 = (int)((long)h * b / bands), r1 = (int)((long)h * (b + 1) / bands);
+            return pinned_pread(fd, dst + (size_t)k * plane + (size_t)r0 * w, (size_t)w * (r1 - r0), (off_t)(f_begin + f + k) * frame_bytes + (off_t)r0 * w);
+        };
+        const int r = host_pool(c)->run(nf * bands, unit);
+        return r ? set_err(c, r, "short read in %s (frames %lld..%lld)", yuv, (long long)(f_begin + f), (long long)(f_begin + f + nf - 1)) : 0;
+    };
+    auto sink = [&](const float* d, int64_t f0, int nf, int pf) -> int {
+        for (int p0 = 0; p0 < nf; p0 += pf) {
+            const int np = std::min(pf, nf - p0);
+            HIPCHK(c, hipMemcpyAsync(c->h_out[0], d + (size_t)p0 * nctu * kNOut, (size_t)np * fb, hipMemcpyDeviceToHost, c->stream));
+            HIPCHK(c, hipStreamSynchronize(c->stream));
+            size_t done = 0;
+            while (done < (size_t)np * fb) {
+                const ssize_t r = pwrite(ofd, (const char*)c->h_out[0] + done, (size_t)np * fb - done, (off_t)((size_t)(f0 + p0) * fb + done));
+                if (r <= 0) return set_err(c, ETHCNN_ERR_IO, "write to %s failed: %s", tmp.c_str(), std::strerror(errno));
+                done += (size_t)r;
+            }
+        }
+        return 0;
+    };
+    rc = seq_host_run(c, nullptr, w, h, w, (ptrdiff_t)plane, f_end - f_begin, qp, (int)f_begin, nullptr, fetch, sink);
+    std::fclose(fin);
+    if (std::fclose(fout) != 0 && rc == 0) rc = set_err(c, ETHCNN_ERR_IO, "close of output failed");
+    if (rc == 0 && std::rename(tmp.c_str(), out_path) != 0) rc = set_err(c, ETHCNN_ERR_IO, "rename %s -> %s failed: %s", tmp.c_str(), out_path, std::strerror(errno));
+    if (rc != 0) std::remove(tmp.c_str());
+    return rc;
 }

@@ -87,6 +87,11 @@ SIGNATURES = {
     "ethcnn_measure_mfma_rate": (_i, [_vp, ctypes.c_double, ctypes.POINTER(ctypes.c_double)]),
     "ethcnn_ldp_step": (_i, [_vp, _vp, _i, _i, _pd, _i, _i, _vp, _fp]),
     "ethcnn_ldp_get_state": (_i, [_vp, _fp, _sz]),
+    "ethcnn_ldp_sequence_device": (_i, [_vp, _vp, _i, _i, _pd, _pd, _i, _i, _i, _vp, _vp]),
+    "ethcnn_ldp_sequence": (_i, [_vp, _vp, _i, _i, _pd, _pd, _i, _i, _i, _vp, _fp]),
+    "ethcnn_ldp_predict_yuv_file": (_i, [_vp, _cp, _i, _i, _i, _cp, ctypes.c_int64, ctypes.c_int64]),
+    "ethcnn_ldp_set_sequence_chunk": (_i, [_vp, _i]),
+    "ethcnn_ldp_sequence_bytes": (ctypes.c_int64, [_i, _i, _i, _i]),
     "ethcnn_ldp_step_begin": (_i, [_vp, _vp, _i, _i, _pd, _i, _i, _vp, _fp]),
     "ethcnn_rows_ready": (_i, [_vp, _i, _i]),
     "ethcnn_predict_luma_begin": (_i, [_vp, _vp, _i, _i, _i, _fp]),
@@ -291,6 +296,11 @@ def crc32c_masked(data):
 def host_thread_budget(local_workers=1, usable_cpus=0):
     """staging-fill threads ONE predictor process starts when `local_workers` of them share the node (no device needed)"""
     return load_library().ethcnn_host_thread_budget(int(local_workers), int(usable_cpus))
+
+
+def ldp_sequence_bytes(width, height, nframes, chunk_frames=0):
+    """device bytes an ldp_sequence call holds for that chunk size (ethcnn_ldp_sequence_bytes; host only); negative = bad arguments"""
+    return int(load_library().ethcnn_ldp_sequence_bytes(int(width), int(height), int(nframes), int(chunk_frames)))
 
 
 def ctus_per_frame(width, height):
@@ -596,6 +606,48 @@ class EthCnn(object):
         state = np.empty((n, 2, NVEC), dtype=np.float32)
         self._chk(self.lib.ethcnn_ldp_get_state(self.h, state.ctypes.data_as(_fp), state.size))
         return state
+
+    # -- config #5 offline: a whole residual sequence = the per-frame ldp_step loop, bit for bit, scheduled for throughput
+    def ldp_sequence(self, luma, width, height, nframes, qp, i_frame_first=1, state_in=None, pitch=None, frame_stride=None,
+                     probs_out=None):
+        """luma: uint8 frames in host memory (pageable or a host_buffer()) -> probs [nframes, nctu, 21]; frame t carries
+        i_frame_first + t; state_in None = zeros (i_frame <= 1) or the resident state.  The final state stays resident
+        (ldp_get_state, or continue with ldp_step)."""
+        assert luma.dtype == np.uint8 and luma.flags["C_CONTIGUOUS"]
+        pitch = width if pitch is None else pitch
+        frame_stride = pitch * height if frame_stride is None else frame_stride
+        need = (nframes - 1) * frame_stride + (height - 1) * pitch + width if min(width, height, nframes) > 0 else 0
+        if luma.size < need:
+            raise ValueError("luma buffer too small: %d < %d" % (luma.size, need))
+        n = ctus_per_frame(width, height)
+        probs = np.empty((max(nframes, 0), n, NOUT), dtype=np.float32) if probs_out is None else probs_out
+        assert probs.dtype == np.float32 and probs.size == max(nframes, 0) * n * NOUT and probs.flags["C_CONTIGUOUS"]
+        sin = None
+        if state_in is not None:
+            sin = np.ascontiguousarray(state_in, dtype=np.float32).reshape(n, 2, NVEC)
+        self._chk(self.lib.ethcnn_ldp_sequence(self.h, luma.ctypes.data, width, height, pitch, frame_stride, int(nframes), int(qp),
+                                               int(i_frame_first), sin.ctypes.data if sin is not None else None,
+                                               probs.ctypes.data_as(_fp)))
+        return probs.reshape(max(nframes, 0), n, NOUT)
+
+    def ldp_sequence_device(self, d_luma, width, height, nframes, qp, i_frame_first, d_probs, d_state_in=None, pitch=None,
+                            frame_stride=None):
+        """asynchronous on the context's stream (ethcnn_ldp_sequence_device): device buffers (alloc()) or raw device addresses"""
+        pitch = width if pitch is None else pitch
+        frame_stride = pitch * height if frame_stride is None else frame_stride
+        ptr = lambda b: None if b is None else getattr(b, "ptr", b)
+        self._chk(self.lib.ethcnn_ldp_sequence_device(self.h, ptr(d_luma), width, height, pitch, frame_stride, int(nframes), int(qp),
+                                                      int(i_frame_first), ptr(d_state_in), ptr(d_probs)))
+
+    def ldp_predict_yuv_file(self, resi_yuv_path, width, height, qp, out_path, frame_begin, frame_end):
+        """frames [frame_begin, frame_end) of a 4:2:0 residual file (frame k = POC k, frame_begin >= 1) -> out_path, float32
+        [frames][nctu][21]"""
+        self._chk(self.lib.ethcnn_ldp_predict_yuv_file(self.h, os.fsencode(resi_yuv_path), width, height, int(qp),
+                                                       os.fsencode(out_path), int(frame_begin), int(frame_end)))
+        return int(frame_end) - int(frame_begin)
+
+    def ldp_set_sequence_chunk(self, frames):
+        self._chk(self.lib.ethcnn_ldp_set_sequence_chunk(self.h, int(frames)))
 
     def host_buffer(self, nbytes):
         """pinned host memory as a uint8 numpy array (freed with the context, or by free_host_buffer)"""

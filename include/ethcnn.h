@@ -206,6 +206,35 @@ int ethcnn_ldp_step_begin(ethcnn_ctx* ctx, const uint8_t* luma, int width, int h
                           const float* state_in /* may be NULL */, float* probs);
 /* (ethcnn_rows_ready: declared with ethcnn_predict_luma_begin above) */
 int ethcnn_ldp_step_end(ethcnn_ctx* ctx);
+/* ---- config #5 offline: a whole residual sequence.  The result EQUALS nframes successive ethcnn_ldp_step calls on the same context, frame t
+ *      carrying i_frame = i_frame_first + t, bit for bit (gates and their zero patterns included): probs[t] is that step's probs, the
+ *      state left resident is the last step's (ethcnn_ldp_get_state returns it; a following ethcnn_ldp_step with state_in == NULL and
+ *      the next i_frame continues from it: a daemon can be warm-started).  Input state of frame t: zeros when its i_frame <= 1, else
+ *      the previous frame's output; for t == 0 with i_frame > 1: state_in when given, else the resident state (the error of
+ *      ethcnn_ldp_step if there is none or it belongs to another CTU count).  efs per frame as in ethcnn_ldp_step; gates per 1024-CTU
+ *      mini-batch of each frame with the context's thresholds; the weights are the ones loaded (the LSTM bundle of the QP band is the
+ *      caller's choice).  i_frame_first >= 0.  What differs is the schedule: the front-end of a CHUNK of frames runs in the big
+ *      multi-launch passes, the recurrence of a chunk is one launch whose blocks own their CTUs for all frames and keep (c, h) on
+ *      chip, a small post-pass applies the gates.  Results do not depend on the chunk size.
+ *   ethcnn_ldp_sequence_device   device pointers, asynchronous on the context's stream; d_probs float32 [nframes][nctu][21]
+ *   ethcnn_ldp_sequence          host pointers (pageable or from ethcnn_host_alloc), synchronous
+ *   ethcnn_ldp_predict_yuv_file  a 4:2:0 file of residual frames (HM-16.5_Resi_Pre's resi_XX.yuv): frame k of the file is POC k, so
+ *                                i_frame = k; frames [frame_begin, frame_end) are processed and out_path holds exactly those as
+ *                                float32 [frames][nctu][21] (temp file + rename).  frame_begin == 0 is refused: POC 0 is the intra
+ *                                picture and has no residual.  frame_begin > 1 continues from the resident state.  Only luma is read.
+ *   ethcnn_ldp_set_sequence_chunk   frames per chunk; 0 = default (256 MB of vectors)
+ *   ethcnn_ldp_sequence_bytes    host only, no context: the device bytes a call holds for that chunk size, F = min(nframes, chunk or
+ *                                default) frames: F nctu 448 x 4 (vectors) + F nctu 21 x 4 (probabilities of the host / file entries)
+ *                                + 2 x roundup16(nctu) x 896 x 4 (the two state buffers); negative for bad arguments.  A call that
+ *                                cannot get its buffers fails with ETHCNN_ERR_NOMEM and this sum in the message, nothing allocated. */
+int ethcnn_ldp_sequence_device(ethcnn_ctx* ctx, const uint8_t* d_luma, int width, int height, ptrdiff_t pitch, ptrdiff_t frame_stride,
+                               int nframes, int qp, int i_frame_first, const float* d_state_in /* may be NULL */, float* d_probs);
+int ethcnn_ldp_sequence(ethcnn_ctx* ctx, const uint8_t* luma, int width, int height, ptrdiff_t pitch, ptrdiff_t frame_stride, int nframes,
+                        int qp, int i_frame_first, const float* state_in /* may be NULL */, float* probs);
+int ethcnn_ldp_predict_yuv_file(ethcnn_ctx* ctx, const char* resi_yuv_path, int width, int height, int qp, const char* out_path,
+                                int64_t frame_begin, int64_t frame_end);
+int ethcnn_ldp_set_sequence_chunk(ethcnn_ctx* ctx, int frames);
+int64_t ethcnn_ldp_sequence_bytes(int width, int height, int nframes, int chunk_frames);
 /* Pinned (page-locked) host memory: buffers a caller fills itself (file reads) and hands to the host entry points are
  * DMA-able directly, without the runtime's pageable staging copy.  ethcnn_ldp_step goes further: a luma / probs pointer that
  * lies inside such a buffer is read / written by the kernels IN PLACE (no copy launch at all); so does ethcnn_predict_luma for ONE

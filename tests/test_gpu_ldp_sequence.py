@@ -1,0 +1,284 @@
+"""-m gpu: a whole Low-Delay-P residual sequence in one call (ethcnn_ldp_sequence*, ethcnn_ldp_predict_yuv_file) against its
+definition: nframes successive ethcnn_ldp_step calls on the same context, frame t carrying i_frame_first + t.  Every comparison is
+bit for bit; synthetic CNN weights, the reference's real QP-32 LSTM bundle and a seeded one."""
+import os
+import subprocess
+import sys
+
+import numpy as np
+import pytest
+
+pytestmark = pytest.mark.gpu
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+REAL = os.path.join(ROOT, "tests", "golden", "model_LDP_200000_qp32.dat")
+QP = 32
+
+
+def _bits(a):
+    return np.ascontiguousarray(a, dtype=np.float32).view(np.uint32)
+
+
+def _frames(seed, w, h, nf):
+    """residual-like luma with quieter bands that move from frame to frame, so that mini-batches and frames differ"""
+    rng = np.random.default_rng(seed)
+    out = rng.integers(0, 256, size=(nf, h, w), dtype=np.uint8)
+    for t in range(nf):
+        r0 = (t * h // nf) // 2
+        out[t, r0: r0 + h // 2] = (out[t, r0: r0 + h // 2] // (8 << (t % 3)) + 120).astype(np.uint8)
+    return out
+
+
+@pytest.fixture(scope="module")
+def lstm(oracle):
+    import ethcnn_lstm_np
+    return ethcnn_lstm_np
+
+
+@pytest.fixture(params=["real", "seeded"])
+def seq(request, pkg, oracle, lstm):
+    c = pkg.EthCnn(device=0)
+    c.load_blob(oracle.synth_blob(21, 1.0))
+    if request.param == "real":
+        c.load_lstm_checkpoint(REAL)
+    else:
+        c.load_lstm_blob(lstm.synth_lstm_blob(22, 3.0))
+    c.set_thresholds(0.5, 0.5)
+    c.kind = request.param
+    yield c
+    c.close()
+
+
+def _loop(c, lum, w, h, first, state_in=None):
+    """the definition: ethcnn_ldp_step frame after frame, resident state"""
+    out = []
+    for t in range(lum.shape[0]):
+        i = first + t
+        out.append(c.ldp_step(lum[t], w, h, QP, i, state_in=state_in if (t == 0 and i > 1) else None).copy())
+    return np.stack(out), c.ldp_get_state(w, h)
+
+
+def _same(got, want, what):
+    assert got.shape == want.shape, what
+    assert np.array_equal(_bits(got), _bits(want)), "%s: %d words differ, max |d| = %g" % (what, int((_bits(got) != _bits(want)).sum()), np.abs(got - want).max())
+
+
+@pytest.mark.parametrize("w,h,nf,first", [(416, 240, 25, 0), (416, 240, 25, 1), (200, 136, 9, 1), (1920, 1080, 12, 1)])
+def test_sequence_equals_the_per_frame_loop(seq, w, h, nf, first):
+    lum = _frames(w + first, w, h, nf)
+    want_p, want_s = _loop(seq, lum, w, h, first)
+    got_p = seq.ldp_sequence(lum, w, h, nf, QP, i_frame_first=first)
+    _same(got_p, want_p, "probabilities")
+    _same(seq.ldp_get_state(w, h), want_s, "final state")
+
+
+def test_sequence_from_a_given_and_from_a_resident_state(seq):
+    w, h, nf, first = 416, 240, 25, 7
+    lum = _frames(77, w, h, nf)
+    rng = np.random.default_rng(5)
+    n = 28
+    sin = np.stack([rng.uniform(-5, 5, (n, 448)), rng.uniform(-1, 1, (n, 448))], 1).astype(np.float32)
+    want_p, want_s = _loop(seq, lum, w, h, first, state_in=sin)
+    _same(seq.ldp_sequence(lum, w, h, nf, QP, i_frame_first=first, state_in=sin), want_p, "given state: probabilities")
+    _same(seq.ldp_get_state(w, h), want_s, "given state: final state")
+    # the state a previous step left resident
+    pre = _frames(78, w, h, 1)
+    seq.ldp_step(pre[0], w, h, QP, first - 1, state_in=sin)
+    want_p, want_s = _loop(seq, lum, w, h, first)
+    seq.ldp_step(pre[0], w, h, QP, first - 1, state_in=sin)
+    _same(seq.ldp_sequence(lum, w, h, nf, QP, i_frame_first=first), want_p, "resident state: probabilities")
+    _same(seq.ldp_get_state(w, h), want_s, "resident state: final state")
+
+
+def test_two_mini_batches_and_every_gate_state(seq):
+    """2560x1920 = 1200 CTUs: above the one-launch LSTM limit, two mini-batches per frame.  The thresholds were chosen on the CPU
+    (oracle lstm_step on these frames, gates open: the maxima of y64 / y32 per (frame, mini-batch) straddle them), so that the LOOP's
+    output holds zero-filled and not zero-filled (frame, mini-batch) pairs for level 2 and for level 3 -- asserted before comparing."""
+    w, h, nf = 2560, 1920, 4
+    thr = {"real": (0.85, 0.51), "seeded": (0.92, 0.98)}[seq.kind]
+    seq.set_thresholds(*thr)
+    lum = _frames(2560, w, h, nf)
+    want_p, want_s = _loop(seq, lum, w, h, 1)
+    mbs = [want_p[t, c0:c0 + 1024] for t in range(nf) for c0 in (0, 1024)]
+    for name, cols in (("level 2", slice(1, 5)), ("level 3", slice(5, 21))):
+        filled = [bool((m[:, cols] == 0).all()) for m in mbs]
+        assert any(filled) and not all(filled), "%s: the cases must contain zero-filled and open mini-batches: %s" % (name, filled)
+    _same(seq.ldp_sequence(lum, w, h, nf, QP, i_frame_first=1), want_p, "probabilities")
+    _same(seq.ldp_get_state(w, h), want_s, "final state")
+
+
+def test_sequence_against_the_oracle(seq, oracle, lstm):
+    w, h, nf = 416, 240, 6
+    lum = _frames(6, w, h, nf)
+    cblob, lblob = seq.get_blob(), seq.get_lstm_blob()
+    got = seq.ldp_sequence(lum, w, h, nf, QP, i_frame_first=1)
+    st = None
+    for t in range(nf):
+        vec = oracle.resi_vectors(cblob, lum[t], w, h).reshape(-1, 448)
+        p, st = lstm.lstm_step(lblob, vec, st, QP, 1 + t, 0.5, 0.5, mode=0)
+        _same(got[t], p, "frame %d" % t)
+    _same(seq.ldp_get_state(w, h), st, "final state")
+
+
+def test_results_do_not_depend_on_the_chunk(seq):
+    w, h, nf = 416, 240, 25
+    lum = _frames(416, w, h, nf)
+    ref = seq.ldp_sequence(lum, w, h, nf, QP, i_frame_first=1).copy()
+    ref_s = seq.ldp_get_state(w, h)
+    for chunk in (1, 3):
+        seq.ldp_set_sequence_chunk(chunk)
+        _same(seq.ldp_sequence(lum, w, h, nf, QP, i_frame_first=1), ref, "chunk %d" % chunk)
+        _same(seq.ldp_get_state(w, h), ref_s, "chunk %d: state" % chunk)
+    seq.ldp_set_sequence_chunk(0)
+
+
+def test_a_step_continues_the_sequence(seq):
+    w, h = 416, 240
+    lum = _frames(11, w, h, 11)
+    want_p, want_s = _loop(seq, lum, w, h, 1)
+    _, want_s10 = _loop(seq, lum[:10], w, h, 1)
+    got = seq.ldp_sequence(lum[:10], w, h, 10, QP, i_frame_first=1)
+    _same(got, want_p[:10], "frames 1..10")
+    _same(seq.ldp_get_state(w, h), want_s10, "ethcnn_ldp_get_state after the sequence")
+    _same(seq.ldp_step(lum[10], w, h, QP, 11), want_p[10], "frame 11 by ethcnn_ldp_step")
+    _same(seq.ldp_get_state(w, h), want_s, "state")
+
+
+def test_host_device_and_file_entries(seq, tmp_path):
+    w, h, nf = 416, 240, 9
+    lum = _frames(9, w, h, nf)
+    want_p, want_s = _loop(seq, lum, w, h, 1)
+    pinned = seq.host_buffer(lum.size)
+    pinned[:] = lum.reshape(-1)
+    _same(seq.ldp_sequence(pinned, w, h, nf, QP, i_frame_first=1), want_p, "page-locked input")
+    # device entry
+    d_l, d_p = seq.alloc(lum.size), seq.alloc(want_p.nbytes)
+    d_l.upload(lum.reshape(-1))
+    seq.ldp_sequence_device(d_l, w, h, nf, QP, 1, d_p)
+    _same(d_p.download(np.float32, want_p.size).reshape(want_p.shape), want_p, "device entry")
+    d_l.free(), d_p.free()
+    # file entry: frame k of the file is POC k; chroma filled with a value that would change the result if it were read
+    path, out = str(tmp_path / "resi.yuv"), str(tmp_path / "cu_depth.dat")
+    with open(path, "wb") as f:
+        for k in range(nf + 1):
+            f.write((lum[k - 1] if k else np.full((h, w), 255, np.uint8)).tobytes())
+            f.write(np.full(w * h // 2, 255, np.uint8).tobytes())
+    assert seq.ldp_predict_yuv_file(path, w, h, QP, out, 1, nf + 1) == nf
+    _same(np.fromfile(out, dtype="<f4").reshape(want_p.shape), want_p, "file entry")
+    _same(seq.ldp_get_state(w, h), want_s, "file entry: state")
+    # a sub-range [3, 9) continues from the state a call over [1, 3) left
+    seq.ldp_predict_yuv_file(path, w, h, QP, out, 1, 3)
+    seq.ldp_predict_yuv_file(path, w, h, QP, out, 3, 9)
+    _same(np.fromfile(out, dtype="<f4").reshape(6, -1, 21), want_p[2:8], "sub-range")
+
+
+def _client_frames(w, h, frames, seed):
+    """the pictures tools/ldp_client.c writes to resi.yuv (splitmix64 stream, one draw per pixel, frame after frame)"""
+    n = w * h * frames
+    with np.errstate(over="ignore"):
+        z = np.uint64(seed) + np.arange(1, n + 1, dtype=np.uint64) * np.uint64(0x9E3779B97F4A7C15)
+        z = (z ^ (z >> np.uint64(30))) * np.uint64(0xBF58476D1CE4E5B9)
+        z = (z ^ (z >> np.uint64(27))) * np.uint64(0x94D049BB133111EB)
+    r = ((z ^ (z >> np.uint64(31))) >> np.uint64(32)).astype(np.int64)
+    v = 128 + (r & 31) - 16 + ((r >> 8) & 15) - 8
+    return np.clip(v, 0, 255).astype(np.uint8).reshape(frames, h, w)
+
+
+def _fnv1a64(b):
+    hsh = 1469598103934665603
+    for x in b:
+        hsh = ((hsh ^ x) * 1099511628211) & 0xFFFFFFFFFFFFFFFF
+    return "%016x" % hsh
+
+
+@pytest.mark.parametrize("w,h,frames", [(416, 240, 12), (200, 136, 7)])
+def test_file_entry_equals_what_the_native_daemon_writes(pkg, tmp_path, w, h, frames):
+    """the native daemon serves the encoder's file protocol frame by frame (helpers of tests/test_gpu_ldp_native.py, whose client
+    digests every cu_depth.dat it reads); the file entry over a resi.yuv that holds the same pictures as POC 1.. writes their
+    concatenation"""
+    sys.path.insert(0, os.path.join(ROOT, "tests"))
+    import test_gpu_ldp_native as nat
+    work = nat._workdir(str(tmp_path / "native"))
+    d = nat._serve("native", work, frames)
+    c = nat._client(work, w, h, frames)  # seed 7, QP 32
+    d.wait(timeout=60)
+    assert c.returncode == 0 and d.returncode == 0, (c.stderr[-500:], d.stderr.read()[-800:])
+    digests = dict(ln.split() for ln in open(os.path.join(work, "digest.txt")).read().splitlines() if ln.strip())
+    assert sorted(int(k) for k in digests) == list(range(1, frames + 1))
+    lum = _client_frames(w, h, frames, 7)
+    path, out = str(tmp_path / "resi.yuv"), str(tmp_path / "cu_depth.dat")
+    with open(path, "wb") as f:
+        for k in range(frames + 1):
+            f.write((lum[k - 1] if k else np.zeros((h, w), np.uint8)).tobytes())
+            f.write(np.full(w * h // 2, 7, np.uint8).tobytes())  # (the client's chroma is 128: never read by either side)
+    ctx = pkg.EthCnn(device=0)
+    ctx.load_synthetic(21, 1.0)  # what the daemon restores under ETHCNN_SYNTHETIC_SEED=21 when the CNN checkpoint is absent
+    ctx.load_lstm_checkpoint(os.path.join(work, "model_LDP_200000_qp32.dat"))
+    ctx.load_thresholds(os.path.join(work, "Thr_info.txt"))
+    assert ctx.ldp_predict_yuv_file(path, w, h, QP, out, 1, frames + 1) == frames
+    ctx.close()
+    got = np.fromfile(out, dtype="<f4").reshape(frames, -1, 21)
+    for k in range(frames):
+        assert _fnv1a64(got[k].tobytes()) == digests[str(k + 1)], "POC %d differs from the daemon's cu_depth.dat" % (k + 1)
+
+
+def test_driver_command_line(pkg, tmp_path):
+    seq = pkg.EthCnn(device=0)
+    seq.load_lstm_checkpoint(REAL)
+    w, h, nf = 200, 136, 5
+    lum = _frames(3, w, h, nf)
+    path = str(tmp_path / "resi.yuv")
+    with open(path, "wb") as f:
+        for k in range(nf + 1):
+            f.write((lum[k - 1] if k else np.zeros((h, w), np.uint8)).tobytes())
+            f.write(np.full(w * h // 2, 128, np.uint8).tobytes())
+    import shutil
+    for ext in (".index", ".data-00000-of-00001"):
+        shutil.copy(REAL + ext, str(tmp_path / ("model_LDP_200000_qp32.dat" + ext)))
+    env = dict(os.environ, ETHCNN_SYNTHETIC_SEED="21")
+    out, st = str(tmp_path / "cu_depth.dat"), str(tmp_path / "state.dat")
+    r = subprocess.run([sys.executable, os.path.join(ROOT, "hevc-complexity-reduction_amd", "resi_video_to_cu_depth_LDP.py"), path, str(w), str(h),
+                        str(QP), "--out", out, "--state-out", st, "--model-dir", str(tmp_path)], capture_output=True, text=True, env=env, timeout=300)
+    assert r.returncode == 0, r.stderr[-800:]
+    assert "Predicting Time" in r.stdout
+    seq.load_synthetic(21, 1.0)
+    ref = str(tmp_path / "ref.dat")
+    seq.ldp_predict_yuv_file(path, w, h, QP, ref, 1, nf + 1)
+    assert open(out, "rb").read() == open(ref, "rb").read()
+    _same(np.fromfile(st, dtype="<f4").reshape(-1, 2, 448), seq.ldp_get_state(w, h), "state.dat")
+    seq.close()
+
+
+def test_errors_leave_the_context_usable(pkg, oracle, lstm, tmp_path):
+    w, h = 416, 240
+    lum = _frames(1, w, h, 3)
+    c = pkg.EthCnn(device=0)
+    c.load_blob(oracle.synth_blob(21, 1.0))
+
+    def refused(fn):
+        with pytest.raises(pkg.EthCnnError) as e:
+            fn()
+        assert e.value.code < 0 and str(e.value).split(":", 1)[1].strip()
+        return e.value.code
+
+    refused(lambda: c.ldp_sequence(lum, w, h, 3, QP))  # no LSTM weights
+    lblob = lstm.synth_lstm_blob(22, 3.0)
+    c.load_lstm_blob(lblob)
+    refused(lambda: c.ldp_sequence(lum, w, h, 0, QP, probs_out=np.empty(0, np.float32)))
+    refused(lambda: c.ldp_sequence(lum, w, h, 3, QP, i_frame_first=5))  # no state
+    path = str(tmp_path / "r.yuv")
+    open(path, "wb").write(bytes(w * h * 3 // 2 * 3))
+    refused(lambda: c.ldp_predict_yuv_file(path, w, h, QP, str(tmp_path / "o.dat"), 0, 2))
+    assert not os.path.exists(str(tmp_path / "o.dat"))
+    # an absurd chunk: 2^20 frames of 1080p are a terabyte of vectors (every frame reads the same picture: stride 0)
+    big = _frames(2, 1920, 1080, 1)
+    d_l, d_p = c.alloc(big.size), c.alloc(510 * 21 * 4)
+    d_l.upload(big.reshape(-1))
+    c.ldp_set_sequence_chunk(1 << 20)
+    assert refused(lambda: c.ldp_sequence_device(d_l, 1920, 1080, 1 << 20, QP, 1, d_p, frame_stride=0)) == -6
+    c.ldp_set_sequence_chunk(0)
+    d_l.free(), d_p.free()
+    got = c.ldp_step(lum[0], w, h, QP, 1)
+    vec = oracle.resi_vectors(oracle.synth_blob(21, 1.0), lum[0], w, h).reshape(-1, 448)
+    want, _ = lstm.lstm_step(lblob, vec, None, QP, 1, 0.5, 0.5, mode=0)
+    _same(got, want, "a step after the refusals")
+    c.close()

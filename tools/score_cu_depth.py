@@ -13,7 +13,10 @@ p64 > thr), per 32x32 of a truly split CTU "split 32?" (mean depth of its 4 bloc
 16x16 of a truly split 32x32 "split 16?" (depth > 2.5 vs p16 > thr).  Vectorized numpy; host-side tooling,
 not part of the hot path.
 
-    score_cu_depth.py <Info_..._CUDepth.dat> <cu_depth.dat> <width> <height> [thr64 thr32 thr16]
+    score_cu_depth.py [--skip-label-frames N] <Info_..._CUDepth.dat> <cu_depth.dat> <width> <height> [thr64 thr32 thr16]
+
+--skip-label-frames N drops the first N frames of the label file: a Low-Delay-P prediction starts at POC 1 (POC 0 is the intra
+picture and has no residual: resi_video_to_cu_depth_LDP.py) while the label files of LDP_Info start at POC 0, so N = 1 lines them up.
 """
 import sys
 
@@ -73,12 +76,27 @@ def accuracy(m):
 
 
 def main(argv):
+    argv = list(argv)
+    skip = 0
+    for k, arg in enumerate(argv):
+        if arg == "--skip-label-frames" or arg.startswith("--skip-label-frames="):
+            val, n = (argv[k + 1] if k + 1 < len(argv) else "", 2) if arg == "--skip-label-frames" else (arg.split("=", 1)[1], 1)
+            if not val.isdigit():
+                sys.stderr.write(__doc__)
+                return 2
+            skip = int(val)
+            del argv[k:k + n]
+            break
     if len(argv) not in (5, 8):
         sys.stderr.write(__doc__)
         return 2
     w, h = int(argv[3]), int(argv[4])
     thr = tuple(float(x) for x in argv[5:8]) if len(argv) == 8 else (0.5, 0.5, 0.5)
-    depth = labels_per_ctu(read_labels(argv[1], w, h))
+    labels = read_labels(argv[1], w, h)
+    if skip >= labels.shape[0]:
+        sys.stderr.write("--skip-label-frames %d: the label file holds %d frames\n" % (skip, labels.shape[0]))
+        return 2
+    depth = labels_per_ctu(labels[skip:])
     probs = np.fromfile(argv[2], dtype="<f4").reshape(-1, 21)
     n = min(depth.shape[0], probs.shape[0])
     if depth.shape[0] != probs.shape[0]:
