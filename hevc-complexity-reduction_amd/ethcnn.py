@@ -189,6 +189,16 @@ SIGNATURES = {
     "ethcnn_bench_lstm_repack": (_i, [_vp, _vp, ctypes.c_int64, ctypes.c_int64, _i, _i, _vp]),
     "ethcnn_bench_lstm_gather": (_i, [_vp, _vp, ctypes.c_int64, _vp, _vp, _vp, ctypes.c_int64, _i, _vp]),
     "ethcnn_bench_copy": (_i, [_vp, _vp, _vp, _sz]),
+    "ethcnn_calib_create": (_i, [_vp, ctypes.POINTER(_vp)]),
+    "ethcnn_calib_destroy": (None, [_vp]),
+    "ethcnn_calib_reset": (_i, [_vp]),
+    "ethcnn_calib_add": (_i, [_vp, _vp, _vp, ctypes.c_int64]),
+    "ethcnn_calib_add_device": (_i, [_vp, _vp, _vp, ctypes.c_int64]),
+    "ethcnn_calib_add_frames": (_i, [_vp, _vp, _vp, _i, _i, ctypes.c_int64, ctypes.c_int64]),
+    "ethcnn_calib_add_frames_device": (_i, [_vp, _vp, _vp, _i, _i, ctypes.c_int64, ctypes.c_int64]),
+    "ethcnn_calib_get": (_i, [_vp, _vp, _vp, ctypes.POINTER(ctypes.c_uint64)]),
+    "ethcnn_calib_choose": (_i, [_vp, ctypes.POINTER(ctypes.c_uint32), ctypes.POINTER(ctypes.c_uint32), _vp]),
+    "ethcnn_calib_write_thr_info": (_i, [_cp, _vp, _i]),
 }
 
 _lib = None
@@ -1216,3 +1226,151 @@ class LstmSampleSet(object):
 
     def write(self, path):
         self._chk(self.lib.ethcnn_lstm_samples_write(self.h, os.fsencode(path)))
+
+
+# ------------------------------------------------------------------------------------------------------------ calibration ---
+CALIB_BINS, CALIB_LEVELS = 1025, 3
+THR_ORDER_AI, THR_ORDER_LDP = 0, 1
+_THR_ORDERS = {"ai": THR_ORDER_AI, "ldp": THR_ORDER_LDP}
+
+
+class CalibLevel(ctypes.Structure):
+    _fields_ = [("n0", ctypes.c_uint64), ("n1", ctypes.c_uint64), ("down_k", ctypes.c_int32), ("up_k", ctypes.c_int32),
+                ("down", ctypes.c_double), ("up", ctypes.c_double), ("miss", ctypes.c_uint64), ("fsplit", ctypes.c_uint64),
+                ("uncertain", ctypes.c_uint64), ("uncertain_share", ctypes.c_double), ("accuracy_512", ctypes.c_double),
+                ("empty_class", ctypes.c_int32), ("crossed", ctypes.c_int32)]
+
+
+class CalibReport(ctypes.Structure):
+    _fields_ = [("level", CalibLevel * 3)]
+
+    def as_dicts(self):
+        return [{name: getattr(lv, name) for name, _ in CalibLevel._fields_} for lv in self.level]
+
+
+def _ppm3(eps):
+    eps = [int(e) for e in (eps if hasattr(eps, "__len__") else (eps,) * 3)]
+    if len(eps) != 3 or min(eps) < 0 or max(eps) > 1000000:
+        raise ValueError("a budget is three values in parts per million, 0..1000000: %r" % (eps,))
+    return (ctypes.c_uint32 * 3)(*eps)
+
+
+def calib_choose(hist, eps_down_ppm, eps_up_ppm, lib=None):
+    """ethcnn_calib_choose (host only): hist uint64 [3, 2, 1025], budgets in parts per million (three values, or one for all levels)
+    -> CalibReport"""
+    lib = lib or load_library()
+    hist = np.ascontiguousarray(hist, dtype=np.uint64)
+    if hist.size != CALIB_LEVELS * 2 * CALIB_BINS:
+        raise ValueError("a histogram holds 3 x 2 x 1025 counts, got %d" % hist.size)
+    rep = CalibReport()
+    rc = lib.ethcnn_calib_choose(hist.ctypes.data, _ppm3(eps_down_ppm), _ppm3(eps_up_ppm), ctypes.byref(rep))
+    if rc:
+        raise EthCnnError(rc, lib.ethcnn_last_error(None).decode())
+    return rep
+
+
+def write_thr_info(path, report, order, lib=None):
+    """ethcnn_calib_write_thr_info (host only).  order "ai": up1 down1 up2 down2 up3 down3 (TEncCu.cpp:250 of HM-16.5_Test_AI);
+    "ldp": down1 up1 down2 up2 down3 up3 (TEncGOP.cpp:1449 of HM-16.5_Test_LDP)."""
+    lib = lib or load_library()
+    if order not in _THR_ORDERS:
+        raise ValueError("order is 'ai' or 'ldp', got %r" % (order,))
+    rc = lib.ethcnn_calib_write_thr_info(os.fsencode(path), ctypes.byref(report), _THR_ORDERS[order])
+    if rc:
+        raise EthCnnError(rc, lib.ethcnn_last_error(None).decode())
+
+
+class Calibrator(object):
+    """Per-level histograms of the split probabilities by ground truth, counted on the GPU, and the Thr_info.txt thresholds chosen
+    from them (include/ethcnn.h "threshold calibration").  The probabilities must come from a prediction with OPEN gates
+    (set_thresholds(0, 0)): the batch gates zero whole sub-batches of p32 / p16."""
+
+    def __init__(self, ctx):
+        self.ctx, self.lib = ctx, ctx.lib
+        h = ctypes.c_void_p()
+        ctx._chk(self.lib.ethcnn_calib_create(ctx.h, ctypes.byref(h)))
+        self.h = h
+        if not hasattr(ctx, "_trainers"):
+            ctx._trainers = weakref.WeakSet()
+        ctx._trainers.add(self)  # closed with the context, before it
+
+    def _chk(self, rc):
+        self.ctx._chk(rc)
+
+    def close(self):
+        if getattr(self, "h", None):
+            self.lib.ethcnn_calib_destroy(self.h)
+            self.h = None
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+    def __enter__(self):
+        return self
+
+    def __exit__(self, *a):
+        self.close()
+
+    def reset(self):
+        self._chk(self.lib.ethcnn_calib_reset(self.h))
+
+    def add(self, probs, depth16):
+        """probs float32 [n, 21], depth16 uint8 [n, 16] (a sample's label bytes) in host memory"""
+        probs = np.ascontiguousarray(probs, dtype=np.float32).reshape(-1, NOUT)
+        depth16 = np.ascontiguousarray(depth16, dtype=np.uint8).reshape(-1, 16)
+        if probs.shape[0] != depth16.shape[0]:
+            raise ValueError("%d rows of probabilities, %d of depths" % (probs.shape[0], depth16.shape[0]))
+        n = probs.shape[0]
+        self._chk(self.lib.ethcnn_calib_add(self.h, probs.ctypes.data if n else None, depth16.ctypes.data if n else None, n))
+
+    def add_device(self, d_probs, d_depth16, n):
+        """the same on buffers in HBM (DeviceBuffer or raw device addresses)"""
+        ptr = lambda b: getattr(b, "ptr", b)
+        self._chk(self.lib.ethcnn_calib_add_device(self.h, ptr(d_probs), ptr(d_depth16), int(n)))
+
+    @staticmethod
+    def _frames(width, height, nprobs, nlabels, nframes, skip):
+        if width % 16 or height % 16 or width <= 0 or height <= 0:
+            return None  # the library names the error
+        per, lab = ctus_per_frame(width, height) * NOUT, (width // 16) * (height // 16)
+        if nframes is None:
+            if nprobs % per:
+                raise ValueError("%d probabilities are not a whole number of %dx%d frames" % (nprobs, width, height))
+            nframes = nprobs // per
+        if nprobs < nframes * per or nlabels < (nframes + skip) * lab:
+            raise ValueError("%d frames (+ %d skipped label frames) need %d probabilities and %d label bytes, got %d and %d"
+                             % (nframes, skip, nframes * per, (nframes + skip) * lab, nprobs, nlabels))
+        return nframes
+
+    def add_frames(self, probs, labels, width, height, skip_label_frames=0, nframes=None):
+        """probs float32 [frames, nctu, 21] (a cu_depth.dat), labels uint8 [skip + frames, height / 16, width / 16] (an
+        Info_*_CUDepth.dat) in host memory; CTUs that are not wholly inside the picture are left out (skipped_partial)"""
+        probs = np.ascontiguousarray(probs, dtype=np.float32)
+        labels = np.ascontiguousarray(labels, dtype=np.uint8)
+        nf = self._frames(width, height, probs.size, labels.size, nframes, int(skip_label_frames))
+        self._chk(self.lib.ethcnn_calib_add_frames(self.h, probs.ctypes.data if probs.size else None, labels.ctypes.data if labels.size else None,
+                                                   int(width), int(height), 0 if nf is None else nf, int(skip_label_frames)))
+
+    def add_frames_device(self, d_probs, d_labels, width, height, nframes, skip_label_frames=0):
+        """the same on buffers in HBM, e.g. the output ldp_sequence_device left there"""
+        ptr = lambda b: getattr(b, "ptr", b)
+        self._chk(self.lib.ethcnn_calib_add_frames_device(self.h, ptr(d_probs), ptr(d_labels), int(width), int(height), int(nframes),
+                                                          int(skip_label_frames)))
+
+    def get(self):
+        """(hist uint64 [3, 2, 1025] = [level, truth, bin], rejected uint64 [3], skipped_partial); waits for the stream"""
+        hist, rej, sk = np.zeros((CALIB_LEVELS, 2, CALIB_BINS), np.uint64), np.zeros(3, np.uint64), ctypes.c_uint64(0)
+        self._chk(self.lib.ethcnn_calib_get(self.h, hist.ctypes.data, rej.ctypes.data, ctypes.byref(sk)))
+        return hist, rej, int(sk.value)
+
+    def histogram(self):
+        return self.get()[0]
+
+    def choose(self, eps_down_ppm, eps_up_ppm):
+        return calib_choose(self.histogram(), eps_down_ppm, eps_up_ppm, self.lib)
+
+    def write_thr_info(self, path, report, order):
+        write_thr_info(path, report, order, self.lib)

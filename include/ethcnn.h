@@ -664,6 +664,74 @@ int ethcnn_bench_lstm_gather(ethcnn_ctx* ctx, const uint8_t* d_records, int64_t 
                              const int64_t* d_strides, int64_t nheads, int slot, uint8_t* d_samples);
 int ethcnn_bench_copy(ethcnn_ctx* ctx, const void* d_src, void* d_dst, size_t nbytes);
 
+/* ---- threshold calibration: Thr_info.txt from labelled predictions (no reference counterpart: the reference ships hand-set values,
+ *      0.5 x 6 for All-Intra and 0.4 0.6 0.3 0.7 0.2 0.8 for LDP).  HM takes "split only" when p > up[depth] and "current only" when
+ *      p <= down[depth] and runs the full rate-distortion search in between (HM-16.5_Test_AI/.../TEncCu.cpp:448-455).  A calibrator
+ *      counts, on the GPU, where the probabilities of truly split and truly unsplit samples fall; the choice and the file are host work.
+ *   Truth and populations (tools/score_cu_depth.py:47-65 in integers).  A CTU carries 16 depth bytes d[0..15] (0..3, the 4 x 4 raster of
+ *      its 16 x 16 blocks) and 21 probabilities p[0..20]; IDX32 = {{0,1,4,5},{2,3,6,7},{8,9,12,13},{10,11,14,15}}.
+ *        level 0: every CTU,                                          probability p[0],               split when t64 = (sum d > 8)
+ *        level 1: each 32 x 32 block j of a CTU with t64,              probability p[1 + j],           split when t32[j] = (sum_i d[IDX32[j][i]] > 6)
+ *        level 2: each 16 x 16 block i of a block j with t64 and t32[j], probability p[5 + IDX32[j][i]], split when d[IDX32[j][i]] == 3
+ *   Bins: 1025 per (level, truth).  bin(p) = ceil(p * 1024) in fp32 (the product is exact): bin 0 holds p == 0, bin j >= 1 holds
+ *      (j - 1) / 1024 < p <= j / 1024.  So HM's comparisons are exact on the grid t_k = k / 1024: p > t_k <=> bin > k, p <= t_k <=> bin <= k.
+ *      A probability that is NaN, below 0 or above 1 is counted in rejected[level] and binned nowhere.  A depth byte above 3 fails the
+ *      call with ETHCNN_ERR_FORMAT (the kernel raises a flag word that the host reads; nothing faults) and the call adds NOTHING.
+ *   Accumulator: hist[3][2][1025] (level, truth, bin) and rejected[3], uint64; over frame layouts also skipped_partial.  Counts are exact
+ *      integers and do not depend on the grid, on the order of calls or on how a set is split over calls.
+ *   Layouts.  Per-CTU: probs float32 [n][21], depth16 uint8 [n][16] (a training sample's label bytes).  Frame: labels uint8
+ *      [skip_label_frames + nframes][height / 16][width / 16] (an Info_*_CUDepth.dat; width and height multiples of 16, else
+ *      ETHCNN_ERR_ARG), of which the first skip_label_frames frames are passed over (tools/score_cu_depth.py --skip-label-frames: LDP
+ *      predictions start at POC 1); probs float32 [nframes][ceil(height / 64) * ceil(width / 64)][21].  The kernel gathers each CTU's
+ *      4 x 4 map itself.  A CTU that is not wholly inside the picture is left out and counted in skipped_partial: HM forces those
+ *      splits and they have no full label map.
+ *   Gates: the predictors' batch gates zero whole sub-batches of p32 / p16, so the probabilities must have been predicted with open
+ *      gates, ethcnn_set_thresholds(ctx, 0, 0).  The calibrator cannot see how a buffer it is given was made.
+ *   Every add entry is synchronous (it waits for the flag word); device pointers must be 4-byte aligned.  n == 0 / nframes == 0: no-op.
+ *   Errors: the usual codes, text in ethcnn_last_error of the calibrator's context (of NULL for the two context-free entries). */
+typedef struct ethcnn_calib ethcnn_calib;
+#define ETHCNN_CALIB_BINS 1025
+#define ETHCNN_CALIB_HIST_WORDS (3 * 2 * ETHCNN_CALIB_BINS)
+int ethcnn_calib_create(ethcnn_ctx* ctx, ethcnn_calib** out);
+void ethcnn_calib_destroy(ethcnn_calib* cal); /* before ethcnn_destroy of its context */
+int ethcnn_calib_reset(ethcnn_calib* cal);
+int ethcnn_calib_add(ethcnn_calib* cal, const float* probs, const uint8_t* depth16, int64_t n); /* host pointers, staged in pieces */
+int ethcnn_calib_add_device(ethcnn_calib* cal, const float* d_probs, const uint8_t* d_depth16, int64_t n);
+int ethcnn_calib_add_frames(ethcnn_calib* cal, const float* probs, const uint8_t* labels, int width, int height, int64_t nframes,
+                            int64_t skip_label_frames);
+int ethcnn_calib_add_frames_device(ethcnn_calib* cal, const float* d_probs, const uint8_t* d_labels, int width, int height,
+                                   int64_t nframes, int64_t skip_label_frames);
+/* waits for the stream; every pointer may be NULL.  hist: ETHCNN_CALIB_HIST_WORDS words */
+int ethcnn_calib_get(ethcnn_calib* cal, uint64_t* hist, uint64_t rejected[3], uint64_t* skipped_partial);
+/* The choice (pure host, no context).  Budgets in parts per million.  Per level, with N1 / N0 the split / non-split totals,
+ *      miss(k) = sum_{bin <= k} hist[l][1] (truly split, forced to "current only") and fsplit(k) = sum_{bin > k} hist[l][0]:
+ *        down_k = the largest k in -1..1024 with miss(k) * 10^6 <= eps_down_ppm * N1   (-1 always qualifies: "never current only")
+ *        up_k   = the smallest k in 0..1024 with fsplit(k) * 10^6 <= eps_up_ppm * N0   (1024 always qualifies: "never split only")
+ *      (128-bit products).  When down_k > up_k both become the k in [up_k, down_k] with the least miss(k) + fsplit(k), the lowest at
+ *      ties; every k of that range meets both budgets.  Budgets above 10^6 are ETHCNN_ERR_ARG. */
+typedef struct ethcnn_calib_level {
+    uint64_t n0, n1;         /* non-split / split samples of the level                                      */
+    int32_t down_k, up_k;    /* the thresholds are down_k / 1024 and up_k / 1024                            */
+    double down, up;
+    uint64_t miss, fsplit;   /* miss(down_k), fsplit(up_k)                                                  */
+    uint64_t uncertain;      /* samples of either truth with down_k < bin <= up_k: the full search remains  */
+    double uncertain_share;  /* uncertain / (n0 + n1); 0 for a level without samples                        */
+    double accuracy_512;     /* accuracy of the plain decision p > 0.5; 0 for a level without samples       */
+    int32_t empty_class;     /* n0 == 0 or n1 == 0: the budgets constrain nothing on that side              */
+    int32_t crossed;         /* down_k > up_k before the joint choice                                       */
+} ethcnn_calib_level;
+typedef struct ethcnn_calib_report {
+    ethcnn_calib_level level[3];
+} ethcnn_calib_report;
+int ethcnn_calib_choose(const uint64_t* hist, const uint32_t eps_down_ppm[3], const uint32_t eps_up_ppm[3], ethcnn_calib_report* report);
+/* One line of six values k / 1024 with 10 decimals (every k / 1024 has at most 10, so fscanf("%f") and float() read it back exactly),
+ * temp file + rename.  THE TWO ENCODERS DIFFER in token order:
+ *   ETHCNN_THR_ORDER_AI   up1 down1 up2 down2 up3 down3   (HM-16.5_Test_AI/source/Lib/TLibEncoder/TEncCu.cpp:250)
+ *   ETHCNN_THR_ORDER_LDP  down1 up1 down2 up2 down3 up3   (HM-16.5_Test_LDP/source/Lib/TLibEncoder/TEncGOP.cpp:1449)
+ * The predictors (ethcnn_load_thresholds) read tokens [1] and [3] of either file, as the reference's do. */
+enum { ETHCNN_THR_ORDER_AI = 0, ETHCNN_THR_ORDER_LDP = 1 };
+int ethcnn_calib_write_thr_info(const char* path, const ethcnn_calib_report* report, int order);
+
 #ifdef __cplusplus
 }
 #endif

@@ -1,0 +1,236 @@
+#!/usr/bin/env python
+"""Calibrates Thr_info.txt -- the upper / lower threshold of each of the three partition levels -- from labelled predictions.
+
+HM takes "split only" when p > up[depth] and "current only" when p <= down[depth] and runs the full rate-distortion search in
+between, so the six values decide both how often the encoder is forced into a wrong partition and how much of the search it still
+runs.  This tool counts, on the GPU, where the probabilities of truly split and truly unsplit CTUs / 32x32 / 16x16 blocks fall
+(1025 bins per level and truth: include/ethcnn.h "threshold calibration"; truth as in tools/score_cu_depth.py) and picks, per level,
+the largest `down` that wrongly stops at most --eps-down parts per million of the truly split samples and the smallest `up` that
+wrongly forces at most --eps-up parts per million of the truly unsplit ones.
+
+    calibrate_thresholds.py [--eps-down E1 E2 E3] [--eps-up E1 E2 E3] [--out Thr_info.txt --order ai|ldp] [--hist FILE] [--json] [--device N]
+                            CASE...
+
+Any number of cases, accumulated into one histogram:
+
+  --case LABELS PROBS W H [--skip-label-frames N]
+        the scorer's inputs: an Info_*_CUDepth.dat and a cu_depth.dat (float32 [frames][ctus][21]).  THE FILE MUST HAVE BEEN
+        PREDICTED WITH OPEN GATES (a Thr_info.txt of zeros / set_thresholds(0, 0)): the predictors' batch gates zero whole
+        sub-batches of p32 / p16, and this tool cannot know how a file it is given was made.
+  --yuv SEQ W H QP --labels L --model-dir D [--ldp [--frame-begin 1]]
+        predicts SEQ itself, gates open, into a temporary file and adds it.  All-Intra: D holds the model_2000000_qpXX~YY.dat of
+        the QP band.  --ldp: SEQ is a residual file (frame k = POC k), D holds model_LDP_2000000_qp22~37.dat and the
+        model_LDP_200000_qpXX.dat of the band; frames [frame-begin, end) are predicted and as many label frames passed over.
+  --samples FILE --model PREFIX --qp Q [--net ai|ldp]
+        a trainer's evaluation (forward only, no gates in that graph) of a validation sample file with the checkpoint PREFIX; the
+        truth is the 16 label bytes of QP row Q (All-Intra records: byte 4160 + 16 Q) or of the slot whose QP byte is Q (LDP records).
+
+Budgets default to 50000 ppm (5 %).  --hist FILE also writes the accumulated histogram, uint64 little-endian [3 levels][2 truths][1025 bins].  --order ai writes "up1 down1 up2 down2 up3 down3" (HM-16.5_Test_AI, TEncCu.cpp:250), --order
+ldp writes "down1 up1 down2 up2 down3 up3" (HM-16.5_Test_LDP, TEncGOP.cpp:1449): the two encoders differ.  CTUs that are not wholly
+inside the picture are left out (HM forces their splits).
+"""
+import importlib
+import json
+import os
+import sys
+import tempfile
+
+import numpy as np
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+LDP_CNN_FILE = "model_LDP_2000000_qp22~37.dat"
+
+
+class Usage(Exception):
+    pass
+
+
+def _take(argv, i, n, what):
+    if i + n > len(argv):
+        raise Usage("%s takes %d value(s)" % (what, n))
+    return argv[i:i + n], i + n
+
+
+def parse(argv):
+    """-> (options, cases); the options after a case belong to it"""
+    opt = {"eps_down": [50000] * 3, "eps_up": [50000] * 3, "out": None, "order": None, "hist": None, "json": False, "device": 0}
+    cases, i = [], 0
+    per_case = {"--skip-label-frames": ("skip", int, ("case",)), "--labels": ("labels", str, ("yuv",)), "--model-dir": ("model_dir", str, ("yuv",)),
+                "--frame-begin": ("frame_begin", int, ("yuv",)), "--model": ("model", str, ("samples",)), "--qp": ("qp", int, ("samples",)),
+                "--net": ("net", str, ("samples",))}
+    while i < len(argv):
+        a = argv[i]
+        i += 1
+        if a in ("-h", "--help"):
+            raise Usage("")
+        elif a in ("--eps-down", "--eps-up"):
+            v, i = _take(argv, i, 3, a)
+            opt[a[2:].replace("-", "_")] = [int(x) for x in v]
+        elif a in ("--out", "--order", "--hist", "--device"):
+            v, i = _take(argv, i, 1, a)
+            opt[a[2:]] = int(v[0]) if a == "--device" else v[0]
+        elif a == "--json":
+            opt["json"] = True
+        elif a == "--case":
+            v, i = _take(argv, i, 4, a)
+            cases.append({"kind": "case", "labels": v[0], "probs": v[1], "w": int(v[2]), "h": int(v[3]), "skip": 0})
+        elif a == "--yuv":
+            v, i = _take(argv, i, 4, a)
+            cases.append({"kind": "yuv", "yuv": v[0], "w": int(v[1]), "h": int(v[2]), "qp": int(v[3]), "ldp": False, "frame_begin": 1})
+        elif a == "--samples":
+            v, i = _take(argv, i, 1, a)
+            cases.append({"kind": "samples", "file": v[0], "net": "ai"})
+        elif a == "--ldp":
+            if not cases or cases[-1]["kind"] != "yuv":
+                raise Usage("--ldp follows a --yuv case")
+            cases[-1]["ldp"] = True
+        elif a in per_case:
+            key, conv, kinds = per_case[a]
+            if not cases or cases[-1]["kind"] not in kinds:
+                raise Usage("%s follows a --%s case" % (a, kinds[0]))
+            v, i = _take(argv, i, 1, a)
+            cases[-1][key] = conv(v[0])
+        else:
+            raise Usage("unknown argument %r" % a)
+    if not cases:
+        raise Usage("no case given")
+    for c in cases:
+        need = {"case": (), "yuv": ("labels", "model_dir"), "samples": ("model", "qp")}[c["kind"]]
+        for k in need:
+            if k not in c:
+                raise Usage("a --%s case needs --%s" % (c["kind"], k.replace("_", "-")))
+        if c["kind"] == "samples" and c["net"] not in ("ai", "ldp"):
+            raise Usage("--net is ai or ldp")
+    if (opt["out"] is None) != (opt["order"] is None) or opt["order"] not in (None, "ai", "ldp"):
+        raise Usage("--out PATH and --order ai|ldp go together")
+    for e in opt["eps_down"] + opt["eps_up"]:
+        if not 0 <= e <= 1000000:
+            raise Usage("budgets are parts per million, 0..1000000")
+    return opt, cases
+
+
+def _label_frames(path, w, h):
+    per = (w // 16) * (h // 16)
+    lab = np.fromfile(path, dtype=np.uint8)
+    if w % 16 or h % 16 or lab.size % per:
+        raise ValueError("%s: %d bytes is not a whole number of %dx%d label frames" % (path, lab.size, w, h))
+    return lab, lab.size // per
+
+
+def _add_file_pair(cal, pkg, labels_path, probs_path, w, h, skip, note):
+    lab, lf = _label_frames(labels_path, w, h)
+    probs = np.fromfile(probs_path, dtype="<f4")
+    per = pkg.ethcnn.ctus_per_frame(w, h) * 21
+    if probs.size % per:
+        raise ValueError("%s: %d floats is not a whole number of %dx%d frames" % (probs_path, probs.size, w, h))
+    pf = probs.size // per
+    if skip >= lf:
+        raise ValueError("--skip-label-frames %d: the label file holds %d frames" % (skip, lf))
+    n = min(lf - skip, pf)
+    if lf - skip != pf:
+        note("note: %d labelled frames, %d predicted frames: using the first %d" % (lf - skip, pf, n))
+    cal.add_frames(probs[:n * per], lab, w, h, skip_label_frames=skip, nframes=n)
+    return n
+
+
+def _sample_labels(records, net, qp, pkg):
+    """uint8 file bytes -> (nrecords, depth16 uint8 [n,16]) for the label row / slot of QP qp"""
+    e = pkg.ethcnn
+    if net == "ai":
+        if records.size == 0 or records.size % e.TRAIN_REC:
+            raise ValueError("%d bytes is not a whole number of %d-byte All-Intra records" % (records.size, e.TRAIN_REC))
+        if not 0 <= qp <= 51:
+            raise ValueError("QP %d outside 0..51" % qp)
+        rec = records.reshape(-1, e.TRAIN_REC)
+        return rec.shape[0], np.ascontiguousarray(rec[:, 4160 + 16 * qp: 4176 + 16 * qp])
+    if records.size == 0 or records.size % e.LDP_REC:
+        raise ValueError("%d bytes is not a whole number of %d-byte LDP records" % (records.size, e.LDP_REC))
+    rec = records.reshape(-1, e.LDP_REC)
+    slot_qps = [int(rec[0, e.LDP_SLOT_BASE + e.LDP_SLOT_BYTES * s]) for s in range(4)]
+    if qp not in slot_qps:
+        raise ValueError("QP %d is not one of the file's slot QPs %s" % (qp, slot_qps))
+    at = e.LDP_SLOT_BASE + e.LDP_SLOT_BYTES * slot_qps.index(qp) + 1
+    return rec.shape[0], np.ascontiguousarray(rec[:, at: at + 16])
+
+
+def run(opt, cases, out=sys.stdout, err=sys.stderr):
+    if ROOT not in sys.path:
+        sys.path.insert(0, ROOT)
+    pkg = importlib.import_module("hevc-complexity-reduction_amd")
+    note = lambda s: err.write(s + "\n")
+    ctx = pkg.EthCnn(device=opt["device"])
+    try:
+        cal = pkg.Calibrator(ctx)
+        for c in cases:
+            if c["kind"] == "case":
+                _add_file_pair(cal, pkg, c["labels"], c["probs"], c["w"], c["h"], c["skip"], note)
+            elif c["kind"] == "yuv":
+                w, h, qp, d = c["w"], c["h"], c["qp"], c["model_dir"]
+                with tempfile.TemporaryDirectory() as tmp:
+                    dat = os.path.join(tmp, "cu_depth.dat")
+                    if c["ldp"]:
+                        ctx.load_checkpoint(os.path.join(d, LDP_CNN_FILE))
+                        ctx.load_lstm_checkpoint(os.path.join(d, pkg.ethcnn.lstm_model_name_for_qp(qp)))
+                        ctx.set_thresholds(0.0, 0.0)  # open gates
+                        frames = os.path.getsize(c["yuv"]) // (w * h * 3 // 2)
+                        ctx.ldp_predict_yuv_file(c["yuv"], w, h, qp, dat, c["frame_begin"], frames)
+                        skip = c["frame_begin"]
+                    else:
+                        ctx.load_checkpoint(os.path.join(d, pkg.ethcnn.model_name_for_qp(qp)))
+                        ctx.set_thresholds(0.0, 0.0)  # open gates
+                        ctx.predict_yuv_file(c["yuv"], w, h, qp, dat)
+                        skip = 0
+                    _add_file_pair(cal, pkg, c["labels"], dat, w, h, skip, note)
+            else:
+                records = np.fromfile(c["file"], dtype=np.uint8)
+                n, depth = _sample_labels(records, c["net"], c["qp"], pkg)
+                with pkg.Trainer(ctx, batch=1, dropout=False, net=c["net"]) as tr:
+                    tr.set_blob(pkg.ethcnn.read_ckpt_blob(c["model"]))
+                    tr.set_samples(pkg.ethcnn.SET_VALID, records)
+                    probs = tr.evaluate(pkg.ethcnn.SET_VALID, c["qp"], n=n, want_probs=True)[2]
+                cal.add(probs, depth)
+        hist, rejected, skipped = cal.get()
+        rep = cal.choose(opt["eps_down"], opt["eps_up"])
+        levels = rep.as_dicts()
+        if opt["out"]:
+            cal.write_thr_info(opt["out"], rep, opt["order"])
+        if opt["hist"]:
+            hist.astype("<u8").tofile(opt["hist"])
+    finally:
+        ctx.close()
+    result = {"levels": levels, "rejected": [int(x) for x in rejected], "skipped_partial": skipped,
+              "eps_down_ppm": opt["eps_down"], "eps_up_ppm": opt["eps_up"], "out": opt["out"], "order": opt["order"]}
+    if opt["json"]:
+        out.write(json.dumps(result) + "\n")
+        return result
+    for name, lv, ed, eu, rj in zip(("64x64", "32x32", "16x16"), levels, opt["eps_down"], opt["eps_up"], result["rejected"]):
+        out.write("%s  unsplit %d  split %d  rejected %d%s%s\n" % (name, lv["n0"], lv["n1"], rj, "  EMPTY CLASS" if lv["empty_class"] else "",
+                                                                "  CROSSED (one threshold for both)" if lv["crossed"] else ""))
+        out.write("    down %.10f (k %d)  wrongly stopped %d of %d split (budget %d ppm)\n" % (lv["down"], lv["down_k"], lv["miss"], lv["n1"], ed))
+        out.write("    up   %.10f (k %d)  wrongly forced  %d of %d unsplit (budget %d ppm)\n" % (lv["up"], lv["up_k"], lv["fsplit"], lv["n0"], eu))
+        out.write("    full search remains for %d (%.4f); accuracy at 0.5: %.4f\n" % (lv["uncertain"], lv["uncertain_share"], lv["accuracy_512"]))
+    if skipped:
+        out.write("%d CTUs not wholly inside the picture were left out\n" % skipped)
+    if opt["out"]:
+        out.write("wrote %s (%s order): %s" % (opt["out"], opt["order"], open(opt["out"]).read()))
+    return result
+
+
+def main(argv):
+    try:
+        opt, cases = parse(list(argv[1:]))
+    except (Usage, ValueError) as e:
+        sys.stderr.write(__doc__)
+        if str(e):
+            sys.stderr.write("\nerror: %s\n" % e)
+        return 2
+    try:
+        run(opt, cases)
+    except (ValueError, OSError, RuntimeError) as e:  # (libethcnn errors are RuntimeErrors)
+        sys.stderr.write("error: %s\n" % e)
+        return 1
+    return 0
+
+
+if __name__ == "__main__":
+    sys.exit(main(sys.argv))
