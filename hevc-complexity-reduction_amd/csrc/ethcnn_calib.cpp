@@ -263,17 +263,15 @@ extern "C" int ethcnn_calib_choose(const uint64_t* hist, const uint32_t eps_down
 
 // HM-16.5_Test_AI/source/Lib/TLibEncoder/TEncCu.cpp:250       fscanf("%f %f %f %f %f %f", &fUp[0], &fDown[0], &fUp[1], &fDown[1], &fUp[2], &fDown[2])
 // HM-16.5_Test_LDP/source/Lib/TLibEncoder/TEncGOP.cpp:1449    fscanf("%f %f %f %f %f %f", &fDown[0], &fUp[0], &fDown[1], &fUp[1], &fDown[2], &fUp[2])
-extern "C" int ethcnn_calib_write_thr_info(const char* path, const ethcnn_calib_report* rep, int order) {
-    if (!path || !rep) return set_err(nullptr, ETHCNN_ERR_ARG, "ethcnn_calib_write_thr_info: null argument");
+int ethcnn::calib::write_thr_line(const char* path, const int32_t down_k[3], const int32_t up_k[3], int order, const char* entry) {
     if (order != ETHCNN_THR_ORDER_AI && order != ETHCNN_THR_ORDER_LDP)
-        return set_err(nullptr, ETHCNN_ERR_ARG, "ethcnn_calib_write_thr_info: order %d is neither ETHCNN_THR_ORDER_AI nor ETHCNN_THR_ORDER_LDP", order);
+        return set_err(nullptr, ETHCNN_ERR_ARG, "%s: order %d is neither ETHCNN_THR_ORDER_AI nor ETHCNN_THR_ORDER_LDP", entry, order);
     double v[6];
     for (int l = 0; l < 3; ++l) {
-        const ethcnn_calib_level& r = rep->level[l];
-        if (r.down_k < -1 || r.down_k > 1024 || r.up_k < 0 || r.up_k > 1024)
-            return set_err(nullptr, ETHCNN_ERR_ARG, "ethcnn_calib_write_thr_info: level %d holds k = %d / %d outside -1..1024 / 0..1024", l + 1, r.down_k, r.up_k);
-        v[2 * l + (order == ETHCNN_THR_ORDER_AI ? 1 : 0)] = r.down_k / 1024.0;
-        v[2 * l + (order == ETHCNN_THR_ORDER_AI ? 0 : 1)] = r.up_k / 1024.0;
+        if (down_k[l] < -1 || down_k[l] > 1024 || up_k[l] < 0 || up_k[l] > 1024)
+            return set_err(nullptr, ETHCNN_ERR_ARG, "%s: level %d holds k = %d / %d outside -1..1024 / 0..1024", entry, l + 1, down_k[l], up_k[l]);
+        v[2 * l + (order == ETHCNN_THR_ORDER_AI ? 1 : 0)] = down_k[l] / 1024.0;
+        v[2 * l + (order == ETHCNN_THR_ORDER_AI ? 0 : 1)] = up_k[l] / 1024.0;
     }
     const std::string tmp = std::string(path) + ".tmp." + std::to_string((long)getpid());  // never a partial Thr_info.txt
     FILE* f = std::fopen(tmp.c_str(), "w");
@@ -285,4 +283,11 @@ extern "C" int ethcnn_calib_write_thr_info(const char* path, const ethcnn_calib_
     if (!rc && std::rename(tmp.c_str(), path) != 0) rc = set_err(nullptr, ETHCNN_ERR_IO, "rename %s -> %s failed: %s", tmp.c_str(), path, std::strerror(errno));
     if (rc) std::remove(tmp.c_str());
     return rc;
+}
+
+extern "C" int ethcnn_calib_write_thr_info(const char* path, const ethcnn_calib_report* rep, int order) {
+    if (!path || !rep) return set_err(nullptr, ETHCNN_ERR_ARG, "ethcnn_calib_write_thr_info: null argument");
+    const int32_t down_k[3] = {rep->level[0].down_k, rep->level[1].down_k, rep->level[2].down_k};
+    const int32_t up_k[3] = {rep->level[0].up_k, rep->level[1].up_k, rep->level[2].up_k};
+    return write_thr_line(path, down_k, up_k, order, "ethcnn_calib_write_thr_info");
 }

@@ -33,6 +33,8 @@ struct Geom {
 // n CTUs (frame layout: n = frames * ctus_w * ctus_h; labels point at the first scored label frame)
 void launch_count(hipStream_t s, const float* probs, const uint8_t* labels, long n, const Geom& g, unsigned long long* call, int cus);
 void launch_commit(hipStream_t s, unsigned long long* acc, unsigned long long* call);
+// ethcnn_calib.cpp: the Thr_info.txt line of six grid values (temp file + rename), behind both writer entries of include/ethcnn.h
+int write_thr_line(const char* path, const int32_t down_k[3], const int32_t up_k[3], int order, const char* entry);
 
 }  // namespace calib
 }  // namespace ethcnn

@@ -199,6 +199,18 @@ SIGNATURES = {
     "ethcnn_calib_get": (_i, [_vp, _vp, _vp, ctypes.POINTER(ctypes.c_uint64)]),
     "ethcnn_calib_choose": (_i, [_vp, ctypes.POINTER(ctypes.c_uint32), ctypes.POINTER(ctypes.c_uint32), _vp]),
     "ethcnn_calib_write_thr_info": (_i, [_cp, _vp, _i]),
+    "ethcnn_sim_create": (_i, [_vp, ctypes.POINTER(_vp)]),
+    "ethcnn_sim_destroy": (None, [_vp]),
+    "ethcnn_sim_reset": (_i, [_vp]),
+    "ethcnn_sim_add": (_i, [_vp, _vp, _vp, ctypes.c_int64]),
+    "ethcnn_sim_add_device": (_i, [_vp, _vp, _vp, ctypes.c_int64]),
+    "ethcnn_sim_add_frames": (_i, [_vp, _vp, _vp, _i, _i, ctypes.c_int64, ctypes.c_int64]),
+    "ethcnn_sim_add_frames_device": (_i, [_vp, _vp, _vp, _i, _i, ctypes.c_int64, ctypes.c_int64]),
+    "ethcnn_sim_info": (_i, [_vp, _vp]),
+    "ethcnn_sim_eval": (_i, [_vp, _vp, ctypes.c_int64, _i, _vp]),
+    "ethcnn_sim_sweep": (_i, [_vp, _vp, _i, _i, _vp]),
+    "ethcnn_sim_search": (_i, [_vp, _vp, _i, _vp, ctypes.c_uint32, _i, _vp, _vp, ctypes.POINTER(_i)]),
+    "ethcnn_sim_write_thr_info": (_i, [_cp, _vp, _i]),
 }
 
 _lib = None
@@ -1374,3 +1386,156 @@ class Calibrator(object):
 
     def write_thr_info(self, path, report, order):
         write_thr_info(path, report, order, self.lib)
+
+
+# ------------------------------------------------------------------------------------------------------------- simulation ---
+SIM_GATES_NONE, SIM_GATES_AI, SIM_GATES_LDP = 0, 1, 2
+_SIM_GATES = {"none": SIM_GATES_NONE, "ai": SIM_GATES_AI, "ldp": SIM_GATES_LDP}
+SIM_COORDS = ("down0", "up0", "down1", "up1", "down2", "up2")
+# ethcnn_sim_thr / ethcnn_sim_counts as numpy records
+SIM_THR = np.dtype([("up_k", "<i4", (3,)), ("down_k", "<i4", (3,))])
+SIM_COUNTS = np.dtype([("checked", "<u8", (4,)), ("split_only", "<u8", (3,)), ("current_only", "<u8", (3,)), ("both", "<u8", (3,)),
+                       ("edge_split", "<u8", (3,)), ("wrong_split", "<u8", (3,)), ("wrong_stop", "<u8", (3,)), ("bad_ctus", "<u8")])
+SIM_FULL_SEARCH = ((1024, 1024, 1024), (-1, -1, -1))
+
+
+def sim_thr(up_k, down_k):
+    """one candidate (or, from [K, 3] arrays, K of them) as SIM_THR records"""
+    up_k, down_k = np.asarray(up_k, dtype=np.int32), np.asarray(down_k, dtype=np.int32)
+    out = np.zeros(up_k.shape[:-1], SIM_THR)
+    out["up_k"], out["down_k"] = up_k, down_k
+    return out
+
+
+def _sim_cands(cands):
+    cands = np.asarray(cands)
+    if cands.dtype != SIM_THR:  # [K, 2, 3]: (up_k, down_k) rows
+        cands = sim_thr(cands[..., 0, :], cands[..., 1, :])
+    return np.ascontiguousarray(cands).reshape(-1)
+
+
+def sim_write_thr_info(path, thr, order, lib=None):
+    """ethcnn_sim_write_thr_info (host only): one SIM_THR record in the line format and token orders of write_thr_info"""
+    lib = lib or load_library()
+    if order not in _THR_ORDERS:
+        raise ValueError("order is 'ai' or 'ldp', got %r" % (order,))
+    thr = _sim_cands(thr)
+    if thr.size != 1:
+        raise ValueError("one candidate makes one Thr_info.txt, got %d" % thr.size)
+    rc = lib.ethcnn_sim_write_thr_info(os.fsencode(path), thr.ctypes.data, _THR_ORDERS[order])
+    if rc:
+        raise EthCnnError(rc, lib.ethcnn_last_error(None).decode())
+
+
+class PartitionSim(object):
+    """HM's pruned CU search simulated over a set of predicted CTUs that stays in HBM, for any number of candidate Thr_info files at
+    once (include/ethcnn.h "partition-search simulation"): the RD checks that remain per CU size and, with labels, the labelled
+    partitions the pruned search can no longer reach.  gates: "none", "ai" or "ldp"."""
+
+    def __init__(self, ctx):
+        self.ctx, self.lib = ctx, ctx.lib
+        h = ctypes.c_void_p()
+        ctx._chk(self.lib.ethcnn_sim_create(ctx.h, ctypes.byref(h)))
+        self.h = h
+        if not hasattr(ctx, "_trainers"):
+            ctx._trainers = weakref.WeakSet()
+        ctx._trainers.add(self)  # closed with the context, before it
+
+    def _chk(self, rc):
+        self.ctx._chk(rc)
+
+    def close(self):
+        if getattr(self, "h", None):
+            self.lib.ethcnn_sim_destroy(self.h)
+            self.h = None
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+    def __enter__(self):
+        return self
+
+    def __exit__(self, *a):
+        self.close()
+
+    def reset(self):
+        self._chk(self.lib.ethcnn_sim_reset(self.h))
+
+    def add(self, probs, depth16=None):
+        """probs float32 [n, 21], depth16 uint8 [n, 16] or None, in host memory"""
+        probs = np.ascontiguousarray(probs, dtype=np.float32).reshape(-1, NOUT)
+        n = probs.shape[0]
+        if depth16 is not None:
+            depth16 = np.ascontiguousarray(depth16, dtype=np.uint8).reshape(-1, 16)
+            if depth16.shape[0] != n:
+                raise ValueError("%d rows of probabilities, %d of depths" % (n, depth16.shape[0]))
+        self._chk(self.lib.ethcnn_sim_add(self.h, probs.ctypes.data if n else None, depth16.ctypes.data if n and depth16 is not None else None, n))
+
+    def add_device(self, d_probs, d_depth16, n):
+        """the same on buffers in HBM (DeviceBuffer or raw device addresses; d_depth16 may be None)"""
+        ptr = lambda b: getattr(b, "ptr", b)
+        self._chk(self.lib.ethcnn_sim_add_device(self.h, ptr(d_probs), ptr(d_depth16), int(n)))
+
+    def add_frames(self, probs, labels, width, height, skip_label_frames=0, nframes=None):
+        """probs float32 [frames, nctu, 21] (a cu_depth.dat), labels uint8 [skip + frames, height / 16, width / 16] (an
+        Info_*_CUDepth.dat) or None, in host memory; partial CTUs are simulated, labels are used on whole CTUs only"""
+        probs = np.ascontiguousarray(probs, dtype=np.float32)
+        unit = 8 if labels is None else 16
+        nf = 0
+        if width > 0 and height > 0 and width % unit == 0 and height % unit == 0:  # (else the library names the error)
+            per = ctus_per_frame(width, height) * NOUT
+            nf = probs.size // per if nframes is None else int(nframes)
+            if (nframes is None and probs.size % per) or probs.size < nf * per:
+                raise ValueError("%d probabilities are not %s %dx%d frames" % (probs.size, "whole" if nframes is None else "%d" % nf, width, height))
+            if labels is not None:
+                labels = np.ascontiguousarray(labels, dtype=np.uint8)
+                if labels.size < (nf + int(skip_label_frames)) * (width // 16) * (height // 16):
+                    raise ValueError("%d frames (+ %d skipped label frames) need %d label bytes, got %d"
+                                     % (nf, skip_label_frames, (nf + int(skip_label_frames)) * (width // 16) * (height // 16), labels.size))
+        self._chk(self.lib.ethcnn_sim_add_frames(self.h, probs.ctypes.data if probs.size else None,
+                                                 labels.ctypes.data if labels is not None and labels.size else None, int(width), int(height), nf,
+                                                 int(skip_label_frames)))
+
+    def add_frames_device(self, d_probs, d_labels, width, height, nframes, skip_label_frames=0):
+        """the same on buffers in HBM, e.g. the output ldp_sequence_device left there (d_labels may be None)"""
+        ptr = lambda b: getattr(b, "ptr", b)
+        self._chk(self.lib.ethcnn_sim_add_frames_device(self.h, ptr(d_probs), ptr(d_labels), int(width), int(height), int(nframes),
+                                                        int(skip_label_frames)))
+
+    def info(self):
+        """dict: ctus, whole_ctus, labelled_ctus, rejected_ctus, sub_batches (all independent of the candidate)"""
+        v = (ctypes.c_uint64 * 5)()
+        self._chk(self.lib.ethcnn_sim_info(self.h, v))
+        return dict(zip(("ctus", "whole_ctus", "labelled_ctus", "rejected_ctus", "sub_batches"), (int(x) for x in v)))
+
+    def eval(self, cands, gates="none"):
+        """cands: SIM_THR records, or integers [K, 2, 3] = (up_k, down_k) rows -> SIM_COUNTS records [K]"""
+        cands = _sim_cands(cands)
+        out = np.zeros(cands.size, SIM_COUNTS)
+        self._chk(self.lib.ethcnn_sim_eval(self.h, cands.ctypes.data if cands.size else None, cands.size, _SIM_GATES[gates],
+                                           out.ctypes.data if cands.size else None))
+        return out
+
+    def sweep(self, base, coord, gates="none"):
+        """every value of one coordinate ("down0", "up0", ... or 0..5) around `base` -> (values int32 [m], SIM_COUNTS records [m])"""
+        coord = SIM_COORDS.index(coord) if coord in SIM_COORDS else int(coord)
+        base = _sim_cands(base)
+        out = np.zeros(1026, SIM_COUNTS)
+        self._chk(self.lib.ethcnn_sim_sweep(self.h, base.ctypes.data, coord, _SIM_GATES[gates], out.ctypes.data))
+        lo = 0 if coord & 1 else -1
+        return np.arange(lo, 1025, dtype=np.int32), out[:1025 - lo]
+
+    def search(self, start, gates, weights, max_bad_ppm, max_rounds=16):
+        """coordinate descent from `start` -> (SIM_THR record, SIM_COUNTS record, rounds)"""
+        start = _sim_cands(start)
+        w = (ctypes.c_uint64 * 4)(*[int(x) for x in weights])
+        thr, counts, rounds = np.zeros(1, SIM_THR), np.zeros(1, SIM_COUNTS), ctypes.c_int(0)
+        self._chk(self.lib.ethcnn_sim_search(self.h, start.ctypes.data, _SIM_GATES[gates], w, int(max_bad_ppm), int(max_rounds), thr.ctypes.data,
+                                             counts.ctypes.data, ctypes.byref(rounds)))
+        return thr[0], counts[0], rounds.value
+
+    def write_thr_info(self, path, thr, order):
+        sim_write_thr_info(path, thr, order, self.lib)

@@ -732,6 +732,98 @@ int ethcnn_calib_choose(const uint64_t* hist, const uint32_t eps_down_ppm[3], co
 enum { ETHCNN_THR_ORDER_AI = 0, ETHCNN_THR_ORDER_LDP = 1 };
 int ethcnn_calib_write_thr_info(const char* path, const ethcnn_calib_report* report, int order);
 
+/* ---- partition-search simulation: what HM's pruned CU search does under a candidate Thr_info.txt (no reference counterpart).  The
+ *      calibrator above counts teacher-forced populations and knows no cost; a simulator evaluates HM's three-way rule
+ *      (HM-16.5_Test_AI/source/Lib/TLibEncoder/TEncCu.cpp:419-463; HM-16.5_Test_LDP/.../TEncCu.cpp:421-470 is identical) over every
+ *      CTU of a set that stays in HBM, for any number of candidate files at once, and counts the rate-distortion (RD) checks that
+ *      remain and, with labels, the labelled partitions the pruned search can no longer reach.
+ *   The rule.  A CU of size s = 64 >> depth has its top-left luma sample at (x, y) of a W x H picture (W, H multiples of 8, as HM
+ *      requires; else ETHCNN_ERR_ARG).  A CTU's 64 x 64 CU is visited; a visited CU is treated by the first line that applies:
+ *        1. x >= W or y >= H: not visited at all (HM's own sub-CU loop).
+ *        2. s == 8: checked, no recursion.  checked[3] += 1.
+ *        3. x + s > W or y + s > H (the frame edge): nothing is checked, its four sub-CUs are visited.  edge_split[depth] += 1.
+ *           (HM writes uiRPelX >= iWidth || uiBPelY > iHeight with uiRPelX = x + s - 1; for W, H multiples of 8 the > and >= forms
+ *           coincide.)
+ *        4. else a DECIDED NODE with probability p[0] (64), p[1 + x32 + 2 y32] (32) or p[5 + x16 + 4 y16] (16), x32 .. y16 the block
+ *           coordinates inside the CTU, and bin = ceil(p * 1024) in fp32 exactly as in the calibration block.  A candidate is six
+ *           integers on that grid, up_k[3] in 0..1024 and down_k[3] in -1..1024 (else ETHCNN_ERR_ARG); with d = depth, in HM's order:
+ *             bin > up_k[d]         SPLIT ONLY    nothing is checked, the four sub-CUs are visited   split_only[d] += 1
+ *             else bin <= down_k[d] CURRENT ONLY  the CU is checked, no recursion                    current_only[d] += 1, checked[d] += 1
+ *             else                  BOTH          the CU is checked, the four sub-CUs are visited    both[d] += 1, checked[d] += 1
+ *           down_k > up_k is allowed: the order of the tests decides.
+ *      up_k = 1024, down_k = -1 on all levels is the full search: every node lands in BOTH.
+ *   Gates.  The predictors zero whole sub-batches of p32 / p16 (<= 1024 consecutive CTUs of one frame), so in the frame layouts each
+ *      sub-batch carries M1 = max bin(p[0]) and M2 = max bin(p[1..4]) over its CTUs' probabilities as given.  With gate thresholds
+ *      g1, g2:  gate 1 is open <=> M1 > g1;  gate 2 is open <=> (gate 1 open ? M2 : 0) > g2;  a closed gate 1 makes every p32 bin of
+ *      the sub-batch 0, a closed gate 2 every p16 bin (bin 0 against down_k = -1 lands in BOTH: the "0 > thr2" corner).  gate_order:
+ *        ETHCNN_SIM_GATES_NONE  no gates: the probabilities are what the encoder will read
+ *        ETHCNN_SIM_GATES_AI    g1 = down_k[0], g2 = down_k[1]  (tokens [1], [3] of an AI-order file; while down_k <= up_k on levels 0
+ *                                                                and 1 these gates change no decision)
+ *        ETHCNN_SIM_GATES_LDP   g1 = up_k[0],   g2 = up_k[1]    (tokens [1], [3] of an LDP-order file; these do change decisions, as
+ *                                                                the reference's predictor does under such a file)
+ *      CTUs added in the per-CTU layout belong to no sub-batch and are never gated.  For the gated orders the probabilities must have
+ *      been predicted with open gates, as for the calibrator.
+ *   Truth.  Labels are optional (NULL) in every add entry and are used on CTUs wholly inside the picture only; with labels, width and
+ *      height must be multiples of 16 (else ETHCNN_ERR_ARG).  A depth byte above 3 fails the call with ETHCNN_ERR_FORMAT and the call
+ *      adds NOTHING.  Flags as in the calibration block: node 64 is split when sum d > 8, node 32 j when sum_i d[IDX32[j][i]] > 6, node
+ *      16 when d == 3.  Every decided node of a labelled CTU is judged by its own flag, whatever happened above it:
+ *        wrong_split[d]  SPLIT ONLY on a node whose flag is unsplit      wrong_stop[d]  CURRENT ONLY on a node whose flag is split
+ *        bad_ctus        labelled CTUs with at least one wrong node: if the full search would return the labelled partition, the
+ *                        pruned search can no longer reach it
+ *   A CTU with a NaN, a negative or a > 1 value among its 21 probabilities is left out of everything (counters, M1 / M2, labels) and
+ *      counted in rejected_ctus.
+ *   Everything is integers; counters are uint64 and do not depend on the grid, on the order of add calls or on how a set is split
+ *      over calls.  The set costs 64 bytes per CTU of device memory (+ 8 per sub-batch); when it cannot grow the add fails with
+ *      ETHCNN_ERR_NOMEM (the byte count is in the message) and changes nothing.
+ *   Layouts: as for the calibrator (per-CTU: probs [n][21], depth16 [n][16] or NULL; frame: probs [nframes][ceil(H / 64) *
+ *      ceil(W / 64)][21], labels [skip_label_frames + nframes][H / 16][W / 16] or NULL).  Every entry is synchronous on the context's
+ *      stream; device pointers must be 4-byte aligned; n == 0 / nframes == 0 is a no-op. */
+typedef struct ethcnn_sim ethcnn_sim;
+enum { ETHCNN_SIM_GATES_NONE = 0, ETHCNN_SIM_GATES_AI = 1, ETHCNN_SIM_GATES_LDP = 2 };
+typedef struct ethcnn_sim_thr {
+    int32_t up_k[3];   /* 0..1024  */
+    int32_t down_k[3]; /* -1..1024 */
+} ethcnn_sim_thr;
+typedef struct ethcnn_sim_counts {
+    uint64_t checked[4];      /* CUs of 64, 32, 16, 8 that are RD-checked */
+    uint64_t split_only[3], current_only[3], both[3]; /* decided nodes by outcome */
+    uint64_t edge_split[3];   /* visited CUs that cross the frame edge */
+    uint64_t wrong_split[3], wrong_stop[3], bad_ctus; /* labelled CTUs only */
+} ethcnn_sim_counts;
+typedef struct ethcnn_sim_set_info { /* all independent of the candidate */
+    uint64_t ctus;          /* CTUs added, the rejected ones included */
+    uint64_t whole_ctus;    /* not rejected and wholly inside the picture */
+    uint64_t labelled_ctus; /* of those, with labels */
+    uint64_t rejected_ctus;
+    uint64_t sub_batches;
+} ethcnn_sim_set_info;
+int ethcnn_sim_create(ethcnn_ctx* ctx, ethcnn_sim** out);
+void ethcnn_sim_destroy(ethcnn_sim* sim); /* before ethcnn_destroy of its context */
+int ethcnn_sim_reset(ethcnn_sim* sim);    /* empties the set; its device memory is kept */
+int ethcnn_sim_add(ethcnn_sim* sim, const float* probs, const uint8_t* depth16, int64_t n); /* host pointers, staged in pieces */
+int ethcnn_sim_add_device(ethcnn_sim* sim, const float* d_probs, const uint8_t* d_depth16, int64_t n);
+int ethcnn_sim_add_frames(ethcnn_sim* sim, const float* probs, const uint8_t* labels, int width, int height, int64_t nframes,
+                          int64_t skip_label_frames);
+int ethcnn_sim_add_frames_device(ethcnn_sim* sim, const float* d_probs, const uint8_t* d_labels, int width, int height, int64_t nframes,
+                                 int64_t skip_label_frames);
+int ethcnn_sim_info(ethcnn_sim* sim, ethcnn_sim_set_info* info);
+/* out[c] = the counters of candidate cand[c] over the whole set; ncand == 0 is a no-op, an empty set gives zeroed output */
+int ethcnn_sim_eval(ethcnn_sim* sim, const ethcnn_sim_thr* cand, int64_t ncand, int gate_order, ethcnn_sim_counts* out);
+/* One eval over every value of one coordinate, the other five as in base.  coord 0..5 = down0, up0, down1, up1, down2, up2;
+ * out[i] is the value -1 + i of a down (ETHCNN_SIM_SWEEP_MAX = 1026 entries) or i of an up (1025 entries). */
+#define ETHCNN_SIM_SWEEP_MAX 1026
+int ethcnn_sim_sweep(ethcnn_sim* sim, const ethcnn_sim_thr* base, int coord, int gate_order, ethcnn_sim_counts* out);
+/* Coordinate descent made of sweeps.  cost = sum_d weight[d] * checked[d]; a candidate is feasible <=> bad_ctus * 10^6 <=
+ * max_bad_ppm * labelled_ctus (128-bit products, as in ethcnn_calib_choose).  A round sweeps the coordinates in the order above and
+ * sets each to its feasible value of least cost, the smallest k at ties; the search stops after a round that changes nothing or after
+ * max_rounds rounds (rounds_out = rounds run, 0 allowed).  start infeasible, no labelled CTU, max_bad_ppm > 10^6 or max_rounds < 0:
+ * ETHCNN_ERR_ARG.  The full search is always feasible, and its cost is the denominator of every "share of the full search".
+ * counts_out / rounds_out may be NULL. */
+int ethcnn_sim_search(ethcnn_sim* sim, const ethcnn_sim_thr* start, int gate_order, const uint64_t weight[4], uint32_t max_bad_ppm,
+                      int max_rounds, ethcnn_sim_thr* thr_out, ethcnn_sim_counts* counts_out, int* rounds_out);
+/* the line and token orders of ethcnn_calib_write_thr_info, from six grid values (host only, no context) */
+int ethcnn_sim_write_thr_info(const char* path, const ethcnn_sim_thr* thr, int order);
+
 #ifdef __cplusplus
 }
 #endif

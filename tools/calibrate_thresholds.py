@@ -51,8 +51,9 @@ def _take(argv, i, n, what):
     return argv[i:i + n], i + n
 
 
-def parse(argv):
-    """-> (options, cases); the options after a case belong to it"""
+def parse(argv, labels_optional=False):
+    """-> (options, cases); the options after a case belong to it.  labels_optional: a --yuv case may come without --labels (the
+    simulation tool, which shares this command line's cases)"""
     opt = {"eps_down": [50000] * 3, "eps_up": [50000] * 3, "out": None, "order": None, "hist": None, "json": False, "device": 0}
     cases, i = [], 0
     per_case = {"--skip-label-frames": ("skip", int, ("case",)), "--labels": ("labels", str, ("yuv",)), "--model-dir": ("model_dir", str, ("yuv",)),
@@ -95,7 +96,7 @@ def parse(argv):
     if not cases:
         raise Usage("no case given")
     for c in cases:
-        need = {"case": (), "yuv": ("labels", "model_dir"), "samples": ("model", "qp")}[c["kind"]]
+        need = {"case": (), "yuv": ("model_dir",) if labels_optional else ("labels", "model_dir"), "samples": ("model", "qp")}[c["kind"]]
         for k in need:
             if k not in c:
                 raise Usage("a --%s case needs --%s" % (c["kind"], k.replace("_", "-")))
@@ -118,12 +119,16 @@ def _label_frames(path, w, h):
 
 
 def _add_file_pair(cal, pkg, labels_path, probs_path, w, h, skip, note):
-    lab, lf = _label_frames(labels_path, w, h)
+    """labels_path None (the simulation tool only): every predicted frame, without labels"""
     probs = np.fromfile(probs_path, dtype="<f4")
     per = pkg.ethcnn.ctus_per_frame(w, h) * 21
     if probs.size % per:
         raise ValueError("%s: %d floats is not a whole number of %dx%d frames" % (probs_path, probs.size, w, h))
     pf = probs.size // per
+    if labels_path is None:
+        cal.add_frames(probs, None, w, h, nframes=pf)
+        return pf
+    lab, lf = _label_frames(labels_path, w, h)
     if skip >= lf:
         raise ValueError("--skip-label-frames %d: the label file holds %d frames" % (skip, lf))
     n = min(lf - skip, pf)
@@ -153,6 +158,38 @@ def _sample_labels(records, net, qp, pkg):
     return rec.shape[0], np.ascontiguousarray(rec[:, at: at + 16])
 
 
+def add_cases(pkg, ctx, cal, cases, note):
+    """feeds every case into `cal`: a Calibrator, or anything with its add / add_frames (the simulation tool's PartitionSim)"""
+    for c in cases:
+        if c["kind"] == "case":
+            _add_file_pair(cal, pkg, c["labels"], c["probs"], c["w"], c["h"], c["skip"], note)
+        elif c["kind"] == "yuv":
+            w, h, qp, d = c["w"], c["h"], c["qp"], c["model_dir"]
+            with tempfile.TemporaryDirectory() as tmp:
+                dat = os.path.join(tmp, "cu_depth.dat")
+                if c["ldp"]:
+                    ctx.load_checkpoint(os.path.join(d, LDP_CNN_FILE))
+                    ctx.load_lstm_checkpoint(os.path.join(d, pkg.ethcnn.lstm_model_name_for_qp(qp)))
+                    ctx.set_thresholds(0.0, 0.0)  # open gates
+                    frames = os.path.getsize(c["yuv"]) // (w * h * 3 // 2)
+                    ctx.ldp_predict_yuv_file(c["yuv"], w, h, qp, dat, c["frame_begin"], frames)
+                    skip = c["frame_begin"]
+                else:
+                    ctx.load_checkpoint(os.path.join(d, pkg.ethcnn.model_name_for_qp(qp)))
+                    ctx.set_thresholds(0.0, 0.0)  # open gates
+                    ctx.predict_yuv_file(c["yuv"], w, h, qp, dat)
+                    skip = 0
+                _add_file_pair(cal, pkg, c.get("labels"), dat, w, h, skip, note)
+        else:
+            records = np.fromfile(c["file"], dtype=np.uint8)
+            n, depth = _sample_labels(records, c["net"], c["qp"], pkg)
+            with pkg.Trainer(ctx, batch=1, dropout=False, net=c["net"]) as tr:
+                tr.set_blob(pkg.ethcnn.read_ckpt_blob(c["model"]))
+                tr.set_samples(pkg.ethcnn.SET_VALID, records)
+                probs = tr.evaluate(pkg.ethcnn.SET_VALID, c["qp"], n=n, want_probs=True)[2]
+            cal.add(probs, depth)
+
+
 def run(opt, cases, out=sys.stdout, err=sys.stderr):
     if ROOT not in sys.path:
         sys.path.insert(0, ROOT)
@@ -161,34 +198,7 @@ def run(opt, cases, out=sys.stdout, err=sys.stderr):
     ctx = pkg.EthCnn(device=opt["device"])
     try:
         cal = pkg.Calibrator(ctx)
-        for c in cases:
-            if c["kind"] == "case":
-                _add_file_pair(cal, pkg, c["labels"], c["probs"], c["w"], c["h"], c["skip"], note)
-            elif c["kind"] == "yuv":
-                w, h, qp, d = c["w"], c["h"], c["qp"], c["model_dir"]
-                with tempfile.TemporaryDirectory() as tmp:
-                    dat = os.path.join(tmp, "cu_depth.dat")
-                    if c["ldp"]:
-                        ctx.load_checkpoint(os.path.join(d, LDP_CNN_FILE))
-                        ctx.load_lstm_checkpoint(os.path.join(d, pkg.ethcnn.lstm_model_name_for_qp(qp)))
-                        ctx.set_thresholds(0.0, 0.0)  # open gates
-                        frames = os.path.getsize(c["yuv"]) // (w * h * 3 // 2)
-                        ctx.ldp_predict_yuv_file(c["yuv"], w, h, qp, dat, c["frame_begin"], frames)
-                        skip = c["frame_begin"]
-                    else:
-                        ctx.load_checkpoint(os.path.join(d, pkg.ethcnn.model_name_for_qp(qp)))
-                        ctx.set_thresholds(0.0, 0.0)  # open gates
-                        ctx.predict_yuv_file(c["yuv"], w, h, qp, dat)
-                        skip = 0
-                    _add_file_pair(cal, pkg, c["labels"], dat, w, h, skip, note)
-            else:
-                records = np.fromfile(c["file"], dtype=np.uint8)
-                n, depth = _sample_labels(records, c["net"], c["qp"], pkg)
-                with pkg.Trainer(ctx, batch=1, dropout=False, net=c["net"]) as tr:
-                    tr.set_blob(pkg.ethcnn.read_ckpt_blob(c["model"]))
-                    tr.set_samples(pkg.ethcnn.SET_VALID, records)
-                    probs = tr.evaluate(pkg.ethcnn.SET_VALID, c["qp"], n=n, want_probs=True)[2]
-                cal.add(probs, depth)
+        add_cases(pkg, ctx, cal, cases, note)
         hist, rejected, skipped = cal.get()
         rep = cal.choose(opt["eps_down"], opt["eps_up"])
         levels = rep.as_dicts()
