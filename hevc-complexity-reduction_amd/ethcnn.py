@@ -211,6 +211,20 @@ SIGNATURES = {
     "ethcnn_sim_sweep": (_i, [_vp, _vp, _i, _i, _vp]),
     "ethcnn_sim_search": (_i, [_vp, _vp, _i, _vp, ctypes.c_uint32, _i, _vp, _vp, ctypes.POINTER(_i)]),
     "ethcnn_sim_write_thr_info": (_i, [_cp, _vp, _i]),
+    "ethcnn_replay_plan": (_i, [_vp, _sz, _vp, _i, ctypes.POINTER(_i), _vp, ctypes.c_char_p, _sz]),
+    "ethcnn_replay_uncut_device": (_i, [_vp, _vp, ctypes.c_int64, _vp, ctypes.c_int64, _i, _i, _i, _vp, _vp]),
+    "ethcnn_replay_create": (_i, [_vp, ctypes.c_uint64, ctypes.POINTER(_vp)]),
+    "ethcnn_replay_destroy": (None, [_vp]),
+    "ethcnn_replay_last_error": (_cp, [_vp]),
+    "ethcnn_replay_open_set": (_i, [_vp, _vp]),
+    "ethcnn_replay_open_records": (_i, [_vp, _vp, _sz]),
+    "ethcnn_replay_run_count": (_i, [_vp]),
+    "ethcnn_replay_run_info": (_i, [_vp, _i, _vp]),
+    "ethcnn_replay_set_chunk_frames": (_i, [_vp, _i]),
+    "ethcnn_replay_run_bytes": (ctypes.c_int64, [_vp, _i, _i, _i]),
+    "ethcnn_replay_run_device": (_i, [_vp, _i, _i, _vp, _vp]),
+    "ethcnn_replay_feed_calib": (_i, [_vp, _i, _i, _vp]),
+    "ethcnn_replay_feed_sim": (_i, [_vp, _i, _i, _vp]),
 }
 
 _lib = None
@@ -1539,3 +1553,162 @@ class PartitionSim(object):
 
     def write_thr_info(self, path, thr, order):
         sim_write_thr_info(path, thr, order, self.lib)
+
+
+# ------------------------------------------------------------------------------------------------------ sample-set replay ---
+class ReplayRun(ctypes.Structure):
+    _fields_ = [("seq", ctypes.c_int32), ("w", ctypes.c_int32), ("h", ctypes.c_int32), ("rows", ctypes.c_int32), ("cols", ctypes.c_int32),
+                ("f0", ctypes.c_uint32), ("frames", ctypes.c_int64), ("nctu", ctypes.c_int64), ("qp", ctypes.c_int32 * 4),
+                ("src_offset", ctypes.c_int64)]
+
+    def as_dict(self):
+        return {"seq": self.seq, "w": self.w, "h": self.h, "rows": self.rows, "cols": self.cols, "f0": self.f0, "frames": self.frames,
+                "nctu": self.nctu, "qps": [int(q) for q in self.qp]}
+
+
+def _record_bytes(x):
+    """bytes / uint8 array / path of a file of 16516-byte records -> a contiguous uint8 array (a file is mapped, not read)"""
+    if isinstance(x, (str, os.PathLike)):
+        return np.memmap(x, dtype=np.uint8, mode="r") if os.path.getsize(x) else np.empty(0, np.uint8)
+    return np.frombuffer(x, dtype=np.uint8) if isinstance(x, (bytes, bytearray)) else np.ascontiguousarray(x, np.uint8).reshape(-1)
+
+
+def replay_plan(records, lib=None):
+    """ethcnn_replay_plan on uint8 LDP records (host only, any record order): a list of runs, each the dict of ReplayRun.as_dict plus
+    "src", int64 [frames, nctu]: the index of the record at (f0 + frame, line, col), CTUs in raster order.  Raises EthCnnError
+    (ERR_FORMAT) with the record and the rule for an invalid file."""
+    lib = lib or load_library()
+    buf = _record_bytes(records)
+    n = buf.size // LDP_RECORD_BYTES
+    src, nruns, err = np.empty(max(n, 1), np.int64), ctypes.c_int(0), ctypes.create_string_buffer(800)
+    rc = lib.ethcnn_replay_plan(buf.ctypes.data if buf.size else None, buf.size, None, 0, ctypes.byref(nruns), src.ctypes.data, err, 800)
+    runs = (ReplayRun * max(nruns.value, 1))()
+    if not rc:
+        rc = lib.ethcnn_replay_plan(buf.ctypes.data, buf.size, ctypes.byref(runs), nruns.value, ctypes.byref(nruns), None, err, 800)
+    if rc:
+        raise EthCnnError(rc, err.value.decode("utf-8", "replace") or "ethcnn_replay_plan: bad arguments")
+    out = []
+    for r in runs[:nruns.value]:
+        d = r.as_dict()
+        d["src"] = src[r.src_offset: r.src_offset + r.frames * r.nctu].reshape(r.frames, r.nctu).copy()
+        out.append(d)
+    return out
+
+
+def replay_uncut_device(ctx, d_records, nrecords, d_src, nframes, rows, cols, slot, d_resi, d_labels):
+    """ethcnn_replay_uncut_device: the uncut kernel on buffers in HBM (DeviceBuffers or raw device addresses); asynchronous"""
+    ptr = lambda b: getattr(b, "ptr", b)
+    ctx._chk(ctx.lib.ethcnn_replay_uncut_device(ctx.h, ptr(d_records), int(nrecords), ptr(d_src), int(nframes), int(rows), int(cols), int(slot),
+                                                ptr(d_resi), ptr(d_labels)))
+
+
+class Replay(object):
+    """An inter sample set run through the deployed Low-Delay-P chain (include/ethcnn.h "sample-set replay"): the residual pictures and
+    label planes of every sequence the set holds are put back together in HBM, in any record order, and go through ldp_sequence as the
+    daemon would run them.  max_bytes: the most device memory a replay may hold (0 = no limit of its own)."""
+
+    def __init__(self, ctx, max_bytes=0):
+        self.ctx, self.lib = ctx, ctx.lib
+        h = ctypes.c_void_p()
+        ctx._chk(self.lib.ethcnn_replay_create(ctx.h, int(max_bytes), ctypes.byref(h)))
+        self.h = h
+        self._source = None  # a SampleSet that is open stays alive with this object
+        if not hasattr(ctx, "_trainers"):
+            ctx._trainers = weakref.WeakSet()
+        ctx._trainers.add(self)  # closed with the context, before it
+
+    def _chk(self, rc):
+        if rc:
+            raise EthCnnError(rc, self.lib.ethcnn_replay_last_error(self.h).decode())
+
+    def close(self):
+        if getattr(self, "h", None):
+            self.lib.ethcnn_replay_destroy(self.h)
+            self.h = None
+        self._source = None
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+    def __enter__(self):
+        return self
+
+    def __exit__(self, *a):
+        self.close()
+
+    def open(self, x):
+        """x: a built inter SampleSet (read in HBM, left as it is), a uint8 array / bytes of 16516-byte records, or the path of a file
+        of them.  Replaces whatever was open."""
+        self._source = None
+        if isinstance(x, SampleSet):
+            self._chk(self.lib.ethcnn_replay_open_set(self.h, x.h))
+            self._source = x
+            return self
+        buf = _record_bytes(x)
+        self._chk(self.lib.ethcnn_replay_open_records(self.h, buf.ctypes.data if buf.size else None, buf.size))
+        return self
+
+    def set_chunk_frames(self, frames):
+        self._chk(self.lib.ethcnn_replay_set_chunk_frames(self.h, int(frames)))
+
+    def __len__(self):
+        return max(0, int(self.lib.ethcnn_replay_run_count(self.h)))
+
+    def run_info(self, i):
+        r = ReplayRun()
+        self._chk(self.lib.ethcnn_replay_run_info(self.h, int(i), ctypes.byref(r)))
+        return r.as_dict()
+
+    def runs(self):
+        return [self.run_info(i) for i in range(len(self))]
+
+    def slot_of(self, i, qp):
+        """the slot of run i whose QP byte is qp (ValueError when there is none)"""
+        qps = self.run_info(i)["qps"]
+        if int(qp) not in qps:
+            raise ValueError("QP %d is not one of the slot QPs %s of run %d" % (qp, qps, i))
+        return qps.index(int(qp))
+
+    def run_bytes(self, i, own_probs=False, own_labels=False):
+        """device bytes run_device holds for run i (own_*: without a buffer of the caller's)"""
+        n = int(self.lib.ethcnn_replay_run_bytes(self.h, int(i), int(bool(own_probs)), int(bool(own_labels))))
+        self._chk(n if n < 0 else 0)
+        return n
+
+    def run_device(self, i, slot, d_probs=None, d_labels=None):
+        """asynchronous on the context's stream: probabilities float32 [frames, nctu, 21] and labels uint8 [frames, 4 rows, 4 cols] of run
+        i at QP slot `slot` into buffers in HBM (DeviceBuffers or raw addresses; None: the object's own)"""
+        ptr = lambda b: None if b is None else getattr(b, "ptr", b)
+        self._chk(self.lib.ethcnn_replay_run_device(self.h, int(i), int(slot), ptr(d_probs), ptr(d_labels)))
+
+    def run(self, i, slot):
+        """-> (probs float32 [frames, nctu, 21], labels uint8 [frames, 4 rows, 4 cols]) in host memory"""
+        r = self.run_info(i)
+        n = r["frames"] * r["nctu"]
+        dp, dl = DeviceBuffer(self.ctx, n * NOUT * 4), DeviceBuffer(self.ctx, n * 16)
+        try:
+            self.run_device(i, slot, dp, dl)
+            probs = dp.download(np.float32, n * NOUT).reshape(r["frames"], r["nctu"], NOUT)
+            labels = dl.download(np.uint8, n * 16).reshape(r["frames"], 4 * r["rows"], 4 * r["cols"])
+        finally:
+            self.ctx.synchronize()
+            dp.free()
+            dl.free()
+        return probs, labels
+
+    def feed(self, consumer, runs=None, slot=None, qp=None):
+        """replays the listed runs (None: all) at `slot`, or at the slot of each run that holds `qp`, into a Calibrator or a
+        PartitionSim without leaving HBM.  The context's gates should be open (set_thresholds(0, 0)), as for any input of those two."""
+        if (slot is None) == (qp is None):
+            raise ValueError("feed takes slot= or qp=")
+        if isinstance(consumer, Calibrator):
+            fn = self.lib.ethcnn_replay_feed_calib
+        elif isinstance(consumer, PartitionSim):
+            fn = self.lib.ethcnn_replay_feed_sim
+        else:
+            raise TypeError("feed takes a Calibrator or a PartitionSim")
+        for i in (range(len(self)) if runs is None else runs):
+            self._chk(fn(self.h, int(i), int(slot) if slot is not None else self.slot_of(i, qp), consumer.h))

@@ -824,6 +824,94 @@ int ethcnn_sim_search(ethcnn_sim* sim, const ethcnn_sim_thr* start, int gate_ord
 /* the line and token orders of ethcnn_calib_write_thr_info, from six grid values (host only, no context) */
 int ethcnn_sim_write_thr_info(const char* path, const ethcnn_sim_thr* thr, int order);
 
+/* ---- sample-set replay: an inter sample set (LDP_Valid.dat, LDP_Test.dat, plain or _shuffled: the 16516-byte records of "sample sets"
+ *      above) put back together into the residual pictures and label planes it was cut from, and run through the deployed Low-Delay-P
+ *      chain, ethcnn_ldp_sequence_device: forward in time, i_frame % 4 features, the state carried over the whole sequence.  The inverse
+ *      of ethcnn_samples_cut_device plus a plan.  (No reference counterpart: the trainers' own evaluation scores 20-step windows from a
+ *      zero state through the training graph.)
+ *   Header fields of a record: w = u16 at byte 2, h = u16 at byte 4; f = u32 at byte 10, the frame number in encoding order; line = u16 at
+ *      byte 14, col = u16 at byte 16, seq = u16 at byte 18; slot QP q_s = the byte at 64 + 4113 s.  All little-endian.  C = w / 64,
+ *      R = h / 64 (integer divisions), nctu = R C.
+ *   Run: a maximal set of records with the same (seq, w, h).  Runs are ordered by seq, then by first appearance.  A run is valid when
+ *        - its frame numbers form one contiguous range f0..f1,
+ *        - every (f, line, col) with line < R, col < C occurs exactly once,
+ *        - no other (line, col) occurs,
+ *        - each q_s is the same in all its records, and the four differ.
+ *      Anything else is ETHCNN_ERR_FORMAT.  The rules are checked over the whole input in this order, and the first one that is broken
+ *      anywhere is reported with its name in quotes and the lowest record index that shows it:
+ *        'geometry'          w < 64, h < 64 or f >= 2^31 (no whole CTU; the sequence call counts frames in an int): that record
+ *        'outside'           line >= R or col >= C: that record
+ *        'QP differs'        a record whose four q_s are not those of the lowest record of its run: that record
+ *        'QPs not distinct'  the lowest record of a run whose four q_s are not distinct
+ *        'duplicate'         a record whose (f, line, col) a lower record of its run holds already: the higher record
+ *        'missing'           with f0 / f1 the lowest / highest frame number of the run: the first (f, line, col) in that order within
+ *                            f0..f1 that no record holds; it is shown by the lowest record of the run whose frame number is >= f
+ *      Record order in the input is irrelevant: an unshuffled file, a "_shuffled" file and ethcnn_samples_read with a seed give the same
+ *      plan up to the source indices.
+ *   Source table of a run: src[F][nctu] int64 with F = f1 - f0 + 1; src[f - f0][line C + col] = the index of the record at (f, line, col).
+ *   Reconstructed planes of a run at slot s: residual [F][64 R][64 C] uint8, byte (y, x) of frame f = residual byte 64 (y % 64) + x % 64 of
+ *      the record at (f, y / 64, x / 64) (a slot's residual starts at record byte 81 + 4113 s); labels [F][4 R][4 C] uint8 from the 16
+ *      depth bytes (record byte 65 + 4113 s on) in the same way.  These are the whole-CTU crops of the planes the set was cut from.
+ *   Replay of a run at slot s: what ethcnn_ldp_sequence_device gives for the residual planes with width = 64 C, height = 64 R, qp = q_s,
+ *      i_frame_first = f0 and a state_in of zeros (also when f0 > 1: a file that starts in the middle of a sequence starts from a zero
+ *      state, and never from whatever state the context holds).  The context's thresholds and weights are used as they are; the LSTM
+ *      bundle that goes with q_s is the caller's choice, as for the sequence call.  Output: float32 [F][nctu][21].
+ *      With open gates (thresholds 0, 0) every value equals, bit for bit, what the sequence call gives for the same CTU of the uncropped
+ *      w x h picture: CTUs are independent everywhere except in the batch gates, whose 1024-CTU sub-batches are drawn over the picture's
+ *      raster.  With closed gates, and w or h not a multiple of 64, the two may differ: replay is the cropped picture's result.
+ *   Chunks: a run is replayed a chunk of frames at a time (ethcnn_replay_set_chunk_frames; 0 = default, 256 MB of residual planes).  The
+ *      state goes from chunk to chunk by the sequence call's resident-state rule, so a chunked run equals an unchunked one bit for bit.
+ *      The context's resident LDP state afterwards is the run's last.
+ *   Memory of ethcnn_replay_run_device for a run of F frames in chunks of Fc: Fc nctu 4096 (one chunk's residual planes) + F nctu 8 (the
+ *      run's source table) + F nctu 84 when d_probs is NULL + F nctu 16 when d_labels is NULL + nctu 3584 (the zero state) when f0 > 1
+ *      + the copy of the records (n 16516) after ethcnn_replay_open_records.  ethcnn_replay_run_bytes returns that sum; it is held
+ *      against max_bytes (0 = no limit of its own) and against the free device memory before anything is allocated, and
+ *      ETHCNN_ERR_NOMEM carries it and leaves the object usable.  The buffers are kept until the next call that needs other sizes.
+ *      Outside the sum: what the sequence call holds itself (ethcnn_ldp_sequence_bytes for nf = Fc), and 20 bytes a record of headers
+ *      while ethcnn_replay_open_set runs.
+ *   Errors: ETHCNN_ERR_NOWEIGHTS without a CNN or without an LSTM bundle; ETHCNN_ERR_FORMAT for an All-Intra set, a set that is not
+ *      built, a byte count that is zero or not whole records, or an invalid run; ETHCNN_ERR_ARG for a bad run or slot, or when nothing is
+ *      open.  Text: ethcnn_replay_last_error (ethcnn_last_error of the context for ethcnn_replay_create and
+ *      ethcnn_replay_uncut_device). */
+typedef struct ethcnn_replay ethcnn_replay;
+typedef struct ethcnn_replay_run {
+    int32_t seq, w, h;   /* the run's key: sequence number, width and height as in the headers */
+    int32_t rows, cols;  /* R, C */
+    uint32_t f0;         /* first frame number */
+    int64_t frames;      /* F */
+    int64_t nctu;        /* R C */
+    int32_t qp[4];       /* slot QPs */
+    int64_t src_offset;  /* first entry of the run in the table of ethcnn_replay_plan */
+} ethcnn_replay_run;
+/* The plan alone, on the host (no context, no GPU), over whole records.  runs_out (may be NULL) takes the first max_runs runs,
+ * *nruns_out their total; src_out (may be NULL) holds nbytes / 16516 entries: the source tables of the runs back to back, run k from
+ * src_offset on.  err (may be NULL) takes the text of ETHCNN_ERR_FORMAT. */
+int ethcnn_replay_plan(const uint8_t* records, size_t nbytes, ethcnn_replay_run* runs_out, int max_runs, int* nruns_out, int64_t* src_out,
+                       char* err, size_t errcap);
+/* The kernel alone, on buffers in HBM; the counterpart of ethcnn_samples_cut_device.  d_src [nframes][R C] (8-byte aligned) picks records
+ * of d_records (4-byte aligned, nrecords of them); d_resi [nframes][64 R][64 C] (16-byte aligned) and d_labels [nframes][4 R][4 C] (4-byte
+ * aligned) are written, every byte once.  An index outside [0, nrecords) gives zeros.  Asynchronous on the context's stream. */
+int ethcnn_replay_uncut_device(ethcnn_ctx* ctx, const uint8_t* d_records, int64_t nrecords, const int64_t* d_src, int64_t nframes, int R, int C,
+                               int slot, uint8_t* d_resi, uint8_t* d_labels);
+int ethcnn_replay_create(ethcnn_ctx* ctx, uint64_t max_bytes, ethcnn_replay** out);
+void ethcnn_replay_destroy(ethcnn_replay* rp); /* before ethcnn_destroy of its context, and before the set it has open */
+const char* ethcnn_replay_last_error(const ethcnn_replay* rp);
+/* Opening replaces whatever was open.  A set (built, inter, of the same context) is only read and stays as it is; it must outlive its use
+ * here.  Host records are planned on the host first (nothing is allocated for an invalid file), then uploaded in pieces of 64 MB. */
+int ethcnn_replay_open_set(ethcnn_replay* rp, ethcnn_samples* inter_set);
+int ethcnn_replay_open_records(ethcnn_replay* rp, const uint8_t* records, size_t nbytes);
+int ethcnn_replay_run_count(const ethcnn_replay* rp);
+int ethcnn_replay_run_info(ethcnn_replay* rp, int run, ethcnn_replay_run* out); /* src_offset: into the object's own table */
+int ethcnn_replay_set_chunk_frames(ethcnn_replay* rp, int frames);
+int64_t ethcnn_replay_run_bytes(ethcnn_replay* rp, int run, int own_probs, int own_labels); /* the memory sum above; negative: error */
+/* Uncut, then the sequence call, chunk by chunk.  d_probs float32 [F][nctu][21] and d_labels uint8 [F][4 R][4 C] in HBM; either may be
+ * NULL: the object's own buffer is used then.  Asynchronous on the context's stream. */
+int ethcnn_replay_run_device(ethcnn_replay* rp, int run, int slot, float* d_probs, uint8_t* d_labels);
+/* ethcnn_replay_run_device into the object's own buffers, then ethcnn_calib_add_frames_device / ethcnn_sim_add_frames_device with
+ * width = 64 C, height = 64 R, skip_label_frames = 0: nothing goes through the host.  Synchronous, as those entries are. */
+int ethcnn_replay_feed_calib(ethcnn_replay* rp, int run, int slot, ethcnn_calib* cal);
+int ethcnn_replay_feed_sim(ethcnn_replay* rp, int run, int slot, ethcnn_sim* sim);
+
 #ifdef __cplusplus
 }
 #endif

@@ -24,6 +24,11 @@ Any number of cases, accumulated into one histogram:
   --samples FILE --model PREFIX --qp Q [--net ai|ldp]
         a trainer's evaluation (forward only, no gates in that graph) of a validation sample file with the checkpoint PREFIX; the
         truth is the 16 label bytes of QP row Q (All-Intra records: byte 4160 + 16 Q) or of the slot whose QP byte is Q (LDP records).
+  --samples FILE --ldp --model-dir D --qp Q
+        an inter sample file (LDP_Valid.dat, LDP_Test.dat, plain or _shuffled) replayed through the deployed Low-Delay-P chain
+        (include/ethcnn.h "sample-set replay"): the residual pictures and label planes of every sequence the file holds are put back
+        together on the GPU, in any record order, and predicted as the daemon would, gates open, with the models of D (as for --yuv
+        --ldp).  Q selects the QP slot; a file without a slot of that QP is an error.  One line per sequence goes to stderr.
 
 Budgets default to 50000 ppm (5 %).  --hist FILE also writes the accumulated histogram, uint64 little-endian [3 levels][2 truths][1025 bins].  --order ai writes "up1 down1 up2 down2 up3 down3" (HM-16.5_Test_AI, TEncCu.cpp:250), --order
 ldp writes "down1 up1 down2 up2 down3 up3" (HM-16.5_Test_LDP, TEncGOP.cpp:1449): the two encoders differ.  CTUs that are not wholly
@@ -56,7 +61,7 @@ def parse(argv, labels_optional=False):
     simulation tool, which shares this command line's cases)"""
     opt = {"eps_down": [50000] * 3, "eps_up": [50000] * 3, "out": None, "order": None, "hist": None, "json": False, "device": 0}
     cases, i = [], 0
-    per_case = {"--skip-label-frames": ("skip", int, ("case",)), "--labels": ("labels", str, ("yuv",)), "--model-dir": ("model_dir", str, ("yuv",)),
+    per_case = {"--skip-label-frames": ("skip", int, ("case",)), "--labels": ("labels", str, ("yuv",)), "--model-dir": ("model_dir", str, ("yuv", "samples")),
                 "--frame-begin": ("frame_begin", int, ("yuv",)), "--model": ("model", str, ("samples",)), "--qp": ("qp", int, ("samples",)),
                 "--net": ("net", str, ("samples",))}
     while i < len(argv):
@@ -80,10 +85,10 @@ def parse(argv, labels_optional=False):
             cases.append({"kind": "yuv", "yuv": v[0], "w": int(v[1]), "h": int(v[2]), "qp": int(v[3]), "ldp": False, "frame_begin": 1})
         elif a == "--samples":
             v, i = _take(argv, i, 1, a)
-            cases.append({"kind": "samples", "file": v[0], "net": "ai"})
+            cases.append({"kind": "samples", "file": v[0], "net": "ai", "ldp": False})
         elif a == "--ldp":
-            if not cases or cases[-1]["kind"] != "yuv":
-                raise Usage("--ldp follows a --yuv case")
+            if not cases or cases[-1]["kind"] not in ("yuv", "samples"):
+                raise Usage("--ldp follows a --yuv or a --samples case")
             cases[-1]["ldp"] = True
         elif a in per_case:
             key, conv, kinds = per_case[a]
@@ -96,12 +101,15 @@ def parse(argv, labels_optional=False):
     if not cases:
         raise Usage("no case given")
     for c in cases:
-        need = {"case": (), "yuv": ("model_dir",) if labels_optional else ("labels", "model_dir"), "samples": ("model", "qp")}[c["kind"]]
+        need = {"case": (), "yuv": ("model_dir",) if labels_optional else ("labels", "model_dir"),
+                "samples": ("model_dir", "qp") if c.get("ldp") else ("model", "qp")}[c["kind"]]
         for k in need:
             if k not in c:
                 raise Usage("a --%s case needs --%s" % (c["kind"], k.replace("_", "-")))
         if c["kind"] == "samples" and c["net"] not in ("ai", "ldp"):
             raise Usage("--net is ai or ldp")
+        if c["kind"] == "samples" and (("model" in c or c["net"] != "ai") if c["ldp"] else "model_dir" in c):
+            raise Usage("a --samples case takes --model PREFIX [--net], or --ldp --model-dir D (a replay)")
     if (opt["out"] is None) != (opt["order"] is None) or opt["order"] not in (None, "ai", "ldp"):
         raise Usage("--out PATH and --order ai|ldp go together")
     for e in opt["eps_down"] + opt["eps_up"]:
@@ -180,6 +188,21 @@ def add_cases(pkg, ctx, cal, cases, note):
                     ctx.predict_yuv_file(c["yuv"], w, h, qp, dat)
                     skip = 0
                 _add_file_pair(cal, pkg, c.get("labels"), dat, w, h, skip, note)
+        elif c["ldp"]:
+            qp, d = c["qp"], c["model_dir"]
+            ctx.load_checkpoint(os.path.join(d, LDP_CNN_FILE))
+            ctx.load_lstm_checkpoint(os.path.join(d, pkg.ethcnn.lstm_model_name_for_qp(qp)))
+            ctx.set_thresholds(0.0, 0.0)  # open gates
+            with pkg.Replay(ctx) as rp:
+                rp.open(c["file"])
+                runs = rp.runs()
+                for r in runs:
+                    if qp not in r["qps"]:
+                        raise ValueError("%s: QP %d is not one of the slot QPs %s of sequence %d" % (c["file"], qp, r["qps"], r["seq"]))
+                for r in runs:
+                    note("sequence %d: %dx%d (%d x %d whole CTUs), frames %d..%d, %d CTUs" % (r["seq"], r["w"], r["h"], r["cols"], r["rows"], r["f0"],
+                                                                                            r["f0"] + r["frames"] - 1, r["frames"] * r["nctu"]))
+                rp.feed(cal, qp=qp)
         else:
             records = np.fromfile(c["file"], dtype=np.uint8)
             n, depth = _sample_labels(records, c["net"], c["qp"], pkg)

@@ -26,9 +26,11 @@ Cases are those of calibrate_thresholds.py, with labels optional:
         made.  With --gates none the probabilities are taken as what the encoder will read.
   --yuv SEQ W H QP [--labels L] --model-dir D [--ldp [--frame-begin 1]]
   --samples FILE --model PREFIX --qp Q [--net ai|ldp]
+  --samples FILE --ldp --model-dir D --qp Q          (an inter sample file replayed through the deployed Low-Delay-P chain; its
+        CTUs come as frames, so the gates apply to them as to a --yuv case)
 
 --gates defaults to --order: input predicted by this tool has open gates, and the simulator applies the gates that a predictor
-reading the candidate file would (tokens [1] and [3]).  CTUs of a --samples case belong to no sub-batch and are never gated.
+reading the candidate file would (tokens [1] and [3]).  CTUs of a --samples case without --ldp belong to no sub-batch and are never gated.
 --weights default to 64 16 4 1: cost proportional to the CU's area.
 
 What this is not: the weighted check count is a proxy, and its relation to HM's encoding time or to BD-rate has not been measured; a
