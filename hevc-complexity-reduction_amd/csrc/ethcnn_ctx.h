@@ -3,6 +3,7 @@
 //   ethcnn_model.cpp    weights: upload, the 16-bit plans' images + their accuracy guard, LSTM bundle, introspection
 //   ethcnn_pass.cpp     one pass over CTUs in HBM (the kernel pipeline), the device entry point
 //   ethcnn_host.cpp     host / file entry points: staging ring, worker pool, latency path, streamed pictures, sharded file driver
+//   ethcnn_narrow.cpp   high-bit-depth and non-4:2:0 sources: the source format, the narrowing rule on the host, the device entries
 //   ethcnn_ldp.cpp      config #5: resi vectors, ETH-LSTM step, the per-frame LDP calls, the offline whole-sequence calls
 // Mirrors /root/reference/HM-16.5_Test_AI/bin/video_to_cu_depth.py (driver) around net_CNN.py (network).  There is no CPU
 // compute path in this library.
@@ -171,6 +172,13 @@ struct ethcnn_ctx {
     float* seq_probs = nullptr;
     size_t seq_vec_cap = 0, seq_probs_cap = 0;  // bytes
     int seq_chunk = 0;                          // frames per chunk (ethcnn_ldp_set_sequence_chunk; 0 = default)
+    // high-bit-depth and non-4:2:0 sources (ethcnn_narrow.cpp): what the file entries read, and the narrowed planes of one chunk of
+    // frames of ethcnn_predict_luma16_device (pitch roundup16(width))
+    ethcnn_source_format src_fmt{8, 420};
+    uint8_t* narrow_buf = nullptr;
+    size_t narrow_cap = 0;                      // bytes
+    int narrow_chunk = 0;                       // frames per chunk (ethcnn_set_narrow_chunk; 0 = default: 256 MB of narrowed planes)
+    std::vector<uint8_t> narrow_host;           // one small call of ethcnn_predict_luma16: its narrowed planes on the way to the latency path
 
     Workspace ws;
     // Cross-pass software pipeline ("pass pipeline"): the tile stage of pass i+1 (HBM-bound, no MFMA) runs

@@ -1,5 +1,6 @@
 // ethcnn_host.cpp -- host and file entry points: staging ring, worker pool, latency path, streamed pictures, the YUV-file driver
 #include "ethcnn_ctx.h"
+#include "ethcnn_narrow.h"
 
 void free_staging(ethcnn_ctx* c) {
     for (int i = 0; i < kStageBufs; ++i) {
@@ -144,6 +145,29 @@ int pinned_pread(int fd, uint8_t* d, size_t want, off_t off) {
         if (r <= 0) return ETHCNN_ERR_IO;
         got += (size_t)r;
     }
+    return 0;
+}
+
+// `nsamples` 16-bit samples of a file at `off` -> narrowed bytes in page-locked staging memory (the rule of include/ethcnn.h): pread into
+// the cache-resident bounce buffer, narrowed from there with non-temporal stores.  One byte per sample is what the DMA engine then moves.
+static int pinned_pread16(int fd, uint8_t* d, size_t nsamples, off_t off, int shift) {
+    constexpr size_t kBounce = 128u << 10;
+    alignas(64) static thread_local uint16_t tmp[kBounce / 2];
+    size_t done = 0;
+    while (done < nsamples) {
+        const size_t n = std::min(kBounce / 2, nsamples - done);
+        size_t got = 0;
+        while (got < 2 * n) {  // (a short read may end inside a sample)
+            const ssize_t r = pread(fd, (char*)tmp + got, 2 * n - got, off + (off_t)(2 * done + got));
+            if (r <= 0) return ETHCNN_ERR_IO;
+            got += (size_t)r;
+        }
+        narrow::narrow_row(tmp, d + done, n, shift, true);
+        done += n;
+    }
+#if defined(__SSE2__)
+    _mm_sfence();
+#endif
     return 0;
 }
 
@@ -488,6 +512,71 @@ extern "C" int ethcnn_predict_luma(ethcnn_ctx* c, const uint8_t* luma, int w, in
     return host_pipeline(c, w, h, nframes, qp, fill, drain);
 }
 
+// ethcnn_predict_luma for 16-bit planes: the fill threads narrow (include/ethcnn.h, the narrowing rule) while they pack the staging ring,
+// so the ring, the DMA engine and every kernel see what they see for an 8-bit source.  A picture (the latency path) is narrowed into a
+// buffer of the context first: those calls are bound by launches, not by the bus.
+extern "C" int ethcnn_predict_luma16(ethcnn_ctx* c, const uint16_t* luma16, int w, int h, ptrdiff_t pitch_bytes, ptrdiff_t fstride_bytes,
+                                     int nframes, int bit_depth, int qp, float* probs) {
+    if (!c || !luma16 || !probs || nframes < 0) return c ? set_err(c, ETHCNN_ERR_ARG, "null pointer / negative frame count") : ETHCNN_ERR_ARG;
+    if (w <= 0 || h <= 0) return set_err(c, ETHCNN_ERR_ARG, "bad frame size %dx%d", w, h);
+    if (bit_depth < 8 || bit_depth > 16) return set_err(c, ETHCNN_ERR_ARG, "ethcnn_predict_luma16: bit depth %d (8..16)", bit_depth);
+    if (reinterpret_cast<uintptr_t>(luma16) % 2 || pitch_bytes % 2 || pitch_bytes < 2 * (ptrdiff_t)w || (nframes > 1 && fstride_bytes % 2))
+        return set_err(c, ETHCNN_ERR_ARG, "ethcnn_predict_luma16: the source must be 2-byte aligned, its pitch even and at least %td bytes, its frame stride even",
+                       2 * (ptrdiff_t)w);
+    const int shift = bit_depth - 8;
+    const uint8_t* base = reinterpret_cast<const uint8_t*>(luma16);
+    auto row = [&](int f, int y) { return reinterpret_cast<const uint16_t*>(base + (size_t)f * fstride_bytes + (size_t)y * pitch_bytes); };
+    const int nctu = ((w + 63) / 64) * ((h + 63) / 64);
+    if (nframes > 0 && (long)nframes * nctu < kPipelineMinCtus) {
+        try {
+            c->narrow_host.resize((size_t)w * h * nframes);
+        } catch (...) {
+            return set_err(c, ETHCNN_ERR_NOMEM, "ethcnn_predict_luma16: %zu bytes of host memory for the narrowed picture", (size_t)w * h * nframes);
+        }
+        uint8_t* const d = c->narrow_host.data();
+        const std::function<int(int)> one = [&](int u) -> int {
+            narrow::narrow_row(row(u / h, u % h), d + (size_t)u * w, (size_t)w, shift, false);
+            return 0;
+        };
+        if ((size_t)w * h * nframes >= (4u << 20)) (void)host_pool(c)->run(nframes * h, one);
+        else for (int u = 0; u < nframes * h; ++u) (void)one(u);
+        return predict_luma_latency(c, d, w, h, w, (ptrdiff_t)w * h, nframes, qp, probs);
+    }
+    auto fill = [&](uint8_t* dst, int f0, int nf) -> int {
+        const int rc = parallel_bands(c, nf, w, h, [&](int f, int r0, int rows) -> int {
+            for (int y = r0; y < r0 + rows; ++y) narrow::narrow_row(row(f0 + f, y), dst + (size_t)f * w * h + (size_t)y * w, (size_t)w, shift, true);
+            return 0;
+        });
+#if defined(__SSE2__)
+        _mm_sfence();
+#endif
+        return rc;
+    };
+    auto drain = [&](const float* src, int f0, int nf) -> int {
+        std::memcpy(probs + (size_t)f0 * nctu * kNOut, src, (size_t)nf * nctu * kNOut * 4);
+        return 0;
+    };
+    return host_pipeline(c, w, h, nframes, qp, fill, drain);
+}
+
+// what the file entries read (ethcnn_set_source_format): frame and luma bytes, the frame count; ERR_FORMAT names the format in force
+static int file_frames(ethcnn_ctx* c, const char* yuv, int w, int h, int64_t* frame_bytes, int64_t* total) {
+    if (w <= 0 || h <= 0) return set_err(c, ETHCNN_ERR_ARG, "bad frame size %dx%d", w, h);
+    struct stat st;
+    if (stat(yuv, &st) != 0) return set_err(c, ETHCNN_ERR_IO, "cannot stat %s: %s", yuv, std::strerror(errno));
+    const ethcnn_source_format& f = c->src_fmt;
+    int64_t luma = 0;
+    if (ethcnn_source_frame_bytes(&f, w, h, &luma, frame_bytes) != ETHCNN_OK)
+        return set_err(c, ETHCNN_ERR_ARG, "%dx%d has no whole chroma planes in the source format in force (%d-bit %d:%d:%d)", w, h, f.bit_depth,
+                       f.chroma_format / 100, f.chroma_format / 10 % 10, f.chroma_format % 10);
+    if (*frame_bytes == 0 || st.st_size % *frame_bytes != 0)  // :137 assert(file_bytes % frame_bytes == 0)
+        return set_err(c, ETHCNN_ERR_FORMAT, "%s: size %lld is not a multiple of the %dx%d %d-bit %d:%d:%d frame size %lld%s", yuv, (long long)st.st_size, w,
+                       h, f.bit_depth, f.chroma_format / 100, f.chroma_format / 10 % 10, f.chroma_format % 10, (long long)*frame_bytes,
+                       f.bit_depth == 8 && f.chroma_format == 420 ? "" : " (ethcnn_set_source_format)");
+    *total = st.st_size / *frame_bytes;
+    return 0;
+}
+
 // video_to_cu_depth.py:120-145 minus argv/model selection (those live in the launcher).
 // shard == false: frames [0, all) -> out_path via temp file + rename.
 // shard == true : frames [f0, f1) pwritten at f0 * nctu * 84 into the EXISTING, pre-sized
@@ -497,14 +586,9 @@ extern "C" int ethcnn_predict_luma(ethcnn_ctx* c, const uint8_t* luma, int w, in
 static int yuv_frames(ethcnn_ctx* c, const char* yuv, int w, int h, int qp, const char* out_path, int mode,
                       int64_t f0, int64_t f1, int64_t* nframes_out) {
     const bool shard = (mode == 1);
-    if (w <= 0 || h <= 0) return set_err(c, ETHCNN_ERR_ARG, "bad frame size %dx%d", w, h);
-    struct stat st;
-    if (stat(yuv, &st) != 0) return set_err(c, ETHCNN_ERR_IO, "cannot stat %s: %s", yuv, std::strerror(errno));
-    const int64_t frame_bytes = (int64_t)w * h * 3 / 2;  // :136  width * height * 3 // 2
-    if (frame_bytes == 0 || st.st_size % frame_bytes != 0)  // :137 assert(file_bytes % frame_bytes == 0)
-        return set_err(c, ETHCNN_ERR_FORMAT, "%s: size %lld is not a multiple of the %dx%d 4:2:0 frame size %lld", yuv,
-                       (long long)st.st_size, w, h, (long long)frame_bytes);
-    const int64_t total = st.st_size / frame_bytes;
+    int64_t frame_bytes = 0, total = 0;  // :136  width * height * 3 // 2 in the default format
+    if (const int frc = file_frames(c, yuv, w, h, &frame_bytes, &total)) return frc;
+    const int deep_shift = c->src_fmt.bit_depth > 8 ? c->src_fmt.bit_depth - 8 : -1;  // >= 0: 16-bit samples, narrowed by the fill threads
     if (nframes_out) *nframes_out = total;
     if (mode == 0) { f0 = 0; f1 = total; }
     if (f0 < 0 || f1 < f0 || f1 > total) return set_err(c, ETHCNN_ERR_ARG, "frame range [%lld,%lld) outside 0..%lld", (long long)f0, (long long)f1, (long long)total);
@@ -519,8 +603,11 @@ static int yuv_frames(ethcnn_ctx* c, const char* yuv, int w, int h, int qp, cons
     }
     const int fd = fileno(fin), ofd = fileno(fout);
     auto fill = [&](uint8_t* dst, int g0, int nf) -> int {
-        // luma only; chroma (w*h/2 bytes per frame) is never read (:47-48)
+        // luma only; chroma (w*h/2 bytes per frame in 8-bit 4:2:0) is never read (:47-48)
         const int rc = parallel_bands(c, nf, w, h, [&](int f, int r0, int rows) -> int {
+            if (deep_shift >= 0)
+                return pinned_pread16(fd, dst + (size_t)f * w * h + (size_t)r0 * w, (size_t)w * rows, (off_t)(f0 + g0 + f) * frame_bytes + (off_t)r0 * w * 2,
+                                      deep_shift);
             return pinned_pread(fd, dst + (size_t)f * w * h + (size_t)r0 * w, (size_t)w * rows, (off_t)(f0 + g0 + f) * frame_bytes + (off_t)r0 * w);
         });
         return rc ? set_err(c, rc, "short read in %s (frames %lld..%lld)", yuv, (long long)(f0 + g0), (long long)(f0 + g0 + nf - 1)) : 0;
@@ -579,6 +666,7 @@ static int sync_peer(const ethcnn_ctx* c, ethcnn_ctx* p) {  // (on the peer's wo
     p->thr2 = c->thr2;
     p->fc1_plan = c->fc1_plan;
     p->max_ctus = c->max_ctus;
+    p->src_fmt = c->src_fmt;  // the workers read the same file
     for (int pl : {2, 3}) {  // the accuracy guard is a function of the weights: decided once, by the caller's context
         p->guard_state[pl] = c->guard_state[pl] == 3 ? 0 : c->guard_state[pl];
         p->guard_bound[pl] = c->guard_bound[pl];
@@ -594,14 +682,8 @@ extern "C" int ethcnn_predict_yuv_file_sharded(ethcnn_ctx* c, const int* devices
     if (devices[0] != c->device)
         return set_err(c, ETHCNN_ERR_ARG, "ethcnn_predict_yuv_file_sharded: devices[0] = %d, but this context (worker 0) lives on device %d", devices[0], c->device);
     if (!c->have_weights) return set_err(c, ETHCNN_ERR_NOWEIGHTS, "no weights loaded");
-    if (w <= 0 || h <= 0) return set_err(c, ETHCNN_ERR_ARG, "bad frame size %dx%d", w, h);
-    struct stat st;
-    if (stat(yuv, &st) != 0) return set_err(c, ETHCNN_ERR_IO, "cannot stat %s: %s", yuv, std::strerror(errno));
-    const int64_t frame_bytes = (int64_t)w * h * 3 / 2;
-    if (frame_bytes == 0 || st.st_size % frame_bytes != 0)
-        return set_err(c, ETHCNN_ERR_FORMAT, "%s: size %lld is not a multiple of the %dx%d 4:2:0 frame size %lld", yuv, (long long)st.st_size, w, h,
-                       (long long)frame_bytes);
-    const int64_t total = st.st_size / frame_bytes;
+    int64_t frame_bytes = 0, total = 0;
+    if (const int frc = file_frames(c, yuv, w, h, &frame_bytes, &total)) return frc;
     if (nframes_out) *nframes_out = total;
     if (ndevices == 1 || total <= 1) return yuv_frames(c, yuv, w, h, qp, out_path, 0, 0, 0, nullptr);
     if (c->fc1_plan) {  // (guard + weight images once, here; the peers inherit the verdict)

@@ -60,6 +60,11 @@ class CkptEntry(ctypes.Structure):
                 ("size", ctypes.c_int64), ("crc32c", ctypes.c_uint32)]
 
 
+class SourceFormat(ctypes.Structure):
+    """ethcnn_source_format: what the file entries read (bit_depth 8..16; chroma_format 400 / 420 / 422 / 444)"""
+    _fields_ = [("bit_depth", ctypes.c_int), ("chroma_format", ctypes.c_int)]
+
+
 # every symbol include/ethcnn.h declares: name -> (restype, argtypes)
 _vp, _cp, _i, _sz = ctypes.c_void_p, ctypes.c_char_p, ctypes.c_int, ctypes.c_size_t
 _fp, _pd = ctypes.POINTER(ctypes.c_float), ctypes.c_ssize_t
@@ -78,6 +83,14 @@ SIGNATURES = {
     "ethcnn_set_thresholds": (_i, [_vp, ctypes.c_float, ctypes.c_float]),
     "ethcnn_get_thresholds": (_i, [_vp, _fp, _fp]),
     "ethcnn_predict_luma_device": (_i, [_vp, _vp, _i, _i, _pd, _pd, _i, _i, _vp]),
+    "ethcnn_narrow_rows_host": (_i, [_vp, _vp, _sz, _i]),
+    "ethcnn_narrow_luma_device": (_i, [_vp, _vp, _i, _i, _pd, _pd, _i, _i, _vp, _pd, _pd]),
+    "ethcnn_predict_luma16_device": (_i, [_vp, _vp, _i, _i, _pd, _pd, _i, _i, _i, _vp]),
+    "ethcnn_predict_luma16": (_i, [_vp, _vp, _i, _i, _pd, _pd, _i, _i, _i, _fp]),
+    "ethcnn_set_narrow_chunk": (_i, [_vp, _i]),
+    "ethcnn_set_source_format": (_i, [_vp, _vp]),
+    "ethcnn_get_source_format": (_i, [_vp, _vp]),
+    "ethcnn_source_frame_bytes": (_i, [_vp, _i, _i, ctypes.POINTER(ctypes.c_int64), ctypes.POINTER(ctypes.c_int64)]),
     "ethcnn_set_pass_pipeline": (_i, [_vp, _i]),
     "ethcnn_set_small_pass_launch": (_i, [_vp, _i]),
     "ethcnn_set_fc1_plan": (_i, [_vp, _i]),
@@ -339,6 +352,26 @@ def ldp_sequence_bytes(width, height, nframes, chunk_frames=0):
     return int(load_library().ethcnn_ldp_sequence_bytes(int(width), int(height), int(nframes), int(chunk_frames)))
 
 
+def source_frame_bytes(width, height, bit_depth=8, chroma=420):
+    """(luma_bytes, frame_bytes) of a planar frame in that source format (ethcnn_source_frame_bytes; host only)"""
+    fmt = SourceFormat(int(bit_depth), int(chroma))
+    a, b = ctypes.c_int64(), ctypes.c_int64()
+    rc = load_library().ethcnn_source_frame_bytes(ctypes.addressof(fmt), int(width), int(height), ctypes.byref(a), ctypes.byref(b))
+    if rc:
+        raise EthCnnError(rc, "source_frame_bytes: no %dx%d frame of whole planes at %d bits, chroma format %d" % (width, height, bit_depth, chroma))
+    return a.value, b.value
+
+
+def narrow_rows_host(src16, bit_depth):
+    """uint16 samples -> uint8 min(s >> (bit_depth - 8), 255), the narrowing rule of include/ethcnn.h on the host (no device)"""
+    src = np.ascontiguousarray(src16, dtype=np.uint16)
+    out = np.empty(src.shape, dtype=np.uint8)
+    rc = load_library().ethcnn_narrow_rows_host(src.ctypes.data, out.ctypes.data, src.size, int(bit_depth))
+    if rc:
+        raise EthCnnError(rc, "narrow_rows_host: bit depth %d (8..16)" % bit_depth)
+    return out
+
+
 def ctus_per_frame(width, height):
     return ((width + 63) // 64) * ((height + 63) // 64)
 
@@ -487,6 +520,55 @@ class EthCnn(object):
         dst = d_probs.ptr if isinstance(d_probs, DeviceBuffer) else int(d_probs)
         self._chk(self.lib.ethcnn_predict_luma_device(self.h, src, width, height, pitch, frame_stride, nframes,
                                                       int(qp), dst))
+
+    # -- high-bit-depth and non-4:2:0 sources
+    def set_source_format(self, bit_depth=8, chroma=420):
+        """what predict_yuv_file / _shard / _file_sharded / _range read from now on (default: 8-bit 4:2:0)"""
+        fmt = SourceFormat(int(bit_depth), int(chroma))
+        self._chk(self.lib.ethcnn_set_source_format(self.h, ctypes.addressof(fmt)))
+
+    def source_format(self):
+        fmt = SourceFormat()
+        self._chk(self.lib.ethcnn_get_source_format(self.h, ctypes.addressof(fmt)))
+        return fmt.bit_depth, fmt.chroma_format
+
+    def set_narrow_chunk(self, frames=0):
+        """frames per chunk of predict_luma16_device (0 = default: 256 MB of narrowed planes)"""
+        self._chk(self.lib.ethcnn_set_narrow_chunk(self.h, int(frames)))
+
+    def predict_luma16(self, luma16, width, height, nframes, qp, bit_depth, pitch_bytes=None, frame_stride_bytes=None):
+        """Host luma planes of 16-bit samples (uint16 buffer) -> float32 [nframes*nctu, 21]: predict_luma on the narrowed planes."""
+        luma16 = np.ascontiguousarray(luma16, dtype=np.uint16)
+        pitch_bytes = 2 * width if pitch_bytes is None else pitch_bytes
+        frame_stride_bytes = pitch_bytes * height if frame_stride_bytes is None else frame_stride_bytes
+        need = (nframes - 1) * frame_stride_bytes + (height - 1) * pitch_bytes + 2 * width if nframes else 0
+        if luma16.nbytes < need:
+            raise ValueError("luma buffer too small: %d < %d bytes" % (luma16.nbytes, need))
+        out = np.empty((nframes * ctus_per_frame(width, height), NOUT), dtype=np.float32)
+        self._chk(self.lib.ethcnn_predict_luma16(self.h, luma16.ctypes.data, width, height, pitch_bytes, frame_stride_bytes, nframes,
+                                                 int(bit_depth), int(qp), out.ctypes.data_as(_fp)))
+        return out
+
+    def predict_luma16_device(self, d_luma16, width, height, nframes, qp, bit_depth, d_probs, pitch_bytes=None, frame_stride_bytes=None):
+        """Both pointers already in HBM (ints or DeviceBuffer); asynchronous."""
+        pitch_bytes = 2 * width if pitch_bytes is None else pitch_bytes
+        frame_stride_bytes = pitch_bytes * height if frame_stride_bytes is None else frame_stride_bytes
+        src = d_luma16.ptr if isinstance(d_luma16, DeviceBuffer) else int(d_luma16)
+        dst = d_probs.ptr if isinstance(d_probs, DeviceBuffer) else int(d_probs)
+        self._chk(self.lib.ethcnn_predict_luma16_device(self.h, src, width, height, pitch_bytes, frame_stride_bytes, nframes,
+                                                        int(bit_depth), int(qp), dst))
+
+    def narrow_luma_device(self, d_src16, width, height, nframes, bit_depth, d_dst8, pitch_bytes=None, frame_stride_bytes=None,
+                           dst_pitch=None, dst_frame_stride=None):
+        """the narrowing kernel alone: 16-bit planes in HBM -> 8-bit planes of pitch roundup16(width) (pad columns zero); asynchronous"""
+        pitch_bytes = 2 * width if pitch_bytes is None else pitch_bytes
+        frame_stride_bytes = pitch_bytes * height if frame_stride_bytes is None else frame_stride_bytes
+        dst_pitch = (width + 15) // 16 * 16 if dst_pitch is None else dst_pitch
+        dst_frame_stride = dst_pitch * height if dst_frame_stride is None else dst_frame_stride
+        src = d_src16.ptr if isinstance(d_src16, DeviceBuffer) else int(d_src16)
+        dst = d_dst8.ptr if isinstance(d_dst8, DeviceBuffer) else int(d_dst8)
+        self._chk(self.lib.ethcnn_narrow_luma_device(self.h, src, width, height, pitch_bytes, frame_stride_bytes, nframes, int(bit_depth),
+                                                     dst, dst_pitch, dst_frame_stride))
 
     def predict_ctus(self, ctus, qp):
         """[n,64,64] uint8 CTUs -> [n,21]; gates per <=1024-CTU sub-batch exactly like

@@ -9,7 +9,10 @@ Differences from the reference, all outside the numbers it produces:
   * the YUV is streamed (luma only) instead of being tiled in Python;
   * when the trained checkpoint blobs are absent (they are not in the reference repo),
     ETHCNN_SYNTHETIC_SEED=<n> [ETHCNN_HEAD_GAIN=<g>] opts into seeded synthetic weights;
-    without it a missing checkpoint is an error (non-zero exit, HM aborts).
+    without it a missing checkpoint is an error (non-zero exit, HM aborts);
+  * HM's command line is fixed, so the source format of the file comes through the environment: ETHCNN_INPUT_BIT_DEPTH=8..16 (HM's
+    InputBitDepth; above 8 the file holds 16-bit samples) and ETHCNN_INPUT_CHROMA_FORMAT=400|420|422|444 (InputChromaFormat).  Unset:
+    the reference's 8-bit 4:2:0.  A bad value is a non-zero exit with a message.
 """
 from __future__ import print_function
 
@@ -37,12 +40,30 @@ def get_y_conv_on_large_data(ctx, input_image, qp_seq):
     return ctx.predict_ctus(input_image, qp_seq)
 
 
+def source_format_from_env():
+    """(bit_depth, chroma) from ETHCNN_INPUT_BIT_DEPTH / ETHCNN_INPUT_CHROMA_FORMAT; ValueError names a bad value"""
+    fmt = []
+    for name, default, ok in (('ETHCNN_INPUT_BIT_DEPTH', 8, range(8, 17)), ('ETHCNN_INPUT_CHROMA_FORMAT', 420, (400, 420, 422, 444))):
+        text = os.environ.get(name)
+        if text is None or text == '':
+            fmt.append(default)
+            continue
+        try:
+            value = int(text)
+        except ValueError:
+            value = None
+        if value not in ok:
+            raise ValueError("%s='%s' (allowed: %s)" % (name, text, ', '.join(str(v) for v in ok)))
+        fmt.append(value)
+    return tuple(fmt)
+
+
 def get_prob(ctx, yuv_name, image_size, save_file, qp_seq, n_frames_start, n_frames_end, frame_width, frame_height):
     """video_to_cu_depth.py:75-118: frames [n_frames_start, n_frames_end) of the file -> save_file (which then holds exactly
     those frames; the reference reads and discards the first n_frames_start, :86-87).  Its own call passes 0 and the frame
     count (:139-140)."""
     assert image_size == IMAGE_SIZE
-    frame_bytes = frame_width * frame_height * 3 // 2
+    frame_bytes = _e.source_frame_bytes(frame_width, frame_height, *ctx.source_format())[1]   # width * height * 3 // 2 by default
     total = get_file_size(yuv_name) // frame_bytes
     if n_frames_start == 0 and n_frames_end == total:
         return ctx.predict_yuv_file(yuv_name, frame_width, frame_height, qp_seq, save_file)
@@ -74,20 +95,21 @@ def guard_fast_plan(ctx):
             ctx.set_fc1_plan(0)
 
 
-def _shard_worker(device, yuv_file, width, height, qp_seq, out_path, f0, f1, thr, nworkers=1):
+def _shard_worker(device, yuv_file, width, height, qp_seq, out_path, f0, f1, thr, nworkers=1, fmt=(8, 420)):
     """One process per GPU: own context, own frame range, pwrite into out_path.
     The node's host-CPU budget is shared: every worker starts budget / nworkers staging-fill threads
     (ethcnn_host_thread_budget), not a full pool each."""
     os.environ['ETHCNN_LOCAL_WORKERS'] = str(max(1, int(nworkers)))
     ctx = _e.EthCnn(device=device)
     ctx.set_thresholds(*thr)
+    ctx.set_source_format(*fmt)
     restore_model(ctx, qp_seq)
     guard_fast_plan(ctx)
     ctx.predict_yuv_shard(yuv_file, width, height, qp_seq, out_path, f0, f1)
     ctx.close()
 
 
-def predict_sharded(yuv_file, width, height, qp_seq, save_file, devices):
+def predict_sharded(yuv_file, width, height, qp_seq, save_file, devices, fmt=(8, 420)):
     """Frame-range sharding over `devices` (list of HIP ordinals).  No collective: ranges are disjoint and the output offsets
     deterministic.  Default: ONE process, a worker thread per device inside the library (ethcnn_predict_yuv_file_sharded: one
     interpreter, one checkpoint parse, peers cloned from the first context -- the encoder blocks on this command, TAppEncCfg.cpp:2317-2321).
@@ -95,6 +117,7 @@ def predict_sharded(yuv_file, width, height, qp_seq, save_file, devices):
     if os.environ.get('ETHCNN_SHARD_PROCESSES', '0') in ('', '0'):
         ctx = _e.EthCnn(device=devices[0])
         ctx.load_thresholds(THR_FILE)
+        ctx.set_source_format(*fmt)
         restore_model(ctx, qp_seq)
         guard_fast_plan(ctx)
         n = ctx.predict_yuv_file_sharded(devices, yuv_file, width, height, qp_seq, save_file)
@@ -102,7 +125,7 @@ def predict_sharded(yuv_file, width, height, qp_seq, save_file, devices):
         return n
     import multiprocessing as mp
     from . import sharding
-    n_frames = get_file_size(yuv_file) // (width * height * 3 // 2)
+    n_frames = get_file_size(yuv_file) // _e.source_frame_bytes(width, height, *fmt)[1]
     thr = nt.get_thresholds(THR_FILE)
     tmp = '%s.tmp.%d' % (save_file, os.getpid())
     sharding.presize_output(tmp, n_frames, width, height)
@@ -111,7 +134,7 @@ def predict_sharded(yuv_file, width, height, qp_seq, save_file, devices):
     ranges = [(dev,) + sharding.frame_range(n_frames, len(devices), g) for g, dev in enumerate(devices)]
     ranges = [r for r in ranges if r[2] > r[1]]
     for dev, f0, f1 in ranges:
-        p = mpctx.Process(target=_shard_worker, args=(dev, yuv_file, width, height, qp_seq, tmp, f0, f1, thr, len(ranges)))
+        p = mpctx.Process(target=_shard_worker, args=(dev, yuv_file, width, height, qp_seq, tmp, f0, f1, thr, len(ranges), fmt))
         p.start()
         procs.append(p)
     ok = True
@@ -130,7 +153,12 @@ def main(argv=None):
     assert len(argv) == 5                      # :120
     yuv_file = argv[1]
     width, height, qp_seq = int(argv[2]), int(argv[3]), int(argv[4])
-    frame_bytes = width * height * 3 // 2
+    try:
+        fmt = source_format_from_env()
+        frame_bytes = _e.source_frame_bytes(width, height, *fmt)[1]         # :136 width * height * 3 // 2 unless the environment says otherwise
+    except (ValueError, _e.EthCnnError) as err:
+        sys.stderr.write('video_to_cu_depth: %s\n' % err)
+        return 1
     assert frame_bytes > 0 and get_file_size(yuv_file) % frame_bytes == 0   # :137
     # ETHCNN_DEVICES="0,1,2,3" shards frames over several GPUs; default: one GPU (ETHCNN_DEVICE)
     devices = [int(d) for d in os.environ.get('ETHCNN_DEVICES', os.environ.get('ETHCNN_DEVICE', '0')).split(',')]
@@ -138,12 +166,13 @@ def main(argv=None):
     stamps = [('imports done', time.perf_counter())]
     t1 = time.time()
     if len(devices) > 1:
-        n_frames = predict_sharded(yuv_file, width, height, qp_seq, SAVE_FILE, devices)
+        n_frames = predict_sharded(yuv_file, width, height, qp_seq, SAVE_FILE, devices, fmt)
         stamps.append(('create + weights + predict (%d workers)' % len(devices), time.perf_counter()))
     else:
         ctx = _e.EthCnn(device=devices[0])
         stamps.append(('create (HIP runtime init %.1f, whole call %.1f)' % ctx.startup_times(), time.perf_counter()))
         ctx.load_thresholds(THR_FILE)          # net_CNN.py:47 (cwd-relative; at import time there)
+        ctx.set_source_format(*fmt)
         restore_model(ctx, qp_seq)
         guard_fast_plan(ctx)
         stamps.append(('thresholds + weights + plan guard', time.perf_counter()))

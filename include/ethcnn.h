@@ -90,7 +90,7 @@ int ethcnn_get_thresholds(const ethcnn_ctx* ctx, float* thr_l1_lower, float* thr
 /* ---- prediction.  Replaces get_prob() (video_to_cu_depth.py:75-118) =
  *      get_Y_for_one_frame (:46-59) + tiling loop (:88-106) + get_y_conv_on_large_data
  *      (:61-73) + net_CNN.net (net_CNN.py:103-195).
- *      luma: 8-bit planes, `pitch` bytes between rows, `frame_stride` bytes between frames
+ *      luma: 8-bit planes (16-bit planes: ethcnn_predict_luma16* below), `pitch` bytes between rows, `frame_stride` bytes between frames
  *      (w*h*3/2 when pointing into a 4:2:0 file image).  probs: float32
  *      [nframes][ceil(h/64)*ceil(w/64)][21], CTUs in raster order, row = [p64,p32[4],p16[16]]
  *      -- the cu_depth.dat layout TEncCu::compressCtu freads (TEncCu.cpp:237-261). */
@@ -146,6 +146,56 @@ int ethcnn_shard_range(int64_t nframes, int workers, int k, int64_t* frame_begin
  * frames, written to a temp file and renamed.  The reference's own call passes 0 and the frame count = ethcnn_predict_yuv_file. */
 int ethcnn_predict_yuv_range(ethcnn_ctx* ctx, const char* yuv_path, int width, int height, int qp,
                              const char* out_path, int64_t frame_begin, int64_t frame_end);
+
+/* ---- high-bit-depth and non-4:2:0 sources.  HM reads InputBitDepth 8..16 and InputChromaFormat 400 / 420 / 422 / 444 (Main10 material:
+ *      UHD content, the 10-bit class-A sequences); the network was trained on 8-bit luma.
+ *   THE NARROWING RULE: a deep sample is an unsigned 16-bit little-endian value s, and the picture the network sees is
+ *        min(s >> (bit_depth - 8), 255),   bit_depth 8..16
+ *      (depth 8: 8-bit data in 16-bit containers).  For every value a plane can hold at its depth, 0 .. 2^bit_depth - 1, this is what
+ *      the in-process encoder hook computes for HM's Pel planes (tools/hm_inprocess_hook.c, convert_row); larger values clamp to 255.
+ *      The host and the device implementation agree on all 65536 values at every depth.  Big-endian or MSB-aligned containers are
+ *      not handled.
+ *   ethcnn_narrow_rows_host      the rule over n samples on the host (SSE2, scalar elsewhere); pure: no context, no device
+ *   ethcnn_narrow_luma_device    the rule over nframes planes resident in HBM, one kernel, asynchronous on the context's stream.  Source:
+ *                                any 2-byte aligned address, pitch_bytes even and >= 2 width, frame_stride_bytes even.  Destination:
+ *                                16-byte aligned, dst_pitch a multiple of 16 and >= roundup16(width) = (width + 15) / 16 * 16,
+ *                                dst_frame_stride a multiple of 16.  Bytes [width, roundup16(width)) of every destination row are
+ *                                written as zero; nothing else outside [0, width) is written, and no source sample outside a row's
+ *                                width is read beyond the 16-byte line its first sample lies in.
+ *   ethcnn_predict_luma16_device ethcnn_predict_luma_device for 16-bit planes in HBM: they are narrowed into a buffer the context owns
+ *                                (pitch roundup16(width), pad columns zero: the predictor pads pictures with zeros up to whole CTUs, so
+ *                                that plane is the same picture, with 16-byte aligned rows) and predicted from there; bit-identical to
+ *                                ethcnn_predict_luma_device on the planes narrowed by the rule.  Long inputs go in chunks of whole frames:
+ *                                the buffer holds at most 256 MB (or ethcnn_set_narrow_chunk frames; 0 = that default; results do not
+ *                                depend on it).  A buffer that cannot be had fails with ETHCNN_ERR_NOMEM and its size in the message,
+ *                                before anything runs.  Asynchronous.
+ *   ethcnn_predict_luma16        the same from host pointers, synchronous: the context's fill threads narrow on the CPU while they fill
+ *                                the staging ring, so one byte per sample crosses PCIe (the bus bounds the host and file entries).
+ *   Source format of the FILE entries (ethcnn_predict_yuv_file, _shard, _file_sharded, _range; sharded workers inherit it):
+ *      ethcnn_set_source_format / ethcnn_get_source_format; default {8, 420}, the reference's only format.  bit_depth > 8: the file
+ *      holds 16-bit samples; bit_depth == 8: one byte per sample.  Planar, luma first; only luma is read.  A file whose size is not a
+ *      multiple of the frame size fails with ETHCNN_ERR_FORMAT, the message names the format in force.  The Low-Delay-P entries
+ *      (ethcnn_ldp_*) are NOT affected: HM's residual writer always emits 8-bit 4:2:0.
+ *   ethcnn_source_frame_bytes    pure: bytes of the luma plane and of a whole frame.  Chroma share in samples: 0 (400), w h / 2 (420),
+ *                                w h (422), 2 w h (444).  8-bit 4:2:0 is exactly the reference's w * h * 3 / 2 (integer division, odd
+ *                                sizes included: video_to_cu_depth.py:136); 4:2:0 at other depths needs even w and h, 4:2:2 an even w,
+ *                                else ETHCNN_ERR_ARG. */
+typedef struct ethcnn_source_format {
+    int bit_depth;     /* 8..16 */
+    int chroma_format; /* 400, 420, 422 or 444 */
+} ethcnn_source_format;
+int ethcnn_narrow_rows_host(const uint16_t* src16, uint8_t* dst8, size_t n, int bit_depth);
+int ethcnn_narrow_luma_device(ethcnn_ctx* ctx, const uint16_t* d_src16, int width, int height, ptrdiff_t pitch_bytes,
+                              ptrdiff_t frame_stride_bytes, int nframes, int bit_depth, uint8_t* d_dst8, ptrdiff_t dst_pitch,
+                              ptrdiff_t dst_frame_stride);
+int ethcnn_predict_luma16_device(ethcnn_ctx* ctx, const uint16_t* d_luma16, int width, int height, ptrdiff_t pitch_bytes,
+                                 ptrdiff_t frame_stride_bytes, int nframes, int bit_depth, int qp, float* d_probs);
+int ethcnn_predict_luma16(ethcnn_ctx* ctx, const uint16_t* luma16, int width, int height, ptrdiff_t pitch_bytes,
+                          ptrdiff_t frame_stride_bytes, int nframes, int bit_depth, int qp, float* probs);
+int ethcnn_set_narrow_chunk(ethcnn_ctx* ctx, int frames);
+int ethcnn_set_source_format(ethcnn_ctx* ctx, const ethcnn_source_format* fmt);
+int ethcnn_get_source_format(const ethcnn_ctx* ctx, ethcnn_source_format* fmt);
+int ethcnn_source_frame_bytes(const ethcnn_source_format* fmt, int width, int height, int64_t* luma_bytes, int64_t* frame_bytes);
 
 /* ---- config #5 front-end: resi_cnn (HM-16.5_Test_LDP/bin/net_CNN_LSTM_one_step.py:151-199)
  *      fed as in resi_to_cu_depth_LDP.py:72-101.  One frame; vec = float32 [nctu][448]. */

@@ -17,7 +17,10 @@
  * (ethcnn_predict_yuv_file_sharded: a worker thread per listed device, no collective; a device
  * may be listed twice).  ETHCNN_FC1_PLAN=2|3: the opted-in plan is checked against the restored
  * checkpoint (ethcnn_check_fc1_plan); a refusal is printed and the run continues with the exact
- * plan -- the encoder asserts a zero exit status.  ETHCNN_TIMING=1 prints where the command's
+ * plan -- the encoder asserts a zero exit status.  ETHCNN_INPUT_BIT_DEPTH=8..16 and
+ * ETHCNN_INPUT_CHROMA_FORMAT=400|420|422|444 name the source format of the file (HM's InputBitDepth
+ * and InputChromaFormat; the command line is fixed); unset: 8-bit 4:2:0; a bad value is exit 1 with a
+ * message.  ETHCNN_TIMING=1 prints where the command's
  * wall time goes (stderr): the blocking system() of the caller sees all of it.
  */
 #include <stdio.h>
@@ -46,11 +49,24 @@ static int file_exists(const char* path) {
     return 1;
 }
 
+/* an integer environment variable: 1 = unset (the default stays), 0 = taken, -1 = not an integer */
+static int env_int(const char* name, int* value) {
+    const char* text = getenv(name);
+    char* end;
+    long v;
+    if (!text || !*text) return 1;
+    v = strtol(text, &end, 10);
+    if (*end != '\0' || v < -100000 || v > 100000) return -1;
+    *value = (int)v;
+    return 0;
+}
+
 int main(int argc, char** argv) {
     ethcnn_ctx* ctx = NULL;
     ethcnn_options opt;
     char model[64], data[96];
     int64_t nframes = 0;
+    ethcnn_source_format fmt = {8, 420};
     int width, height, qp, rc, ndev = 0, devices[64];
     const char* seed = getenv("ETHCNN_SYNTHETIC_SEED");
     const char* dev = getenv("ETHCNN_DEVICE");
@@ -66,6 +82,12 @@ int main(int argc, char** argv) {
     width = atoi(argv[2]);
     height = atoi(argv[3]);
     qp = atoi(argv[4]);
+    if (env_int("ETHCNN_INPUT_BIT_DEPTH", &fmt.bit_depth) < 0 || env_int("ETHCNN_INPUT_CHROMA_FORMAT", &fmt.chroma_format) < 0 ||
+        fmt.bit_depth < 8 || fmt.bit_depth > 16 ||
+        (fmt.chroma_format != 400 && fmt.chroma_format != 420 && fmt.chroma_format != 422 && fmt.chroma_format != 444)) {
+        fprintf(stderr, "video_to_cu_depth: bad ETHCNN_INPUT_BIT_DEPTH (8..16) or ETHCNN_INPUT_CHROMA_FORMAT (400, 420, 422, 444)\n");
+        return 1;
+    }
     if (devs && *devs) { /* "0,1,2,3": worker k on the k-th entry */
         const char* q = devs;
         while (*q && ndev < 64) {
@@ -82,6 +104,7 @@ int main(int argc, char** argv) {
     opt.device = devices[0];
     if (ethcnn_create(&ctx, &opt) != ETHCNN_OK) return fail(NULL, "create");
     t_create = now_ms();
+    if (ethcnn_set_source_format(ctx, &fmt) != ETHCNN_OK) { rc = fail(ctx, "source format"); goto out; }
     if (ethcnn_load_thresholds(ctx, "Thr_info.txt") != ETHCNN_OK) { rc = fail(ctx, "Thr_info.txt"); goto out; }
     if (ethcnn_model_name_for_qp(qp, model, sizeof model) != ETHCNN_OK) { rc = fail(ctx, "model name"); goto out; }
     snprintf(data, sizeof data, "%s.data-00000-of-00001", model);
