@@ -97,6 +97,13 @@ struct Add {
     }
     int commit() {
         if (bad) return set_err(k->c, ETHCNN_ERR_FORMAT, "%llu CTU(s) hold a depth byte above 3 (CU depths are 0..3); nothing was added", (unsigned long long)bad);
+        if (g.ctus_w && done) {  // a run of whole frames: joined to the run in front of it when that has the same geometry
+            if (!k->runs.empty() && k->runs.back().width == g.width && k->runs.back().height == g.height &&
+                k->runs.back().first + k->runs.back().nframes * per == k->ctus)
+                k->runs.back().nframes += done;
+            else
+                k->runs.push_back({k->ctus, g.width, g.height, done});
+        }
         k->ctus += done * per;
         k->subs += done * subs_per_unit;
         k->whole += whole;
@@ -145,6 +152,17 @@ int sim_geom(ethcnn_ctx* c, int width, int height, bool labels, Geom* g) {
     return 0;
 }
 
+int& coord_of(ethcnn_sim_thr& t, int coord) { return coord & 1 ? t.up_k[coord >> 1] : t.down_k[coord >> 1]; }
+
+u128 cost_of(const ethcnn_sim_counts& n, const uint64_t weight[4]) {
+    u128 v = 0;
+    for (int d = 0; d < 4; ++d) v += (u128)weight[d] * n.checked[d];
+    return v;
+}
+}  // namespace
+
+namespace ethcnn {
+namespace sim {
 int check_cand(ethcnn_ctx* c, const ethcnn_sim_thr& t, long long at) {
     for (int l = 0; l < 3; ++l)
         if (t.up_k[l] < 0 || t.up_k[l] > 1024 || t.down_k[l] < -1 || t.down_k[l] > 1024)
@@ -157,15 +175,8 @@ int check_gates(ethcnn_ctx* c, int gate_order) {
         return set_err(c, ETHCNN_ERR_ARG, "gate order %d is none of ETHCNN_SIM_GATES_NONE / _AI / _LDP", gate_order);
     return 0;
 }
-
-int& coord_of(ethcnn_sim_thr& t, int coord) { return coord & 1 ? t.up_k[coord >> 1] : t.down_k[coord >> 1]; }
-
-u128 cost_of(const ethcnn_sim_counts& n, const uint64_t weight[4]) {
-    u128 v = 0;
-    for (int d = 0; d < 4; ++d) v += (u128)weight[d] * n.checked[d];
-    return v;
-}
-}  // namespace
+}  // namespace sim
+}  // namespace ethcnn
 
 extern "C" int ethcnn_sim_create(ethcnn_ctx* c, ethcnn_sim** out) {
     if (!c) return ETHCNN_ERR_ARG;
@@ -208,6 +219,7 @@ extern "C" int ethcnn_sim_reset(ethcnn_sim* k) {
     k->ctus = 0;
     k->subs = 1;
     k->whole = k->labelled = k->rejected = 0;
+    k->runs.clear();
     return ETHCNN_OK;
 }
 

@@ -15,6 +15,7 @@
 // was flagged: a failed add leaves the set as it was.
 #pragma once
 #include <cstdint>
+#include <vector>
 
 #include <hip/hip_runtime_api.h>
 
@@ -44,10 +45,27 @@ void launch_pack(hipStream_t s, const float* probs, const uint8_t* labels, long 
 void launch_eval(hipStream_t s, const unsigned* recs, const unsigned* m, long n, const int* cand, long ncand, int gate_order, unsigned long long* out,
                  int cus);
 
+// a run of whole frames of one geometry inside the set (adjacent adds of the same geometry are one run): what the frame form of
+// the partition decisions (ethcnn_decide.h) checks its window against
+struct FrameRun {
+    int64_t first;  // its first CTU
+    int width, height;
+    int64_t nframes;
+};
+
 }  // namespace sim
 }  // namespace ethcnn
 
 struct ethcnn_ctx;
+struct ethcnn_sim_thr;
+namespace ethcnn {
+namespace sim {
+// the argument rules of a candidate and of a gate order (ethcnn_sim.cpp); 0, or ETHCNN_ERR_ARG with the message set
+int check_cand(ethcnn_ctx* c, const ethcnn_sim_thr& t, long long at);
+int check_gates(ethcnn_ctx* c, int gate_order);
+}  // namespace sim
+}  // namespace ethcnn
+
 struct ethcnn_sim {
     ethcnn_ctx* c = nullptr;
     unsigned* d_recs = nullptr;  // [cap_ctus][16]
@@ -59,4 +77,6 @@ struct ethcnn_sim {
     int* d_cand = nullptr;                 // evaluation buffers, grown on demand
     unsigned long long* d_out = nullptr;
     int64_t cap_cand = 0;
+    std::vector<ethcnn::sim::FrameRun> runs;  // the frame-layout adds, in set order
+    int64_t decide_piece = 0;                 // CTUs per staged piece of ethcnn_decide; 0 = the default
 };

@@ -224,6 +224,11 @@ SIGNATURES = {
     "ethcnn_sim_sweep": (_i, [_vp, _vp, _i, _i, _vp]),
     "ethcnn_sim_search": (_i, [_vp, _vp, _i, _vp, ctypes.c_uint32, _i, _vp, _vp, ctypes.POINTER(_i)]),
     "ethcnn_sim_write_thr_info": (_i, [_cp, _vp, _i]),
+    "ethcnn_decide_device": (_i, [_vp, _vp, _i, _i, ctypes.c_int64, ctypes.c_int64, _vp, _vp, _vp]),
+    "ethcnn_decide": (_i, [_vp, _vp, _i, _i, ctypes.c_int64, ctypes.c_int64, _vp, _vp, _vp]),
+    "ethcnn_decide_set_piece": (_i, [_vp, ctypes.c_int64]),
+    "ethcnn_decide_frames_device": (_i, [_vp, _vp, _i, _i, ctypes.c_int64, _i, _i, ctypes.c_int64, _vp, _vp, _vp]),
+    "ethcnn_decide_counts_from_codes": (_i, [_vp, ctypes.c_int64, _vp]),
     "ethcnn_replay_plan": (_i, [_vp, _sz, _vp, _i, ctypes.POINTER(_i), _vp, ctypes.c_char_p, _sz]),
     "ethcnn_replay_uncut_device": (_i, [_vp, _vp, ctypes.c_int64, _vp, ctypes.c_int64, _i, _i, _i, _vp, _vp]),
     "ethcnn_replay_create": (_i, [_vp, ctypes.c_uint64, ctypes.POINTER(_vp)]),
@@ -1493,6 +1498,9 @@ SIM_THR = np.dtype([("up_k", "<i4", (3,)), ("down_k", "<i4", (3,))])
 SIM_COUNTS = np.dtype([("checked", "<u8", (4,)), ("split_only", "<u8", (3,)), ("current_only", "<u8", (3,)), ("both", "<u8", (3,)),
                        ("edge_split", "<u8", (3,)), ("wrong_split", "<u8", (3,)), ("wrong_stop", "<u8", (3,)), ("bad_ctus", "<u8")])
 SIM_FULL_SEARCH = ((1024, 1024, 1024), (-1, -1, -1))
+# partition decisions: bytes of a codes row, and its flag bits (byte 21)
+SIM_CODE_BYTES = 24
+SIM_FLAG_BAD, SIM_FLAG_LABELLED, SIM_FLAG_REJECTED, SIM_FLAG_GATE1_CLOSED, SIM_FLAG_GATE2_CLOSED = 1, 2, 4, 8, 16
 
 
 def sim_thr(up_k, down_k):
@@ -1521,6 +1529,20 @@ def sim_write_thr_info(path, thr, order, lib=None):
     rc = lib.ethcnn_sim_write_thr_info(os.fsencode(path), thr.ctypes.data, _THR_ORDERS[order])
     if rc:
         raise EthCnnError(rc, lib.ethcnn_last_error(None).decode())
+
+
+def sim_counts_from_codes(codes, lib=None):
+    """ethcnn_decide_counts_from_codes (host only): the SIM_COUNTS record of codes uint8 [n, 24] as PartitionSim.decide returns them --
+    of the whole set it equals PartitionSim.eval of the same candidate; of a frame's or a sequence's rows it is their share"""
+    lib = lib or load_library()
+    codes = np.ascontiguousarray(codes, dtype=np.uint8)
+    if codes.size % SIM_CODE_BYTES:
+        raise ValueError("%d bytes are not whole %d-byte code rows" % (codes.size, SIM_CODE_BYTES))
+    out = np.zeros(1, SIM_COUNTS)
+    rc = lib.ethcnn_decide_counts_from_codes(codes.ctypes.data if codes.size else None, codes.size // SIM_CODE_BYTES, out.ctypes.data)
+    if rc:
+        raise EthCnnError(rc, lib.ethcnn_last_error(None).decode())
+    return out[0]
 
 
 class PartitionSim(object):
@@ -1635,6 +1657,69 @@ class PartitionSim(object):
 
     def write_thr_info(self, path, thr, order):
         sim_write_thr_info(path, thr, order, self.lib)
+
+    # --------------------------------------------------------------------------------------------------- partition decisions ---
+    @staticmethod
+    def _one(thr):
+        thr = _sim_cands(thr)
+        if thr.size != 1:
+            raise ValueError("the decisions are those of one candidate, got %d" % thr.size)
+        return thr
+
+    def set_decide_piece(self, ctus=0):
+        """CTUs per staged piece of decide() (0: the default)"""
+        self._chk(self.lib.ethcnn_decide_set_piece(self.h, int(ctus)))
+
+    def decide(self, thr, gates="none", mid_k=512, first=0, n=None, want=("codes", "reach", "depth")):
+        """the decisions of candidate `thr` on CTUs first .. first + n of the set (include/ethcnn.h "partition decisions") -> dict of
+        numpy arrays: codes uint8 [n, 24], reach uint8 [n, 16], depth uint8 [n, 16] (those named in `want`)"""
+        thr = self._one(thr)
+        n = self.info()["ctus"] - int(first) if n is None else int(n)
+        out = {"codes": np.zeros((max(n, 0), SIM_CODE_BYTES), np.uint8), "reach": np.zeros((max(n, 0), 16), np.uint8),
+               "depth": np.zeros((max(n, 0), 16), np.uint8)}
+        out = {k: v for k, v in out.items() if k in want}
+        ptr = lambda k: out[k].ctypes.data if k in out and out[k].size else None
+        self._chk(self.lib.ethcnn_decide(self.h, thr.ctypes.data, _SIM_GATES[gates], int(mid_k), int(first), n, ptr("codes"), ptr("reach"), ptr("depth")))
+        return out
+
+    def decide_device(self, thr, gates, mid_k, first, n, d_codes, d_reach, d_depth):
+        """the same into buffers in HBM (DeviceBuffer, raw device address or None): [n, 24], [n, 16], [n, 16] bytes"""
+        ptr = lambda b: getattr(b, "ptr", b)
+        self._chk(self.lib.ethcnn_decide_device(self.h, self._one(thr).ctypes.data, _SIM_GATES[gates], int(mid_k), int(first), int(n), ptr(d_codes),
+                                                ptr(d_reach), ptr(d_depth)))
+
+    def decide_frames_device(self, thr, gates, mid_k, first, width, height, nframes, d_codes, d_reach, d_planes):
+        """the frame form into buffers in HBM: whole frames from CTU `first` on, which were added as width x height frames; d_planes
+        [nframes, height / 16, width / 16] takes the preferred partition as label planes"""
+        ptr = lambda b: getattr(b, "ptr", b)
+        self._chk(self.lib.ethcnn_decide_frames_device(self.h, self._one(thr).ctypes.data, _SIM_GATES[gates], int(mid_k), int(first), int(width),
+                                                       int(height), int(nframes), ptr(d_codes), ptr(d_reach), ptr(d_planes)))
+
+    def decide_frames(self, thr, gates, width, height, first_frame=0, nframes=None, mid_k=512, first=0, planes=True):
+        """frames first_frame .. + nframes (default: to the end of the set) of the CTUs added as width x height frames from CTU `first`
+        on -> dict: codes uint8 [nframes * nctu, 24], reach uint8 [nframes * nctu, 16] and, with planes, planes uint8 [nframes,
+        height / 16, width / 16]: the preferred partition in the layout of an Info_*_CUDepth.dat"""
+        width, height = int(width), int(height)
+        if width <= 0 or height <= 0:
+            raise ValueError("got %d x %d" % (width, height))
+        per = ctus_per_frame(width, height)
+        at = int(first) + int(first_frame) * per
+        nf = (self.info()["ctus"] - at) // per if nframes is None else int(nframes)
+        nf = max(nf, 0)
+        sizes = {"codes": nf * per * SIM_CODE_BYTES, "reach": nf * per * 16}
+        if planes:
+            sizes["planes"] = nf * (height // 16) * (width // 16)
+        bufs = {k: self.ctx.alloc(max(v, 16)) for k, v in sizes.items()}
+        try:
+            self.decide_frames_device(thr, gates, mid_k, at, width, height, nf, bufs["codes"], bufs["reach"], bufs.get("planes"))
+            out = {k: bufs[k].download(np.uint8, v) if v else np.zeros(0, np.uint8) for k, v in sizes.items()}
+        finally:
+            for b in bufs.values():
+                b.free()
+        out["codes"], out["reach"] = out["codes"].reshape(-1, SIM_CODE_BYTES), out["reach"].reshape(-1, 16)
+        if planes:
+            out["planes"] = out["planes"].reshape(nf, height // 16, width // 16)
+        return out
 
 
 # ------------------------------------------------------------------------------------------------------ sample-set replay ---

@@ -874,6 +874,62 @@ int ethcnn_sim_search(ethcnn_sim* sim, const ethcnn_sim_thr* start, int gate_ord
 /* the line and token orders of ethcnn_calib_write_thr_info, from six grid values (host only, no context) */
 int ethcnn_sim_write_thr_info(const char* path, const ethcnn_sim_thr* thr, int order);
 
+/* ---- partition decisions: the rule of "partition-search simulation" above under ONE candidate, written out per node of every CTU of a
+ *      simulator's set instead of summed (no reference counterpart).  Where the simulator answers "how many checks remain", this
+ *      answers "where": which nodes are checked, split or forced against their label, which depths stay reachable per 16 x 16 block,
+ *      and the one partition the predictor prefers, in the label format of Info_*_CUDepth.dat.
+ *   Input: CTUs first .. first + n of the set of `sim` (set order = the order of the add calls), the candidate thr (the simulator's
+ *      ranges, else ETHCNN_ERR_ARG), gate_order as for ethcnn_sim_eval -- the gates are applied exactly as there: a closed gate makes
+ *      the level's bins 0 BEFORE the rule and before the comparison with mid_k -- and mid_k in 0..1024 (else ETHCNN_ERR_ARG), on the same
+ *      k / 1024 grid.  first < 0, n < 0 or first + n above the set's size: ETHCNN_ERR_ARG.
+ *   Outputs, per CTU; nodes and blocks in the RASTER order of the 21 probabilities (node 0 = 64 x 64, 1 + x32 + 2 y32, 5 + x16 + 4 y16;
+ *      block b = x16 + 4 y16), whatever order the set keeps inside:
+ *      codes  uint8 [n][24]
+ *        bytes 0..20  one code per node: 0 not visited (rule 1 included), 1 CURRENT ONLY, 2 SPLIT ONLY, 3 BOTH, 4 split because the CU
+ *                     crosses the frame edge (rule 3); 8 is OR-ed in where a labelled CTU is forced against its label: 2 | 8 is a
+ *                     wrong_split, 1 | 8 a wrong_stop of the simulator's counters
+ *        byte 21      flags: bit 0 bad CTU (some node carries the 8), bit 1 labelled, bit 2 rejected, bit 3 the level-1 gate of the CTU's
+ *                     sub-batch is closed, bit 4 the level-2 gate is closed (a closed level-1 gate reads M2 as 0, as in the simulator)
+ *        byte 22      the 8 x 8 CUs that are checked, 0..64 (rule 2: four under a 16 x 16 node with code 2 or 3, the two or the one inside
+ *                     the picture under one with code 4)
+ *        byte 23      0
+ *        A rejected CTU has codes 0, flags 4 (bit 2 alone) and byte 22 = 0.
+ *      reach  uint8 [n][16]: bit d (0..3) of block b is set <=> the pruned search can still give block b depth d: every node above
+ *        depth d on b's path has code 2, 3 or 4 and the node at depth d has code 1 or 3; for d = 3 the 16 x 16 node has code 2, 3 or 4.
+ *        (The 8 does not count.)  Blocks that start outside the picture and rejected CTUs get 0.
+ *      depth  uint8 [n][16]: the ONE partition the predictor prefers, as depths 0..3: from the 64 x 64 node down, a node with code 2 or 4
+ *        splits, with code 1 stops, with code 3 splits <=> its bin > mid_k (the strict > of HM's p > up; 512 is p > 0.5); a block's depth
+ *        is the level of the node that stops above it, 3 when its 16 x 16 node splits.  Blocks that start outside the picture and
+ *        rejected CTUs get 255.  depth always lies inside reach: bit depth[b] of reach[b] is set wherever depth[b] != 255.
+ *        What the bad flag is NOT: a labelled CTU whose reach lacks its label's bit somewhere is bad, but a bad CTU need not lack one:
+ *        the simulator judges every decided node by its own flag, "whatever happened above it", so a SPLIT ONLY node BELOW the label's
+ *        leaf (reached through a BOTH node that the label does not split) is a wrong_split although the label stays reachable.
+ *      planes uint8 [nframes][H / 16][W / 16] (frame form only): depth scattered into label planes, the layout of Info_*_CUDepth.dat.
+ *        Every block inside the picture is written, those of partial CTUs included; nothing outside the planes is.
+ *   counts_from_codes gives back the simulator's counters of any slice of codes: codes of ethcnn_decide* summed over the whole set EQUAL
+ *      ethcnn_sim_eval of the same candidate and gate order in every field; slices by frame or sequence give the breakdowns.
+ *   Any output pointer may be NULL (nothing of it is computed); device pointers must be 4-byte aligned (else ETHCNN_ERR_ARG); every
+ *      entry is synchronous on the context's stream; n == 0 / nframes == 0 is a no-op; a call that fails leaves the outputs untouched.
+ *      Every output byte has one writer and everything is integers: the bytes do not depend on the grid or on how a set is split. */
+int ethcnn_decide_device(ethcnn_sim* sim, const ethcnn_sim_thr* thr, int gate_order, int mid_k, int64_t first, int64_t n, uint8_t* d_codes,
+                         uint8_t* d_reach, uint8_t* d_depth);
+/* The same into host memory, staged in pieces of ethcnn_decide_set_piece CTUs (0 = the default, 2^20) through one device buffer of
+ * piece * (24 + 16 + 16) bytes (the outputs asked for only).  That size is checked against the free device memory before anything is
+ * allocated: on shortage ETHCNN_ERR_NOMEM, the byte count in the message.  The bytes do not depend on the piece size. */
+int ethcnn_decide(ethcnn_sim* sim, const ethcnn_sim_thr* thr, int gate_order, int mid_k, int64_t first, int64_t n, uint8_t* codes, uint8_t* reach,
+                  uint8_t* depth);
+int ethcnn_decide_set_piece(ethcnn_sim* sim, int64_t ctus);
+/* The frame form: nframes whole frames from CTU `first` on, which must have been added as width x height frames by ethcnn_sim_add_frames*
+ * (or ethcnn_replay_feed_sim): first on a frame boundary of such an add and all nframes inside it (adds of one geometry that follow
+ * each other count as one), else ETHCNN_ERR_ARG.  d_codes [nframes * nctu][24], d_reach [nframes * nctu][16] as above; d_planes
+ * [nframes][height / 16][width / 16] needs width and height to be multiples of 16 (else ETHCNN_ERR_ARG) and no alignment. */
+int ethcnn_decide_frames_device(ethcnn_sim* sim, const ethcnn_sim_thr* thr, int gate_order, int mid_k, int64_t first, int width, int height,
+                                int64_t nframes, uint8_t* d_codes, uint8_t* d_reach, uint8_t* d_planes);
+/* Host only, no context: the ethcnn_sim_counts of codes [n][24]: checked[0..2] from codes 1 and 3, checked[3] from byte 22, split_only /
+ * current_only / both / edge_split from codes 2 / 1 / 3 / 4, wrong_split / wrong_stop from the 8, bad_ctus from flag bit 0.  n == 0 gives
+ * zeroes.  NULL or n < 0: ETHCNN_ERR_ARG; a byte that no ethcnn_decide* call writes: ETHCNN_ERR_FORMAT; both leave counts_out untouched. */
+int ethcnn_decide_counts_from_codes(const uint8_t* codes, int64_t n, ethcnn_sim_counts* counts_out);
+
 /* ---- sample-set replay: an inter sample set (LDP_Valid.dat, LDP_Test.dat, plain or _shuffled: the 16516-byte records of "sample sets"
  *      above) put back together into the residual pictures and label planes it was cut from, and run through the deployed Low-Delay-P
  *      chain, ethcnn_ldp_sequence_device: forward in time, i_frame % 4 features, the state carried over the whole sequence.  The inverse

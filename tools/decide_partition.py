@@ -1,0 +1,163 @@
+#!/usr/bin/env python
+"""Writes out WHERE HM's pruned CU search goes under a Thr_info.txt: per node, per block, per frame.
+
+simulate_thresholds.py counts the rate-distortion checks a candidate file leaves over a whole set.  This tool evaluates the same rule
+on the GPU for one file and keeps the outcome of every node (include/ethcnn.h "partition decisions"): the partition the predictor
+prefers in the encoder's own label format, the depths that stay reachable per 16x16 block, and per-frame tables of checks and bad CTUs.
+
+    decide_partition.py --thr-info FILE --order ai|ldp [--gates ai|ldp|none] [--mid P] OUTPUT... [--device N] CASE...
+
+Outputs (at least one):
+  --depth-out FILE   the preferred partition as an Info_*_CUDepth.dat: one byte per 16x16 block, raster, frame after frame, the cases
+                     in the order given.  tools/score_cu_depth.py, the sample-set builders and label viewers read it as a label
+                     file.  Needs cases that come as frames (--case, --yuv) with sizes that are multiples of 16 and no rejected CTU
+                     (a NaN or a value outside [0, 1] among its probabilities); refuses otherwise and says which.
+  --codes-out FILE   raw uint8 [CTUs][24]: one code per node (0 not visited, 1 current only, 2 split only, 3 both, 4 frame edge, +8
+                     forced against the label), then flags, the checked 8x8 CUs and a zero byte.
+  --reach-out FILE   raw uint8 [CTUs][16]: bit d of a block's byte is set when the pruned search can still give it depth d.
+  --per-frame        one CSV row per frame on stdout: checks per CU size, their weighted sum (--weights W64 W32 W16 W8, default
+                     64 16 4 1) absolutely and as a share of the full search's on that frame, bad and labelled CTUs, CTUs whose
+                     level-1 / level-2 gate is closed.  CTUs of a --samples case without --ldp have no frames: one row per case.
+
+--mid P (0..1, default 0.5, snapped to the grid k / 1024): where both choices are left open the preferred partition splits when
+p > P.  Cases, --gates and the rounding of the thresholds are those of simulate_thresholds.py.
+"""
+import importlib
+import importlib.util
+import os
+import sys
+
+import numpy as np
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+_spec = importlib.util.spec_from_file_location("simulate_thresholds", os.path.join(ROOT, "tools", "simulate_thresholds.py"))
+sim_tool = importlib.util.module_from_spec(_spec)
+_spec.loader.exec_module(sim_tool)
+cal_tool = sim_tool.cal_tool
+Usage = sim_tool.Usage
+
+
+def parse(argv):
+    """-> (options, cases): this tool's options are taken out, the cases go through the calibrate tool's parser"""
+    opt = {"thr_info": None, "order": None, "gates": None, "mid": 0.5, "depth_out": None, "codes_out": None, "reach_out": None, "per_frame": False,
+           "weights": [64, 16, 4, 1], "device": 0}
+    one = {"--thr-info": ("thr_info", str), "--order": ("order", str), "--gates": ("gates", str), "--mid": ("mid", float), "--depth-out": ("depth_out", str),
+           "--codes-out": ("codes_out", str), "--reach-out": ("reach_out", str), "--device": ("device", int)}
+    rest, i = [], 0
+    while i < len(argv):
+        a = argv[i]
+        i += 1
+        if a in ("-h", "--help"):
+            raise Usage("")
+        elif a in one:
+            v, i = cal_tool._take(argv, i, 1, a)
+            opt[one[a][0]] = one[a][1](v[0])
+        elif a == "--weights":
+            v, i = cal_tool._take(argv, i, 4, a)
+            opt["weights"] = [int(x) for x in v]
+        elif a == "--per-frame":
+            opt["per_frame"] = True
+        else:
+            rest.append(a)
+    if opt["thr_info"] is None or opt["order"] not in ("ai", "ldp"):
+        raise Usage("--thr-info FILE and --order ai|ldp name the candidate and say how it is read")
+    if opt["gates"] is None:
+        opt["gates"] = opt["order"]
+    if opt["gates"] not in ("ai", "ldp", "none"):
+        raise Usage("--gates is ai, ldp or none")
+    if not 0.0 <= opt["mid"] <= 1.0:
+        raise Usage("--mid is a probability, 0..1")
+    opt["mid_k"] = int(round(opt["mid"] * 1024))
+    if min(opt["weights"]) < 0:
+        raise Usage("--weights are not negative")
+    if not (opt["depth_out"] or opt["codes_out"] or opt["reach_out"] or opt["per_frame"]):
+        raise Usage("nothing to do: give --depth-out, --codes-out, --reach-out or --per-frame")
+    _, cases = cal_tool.parse(rest, labels_optional=True)
+    for c in cases:
+        if c["kind"] == "case" and c["labels"] == "-":
+            c["labels"] = None
+        if c["kind"] == "samples" and opt["depth_out"]:
+            raise Usage("--depth-out needs cases that come as frames (--case, --yuv): a --samples case has no label planes to fill")
+    return opt, cases
+
+
+def run(opt, cases, out=sys.stdout, err=sys.stderr):
+    if ROOT not in sys.path:
+        sys.path.insert(0, ROOT)
+    pkg = importlib.import_module("hevc-complexity-reduction_amd")
+    e = pkg.ethcnn
+    note = lambda s: err.write(s + "\n")
+    thr = e.sim_thr(*sim_tool.read_thr_info(opt["thr_info"], opt["order"]))
+    full = e.sim_thr(*e.SIM_FULL_SEARCH)
+    ctx = pkg.EthCnn(device=opt["device"])
+    try:
+        sim = pkg.PartitionSim(ctx)
+        spans = []  # (first CTU, CTUs, width, height) per case; width 0: no frames
+        for c in cases:
+            first = sim.info()["ctus"]
+            cal_tool.add_cases(pkg, ctx, sim, [c], note)
+            framed = c["kind"] != "samples"
+            spans.append((first, sim.info()["ctus"] - first, c["w"] if framed else 0, c["h"] if framed else 0))
+        info = sim.info()
+        if opt["depth_out"]:
+            odd = ["%dx%d" % (w, h) for _, _, w, h in spans if w % 16 or h % 16]
+            if info["rejected_ctus"]:
+                raise ValueError("--depth-out: %d CTU(s) were rejected (a NaN or a value outside [0, 1] among their probabilities): they have no partition"
+                                 % info["rejected_ctus"])
+            if odd:
+                raise ValueError("--depth-out: label planes exist for sizes that are multiples of 16, not for %s" % ", ".join(odd))
+        codes, reach, planes, rows = [], [], [], []
+        for k, (first, n, w, h) in enumerate(spans):
+            if w:
+                per = e.ctus_per_frame(w, h)
+                got = sim.decide_frames(thr, opt["gates"], w, h, nframes=n // per, mid_k=opt["mid_k"], first=first, planes=bool(opt["depth_out"]))
+                if opt["depth_out"]:
+                    planes.append(got["planes"])
+            else:
+                per = n
+                got = sim.decide(thr, opt["gates"], opt["mid_k"], first, n, want=("codes", "reach"))
+            codes.append(got["codes"])
+            reach.append(got["reach"])
+            if opt["per_frame"] and n:
+                ref = sim.decide(full, "none", 512, first, n, want=("codes",))["codes"]
+                for f in range(n // per):
+                    sl = slice(f * per, (f + 1) * per)
+                    a, b = e.sim_counts_from_codes(got["codes"][sl], ctx.lib), e.sim_counts_from_codes(ref[sl], ctx.lib)
+                    cost = sum(wt * int(x) for wt, x in zip(opt["weights"], a["checked"]))
+                    full_cost = sum(wt * int(x) for wt, x in zip(opt["weights"], b["checked"]))
+                    flags = got["codes"][sl, 21]
+                    rows.append((k, f, per) + tuple(int(x) for x in a["checked"]) + (cost, sim_tool._share(cost, full_cost), int(a["bad_ctus"]))
+                                + tuple(int(((flags & bit) != 0).sum()) for bit in (e.SIM_FLAG_LABELLED, e.SIM_FLAG_GATE1_CLOSED, e.SIM_FLAG_GATE2_CLOSED)))
+    finally:
+        ctx.close()
+    for path, parts in ((opt["depth_out"], planes), (opt["codes_out"], codes), (opt["reach_out"], reach)):
+        if path:
+            with open(path, "wb") as f:
+                for p in parts:
+                    f.write(np.ascontiguousarray(p).tobytes())
+            note("wrote %s: %d bytes" % (path, sum(p.size for p in parts)))
+    if opt["per_frame"]:
+        out.write("case,frame,ctus,checked64,checked32,checked16,checked8,cost,cost_share,bad_ctus,labelled_ctus,gate1_closed_ctus,gate2_closed_ctus\n")
+        for r in rows:
+            out.write("%d,%d,%d,%d,%d,%d,%d,%d,%.6f,%d,%d,%d,%d\n" % r)
+    return {"info": info, "spans": spans, "rows": rows}
+
+
+def main(argv):
+    try:
+        opt, cases = parse(list(argv[1:]))
+    except (Usage, ValueError) as e:
+        sys.stderr.write(__doc__)
+        if str(e):
+            sys.stderr.write("\nerror: %s\n" % e)
+        return 2
+    try:
+        run(opt, cases)
+    except (ValueError, OSError, RuntimeError) as e:  # (libethcnn errors are RuntimeErrors)
+        sys.stderr.write("error: %s\n" % e)
+        return 1
+    return 0
+
+
+if __name__ == "__main__":
+    sys.exit(main(sys.argv))
