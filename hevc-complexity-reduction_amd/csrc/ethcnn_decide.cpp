@@ -115,14 +115,7 @@ extern "C" int ethcnn_decide_frames_device(ethcnn_sim* k, const ethcnn_sim_thr* 
     if (((uintptr_t)d_codes | (uintptr_t)d_reach) % 4) return set_err(c, ETHCNN_ERR_ARG, "device buffer not 4-byte aligned");
     const int ctus_w = (width + 63) / 64, ctus_h = (height + 63) / 64;
     const int64_t per = (int64_t)ctus_w * ctus_h;
-    bool found = false;
-    for (const ethcnn::sim::FrameRun& r : k->runs)
-        if (r.width == width && r.height == height && first >= r.first && (first - r.first) % per == 0 && (first - r.first) / per <= r.nframes &&
-            nframes <= r.nframes - (first - r.first) / per)
-            found = true;
-    if (!found)
-        return set_err(c, ETHCNN_ERR_ARG, "CTU %lld + %lld frames do not lie on the frame boundaries of CTUs added as %d x %d frames", (long long)first,
-                       (long long)nframes, width, height);
+    if (int rc = ethcnn::sim::check_frame_run(k, first, width, height, nframes)) return rc;
     if (nframes == 0) return ETHCNN_OK;
     return run(k, cand, first, nframes * per, Planes{d_planes, ctus_w, ctus_h, width / 16, height / 16}, d_codes, d_reach, nullptr);
 }

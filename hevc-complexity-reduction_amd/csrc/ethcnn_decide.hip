@@ -5,6 +5,7 @@
 #include <hip/hip_runtime.h>
 
 #include "ethcnn_decide.h"
+#include "ethcnn_node_masks.h"
 #include "ethcnn_sim.h"
 
 namespace ethcnn {
@@ -13,14 +14,10 @@ namespace decide {
 namespace {
 using sim::kL1;
 using sim::kL2;
+using sim::raster_of;
 constexpr int kThreads = 256;
 constexpr int kNout = 21;
 constexpr int kCodeDwords = kCodeBytes / 4;
-
-// quad-order node k -> its raster index among the 21 probabilities (ethcnn_sim.hip, k_sim_pack)
-__host__ __device__ constexpr int raster_of(int k) {
-    return k < 5 ? k : 5 + (2 * (((k - 5) >> 2) & 1) + ((k - 5) & 1)) + 4 * (2 * (((k - 5) >> 2) >> 1) + (((k - 5) & 3) >> 1));
-}
 
 __device__ __forceinline__ void store_block16(uint8_t* dst, long ctu, const unsigned v[4], bool wide) {
     if (wide) {
@@ -71,13 +68,8 @@ __global__ __launch_bounds__(kThreads) void k_decide(const uint4* __restrict__ r
         so &= ~closed;
         gm &= ~closed;  // (mid >= 0: a zeroed bin is never above it)
         le = (le & ~closed) | (closed & zero_le);
-        const unsigned co = le & ~so;
-        const unsigned rec = (inside & ~co) | edge;  // a visited node with this bit visits its sub-CUs
-        unsigned vis = 1u | ((0u - (rec & 1u)) & kL1);
-        const unsigned tt = (rec & vis) >> 1 & 0xfu, x = (tt | tt << 3 | tt << 6 | tt << 9) & 0x1111u;
-        vis |= (x * 15u) << 5;
-        const unsigned dec = vis & inside, edg = vis & edge;
-        const unsigned d_so = dec & so, d_co = dec & co, d_bo = dec & ~so & ~le;
+        const sim::Descent ds = sim::descend(so, le, inside, edge);
+        const unsigned rec = ds.rec, dec = ds.dec, edg = ds.edg, d_so = ds.d_so, d_co = ds.d_co, d_bo = ds.d_bo;
         const unsigned t_split = truth & 0x1fffffu, t_unsplit = (truth >> 31 ? ~truth : 0u) & 0x1fffffu;
         const unsigned wrong = (d_so & t_unsplit) | (d_co & t_split);
         const unsigned cur_m = d_co | d_bo;           // the node itself can be the leaf

@@ -175,6 +175,16 @@ int check_gates(ethcnn_ctx* c, int gate_order) {
         return set_err(c, ETHCNN_ERR_ARG, "gate order %d is none of ETHCNN_SIM_GATES_NONE / _AI / _LDP", gate_order);
     return 0;
 }
+
+int check_frame_run(ethcnn_sim* k, int64_t first, int width, int height, int64_t nframes) {
+    const int64_t per = (int64_t)((width + 63) / 64) * ((height + 63) / 64);
+    for (const FrameRun& r : k->runs)
+        if (r.width == width && r.height == height && first >= r.first && (first - r.first) % per == 0 && (first - r.first) / per <= r.nframes &&
+            nframes <= r.nframes - (first - r.first) / per)
+            return 0;
+    return set_err(k->c, ETHCNN_ERR_ARG, "CTU %lld + %lld frames do not lie on the frame boundaries of CTUs added as %d x %d frames", (long long)first,
+                   (long long)nframes, width, height);
+}
 }  // namespace sim
 }  // namespace ethcnn
 
@@ -210,6 +220,8 @@ extern "C" void ethcnn_sim_destroy(ethcnn_sim* k) {
     if (k->d_call) (void)hipFree(k->d_call);
     if (k->d_cand) (void)hipFree(k->d_cand);
     if (k->d_out) (void)hipFree(k->d_out);
+    for (int* p : k->d_budget_thr)
+        if (p) (void)hipFree(p);
     if (k->h_call) (void)hipHostFree(k->h_call);
     delete k;
 }

@@ -66,6 +66,15 @@ int check_gates(ethcnn_ctx* c, int gate_order);
 }  // namespace sim
 }  // namespace ethcnn
 
+struct ethcnn_sim;
+namespace ethcnn {
+namespace sim {
+// the window rule of the frame forms (ethcnn_decide_frames_device, ethcnn_budget_*): nframes whole frames from CTU `first` on lie
+// inside one run of width x height frames, `first` on a frame boundary of it; 0, or ETHCNN_ERR_ARG with the message set
+int check_frame_run(ethcnn_sim* k, int64_t first, int width, int height, int64_t nframes);
+}  // namespace sim
+}  // namespace ethcnn
+
 struct ethcnn_sim {
     ethcnn_ctx* c = nullptr;
     unsigned* d_recs = nullptr;  // [cap_ctus][16]
@@ -78,5 +87,7 @@ struct ethcnn_sim {
     unsigned long long* d_out = nullptr;
     int64_t cap_cand = 0;
     std::vector<ethcnn::sim::FrameRun> runs;  // the frame-layout adds, in set order
-    int64_t decide_piece = 0;                 // CTUs per staged piece of ethcnn_decide; 0 = the default
+    int64_t decide_piece = 0;                 // CTUs per staged piece of ethcnn_decide and ethcnn_budget_bake; 0 = the default
+    int* d_budget_thr[2] = {nullptr, nullptr};  // search budget: the ladder and the per-frame thresholds, grown on demand
+    int64_t cap_budget_thr[2] = {0, 0};         // (in rows of six ints)
 };

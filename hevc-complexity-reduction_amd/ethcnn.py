@@ -229,6 +229,14 @@ SIGNATURES = {
     "ethcnn_decide_set_piece": (_i, [_vp, ctypes.c_int64]),
     "ethcnn_decide_frames_device": (_i, [_vp, _vp, _i, _i, ctypes.c_int64, _i, _i, ctypes.c_int64, _vp, _vp, _vp]),
     "ethcnn_decide_counts_from_codes": (_i, [_vp, ctypes.c_int64, _vp]),
+    "ethcnn_budget_default_ladder": (_i, [_vp]),
+    "ethcnn_budget_companion_thr": (_i, [_vp]),
+    "ethcnn_budget_choose": (_i, [_vp, ctypes.c_int64, ctypes.c_int64, _vp, ctypes.c_uint32, _i, _vp, _vp, _vp, _vp]),
+    "ethcnn_budget_cost": (_i, [_vp, _vp, ctypes.c_int64, ctypes.c_int64, _i, _i, ctypes.c_int64, _vp]),
+    "ethcnn_budget_cost_device": (_i, [_vp, _vp, ctypes.c_int64, ctypes.c_int64, _i, _i, ctypes.c_int64, _vp]),
+    "ethcnn_budget_bake_device": (_i, [_vp, _vp, ctypes.c_int64, _vp, ctypes.c_int64, _i, _i, ctypes.c_int64, _vp]),
+    "ethcnn_budget_bake": (_i, [_vp, _vp, ctypes.c_int64, _vp, ctypes.c_int64, _i, _i, ctypes.c_int64, _vp]),
+    "ethcnn_budget_control": (_i, [_vp, _vp, ctypes.c_int64, _vp, ctypes.c_uint32, _i, ctypes.c_int64, _i, _i, ctypes.c_int64, _vp, _vp, _vp, _vp, _vp]),
     "ethcnn_replay_plan": (_i, [_vp, _sz, _vp, _i, ctypes.POINTER(_i), _vp, ctypes.c_char_p, _sz]),
     "ethcnn_replay_uncut_device": (_i, [_vp, _vp, ctypes.c_int64, _vp, ctypes.c_int64, _i, _i, _i, _vp, _vp]),
     "ethcnn_replay_create": (_i, [_vp, ctypes.c_uint64, ctypes.POINTER(_vp)]),
@@ -1545,6 +1553,58 @@ def sim_counts_from_codes(codes, lib=None):
     return out[0]
 
 
+# search budget (include/ethcnn.h "search budget")
+BUDGET_FRAME, BUDGET_CARRY = 0, 1
+_BUDGET_MODES = {"frame": BUDGET_FRAME, "carry": BUDGET_CARRY}
+BUDGET_DEFAULT_RUNGS, BUDGET_MAX_RUNGS = 513, 4096
+BUDGET_WEIGHTS = (64, 16, 4, 1)
+
+
+def budget_default_ladder(lib=None):
+    """ethcnn_budget_default_ladder (host only): SIM_THR records [513], rung j = up_k 1024 - j, down_k j - 1 on all levels"""
+    lib = lib or load_library()
+    out = np.zeros(BUDGET_DEFAULT_RUNGS, SIM_THR)
+    rc = lib.ethcnn_budget_default_ladder(out.ctypes.data)
+    if rc:
+        raise EthCnnError(rc, lib.ethcnn_last_error(None).decode())
+    return out
+
+
+def budget_companion_thr(lib=None):
+    """ethcnn_budget_companion_thr (host only): the SIM_THR record (768, 256 on all levels) of the Thr_info.txt that goes with a baked
+    cu_depth.dat; sim_write_thr_info writes it"""
+    lib = lib or load_library()
+    out = np.zeros(1, SIM_THR)
+    rc = lib.ethcnn_budget_companion_thr(out.ctypes.data)
+    if rc:
+        raise EthCnnError(rc, lib.ethcnn_last_error(None).decode())
+    return out[0]
+
+
+def _budget_mode(mode):
+    if mode not in _BUDGET_MODES:
+        raise ValueError("mode is 'frame' or 'carry', got %r" % (mode,))
+    return _BUDGET_MODES[mode]
+
+
+def budget_choose(checked, weights=None, budget_ppm=1000000, mode="frame", lib=None):
+    """ethcnn_budget_choose (host only): checked uint32 [F, K + 1, 4] as PartitionSim.budget_cost returns it (column K = the full
+    search) -> dict: rung int32 [F], over bool [F], cost uint64 [F], full uint64 [F]"""
+    lib = lib or load_library()
+    checked = np.ascontiguousarray(checked, dtype=np.uint32)
+    if checked.ndim != 3 or checked.shape[1] < 2 or checked.shape[2] != 4:
+        raise ValueError("checked is [frames, K + 1, 4], got shape %r" % (checked.shape,))
+    nf, k = checked.shape[0], checked.shape[1] - 1
+    w = (ctypes.c_uint64 * 4)(*[int(x) for x in (BUDGET_WEIGHTS if weights is None else weights)])
+    rung, over = np.zeros(nf, np.int32), np.zeros(nf, np.uint8)
+    cost, full = np.zeros(nf, np.uint64), np.zeros(nf, np.uint64)
+    rc = lib.ethcnn_budget_choose(checked.ctypes.data if nf else None, nf, k, w, int(budget_ppm), _budget_mode(mode), rung.ctypes.data, over.ctypes.data,
+                                  cost.ctypes.data, full.ctypes.data)
+    if rc:
+        raise EthCnnError(rc, lib.ethcnn_last_error(None).decode())
+    return {"rung": rung, "over": over.astype(bool), "cost": cost, "full": full}
+
+
 class PartitionSim(object):
     """HM's pruned CU search simulated over a set of predicted CTUs that stays in HBM, for any number of candidate Thr_info files at
     once (include/ethcnn.h "partition-search simulation"): the RD checks that remain per CU size and, with labels, the labelled
@@ -1719,6 +1779,70 @@ class PartitionSim(object):
         out["codes"], out["reach"] = out["codes"].reshape(-1, SIM_CODE_BYTES), out["reach"].reshape(-1, 16)
         if planes:
             out["planes"] = out["planes"].reshape(nf, height // 16, width // 16)
+        return out
+
+    # --------------------------------------------------------------------------------------------------------- search budget ---
+    def _budget_window(self, ladder, width, height, first, nframes):
+        """-> (ladder records, K, first CTU, frames): nframes None = to the end of the set"""
+        ladder = budget_default_ladder(self.lib) if ladder is None else _sim_cands(ladder)
+        width, height = int(width), int(height)
+        if width <= 0 or height <= 0:
+            raise ValueError("got %d x %d" % (width, height))
+        nf = (self.info()["ctus"] - int(first)) // ctus_per_frame(width, height) if nframes is None else int(nframes)
+        return ladder, ladder.size, int(first), max(nf, 0)
+
+    def budget_cost(self, ladder=None, first=0, width=0, height=0, nframes=None):
+        """the checks that every rung of `ladder` (SIM_THR records, default: budget_default_ladder()) leaves on each of nframes whole
+        width x height frames from CTU `first` on (include/ethcnn.h "search budget") -> uint32 [F, K + 1, 4]: checked[0..3] per frame and
+        rung, column K the full search"""
+        ladder, k, first, nf = self._budget_window(ladder, width, height, first, nframes)
+        out = np.zeros((nf, k + 1, 4), np.uint32)
+        self._chk(self.lib.ethcnn_budget_cost(self.h, ladder.ctypes.data, k, first, int(width), int(height), nf, out.ctypes.data if nf else None))
+        return out
+
+    def budget_cost_device(self, ladder, first, width, height, nframes, d_checked):
+        """the same into a buffer in HBM (DeviceBuffer or raw device address): [nframes, K + 1, 4] uint32"""
+        ladder = budget_default_ladder(self.lib) if ladder is None else _sim_cands(ladder)
+        self._chk(self.lib.ethcnn_budget_cost_device(self.h, ladder.ctypes.data, ladder.size, int(first), int(width), int(height), int(nframes),
+                                                     getattr(d_checked, "ptr", d_checked)))
+
+    def budget_bake(self, ladder, rung, first=0, width=0, height=0, nframes=None):
+        """the decisions of rung[f] of `ladder` (None: the default ladder) on frame f, as the values an unchanged encoder reads under the
+        companion thresholds -> float32 [n, 21]: 1.0 split only or frame edge, 0.0 current only or not visited, 0.5 both (a rejected
+        CTU: 0.5 everywhere)"""
+        ladder, k, first, nf = self._budget_window(ladder, width, height, first, nframes)
+        rung = np.ascontiguousarray(rung, dtype=np.int32).reshape(-1)
+        if rung.size != nf:
+            raise ValueError("%d frames, %d rungs" % (nf, rung.size))
+        out = np.zeros((nf * ctus_per_frame(int(width), int(height)), NOUT), np.float32)
+        self._chk(self.lib.ethcnn_budget_bake(self.h, ladder.ctypes.data, k, rung.ctypes.data if nf else None, first, int(width), int(height), nf,
+                                              out.ctypes.data if nf else None))
+        return out
+
+    def budget_bake_device(self, ladder, rung, first, width, height, nframes, d_probs):
+        """the same into a buffer in HBM (DeviceBuffer or raw device address): [nframes * nctu, 21] float32; rung stays a host array"""
+        ladder = budget_default_ladder(self.lib) if ladder is None else _sim_cands(ladder)
+        rung = np.ascontiguousarray(rung, dtype=np.int32).reshape(-1)
+        if rung.size != int(nframes):
+            raise ValueError("%d frames, %d rungs" % (int(nframes), rung.size))
+        self._chk(self.lib.ethcnn_budget_bake_device(self.h, ladder.ctypes.data, ladder.size, rung.ctypes.data if rung.size else None, int(first), int(width),
+                                                     int(height), int(nframes), getattr(d_probs, "ptr", d_probs)))
+
+    def budget_control(self, budget, mode="frame", ladder=None, weights=None, first=0, width=0, height=0, nframes=None, probs=True):
+        """cost, choice and bake in one call.  budget: the share of the full search a frame may take, 0..1 (rounded to parts per
+        million); mode "frame" (every frame on its own) or "carry" (what a frame leaves goes to the next) -> dict: probs float32 [n, 21]
+        (unless probs=False), rung int32 [F], over bool [F], cost uint64 [F], full uint64 [F]"""
+        if not 0.0 <= float(budget) <= 1.0:
+            raise ValueError("the budget is a share of the full search, 0..1: got %r" % (budget,))
+        lad, k, first, nf = self._budget_window(ladder, width, height, first, nframes)
+        w = None if weights is None else (ctypes.c_uint64 * 4)(*[int(x) for x in weights])
+        out = {"rung": np.zeros(nf, np.int32), "over": np.zeros(nf, np.uint8), "cost": np.zeros(nf, np.uint64), "full": np.zeros(nf, np.uint64)}
+        if probs:
+            out["probs"] = np.zeros((nf * ctus_per_frame(int(width), int(height)), NOUT), np.float32)
+        ptr = lambda name: out[name].ctypes.data if name in out and out[name].size else None
+        self._chk(self.lib.ethcnn_budget_control(self.h, None if ladder is None else lad.ctypes.data, k, w, int(round(float(budget) * 1e6)), _budget_mode(mode),
+                                                 first, int(width), int(height), nf, ptr("probs"), ptr("rung"), ptr("over"), ptr("cost"), ptr("full")))
+        out["over"] = out["over"].astype(bool)
         return out
 
 

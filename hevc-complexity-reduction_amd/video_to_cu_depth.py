@@ -13,6 +13,11 @@ Differences from the reference, all outside the numbers it produces:
   * HM's command line is fixed, so the source format of the file comes through the environment: ETHCNN_INPUT_BIT_DEPTH=8..16 (HM's
     InputBitDepth; above 8 the file holds 16-bit samples) and ETHCNN_INPUT_CHROMA_FORMAT=400|420|422|444 (InputChromaFormat).  Unset:
     the reference's 8-bit 4:2:0.  A bad value is a non-zero exit with a message.
+  * ETHCNN_SEARCH_BUDGET=<share, 0..1> holds every frame's pruned search under that share of the full search's weighted checks
+    (include/ethcnn.h "search budget"): the launcher predicts with open gates, picks a rung of the default ladder per frame and
+    writes a BAKED cu_depth.dat (values 0, 0.5, 1).  HM reads Thr_info.txt afterwards, so the launcher refuses (exit status 1, no
+    cu_depth.dat) unless that file is the companion line "0.75 0.25 0.75 0.25 0.75 0.25".  ETHCNN_SEARCH_BUDGET_MODE=frame|carry
+    (default frame) and ETHCNN_SEARCH_BUDGET_WEIGHTS="64 16 4 1" are optional.  One GPU only: ETHCNN_DEVICES with a budget is refused.
 """
 from __future__ import print_function
 
@@ -56,6 +61,71 @@ def source_format_from_env():
             raise ValueError("%s='%s' (allowed: %s)" % (name, text, ', '.join(str(v) for v in ok)))
         fmt.append(value)
     return tuple(fmt)
+
+
+COMPANION_LINE = '0.75 0.25 0.75 0.25 0.75 0.25'   # ethcnn_budget_companion_thr in All-Intra token order
+
+
+def search_budget_from_env():
+    """None when ETHCNN_SEARCH_BUDGET is unset or empty, else (share, mode, weights or None); ValueError names a bad value"""
+    text = os.environ.get('ETHCNN_SEARCH_BUDGET')
+    if text is None or text == '':
+        return None
+    try:
+        share = float(text)
+    except ValueError:
+        share = -1.0
+    if not 0.0 <= share <= 1.0:   # (a NaN fails both comparisons)
+        raise ValueError("ETHCNN_SEARCH_BUDGET='%s' is not a share of the full search, 0..1" % text)
+    mode = os.environ.get('ETHCNN_SEARCH_BUDGET_MODE') or 'frame'
+    if mode not in ('frame', 'carry'):
+        raise ValueError("ETHCNN_SEARCH_BUDGET_MODE='%s' (allowed: frame, carry)" % mode)
+    weights = None
+    text = os.environ.get('ETHCNN_SEARCH_BUDGET_WEIGHTS')
+    if text:
+        try:
+            weights = [int(t) for t in text.split()]
+        except ValueError:
+            weights = []
+        if len(weights) != 4 or min(weights) < 0 or max(weights) >= 1 << 32:
+            raise ValueError("ETHCNN_SEARCH_BUDGET_WEIGHTS='%s' is not four integers W64 W32 W16 W8 in 0..2^32-1" % text)
+    if os.environ.get('ETHCNN_DEVICES'):
+        raise ValueError('ETHCNN_SEARCH_BUDGET runs on one GPU: unset ETHCNN_DEVICES (ETHCNN_DEVICE picks the GPU)')
+    return share, mode, weights
+
+
+def check_companion_thr_file(path=THR_FILE):
+    """A baked cu_depth.dat means what it says only under the companion thresholds, and HM reads them from this file after the
+    launcher has run: ValueError unless it holds exactly that line's six values"""
+    try:
+        tokens = [float(t) for t in open(path).read().split()]
+    except (OSError, ValueError):
+        tokens = None
+    if tokens != [float(t) for t in COMPANION_LINE.split()]:
+        raise ValueError("ETHCNN_SEARCH_BUDGET is set, so the encoder must read the companion thresholds: put the line\n    %s\ninto %s "
+                         "(found: %s)" % (COMPANION_LINE, path, 'no readable file' if tokens is None else ' '.join('%g' % t for t in tokens)))
+
+
+def write_budgeted(ctx, yuv_name, qp_seq, frame_width, frame_height, budget, save_file):
+    """budget mode: every frame of the file predicted with open gates, one rung of the default ladder picked per frame under the
+    budget, the picked decisions baked into save_file (temp file + rename).  -> (frames, achieved share, over-budget frames)"""
+    import numpy as np
+    share, mode, weights = budget
+    tmp = '%s.tmp.%d' % (save_file, os.getpid())
+    try:
+        ctx.set_thresholds(0.0, 0.0)    # open gates, whatever Thr_info.txt says: the baked file is what the encoder reads
+        n_frames = ctx.predict_yuv_file(yuv_name, frame_width, frame_height, qp_seq, tmp)
+        probs = np.fromfile(tmp, dtype='<f4')
+        with _e.PartitionSim(ctx) as sim:
+            sim.add_frames(probs, None, frame_width, frame_height, nframes=n_frames)
+            out = sim.budget_control(share, mode, weights=weights, width=frame_width, height=frame_height, nframes=n_frames)
+        out['probs'].astype('<f4').tofile(tmp)
+        os.replace(tmp, save_file)
+    finally:
+        if os.path.exists(tmp):
+            os.remove(tmp)
+    cost, full = sum(int(x) for x in out['cost']), sum(int(x) for x in out['full'])
+    return n_frames, (float(cost) / full if full else 0.0), int(out['over'].sum())
 
 
 def get_prob(ctx, yuv_name, image_size, save_file, qp_seq, n_frames_start, n_frames_end, frame_width, frame_height):
@@ -156,6 +226,9 @@ def main(argv=None):
     try:
         fmt = source_format_from_env()
         frame_bytes = _e.source_frame_bytes(width, height, *fmt)[1]         # :136 width * height * 3 // 2 unless the environment says otherwise
+        budget = search_budget_from_env()
+        if budget is not None:
+            check_companion_thr_file()
     except (ValueError, _e.EthCnnError) as err:
         sys.stderr.write('video_to_cu_depth: %s\n' % err)
         return 1
@@ -177,8 +250,13 @@ def main(argv=None):
         guard_fast_plan(ctx)
         stamps.append(('thresholds + weights + plan guard', time.perf_counter()))
         t1 = time.time()                       # the reference times get_prob only (:142-145)
-        n_frames = get_prob(ctx, yuv_file, IMAGE_SIZE, SAVE_FILE, qp_seq, 0,
-                            get_file_size(yuv_file) // frame_bytes, width, height)
+        if budget is not None:
+            n_frames, share, over = write_budgeted(ctx, yuv_file, qp_seq, width, height, budget, SAVE_FILE)
+            sys.stderr.write('video_to_cu_depth: search budget %g (%s): %.6f of the full search over %d frames, %d over budget\n'
+                             % (budget[0], budget[1], share, n_frames, over))
+        else:
+            n_frames = get_prob(ctx, yuv_file, IMAGE_SIZE, SAVE_FILE, qp_seq, 0,
+                                get_file_size(yuv_file) // frame_bytes, width, height)
         stamps.append(('predict', time.perf_counter()))
         ctx.close()
         stamps.append(('destroy', time.perf_counter()))

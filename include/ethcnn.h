@@ -930,6 +930,69 @@ int ethcnn_decide_frames_device(ethcnn_sim* sim, const ethcnn_sim_thr* thr, int 
  * zeroes.  NULL or n < 0: ETHCNN_ERR_ARG; a byte that no ethcnn_decide* call writes: ETHCNN_ERR_FORMAT; both leave counts_out untouched. */
 int ethcnn_decide_counts_from_codes(const uint8_t* codes, int64_t n, ethcnn_sim_counts* counts_out);
 
+/* ---- search budget: a stated share of the full search held FRAME BY FRAME by an encoder that does not change (no reference
+ *      counterpart).  HM reads Thr_info.txt once (HM-16.5_Test_AI/source/Lib/TLibEncoder/TEncCu.cpp:245-255: the file handles are
+ *      static and later fscanfs hit the end of the file), so one file sets an average over a sequence and nothing per frame.  But HM's
+ *      rule (TEncCu.cpp:448-462) only compares p with up and down: a cu_depth.dat whose values are 1.0 where a node is to be SPLIT ONLY,
+ *      0.0 where CURRENT ONLY and 0.5 where BOTH, read under the fixed COMPANION file up = 0.75, down = 0.25, makes the unchanged encoder
+ *      carry out any per-frame, per-node decision.  These entries count, per frame of a simulator's set, the checks that every rung of
+ *      a LADDER of candidates leaves, pick one rung per frame under a budget, and bake the picked decisions into 21 floats per CTU.
+ *   Ladder: K candidates (ethcnn_sim_thr[K], 1 <= K <= ETHCNN_BUDGET_MAX_RUNGS, each in the simulator's ranges, else ETHCNN_ERR_ARG); rung
+ *      0 is meant to be the most thorough.  ethcnn_budget_default_ladder fills ETHCNN_BUDGET_DEFAULT_RUNGS = 513 rungs: rung j has
+ *      up_k = 1024 - j and down_k = j - 1 on all three levels, so rung 0 is the full search and rung 512 leaves only bin == 512 to BOTH.
+ *      The cost does not rise along that ladder (up falls and down rises with j); the choice below does not rely on it.
+ *   Cost.  The gates are always ETHCNN_SIM_GATES_NONE: the baked file is what the encoder reads.  checked[f][k][0..3] are the
+ *      simulator's checked[0..3] (ethcnn_sim_counts) over the CTUs of frame f of the window under rung k; rejected CTUs count nowhere.
+ *      Column K is the full search (up_k = 1024, down_k = -1).  Layout uint32 [nframes][K + 1][4]; a frame has fewer than 2^24 CTUs
+ *      (else ETHCNN_ERR_ARG), so 32 bits hold every counter.  cost = sum_d weight[d] * checked[d]; weight[d] < 2^32 (else ETHCNN_ERR_ARG),
+ *      default 64 16 4 1 as everywhere.  Integers only: the counters do not depend on the grid or on how a frame is cut over waves.
+ *   Choice (ethcnn_budget_choose: host only, pure, no context).  Per frame f in order, with full_f = cost[f][K], in units of cost x 10^6
+ *      and 128-bit products as in ethcnn_calib_choose:
+ *        allow_f = budget_ppm * full_f + carry_{f-1}                      (carry_{-1} = 0: it starts at the first frame of the call)
+ *        rung_f  = the smallest k in 0..K-1 with cost[f][k] * 10^6 <= allow_f
+ *        no such k: rung_f = the rung of least cost (the smallest k at ties), over[f] = 1 and carry_f = 0
+ *        ETHCNN_BUDGET_FRAME: carry_f = 0 always.   ETHCNN_BUDGET_CARRY: carry_f = allow_f - cost[f][rung_f] * 10^6.
+ *      Outputs per frame: rung (int32), over (uint8, 0 / 1), cost = cost[f][rung_f] and full = full_f (uint64); each may be NULL.
+ *      budget_ppm > 10^6, K outside 1..4096, an unknown mode, NULL checked (with nframes > 0) or weight, nframes < 0, a weight of 2^32
+ *      or more, or a cost that does not fit in 64 bits (no frame below 2^24 CTUs gives one): ETHCNN_ERR_ARG, outputs untouched.
+ *   Companion thresholds: ethcnn_budget_companion_thr gives up_k = 768, down_k = 256 on all levels; ethcnn_sim_write_thr_info writes them
+ *      in either token order ("0.75 0.25 0.75 0.25 0.75 0.25" for All-Intra).  The encoder must read THAT file beside a baked cu_depth.dat.
+ *   Baked values: one row of 21 float32 per CTU in the RASTER order of the 21 probabilities, by the codes of "partition decisions" under
+ *      the rung of the CTU's frame, gates none:
+ *        SPLIT ONLY (2) 1.0f     CURRENT ONLY (1) 0.0f     BOTH (3) 0.5f     frame-edge node (4, rule 3) 1.0f     not visited (0) 0.0f
+ *        every node of a REJECTED CTU 0.5f: it gets the full search.
+ *      Under the companion thresholds 1.0 is bin 1024 > 768, 0.0 is bin 0 <= 256 and 0.5 is bin 512 in between: ethcnn_decide* over the
+ *      baked rows, gates none, gives every non-rejected CTU the codes bytes 0..22 it has on the original set under its frame's rung.  The
+ *      three values are constants: no float arithmetic, every float has one writer, and the bytes do not depend on the grid or the pieces.
+ *   Windows are those of ethcnn_decide_frames_device: nframes whole frames from CTU `first` on, inside one run of width x height frames,
+ *      `first` on a frame boundary of it (else ETHCNN_ERR_ARG).  Every entry is synchronous on the context's stream; device pointers must
+ *      be 4-byte aligned (else ETHCNN_ERR_ARG); nframes == 0 is a no-op; a call that fails leaves its outputs untouched. */
+#define ETHCNN_BUDGET_DEFAULT_RUNGS 513
+#define ETHCNN_BUDGET_MAX_RUNGS 4096
+enum { ETHCNN_BUDGET_FRAME = 0, ETHCNN_BUDGET_CARRY = 1 };
+int ethcnn_budget_default_ladder(ethcnn_sim_thr* out /* [ETHCNN_BUDGET_DEFAULT_RUNGS] */); /* host only, no context */
+int ethcnn_budget_companion_thr(ethcnn_sim_thr* out);                                      /* host only, no context */
+int ethcnn_budget_choose(const uint32_t* checked, int64_t nframes, int64_t K, const uint64_t weight[4], uint32_t budget_ppm, int mode,
+                         int32_t* rung_out, uint8_t* over_out, uint64_t* cost_out, uint64_t* full_out);
+/* checked_out uint32 [nframes][K + 1][4] in host memory / in HBM */
+int ethcnn_budget_cost(ethcnn_sim* sim, const ethcnn_sim_thr* ladder, int64_t K, int64_t first, int width, int height, int64_t nframes,
+                       uint32_t* checked_out);
+int ethcnn_budget_cost_device(ethcnn_sim* sim, const ethcnn_sim_thr* ladder, int64_t K, int64_t first, int width, int height, int64_t nframes,
+                              uint32_t* d_checked_out);
+/* rung int32 [nframes] in HOST memory, each in 0..K-1 (else ETHCNN_ERR_ARG); probs float32 [nframes * nctu][21] in HBM / in host memory.
+ * The host form is staged in pieces of ethcnn_decide_set_piece CTUs (0 = the default, 2^20; a piece may start inside a frame) through one
+ * device buffer of piece * 84 bytes, checked against the free device memory first (ETHCNN_ERR_NOMEM); the bytes do not depend on it. */
+int ethcnn_budget_bake_device(ethcnn_sim* sim, const ethcnn_sim_thr* ladder, int64_t K, const int32_t* rung, int64_t first, int width, int height,
+                              int64_t nframes, float* d_probs_out);
+int ethcnn_budget_bake(ethcnn_sim* sim, const ethcnn_sim_thr* ladder, int64_t K, const int32_t* rung, int64_t first, int width, int height,
+                       int64_t nframes, float* probs_out);
+/* cost, then choose, then bake in one call, into host memory.  ladder NULL: the default ladder (K is not read); weight NULL: 64 16 4 1.
+ * probs_out [nframes * nctu][21] and the four per-frame outputs of ethcnn_budget_choose; any of them may be NULL (a NULL probs_out
+ * skips the bake). */
+int ethcnn_budget_control(ethcnn_sim* sim, const ethcnn_sim_thr* ladder, int64_t K, const uint64_t weight[4], uint32_t budget_ppm, int mode,
+                          int64_t first, int width, int height, int64_t nframes, float* probs_out, int32_t* rung_out, uint8_t* over_out,
+                          uint64_t* cost_out, uint64_t* full_out);
+
 /* ---- sample-set replay: an inter sample set (LDP_Valid.dat, LDP_Test.dat, plain or _shuffled: the 16516-byte records of "sample sets"
  *      above) put back together into the residual pictures and label planes it was cut from, and run through the deployed Low-Delay-P
  *      chain, ethcnn_ldp_sequence_device: forward in time, i_frame % 4 features, the state carried over the whole sequence.  The inverse
