@@ -237,6 +237,13 @@ SIGNATURES = {
     "ethcnn_budget_bake_device": (_i, [_vp, _vp, ctypes.c_int64, _vp, ctypes.c_int64, _i, _i, ctypes.c_int64, _vp]),
     "ethcnn_budget_bake": (_i, [_vp, _vp, ctypes.c_int64, _vp, ctypes.c_int64, _i, _i, ctypes.c_int64, _vp]),
     "ethcnn_budget_control": (_i, [_vp, _vp, ctypes.c_int64, _vp, ctypes.c_uint32, _i, ctypes.c_int64, _i, _i, ctypes.c_int64, _vp, _vp, _vp, _vp, _vp]),
+    "ethcnn_pacer_check": (_i, [_vp, ctypes.c_int64, _vp, ctypes.c_uint32, _i]),
+    "ethcnn_pacer_create": (_i, [_vp, _vp, ctypes.c_int64, _vp, ctypes.c_uint32, _i, ctypes.POINTER(_vp)]),
+    "ethcnn_pacer_destroy": (None, [_vp]),
+    "ethcnn_pacer_reset": (_i, [_vp]),
+    "ethcnn_pacer_frame_device": (_i, [_vp, _vp, _i, _i, _vp, _vp]),
+    "ethcnn_pacer_frame": (_i, [_vp, _vp, _i, _i, _vp, _vp]),
+    "ethcnn_pacer_last": (_i, [_vp, _vp]),
     "ethcnn_replay_plan": (_i, [_vp, _sz, _vp, _i, ctypes.POINTER(_i), _vp, ctypes.c_char_p, _sz]),
     "ethcnn_replay_uncut_device": (_i, [_vp, _vp, ctypes.c_int64, _vp, ctypes.c_int64, _i, _i, _i, _vp, _vp]),
     "ethcnn_replay_create": (_i, [_vp, ctypes.c_uint64, ctypes.POINTER(_vp)]),
@@ -1844,6 +1851,100 @@ class PartitionSim(object):
                                                  first, int(width), int(height), nf, ptr("probs"), ptr("rung"), ptr("over"), ptr("cost"), ptr("full")))
         out["over"] = out["over"].astype(bool)
         return out
+
+
+# search budget, online (include/ethcnn.h "search budget, online")
+# ethcnn_pacer_result as a numpy record: 72 bytes, no padding
+PACER_RESULT = np.dtype([("frame", "<i8"), ("rung", "<i4"), ("over", "<i4"), ("cost", "<u8"), ("full", "<u8"), ("carry_lo", "<u8"), ("carry_hi", "<u8"),
+                         ("up_k", "<i4", (3,)), ("down_k", "<i4", (3,))])
+
+
+def _budget_ppm(budget):
+    if not 0.0 <= float(budget) <= 1.0:
+        raise ValueError("the budget is a share of the full search, 0..1: got %r" % (budget,))
+    return int(round(float(budget) * 1e6))
+
+
+def pacer_check(budget_ppm, mode=BUDGET_FRAME, ladder=None, weights=None, lib=None):
+    """ethcnn_pacer_check (host only): the argument rules of a pacer -- ladder (SIM_THR records, None: the default), weights (None: 64 16
+    4 1), budget in parts per million, mode as a number; EthCnnError where the library says ETHCNN_ERR_ARG"""
+    lib = lib or load_library()
+    lad = None if ladder is None else _sim_cands(ladder)
+    w = None if weights is None else (ctypes.c_uint64 * 4)(*[int(x) for x in weights])
+    rc = lib.ethcnn_pacer_check(None if lad is None else lad.ctypes.data, 0 if lad is None else lad.size, w, int(budget_ppm), int(mode))
+    if rc:
+        raise EthCnnError(rc, lib.ethcnn_last_error(None).decode())
+
+
+class Pacer(object):
+    """The search budget held one frame at a time (include/ethcnn.h "search budget, online"): owns the ladder, the weights, the budget
+    (a share 0..1), the mode ("frame" or "carry"), the carry and the frame count; a frame is two launches on the context's stream."""
+
+    def __init__(self, ctx, budget, mode="frame", ladder=None, weights=None):
+        self.ctx, self.lib = ctx, ctx.lib
+        lad = None if ladder is None else _sim_cands(ladder)
+        w = None if weights is None else (ctypes.c_uint64 * 4)(*[int(x) for x in weights])
+        h = ctypes.c_void_p()
+        ctx._chk(self.lib.ethcnn_pacer_create(ctx.h, None if lad is None else lad.ctypes.data, 0 if lad is None else lad.size, w, _budget_ppm(budget),
+                                              _budget_mode(mode), ctypes.byref(h)))
+        self.h = h
+        if not hasattr(ctx, "_trainers"):
+            ctx._trainers = weakref.WeakSet()
+        ctx._trainers.add(self)  # closed with the context, before it
+
+    def _chk(self, rc):
+        self.ctx._chk(rc)
+
+    def _handle(self):
+        if not getattr(self, "h", None):
+            raise ValueError("the pacer is closed")
+        return self.h
+
+    def close(self):
+        if getattr(self, "h", None):
+            self.lib.ethcnn_pacer_destroy(self.h)
+            self.h = None
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+    def __enter__(self):
+        return self
+
+    def __exit__(self, *a):
+        self.close()
+
+    def reset(self):
+        """carry = 0, frame = 0 (in stream order behind the frames already queued)"""
+        self._chk(self.lib.ethcnn_pacer_reset(self._handle()))
+
+    def frame(self, probs, width, height, out=None):
+        """one frame: probs float32 [nctu, 21] (a host array; a view of ctx.host_buffer() is used in place) -> (baked float32 [nctu, 21],
+        result record).  out: the array the baked rows go to (None: a new one; `probs` itself: in place)"""
+        n = ctus_per_frame(int(width), int(height))
+        probs = np.ascontiguousarray(probs, dtype=np.float32)
+        if probs.size != n * NOUT:
+            raise ValueError("a %d x %d frame has %d x 21 probabilities, got %d values" % (width, height, n, probs.size))
+        baked = np.empty((n, NOUT), np.float32) if out is None else out
+        assert baked.dtype == np.float32 and baked.size == n * NOUT and baked.flags["C_CONTIGUOUS"]
+        res = np.zeros(1, PACER_RESULT)
+        self._chk(self.lib.ethcnn_pacer_frame(self._handle(), probs.ctypes.data, int(width), int(height), baked.ctypes.data, res.ctypes.data))
+        return baked.reshape(n, NOUT), res[0]
+
+    def frame_device(self, d_probs, width, height, d_baked, d_result=None):
+        """the same on buffers in HBM (DeviceBuffer or raw device addresses), asynchronous on the context's stream; d_baked may be
+        d_probs; d_result (72 bytes) may be None"""
+        ptr = lambda b: None if b is None else getattr(b, "ptr", b)
+        self._chk(self.lib.ethcnn_pacer_frame_device(self._handle(), ptr(d_probs), int(width), int(height), ptr(d_baked), ptr(d_result)))
+
+    def last(self):
+        """the result record of the most recent frame (synchronous)"""
+        res = np.zeros(1, PACER_RESULT)
+        self._chk(self.lib.ethcnn_pacer_last(self._handle(), res.ctypes.data))
+        return res[0]
 
 
 # ------------------------------------------------------------------------------------------------------ sample-set replay ---

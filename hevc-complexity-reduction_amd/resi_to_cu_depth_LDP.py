@@ -25,7 +25,13 @@ step + heads + gates on the GPU).  Differences from the reference, none in the n
     it is from -- as the reference does (HM may skip frames: intra pictures are not predicted);
   * resi.yuv is read straight into pinned host memory (DMA-able without a staging copy);
   * missing trained CNN blob (model_LDP_2000000_qp22~37.dat.data is not in the reference repo):
-    ETHCNN_SYNTHETIC_SEED=<n> opts into seeded synthetic CNN weights, otherwise it is an error.
+    ETHCNN_SYNTHETIC_SEED=<n> opts into seeded synthetic CNN weights, otherwise it is an error;
+  * ETHCNN_SEARCH_BUDGET=<share, 0..1> [ETHCNN_SEARCH_BUDGET_MODE=frame|carry] [ETHCNN_SEARCH_BUDGET_WEIGHTS="64 16 4 1"] holds every
+    frame's pruned search under that share of the full search's weighted checks (include/ethcnn.h "search budget, online"): the daemon
+    predicts with open gates, whatever Thr_info.txt says, and a pacer (ethcnn.Pacer) picks a rung of the default ladder per frame and
+    bakes the picked decisions into cu_depth.dat (values 0, 0.5, 1) inside the handshake.  The encoder reads Thr_info.txt itself, so the
+    daemon refuses at start-up (status 1, before a GPU is touched, no signal file) unless that file is the companion line in
+    Low-Delay-P token order, "0.25 0.75 0.25 0.75 0.25 0.75".  A frame with i_frame <= 1 or another geometry starts a new allowance.
 """
 from __future__ import print_function
 
@@ -37,6 +43,7 @@ import numpy as np
 
 from . import ethcnn as _e
 from . import net_CNN as nt
+from . import search_budget as _sb
 
 IMAGE_SIZE = nt.IMAGE_SIZE
 NUM_CHANNELS = nt.NUM_CHANNELS
@@ -206,9 +213,16 @@ def serve(workdir='.', max_frames=None, idle_timeout=None, poll_s=2e-4, device=0
     state.dat as it is, or restart the encode -- unless accept_stale is set, in which case the file is used as it is after
     a warning.  (HM then keeps spinning on pred_end.sig, exactly as it does when the reference's daemon dies.)"""
     p = lambda name: os.path.join(workdir, name)
+    budget = _sb.from_env()   # (ValueError for a bad value: before a GPU is touched)
+    if budget is not None:
+        _sb.check_companion_thr_file(p(THR_FILE), _sb.COMPANION_LINE_LDP)
     ctx = _e.EthCnn(device=device)
+    pacer, paced_geom, paced = None, None, [0, 0, 0, 0]   # frames, over budget, sum of cost, sum of full
     try:
         ctx.load_thresholds(p(THR_FILE))
+        if budget is not None:
+            ctx.set_thresholds(0.0, 0.0)    # open gates, whatever Thr_info.txt says: the baked file is what the encoder reads
+            pacer = _e.Pacer(ctx, budget[0], budget[1], weights=budget[2])
         restore_cnn(ctx, workdir)
         if verbose:
             print('Python: predictor initialized on %s.' % ctx.device_name)
@@ -257,6 +271,15 @@ def serve(workdir='.', max_frames=None, idle_timeout=None, poll_s=2e-4, device=0
                 state_in = np.asarray(state_in, dtype=np.float32).reshape(num_vectors, 2, VECTOR_LENGTH)
             depth_out = ctx.ldp_step(luma, frame_width, frame_height, qp_seq, i_frame, state_in,
                                      probs_out=pinned_probs[:num_vectors * 21].reshape(num_vectors, 21))
+            if pacer is not None:   # (only once the step has succeeded: a frame is never paced twice)
+                if i_frame <= 1 or paced_geom != (frame_width, frame_height):
+                    pacer.reset()   # a new sequence starts with a new allowance, as it starts with a zero LSTM state
+                    paced_geom = (frame_width, frame_height)
+                depth_out, res = pacer.frame(depth_out, frame_width, frame_height, out=depth_out)   # page-locked, in place
+                paced = [paced[0] + 1, paced[1] + int(res['over']), paced[2] + int(res['cost']), paced[3] + int(res['full'])]
+                if verbose:
+                    print('frame %d: rung %d, %.6f of the full search%s' % (i_frame, int(res['rung']), int(res['cost']) / float(int(res['full']) or 1),
+                                                                           ', over budget' if res['over'] else ''))
             save_cu_depth_and_state(depth_out, lambda: ctx.ldp_get_state(frame_width, frame_height), p(SAVE_FILE),
                                     p(STATE_FILE), p(END_FILE), num_vectors, tag=(i_frame, frame_width, frame_height))
             last_key, state_sig = (frame_width, frame_height, i_frame), _file_sig(p(STATE_FILE))
@@ -266,6 +289,9 @@ def serve(workdir='.', max_frames=None, idle_timeout=None, poll_s=2e-4, device=0
                 print('%d frames predicted.' % n_frame_total)
         return n_frame_total
     finally:
+        if pacer is not None:
+            sys.stderr.write('resi_to_cu_depth_LDP: search budget %g (%s): %.6f of the full search over %d frames, %d over budget\n'
+                             % (budget[0], budget[1], paced[2] / float(paced[3] or 1), paced[0], paced[1]))
         ctx.close()
 
 
@@ -286,6 +312,12 @@ def main(argv):
         else:
             sys.stderr.write('usage: resi_to_cu_depth_LDP.py [--max-frames N] [--idle-timeout S] [--accept-stale]\n')
             return 2
+    try:  # a bad ETHCNN_SEARCH_BUDGET* value, or a Thr_info.txt that is not the companion line: refused before a GPU is touched
+        if _sb.from_env() is not None:
+            _sb.check_companion_thr_file(THR_FILE, _sb.COMPANION_LINE_LDP)
+    except ValueError as err:
+        sys.stderr.write('resi_to_cu_depth_LDP: %s\n' % err)
+        return 1
     try:
         serve('.', max_frames=max_frames, idle_timeout=idle, accept_stale=accept_stale)
     except StaleStateError:

@@ -1,0 +1,45 @@
+"""The environment of the search budget (include/ethcnn.h "search budget"), shared by the launchers that take one: the All-Intra
+launcher (video_to_cu_depth.py) and the Low-Delay-P daemon (resi_to_cu_depth_LDP.py).  ETHCNN_SEARCH_BUDGET=<share, 0..1>,
+ETHCNN_SEARCH_BUDGET_MODE=frame|carry (default frame), ETHCNN_SEARCH_BUDGET_WEIGHTS="64 16 4 1".  Nothing here touches a GPU."""
+import os
+
+COMPANION_LINE_AI = '0.75 0.25 0.75 0.25 0.75 0.25'    # ethcnn_budget_companion_thr in All-Intra token order: up down ...
+COMPANION_LINE_LDP = '0.25 0.75 0.25 0.75 0.25 0.75'   # ... and in Low-Delay-P token order: down up ...
+
+
+def from_env():
+    """None when ETHCNN_SEARCH_BUDGET is unset or empty, else (share, mode, weights or None); ValueError names a bad value"""
+    text = os.environ.get('ETHCNN_SEARCH_BUDGET')
+    if text is None or text == '':
+        return None
+    try:
+        share = float(text)
+    except ValueError:
+        share = -1.0
+    if not 0.0 <= share <= 1.0:   # (a NaN fails both comparisons)
+        raise ValueError("ETHCNN_SEARCH_BUDGET='%s' is not a share of the full search, 0..1" % text)
+    mode = os.environ.get('ETHCNN_SEARCH_BUDGET_MODE') or 'frame'
+    if mode not in ('frame', 'carry'):
+        raise ValueError("ETHCNN_SEARCH_BUDGET_MODE='%s' (allowed: frame, carry)" % mode)
+    weights = None
+    text = os.environ.get('ETHCNN_SEARCH_BUDGET_WEIGHTS')
+    if text:
+        try:
+            weights = [int(t) for t in text.split()]
+        except ValueError:
+            weights = []
+        if len(weights) != 4 or min(weights) < 0 or max(weights) >= 1 << 32:
+            raise ValueError("ETHCNN_SEARCH_BUDGET_WEIGHTS='%s' is not four integers W64 W32 W16 W8 in 0..2^32-1" % text)
+    return share, mode, weights
+
+
+def check_companion_thr_file(path, line):
+    """A baked cu_depth.dat means what it says only under the companion thresholds, and HM reads them from this file: ValueError unless
+    it holds exactly the six values of `line` (the companion line in the token order of the encoder that reads it)"""
+    try:
+        tokens = [float(t) for t in open(path).read().split()]
+    except (OSError, ValueError):
+        tokens = None
+    if tokens != [float(t) for t in line.split()]:
+        raise ValueError("ETHCNN_SEARCH_BUDGET is set, so the encoder must read the companion thresholds: put the line\n    %s\ninto %s "
+                         "(found: %s)" % (line, path, 'no readable file' if tokens is None else ' '.join('%g' % t for t in tokens)))

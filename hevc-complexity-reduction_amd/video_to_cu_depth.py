@@ -27,6 +27,7 @@ import time
 
 from . import ethcnn as _e
 from . import net_CNN as nt
+from . import search_budget as _sb
 
 NUM_CHANNELS = nt.NUM_CHANNELS
 NUM_EXT_FEATURES = nt.NUM_EXT_FEATURES
@@ -63,47 +64,21 @@ def source_format_from_env():
     return tuple(fmt)
 
 
-COMPANION_LINE = '0.75 0.25 0.75 0.25 0.75 0.25'   # ethcnn_budget_companion_thr in All-Intra token order
+COMPANION_LINE = _sb.COMPANION_LINE_AI   # ethcnn_budget_companion_thr in All-Intra token order
 
 
 def search_budget_from_env():
     """None when ETHCNN_SEARCH_BUDGET is unset or empty, else (share, mode, weights or None); ValueError names a bad value"""
-    text = os.environ.get('ETHCNN_SEARCH_BUDGET')
-    if text is None or text == '':
-        return None
-    try:
-        share = float(text)
-    except ValueError:
-        share = -1.0
-    if not 0.0 <= share <= 1.0:   # (a NaN fails both comparisons)
-        raise ValueError("ETHCNN_SEARCH_BUDGET='%s' is not a share of the full search, 0..1" % text)
-    mode = os.environ.get('ETHCNN_SEARCH_BUDGET_MODE') or 'frame'
-    if mode not in ('frame', 'carry'):
-        raise ValueError("ETHCNN_SEARCH_BUDGET_MODE='%s' (allowed: frame, carry)" % mode)
-    weights = None
-    text = os.environ.get('ETHCNN_SEARCH_BUDGET_WEIGHTS')
-    if text:
-        try:
-            weights = [int(t) for t in text.split()]
-        except ValueError:
-            weights = []
-        if len(weights) != 4 or min(weights) < 0 or max(weights) >= 1 << 32:
-            raise ValueError("ETHCNN_SEARCH_BUDGET_WEIGHTS='%s' is not four integers W64 W32 W16 W8 in 0..2^32-1" % text)
-    if os.environ.get('ETHCNN_DEVICES'):
+    budget = _sb.from_env()
+    if budget is not None and os.environ.get('ETHCNN_DEVICES'):
         raise ValueError('ETHCNN_SEARCH_BUDGET runs on one GPU: unset ETHCNN_DEVICES (ETHCNN_DEVICE picks the GPU)')
-    return share, mode, weights
+    return budget
 
 
 def check_companion_thr_file(path=THR_FILE):
     """A baked cu_depth.dat means what it says only under the companion thresholds, and HM reads them from this file after the
     launcher has run: ValueError unless it holds exactly that line's six values"""
-    try:
-        tokens = [float(t) for t in open(path).read().split()]
-    except (OSError, ValueError):
-        tokens = None
-    if tokens != [float(t) for t in COMPANION_LINE.split()]:
-        raise ValueError("ETHCNN_SEARCH_BUDGET is set, so the encoder must read the companion thresholds: put the line\n    %s\ninto %s "
-                         "(found: %s)" % (COMPANION_LINE, path, 'no readable file' if tokens is None else ' '.join('%g' % t for t in tokens)))
+    _sb.check_companion_thr_file(path, COMPANION_LINE)
 
 
 def write_budgeted(ctx, yuv_name, qp_seq, frame_width, frame_height, budget, save_file):

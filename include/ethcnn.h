@@ -993,6 +993,64 @@ int ethcnn_budget_control(ethcnn_sim* sim, const ethcnn_sim_thr* ladder, int64_t
                           int64_t first, int width, int height, int64_t nframes, float* probs_out, int32_t* rung_out, uint8_t* over_out,
                           uint64_t* cost_out, uint64_t* full_out);
 
+/* ---- search budget, online: the budget above held ONE FRAME AT A TIME, for a loop that has no sequence to pre-process (the Low-Delay-P
+ *      daemons: the encoder produces one residual frame and blocks on its prediction).  A PACER owns what carries over from frame to
+ *      frame -- the ladder, the weights, the budget, the mode, the 128-bit carry and the frame count -- and turns one frame's
+ *      probabilities into its baked rows in two launches on the context's stream: one kernel packs the frame's records, counts the checks
+ *      of every rung and makes the choice ON THE DEVICE, the bake kernel of "search budget" writes the rows.  No reference counterpart.
+ *   Argument rules: ladder, K, weights, budget_ppm, mode and the W / H rule are exactly those of "search budget" and "partition-search
+ *      simulation": K in 1..ETHCNN_BUDGET_MAX_RUNGS, each rung in the simulator's ranges, weight[d] < 2^32, budget_ppm <= 10^6, mode
+ *      ETHCNN_BUDGET_FRAME or ETHCNN_BUDGET_CARRY; W and H multiples of 8 (up to 65536), a frame of fewer than 2^24 CTUs.  Otherwise
+ *      ETHCNN_ERR_ARG with nothing changed.  ladder NULL: the default ladder (K is not read); weight NULL: 64 16 4 1.
+ *      ethcnn_pacer_check applies the rules of ladder, K, weights, budget and mode alone (host only, pure, no context; the message is
+ *      read with ethcnn_last_error(NULL)).
+ *   A cost that cannot fit: a frame whose weighted cost could not fit in 64 bits -- nctu * (weight[0] + 4 weight[1] + 16 weight[2] +
+ *      64 weight[3]) >= 2^64, which no frame below 2^24 CTUs reaches -- is refused with ETHCNN_ERR_ARG as in ethcnn_budget_choose, BEFORE
+ *      anything is launched: carry and frame count stay untouched.
+ *   Input per frame: probs float32 [nctu][21] in raster order as the predictors write it, read as given: gates none.  The CTU rejection
+ *      rule (a NaN, a negative or a > 1 value) and bin = ceil(p * 1024) in fp32 are those of the simulator.
+ *   What the pacer keeps, all in HBM: the ladder with the full search appended as rung K (int32 [K + 1][6]), the table checked uint32
+ *      [K + 1][4], a record scratch of 64 bytes per CTU of the largest frame seen (grown on demand: ETHCNN_ERR_NOMEM with the byte count
+ *      in the message, nothing changed; growing waits for the frames in flight), the 128-bit carry and the frame counter.  One result
+ *      slot lies in page-locked memory.  The host form holds 84 bytes per CTU of staging when a pointer is not page-locked.
+ *   The equality that defines it: F frames of one geometry paced one by one, from create or reset on, give per frame the rung, over,
+ *      cost and full, and every baked byte, that ethcnn_budget_control returns for the same ladder, weights, budget and mode with
+ *      first = 0 on a simulator that got the same F frames through ethcnn_sim_add_frames (labels NULL); carry is carry_f of the choice
+ *      rule, in units of cost x 10^6.
+ *   The geometry may change between frames: the carry is in cost units and continues; the results then equal ethcnn_budget_choose over
+ *      the concatenated per-frame checked tables.
+ *   ethcnn_pacer_result, 72 bytes, little-endian, no padding: frame int64 at 0 (0-based count of frames paced since create / reset), rung
+ *      int32 at 8, over int32 at 12, cost uint64 at 16, full uint64 at 24, carry_lo uint64 at 32, carry_hi uint64 at 40, up_k int32[3] at
+ *      48, down_k int32[3] at 60 (the picked rung's thresholds).
+ *   ethcnn_pacer_frame_device is asynchronous on the context's stream and synchronises nothing (but for a scratch that has to grow):
+ *      frames queued back to back without a host wait give the same results.  d_baked == d_probs (in place) is allowed; d_result may be
+ *      NULL; pointers must be 4-byte aligned (else ETHCNN_ERR_ARG).
+ *   ethcnn_pacer_frame is synchronous.  A pointer that lies in an ethcnn_host_alloc buffer is read or written in place by the kernels,
+ *      anything else is staged; the bytes do not depend on the path.  baked == probs is allowed; result may be NULL.  With a page-locked
+ *      output the wait is a bounded spin on the context's completion word, which one lane stores behind the bake, with
+ *      hipStreamSynchronize as the fallback: the pattern of ethcnn_synchronize.
+ *   ethcnn_pacer_last is synchronous: the result of the most recent frame queued by either form (ETHCNN_ERR_ARG when none has been since
+ *      create / reset).  ethcnn_pacer_reset sets carry = 0 and frame = 0, in stream order behind the frames already queued.
+ *   A call that fails leaves outputs, carry and frame count untouched.  Integers and three float constants only: nothing depends on the
+ *      grid or on the order in which blocks finish.  A pacer is destroyed before its context. */
+typedef struct ethcnn_pacer ethcnn_pacer;
+typedef struct ethcnn_pacer_result {
+    int64_t frame;
+    int32_t rung;
+    int32_t over;
+    uint64_t cost, full;
+    uint64_t carry_lo, carry_hi;
+    int32_t up_k[3], down_k[3];
+} ethcnn_pacer_result;
+int ethcnn_pacer_check(const ethcnn_sim_thr* ladder, int64_t K, const uint64_t weight[4], uint32_t budget_ppm, int mode);
+int ethcnn_pacer_create(ethcnn_ctx* ctx, const ethcnn_sim_thr* ladder, int64_t K, const uint64_t weight[4], uint32_t budget_ppm, int mode,
+                        ethcnn_pacer** out);
+void ethcnn_pacer_destroy(ethcnn_pacer* pacer);
+int ethcnn_pacer_reset(ethcnn_pacer* pacer);
+int ethcnn_pacer_frame_device(ethcnn_pacer* pacer, const float* d_probs, int width, int height, float* d_baked, ethcnn_pacer_result* d_result);
+int ethcnn_pacer_frame(ethcnn_pacer* pacer, const float* probs, int width, int height, float* baked, ethcnn_pacer_result* result);
+int ethcnn_pacer_last(ethcnn_pacer* pacer, ethcnn_pacer_result* out);
+
 /* ---- sample-set replay: an inter sample set (LDP_Valid.dat, LDP_Test.dat, plain or _shuffled: the 16516-byte records of "sample sets"
  *      above) put back together into the residual pictures and label planes it was cut from, and run through the deployed Low-Delay-P
  *      chain, ethcnn_ldp_sequence_device: forward in time, i_frame % 4 features, the state carried over the whole sequence.  The inverse

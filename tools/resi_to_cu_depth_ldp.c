@@ -32,7 +32,13 @@
  *   resi_to_cu_depth_ldp [--max-frames N] [--idle-timeout SECONDS] [--quiet] [--accept-stale] [--trace] [--trace-slow US] [--spin] [--no-stream]   (cwd = HM-LDP's bin/)
  *
  * Environment as the Python daemon: ETHCNN_SYNTHETIC_SEED / ETHCNN_HEAD_GAIN (seeded weights when a trained blob is absent:
- * model_LDP_2000000_qp22~37.dat.data is not in the reference repository), ETHCNN_DEVICE.
+ * model_LDP_2000000_qp22~37.dat.data is not in the reference repository), ETHCNN_DEVICE, and the search budget:
+ * ETHCNN_SEARCH_BUDGET=<share, 0..1> [ETHCNN_SEARCH_BUDGET_MODE=frame|carry] [ETHCNN_SEARCH_BUDGET_WEIGHTS="64 16 4 1"] (names, value
+ * rules and error texts of the All-Intra launcher).  With it the daemon predicts with open gates, whatever Thr_info.txt says, and a pacer
+ * (include/ethcnn.h "search budget, online") bakes each frame's picked decisions into the page-locked buffer cu_depth.dat is written from,
+ * in place, once the frame's step has succeeded.  It refuses at start-up (status 1, before a GPU is touched, no signal file) unless
+ * Thr_info.txt is the companion line in Low-Delay-P token order, "0.25 0.75 0.25 0.75 0.25 0.75".  A frame with i_frame <= 1 or another
+ * geometry starts a new allowance, as it starts from a zero LSTM state.  Unset: the daemon runs the code it always ran.
  */
 #define _GNU_SOURCE
 #include <errno.h>
@@ -322,6 +328,94 @@ static int write_state(const void* data, size_t bytes) {
     return 0;
 }
 
+/* ETHCNN_SEARCH_BUDGET and its companions -> 0 (*on says whether a budget is set), or -1 with the message printed: the value rules and
+ * texts of the Python launchers (hevc-complexity-reduction_amd/search_budget.py) */
+#define COMPANION_LINE_LDP "0.25 0.75 0.25 0.75 0.25 0.75"
+static int is_space(char ch) { return ch == ' ' || ch == '\t' || ch == '\n' || ch == '\r' || ch == '\f' || ch == '\v'; }
+static int budget_from_env(int* on, uint32_t* ppm, int* mode, uint64_t weight[4]) {
+    const char* text = getenv("ETHCNN_SEARCH_BUDGET");
+    *on = 0;
+    if (!text || !*text) return 0;
+    char* end = NULL;
+    double share = strtod(text, &end);
+    while (end && is_space(*end)) ++end;
+    if (end == text || *end) share = -1.0;
+    if (!(share >= 0.0 && share <= 1.0)) { /* (a NaN fails both comparisons) */
+        fprintf(stderr, "resi_to_cu_depth_ldp: ETHCNN_SEARCH_BUDGET='%s' is not a share of the full search, 0..1\n", text);
+        return -1;
+    }
+    const double v = share * 1e6; /* parts per million, rounded half to even as the Python launchers round */
+    uint32_t k = (uint32_t)v;
+    if (v - (double)k > 0.5 || (v - (double)k == 0.5 && (k & 1u))) ++k;
+    *ppm = k;
+    const char* m = getenv("ETHCNN_SEARCH_BUDGET_MODE");
+    if (!m || !*m) m = "frame";
+    if (strcmp(m, "frame") != 0 && strcmp(m, "carry") != 0) {
+        fprintf(stderr, "resi_to_cu_depth_ldp: ETHCNN_SEARCH_BUDGET_MODE='%s' (allowed: frame, carry)\n", m);
+        return -1;
+    }
+    *mode = strcmp(m, "carry") == 0 ? ETHCNN_BUDGET_CARRY : ETHCNN_BUDGET_FRAME;
+    weight[0] = 64; weight[1] = 16; weight[2] = 4; weight[3] = 1;
+    const char* w = getenv("ETHCNN_SEARCH_BUDGET_WEIGHTS");
+    if (w && *w) {
+        int n = 0, bad = 0;
+        const char* q = w;
+        for (;;) {
+            while (is_space(*q)) ++q;
+            if (!*q) break;
+            if (*q == '+') ++q;
+            if (*q < '0' || *q > '9') { bad = 1; break; }
+            errno = 0;
+            const unsigned long long x = strtoull(q, &end, 10);
+            if (errno || x >= (1ull << 32) || (*end && !is_space(*end)) || n >= 4) { bad = 1; break; }
+            weight[n++] = (uint64_t)x;
+            q = end;
+        }
+        if (bad || n != 4) {
+            fprintf(stderr, "resi_to_cu_depth_ldp: ETHCNN_SEARCH_BUDGET_WEIGHTS='%s' is not four integers W64 W32 W16 W8 in 0..2^32-1\n", w);
+            return -1;
+        }
+    }
+    *on = 1;
+    return 0;
+}
+/* the encoder reads Thr_info.txt itself: a baked cu_depth.dat means what it says only under the companion thresholds */
+static int check_companion_thr_file(void) {
+    static const double want[6] = {0.25, 0.75, 0.25, 0.75, 0.25, 0.75};
+    char buf[512], found[640];
+    int ok = 0;
+    FILE* f = fopen("Thr_info.txt", "r");
+    snprintf(found, sizeof found, "no readable file");
+    if (f) {
+        const size_t n = fread(buf, 1, sizeof buf - 1, f);
+        fclose(f);
+        buf[n] = 0;
+        double v[8];
+        int cnt = 0, bad = n == sizeof buf - 1;
+        char* q = buf;
+        while (!bad) {
+            while (is_space(*q)) ++q;
+            if (!*q) break;
+            char* end = NULL;
+            const double x = strtod(q, &end);
+            if (end == q || (*end && !is_space(*end)) || cnt >= 8) { bad = 1; break; }
+            v[cnt++] = x;
+            q = end;
+        }
+        if (!bad) {
+            size_t at = 0;
+            found[0] = 0;
+            for (int i = 0; i < cnt && at < sizeof found - 32; ++i) at += (size_t)snprintf(found + at, sizeof found - at, "%s%g", i ? " " : "", v[i]);
+            ok = cnt == 6;
+            for (int i = 0; i < 6 && ok; ++i) ok = v[i] == want[i];
+        }
+    }
+    if (!ok)
+        fprintf(stderr, "resi_to_cu_depth_ldp: ETHCNN_SEARCH_BUDGET is set, so the encoder must read the companion thresholds: put the line\n    %s\n"
+                        "into Thr_info.txt (found: %s)\n", COMPANION_LINE_LDP, found);
+    return ok ? 0 : -1;
+}
+
 /* --trace: per-stage times of up to TRACE_N frames; medians are printed (a mean is at the mercy of one 5 ms scheduling hiccup) */
 #define TRACE_N 8192
 static float g_tr[7][TRACE_N];
@@ -347,6 +441,16 @@ int main(int argc, char** argv) {
         else if (!strcmp(argv[i], "--no-stream")) no_stream_opt = 1; /* read resi.yuv first, then predict (A/B runs) */
         else { fprintf(stderr, "usage: resi_to_cu_depth_ldp [--max-frames N] [--idle-timeout S] [--quiet] [--accept-stale] [--trace] [--trace-slow US] [--spin] [--no-stream]\n"); return 2; }
     }
+    /* the search budget: read and checked before a GPU is touched */
+    int budget_on = 0, budget_mode = ETHCNN_BUDGET_FRAME;
+    uint32_t budget_ppm = 0;
+    uint64_t budget_weight[4] = {64, 16, 4, 1};
+    if (budget_from_env(&budget_on, &budget_ppm, &budget_mode, budget_weight) != 0) return 1;
+    if (budget_on && check_companion_thr_file() != 0) return 1;
+    ethcnn_pacer* pacer = NULL;
+    int paced_w = -1, paced_h = -1;
+    long paced_frames = 0, paced_over = 0;
+    double paced_cost = 0.0, paced_full = 0.0;
     ethcnn_ctx* ctx = NULL;
     ethcnn_options opt;
     memset(&opt, 0, sizeof opt);
@@ -360,6 +464,12 @@ int main(int argc, char** argv) {
     size_t luma_cap = 0, probs_cap = 0, state_cap = 0;
     if (ethcnn_load_thresholds(ctx, "Thr_info.txt") != ETHCNN_OK || load_cnn(ctx) != ETHCNN_OK) {
         fprintf(stderr, "resi_to_cu_depth_ldp: %s\n", ethcnn_last_error(ctx));
+        goto out;
+    }
+    /* open gates, whatever Thr_info.txt says: the baked file is what the encoder reads; one pacer with the default ladder */
+    if (budget_on && (ethcnn_set_thresholds(ctx, 0.0f, 0.0f) != ETHCNN_OK ||
+                      ethcnn_pacer_create(ctx, NULL, 0, budget_weight, budget_ppm, budget_mode, &pacer) != ETHCNN_OK)) {
+        fprintf(stderr, "resi_to_cu_depth_ldp: search budget: %s\n", ethcnn_last_error(ctx));
         goto out;
     }
     {
@@ -491,6 +601,17 @@ int main(int argc, char** argv) {
             fprintf(stderr, "resi_to_cu_depth_ldp: frame %d: %s\n", i_frame, ethcnn_last_error(ctx));
             goto out;
         }
+        if (pacer) { /* (only here, once the step has succeeded: a frame that was run again is not paced twice) */
+            ethcnn_pacer_result res;
+            int prc = ETHCNN_OK;
+            if (i_frame <= 1 || w != paced_w || h != paced_h) prc = ethcnn_pacer_reset(pacer); /* a new sequence: a new allowance */
+            paced_w = w; paced_h = h;
+            if (prc == ETHCNN_OK) prc = ethcnn_pacer_frame(pacer, probs, w, h, probs, &res); /* page-locked, in place */
+            if (prc != ETHCNN_OK) { fprintf(stderr, "resi_to_cu_depth_ldp: frame %d: search budget: %s\n", i_frame, ethcnn_last_error(ctx)); goto out; }
+            ++paced_frames; paced_over += res.over; paced_cost += (double)res.cost; paced_full += (double)res.full;
+            if (!quiet) printf("frame %d: rung %d, %.6f of the full search%s\n", i_frame, (int)res.rung, res.full ? (double)res.cost / (double)res.full : 0.0,
+                               res.over ? ", over budget" : "");
+        }
         const double ts4 = now_s();
         if (write_cu_depth(probs, nctu * 21 * sizeof(float)) != 0) { fprintf(stderr, "resi_to_cu_depth_ldp: cannot write cu_depth.dat: %s\n", strerror(errno)); goto out; }
         /* the ending signal: a second name for an empty file this daemon keeps (one link() instead of open + close; HM only ever
@@ -538,6 +659,11 @@ int main(int argc, char** argv) {
                 !streamed_frames ? "sidecar + ethcnn_ldp_step" : "sidecar + ethcnn_ldp_step_end", m[4], m[5], m[6]);
     }
 out:
+    if (pacer) {
+        fprintf(stderr, "resi_to_cu_depth_ldp: search budget %g (%s): %.6f of the full search over %ld frames, %ld over budget\n", (double)budget_ppm * 1e-6,
+                budget_mode == ETHCNN_BUDGET_CARRY ? "carry" : "frame", paced_full > 0.0 ? paced_cost / paced_full : 0.0, paced_frames, paced_over);
+        ethcnn_pacer_destroy(pacer);
+    }
     unlink(".pred_end.sig.ethcnn");
     if (sig_pending) unlink("pred_start.sig"); /* an error exit in between: the request counts as taken, as with the reference's daemon */
     free(state);
