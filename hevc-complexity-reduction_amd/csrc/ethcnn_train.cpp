@@ -10,6 +10,7 @@
 #include "ethcnn_ctx.h"
 #include "ethcnn_samples.h"
 #include "ethcnn_train.h"
+#include "ethcnn_train_host.h"
 
 namespace ethcnn {
 namespace train {
@@ -47,32 +48,6 @@ int tensor_off(const char* name) {
     return -1;
 }
 }  // namespace
-
-struct ethcnn_trainer {
-    ethcnn_ctx* c = nullptr;
-    ethcnn_train_options opt{};
-    int B = 0, cap = 0;  // batch; rows of every per-sample buffer (>= the evaluation chunk)
-    NetOffsets o{};
-    std::string err;
-    // weights, accumulators, gradient (blob layout)
-    float *W = nullptr, *acc = nullptr, *grad = nullptr;
-    // per-sample buffers, cap rows
-    int32_t *idx = nullptr, *qp = nullptr, *idx_in = nullptr, *qp_in = nullptr;
-    float *lab = nullptr, *trunk = nullptr, *F = nullptr, *Z1 = nullptr, *A1 = nullptr, *M1 = nullptr, *H1 = nullptr, *A2 = nullptr,
-          *M2 = nullptr, *H2 = nullptr, *P = nullptr, *dZ3 = nullptr, *dZ2 = nullptr, *dZ1 = nullptr, *dF = nullptr, *part = nullptr,
-          *stats = nullptr;
-    GemmGroup *g_fwd = nullptr, *g_bwd = nullptr, *g_eval = nullptr;  // device tables
-    int t_fwd = 0, t_bwd = 0, t_eval = 0;
-    uint8_t* data[2] = {nullptr, nullptr};
-    int64_t nrec[2] = {0, 0};
-    int qps[52] = {0};
-    int nqps = 0;
-    int net = kNetAi, tune = 0;  // ethcnn_train_options.net / .tune
-    TuneMask mask{};             // the tensors tune 1..3 optimises (n == 0: all)
-    int slot_of_qp[2][52];       // LDP, per set: the slot of each of its four QPs, -1 elsewhere
-    int slot_qps[2][4] = {{0}};
-    std::vector<void*> allocs;
-};
 
 static int terr(ethcnn_trainer* t, int code, const char* fmt, ...) {
     char buf[512];
@@ -114,7 +89,7 @@ static void add_desc(GemmGroup& g, GemmDesc d) {
 }
 
 // FC1 forward of m rows: Z1[:, head] = F[:, :2688] x W1_head
-static GemmGroup fc1_group(const ethcnn_trainer* t, int m) {
+GemmGroup train_fc1_group(const ethcnn_trainer* t, int m) {
     GemmGroup g{};
     for (int h = 0; h < 3; ++h) {
         GemmDesc d{};
@@ -129,7 +104,7 @@ static GemmGroup fc1_group(const ethcnn_trainer* t, int m) {
 
 // dF = dZ1 x W1^T (K = 448 over the three heads' tensors) and the nine FC weight / bias gradients X_aug^T x dZ, written into grad
 // (tune 1..3: only the tuned head's three GEMMs; the conv gradients have no reader, so dF is not formed)
-static GemmGroup bwd_group(const ethcnn_trainer* t, int m) {
+GemmGroup train_bwd_group(const ethcnn_trainer* t, int m) {
     GemmGroup g{};
     if (!t->tune) {
         GemmDesc f{};
@@ -165,7 +140,7 @@ static GemmGroup bwd_group(const ethcnn_trainer* t, int m) {
     return g;
 }
 
-static float lr_at(const ethcnn_trainer* t, int64_t step) {  // tf.train.exponential_decay(..., staircase=True)
+float train_lr_at(const ethcnn_trainer* t, int64_t step) {  // tf.train.exponential_decay(..., staircase=True)
     const double p = std::floor((double)step / (double)t->opt.decay_steps);
     return (float)((double)t->opt.lr_init * std::pow((double)t->opt.decay_rate, p));
 }
@@ -206,7 +181,7 @@ static int enqueue_step(ethcnn_trainer* t, int64_t step, bool explicit_batch) {
     launch_heads_bwd(s, t->B, t->dZ3, t->A1, t->M1, t->A2, t->M2, t->dZ2, t->dZ1, t->W, t->o, dropout);
     launch_gemm(s, t->g_bwd, t->t_bwd);
     if (!t->tune) launch_trunk_bwd(s, t->B, t->trunk, t->F, t->dF, t->W, t->o, t->part);
-    launch_update(s, t->W, t->acc, t->grad, t->part, t->B, lr_at(t, step), t->opt.momentum, (long)kBlobFloats, t->mask);
+    launch_update(s, t->W, t->acc, t->grad, t->part, t->B, train_lr_at(t, step), t->opt.momentum, (long)kBlobFloats, t->mask);
     TCHK(t, hipGetLastError());
     return 0;
 }
@@ -320,7 +295,7 @@ extern "C" int ethcnn_train_create(ethcnn_ctx* c, const ethcnn_train_options* op
     for (void* p : {(void*)t->W, (void*)t->acc, (void*)t->grad}) e = e ? e : hipMemsetAsync(p, 0, kBlobFloats * 4, c->stream);
     e = e ? e : hipMemsetAsync(t->F, 0, R * kLdF * 4, c->stream);
     e = e ? e : hipMemsetAsync(t->stats, 0, 32, c->stream);
-    const GemmGroup gf = fc1_group(t, t->B), gb = bwd_group(t, t->B), ge = fc1_group(t, t->cap);
+    const GemmGroup gf = train_fc1_group(t, t->B), gb = train_bwd_group(t, t->B), ge = train_fc1_group(t, t->cap);
     t->t_fwd = gf.tiles; t->t_bwd = gb.tiles; t->t_eval = ge.tiles;
     e = e ? e : hipMemcpy(t->g_fwd, &gf, sizeof gf, hipMemcpyHostToDevice);
     e = e ? e : hipMemcpy(t->g_bwd, &gb, sizeof gb, hipMemcpyHostToDevice);

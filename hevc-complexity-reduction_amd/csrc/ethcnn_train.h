@@ -99,6 +99,43 @@ struct TuneMask {
     int n;
 };
 
+// ---- trainer group (include/ethcnn.h "training, several models at once"): K independent trainers of one net, batch and tuning mode
+// in every launch of a step.  A step is still the 8 (tune 1..3: 7) launches above; launch i covers all K members:
+//   trunk forward / heads forward / heads backward / trunk backward   grid (B, K): block (b, m) is sample slot b of member m
+//   loss                                                              K blocks: block m owns member m's batch-global counts
+//   GEMM                                                              K x T blocks, T = the tiles of one member's descriptor group:
+//                                                                     block i runs tile i % T of member i / T (every member has the
+//                                                                     same shapes); the members' GemmGroups lie side by side in
+//                                                                     an array of the group's own, launch_gemm is not involved
+//   update                                                            grid (1024, K): row m strides over member m's parameters
+// Every block runs the solo kernel's body on its member's buffers (ethcnn_train_kernels.hip), so member m computes what a solo trainer
+// with its options computes, bit for bit, whatever K and m are.  The members share the sample records and nothing else.
+// The member table lives in device memory and changes only when a member's QP list does; what changes from launch to launch goes by
+// value: the step number, the sample set (GroupStep) and the K learning rates of the step (GroupRates).
+struct Member {
+    float *W, *acc, *grad;                // blob layout: weights, momentum accumulators, gradient
+    const int32_t *idx_in, *qp_in;        // explicit batch / evaluation samples (ignored when GroupStep.drawn)
+    int32_t *idx, *qp;                    // the batch's sample indices and QPs, as drawn or read
+    float *lab, *trunk, *F, *Z1, *A1, *M1, *H1, *A2, *M2, *H2, *P, *dZ3, *dZ2, *dZ1, *dF, *part, *stats;  // workspaces
+    uint64_t seed;
+    int qps[52];
+    int nqps;
+    int qp_fixed;  // >= 0: every sample at this QP (evaluation)
+    int dropout;
+    float momentum;
+};
+struct GroupStep {
+    const uint8_t* data;  // the shared records
+    long nrec;
+    int slot_of_qp[52];  // LDP: of the shared set
+    uint64_t step;
+    int drawn;  // 1: indices and QPs drawn on the device
+};
+constexpr int kMaxMembers = 8;
+struct GroupRates {
+    float lr[kMaxMembers];
+};
+
 // launchers other trainers share (ethcnn_train_kernels.hip); the ETH-LSTM trainer uses both unchanged
 void launch_gemm(hipStream_t s, const GemmGroup* d_grp, int tiles);
 void launch_loss(hipStream_t s, const float* P, const float* lab, int n, float* stats, float* dZ);

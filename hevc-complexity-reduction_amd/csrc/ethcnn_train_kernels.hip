@@ -29,13 +29,17 @@ __device__ inline float keep_mask(uint64_t seed, uint64_t step, int slot, int un
 // ------------------------------------------------------------------------------------------------------------ trunk forward ---
 // NET = kNetAi: a 4992-byte record, luma * (1/255), the label row of QP q at 4160 + 16 q.  NET = kNetLdp: a 16516-byte record, the
 // slot of QP q (a.slot_of_qp) holds [qp | 16 labels | 4096 residual bytes] at 64 + 4113 slot, residual (x - 128) / 255 * 10.
-template <int NET>
-__global__ __launch_bounds__(256) void k_train_trunk_fwd(StepArgs a, const float* __restrict__ W, NetOffsets o) {
+// The step kernels' bodies are device functions: the solo kernels (one trainer) and the group kernels (K trainers in one launch,
+// "trainer group" below) are thin wrappers that only decide whose buffers a block works on, so a group member's arithmetic is the
+// solo trainer's, operation for operation.
+// A: StepArgs, or MemberArgs (the same fields, the QP list and slot table behind pointers).
+template <int NET, class A>
+__device__ __forceinline__ void trunk_fwd_body(const int b, const A& a, const float* __restrict__ W, const NetOffsets& o) {
     __shared__ float rec[kTrunkRec];  // images then conv1 outputs (trunk record layout)
     __shared__ float feat[kTF];
     __shared__ float mean[21];
     __shared__ int sidx, sqp;
-    const int b = blockIdx.x, t = threadIdx.x;
+    const int t = threadIdx.x;
     if (t == 0) {
         int64_t i;
         if (a.idx_in) i = a.idx_in[b];
@@ -133,12 +137,16 @@ __global__ __launch_bounds__(256) void k_train_trunk_fwd(StepArgs a, const float
     for (int p = t; p < kTF; p += 256) f[p] = feat[p];
     if (t == 0) f[kTF] = 1.f;  // ones column: the bias row of dW1 = F_aug^T dZ1
 }
+template <int NET>
+__global__ __launch_bounds__(256) void k_train_trunk_fwd(StepArgs a, const float* __restrict__ W, NetOffsets o) {
+    trunk_fwd_body<NET>(blockIdx.x, a, W, o);
+}
 
 // ------------------------------------------------------------------------------------------------------------ grouped GEMM ---
 // 64 x 64 output tile per block, 4 waves of 32 x 32 (v_mfma_f32_32x32x2_f32), K in steps of 32 staged through LDS
-__global__ __launch_bounds__(256) void k_train_gemm(const GemmGroup* __restrict__ grp) {
+__device__ __forceinline__ void gemm_body(const GemmGroup* __restrict__ grp, const int bid) {
     __shared__ float As[32][65], Bs[32][65];
-    const int bid = blockIdx.x, t = threadIdx.x, lane = t & 63, w = t >> 6, wm = w >> 1, wn = w & 1;
+    const int t = threadIdx.x, lane = t & 63, w = t >> 6, wm = w >> 1, wn = w & 1;
     int gi = 0;
     const int n = grp->n;
     while (gi + 1 < n && bid >= grp->d[gi + 1].tile_begin) ++gi;
@@ -183,6 +191,7 @@ __global__ __launch_bounds__(256) void k_train_gemm(const GemmGroup* __restrict_
         }
     }
 }
+__global__ __launch_bounds__(256) void k_train_gemm(const GemmGroup* __restrict__ grp) { gemm_body(grp, blockIdx.x); }
 
 // ------------------------------------------------------------------------------------------------------------ heads forward ---
 struct HeadBufs {
@@ -192,10 +201,10 @@ struct HeadBufs {
 };
 
 template <int NET>
-__global__ __launch_bounds__(256) void k_train_heads_fwd(HeadBufs h, const float* __restrict__ W, NetOffsets o, uint64_t seed,
-                                                          uint64_t step, int dropout) {
+__device__ __forceinline__ void heads_fwd_body(const int b, const HeadBufs& h, const float* __restrict__ W, const NetOffsets& o,
+                                               const uint64_t seed, const uint64_t step, const int dropout) {
     __shared__ float h1[kLdH1], h2[kLdH2];
-    const int b = blockIdx.x, t = threadIdx.x;
+    const int t = threadIdx.x;
     const float qpf = NET == kNetAi ? (float)h.qp[b] * (float)(1.0 / 51.0)   // tf.scalar_mul(1 / 51.0, qp)
                                     : ((float)h.qp[b] / 51.f) * 0.18f;       // LDP net_CTU64.py:103
     for (int u = t; u < kTV; u += 256) {
@@ -242,6 +251,11 @@ __global__ __launch_bounds__(256) void k_train_heads_fwd(HeadBufs h, const float
         h.P[(long)b * kTOut + t] = 1.f / (1.f + expf(-z));
     }
 }
+template <int NET>
+__global__ __launch_bounds__(256) void k_train_heads_fwd(HeadBufs h, const float* __restrict__ W, NetOffsets o, uint64_t seed,
+                                                          uint64_t step, int dropout) {
+    heads_fwd_body<NET>(blockIdx.x, h, W, o, seed, step, dropout);
+}
 
 // ------------------------------------------------------------------------------------------------------------ loss ---
 // labels of element e of a sample (net_CTU64.py:97-111): level 0 = 64x64 (1), 1 = 32x32 (4), 2 = 16x16 (16)
@@ -270,8 +284,8 @@ __device__ inline void label_of(const float* d, int e, float& y, float& valid, i
 }
 
 // stats: [0..2] loss_list (64, 32, 16), [3..5] accuracy_list, [6] total_loss.  dZ (may be NULL): dL/dlogit [n][21].
-__global__ __launch_bounds__(256) void k_train_loss(const float* __restrict__ P, const float* __restrict__ lab, int n, float* stats,
-                                                     float* dZ) {
+__device__ __forceinline__ void loss_body(const float* __restrict__ P, const float* __restrict__ lab, const int n, float* stats,
+                                          float* dZ) {
     constexpr int kQ = 18;  // per level: pos sum, neg sum, #pos, #neg, accuracy numerator, accuracy denominator
     __shared__ double red[kQ][256];
     __shared__ float fin[kQ];
@@ -331,6 +345,10 @@ __global__ __launch_bounds__(256) void k_train_loss(const float* __restrict__ P,
         dZ[i] = gp * p * (1.f - p);  // SigmoidGrad: dy * y * (1 - y)
     }
 }
+__global__ __launch_bounds__(256) void k_train_loss(const float* __restrict__ P, const float* __restrict__ lab, int n, float* stats,
+                                                     float* dZ) {
+    loss_body(P, lab, n, stats, dZ);
+}
 
 // ------------------------------------------------------------------------------------------------------------ heads backward ---
 struct HeadGrads {
@@ -338,9 +356,10 @@ struct HeadGrads {
     float *dZ2, *dZ1;
 };
 
-__global__ __launch_bounds__(256) void k_train_heads_bwd(HeadGrads g, const float* __restrict__ W, NetOffsets o, int dropout) {
+__device__ __forceinline__ void heads_bwd_body(const int b, const HeadGrads& g, const float* __restrict__ W, const NetOffsets& o,
+                                               const int dropout) {
     __shared__ float dz3[kTOut], dz2[kT2];
-    const int b = blockIdx.x, t = threadIdx.x;
+    const int t = threadIdx.x;
     if (t < kTOut) dz3[t] = g.dZ3[(long)b * kTOut + t];
     __syncthreads();
     for (int v = t; v < kT2; v += 256) {
@@ -363,14 +382,17 @@ __global__ __launch_bounds__(256) void k_train_heads_bwd(HeadGrads g, const floa
         g.dZ1[(long)b * kTV + u] = da * lrelu_grad(g.A1[(long)b * kTV + u]);
     }
 }
+__global__ __launch_bounds__(256) void k_train_heads_bwd(HeadGrads g, const float* __restrict__ W, NetOffsets o, int dropout) {
+    heads_bwd_body(blockIdx.x, g, W, o, dropout);
+}
 
 // ------------------------------------------------------------------------------------------------------------ trunk backward ---
 // per-sample partial gradients of the 18 conv tensors, written at their blob offsets: part[b][0 .. kConvFloats)
-__global__ __launch_bounds__(256) void k_train_trunk_bwd(const float* __restrict__ trunk, const float* __restrict__ F,
-                                                          const float* __restrict__ dF, const float* __restrict__ W, NetOffsets o,
-                                                          float* __restrict__ part) {
+__device__ __forceinline__ void trunk_bwd_body(const int b, const float* __restrict__ trunk, const float* __restrict__ F,
+                                               const float* __restrict__ dF, const float* __restrict__ W, const NetOffsets& o,
+                                               float* __restrict__ part) {
     __shared__ float d3[672], d2[2016], d1[5376];
-    const int b = blockIdx.x, t = threadIdx.x;
+    const int t = threadIdx.x;
     const float* tr = trunk + (long)b * kTrunkRec;
     const float* f = F + (long)b * kLdF;
     const float* df = dF + (long)b * kTF;
@@ -450,14 +472,19 @@ __global__ __launch_bounds__(256) void k_train_trunk_bwd(const float* __restrict
         }
     }
 }
+__global__ __launch_bounds__(256) void k_train_trunk_bwd(const float* __restrict__ trunk, const float* __restrict__ F,
+                                                          const float* __restrict__ dF, const float* __restrict__ W, NetOffsets o,
+                                                          float* __restrict__ part) {
+    trunk_bwd_body(blockIdx.x, trunk, F, dF, W, o, part);
+}
 
 // ------------------------------------------------------------------------------------------------------------ update ---
 // MomentumOptimizer (use_nesterov=False): accum = accum * momentum + grad; var -= lr * accum.  Conv gradients: sum of the
 // per-sample partials in sample order.  mask.n > 0 (PARTLY_TUNING_MODE 1..3): only the blob ranges [lo, hi) are optimised; every
 // other weight and its accumulator is left untouched (not even rewritten).
-__global__ __launch_bounds__(256) void k_train_update(float* __restrict__ W, float* __restrict__ acc, float* __restrict__ grad,
-                                                       const float* __restrict__ part, int nb, float lr, float momentum, long n,
-                                                       TuneMask mask) {
+__device__ __forceinline__ void update_body(float* __restrict__ W, float* __restrict__ acc, float* __restrict__ grad,
+                                            const float* __restrict__ part, const int nb, const float lr, const float momentum,
+                                            const long n, const TuneMask& mask) {
     for (long j = (long)blockIdx.x * 256 + threadIdx.x; j < n; j += (long)gridDim.x * 256) {
         if (mask.n) {
             bool on = false;
@@ -476,6 +503,62 @@ __global__ __launch_bounds__(256) void k_train_update(float* __restrict__ W, flo
         acc[j] = a;
         W[j] = W[j] - lr * a;
     }
+}
+__global__ __launch_bounds__(256) void k_train_update(float* __restrict__ W, float* __restrict__ acc, float* __restrict__ grad,
+                                                       const float* __restrict__ part, int nb, float lr, float momentum, long n,
+                                                       TuneMask mask) {
+    update_body(W, acc, grad, part, nb, lr, momentum, n, mask);
+}
+
+// ------------------------------------------------------------------------------------------------------------ trainer group ---
+// K trainers in every launch of a step (ethcnn_train.h "trainer group").  tab: the device-resident member table; grid (B, K) for
+// the per-sample kernels, K blocks for the loss, K x tiles for the GEMMs, (1024, K) for the update.  Each block runs the solo body
+// on its member's buffers; the members share only the sample records.
+struct MemberArgs {  // the fields trunk_fwd_body reads, as in StepArgs
+    const uint8_t* data;
+    long nrec;
+    const int32_t *idx_in, *qp_in;
+    const int* qps;
+    int nqps, qp_fixed;
+    const int* slot_of_qp;
+    uint64_t seed, step;
+    int32_t *idx_out, *qp_out;
+    float *labels, *trunk, *F;
+};
+
+template <int NET>
+__global__ __launch_bounds__(256) void k_group_trunk_fwd(const Member* __restrict__ tab, GroupStep g, NetOffsets o) {
+    const Member& m = tab[blockIdx.y];
+    const MemberArgs a{g.data,       g.nrec, g.drawn ? nullptr : m.idx_in, g.drawn ? nullptr : m.qp_in, m.qps, m.nqps, m.qp_fixed,
+                       g.slot_of_qp, m.seed, g.step, m.idx, m.qp, m.lab, m.trunk, m.F};
+    trunk_fwd_body<NET>(blockIdx.x, a, m.W, o);
+}
+// the members' descriptor groups side by side: every member has the same shapes, hence the same tile count
+__global__ __launch_bounds__(256) void k_group_gemm(const GemmGroup* __restrict__ grps, int tiles_per) {
+    gemm_body(grps + blockIdx.x / tiles_per, blockIdx.x % tiles_per);
+}
+template <int NET>
+__global__ __launch_bounds__(256) void k_group_heads_fwd(const Member* __restrict__ tab, NetOffsets o, uint64_t step) {
+    const Member& m = tab[blockIdx.y];
+    const HeadBufs h{m.Z1, m.A1, m.M1, m.H1, m.A2, m.M2, m.H2, m.P, m.qp};
+    heads_fwd_body<NET>(blockIdx.x, h, m.W, o, m.seed, step, m.dropout);
+}
+__global__ __launch_bounds__(256) void k_group_loss(const Member* __restrict__ tab, int n, int with_grad) {
+    const Member& m = tab[blockIdx.x];
+    loss_body(m.P, m.lab, n, m.stats, with_grad ? m.dZ3 : nullptr);
+}
+__global__ __launch_bounds__(256) void k_group_heads_bwd(const Member* __restrict__ tab, NetOffsets o) {
+    const Member& m = tab[blockIdx.y];
+    const HeadGrads g{m.dZ3, m.A1, m.M1, m.A2, m.M2, m.dZ2, m.dZ1};
+    heads_bwd_body(blockIdx.x, g, m.W, o, m.dropout);
+}
+__global__ __launch_bounds__(256) void k_group_trunk_bwd(const Member* __restrict__ tab, NetOffsets o) {
+    const Member& m = tab[blockIdx.y];
+    trunk_bwd_body(blockIdx.x, m.trunk, m.F, m.dF, m.W, o, m.part);
+}
+__global__ __launch_bounds__(256) void k_group_update(const Member* __restrict__ tab, int nb, GroupRates r, long n, TuneMask mask) {
+    const Member& m = tab[blockIdx.y];
+    update_body(m.W, m.acc, m.grad, m.part, nb, r.lr[blockIdx.y], m.momentum, n, mask);
 }
 
 // ------------------------------------------------------------------------------------------------------------ LDP set check ---
@@ -533,6 +616,31 @@ void launch_update(hipStream_t s, float* W, float* acc, float* grad, const float
 }
 void launch_check_slots(hipStream_t s, const uint8_t* data, long nrec, uint32_t want, long* first_bad, int nblocks) {
     hipLaunchKernelGGL(k_train_check_slots, dim3(nblocks), dim3(256), 0, s, data, nrec, want, first_bad);
+}
+
+// trainer group: the same eight launches, each over all k members
+void launch_group_trunk_fwd(hipStream_t s, int nb, int k, const Member* tab, const GroupStep& g, const NetOffsets& o, int net) {
+    if (net == kNetLdp) hipLaunchKernelGGL(k_group_trunk_fwd<kNetLdp>, dim3(nb, k), dim3(256), 0, s, tab, g, o);
+    else hipLaunchKernelGGL(k_group_trunk_fwd<kNetAi>, dim3(nb, k), dim3(256), 0, s, tab, g, o);
+}
+void launch_group_gemm(hipStream_t s, const GemmGroup* d_grps, int tiles_per, int k) {
+    hipLaunchKernelGGL(k_group_gemm, dim3(tiles_per * k), dim3(256), 0, s, d_grps, tiles_per);
+}
+void launch_group_heads_fwd(hipStream_t s, int nb, int k, const Member* tab, const NetOffsets& o, uint64_t step, int net) {
+    if (net == kNetLdp) hipLaunchKernelGGL(k_group_heads_fwd<kNetLdp>, dim3(nb, k), dim3(256), 0, s, tab, o, step);
+    else hipLaunchKernelGGL(k_group_heads_fwd<kNetAi>, dim3(nb, k), dim3(256), 0, s, tab, o, step);
+}
+void launch_group_loss(hipStream_t s, int k, const Member* tab, int n, int with_grad) {
+    hipLaunchKernelGGL(k_group_loss, dim3(k), dim3(256), 0, s, tab, n, with_grad);
+}
+void launch_group_heads_bwd(hipStream_t s, int nb, int k, const Member* tab, const NetOffsets& o) {
+    hipLaunchKernelGGL(k_group_heads_bwd, dim3(nb, k), dim3(256), 0, s, tab, o);
+}
+void launch_group_trunk_bwd(hipStream_t s, int nb, int k, const Member* tab, const NetOffsets& o) {
+    hipLaunchKernelGGL(k_group_trunk_bwd, dim3(nb, k), dim3(256), 0, s, tab, o);
+}
+void launch_group_update(hipStream_t s, int k, const Member* tab, int nb, const GroupRates& r, long n, const TuneMask& mask) {
+    hipLaunchKernelGGL(k_group_update, dim3(1024, k), dim3(256), 0, s, tab, nb, r, n, mask);
 }
 
 }  // namespace train

@@ -159,6 +159,21 @@ SIGNATURES = {
     "ethcnn_train_evaluate": (_i, [_vp, _i, ctypes.POINTER(ctypes.c_int32), ctypes.c_int64, _i, _fp, _fp, _fp]),
     "ethcnn_train_debug_fetch": (_i, [_vp, _i, _fp, _sz]),
     "ethcnn_train_last_error": (_cp, [_vp]),
+    "ethcnn_train_group_check": (_i, [ctypes.c_void_p, _i, ctypes.c_char_p, _sz]),
+    "ethcnn_train_group_create": (_i, [_vp, ctypes.c_void_p, _i, ctypes.POINTER(_vp)]),
+    "ethcnn_train_group_destroy": (None, [_vp]),
+    "ethcnn_train_group_init_weights": (_i, [_vp, ctypes.POINTER(ctypes.c_uint64)]),
+    "ethcnn_train_group_set_blob": (_i, [_vp, _i, _fp, _fp, _sz]),
+    "ethcnn_train_group_get_blob": (_i, [_vp, _i, _fp, _fp, _sz]),
+    "ethcnn_train_group_set_samples": (_i, [_vp, _i, _vp, _sz]),
+    "ethcnn_train_group_set_samples_from": (_i, [_vp, _i, _vp, _i]),
+    "ethcnn_train_group_set_qps": (_i, [_vp, _i, ctypes.POINTER(ctypes.c_int), _i]),
+    "ethcnn_train_group_run": (_i, [_vp, ctypes.c_int64, ctypes.c_int64]),
+    "ethcnn_train_group_last_stats": (_i, [_vp, _fp, _fp]),
+    "ethcnn_train_group_step_indices": (_i, [_vp, ctypes.c_int64, ctypes.POINTER(ctypes.c_int32), ctypes.POINTER(ctypes.c_int), _i, _fp, _fp]),
+    "ethcnn_train_group_evaluate": (_i, [_vp, _i, ctypes.POINTER(ctypes.c_int32), ctypes.c_int64, ctypes.POINTER(ctypes.c_int), _fp, _fp, _fp]),
+    "ethcnn_train_group_debug_fetch": (_i, [_vp, _i, _i, _fp, _sz]),
+    "ethcnn_train_group_last_error": (_cp, [_vp]),
     "ethcnn_ckpt_write_lstm_blob": (_i, [_cp, _fp, _sz, ctypes.c_char_p, _sz]),
     "ethcnn_lstm_train_create": (_i, [_vp, ctypes.c_void_p, ctypes.POINTER(_vp)]),
     "ethcnn_lstm_train_destroy": (None, [_vp]),
@@ -999,6 +1014,154 @@ class Trainer(object):
              TDBG_PROBS: self.batch * NOUT, TDBG_INDICES: self.batch * 2, TDBG_H1: self.batch * NVEC}[which]
         out = np.empty(n, dtype=np.float32)
         self._chk(self.lib.ethcnn_train_debug_fetch(self.h, int(which), out.ctypes.data_as(_fp), n))
+        return out
+
+
+def _train_options_array(opts):
+    opts = list(opts)
+    for o in opts:
+        if not isinstance(o, TrainOptions):
+            raise TypeError("a trainer group takes TrainOptions, got %r" % type(o).__name__)
+    return (TrainOptions * max(len(opts), 1))(*opts), len(opts)
+
+
+def train_options(batch=64, lr=0.01, momentum=0.9, decay_rate=0.3163, decay_steps=250000, dropout=True, seed=0, net="ai", tune=0):
+    """the TrainOptions of Trainer's keyword arguments (a TrainerGroup takes a list of them)"""
+    nets = {"ai": TRAIN_NET_AI, "ldp": TRAIN_NET_LDP}
+    return TrainOptions(int(batch), float(lr), float(momentum), float(decay_rate), int(decay_steps), 1 if dropout else 0,
+                        int(seed) & _M64, nets[net] if net in nets else int(net), int(tune))
+
+
+def train_group_check(opts, lib=None):
+    """host-only check of a trainer group's options (no context): raises EthCnnError(ERR_ARG) naming the member and the field"""
+    lib = lib or load_library()
+    arr, k = _train_options_array(opts)
+    err = ctypes.create_string_buffer(256)
+    rc = lib.ethcnn_train_group_check(arr, k, err, len(err))
+    if rc:
+        raise EthCnnError(rc, err.value.decode())
+
+
+class TrainerGroup(object):
+    """K (1..8) independent ETH-CNN trainers in every launch of a step (include/ethcnn.h "training, several models at once"):
+    one context, one stream, one copy of the sample sets.  Member m computes what Trainer computes with opts[m], bit for bit.
+    opts: a list of TrainOptions (train_options(...)) with the same net, batch and tune."""
+
+    def __init__(self, ctx, opts):
+        self.ctx, self.lib = ctx, ctx.lib
+        arr, k = _train_options_array(opts)
+        h = ctypes.c_void_p()
+        rc = self.lib.ethcnn_train_group_create(ctx.h, arr, k, ctypes.byref(h))
+        if rc:
+            raise EthCnnError(rc, self.lib.ethcnn_last_error(ctx.h).decode())
+        self.h, self.k, self.batch = h, k, int(arr[0].batch)
+        self.seeds = [int(arr[m].seed) for m in range(k)]
+        self.net = "ldp" if arr[0].net == TRAIN_NET_LDP else "ai"
+        if not hasattr(ctx, "_trainers"):
+            ctx._trainers = weakref.WeakSet()
+        ctx._trainers.add(self)
+
+    def __len__(self):
+        return self.k
+
+    def _chk(self, rc):
+        if rc:
+            raise EthCnnError(rc, self.lib.ethcnn_train_group_last_error(self.h).decode())
+
+    def close(self):
+        if getattr(self, "h", None):
+            self.lib.ethcnn_train_group_destroy(self.h)
+            self.h = None
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+    def __enter__(self):
+        return self
+
+    def __exit__(self, *a):
+        self.close()
+
+    def init_weights(self, seeds):
+        """seeds: one per member, or one number for all"""
+        seeds = [seeds] * self.k if np.isscalar(seeds) else list(seeds)
+        if len(seeds) != self.k:
+            raise ValueError("%d seeds for %d members" % (len(seeds), self.k))
+        self._chk(self.lib.ethcnn_train_group_init_weights(self.h, (ctypes.c_uint64 * self.k)(*[int(x) & _M64 for x in seeds])))
+
+    def set_blob(self, m, blob, accum=None):
+        blob = np.ascontiguousarray(blob, dtype=np.float32)
+        acc = None if accum is None else np.ascontiguousarray(accum, dtype=np.float32)
+        if acc is not None and acc.size != blob.size:
+            raise ValueError("accumulators and blob differ in size")
+        self._chk(self.lib.ethcnn_train_group_set_blob(self.h, int(m), blob.ctypes.data_as(_fp),
+                                                       None if acc is None else acc.ctypes.data_as(_fp), blob.size))
+
+    def get_blob(self, m, with_accum=False):
+        blob = np.empty(BLOB_FLOATS, dtype=np.float32)
+        acc = np.empty(BLOB_FLOATS, dtype=np.float32) if with_accum else None
+        self._chk(self.lib.ethcnn_train_group_get_blob(self.h, int(m), blob.ctypes.data_as(_fp),
+                                                       None if acc is None else acc.ctypes.data_as(_fp), BLOB_FLOATS))
+        return (blob, acc) if with_accum else blob
+
+    def set_samples(self, which, records, take=False):
+        """what Trainer.set_samples takes; one copy in HBM serves every member"""
+        if isinstance(records, SampleSet):
+            self._chk(self.lib.ethcnn_train_group_set_samples_from(self.h, int(which), records.h, 1 if take else 0))
+            return
+        buf = np.frombuffer(records, dtype=np.uint8) if isinstance(records, (bytes, bytearray)) else np.ascontiguousarray(records, np.uint8)
+        self._chk(self.lib.ethcnn_train_group_set_samples(self.h, int(which), buf.ctypes.data if buf.size else None, buf.size))
+
+    def set_qps(self, m, qps):
+        arr = (ctypes.c_int * len(qps))(*[int(q) for q in qps])
+        self._chk(self.lib.ethcnn_train_group_set_qps(self.h, int(m), arr, len(qps)))
+
+    def run(self, first_step, nsteps):
+        """enqueue steps first_step .. first_step + nsteps - 1 of every member (device-drawn batches); returns at once"""
+        self._chk(self.lib.ethcnn_train_group_run(self.h, int(first_step), int(nsteps)))
+
+    def last_stats(self):
+        """(loss_list [k,3], accuracy_list [k,3]) of the last step enqueued (waits for it)"""
+        l3, a3 = np.zeros((self.k, 3), np.float32), np.zeros((self.k, 3), np.float32)
+        self._chk(self.lib.ethcnn_train_group_last_stats(self.h, l3.ctypes.data_as(_fp), a3.ctypes.data_as(_fp)))
+        return l3, a3
+
+    def step_indices(self, step, idx, qps):
+        """idx [k, batch]; qps [k, batch], or anything that broadcasts to it"""
+        idx = np.ascontiguousarray(idx, dtype=np.int32)
+        if idx.shape != (self.k, self.batch):
+            raise ValueError("idx must be [%d, %d]" % (self.k, self.batch))
+        qps = np.ascontiguousarray(np.broadcast_to(np.asarray(qps, dtype=np.int32), idx.shape))
+        l3, a3 = np.zeros((self.k, 3), np.float32), np.zeros((self.k, 3), np.float32)
+        self._chk(self.lib.ethcnn_train_group_step_indices(self.h, int(step), idx.ctypes.data_as(ctypes.POINTER(ctypes.c_int32)),
+                                                           qps.ctypes.data_as(ctypes.POINTER(ctypes.c_int)), self.batch,
+                                                           l3.ctypes.data_as(_fp), a3.ctypes.data_as(_fp)))
+        return l3, a3
+
+    def evaluate(self, which, qps, idx=None, n=None, want_probs=False):
+        """(loss_list [k,3], accuracy_list [k,3][, probs [k,n,21]]): every member over the same samples idx (or 0 .. n-1), member m
+        at qps[m]; LDP: qps[m] = -1 puts sample i at slot mixed_eval_slots(seed of m, n)[i]"""
+        qps = [int(q) for q in qps]
+        if len(qps) != self.k:
+            raise ValueError("%d QPs for %d members" % (len(qps), self.k))
+        if idx is not None:
+            idx = np.ascontiguousarray(idx, dtype=np.int32)
+            n = idx.size
+        probs = np.empty((self.k, int(n), NOUT), dtype=np.float32) if want_probs else None
+        l3, a3 = np.zeros((self.k, 3), np.float32), np.zeros((self.k, 3), np.float32)
+        self._chk(self.lib.ethcnn_train_group_evaluate(self.h, int(which), None if idx is None else idx.ctypes.data_as(ctypes.POINTER(ctypes.c_int32)),
+                                                       int(n), (ctypes.c_int * self.k)(*qps), l3.ctypes.data_as(_fp), a3.ctypes.data_as(_fp),
+                                                       None if probs is None else probs.ctypes.data_as(_fp)))
+        return (l3, a3, probs) if want_probs else (l3, a3)
+
+    def debug_fetch(self, m, which):
+        n = {TDBG_GRADS: BLOB_FLOATS, TDBG_ACCUM: BLOB_FLOATS, TDBG_MASK_FC1: self.batch * NVEC, TDBG_MASK_FC2: self.batch * NFC2,
+             TDBG_PROBS: self.batch * NOUT, TDBG_INDICES: self.batch * 2, TDBG_H1: self.batch * NVEC}[which]
+        out = np.empty(n, dtype=np.float32)
+        self._chk(self.lib.ethcnn_train_group_debug_fetch(self.h, int(m), int(which), out.ctypes.data_as(_fp), n))
         return out
 
 

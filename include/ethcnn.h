@@ -512,6 +512,41 @@ int ethcnn_train_evaluate(ethcnn_trainer* tr, int set, const int32_t* idx, int64
 int ethcnn_train_debug_fetch(ethcnn_trainer* tr, int which, float* out, size_t nfloats);
 const char* ethcnn_train_last_error(const ethcnn_trainer* tr);
 
+/* ---- training, several models at once: a trainer GROUP is k (1..8) independent trainers of "training" above that share a context,
+ *      its stream, the two resident sample sets and every launch of a step.  A deployment of the All-Intra predictor needs four models
+ *      (model_2000000_qp20~25 .. qp35~40) that differ only in the QP list and read the same sample file; several seeds or learning
+ *      rates of one model are the other use.  A step of the group is still 8 launches (tune 1..3: 7), each over all members
+ *      (csrc/ethcnn_train.h "trainer group"); an evaluation is still launches 1-3 over pieces, then one loss launch.
+ *   Exactness: member m computes what ethcnn_train_* computes for a trainer with opts[m], its weights, its QP list and the same
+ *      samples -- bit for bit, whatever k is and wherever in the group the member sits.  The members share the records and nothing
+ *      else: each has its own weights, accumulators, RNG streams (opts[m].seed), batch-global label counts and learning rate.
+ *   Members of one group have the same net, batch and tune; they may differ in seed, lr_init, momentum, decay_rate, decay_steps and
+ *      dropout.  ethcnn_train_group_check (host only, no context) returns ETHCNN_ERR_ARG and a message that names the member and
+ *      the field for anything else, and for an option ethcnn_train_create refuses; err may be NULL.
+ *   Arrays over members are member-major: seeds[k], qps[k], loss[k][3], acc[k][3], idx[k][batch], qp[k][batch], probs[k][n][21].
+ *   A member index outside 0..k-1 is ETHCNN_ERR_ARG. */
+typedef struct ethcnn_train_group ethcnn_train_group;
+int ethcnn_train_group_check(const ethcnn_train_options* opts, int k, char* err, size_t errcap);
+int ethcnn_train_group_create(ethcnn_ctx* ctx, const ethcnn_train_options* opts, int k, ethcnn_train_group** out);
+void ethcnn_train_group_destroy(ethcnn_train_group* grp); /* before ethcnn_destroy of its context */
+int ethcnn_train_group_init_weights(ethcnn_train_group* grp, const uint64_t* seeds /* [k] */); /* member m: ethcnn_train_init_weights(seeds[m]) */
+int ethcnn_train_group_set_blob(ethcnn_train_group* grp, int member, const float* blob, const float* accum /* NULL = zeros */, size_t nfloats);
+int ethcnn_train_group_get_blob(ethcnn_train_group* grp, int member, float* blob, float* accum /* may be NULL */, size_t nfloats);
+/* ONE copy in HBM for all members; LDP: the slot-QP pass runs once and every member's QP list becomes the four slots */
+int ethcnn_train_group_set_samples(ethcnn_train_group* grp, int set, const uint8_t* records, size_t nbytes);
+int ethcnn_train_group_set_qps(ethcnn_train_group* grp, int member, const int* qps, int nqps);
+/* steps first_step .. first_step + nsteps - 1 of every member, device-drawn batches; asynchronous (nothing read back) */
+int ethcnn_train_group_run(ethcnn_train_group* grp, int64_t first_step, int64_t nsteps);
+int ethcnn_train_group_last_stats(ethcnn_train_group* grp, float* loss /* [k][3] */, float* acc /* [k][3] */);
+/* one step on explicit batches, n == batch samples per member: idx [k][n], qp [k][n]; synchronous */
+int ethcnn_train_group_step_indices(ethcnn_train_group* grp, int64_t step, const int32_t* idx, const int* qp, int n, float* loss, float* acc);
+/* every member evaluates the same n samples (idx NULL: 0 .. n-1), member m at qps[m] (LDP: a slot QP or -1, the slot draw with the
+ * member's seed); each member's loss and accuracy lists are those of ONE batch of all n.  probs [k][n][21] may be NULL. */
+int ethcnn_train_group_evaluate(ethcnn_train_group* grp, int set, const int32_t* idx, int64_t n, const int* qps /* [k] */, float* loss,
+                                float* acc, float* probs);
+int ethcnn_train_group_debug_fetch(ethcnn_train_group* grp, int member, int which, float* out, size_t nfloats);
+const char* ethcnn_train_group_last_error(const ethcnn_train_group* grp);
+
 /* ---- ETH-LSTM training (ETH-LSTM_Training_LDP/net_CTU64.py:85-276, input_data.py:88-147, train_LSTM_CTU64.py:42-52): the 20-step
  *      unrolled LSTM of the Low-Delay-P path with back-propagation through time, one model per QP (model_LDP_200000_qp<QP>.dat).
  *      Mirrors ethcnn_train_* one to one; bound to a context (its device and stream); hand-written gfx950 kernels, exact fp32,
@@ -655,6 +690,8 @@ int ethcnn_samples_write(ethcnn_samples* set, const char* path, int permuted, ui
  * the four slots, as there.  take != 0: the trainer adopts the buffer and the set becomes empty (0 records, not built); else a
  * device-to-device copy. */
 int ethcnn_train_set_samples_from(ethcnn_trainer* tr, int set_index, ethcnn_samples* set, int take);
+/* the same for a trainer group ("training, several models at once"): one buffer serves every member */
+int ethcnn_train_group_set_samples_from(ethcnn_train_group* grp, int set_index, ethcnn_samples* set, int take);
 
 /* ---- ETH-LSTM sample sets (ETH-LSTM_Training_LDP/get_LSTM_input.py): the 37264-byte samples of "ETH-LSTM training" above, built in HBM
  *      from 16516-byte Low-Delay-P records (an inter sample set that is resident there, or records in host memory) with the context's
