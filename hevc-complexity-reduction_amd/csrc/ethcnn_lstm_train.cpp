@@ -12,6 +12,7 @@
 #include "ethcnn_ctx.h"
 #include "ethcnn_lstm_samples.h"
 #include "ethcnn_lstm_train.h"
+#include "ethcnn_lstm_train_host.h"
 
 using namespace ethcnn::lstm_train;
 using ethcnn::kLstmBlobFloats;
@@ -33,27 +34,6 @@ int lstm_tensor_off(const std::string& name) {
     return -1;
 }
 }  // namespace
-
-struct ethcnn_lstm_trainer {
-    ethcnn_ctx* c = nullptr;
-    ethcnn_lstm_train_options opt{};
-    int B = 0, cap = 0;  // batch; samples the per-row buffers hold (>= the evaluation chunk)
-    float qp_scale = 1.f;
-    LstmOffsets o{};
-    std::string err;
-    float *W = nullptr, *acc = nullptr, *grad = nullptr, *stats = nullptr;
-    double* part = nullptr;
-    int32_t *idx = nullptr, *idx_in = nullptr;
-    LstmBufs u{};
-    GemmGroup *g_fwd = nullptr, *g_bwd = nullptr, *g_eval = nullptr;
-    int t_fwd = 0, t_bwd = 0, t_eval = 0;
-    uint8_t* data[2] = {nullptr, nullptr};
-    int64_t nrec[2] = {0, 0};
-    int qps[52] = {0};
-    int nqps = 0;        // 0: every sample is kept
-    int last_rows = 0;   // rows of the last step / the last evaluation piece (debug buffers)
-    std::vector<void*> allocs;
-};
 
 static int terr(ethcnn_lstm_trainer* t, int code, const char* fmt, ...) {
     char buf[512];
@@ -93,7 +73,7 @@ static void add_desc(GemmGroup& g, GemmDesc d) {
 }
 
 // input projections of `rows` rows: Z_cell = X[:, cell columns] x kernel[0:H, :]
-static GemmGroup proj_group(const ethcnn_lstm_trainer* t, int rows) {
+GemmGroup lstm_proj_group(const ethcnn_lstm_trainer* t, int rows) {
     GemmGroup g{};
     for (int c = 0; c < 3; ++c) {
         GemmDesc d{};
@@ -107,7 +87,7 @@ static GemmGroup proj_group(const ethcnn_lstm_trainer* t, int rows) {
 }
 
 // the 18 tensors' gradients, K = rows, written into grad at their blob offsets
-static GemmGroup grad_group(const ethcnn_lstm_trainer* t, int rows) {
+GemmGroup lstm_grad_group(const ethcnn_lstm_trainer* t, int rows) {
     GemmGroup g{};
     for (int c = 0; c < 3; ++c) {
         const int H = kH[c];
@@ -139,7 +119,7 @@ static GemmGroup grad_group(const ethcnn_lstm_trainer* t, int rows) {
     return g;
 }
 
-static float lr_at(const ethcnn_lstm_trainer* t, int64_t step) {  // tf.train.exponential_decay(..., staircase=True)
+float lstm_lr_at(const ethcnn_lstm_trainer* t, int64_t step) {  // tf.train.exponential_decay(..., staircase=True)
     const double p = std::floor((double)step / (double)t->opt.decay_steps);
     return (float)((double)t->opt.lr_init * std::pow((double)t->opt.decay_rate, p));
 }
@@ -176,7 +156,7 @@ static int enqueue_step(ethcnn_lstm_trainer* t, int64_t step, bool explicit_batc
     launch_heads_bwd(s, t->B, t->u, t->W, t->o, dropout);
     launch_bwd(s, t->B, t->u, t->W, t->o);
     ethcnn::train::launch_gemm(s, t->g_bwd, t->t_bwd);
-    launch_norm_update(s, t->W, t->acc, t->grad, t->part, t->opt.clip_norm, lr_at(t, step), t->opt.momentum, (long)kLstmBlobFloats,
+    launch_norm_update(s, t->W, t->acc, t->grad, t->part, t->opt.clip_norm, lstm_lr_at(t, step), t->opt.momentum, (long)kLstmBlobFloats,
                        t->stats);
     TCHK(t, hipGetLastError());
     return 0;
@@ -262,7 +242,7 @@ extern "C" int ethcnn_lstm_train_create(ethcnn_ctx* c, const ethcnn_lstm_train_o
     for (void* p : {(void*)t->W, (void*)t->acc, (void*)t->grad}) e = e ? e : hipMemsetAsync(p, 0, kLstmBlobFloats * 4, c->stream);
     e = e ? e : hipMemsetAsync(u.X, 0, R * kVec * 4, c->stream);
     e = e ? e : hipMemsetAsync(t->stats, 0, 32, c->stream);
-    const GemmGroup gf = proj_group(t, t->B * kSteps), gb = grad_group(t, t->B * kSteps), ge = proj_group(t, t->cap * kSteps);
+    const GemmGroup gf = lstm_proj_group(t, t->B * kSteps), gb = lstm_grad_group(t, t->B * kSteps), ge = lstm_proj_group(t, t->cap * kSteps);
     t->t_fwd = gf.tiles; t->t_bwd = gb.tiles; t->t_eval = ge.tiles;
     e = e ? e : hipMemcpy(t->g_fwd, &gf, sizeof gf, hipMemcpyHostToDevice);
     e = e ? e : hipMemcpy(t->g_bwd, &gb, sizeof gb, hipMemcpyHostToDevice);

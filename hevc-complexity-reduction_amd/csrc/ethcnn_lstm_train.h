@@ -77,6 +77,42 @@ struct GatherArgs {
     int32_t* idx_out;       // [nb]
     uint64_t seed, step;
     float qp_scale;
+    const int64_t* keep;  // trainer group: sample i is record keep[i] of data; NULL (solo): record i
+};
+
+// ---- trainer group (include/ethcnn.h "ETH-LSTM training, several models at once"): K independent LSTM trainers of one batch size in
+// every launch of a step.  A step is still the 10 launches above; launch i covers all K members:
+//   gather / heads forward / heads backward     grid (20 B, K): block (r, m) is row r of member m
+//   GEMMs (projections, weight gradients)       the CNN group's k_group_gemm: K x T blocks, T = the tiles of one member's descriptors
+//   recurrences                                 grid (ceil(B / 16), 3, K): block (s, cell, m)
+//   loss                                        the CNN group's k_group_loss: K blocks, block m owns member m's counts over 20 B rows
+//   norm / update                               grid (512, K) / (1024, K): gridDim.x is the solo kernel's, so are chunk and stride
+// Every block runs the solo kernel's body (ethcnn_lstm_train_kernels.hip) on its member's solo-shaped buffers, no sum crosses
+// members and nothing is atomic, so member m computes what a solo trainer with its options computes, bit for bit, whatever K and m.
+// The members share the two sample sets: one copy each, and per member and set the list of the records its QP selection keeps, in
+// file order (keep NULL: all).  A member's sample index i is its i-th kept record -- what the solo trainer's index means after it
+// compacted its copy -- so the index draw over nkept gives the solo batches.
+// The table lives in device memory and changes only with the sample sets; what changes per launch goes by value (LstmGroupStep, and
+// train::GroupRates for the K learning rates of the step).
+struct LstmMember {
+    LstmBufs u;
+    float *W, *acc, *grad;  // blob layout
+    double* part;           // [kNormBlocks]
+    float* stats;           // [8]
+    const int32_t* idx_in;  // explicit batch / evaluation samples (ignored when LstmGroupStep.drawn)
+    int32_t* idx;           // the batch's sample indices, as drawn or read
+    const int64_t* keep[2];  // per set: the kept records (NULL: every record)
+    long nkept[2];
+    uint64_t seed;
+    float qp_scale;
+    int dropout;
+    float momentum, clip;
+};
+struct LstmGroupStep {
+    const uint8_t* data;  // the shared records of `set`
+    uint64_t step;
+    int set;
+    int drawn;  // 1: indices drawn on the device
 };
 
 // launchers (ethcnn_lstm_train_kernels.hip)
@@ -89,6 +125,13 @@ void launch_bwd(hipStream_t s, int nb, const LstmBufs& u, const float* W, const 
 void launch_norm_update(hipStream_t s, float* W, float* acc, const float* grad, double* part, float clip, float lr, float momentum, long n,
                         float* stats);
 void launch_check(hipStream_t s, const uint8_t* data, long nrec, long* first_bad, int nblocks);
+void launch_check_list(hipStream_t s, const uint8_t* data, const int64_t* list, long n, uint8_t* bad, int nblocks);
+void launch_group_gather(hipStream_t s, int nb, int k, const LstmMember* tab, const LstmGroupStep& g);
+void launch_group_fwd(hipStream_t s, int nb, int k, const LstmMember* tab, const LstmOffsets& o);
+void launch_group_heads_fwd(hipStream_t s, int nb, int k, const LstmMember* tab, const LstmOffsets& o, uint64_t step, int train);
+void launch_group_heads_bwd(hipStream_t s, int nb, int k, const LstmMember* tab, const LstmOffsets& o);
+void launch_group_bwd(hipStream_t s, int nb, int k, const LstmMember* tab, const LstmOffsets& o);
+void launch_group_norm_update(hipStream_t s, int k, const LstmMember* tab, const train::GroupRates& r, long n);
 
 }  // namespace lstm_train
 }  // namespace ethcnn

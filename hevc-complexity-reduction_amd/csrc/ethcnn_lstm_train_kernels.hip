@@ -28,12 +28,13 @@ __device__ inline float keep_mask(uint64_t seed, uint64_t step, int row, int uni
 }
 
 // ------------------------------------------------------------------------------------------------------------------ gather ---
-__global__ __launch_bounds__(128) void k_lstm_gather(GatherArgs a, LstmBufs u) {
+// a.keep (trainer group: the member's kept records of the shared set, file order): sample i is record keep[i]; NULL: record i
+__device__ __forceinline__ void gather_body(const GatherArgs& a, const LstmBufs& u) {
     const int row = blockIdx.x, b = row / kSteps, p = row % kSteps, t = threadIdx.x;
     long i;
     if (a.idx_in) i = a.idx_in[b];
     else i = (long)(((draw(a.seed, kStreamLstmIndex, a.step, (uint64_t)b, 0) >> 32) * (uint64_t)a.nrec) >> 32);
-    const uint8_t* rec = a.data + i * kRecBytes;
+    const uint8_t* rec = a.data + (a.keep ? (long)a.keep[i] : i) * kRecBytes;
     const float* slots = (const float*)(rec + 64);  // 64 and 37264 are multiples of 4
     const float* slot = slots + p * kSlotFloats;
     for (int k = t; k < kVec; k += 128) u.X[(long)row * kVec + k] = slot[17 + k];
@@ -51,6 +52,7 @@ __global__ __launch_bounds__(128) void k_lstm_gather(GatherArgs a, LstmBufs u) {
         for (int k = 0; k < 4; ++k) e[1 + k] = k == gop ? 1.f : 0.f;
     }
 }
+__global__ __launch_bounds__(128) void k_lstm_gather(GatherArgs a, LstmBufs u) { gather_body(a, u); }
 
 // ------------------------------------------------------------------------------------------------------ forward recurrence ---
 // 256 threads = 4 waves; wave w owns the hidden-unit tiles (w + 4 i) * 16 .. + 16 and, per tile, the four gate accumulators of
@@ -127,17 +129,18 @@ __device__ void fwd_cell(const LstmBufs& u, const float* __restrict__ W, int ker
     }
 }
 
-__global__ __launch_bounds__(256) void k_lstm_fwd(LstmBufs u, const float* __restrict__ W, LstmOffsets o, int nb) {
+__device__ __forceinline__ void fwd_body(const LstmBufs& u, const float* __restrict__ W, const LstmOffsets& o, const int nb) {
     __shared__ float hs[16 * 260];
     const int cell = blockIdx.y;
     if (cell == 0) fwd_cell<64>(u, W, o.kern[0], o.bias[0], 0, u.Z[0], u.HP[0], nb, hs);
     else if (cell == 1) fwd_cell<128>(u, W, o.kern[1], o.bias[1], 64, u.Z[1], u.HP[1], nb, hs);
     else fwd_cell<256>(u, W, o.kern[2], o.bias[2], 192, u.Z[2], u.HP[2], nb, hs);
 }
+__global__ __launch_bounds__(256) void k_lstm_fwd(LstmBufs u, const float* __restrict__ W, LstmOffsets o, int nb) { fwd_body(u, W, o, nb); }
 
 // ------------------------------------------------------------------------------------------------------------ heads forward ---
-__global__ __launch_bounds__(256) void k_lstm_heads_fwd(LstmBufs u, const float* __restrict__ W, LstmOffsets o, uint64_t seed,
-                                                         uint64_t step, int dropout) {
+__device__ __forceinline__ void heads_fwd_body(const LstmBufs& u, const float* __restrict__ W, const LstmOffsets& o, const uint64_t seed,
+                                               const uint64_t step, const int dropout) {
     __shared__ float h1[kLdH1], h2[kLdH2];
     const int row = blockIdx.x, t = threadIdx.x;
     const float* ef = u.E + (long)row * kEf;
@@ -178,9 +181,13 @@ __global__ __launch_bounds__(256) void k_lstm_heads_fwd(LstmBufs u, const float*
         u.P[(long)row * kOut + t] = sigm(acc + W[o.b3[cl] + j]);
     }
 }
+__global__ __launch_bounds__(256) void k_lstm_heads_fwd(LstmBufs u, const float* __restrict__ W, LstmOffsets o, uint64_t seed,
+                                                         uint64_t step, int dropout) {
+    heads_fwd_body(u, W, o, seed, step, dropout);
+}
 
 // ----------------------------------------------------------------------------------------------------------- heads backward ---
-__global__ __launch_bounds__(256) void k_lstm_heads_bwd(LstmBufs u, const float* __restrict__ W, LstmOffsets o, int dropout) {
+__device__ __forceinline__ void heads_bwd_body(const LstmBufs& u, const float* __restrict__ W, const LstmOffsets& o, const int dropout) {
     __shared__ float dz3[kOut], dz2[kFc2];
     const int row = blockIdx.x, t = threadIdx.x;
     if (t < kOut) dz3[t] = u.dZ3[(long)row * kOut + t];
@@ -203,6 +210,9 @@ __global__ __launch_bounds__(256) void k_lstm_heads_bwd(LstmBufs u, const float*
         for (int c = 0; c < n2; ++c) acc += w[j * n2 + c] * dz2[kN2Off[cl] + c];
         u.dH[(long)row * kVec + x] = dropout ? (acc * u.M1[(long)row * kVec + x]) / 0.5f : acc;
     }
+}
+__global__ __launch_bounds__(256) void k_lstm_heads_bwd(LstmBufs u, const float* __restrict__ W, LstmOffsets o, int dropout) {
+    heads_bwd_body(u, W, o, dropout);
 }
 
 // ----------------------------------------------------------------------------------------------------- backward recurrence ---
@@ -284,7 +294,7 @@ __device__ void bwd_cell(const LstmBufs& u, const float* __restrict__ W, int ker
     }
 }
 
-__global__ __launch_bounds__(256) void k_lstm_bwd(LstmBufs u, const float* __restrict__ W, LstmOffsets o, int nb) {
+__device__ __forceinline__ void bwd_body(const LstmBufs& u, const float* __restrict__ W, const LstmOffsets& o, const int nb) {
     __shared__ __attribute__((aligned(16))) float dzs[16 * 516];
     __shared__ float dhs[16 * 260];
     const int cell = blockIdx.y;
@@ -292,10 +302,11 @@ __global__ __launch_bounds__(256) void k_lstm_bwd(LstmBufs u, const float* __res
     else if (cell == 1) bwd_cell<128>(u, W, o.kern[1], 64, u.Z[1], u.dZ[1], nb, dzs, dhs);
     else bwd_cell<256>(u, W, o.kern[2], 192, u.Z[2], u.dZ[2], nb, dzs, dhs);
 }
+__global__ __launch_bounds__(256) void k_lstm_bwd(LstmBufs u, const float* __restrict__ W, LstmOffsets o, int nb) { bwd_body(u, W, o, nb); }
 
 // ------------------------------------------------------------------------------------------------- global norm and update ---
 // level 1: block k sums the squares of floats [k chunk, (k + 1) chunk): thread t takes t, t + 256, ... in order, then a tree in LDS
-__global__ __launch_bounds__(256) void k_lstm_norm(const float* __restrict__ grad, long n, double* __restrict__ part) {
+__device__ __forceinline__ void norm_body(const float* __restrict__ grad, const long n, double* __restrict__ part) {
     __shared__ double red[256];
     const long chunk = (n + gridDim.x - 1) / gridDim.x, lo = (long)blockIdx.x * chunk, hi = min(n, lo + chunk);
     double s = 0.0;
@@ -308,12 +319,15 @@ __global__ __launch_bounds__(256) void k_lstm_norm(const float* __restrict__ gra
     }
     if (threadIdx.x == 0) part[blockIdx.x] = red[0];
 }
+__global__ __launch_bounds__(256) void k_lstm_norm(const float* __restrict__ grad, long n, double* __restrict__ part) {
+    norm_body(grad, n, part);
+}
 
 // level 2 (every block, the same order) + tf.clip_by_global_norm (scale = clip * min(1 / norm, 1 / clip)) + MomentumOptimizer.
 // grad keeps the unclipped gradient; stats[7] = the global norm.
-__global__ __launch_bounds__(256) void k_lstm_update(float* __restrict__ W, float* __restrict__ acc, const float* __restrict__ grad,
-                                                      const double* __restrict__ part, int nparts, float clip, float lr, float momentum,
-                                                      long n, float* __restrict__ stats) {
+__device__ __forceinline__ void update_body(float* __restrict__ W, float* __restrict__ acc, const float* __restrict__ grad,
+                                            const double* __restrict__ part, const int nparts, const float clip, const float lr,
+                                            const float momentum, const long n, float* __restrict__ stats) {
     __shared__ float s_scale;
     if (threadIdx.x == 0) {
         double s = 0.0;
@@ -331,10 +345,52 @@ __global__ __launch_bounds__(256) void k_lstm_update(float* __restrict__ W, floa
         W[j] = W[j] - lr * a;
     }
 }
+__global__ __launch_bounds__(256) void k_lstm_update(float* __restrict__ W, float* __restrict__ acc, const float* __restrict__ grad,
+                                                      const double* __restrict__ part, int nparts, float clip, float lr, float momentum,
+                                                      long n, float* __restrict__ stats) {
+    update_body(W, acc, grad, part, nparts, clip, lr, momentum, n, stats);
+}
+
+// ------------------------------------------------------------------------------------------------------------ trainer group ---
+// K trainers in every launch of a step (ethcnn_lstm_train.h "trainer group").  tab: the device-resident member table.  The member is
+// the grid's last dimension; blockIdx.x (and, in the recurrences, blockIdx.y = the cell) and gridDim.x are what the solo launch gives
+// the body, so each block runs the solo kernel's instructions on its member's buffers.  The members share the sample records only.
+__global__ __launch_bounds__(128) void k_lstm_group_gather(const LstmMember* __restrict__ tab, LstmGroupStep g) {
+    const LstmMember& m = tab[blockIdx.y];
+    const GatherArgs a{g.data, m.nkept[g.set], g.drawn ? nullptr : m.idx_in, m.idx, m.seed, g.step, m.qp_scale, m.keep[g.set]};
+    gather_body(a, m.u);
+}
+__global__ __launch_bounds__(256) void k_lstm_group_fwd(const LstmMember* __restrict__ tab, LstmOffsets o, int nb) {
+    const LstmMember& m = tab[blockIdx.z];
+    fwd_body(m.u, m.W, o, nb);
+}
+__global__ __launch_bounds__(256) void k_lstm_group_heads_fwd(const LstmMember* __restrict__ tab, LstmOffsets o, uint64_t step, int train) {
+    const LstmMember& m = tab[blockIdx.y];
+    heads_fwd_body(m.u, m.W, o, m.seed, step, train ? m.dropout : 0);
+}
+__global__ __launch_bounds__(256) void k_lstm_group_heads_bwd(const LstmMember* __restrict__ tab, LstmOffsets o) {
+    const LstmMember& m = tab[blockIdx.y];
+    heads_bwd_body(m.u, m.W, o, m.dropout);
+}
+__global__ __launch_bounds__(256) void k_lstm_group_bwd(const LstmMember* __restrict__ tab, LstmOffsets o, int nb) {
+    const LstmMember& m = tab[blockIdx.z];
+    bwd_body(m.u, m.W, o, nb);
+}
+__global__ __launch_bounds__(256) void k_lstm_group_norm(const LstmMember* __restrict__ tab, long n) {
+    const LstmMember& m = tab[blockIdx.y];
+    norm_body(m.grad, n, m.part);
+}
+__global__ __launch_bounds__(256) void k_lstm_group_update(const LstmMember* __restrict__ tab, train::GroupRates r, long n) {
+    const LstmMember& m = tab[blockIdx.y];
+    update_body(m.W, m.acc, m.grad, m.part, kNormBlocks, m.clip, r.lr[blockIdx.y], m.momentum, n, m.stats);
+}
 
 // ------------------------------------------------------------------------------------------------------------- sample check ---
 // first record (per block, over a contiguous range) with a QP that is not an integer in 0..51, a label that is not an integer in 0..3
 // or a vector element that is not finite; nrec when there is none.  The host takes the min over the blocks.
+__device__ inline bool sample_float_ok(int c, float v) {  // float c of a slot: [qp | 16 labels | 448 vector]
+    return c == 0 ? (v >= 0.f && v <= 51.f && v == truncf(v)) : (c <= 16 ? (v >= 0.f && v <= 3.f && v == truncf(v)) : isfinite(v));
+}
 __global__ __launch_bounds__(256) void k_lstm_check(const uint8_t* __restrict__ data, long nrec, long* __restrict__ first_bad) {
     __shared__ long red[256];
     const long per = (nrec + gridDim.x - 1) / gridDim.x, r0 = (long)blockIdx.x * per, r1 = min(nrec, r0 + per);
@@ -345,8 +401,7 @@ __global__ __launch_bounds__(256) void k_lstm_check(const uint8_t* __restrict__ 
         for (int j = threadIdx.x; j < kF; j += 256) {
             const int c = j % kSlotFloats;
             const float v = f[j];
-            const bool ok = c == 0 ? (v >= 0.f && v <= 51.f && v == truncf(v)) : (c <= 16 ? (v >= 0.f && v <= 3.f && v == truncf(v)) : isfinite(v));
-            if (!ok) bad = i;
+            if (!sample_float_ok(c, v)) bad = i;
         }
     }
     red[threadIdx.x] = bad;
@@ -356,6 +411,25 @@ __global__ __launch_bounds__(256) void k_lstm_check(const uint8_t* __restrict__ 
         __syncthreads();
     }
     if (threadIdx.x == 0) first_bad[blockIdx.x] = red[0];
+}
+
+// trainer group: the same test per listed record, bad[j] = 1 when record list[j] (NULL: j) fails it.  Every thread that finds a bad
+// float stores the same 1: no sum, no order.
+__global__ __launch_bounds__(256) void k_lstm_check_list(const uint8_t* __restrict__ data, const int64_t* __restrict__ list, long n,
+                                                          uint8_t* __restrict__ bad) {
+    __shared__ int any;
+    constexpr int kF = kSlotFloats * kSteps;
+    for (long j = blockIdx.x; j < n; j += gridDim.x) {
+        if (threadIdx.x == 0) any = 0;
+        __syncthreads();
+        const float* f = (const float*)(data + (list ? (long)list[j] : j) * kRecBytes + 64);
+        bool ok = true;
+        for (int e = threadIdx.x; e < kF; e += 256) ok = ok && sample_float_ok(e % kSlotFloats, f[e]);
+        if (!ok) any = 1;
+        __syncthreads();
+        if (threadIdx.x == 0) bad[j] = (uint8_t)any;
+        __syncthreads();
+    }
 }
 
 // --------------------------------------------------------------------------------------------------------------- launchers ---
@@ -382,6 +456,30 @@ void launch_norm_update(hipStream_t s, float* W, float* acc, const float* grad, 
 }
 void launch_check(hipStream_t s, const uint8_t* data, long nrec, long* first_bad, int nblocks) {
     hipLaunchKernelGGL(k_lstm_check, dim3(nblocks), dim3(256), 0, s, data, nrec, first_bad);
+}
+void launch_check_list(hipStream_t s, const uint8_t* data, const int64_t* list, long n, uint8_t* bad, int nblocks) {
+    hipLaunchKernelGGL(k_lstm_check_list, dim3(nblocks), dim3(256), 0, s, data, list, n, bad);
+}
+
+// trainer group: the same launches, each over all k members
+void launch_group_gather(hipStream_t s, int nb, int k, const LstmMember* tab, const LstmGroupStep& g) {
+    hipLaunchKernelGGL(k_lstm_group_gather, dim3(nb * kSteps, k), dim3(128), 0, s, tab, g);
+}
+void launch_group_fwd(hipStream_t s, int nb, int k, const LstmMember* tab, const LstmOffsets& o) {
+    hipLaunchKernelGGL(k_lstm_group_fwd, dim3((nb + 15) / 16, 3, k), dim3(256), 0, s, tab, o, nb);
+}
+void launch_group_heads_fwd(hipStream_t s, int nb, int k, const LstmMember* tab, const LstmOffsets& o, uint64_t step, int train) {
+    hipLaunchKernelGGL(k_lstm_group_heads_fwd, dim3(nb * kSteps, k), dim3(256), 0, s, tab, o, step, train);
+}
+void launch_group_heads_bwd(hipStream_t s, int nb, int k, const LstmMember* tab, const LstmOffsets& o) {
+    hipLaunchKernelGGL(k_lstm_group_heads_bwd, dim3(nb * kSteps, k), dim3(256), 0, s, tab, o);
+}
+void launch_group_bwd(hipStream_t s, int nb, int k, const LstmMember* tab, const LstmOffsets& o) {
+    hipLaunchKernelGGL(k_lstm_group_bwd, dim3((nb + 15) / 16, 3, k), dim3(256), 0, s, tab, o, nb);
+}
+void launch_group_norm_update(hipStream_t s, int k, const LstmMember* tab, const train::GroupRates& r, long n) {
+    hipLaunchKernelGGL(k_lstm_group_norm, dim3(kNormBlocks, k), dim3(256), 0, s, tab, n);
+    hipLaunchKernelGGL(k_lstm_group_update, dim3(1024, k), dim3(256), 0, s, tab, r, n);
 }
 
 }  // namespace lstm_train

@@ -190,6 +190,25 @@ SIGNATURES = {
     "ethcnn_lstm_train_debug_fetch": (_i, [_vp, _i, _fp, _sz]),
     "ethcnn_lstm_train_debug_rows": (ctypes.c_int64, [_vp]),
     "ethcnn_lstm_train_last_error": (_cp, [_vp]),
+    "ethcnn_lstm_train_group_check": (_i, [ctypes.c_void_p, _i, ctypes.c_char_p, _sz]),
+    "ethcnn_lstm_train_group_keep_list": (_i, [_vp, _sz, ctypes.POINTER(ctypes.c_int), _i, ctypes.POINTER(ctypes.c_int64),
+                                               ctypes.POINTER(ctypes.c_int64)]),
+    "ethcnn_lstm_train_group_create": (_i, [_vp, ctypes.c_void_p, _i, ctypes.POINTER(_vp)]),
+    "ethcnn_lstm_train_group_destroy": (None, [_vp]),
+    "ethcnn_lstm_train_group_init_weights": (_i, [_vp, ctypes.POINTER(ctypes.c_uint64)]),
+    "ethcnn_lstm_train_group_set_blob": (_i, [_vp, _i, _fp, _fp, _sz]),
+    "ethcnn_lstm_train_group_get_blob": (_i, [_vp, _i, _fp, _fp, _sz]),
+    "ethcnn_lstm_train_group_set_qps": (_i, [_vp, _i, ctypes.POINTER(ctypes.c_int), _i]),
+    "ethcnn_lstm_train_group_set_samples": (_i, [_vp, _i, _vp, _sz]),
+    "ethcnn_lstm_train_group_set_samples_from": (_i, [_vp, _i, _vp, _i]),
+    "ethcnn_lstm_train_group_num_samples": (ctypes.c_int64, [_vp, _i, _i]),
+    "ethcnn_lstm_train_group_run": (_i, [_vp, ctypes.c_int64, ctypes.c_int64]),
+    "ethcnn_lstm_train_group_last_stats": (_i, [_vp, _fp, _fp]),
+    "ethcnn_lstm_train_group_step_indices": (_i, [_vp, ctypes.c_int64, ctypes.POINTER(ctypes.c_int32), _i, _fp, _fp]),
+    "ethcnn_lstm_train_group_evaluate": (_i, [_vp, _i, ctypes.POINTER(ctypes.c_int32), ctypes.c_int64, _fp, _fp, _fp]),
+    "ethcnn_lstm_train_group_debug_fetch": (_i, [_vp, _i, _i, _fp, _sz]),
+    "ethcnn_lstm_train_group_debug_rows": (ctypes.c_int64, [_vp, _i]),
+    "ethcnn_lstm_train_group_last_error": (_cp, [_vp]),
     "ethcnn_samples_create": (_i, [_vp, _i, ctypes.POINTER(ctypes.c_int), _i, _i, ctypes.c_uint64, ctypes.POINTER(_vp)]),
     "ethcnn_samples_destroy": (None, [_vp]),
     "ethcnn_samples_last_error": (_cp, [_vp]),
@@ -1423,6 +1442,177 @@ class LstmTrainer(object):
              LDBG_STATE_C: rows * NVEC, LDBG_STATE_H: rows * NVEC}.get(which, 1)
         out = np.empty(n, dtype=np.float32)
         self._chk(self.lib.ethcnn_lstm_train_debug_fetch(self.h, int(which), out.ctypes.data_as(_fp), n))
+        return out
+
+
+def lstm_train_options(batch=64, lr=0.1, momentum=0.9, decay_rate=0.3163, decay_steps=25000, dropout=True, seed=0, qp_scale=1.0,
+                       clip_norm=5.0):
+    """the LstmTrainOptions of LstmTrainer's keyword arguments (an LstmTrainerGroup takes a list of them)"""
+    return LstmTrainOptions(int(batch), float(lr), float(momentum), float(decay_rate), int(decay_steps), 1 if dropout else 0,
+                            int(seed) & _M64, float(qp_scale), float(clip_norm))
+
+
+def _lstm_train_options_array(opts):
+    opts = list(opts)
+    for o in opts:
+        if not isinstance(o, LstmTrainOptions):
+            raise TypeError("an LSTM trainer group takes LstmTrainOptions, got %r" % type(o).__name__)
+    return (LstmTrainOptions * max(len(opts), 1))(*opts), len(opts)
+
+
+def lstm_train_group_check(opts, lib=None):
+    """host-only check of an LSTM trainer group's options (no context): raises EthCnnError(ERR_ARG) naming the member and the field"""
+    lib = lib or load_library()
+    arr, k = _lstm_train_options_array(opts)
+    err = ctypes.create_string_buffer(256)
+    rc = lib.ethcnn_lstm_train_group_check(arr, k, err, len(err))
+    if rc:
+        raise EthCnnError(rc, err.value.decode())
+
+
+def lstm_group_keep_list(records, qps, lib=None):
+    """host only: the records (file order) an LstmTrainerGroup member with the QP list `qps` keeps of a sample file -- the library's
+    own selection, equal to lstm_select_qp(records, qps)"""
+    lib = lib or load_library()
+    buf = np.frombuffer(records, dtype=np.uint8) if isinstance(records, (bytes, bytearray)) else np.ascontiguousarray(records, np.uint8)
+    keep = np.empty(max(buf.size // LSTM_SAMPLE_BYTES, 1), np.int64)
+    n = ctypes.c_int64()
+    arr = (ctypes.c_int * max(1, len(qps)))(*[int(q) for q in qps])
+    rc = lib.ethcnn_lstm_train_group_keep_list(buf.ctypes.data if buf.size else None, buf.size, arr, len(qps),
+                                               keep.ctypes.data_as(ctypes.POINTER(ctypes.c_int64)), ctypes.byref(n))
+    if rc:
+        raise EthCnnError(rc, "%d bytes is not a whole number of %d-byte samples, or a bad QP list" % (buf.size, LSTM_SAMPLE_BYTES))
+    return keep[:n.value].copy()
+
+
+class LstmTrainerGroup(object):
+    """K (1..8) independent ETH-LSTM trainers in every launch of a step (include/ethcnn.h "ETH-LSTM training, several models at
+    once"): one context, one stream, one copy of the sample sets.  Member m computes what LstmTrainer computes with opts[m], its QP
+    list and its own upload of the same samples, bit for bit.  opts: a list of LstmTrainOptions (lstm_train_options(...)) with the
+    same batch.  Sample indices of member m count the samples m keeps."""
+
+    def __init__(self, ctx, opts):
+        self.ctx, self.lib = ctx, ctx.lib
+        arr, k = _lstm_train_options_array(opts)
+        h = ctypes.c_void_p()
+        rc = self.lib.ethcnn_lstm_train_group_create(ctx.h, arr, k, ctypes.byref(h))
+        if rc:
+            raise EthCnnError(rc, self.lib.ethcnn_last_error(ctx.h).decode())
+        self.h, self.k, self.batch = h, k, int(arr[0].batch)
+        self.seeds = [int(arr[m].seed) for m in range(k)]
+        if not hasattr(ctx, "_trainers"):
+            ctx._trainers = weakref.WeakSet()
+        ctx._trainers.add(self)
+
+    def __len__(self):
+        return self.k
+
+    def _chk(self, rc):
+        if rc:
+            raise EthCnnError(rc, self.lib.ethcnn_lstm_train_group_last_error(self.h).decode())
+
+    def close(self):
+        if getattr(self, "h", None):
+            self.lib.ethcnn_lstm_train_group_destroy(self.h)
+            self.h = None
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+    def __enter__(self):
+        return self
+
+    def __exit__(self, *a):
+        self.close()
+
+    def init_weights(self, seeds):
+        """seeds: one per member, or one number for all"""
+        seeds = [seeds] * self.k if np.isscalar(seeds) else list(seeds)
+        if len(seeds) != self.k:
+            raise ValueError("%d seeds for %d members" % (len(seeds), self.k))
+        self._chk(self.lib.ethcnn_lstm_train_group_init_weights(self.h, (ctypes.c_uint64 * self.k)(*[int(x) & _M64 for x in seeds])))
+
+    def set_blob(self, m, blob, accum=None):
+        blob = np.ascontiguousarray(blob, dtype=np.float32)
+        acc = None if accum is None else np.ascontiguousarray(accum, dtype=np.float32)
+        if acc is not None and acc.size != blob.size:
+            raise ValueError("accumulators and blob differ in size")
+        self._chk(self.lib.ethcnn_lstm_train_group_set_blob(self.h, int(m), blob.ctypes.data_as(_fp),
+                                                            None if acc is None else acc.ctypes.data_as(_fp), blob.size))
+
+    def get_blob(self, m, with_accum=False):
+        blob = np.empty(LSTM_BLOB_FLOATS, dtype=np.float32)
+        acc = np.empty(LSTM_BLOB_FLOATS, dtype=np.float32) if with_accum else None
+        self._chk(self.lib.ethcnn_lstm_train_group_get_blob(self.h, int(m), blob.ctypes.data_as(_fp),
+                                                            None if acc is None else acc.ctypes.data_as(_fp), LSTM_BLOB_FLOATS))
+        return (blob, acc) if with_accum else blob
+
+    def set_qps(self, m, qps):
+        """SELECT_QP_LIST of member m for the uploads that follow ([] keeps every sample)"""
+        arr = (ctypes.c_int * max(1, len(qps)))(*[int(q) for q in qps])
+        self._chk(self.lib.ethcnn_lstm_train_group_set_qps(self.h, int(m), arr, len(qps)))
+
+    def set_samples(self, which, records, take=False):
+        """what LstmTrainer.set_samples takes; one copy in HBM serves every member (take=True: an LstmSampleSet's buffer is adopted
+        and the set is empty afterwards); returns the number of samples each member keeps"""
+        if isinstance(records, LstmSampleSet):
+            self._chk(self.lib.ethcnn_lstm_train_group_set_samples_from(self.h, int(which), records.h, 1 if take else 0))
+        else:
+            buf = np.frombuffer(records, dtype=np.uint8) if isinstance(records, (bytes, bytearray)) else np.ascontiguousarray(records, np.uint8)
+            self._chk(self.lib.ethcnn_lstm_train_group_set_samples(self.h, int(which), buf.ctypes.data if buf.size else None, buf.size))
+        return [self.num_samples(m, which) for m in range(self.k)]
+
+    def num_samples(self, m, which):
+        return int(self.lib.ethcnn_lstm_train_group_num_samples(self.h, int(m), int(which)))
+
+    def run(self, first_step, nsteps):
+        """enqueue steps first_step .. first_step + nsteps - 1 of every member (device-drawn batches); returns at once"""
+        self._chk(self.lib.ethcnn_lstm_train_group_run(self.h, int(first_step), int(nsteps)))
+
+    def last_stats(self):
+        """(loss_list [k,3], accuracy_list [k,3]) of the last step enqueued (waits for it)"""
+        l3, a3 = np.zeros((self.k, 3), np.float32), np.zeros((self.k, 3), np.float32)
+        self._chk(self.lib.ethcnn_lstm_train_group_last_stats(self.h, l3.ctypes.data_as(_fp), a3.ctypes.data_as(_fp)))
+        return l3, a3
+
+    def step_indices(self, step, idx):
+        """idx [k, batch], row m in member m's own kept indices"""
+        idx = np.ascontiguousarray(idx, dtype=np.int32)
+        if idx.shape != (self.k, self.batch):
+            raise ValueError("idx must be [%d, %d]" % (self.k, self.batch))
+        l3, a3 = np.zeros((self.k, 3), np.float32), np.zeros((self.k, 3), np.float32)
+        self._chk(self.lib.ethcnn_lstm_train_group_step_indices(self.h, int(step), idx.ctypes.data_as(ctypes.POINTER(ctypes.c_int32)),
+                                                                self.batch, l3.ctypes.data_as(_fp), a3.ctypes.data_as(_fp)))
+        return l3, a3
+
+    def evaluate(self, which, idx=None, n=None, want_probs=False):
+        """(loss_list [k,3], accuracy_list [k,3][, probs [k, 20 n, 21]]): member m over its samples idx[m] (idx [k, n], its own kept
+        indices) or, idx None, its samples 0 .. n-1; per member ONE forward batch"""
+        if idx is not None:
+            idx = np.ascontiguousarray(idx, dtype=np.int32)
+            if idx.ndim != 2 or idx.shape[0] != self.k:
+                raise ValueError("idx must be [%d, n]" % self.k)
+            n = idx.shape[1]
+        if n is None:
+            raise ValueError("evaluate needs idx or n")
+        probs = np.empty((self.k, int(n) * LSTM_STEPS, NOUT), dtype=np.float32) if want_probs else None
+        l3, a3 = np.zeros((self.k, 3), np.float32), np.zeros((self.k, 3), np.float32)
+        self._chk(self.lib.ethcnn_lstm_train_group_evaluate(self.h, int(which),
+                                                            None if idx is None else idx.ctypes.data_as(ctypes.POINTER(ctypes.c_int32)),
+                                                            int(n), l3.ctypes.data_as(_fp), a3.ctypes.data_as(_fp),
+                                                            None if probs is None else probs.ctypes.data_as(_fp)))
+        return (l3, a3, probs) if want_probs else (l3, a3)
+
+    def debug_fetch(self, m, which):
+        rows = int(self.lib.ethcnn_lstm_train_group_debug_rows(self.h, int(m)))
+        n = {LDBG_GRADS: LSTM_BLOB_FLOATS, LDBG_ACCUM: LSTM_BLOB_FLOATS, LDBG_NORM: 1, LDBG_MASK_H: rows * NVEC,
+             LDBG_MASK_FC2: rows * NFC2, LDBG_PROBS: self.batch * LSTM_STEPS * NOUT, LDBG_INDICES: rows // LSTM_STEPS,
+             LDBG_STATE_C: rows * NVEC, LDBG_STATE_H: rows * NVEC}.get(which, 1)
+        out = np.empty(n, dtype=np.float32)
+        self._chk(self.lib.ethcnn_lstm_train_group_debug_fetch(self.h, int(m), int(which), out.ctypes.data_as(_fp), n))
         return out
 
 

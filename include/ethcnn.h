@@ -631,6 +631,54 @@ int ethcnn_lstm_train_debug_fetch(ethcnn_lstm_trainer* tr, int which, float* out
 int64_t ethcnn_lstm_train_debug_rows(const ethcnn_lstm_trainer* tr); /* `rows` of the per-row debug buffers right now */
 const char* ethcnn_lstm_train_last_error(const ethcnn_lstm_trainer* tr);
 
+/* ---- ETH-LSTM training, several models at once: an LSTM trainer GROUP is k (1..8) independent trainers of "ETH-LSTM training" above
+ *      that share a context, its stream, ONE copy of each resident sample set and every launch of a step.  A Low-Delay-P deployment
+ *      needs four models (model_LDP_200000_qp22 .. qp37) that differ only in the samples they keep (slot-0 QP) and in their seeds, and
+ *      read the same sample file.  A step of the group is still 10 launches, each over all members (csrc/ethcnn_lstm_train.h "trainer
+ *      group"); an evaluation is still launches 1-4 over pieces of max(batch, 256) samples, then one loss launch.
+ *   Exactness: member m computes what ethcnn_lstm_train_* computes for a trainer with opts[m], its weights, its QP list and its own
+ *      upload of the same bytes -- bit for bit, whatever k is and wherever in the group the member sits.  The members share the
+ *      records and nothing else: each has its own weights, accumulators, RNG streams (opts[m].seed), batch-global label counts,
+ *      global norm, clip and learning rate.
+ *   Members of one group have the same batch; every other option may differ.  ethcnn_lstm_train_group_check (host only, no context)
+ *      returns ETHCNN_ERR_ARG and a message that names the member and the field for differing batches and for an option
+ *      ethcnn_lstm_train_create refuses; err may be NULL.
+ *   Samples: ethcnn_lstm_train_group_set_qps(member) applies to the uploads that follow, as solo.  An upload keeps, per member, the
+ *      list of the records whose slot-0 QP is in that member's list (file order; an empty list keeps all), and a member's sample
+ *      index i means the i-th record it keeps -- what the solo trainer's index means -- so the index draw over its count gives the solo
+ *      batches.  Only records at least one member keeps go to HBM and through the device validation: an upload returns
+ *      ETHCNN_ERR_FORMAT exactly when some member's own solo upload would, with "member m: " in front of that member's solo message
+ *      (the lowest such m), and ETHCNN_ERR_FORMAT with the member named when a member's selection is empty.  After a failed upload the
+ *      group's previous set is still in place.  ethcnn_lstm_train_group_set_samples_from: take != 0 adopts the set's buffer whatever
+ *      the members keep (the set is empty afterwards), else ONE device-to-device copy.
+ *   Arrays over members are member-major: seeds[k], loss[k][3], acc[k][3], idx[k][n], probs[k][20 n][21].
+ *   A member index outside 0..k-1 is ETHCNN_ERR_ARG. */
+typedef struct ethcnn_lstm_train_group ethcnn_lstm_train_group;
+int ethcnn_lstm_train_group_check(const ethcnn_lstm_train_options* opts, int k, char* err, size_t errcap);
+/* host only: the records (indices, file order) of a sample file that a member with this QP list keeps; keep may be NULL (count only),
+ * else it holds nbytes / 37264 entries.  ERR_FORMAT when nbytes is not a whole number of samples. */
+int ethcnn_lstm_train_group_keep_list(const uint8_t* records, size_t nbytes, const int* qps, int nqps, int64_t* keep, int64_t* nkept);
+int ethcnn_lstm_train_group_create(ethcnn_ctx* ctx, const ethcnn_lstm_train_options* opts, int k, ethcnn_lstm_train_group** out);
+void ethcnn_lstm_train_group_destroy(ethcnn_lstm_train_group* grp); /* before ethcnn_destroy of its context */
+int ethcnn_lstm_train_group_init_weights(ethcnn_lstm_train_group* grp, const uint64_t* seeds /* [k] */);
+int ethcnn_lstm_train_group_set_blob(ethcnn_lstm_train_group* grp, int member, const float* blob, const float* accum /* NULL = zeros */, size_t nfloats);
+int ethcnn_lstm_train_group_get_blob(ethcnn_lstm_train_group* grp, int member, float* blob, float* accum /* may be NULL */, size_t nfloats);
+int ethcnn_lstm_train_group_set_qps(ethcnn_lstm_train_group* grp, int member, const int* qps, int nqps); /* applies to the uploads that follow */
+int ethcnn_lstm_train_group_set_samples(ethcnn_lstm_train_group* grp, int set, const uint8_t* records, size_t nbytes);
+int64_t ethcnn_lstm_train_group_num_samples(const ethcnn_lstm_train_group* grp, int member, int set); /* samples the member keeps */
+/* steps first_step .. first_step + nsteps - 1 of every member, device-drawn batches; asynchronous (nothing read back) */
+int ethcnn_lstm_train_group_run(ethcnn_lstm_train_group* grp, int64_t first_step, int64_t nsteps);
+int ethcnn_lstm_train_group_last_stats(ethcnn_lstm_train_group* grp, float* loss /* [k][3] */, float* acc /* [k][3] */);
+/* one step on explicit batches, n == batch samples per member: idx [k][n], each row in that member's own kept indices; synchronous */
+int ethcnn_lstm_train_group_step_indices(ethcnn_lstm_train_group* grp, int64_t step, const int32_t* idx, int n, float* loss, float* acc);
+/* forward only: member m over its samples idx[m][0..n-1] (its own kept indices), or, idx NULL, over its samples 0 .. n-1 (n must
+ * then be <= every member's count); each member's loss and accuracy lists are those of ONE batch of all its n samples.
+ * probs [k][20 n][21] may be NULL. */
+int ethcnn_lstm_train_group_evaluate(ethcnn_lstm_train_group* grp, int set, const int32_t* idx, int64_t n, float* loss, float* acc, float* probs);
+int ethcnn_lstm_train_group_debug_fetch(ethcnn_lstm_train_group* grp, int member, int which, float* out, size_t nfloats);
+int64_t ethcnn_lstm_train_group_debug_rows(const ethcnn_lstm_train_group* grp, int member);
+const char* ethcnn_lstm_train_group_last_error(const ethcnn_lstm_train_group* grp);
+
 /* ---- sample sets (Extract_Data/extract_data_AI.py:94-170, extract_data_LDP_LDB_RA.py:68-208): the trainers' sample records cut out of
  *      YUV and label files into HBM, handed to a trainer there, or written as the reference's sample files, byte for byte.
  *   Samples are the WHOLE 64 x 64 CTUs of a frame, (height / 64) x (width / 64) of them in raster order (the ragged right and bottom
@@ -738,6 +786,9 @@ int ethcnn_lstm_samples_write(ethcnn_lstm_samples* set, const char* path); /* te
  * and the same validation pass runs on the device.  When the selection keeps every sample and take != 0 the trainer adopts the buffer;
  * else it gets a device-to-device copy of the kept samples.  take != 0: the set is empty afterwards (0 samples, not built). */
 int ethcnn_lstm_train_set_samples_from(ethcnn_lstm_trainer* tr, int set_index, ethcnn_lstm_samples* set, int take);
+/* the same for an LSTM trainer group ("ETH-LSTM training, several models at once"): one buffer serves every member, each through
+ * its own keep list; take != 0 always adopts the buffer */
+int ethcnn_lstm_train_group_set_samples_from(ethcnn_lstm_train_group* grp, int set_index, ethcnn_lstm_samples* set, int take);
 /* MEASUREMENT ENTRIES, not part of the feature's interface: they exist for scripts/lstm_samples_rate.py, may change or go without
  * notice, and nothing should be built on them.  All asynchronous on the context's stream.
  * repack / gather: the two kernels alone, on buffers already in HBM.  repack: the residuals of records first .. first + n - 1 (of
