@@ -5,6 +5,7 @@
 //   ethcnn_host.cpp     host / file entry points: staging ring, worker pool, latency path, streamed pictures, sharded file driver
 //   ethcnn_narrow.cpp   high-bit-depth and non-4:2:0 sources: the source format, the narrowing rule on the host, the device entries
 //   ethcnn_ldp.cpp      config #5: resi vectors, ETH-LSTM step, the per-frame LDP calls, the offline whole-sequence calls
+//   ethcnn_ldp_group.cpp   config #5 offline, group form: K sequences of one geometry through one recurrence launch
 // Mirrors /root/reference/HM-16.5_Test_AI/bin/video_to_cu_depth.py (driver) around net_CNN.py (network).  There is no CPU
 // compute path in this library.
 #pragma once
@@ -299,6 +300,7 @@ int ensure_side_streams(ethcnn_ctx* c);  // copy_in / copy_out / s_tile: created
 hipEvent_t get_event(ethcnn_ctx* c);
 // ethcnn_model.cpp
 int ensure_fast_weights(ethcnn_ctx* c, int plan);
+int upload_lstm_image(ethcnn_ctx* c, const float* blob, float** d_image);  // an LSTM bundle's payload + packed kernels in HBM
 // ethcnn_pass.cpp: the measured stage of the plans' accuracy guard (max |dp| of the plan vs the exact plan on the calibration picture)
 int calibrate_fast_plan(ethcnn_ctx* c, int plan, double* max_abs);
 // ethcnn_pass.cpp
@@ -318,6 +320,10 @@ int ensure_staging(ethcnn_ctx* c, size_t in_bytes, size_t out_bytes, int nbufs =
 bool in_pinned(const ethcnn_ctx* c, const void* p, size_t bytes);
 HostPool* host_pool(ethcnn_ctx* c);  // the context's fill threads (created on first use)
 int pinned_pread(int fd, uint8_t* dst, size_t want, off_t off);  // file bytes -> page-locked memory; 0 or ETHCNN_ERR_IO
+
+// ethcnn_ldp.cpp: the residual vectors of nf frames by the throughput stages, over passes of whole frames (the front-end of the
+// offline sequence calls and of ethcnn_ldp_group.cpp)
+int seq_front(ethcnn_ctx* c, const uint8_t* d_luma, const FrameGeom& g, int nf, float* d_vec);
 
 struct StageTimer {
     ethcnn_ctx* c;

@@ -393,7 +393,7 @@ static int seq_ensure(ethcnn_ctx* c, int w, int h, int64_t nframes, int64_t F, b
 }
 
 // the residual vectors of nf frames: the throughput stages ethcnn_resi_vectors_device falls back to, over passes of whole frames
-static int seq_front(ethcnn_ctx* c, const uint8_t* d_luma, const FrameGeom& g, int nf, float* d_vec) {
+int seq_front(ethcnn_ctx* c, const uint8_t* d_luma, const FrameGeom& g, int nf, float* d_vec) {
     int rc = ensure_workspace(c, (int)std::min<int64_t>((int64_t)g.nctu * nf, c->max_ctus), 1);
     if (rc) return rc;
     for (const Pass& p : plan_passes(g.nctu, nf, c->max_ctus)) {

@@ -21,6 +21,24 @@ void launch_lstm_seq(const float* d_vec, const float* d_state_in, float* d_state
                      int qp, int i_frame0, float* d_probs, hipStream_t s);
 void launch_lstm_seq_gates(float* d_probs, int n, int nframes, float thr1, float thr2, hipStream_t s);
 
+// ---- group form (ethcnn_ldp_group.cpp): K <= kLstmSeqGroupMax independent sequences of one geometry, one run of frames and one
+// i_frame0 share the two launches.  A member brings what differs: its vectors, states, bundle image, probabilities and QP feature
+// (lstm_seq_efs0(qp): the expression of launch_lstm_seq).  The blocks of member m run the body of launch_lstm_seq on m's pointers, so
+// every member's result is that launch's, bit for bit; the rule for state_in == state_out above holds per member, and no member's
+// buffers may overlap another member's outputs.  launch_lstm_seq_gates_group: the gate pass over every member's probabilities.
+constexpr int kLstmSeqGroupMax = 8;
+struct SeqMember {
+    const float* vec;       // [F][n][448]
+    const float* state_in;  // [n][2][448] or null
+    float* state_out;       // [n][2][448]
+    const float* blob;      // the member's bundle image: payload + packed kernels
+    float* probs;           // [F][n][21]
+    float efs0;
+};
+inline float lstm_seq_efs0(int qp) { return ((float)qp / 51.0f) * 0.18f; }
+void launch_lstm_seq_group(const SeqMember* members, int k, int n, int nframes, int i_frame0, hipStream_t s);
+void launch_lstm_seq_gates_group(float* const* d_probs, int k, int n, int nframes, float thr1, float thr2, hipStream_t s);
+
 // dependent v_mfma_f32_16x16x4_f32 links per frame of the wave that owns a hidden tile (its four gate chains are interleaved), and of
 // the head waves, per level (64, 32, 16): what scripts/ldp_sequence_rate.py holds against the measured link latency
 constexpr int kLstmSeqChainLinks[3] = {2 * 64 / 4, 2 * 128 / 4, 2 * 256 / 4};

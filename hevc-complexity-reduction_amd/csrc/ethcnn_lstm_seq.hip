@@ -292,11 +292,58 @@ void launch_lstm_seq(const float* d_vec, const float* d_state_in, float* d_state
     hipLaunchKernelGGL(k_lstm_seq, dim3(blocks), dim3(64 * kSeqWaves), 0, s, P);
 }
 
+// ---- group form: K independent sequences of one geometry in the same launch.  The kernel only chooses whose SeqParams a block works
+// on and calls the body above.  Linear grid, level-major, the member index fastest: [level 16: G x K][level 32: ceil(G / 2) x K]
+// [level 64: ceil(G / 4) x K] -- when K x blocks exceeds the compute units every member's long chains are dispatched first, as in the
+// solo kernel.  The member table travels by value in the kernel arguments (404 bytes; the member index is block-uniform, so a block
+// reads its row with scalar loads): no device copy that would have to be kept current with bundles and buffers.  No block reads
+// what another member's block writes; a member's state_in and state_out may be the same buffer under the rule of ethcnn_lstm_seq.h.
+struct SeqGroupParams {
+    SeqMember m[kLstmSeqGroupMax];
+    int k, n, groups, F;
+    int i_frame0;
+};
+
+__global__ __launch_bounds__(1024) void k_lstm_seq_group(SeqGroupParams G) {
+    __shared__ f32x4 smem[kSeqWaves * 3 * 64 + ((192 + 5) * 16 + 16) / 4];
+    const int K = G.k, n2 = G.groups * K, n1 = ((G.groups + 1) / 2) * K;
+    const int b = (int)blockIdx.x;
+    const int r = b < n2 ? b : (b < n2 + n1 ? b - n2 : b - n2 - n1);  // position inside the level
+    const int blk = r / K;
+    const SeqMember& M = G.m[r - blk * K];
+    SeqParams P;
+    P.vec = M.vec;
+    P.state_in = M.state_in;
+    P.state_out = M.state_out;
+    P.blob = M.blob;
+    P.probs = M.probs;
+    P.n = G.n;
+    P.groups = G.groups;
+    P.F = G.F;
+    P.i_frame0 = G.i_frame0;
+    P.efs0 = M.efs0;
+    if (b < n2) lstm_seq_level<2>(P, blk, smem);
+    else if (b < n2 + n1) lstm_seq_level<1>(P, blk, smem);
+    else lstm_seq_level<0>(P, blk, smem);
+}
+
+void launch_lstm_seq_group(const SeqMember* members, int k, int n, int nframes, int i_frame0, hipStream_t s) {
+    SeqGroupParams G;
+    for (int m = 0; m < kLstmSeqGroupMax; ++m) G.m[m] = members[m < k ? m : 0];
+    G.k = k;
+    G.n = n;
+    G.groups = (n + 15) / 16;
+    G.F = nframes;
+    G.i_frame0 = i_frame0;
+    const unsigned blocks = (unsigned)(k * (G.groups + (G.groups + 1) / 2 + (G.groups + 3) / 4));
+    hipLaunchKernelGGL(k_lstm_seq_group, dim3(blocks), dim3(64 * kSeqWaves), 0, s, G);
+}
+
 // ---- gates: the tf.cond pair of net():305,317 per (frame, mini-batch of 1024 CTUs).  One block owns the mini-batch: it reduces the
 // two predicates over the UNGATED probabilities (any y64 > thr1; any y32 > thr2) and zero-fills what the per-frame launch's last
 // block zero-fills: y32 and y16 when the first gate is closed, y16 when the second is -- which, behind a closed first gate, sees
 // zeros and is open only if 0 > thr2.
-__global__ __launch_bounds__(256) void k_lstm_seq_gates(float* __restrict__ probs, int n, int chunks, float thr1, float thr2) {
+__device__ __forceinline__ void lstm_seq_gates_body(float* __restrict__ probs, int n, int chunks, float thr1, float thr2) {
     const int frame = (int)blockIdx.x / chunks, c0 = ((int)blockIdx.x - frame * chunks) * kSubBatch, cnt = min(n - c0, kSubBatch);
     float* const p = probs + ((size_t)frame * n + c0) * kNOut;
     int a32 = 0, a16 = 0;
@@ -315,9 +362,28 @@ __global__ __launch_bounds__(256) void k_lstm_seq_gates(float* __restrict__ prob
     }
 }
 
+__global__ __launch_bounds__(256) void k_lstm_seq_gates(float* __restrict__ probs, int n, int chunks, float thr1, float thr2) {
+    lstm_seq_gates_body(probs, n, chunks, thr1, thr2);
+}
+
+// group form: grid (frames x mini-batches, K); the member is blockIdx.y, the body above runs over its probabilities
+struct SeqGateGroup {
+    float* probs[kLstmSeqGroupMax];
+};
+__global__ __launch_bounds__(256) void k_lstm_seq_gates_group(SeqGateGroup Q, int n, int chunks, float thr1, float thr2) {
+    lstm_seq_gates_body(Q.probs[blockIdx.y], n, chunks, thr1, thr2);
+}
+
 void launch_lstm_seq_gates(float* d_probs, int n, int nframes, float thr1, float thr2, hipStream_t s) {
     const unsigned chunks = (unsigned)((n + kSubBatch - 1) / kSubBatch);
     hipLaunchKernelGGL(k_lstm_seq_gates, dim3(chunks * (unsigned)nframes), dim3(256), 0, s, d_probs, n, (int)chunks, thr1, thr2);
+}
+
+void launch_lstm_seq_gates_group(float* const* d_probs, int k, int n, int nframes, float thr1, float thr2, hipStream_t s) {
+    SeqGateGroup Q;
+    for (int m = 0; m < kLstmSeqGroupMax; ++m) Q.probs[m] = d_probs[m < k ? m : 0];
+    const unsigned chunks = (unsigned)((n + kSubBatch - 1) / kSubBatch);
+    hipLaunchKernelGGL(k_lstm_seq_gates_group, dim3(chunks * (unsigned)nframes, (unsigned)k), dim3(256), 0, s, Q, n, (int)chunks, thr1, thr2);
 }
 
 }  // namespace ethcnn

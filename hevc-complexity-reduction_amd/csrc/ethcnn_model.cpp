@@ -228,17 +228,24 @@ extern "C" int ethcnn_get_blob(const ethcnn_ctx* c, float* out, size_t nfloats) 
 }
 
 // ------------------------------------------------ config #5: ETH-LSTM one step -------
-static int upload_lstm(ethcnn_ctx* c) {
+// the device image of an LSTM bundle: the payload as stored, and behind it the LSTMCell kernels in the cell kernel's load order.
+// *d_image is allocated on first use and rewritten in place afterwards (the device is idle while it changes).  Shared by the
+// context's own bundle and the members of an ethcnn_ldp_group.
+int upload_lstm_image(ethcnn_ctx* c, const float* blob, float** d_image) {
     HIPCHK(c, hipSetDevice(c->device));
-    if (!c->d_lstm) HIPCHK(c, hipMalloc((void**)&c->d_lstm, (kLstmBlobFloats + kLstmPackFloats) * sizeof(float)));
-    std::vector<float> pack(kLstmPackFloats);  // the LSTMCell kernels in the cell kernel's load order, behind the blob
-    pack_lstm_kernels(c->lstm_blob.data(), pack.data());
+    if (!*d_image) HIPCHK(c, hipMalloc((void**)d_image, (kLstmBlobFloats + kLstmPackFloats) * sizeof(float)));
+    std::vector<float> pack(kLstmPackFloats);
+    pack_lstm_kernels(blob, pack.data());
     HIPCHK(c, hipDeviceSynchronize());
-    HIPCHK(c, hipMemcpyAsync(c->d_lstm, c->lstm_blob.data(), kLstmBlobFloats * sizeof(float), hipMemcpyHostToDevice,
-                             c->stream));
-    HIPCHK(c, hipMemcpyAsync(c->d_lstm + kLstmBlobFloats, pack.data(), kLstmPackFloats * sizeof(float), hipMemcpyHostToDevice,
-                             c->stream));
+    HIPCHK(c, hipMemcpyAsync(*d_image, blob, kLstmBlobFloats * sizeof(float), hipMemcpyHostToDevice, c->stream));
+    HIPCHK(c, hipMemcpyAsync(*d_image + kLstmBlobFloats, pack.data(), kLstmPackFloats * sizeof(float), hipMemcpyHostToDevice, c->stream));
     HIPCHK(c, hipStreamSynchronize(c->stream));
+    return ETHCNN_OK;
+}
+
+static int upload_lstm(ethcnn_ctx* c) {
+    const int rc = upload_lstm_image(c, c->lstm_blob.data(), &c->d_lstm);
+    if (rc) return rc;
     c->have_lstm = true;
     return ETHCNN_OK;
 }

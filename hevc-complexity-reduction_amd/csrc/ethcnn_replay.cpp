@@ -3,6 +3,7 @@
 // calibrator and the partition-search simulator.  Kernels: ethcnn_replay.hip.
 #include "ethcnn_ctx.h"
 #include "ethcnn_calib.h"
+#include "ethcnn_ldp_group.h"
 #include "ethcnn_replay.h"
 #include "ethcnn_samples.h"
 #include "ethcnn_sim.h"
@@ -241,10 +242,10 @@ struct Need {
     size_t rec, resi, src, probs, labels, zero;
     unsigned long long total() const { return (unsigned long long)rec + resi + src + probs + labels + zero; }
 };
-Need need_of(const ethcnn_replay* p, const Run& r, bool own_probs, bool own_labels) {
+Need need_of(const ethcnn_replay* p, const Run& r, bool own_probs, bool own_labels, int nslots = 1) {
     Need n;
     n.rec = p->own ? (size_t)p->nrec * kRec : 0;
-    n.resi = (size_t)(chunk_frames(p, r) * r.nctu) * 4096;
+    n.resi = (size_t)nslots * (size_t)(chunk_frames(p, r) * r.nctu) * 4096;  // the chunk's planes of every slot replayed together
     n.src = (size_t)(r.F * r.nctu) * 8;
     n.probs = own_probs ? (size_t)(r.F * r.nctu) * kNOut * 4 : 0;
     n.labels = own_labels ? (size_t)(r.F * r.nctu) * 16 : 0;
@@ -256,6 +257,58 @@ int check_run(ethcnn_replay* p, int run, int slot) {
     if (p->plan.runs.empty()) return rerr(p, ETHCNN_ERR_ARG, "nothing is open (ethcnn_replay_open_set / ethcnn_replay_open_records)");
     if (run < 0 || run >= (int)p->plan.runs.size()) return rerr(p, ETHCNN_ERR_ARG, "run %d outside 0..%d", run, (int)p->plan.runs.size() - 1);
     if (slot < 0 || slot > 3) return rerr(p, ETHCNN_ERR_ARG, "QP slot %d outside 0..3", slot);
+    return 0;
+}
+
+// the object's buffers at exactly the sizes of `nd` (what is held is what was checked), and the run's source table in HBM; refuses
+// with the whole sum before it allocates what it cannot get
+int ensure_run(ethcnn_replay* p, int run, const Need& nd) {
+    ethcnn_ctx* c = p->c;
+    const Run& r = p->plan.runs[(size_t)run];
+    const unsigned long long total = nd.total();
+    if (p->max_bytes && total > p->max_bytes)
+        return rerr(p, ETHCNN_ERR_NOMEM, "run %d (%lld frames of %lld CTUs) needs %llu bytes on the device, above the object's limit of %llu", run, (long long)r.F,
+                    (long long)r.nctu, total, (unsigned long long)p->max_bytes);
+    // buffers of exactly this run's sizes: what is held is what was checked
+    const size_t want[5] = {nd.resi, nd.src, nd.probs, nd.labels, nd.zero};
+    size_t* cap[5] = {&p->resi_cap, &p->src_cap, &p->probs_cap, &p->labels_cap, &p->zero_cap};
+    void** buf[5] = {(void**)&p->d_resi, (void**)&p->d_src, (void**)&p->d_probs, (void**)&p->d_labels, (void**)&p->d_zero};
+    size_t grow = 0, back = 0;
+    for (int k = 0; k < 5; ++k)
+        if (*cap[k] != want[k]) grow += want[k], back += *cap[k];
+    if (grow || back) {
+        size_t free_b = 0, total_b = 0;
+        if (hipMemGetInfo(&free_b, &total_b) != hipSuccess) return rerr(p, ETHCNN_ERR_DEVICE, "hipMemGetInfo failed");
+        if (grow > free_b + back)
+            return rerr(p, ETHCNN_ERR_NOMEM, "run %d (%lld frames of %lld CTUs) needs %llu bytes on the device; %zu are free", run, (long long)r.F,
+                        (long long)r.nctu, total, free_b + back);
+        if (hipStreamSynchronize(c->stream) != hipSuccess) return rerr(p, ETHCNN_ERR_DEVICE, "hipStreamSynchronize failed");
+        for (int k = 0; k < 5; ++k)
+            if (*cap[k] != want[k]) {
+                if (*buf[k]) (void)hipFree(*buf[k]);
+                *buf[k] = nullptr;
+                *cap[k] = 0;
+                if (k == 1) p->src_run = -1;
+            }
+        for (int k = 0; k < 5; ++k)
+            if (want[k] && !*buf[k]) {
+                if (hipMalloc(buf[k], want[k]) != hipSuccess) {
+                    (void)hipGetLastError();
+                    *buf[k] = nullptr;
+                    return rerr(p, ETHCNN_ERR_NOMEM, "run %d (%lld frames of %lld CTUs) needs %llu bytes on the device: %zu of them do not fit", run,
+                                (long long)r.F, (long long)r.nctu, total, want[k]);
+                }
+                *cap[k] = want[k];
+                if (k == 4 && hipMemsetAsync(*buf[k], 0, want[k], c->stream) != hipSuccess) return rerr(p, ETHCNN_ERR_DEVICE, "hipMemsetAsync failed");
+            }
+    }
+    c->done_armed = 0;
+    if (p->src_run != run) {
+        p->src_run = -1;
+        const hipError_t e = hipMemcpyAsync(p->d_src, p->plan.src.data() + r.src_at, nd.src, hipMemcpyHostToDevice, c->stream);
+        if (e != hipSuccess) return rerr(p, ETHCNN_ERR_DEVICE, "upload of the source table: %s", hipGetErrorString(e));
+        p->src_run = run;
+    }
     return 0;
 }
 
@@ -432,52 +485,8 @@ extern "C" int ethcnn_replay_run_device(ethcnn_replay* p, int run, int slot, flo
     if (!c->have_lstm)
         return rerr(p, ETHCNN_ERR_NOWEIGHTS, "the context has no ETH-LSTM bundle loaded for QP %d of slot %d (ethcnn_load_lstm_checkpoint / ethcnn_load_lstm_blob)", r.qp[slot], slot);
     if (hipSetDevice(c->device) != hipSuccess) return rerr(p, ETHCNN_ERR_DEVICE, "hipSetDevice(%d) failed", c->device);
-    const Need nd = need_of(p, r, d_probs == nullptr, d_labels == nullptr);
-    const unsigned long long total = nd.total();
-    if (p->max_bytes && total > p->max_bytes)
-        return rerr(p, ETHCNN_ERR_NOMEM, "run %d (%lld frames of %lld CTUs) needs %llu bytes on the device, above the object's limit of %llu", run, (long long)r.F,
-                    (long long)r.nctu, total, (unsigned long long)p->max_bytes);
-    // buffers of exactly this run's sizes: what is held is what was checked
-    const size_t want[5] = {nd.resi, nd.src, nd.probs, nd.labels, nd.zero};
-    size_t* cap[5] = {&p->resi_cap, &p->src_cap, &p->probs_cap, &p->labels_cap, &p->zero_cap};
-    void** buf[5] = {(void**)&p->d_resi, (void**)&p->d_src, (void**)&p->d_probs, (void**)&p->d_labels, (void**)&p->d_zero};
-    size_t grow = 0, back = 0;
-    for (int k = 0; k < 5; ++k)
-        if (*cap[k] != want[k]) grow += want[k], back += *cap[k];
-    if (grow || back) {
-        size_t free_b = 0, total_b = 0;
-        if (hipMemGetInfo(&free_b, &total_b) != hipSuccess) return rerr(p, ETHCNN_ERR_DEVICE, "hipMemGetInfo failed");
-        if (grow > free_b + back)
-            return rerr(p, ETHCNN_ERR_NOMEM, "run %d (%lld frames of %lld CTUs) needs %llu bytes on the device; %zu are free", run, (long long)r.F,
-                        (long long)r.nctu, total, free_b + back);
-        if (hipStreamSynchronize(c->stream) != hipSuccess) return rerr(p, ETHCNN_ERR_DEVICE, "hipStreamSynchronize failed");
-        for (int k = 0; k < 5; ++k)
-            if (*cap[k] != want[k]) {
-                if (*buf[k]) (void)hipFree(*buf[k]);
-                *buf[k] = nullptr;
-                *cap[k] = 0;
-                if (k == 1) p->src_run = -1;
-            }
-        for (int k = 0; k < 5; ++k)
-            if (want[k] && !*buf[k]) {
-                if (hipMalloc(buf[k], want[k]) != hipSuccess) {
-                    (void)hipGetLastError();
-                    *buf[k] = nullptr;
-                    return rerr(p, ETHCNN_ERR_NOMEM, "run %d (%lld frames of %lld CTUs) needs %llu bytes on the device: %zu of them do not fit", run,
-                                (long long)r.F, (long long)r.nctu, total, want[k]);
-                }
-                *cap[k] = want[k];
-                if (k == 4 && hipMemsetAsync(*buf[k], 0, want[k], c->stream) != hipSuccess) return rerr(p, ETHCNN_ERR_DEVICE, "hipMemsetAsync failed");
-            }
-    }
-    c->done_armed = 0;
+    if (int rc = ensure_run(p, run, need_of(p, r, d_probs == nullptr, d_labels == nullptr))) return rc;
     hipError_t e = hipSuccess;
-    if (p->src_run != run) {
-        p->src_run = -1;
-        e = hipMemcpyAsync(p->d_src, p->plan.src.data() + r.src_at, nd.src, hipMemcpyHostToDevice, c->stream);
-        if (e != hipSuccess) return rerr(p, ETHCNN_ERR_DEVICE, "upload of the source table: %s", hipGetErrorString(e));
-        p->src_run = run;
-    }
     float* probs = d_probs ? d_probs : p->d_probs;
     uint8_t* labels = d_labels ? d_labels : p->d_labels;
     const int64_t Fc = chunk_frames(p, r);
@@ -493,6 +502,60 @@ extern "C" int ethcnn_replay_run_device(ethcnn_replay* p, int run, int slot, flo
         const int rc = ethcnn_ldp_sequence_device(c, p->d_resi, W, H, W, (ptrdiff_t)W * H, nf, r.qp[slot], (int)(r.f0 + (uint32_t)at),
                                                   at == 0 && r.f0 > 1 ? p->d_zero : nullptr, probs + at * r.nctu * kNOut);
         if (rc) return rerr(p, rc, "run %d, frames %lld..%lld: %s", run, (long long)(r.f0 + at), (long long)(r.f0 + at + nf - 1), ethcnn_last_error(c));
+    }
+    return ETHCNN_OK;
+}
+
+extern "C" int64_t ethcnn_replay_run_group_bytes(ethcnn_replay* p, int run, int nslots) {
+    if (!p) return ETHCNN_ERR_ARG;
+    if (int rc = check_run(p, run, 0)) return rc;
+    if (nslots < 1 || nslots > kLstmSeqGroupMax) return rerr(p, ETHCNN_ERR_ARG, "%d slots (1..%d)", nslots, kLstmSeqGroupMax);
+    return (int64_t)need_of(p, p->plan.runs[(size_t)run], false, false, nslots).total();
+}
+
+extern "C" int ethcnn_replay_run_group_device(ethcnn_replay* p, int run, int nslots, const int* slots, ethcnn_ldp_group* grp, float* const* d_probs,
+                                              uint8_t* const* d_labels) {
+    if (!p) return ETHCNN_ERR_ARG;
+    if (int rc = check_run(p, run, 0)) return rc;
+    if (!grp || !slots || !d_probs || !d_labels) return rerr(p, ETHCNN_ERR_ARG, "ethcnn_replay_run_group_device: null pointer");
+    if (grp->c != p->c) return rerr(p, ETHCNN_ERR_ARG, "the group lives on another context");
+    if (nslots != grp->k) return rerr(p, ETHCNN_ERR_ARG, "%d slots for a group of %d members", nslots, grp->k);
+    for (int j = 0; j < nslots; ++j) {
+        if (int rc = check_run(p, run, slots[j])) return rc;
+        if (!d_probs[j] || !d_labels[j]) return rerr(p, ETHCNN_ERR_ARG, "ethcnn_replay_run_group_device: null output buffer (slot %d)", slots[j]);
+        if (((uintptr_t)d_probs[j] | (uintptr_t)d_labels[j]) % 4) return rerr(p, ETHCNN_ERR_ARG, "output buffers are 4-byte aligned");
+    }
+    ethcnn_ctx* c = p->c;
+    const Run& r = p->plan.runs[(size_t)run];
+    if (!c->have_weights) return rerr(p, ETHCNN_ERR_NOWEIGHTS, "the context has no residual CNN loaded (ethcnn_load_checkpoint / ethcnn_load_blob)");
+    for (int j = 0; j < nslots; ++j)
+        if (!grp->m[j].have)
+            return rerr(p, ETHCNN_ERR_NOWEIGHTS, "member %d of the group has no ETH-LSTM bundle loaded for QP %d of slot %d", j, r.qp[slots[j]], slots[j]);
+    if (hipSetDevice(c->device) != hipSuccess) return rerr(p, ETHCNN_ERR_DEVICE, "hipSetDevice(%d) failed", c->device);
+    if (int rc = ensure_run(p, run, need_of(p, r, false, false, nslots))) return rc;
+    const int64_t Fc = chunk_frames(p, r);
+    const int W = 64 * r.C, H = 64 * r.R;
+    const size_t plane_chunk = (size_t)(Fc * r.nctu) * 4096;  // slot j's planes of a chunk start at j * plane_chunk
+    const uint8_t* luma[kLstmSeqGroupMax];
+    const float* zero[kLstmSeqGroupMax];
+    float* probs[kLstmSeqGroupMax];
+    int qp[kLstmSeqGroupMax];
+    for (int j = 0; j < nslots; ++j) luma[j] = p->d_resi + (size_t)j * plane_chunk, zero[j] = p->d_zero, qp[j] = r.qp[slots[j]];
+    for (int64_t at = 0; at < r.F; at += Fc) {
+        const int nf = (int)std::min<int64_t>(Fc, r.F - at);
+        c->done_armed = 0;
+        for (int j = 0; j < nslots; ++j) {
+            launch_uncut(c->stream, p->rec, (long)p->nrec, p->d_src + at * r.nctu, nf, r.R, r.C, slots[j], p->d_resi + (size_t)j * plane_chunk,
+                         d_labels[j] + at * r.nctu * 16, cus_of(c));
+            probs[j] = d_probs[j] + at * r.nctu * kNOut;
+        }
+        const hipError_t e = hipGetLastError();
+        if (e != hipSuccess) return rerr(p, ETHCNN_ERR_DEVICE, "uncut: %s", hipGetErrorString(e));
+        // the first chunk starts from zeros (the object's zero state when its frame number is above 1); the following ones from the
+        // states the call before left resident in the group
+        const int rc = ethcnn_ldp_group_sequence_device(grp, luma, W, H, W, (ptrdiff_t)W * H, nf, qp, (int)(r.f0 + (uint32_t)at),
+                                                        at == 0 && r.f0 > 1 ? zero : nullptr, probs);
+        if (rc) return rerr(p, rc, "run %d, frames %lld..%lld: %s", run, (long long)(r.f0 + at), (long long)(r.f0 + at + nf - 1), ethcnn_ldp_group_last_error(grp));
     }
     return ETHCNN_OK;
 }

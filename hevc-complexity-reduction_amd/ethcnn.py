@@ -105,6 +105,19 @@ SIGNATURES = {
     "ethcnn_ldp_predict_yuv_file": (_i, [_vp, _cp, _i, _i, _i, _cp, ctypes.c_int64, ctypes.c_int64]),
     "ethcnn_ldp_set_sequence_chunk": (_i, [_vp, _i]),
     "ethcnn_ldp_sequence_bytes": (ctypes.c_int64, [_i, _i, _i, _i]),
+    "ethcnn_ldp_group_create": (_i, [_vp, _i, ctypes.POINTER(_vp)]),
+    "ethcnn_ldp_group_destroy": (None, [_vp]),
+    "ethcnn_ldp_group_last_error": (_cp, [_vp]),
+    "ethcnn_ldp_group_count": (_i, [_vp]),
+    "ethcnn_ldp_group_load_lstm_checkpoint": (_i, [_vp, _i, _cp]),
+    "ethcnn_ldp_group_load_lstm_blob": (_i, [_vp, _i, _fp, _sz]),
+    "ethcnn_ldp_group_load_lstm_synthetic": (_i, [_vp, _i, ctypes.c_uint64, ctypes.c_double]),
+    "ethcnn_ldp_group_get_lstm_blob": (_i, [_vp, _i, _fp, _sz]),
+    "ethcnn_ldp_group_sequence_device": (_i, [_vp, _vp, _i, _i, _pd, _pd, _i, ctypes.POINTER(_i), _i, _vp, _vp]),
+    "ethcnn_ldp_group_get_state": (_i, [_vp, _i, _fp, _sz]),
+    "ethcnn_ldp_group_state_ctus": (ctypes.c_int64, [_vp, _i]),
+    "ethcnn_ldp_group_set_chunk": (_i, [_vp, _i]),
+    "ethcnn_ldp_group_bytes": (ctypes.c_int64, [_i, _i, _i, _i, _i]),
     "ethcnn_ldp_step_begin": (_i, [_vp, _vp, _i, _i, _pd, _i, _i, _vp, _fp]),
     "ethcnn_rows_ready": (_i, [_vp, _i, _i]),
     "ethcnn_predict_luma_begin": (_i, [_vp, _vp, _i, _i, _i, _fp]),
@@ -290,6 +303,8 @@ SIGNATURES = {
     "ethcnn_replay_set_chunk_frames": (_i, [_vp, _i]),
     "ethcnn_replay_run_bytes": (ctypes.c_int64, [_vp, _i, _i, _i]),
     "ethcnn_replay_run_device": (_i, [_vp, _i, _i, _vp, _vp]),
+    "ethcnn_replay_run_group_bytes": (ctypes.c_int64, [_vp, _i, _i]),
+    "ethcnn_replay_run_group_device": (_i, [_vp, _i, _i, ctypes.POINTER(_i), _vp, _vp, _vp]),
     "ethcnn_replay_feed_calib": (_i, [_vp, _i, _i, _vp]),
     "ethcnn_replay_feed_sim": (_i, [_vp, _i, _i, _vp]),
 }
@@ -404,6 +419,12 @@ def host_thread_budget(local_workers=1, usable_cpus=0):
 def ldp_sequence_bytes(width, height, nframes, chunk_frames=0):
     """device bytes an ldp_sequence call holds for that chunk size (ethcnn_ldp_sequence_bytes; host only); negative = bad arguments"""
     return int(load_library().ethcnn_ldp_sequence_bytes(int(width), int(height), int(nframes), int(chunk_frames)))
+
+
+def ldp_group_bytes(width, height, nframes, chunk_frames=0, k=1):
+    """device bytes an LdpGroup.sequence_device call of k members holds for that chunk size (ethcnn_ldp_group_bytes; host only), the
+    k bundle images apart; negative = bad arguments"""
+    return int(load_library().ethcnn_ldp_group_bytes(int(width), int(height), int(nframes), int(chunk_frames), int(k)))
 
 
 def source_frame_bytes(width, height, bit_depth=8, chroma=420):
@@ -2300,6 +2321,126 @@ class Pacer(object):
         return res[0]
 
 
+# ------------------------------------------------------------------------------------- config #5 offline, group form ---
+def _ptr_array(bufs):
+    """DeviceBuffers / raw device addresses / None -> a C array of pointers"""
+    vals = [None if b is None else getattr(b, "ptr", b) for b in bufs]
+    return (ctypes.c_void_p * max(len(vals), 1))(*vals)
+
+
+class LdpGroup(object):
+    """K = 1..8 Low-Delay-P residual sequences of one geometry through one recurrence launch (include/ethcnn.h "config #5 offline,
+    group form"): each member has its own ETH-LSTM bundle, QP, resident state and output, and its result equals
+    EthCnn.ldp_sequence_device on a context that holds its bundle, bit for bit.  The residual CNN and the thresholds are the
+    context's; the context's own LSTM bundle and resident state are not touched."""
+
+    def __init__(self, ctx, k):
+        self.ctx, self.lib = ctx, ctx.lib
+        h = ctypes.c_void_p()
+        ctx._chk(self.lib.ethcnn_ldp_group_create(ctx.h, int(k), ctypes.byref(h)))
+        self.h = h
+        if not hasattr(ctx, "_trainers"):
+            ctx._trainers = weakref.WeakSet()
+        ctx._trainers.add(self)  # closed with the context, before it
+
+    def _chk(self, rc):
+        if rc:
+            raise EthCnnError(rc, self.lib.ethcnn_ldp_group_last_error(self.h).decode())
+
+    def close(self):
+        if getattr(self, "h", None):
+            self.lib.ethcnn_ldp_group_destroy(self.h)
+            self.h = None
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+    def __enter__(self):
+        return self
+
+    def __exit__(self, *a):
+        self.close()
+
+    def __len__(self):
+        return max(0, int(self.lib.ethcnn_ldp_group_count(self.h)))
+
+    def load_lstm_checkpoint(self, m, prefix):
+        self._chk(self.lib.ethcnn_ldp_group_load_lstm_checkpoint(self.h, int(m), os.fsencode(prefix)))
+
+    def load_lstm_blob(self, m, blob):
+        blob = np.ascontiguousarray(blob, dtype=np.float32)
+        self._chk(self.lib.ethcnn_ldp_group_load_lstm_blob(self.h, int(m), blob.ctypes.data_as(_fp), blob.size))
+
+    def load_lstm_synthetic(self, m, seed=1, head_gain=1.0):
+        self._chk(self.lib.ethcnn_ldp_group_load_lstm_synthetic(self.h, int(m), int(seed), float(head_gain)))
+
+    def get_lstm_blob(self, m):
+        out = np.empty(LSTM_BLOB_FLOATS, dtype=np.float32)
+        self._chk(self.lib.ethcnn_ldp_group_get_lstm_blob(self.h, int(m), out.ctypes.data_as(_fp), out.size))
+        return out
+
+    def set_chunk_frames(self, frames):
+        self._chk(self.lib.ethcnn_ldp_group_set_chunk(self.h, int(frames)))
+
+    def state_ctus(self, m):
+        """the CTU count of member m's resident state (0: none)"""
+        n = int(self.lib.ethcnn_ldp_group_state_ctus(self.h, int(m)))
+        self._chk(n if n < 0 else 0)
+        return n
+
+    def get_state(self, m):
+        """member m's resident (c, h) state -> float32 [nctu, 2, 448]"""
+        state = np.empty((self.state_ctus(m), 2, NVEC), dtype=np.float32)
+        self._chk(self.lib.ethcnn_ldp_group_get_state(self.h, int(m), state.ctypes.data_as(_fp), state.size))
+        return state
+
+    def sequence_device(self, d_lumas, width, height, nframes, qps, i_frame_first, d_probs, d_state_ins=None, pitch=None, frame_stride=None):
+        """asynchronous on the context's stream (ethcnn_ldp_group_sequence_device): one luma buffer, QP and probability buffer per
+        member (DeviceBuffers or raw device addresses); d_state_ins: None, or one entry per member of which any may be None"""
+        k = len(self)
+        if len(d_lumas) != k or len(qps) != k or len(d_probs) != k or (d_state_ins is not None and len(d_state_ins) != k):
+            raise ValueError("sequence_device takes one entry per member (%d)" % k)
+        pitch = width if pitch is None else pitch
+        frame_stride = pitch * height if frame_stride is None else frame_stride
+        self._chk(self.lib.ethcnn_ldp_group_sequence_device(self.h, _ptr_array(d_lumas), width, height, pitch, frame_stride, int(nframes),
+                                                            (ctypes.c_int * k)(*[int(q) for q in qps]), int(i_frame_first),
+                                                            None if d_state_ins is None else _ptr_array(d_state_ins), _ptr_array(d_probs)))
+
+    def sequence(self, lumas, width, height, qps, i_frame_first=1, state_ins=None):
+        """lumas: one uint8 array [nframes, height, width] per member, in host memory -> a list of probs [nframes, nctu, 21].  The
+        inputs are uploaded to DeviceBuffers and the results downloaded (a convenience for small inputs: a job keeps its frames in HBM
+        and calls sequence_device).  state_ins: None, or per member None / float32 [nctu, 2, 448]."""
+        k, n = len(self), ctus_per_frame(width, height)
+        lumas = [np.ascontiguousarray(a, dtype=np.uint8).reshape(-1, height, width) for a in lumas]
+        if len(lumas) != k or len(set(a.shape[0] for a in lumas)) != 1:
+            raise ValueError("sequence takes %d inputs of one frame count" % k)
+        nframes = lumas[0].shape[0]
+        bufs = []
+        alloc = lambda nbytes: bufs.append(DeviceBuffer(self.ctx, max(int(nbytes), 4))) or bufs[-1]
+        try:
+            d_l, d_p, d_s = [], [], None
+            for a in lumas:
+                d_l.append(alloc(a.nbytes))
+                d_l[-1].upload(a)
+                d_p.append(alloc(nframes * n * NOUT * 4))
+            if state_ins is not None:
+                d_s = []
+                for st in state_ins:
+                    d_s.append(None)
+                    if st is not None:
+                        d_s[-1] = alloc(n * 2 * NVEC * 4)
+                        d_s[-1].upload(np.ascontiguousarray(st, dtype=np.float32).reshape(n, 2, NVEC))
+            self.sequence_device(d_l, width, height, nframes, qps, i_frame_first, d_p, d_s)
+            return [b.download(np.float32, nframes * n * NOUT).reshape(nframes, n, NOUT) for b in d_p]
+        finally:
+            self.ctx.synchronize()
+            for b in bufs:
+                b.free()
+
+
 # ------------------------------------------------------------------------------------------------------ sample-set replay ---
 class ReplayRun(ctypes.Structure):
     _fields_ = [("seq", ctypes.c_int32), ("w", ctypes.c_int32), ("h", ctypes.c_int32), ("rows", ctypes.c_int32), ("cols", ctypes.c_int32),
@@ -2443,6 +2584,39 @@ class Replay(object):
             dp.free()
             dl.free()
         return probs, labels
+
+    def run_group_bytes(self, i, nslots):
+        """device bytes run_group_device holds for run i with nslots slots replayed together (the group's own memory apart)"""
+        n = int(self.lib.ethcnn_replay_run_group_bytes(self.h, int(i), int(nslots)))
+        self._chk(n if n < 0 else 0)
+        return n
+
+    def run_group_device(self, i, slots, group, d_probs, d_labels):
+        """asynchronous on the context's stream: run i at every listed QP slot through an LdpGroup (member j takes slots[j] with that
+        slot's QP and the bundle loaded into member j); d_probs[j] float32 [frames, nctu, 21] and d_labels[j] uint8 [frames, 4 rows,
+        4 cols] in HBM (DeviceBuffers or raw addresses), one each per slot"""
+        slots = [int(x) for x in slots]
+        if len(d_probs) != len(slots) or len(d_labels) != len(slots):
+            raise ValueError("run_group_device takes one probability and one label buffer per slot")
+        self._chk(self.lib.ethcnn_replay_run_group_device(self.h, int(i), len(slots), (ctypes.c_int * max(len(slots), 1))(*slots), group.h,
+                                                          _ptr_array(d_probs), _ptr_array(d_labels)))
+
+    def run_group(self, i, slots, group):
+        """-> [(probs float32 [frames, nctu, 21], labels uint8 [frames, 4 rows, 4 cols])] in host memory, one pair per listed slot"""
+        r = self.run_info(i)
+        n = r["frames"] * r["nctu"]
+        bufs = []
+        try:
+            for _ in slots:
+                bufs.append((DeviceBuffer(self.ctx, n * NOUT * 4), DeviceBuffer(self.ctx, n * 16)))
+            self.run_group_device(i, slots, group, [b[0] for b in bufs], [b[1] for b in bufs])
+            return [(dp.download(np.float32, n * NOUT).reshape(r["frames"], r["nctu"], NOUT),
+                     dl.download(np.uint8, n * 16).reshape(r["frames"], 4 * r["rows"], 4 * r["cols"])) for dp, dl in bufs]
+        finally:
+            self.ctx.synchronize()
+            for dp, dl in bufs:
+                dp.free()
+                dl.free()
 
     def feed(self, consumer, runs=None, slot=None, qp=None):
         """replays the listed runs (None: all) at `slot`, or at the slot of each run that holds `qp`, into a Calibrator or a

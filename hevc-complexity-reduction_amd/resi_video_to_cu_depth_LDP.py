@@ -2,6 +2,7 @@
 
     resi_video_to_cu_depth_LDP.py <resi.yuv> <width> <height> <qp> [--first-frame 1] [--frames N] [--out cu_depth.dat]
                                   [--state-out state.dat] [--model-dir DIR] [--device 0] [--chunk FRAMES]
+                                  [--also RESI_YUV QP OUT]... [--piece-frames FRAMES]
 
 <resi.yuv> is the whole-sequence 4:2:0 residual file HM-16.5_Resi_Pre writes per QP: frame k of the file is POC k.  POC 0 is the intra
 picture and has no residual, so the first frame is 1 unless a later one is asked for (--first-frame > 1 needs the state of the frames
@@ -11,6 +12,14 @@ frame after frame when it carries its state through the sequence, bit for bit.  
 them: model_LDP_2000000_qp22~37.dat and the model_LDP_200000_qpXX.dat of the QP band from --model-dir (default: the directory of
 this command's caller, '.'); ETHCNN_SYNTHETIC_SEED / ETHCNN_HEAD_GAIN select seeded weights where a checkpoint is missing.
 Score the result with tools/score_cu_depth.py --skip-label-frames <first>.
+
+--also RESI_YUV QP OUT (repeatable, up to seven) predicts further residual files of the same frame size and frame count in the same
+run: the resi_XX.yuv of the other QPs of a sequence.  Each gets the model_LDP_200000_qpXX.dat of its own QP band and its own output
+file; all of them share every recurrence launch (LdpGroup), and each output is byte for byte what a run of its own writes.  Luma is
+read in pieces of --piece-frames frames (default 0: as many frames as hold 64 MB of luma per sequence) and the states stay resident
+from piece to piece.  --state-out is the first sequence's.  Every output is written to a temp file; when all sequences are done the
+temp files are renamed one after another and --state-out is written last, so a rename that fails (status 1) leaves the outputs renamed
+before it in place and complete, the others and --state-out absent.
 """
 import argparse
 import os
@@ -35,6 +44,83 @@ def _fail(msg):
     return 1
 
 
+def group_members(a):
+    """[(yuv, qp, out)] of a parsed command line: the positional sequence first, then every --also"""
+    members = [(a.yuv, a.qp, a.out)]
+    for yuv, qp, out in a.also or []:
+        try:
+            members.append((yuv, int(qp), out))
+        except ValueError:
+            raise ValueError("--also %s %s %s: QP is not a number" % (yuv, qp, out))
+    if len(members) > 8:
+        raise ValueError("%d sequences: a run takes the positional one and up to seven --also" % len(members))
+    outs = [os.path.abspath(m[2]) for m in members]
+    if len(set(outs)) != len(outs):
+        raise ValueError("two sequences write the same output file")
+    return members
+
+
+def restore_member_lstm(group, m, qp, model_dir):
+    """restore_lstm of the daemon for member m of a group"""
+    prefix = os.path.join(model_dir, _e.lstm_model_name_for_qp(qp))
+    seed = os.environ.get('ETHCNN_SYNTHETIC_SEED')
+    if os.path.exists(prefix + '.data-00000-of-00001') or seed is None:
+        group.load_lstm_checkpoint(m, prefix)
+        return prefix
+    group.load_lstm_synthetic(m, int(seed), float(os.environ.get('ETHCNN_HEAD_GAIN', '1.0')))
+    return 'synthetic(seed=%s)' % seed
+
+
+def run_group(ctx, a, members, nframes):
+    """several sequences through one LdpGroup: luma is read with numpy a piece of frames at a time, every piece goes through the
+    device entry, the resident states carry each sequence on; every output is written to a temp file and renamed at the end"""
+    k, n = len(members), _e.ctus_per_frame(a.width, a.height)
+    plane, frame_bytes = a.width * a.height, a.width * a.height * 3 // 2
+    piece = max(1, min(nframes, a.piece_frames if a.piece_frames > 0 else (64 << 20) // plane))
+    tmps = ["%s.tmp.%d" % (m[2], os.getpid()) for m in members]
+    files, bufs = [], []
+    try:
+        with _e.LdpGroup(ctx, k) as group:
+            for m, (_, qp, _) in enumerate(members):
+                print("LSTM model %d (QP %d): %s" % (m, qp, restore_member_lstm(group, m, qp, a.model_dir)))
+            group.set_chunk_frames(a.chunk)
+            maps = [np.memmap(m[0], dtype=np.uint8, mode="r") for m in members]
+            files = [open(t, "wb") for t in tmps]
+            d_l = [ctx.alloc(piece * plane) for _ in range(k)]
+            d_p = [ctx.alloc(piece * n * _e.NOUT * 4) for _ in range(k)]
+            bufs = d_l + d_p
+            luma = np.empty((piece, plane), np.uint8)
+            t0 = time.time()
+            for f0 in range(0, nframes, piece):
+                nf = min(piece, nframes - f0)
+                for m in range(k):
+                    for t in range(nf):  # luma only: the chroma planes are never read
+                        at = (a.first_frame + f0 + t) * frame_bytes
+                        luma[t] = maps[m][at: at + plane]
+                    d_l[m].upload(luma[:nf])
+                group.sequence_device(d_l, a.width, a.height, nf, [m[1] for m in members], a.first_frame + f0, d_p)
+                for m in range(k):
+                    d_p[m].download(np.float32, nf * n * _e.NOUT).astype("<f4").tofile(files[m])
+            dt = time.time() - t0
+            print("Predicting Time: %.3f sec. (%d sequences, %d frames, %d CTUs each)" % (dt, k, nframes, n))
+            state = group.get_state(0) if a.state_out else None
+        for f in files:
+            f.close()
+        files = []
+        for t, m in zip(tmps, members):
+            os.replace(t, m[2])
+        return state
+    finally:
+        ctx.synchronize()
+        for b in bufs:
+            b.free()
+        for f in files:
+            f.close()
+        for t in tmps:
+            if os.path.exists(t):
+                os.remove(t)
+
+
 def main(argv):
     ap = argparse.ArgumentParser(prog="resi_video_to_cu_depth_LDP.py", description=__doc__, formatter_class=argparse.RawDescriptionHelpFormatter)
     ap.add_argument("yuv")
@@ -48,6 +134,8 @@ def main(argv):
     ap.add_argument("--model-dir", default=".")
     ap.add_argument("--device", type=int, default=0)
     ap.add_argument("--chunk", type=int, default=0)
+    ap.add_argument("--also", nargs=3, action="append", metavar=("RESI_YUV", "QP", "OUT"))
+    ap.add_argument("--piece-frames", type=int, default=0)
     try:
         a = ap.parse_args(argv[1:])
     except SystemExit as e:
@@ -70,13 +158,32 @@ def main(argv):
     if a.chunk < 0:
         return _fail("--chunk %d" % a.chunk)
     try:
+        members = group_members(a)
+    except ValueError as e:
+        return _fail(str(e))
+    for yuv, _, _ in members[1:]:
+        if not os.path.isfile(yuv):
+            return _fail("cannot read %s" % yuv)
+        if os.path.getsize(yuv) != size:
+            return _fail("%s holds %s frames of %dx%d, %s holds %d: the sequences of one run have one frame size and one frame count"
+                         % (yuv, "%g" % (os.path.getsize(yuv) / frame_bytes), a.width, a.height, a.yuv, total))
+    if a.piece_frames < 0:
+        return _fail("--piece-frames %d" % a.piece_frames)
+    try:
         ctx = _e.EthCnn(device=a.device)
         try:
             print("CNN  model: %s" % restore_cnn(ctx, a.model_dir))
-            print("LSTM model: %s" % restore_lstm(ctx, a.qp, a.model_dir))
             thr = os.path.join(a.model_dir, "Thr_info.txt")
             if os.path.exists(thr):
                 ctx.load_thresholds(thr)
+            if len(members) > 1:
+                state = run_group(ctx, a, members, nframes)
+                if a.state_out:
+                    tmp = "%s.tmp.%d" % (a.state_out, os.getpid())
+                    np.ascontiguousarray(state, dtype="<f4").tofile(tmp)
+                    os.replace(tmp, a.state_out)
+                return 0
+            print("LSTM model: %s" % restore_lstm(ctx, a.qp, a.model_dir))
             ctx.ldp_set_sequence_chunk(a.chunk)
             t0 = time.time()
             ctx.ldp_predict_yuv_file(a.yuv, a.width, a.height, a.qp, a.out, a.first_frame, a.first_frame + nframes)

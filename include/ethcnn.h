@@ -285,6 +285,54 @@ int ethcnn_ldp_predict_yuv_file(ethcnn_ctx* ctx, const char* resi_yuv_path, int 
                                 int64_t frame_begin, int64_t frame_end);
 int ethcnn_ldp_set_sequence_chunk(ethcnn_ctx* ctx, int frames);
 int64_t ethcnn_ldp_sequence_bytes(int width, int height, int nframes, int chunk_frames);
+/* ---- config #5 offline, group form: K = 1..8 residual sequences of ONE geometry, length and first frame number through the chain together.
+ *      HM-16.5_Resi_Pre writes one resi_XX.yuv per QP of a sequence and every record of an inter sample file carries four QP slots: the
+ *      members of a group are such sequences, each with its own ETH-LSTM bundle, QP, state and output.
+ *      DEFINITION: for every member m, d_probs[m] and m's resident state EQUAL what ethcnn_ldp_sequence_device gives on a context that
+ *      holds m's bundle, for d_luma[m], qp[m] and the same remaining arguments (d_state_in[m] for d_state_in), bit for bit, gates and
+ *      their zero patterns included.  The residual CNN, the thresholds and the stream are the context's; the context's own LSTM bundle,
+ *      resident LDP state and sequence buffers are neither used nor changed.
+ *      What differs is the schedule: the front-end runs per member and chunk as in the solo call; the recurrence of a run of frames is
+ *      ONE launch for all members (level-major block order: every member's long chains first), the gates of a chunk ONE launch.
+ *      Geometry, nframes and i_frame_first are common, so all members split into runs at the same frames (i_frame <= 1).
+ *   ethcnn_ldp_group_create       k members on ctx (ETHCNN_ERR_ARG outside 1..8; text: ethcnn_last_error of the context).  Destroy the
+ *                                 group before its context.  Errors of every other entry: ethcnn_ldp_group_last_error.
+ *   ethcnn_ldp_group_load_lstm_checkpoint / _load_lstm_blob / _load_lstm_synthetic   member m's bundle, as the context's loaders take
+ *                                 theirs (a blob holds exactly the floats of ethcnn_get_lstm_blob, else ETHCNN_ERR_ARG and the member
+ *                                 keeps what it had).  Each member keeps its own device image, payload + packed kernels (6.05 MB),
+ *                                 from load time on.  ethcnn_ldp_group_get_lstm_blob returns the payload.
+ *   ethcnn_ldp_group_sequence_device   d_luma, qp, d_probs: arrays of k entries; d_state_in: NULL, or an array of k entries of which
+ *                                 any may be NULL.  Device pointers, asynchronous on the context's stream.  Each member has ONE resident
+ *                                 state buffer, owned by the group and advanced in place; input state of member m's frame 0 when
+ *                                 i_frame_first > 1: d_state_in[m] when given, else m's resident state (the error of ethcnn_ldp_step,
+ *                                 ETHCNN_ERR_ARG, if it is empty or belongs to another CTU count).  No member's d_probs or d_state_in
+ *                                 may overlap another's d_probs.  Refused before anything is allocated or enqueued, states left as
+ *                                 they were: an open streamed call (ETHCNN_ERR_ARG), no CNN weights, a member without a bundle
+ *                                 (ETHCNN_ERR_NOWEIGHTS, the text names the member), a null pointer, bad geometry, nframes <= 0,
+ *                                 i_frame_first < 0 (ETHCNN_ERR_ARG).  A failure after that point drops every member's resident state.
+ *   ethcnn_ldp_group_get_state    member m's resident state, float32 [nctu][2][448]; synchronous
+ *   ethcnn_ldp_group_state_ctus   the CTU count of member m's resident state; 0: none; negative: bad arguments
+ *   ethcnn_ldp_group_set_chunk    frames per chunk; 0 = default (256 MB of vectors for the whole group).  Results do not depend on it.
+ *   ethcnn_ldp_group_bytes        host only, no context: the device bytes a call holds, F = min(nframes, chunk or default) frames:
+ *                                 k F nctu 448 x 4 (vectors) + k x roundup16(nctu) x 896 x 4 (the resident states); negative for bad
+ *                                 arguments.  Beside it, from load time: k bundle images.  A call that cannot get its buffers fails
+ *                                 with ETHCNN_ERR_NOMEM and this sum in the message, before anything is allocated or enqueued. */
+typedef struct ethcnn_ldp_group ethcnn_ldp_group;
+int ethcnn_ldp_group_create(ethcnn_ctx* ctx, int k, ethcnn_ldp_group** out);
+void ethcnn_ldp_group_destroy(ethcnn_ldp_group* grp);
+const char* ethcnn_ldp_group_last_error(const ethcnn_ldp_group* grp);
+int ethcnn_ldp_group_count(const ethcnn_ldp_group* grp);
+int ethcnn_ldp_group_load_lstm_checkpoint(ethcnn_ldp_group* grp, int m, const char* prefix);
+int ethcnn_ldp_group_load_lstm_blob(ethcnn_ldp_group* grp, int m, const float* blob, size_t nfloats);
+int ethcnn_ldp_group_load_lstm_synthetic(ethcnn_ldp_group* grp, int m, uint64_t seed, double head_gain);
+int ethcnn_ldp_group_get_lstm_blob(ethcnn_ldp_group* grp, int m, float* out, size_t nfloats);
+int ethcnn_ldp_group_sequence_device(ethcnn_ldp_group* grp, const uint8_t* const* d_luma, int width, int height, ptrdiff_t pitch,
+                                     ptrdiff_t frame_stride, int nframes, const int* qp, int i_frame_first,
+                                     const float* const* d_state_in /* NULL, or entries NULL */, float* const* d_probs);
+int ethcnn_ldp_group_get_state(ethcnn_ldp_group* grp, int m, float* state_out, size_t nfloats /* nctu * 896 */);
+int64_t ethcnn_ldp_group_state_ctus(ethcnn_ldp_group* grp, int m);
+int ethcnn_ldp_group_set_chunk(ethcnn_ldp_group* grp, int frames);
+int64_t ethcnn_ldp_group_bytes(int width, int height, int nframes, int chunk_frames, int k);
 /* Pinned (page-locked) host memory: buffers a caller fills itself (file reads) and hands to the host entry points are
  * DMA-able directly, without the runtime's pageable staging copy.  ethcnn_ldp_step goes further: a luma / probs pointer that
  * lies inside such a buffer is read / written by the kernels IN PLACE (no copy launch at all); so does ethcnn_predict_luma for ONE
@@ -1222,6 +1270,20 @@ int64_t ethcnn_replay_run_bytes(ethcnn_replay* rp, int run, int own_probs, int o
 /* Uncut, then the sequence call, chunk by chunk.  d_probs float32 [F][nctu][21] and d_labels uint8 [F][4 R][4 C] in HBM; either may be
  * NULL: the object's own buffer is used then.  Asynchronous on the context's stream. */
 int ethcnn_replay_run_device(ethcnn_replay* rp, int run, int slot, float* d_probs, uint8_t* d_labels);
+/* Several slots of a run through an ethcnn_ldp_group (config #5 offline, group form) of the same context: per chunk the uncut kernel runs
+ * once per listed slot, then ONE group call runs on the chunk's planes with member j at slot slots[j] and that slot's QP; the bundle of
+ * member j is the caller's choice, as the context's is for ethcnn_replay_run_device.  nslots must equal the group's member count; a slot
+ * may be listed more than once.  d_probs[j] float32 [F][nctu][21] and d_labels[j] uint8 [F][4 R][4 C] in HBM, all given.  Per slot the
+ * outputs equal ethcnn_replay_run_device(rp, run, slots[j], ...) on a context with member j's bundle, word for word; chunked equals
+ * unchunked.  The states travel in the group's resident buffers; the context's resident LDP state stays as it is.
+ * Memory: ethcnn_replay_run_group_bytes = nslots x Fc nctu 4096 (the chunk's planes of every slot) + F nctu 8 + nctu 3584 when f0 > 1
+ * + the copy of the records; held against max_bytes and the free device memory as ethcnn_replay_run_bytes is.  Outside the sum: what
+ * the group holds (ethcnn_ldp_group_bytes).  The object keeps its buffers at exactly the sizes of the last call: a caller that alternates
+ * this entry and ethcnn_replay_run_device on one run frees and reallocates the plane buffer and waits for the stream at every switch
+ * (the results are the same; replay one way, then the other).  Asynchronous on the context's stream. */
+int64_t ethcnn_replay_run_group_bytes(ethcnn_replay* rp, int run, int nslots);
+int ethcnn_replay_run_group_device(ethcnn_replay* rp, int run, int nslots, const int* slots, ethcnn_ldp_group* grp, float* const* d_probs,
+                                   uint8_t* const* d_labels);
 /* ethcnn_replay_run_device into the object's own buffers, then ethcnn_calib_add_frames_device / ethcnn_sim_add_frames_device with
  * width = 64 C, height = 64 R, skip_label_frames = 0: nothing goes through the host.  Synchronous, as those entries are. */
 int ethcnn_replay_feed_calib(ethcnn_replay* rp, int run, int slot, ethcnn_calib* cal);
