@@ -17,11 +17,17 @@
 //               one byte permute per output dword that picks the low bytes of four samples.
 //   stores      one dwordx4 per lane; bytes [width, roundup16(width)) of a row are written as zero, nothing behind them is touched.
 // No LDS, no atomics, every output byte has one writer.
+//
+// The device form of the rule (narrow2, pack4, narrow8 below) is shared with the deep cut kernel of the sample sets (k_cut_ai16,
+// ethcnn_samples_kernels.hip), which narrows while it cuts: one statement of the arithmetic for both kernels.
 #pragma once
 #include <cstddef>
 #include <cstdint>
 
 #include <hip/hip_runtime_api.h>
+#if defined(__HIPCC__)
+#include <hip/hip_runtime.h>  // the device inlines at the end
+#endif
 
 namespace ethcnn {
 namespace narrow {
@@ -38,6 +44,29 @@ void launch_narrow(hipStream_t s, const uint8_t* src, int width, int height, lon
 // host form of the rule over n samples; nt: non-temporal stores (the destination is page-locked staging memory that the DMA engine
 // reads next, never this CPU).  SSE2 body + scalar tail; scalar alone where the host ISA has no SSE2.
 void narrow_row(const uint16_t* src, uint8_t* dst, size_t n, int shift, bool nt);
+
+#if defined(__HIPCC__)
+typedef unsigned short u16x2 __attribute__((ext_vector_type(2)));
+
+// two samples of a dword: min(s >> shift, 255) in each half (v_pk_lshrrev_b16, v_pk_min_u16)
+__device__ __forceinline__ uint32_t narrow2(uint32_t d, int shift) {
+    u16x2 v = __builtin_bit_cast(u16x2, d);
+    v = v >> (u16x2)((unsigned short)shift);
+    v = __builtin_elementwise_min(v, (u16x2)((unsigned short)255));
+    return __builtin_bit_cast(uint32_t, v);
+}
+
+// the low bytes of the four narrowed samples in two dwords (lo: samples 0 and 1, hi: 2 and 3) as one output dword (v_perm_b32)
+__device__ __forceinline__ uint32_t pack4(uint32_t lo, uint32_t hi) { return __builtin_amdgcn_perm(hi, lo, 0x06040200u); }
+
+// 16 samples in eight source dwords -> their 16 narrowed bytes
+__device__ __forceinline__ uint4 narrow8(const uint32_t (&w)[8], int shift) {
+    uint32_t s[8];
+#pragma unroll
+    for (int i = 0; i < 8; ++i) s[i] = narrow2(w[i], shift);
+    return make_uint4(pack4(s[0], s[1]), pack4(s[2], s[3]), pack4(s[4], s[5]), pack4(s[6], s[7]));
+}
+#endif
 
 }  // namespace narrow
 }  // namespace ethcnn

@@ -12,8 +12,6 @@ namespace {
 constexpr int kThreads = 256, kWaves = kThreads / 64;
 constexpr int kFlight = 2;  // units a wave has in flight (the loads of both before the stores of either)
 
-typedef unsigned short u16x2 __attribute__((ext_vector_type(2)));
-
 // 16 source bytes at the 16-byte aligned p of a row of which `left` bytes (even; may be <= 0) lie at and behind p: whole dwords
 // below the row's end, then one 16-bit load when it ends on half a dword; what does not exist reads as zero
 __device__ __forceinline__ uint4 load16_left(const uint8_t* p, long left) {
@@ -28,14 +26,6 @@ __device__ __forceinline__ uint4 load16_left(const uint8_t* p, long left) {
     return make_uint4(w[0], w[1], w[2], w[3]);
 }
 
-// two samples of a dword: min(s >> shift, 255) in each half (v_pk_lshrrev_b16, v_pk_min_u16)
-__device__ __forceinline__ uint32_t narrow2(uint32_t d, int shift) {
-    u16x2 v = __builtin_bit_cast(u16x2, d);
-    v = v >> (u16x2)((unsigned short)shift);
-    v = __builtin_elementwise_min(v, (u16x2)((unsigned short)255));
-    return __builtin_bit_cast(uint32_t, v);
-}
-
 // 32 source bytes (16 samples) out of the three aligned words around them -> 16 narrowed bytes; Q = whole dwords and half = whether
 // a further 16 bits lie between the aligned boundary and the first sample
 template <int Q>
@@ -43,11 +33,8 @@ __device__ __forceinline__ uint4 narrow16(const uint4 a, const uint4 b, const ui
     const uint32_t w[12] = {a.x, a.y, a.z, a.w, b.x, b.y, b.z, b.w, c.x, c.y, c.z, c.w};
     uint32_t s[8];
 #pragma unroll
-    for (int i = 0; i < 8; ++i) s[i] = narrow2(half ? (w[Q + i] >> 16 | w[Q + i + 1] << 16) : w[Q + i], shift);
-    uint32_t o[4];
-#pragma unroll
-    for (int i = 0; i < 4; ++i) o[i] = __builtin_amdgcn_perm(s[2 * i + 1], s[2 * i], 0x06040200u);  // the low bytes of four samples
-    return make_uint4(o[0], o[1], o[2], o[3]);
+    for (int i = 0; i < 8; ++i) s[i] = half ? (w[Q + i] >> 16 | w[Q + i + 1] << 16) : w[Q + i];
+    return narrow8(s, shift);  // (ethcnn_narrow.h)
 }
 
 // unit u = (frame * height + row) * chunks + chunk: segments [64 chunk, 64 chunk + 64) of that row, one per lane

@@ -83,9 +83,11 @@ struct Staging {
     }
 };
 
-// geometry + alignment checks of one cut, then the launch (asynchronous on the context's stream)
+// geometry + alignment checks of one cut, then the launch (asynchronous on the context's stream).  bps = 2 (All-Intra only): the luma
+// holds 16-bit samples, pitch and frame stride stay in bytes, and the records take min(s >> shift, 255)
 int cut(ethcnn_ctx* c, std::string* why, int kind, const int* qps, int nqps, int w, int h, int nframes, const uint8_t* const* luma,
-        const ptrdiff_t* pitch, const ptrdiff_t* fstride, const uint8_t* const* labels, int frame0, int seq, uint8_t* out) {
+        const ptrdiff_t* pitch, const ptrdiff_t* fstride, const uint8_t* const* labels, int frame0, int seq, uint8_t* out, int bps = 1,
+        int shift = 0) {
     char buf[256];
     const int nplanes = kind == kKindAi ? 1 : 4;
     auto bad = [&](const char* m) {
@@ -101,9 +103,13 @@ int cut(ethcnn_ctx* c, std::string* why, int kind, const int* qps, int nqps, int
     if ((uintptr_t)out % (kind == kKindAi ? 16 : 4)) return bad("the record buffer must be 16-byte (inter: 4-byte) aligned");
     CutArgs a{};
     uintptr_t bits = 0, lbits = 0;
+    const ptrdiff_t row_bytes = (ptrdiff_t)w * bps;
     for (int p = 0; p < nplanes; ++p) {
-        if (!luma[p] || pitch[p] < w || (nframes > 1 && fstride[p] < pitch[p] * (ptrdiff_t)(h / 64 * 64 - 1) + w))
-            return bad("null plane, pitch below the width or frame stride below a frame");
+        if (!luma[p] || pitch[p] < row_bytes || (nframes > 1 && fstride[p] < pitch[p] * (ptrdiff_t)(h / 64 * 64 - 1) + row_bytes))
+            return bad(bps == 1 ? "null plane, pitch below the width or frame stride below a frame"
+                                : "null plane, pitch below 2 * width bytes or frame stride below a frame");
+        if (bps == 2 && (((uintptr_t)luma[p] | (uintptr_t)pitch[p] | (uintptr_t)fstride[p]) & 1))
+            return bad("16-bit luma must be 2-byte aligned, with an even pitch and an even frame stride in bytes");
         a.luma[p] = luma[p];
         a.pitch[p] = (long)pitch[p];
         a.fstride[p] = (long)fstride[p];
@@ -127,6 +133,8 @@ int cut(ethcnn_ctx* c, std::string* why, int kind, const int* qps, int nqps, int
     a.frame0 = frame0;
     a.seq = seq;
     a.out = out;
+    a.deep = bps == 2;
+    a.shift = shift;
     c->done_armed = 0;  // the context's completion word does not cover this launch
     launch_cut(c->stream, kind, a, (bits & 15) == 0 ? 16 : ((bits & 3) == 0 ? 4 : 1), c->cus > 0 ? c->cus : 256);
     if (hipGetLastError() != hipSuccess) {
@@ -185,17 +193,30 @@ extern "C" int ethcnn_samples_add_sequence(ethcnn_samples* s, int w, int h, cons
     if (w < 64 || h < 64 || w % 8 || h % 8 || w > 65535 || h > 65535)  // read_info_frame asserts the multiple of 8; below 64 there is no whole CTU
         return serr(s, ETHCNN_ERR_FORMAT, "%s: frame size %dx%d: width and height must be multiples of 8, 64..65535", yuv_paths[0], w, h);
     if (s->kind == kKindInter && s->seqs.size() >= 65536) return serr(s, ETHCNN_ERR_ARG, "more than 65536 sequences (the header holds 16 bits)");
-    const int64_t frame_bytes = (int64_t)w * h * 3 / 2, label_bytes = (int64_t)(h / 16) * (w / 16);
+    const ethcnn_source_format fmt{s->bit_depth, s->chroma};
+    const bool plain = fmt.bit_depth == 8 && fmt.chroma_format == 420;
+    int64_t luma_bytes = 0, frame_bytes = 0;
+    if (ethcnn_source_frame_bytes(&fmt, w, h, &luma_bytes, &frame_bytes) != ETHCNN_OK)
+        return serr(s, ETHCNN_ERR_ARG, "%s: no %dx%d frame of whole planes at %d bits, chroma format %d", yuv_paths[0], w, h, fmt.bit_depth,
+                    fmt.chroma_format);
+    const int64_t label_bytes = (int64_t)(h / 16) * (w / 16);
     ethcnn_samples::Seq q;
     q.w = w;
     q.h = h;
+    q.bit_depth = fmt.bit_depth;
+    q.chroma = fmt.chroma_format;
+    q.luma_bytes = luma_bytes;
+    q.frame_bytes = frame_bytes;
     q.frames = -1;
     struct stat st;
     for (int i = 0; i < nyuv; ++i) {
         if (stat(yuv_paths[i], &st) != 0) return serr(s, ETHCNN_ERR_IO, "cannot stat %s: %s", yuv_paths[i], std::strerror(errno));
-        if (st.st_size % frame_bytes)
+        if (st.st_size % frame_bytes && plain)
             return serr(s, ETHCNN_ERR_FORMAT, "%s: size %lld is not a multiple of the %dx%d 4:2:0 frame size %lld", yuv_paths[i],
                         (long long)st.st_size, w, h, (long long)frame_bytes);
+        if (st.st_size % frame_bytes)
+            return serr(s, ETHCNN_ERR_FORMAT, "%s: size %lld is not a multiple of the %dx%d frame size %lld at %d bits, chroma format %d (ethcnn_samples_set_source_format)",
+                        yuv_paths[i], (long long)st.st_size, w, h, (long long)frame_bytes, fmt.bit_depth, fmt.chroma_format);
         const int64_t n = st.st_size / frame_bytes;
         if (q.frames >= 0 && n != q.frames)
             return serr(s, ETHCNN_ERR_FORMAT, "%s holds %lld frames, %s holds %lld", yuv_paths[i], (long long)n, yuv_paths[0], (long long)q.frames);
@@ -216,6 +237,42 @@ extern "C" int ethcnn_samples_add_sequence(ethcnn_samples* s, int w, int h, cons
     s->count += q.nrec;
     s->seqs.push_back(q);
     return ETHCNN_OK;
+}
+
+extern "C" int ethcnn_samples_set_source_format(ethcnn_samples* s, const ethcnn_source_format* fmt) {
+    if (!s) return ETHCNN_ERR_ARG;
+    if (!fmt) return serr(s, ETHCNN_ERR_ARG, "ethcnn_samples_set_source_format: null format");
+    if (s->built) return serr(s, ETHCNN_ERR_ARG, "the set is built: the source format belongs to the sequences added before ethcnn_samples_build");
+    if (ethcnn_source_frame_bytes(fmt, 2, 2, nullptr, nullptr) != ETHCNN_OK)  // (the one place that knows the formats)
+        return serr(s, ETHCNN_ERR_ARG, "ethcnn_samples_set_source_format: bit depth %d / chroma format %d (8..16; 400, 420, 422 or 444)", fmt->bit_depth,
+                    fmt->chroma_format);
+    if (s->kind == kKindInter && (fmt->bit_depth != 8 || fmt->chroma_format != 420))
+        return serr(s, ETHCNN_ERR_ARG, "an inter set reads HM's residual files, which are always 8-bit 4:2:0: source format %d bits / chroma format %d refused",
+                    fmt->bit_depth, fmt->chroma_format);
+    s->bit_depth = fmt->bit_depth;
+    s->chroma = fmt->chroma_format;
+    return ETHCNN_OK;
+}
+
+extern "C" int ethcnn_samples_cut16_device(ethcnn_ctx* c, const int* qps, int nqps, int width, int height, int nframes, const uint16_t* d_luma16,
+                                           ptrdiff_t pitch_bytes, ptrdiff_t frame_stride_bytes, int bit_depth, const uint8_t* const* d_labels,
+                                           uint8_t* d_records, int64_t record_offset) {
+    if (!c) return ETHCNN_ERR_ARG;
+    std::string why;
+    int rc = check_qps(kKindAi, qps, nqps, &why);
+    if (!rc && record_offset < 0) {
+        rc = ETHCNN_ERR_ARG;
+        why = "negative record offset";
+    }
+    if (!rc && (bit_depth < 8 || bit_depth > 16)) {
+        rc = ETHCNN_ERR_ARG;
+        why = "ethcnn_samples_cut16_device: bit depth " + std::to_string(bit_depth) + " (8..16)";
+    }
+    if (!rc) rc = hipSetDevice(c->device) == hipSuccess ? 0 : ETHCNN_ERR_DEVICE;
+    if (!rc && d_records) d_records += (size_t)record_offset * (size_t)ethcnn::train::kRec;
+    const uint8_t* luma = reinterpret_cast<const uint8_t*>(d_luma16);
+    if (!rc) rc = cut(c, &why, kKindAi, qps, nqps, width, height, nframes, &luma, &pitch_bytes, &frame_stride_bytes, d_labels, 0, 0, d_records, 2, bit_depth - 8);
+    return rc ? set_err(c, rc, "%s", why.c_str()) : ETHCNN_OK;
 }
 
 extern "C" int ethcnn_samples_cut_device(ethcnn_ctx* c, int kind, const int* qps, int nqps, int width, int height, int nframes,
@@ -253,10 +310,11 @@ extern "C" int ethcnn_samples_build(ethcnn_samples* s) {
     }
     const int nplanes = s->kind == kKindAi ? 1 : 4;
     // frames per chunk and the staging size
-    auto frame_bytes_of = [&](const ethcnn_samples::Seq& q) { return (size_t)nplanes * q.w * q.h + (size_t)s->nqps * (q.h / 16) * (q.w / 16); };
+    // (a luma plane counts its bytes in the file: two per sample above 8 bits -- the chunk is uploaded as it is, the kernel narrows)
+    auto frame_bytes_of = [&](const ethcnn_samples::Seq& q) { return (size_t)nplanes * (size_t)q.luma_bytes + (size_t)s->nqps * (q.h / 16) * (q.w / 16); };
     auto chunk_frames = [&](const ethcnn_samples::Seq& q) { return (int)std::max<size_t>(1, std::min<size_t>((size_t)q.frames, kChunkBytes / frame_bytes_of(q))); };
     auto chunk_bytes = [&](const ethcnn_samples::Seq& q, int nf) {
-        return nplanes * up256((size_t)nf * q.w * q.h) + s->nqps * up256((size_t)nf * (q.h / 16) * (q.w / 16));
+        return nplanes * up256((size_t)nf * (size_t)q.luma_bytes) + s->nqps * up256((size_t)nf * (q.h / 16) * (q.w / 16));
     };
     size_t stage = 0;
     for (const auto& q : s->seqs)
@@ -291,8 +349,9 @@ extern "C" int ethcnn_samples_build(ethcnn_samples* s) {
                 if (fds.v.back() < 0 && !rc) rc = serr(s, ETHCNN_ERR_IO, "cannot open %s: %s", p.c_str(), std::strerror(errno));
             }
         if (rc) break;
-        const size_t plane = (size_t)q.w * q.h, lplane = (size_t)(q.h / 16) * (q.w / 16);
-        const off_t frame_bytes = (off_t)plane * 3 / 2;
+        const int bps = q.bit_depth > 8 ? 2 : 1;
+        const size_t plane = (size_t)q.luma_bytes, rowb = (size_t)q.w * bps, lplane = (size_t)(q.h / 16) * (q.w / 16);
+        const off_t frame_bytes = (off_t)q.frame_bytes;
         const int per = (q.h / 64) * (q.w / 64), nfmax = chunk_frames(q);
         const int bands = (int)std::max<size_t>(1, std::min<size_t>((size_t)std::min(q.h, 32), plane / (512u << 10)));
         const int64_t e_begin = s->kind == kKindAi ? 0 : 1;
@@ -309,8 +368,8 @@ extern "C" int ethcnn_samples_build(ethcnn_samples* s) {
                 for (int p = 0; p < nplanes; ++p)  // luma only: chroma is never read
                     for (int bd = 0; bd < bands; ++bd) {
                         const int r0 = (int)((long)q.h * bd / bands), r1 = (int)((long)q.h * (bd + 1) / bands);
-                        jobs.push_back({fds.v[p], (off_t)disp * frame_bytes + (off_t)r0 * q.w, (size_t)(r1 - r0) * q.w,
-                                        st.h[b] + p * lreg + (size_t)k * plane + (size_t)r0 * q.w});
+                        jobs.push_back({fds.v[p], (off_t)disp * frame_bytes + (off_t)(r0 * rowb), (size_t)(r1 - r0) * rowb,
+                                        st.h[b] + p * lreg + (size_t)k * plane + (size_t)r0 * rowb});
                     }
                 for (int l = 0; l < s->nqps; ++l)
                     jobs.push_back({fds.v[nplanes + l], (off_t)disp * (off_t)lplane, lplane, st.h[b] + nplanes * lreg + l * qreg + (size_t)k * lplane});
@@ -330,13 +389,13 @@ extern "C" int ethcnn_samples_build(ethcnn_samples* s) {
             ptrdiff_t pitch[4], fstride[4];
             for (int p = 0; p < nplanes; ++p) {
                 luma[p] = st.d[b] + p * lreg;
-                pitch[p] = q.w;
+                pitch[p] = (ptrdiff_t)rowb;
                 fstride[p] = (ptrdiff_t)plane;
             }
             for (int l = 0; l < s->nqps; ++l) labels[l] = st.d[b] + nplanes * lreg + l * qreg;
             std::string why;
             const int64_t rec0 = q.first_rec + (e0 - e_begin) * per;
-            if (int r = cut(c, &why, s->kind, s->qps, s->nqps, q.w, q.h, nf, luma, pitch, fstride, labels, (int)e0, (int)iq, (uint8_t*)data + (size_t)rec0 * rb)) {
+            if (int r = cut(c, &why, s->kind, s->qps, s->nqps, q.w, q.h, nf, luma, pitch, fstride, labels, (int)e0, (int)iq, (uint8_t*)data + (size_t)rec0 * rb, bps, q.bit_depth - 8)) {
                 rc = serr(s, r, "build: %s", why.c_str());
                 break;
             }

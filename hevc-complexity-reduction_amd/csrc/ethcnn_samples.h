@@ -6,6 +6,10 @@
 //                   (A = 16: one dwordx4 load per lane; A = 4 / 1: dword / byte loads for bases and pitches that are not 16-byte
 //                   aligned), one dwordx4 store per lane into the record; lanes 0..55 also write the 896-byte tail (64 fill bytes
 //                   and 52 label rows, 255 where the QP is not in the list) as dwordx4 stores
+//   k_cut_ai16<A>   k_cut_ai over 16-bit luma (CutArgs::deep): a lane owns the same 16 samples, now 32 source bytes (A = 16: two
+//                   dwordx4 loads; A = 4: eight dword loads; A = 2: sixteen 16-bit loads), narrows them by the rule of include/ethcnn.h
+//                   (the device inlines of ethcnn_narrow.h: a packed shift and a packed minimum per source dword, a byte permute per
+//                   output dword) and stores the same dwordx4; tail, loop, block count and record stores as k_cut_ai
 //   k_cut_inter<A>  one record per block and trip: the four residual tiles go to LDS with the same wide loads (16 KB, aligned), the
 //                   header and the four [QP | 16 labels] groups to a 132-byte LDS area; the record leaves as 4129 coalesced dwords,
 //                   each funnel-shifted out of two aligned LDS words (a slot's residual starts at byte 81 + 4113 s, never on a word)
@@ -49,7 +53,7 @@ __host__ __device__ inline uint64_t perm(uint64_t seed, uint64_t count, uint64_t
 // one launch: `nrec` records = frames x whole CTUs of a picture, record r = (frame r / (nl nc), CTU line, CTU column) in raster order
 struct CutArgs {
     const uint8_t* luma[4];    // All-Intra: [0] only; inter: the residual plane of slot s
-    long pitch[4], fstride[4];
+    long pitch[4], fstride[4];  // in bytes
     const uint8_t* label[52];  // All-Intra: by QP (NULL: that row stays 255); inter: by slot.  (h / 16) x lw bytes per frame
     long label_fstride;
     int label_al4;             // label bases and lw are multiples of 4: a CTU's four label runs are dword loads
@@ -58,8 +62,10 @@ struct CutArgs {
     long nrec;
     int frame0, seq;           // inter header: frame number of the first frame (then + 1 per frame), sequence number
     uint8_t* out;              // first record written
+    int deep, shift;           // All-Intra: luma[0] holds 16-bit samples, a record takes min(s >> shift, 255) (k_cut_ai16)
 };
 
+// align: what the luma bases, pitches and frame strides are all multiples of (16, 4, or less)
 void launch_cut(hipStream_t s, int kind, const CutArgs& a, int align, int cus);
 void launch_gather(hipStream_t s, int kind, const uint8_t* in, uint8_t* out, long first, long n, long count, uint64_t seed, int permuted,
                    int cus);
@@ -73,8 +79,11 @@ struct ethcnn_samples {
     int kind = 0, order = 0, nqps = 0;
     int qps[52] = {0};
     uint64_t max_bytes = 0;
+    int bit_depth = 8, chroma = 420;  // source format of the sequences added next (ethcnn_samples_set_source_format)
     struct Seq {
         int w, h;
+        int bit_depth, chroma;
+        int64_t luma_bytes, frame_bytes;  // of one frame of the YUV (ethcnn_source_frame_bytes)
         int64_t frames, first_rec, nrec;
         std::vector<std::string> yuv, labels;
     };

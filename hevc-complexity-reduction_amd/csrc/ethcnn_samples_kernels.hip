@@ -1,7 +1,9 @@
 // ethcnn_samples_kernels.hip -- the sample-set kernels (launch list: ethcnn_samples.h; record layouts: include/ethcnn.h "sample sets").
-// They move bytes: no arithmetic beyond addresses, no atomics, every byte of a record is written exactly once and never read back.
+// They move bytes: no arithmetic beyond addresses (k_cut_ai16: and the narrowing rule), no atomics, every byte of a record is written
+// exactly once and never read back.
 #include <hip/hip_runtime.h>
 
+#include "ethcnn_narrow.h"
 #include "ethcnn_samples.h"
 
 namespace ethcnn {
@@ -81,6 +83,59 @@ __global__ __launch_bounds__(kThreads) void k_cut_ai(const CutArgs a) {
             if (!on[u]) continue;
             uint4* dst = reinterpret_cast<uint4*>(a.out + (r0 + u * stride) * (long)kRec);
             dst[t] = v[u];
+            if (t < 56) dst[256 + t] = tail[u];
+        }
+    }
+}
+
+// 32 consecutive source bytes = 16 samples of 16 bits; A = what the address is known to be a multiple of (16, 4 or 2)
+template <int A>
+__device__ __forceinline__ void load32(const uint8_t* p, uint32_t (&w)[8]) {
+    if (A == 16) {
+        const uint4 a = reinterpret_cast<const uint4*>(p)[0], b = reinterpret_cast<const uint4*>(p)[1];
+        w[0] = a.x, w[1] = a.y, w[2] = a.z, w[3] = a.w, w[4] = b.x, w[5] = b.y, w[6] = b.z, w[7] = b.w;
+    } else if (A == 4) {
+#pragma unroll
+        for (int i = 0; i < 8; ++i) w[i] = reinterpret_cast<const uint32_t*>(p)[i];
+    } else {
+        const uint16_t* h = reinterpret_cast<const uint16_t*>(p);
+#pragma unroll
+        for (int i = 0; i < 8; ++i) w[i] = (uint32_t)h[2 * i] | (uint32_t)h[2 * i + 1] << 16;
+    }
+}
+
+// All-Intra from 16-bit luma: k_cut_ai with a deep source.  The same lane owns the same 16 samples of its tile row: 32 source bytes at
+// byte column 128 cc + 32 (lane % 4) of row 64 cl + lane / 4, narrowed to the 16 record bytes by the rule (ethcnn_narrow.h).  Only whole
+// CTUs are samples, so those 32 bytes always lie inside the row's 2 * width bytes: there is no edge path, and nothing is read outside
+// rows [0, 64 (height / 64)) or outside columns [0, 64 (width / 64)) of a plane.  Record layout, tail, loop and stores as k_cut_ai; the
+// loads of both records in flight are issued before the stores of either.
+template <int A>
+__global__ __launch_bounds__(kThreads) void k_cut_ai16(const CutArgs a) {
+    const int t = threadIdx.x, row = t >> 2, c32 = (t & 3) * 32;
+    const long stride = gridDim.x;
+    for (long r0 = blockIdx.x; r0 < a.nrec; r0 += 2 * stride) {
+        uint32_t v[2][8];
+        uint4 tail[2];
+        bool on[2];
+#pragma unroll
+        for (int u = 0; u < 2; ++u) {
+            const long r = r0 + u * stride;
+            on[u] = r < a.nrec;
+            if (!on[u]) continue;
+            const Where w = locate(a, r);
+            load32<A>(a.luma[0] + w.f * a.fstride[0] + (long)(w.cl * 64 + row) * a.pitch[0] + w.cc * 128 + c32, v[u]);
+            tail[u] = make_uint4(~0u, ~0u, ~0u, ~0u);
+            if (t >= 4 && t < 56 && a.label[t - 4]) {
+                const uint8_t* lp = a.label[t - 4] + w.f * a.label_fstride + (long)(w.cl * 4) * a.lw + w.cc * 4;
+                tail[u] = make_uint4(load4(lp, a.label_al4), load4(lp + a.lw, a.label_al4), load4(lp + 2 * a.lw, a.label_al4),
+                                     load4(lp + 3 * a.lw, a.label_al4));
+            }
+        }
+#pragma unroll
+        for (int u = 0; u < 2; ++u) {
+            if (!on[u]) continue;
+            uint4* dst = reinterpret_cast<uint4*>(a.out + (r0 + u * stride) * (long)kRec);
+            dst[t] = narrow::narrow8(v[u], a.shift);
             if (t < 56) dst[256 + t] = tail[u];
         }
     }
@@ -173,7 +228,11 @@ void launch_cut(hipStream_t s, int kind, const CutArgs& a, int align, int cus) {
     if (a.nrec <= 0) return;
     const long want = kind == kKindAi ? (a.nrec + 1) / 2 : a.nrec;
     const int blocks = (int)(want < (long)cus * 8 ? want : (long)cus * 8);
-    if (kind == kKindAi) {
+    if (kind == kKindAi && a.deep) {
+        if (align >= 16) hipLaunchKernelGGL(k_cut_ai16<16>, dim3(blocks), dim3(kThreads), 0, s, a);
+        else if (align >= 4) hipLaunchKernelGGL(k_cut_ai16<4>, dim3(blocks), dim3(kThreads), 0, s, a);
+        else hipLaunchKernelGGL(k_cut_ai16<2>, dim3(blocks), dim3(kThreads), 0, s, a);
+    } else if (kind == kKindAi) {
         if (align >= 16) hipLaunchKernelGGL(k_cut_ai<16>, dim3(blocks), dim3(kThreads), 0, s, a);
         else if (align >= 4) hipLaunchKernelGGL(k_cut_ai<4>, dim3(blocks), dim3(kThreads), 0, s, a);
         else hipLaunchKernelGGL(k_cut_ai<1>, dim3(blocks), dim3(kThreads), 0, s, a);

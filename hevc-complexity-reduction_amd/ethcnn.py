@@ -226,6 +226,9 @@ SIGNATURES = {
     "ethcnn_samples_destroy": (None, [_vp]),
     "ethcnn_samples_last_error": (_cp, [_vp]),
     "ethcnn_samples_add_sequence": (_i, [_vp, _i, _i, ctypes.POINTER(ctypes.c_char_p), _i, ctypes.POINTER(ctypes.c_char_p), _i]),
+    "ethcnn_samples_set_source_format": (_i, [_vp, _vp]),
+    "ethcnn_samples_cut16_device": (_i, [_vp, ctypes.POINTER(ctypes.c_int), _i, _i, _i, _i, _vp, _pd, _pd, _i, ctypes.POINTER(_vp), _vp,
+                                         ctypes.c_int64]),
     "ethcnn_samples_count": (ctypes.c_int64, [_vp]),
     "ethcnn_samples_record_bytes": (_i, [_vp]),
     "ethcnn_samples_build": (_i, [_vp]),
@@ -1250,6 +1253,20 @@ def cut_device(ctx, kind, qps, width, height, nframes, d_luma, pitch, frame_stri
         raise EthCnnError(rc, ctx.lib.ethcnn_last_error(ctx.h).decode())
 
 
+def cut16_device(ctx, qps, width, height, nframes, d_luma16, bit_depth, d_labels, d_records, pitch_bytes=None, frame_stride_bytes=None,
+                 record_offset=0):
+    """ethcnn_samples_cut16_device: the All-Intra cut kernel on 16-bit luma planes in HBM, narrowed by the rule of include/ethcnn.h while
+    they are cut.  pitch_bytes defaults to 2 * width, frame_stride_bytes to height * pitch_bytes; addresses as integers."""
+    nq = len(qps)
+    pitch_bytes = 2 * int(width) if pitch_bytes is None else int(pitch_bytes)
+    frame_stride_bytes = int(height) * pitch_bytes if frame_stride_bytes is None else int(frame_stride_bytes)
+    rc = ctx.lib.ethcnn_samples_cut16_device(ctx.h, (ctypes.c_int * nq)(*[int(q) for q in qps]), nq, int(width), int(height), int(nframes),
+                                             int(d_luma16), pitch_bytes, frame_stride_bytes, int(bit_depth),
+                                             (_vp * nq)(*[int(p) for p in d_labels]), int(d_records), int(record_offset))
+    if rc:
+        raise EthCnnError(rc, ctx.lib.ethcnn_last_error(ctx.h).decode())
+
+
 class SampleSet(object):
     """The trainers' sample records, cut out of YUV and label files into HBM (include/ethcnn.h "sample sets").
     kind "ai": 4992-byte records from one YUV and one *_CUDepth.dat per QP; kind "inter" (LDP / LDB / RA): 16516-byte records from four
@@ -1292,8 +1309,15 @@ class SampleSet(object):
     def __exit__(self, *a):
         self.close()
 
-    def add_sequence(self, width, height, yuv, labels):
-        """yuv: the YUV path (All-Intra) or the four residual paths; labels: one *_CUDepth.dat path per QP, in QP-list order"""
+    def set_source_format(self, bit_depth=8, chroma=420):
+        """the source format of the sequences added next (ethcnn_samples_set_source_format; All-Intra sets)"""
+        fmt = SourceFormat(int(bit_depth), int(chroma))
+        self._chk(self.lib.ethcnn_samples_set_source_format(self.h, ctypes.addressof(fmt)))
+
+    def add_sequence(self, width, height, yuv, labels, bit_depth=8, chroma=420):
+        """yuv: the YUV path (All-Intra) or the four residual paths; labels: one *_CUDepth.dat path per QP, in QP-list order;
+        bit_depth / chroma: the YUV's source format (bit_depth 8..16, chroma 400 / 420 / 422 / 444; All-Intra sets only)"""
+        self.set_source_format(bit_depth, chroma)
         yuv = [yuv] if isinstance(yuv, (str, bytes, os.PathLike)) else list(yuv)
         y = [os.fsencode(p) for p in yuv]
         lab = [os.fsencode(p) for p in labels]

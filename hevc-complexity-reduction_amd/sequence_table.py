@@ -93,17 +93,35 @@ INTER_INDEX = {"train": [v for v in range(30, 123) if v not in _INTER_VALID], "v
 SET_NAMES = {"train": "Train", "valid": "Valid", "test": "Test"}
 
 
-def parse_sequences(path):
-    """`name width height` per line (blank lines and # comments skipped) -> [(name, width, height)]"""
+CHROMA_FORMATS = (400, 420, 422, 444)
+
+
+def check_format(bit_depth, chroma, where):
+    """SystemExit unless (bit_depth, chroma) is a source format of include/ethcnn.h; `where` names the option or line at fault"""
+    if not 8 <= bit_depth <= 16:
+        raise SystemExit("%s: bit depth %d outside 8..16" % (where, bit_depth))
+    if chroma not in CHROMA_FORMATS:
+        raise SystemExit("%s: chroma format %d is not one of %s" % (where, chroma, " ".join(str(c) for c in CHROMA_FORMATS)))
+
+
+def parse_sequences(path, fmt=None):
+    """`name width height` per line (blank lines and # comments skipped) -> [(name, width, height)].
+    fmt = (bit_depth, chroma), the All-Intra drivers: a line may go on with `bit_depth [chroma]`, which override fmt for that line
+    -> [(name, width, height, bit_depth, chroma)]"""
     out = []
+    most, form = (3, "`name width height`") if fmt is None else (5, "`name width height [bit_depth [chroma]]`")
     with open(path) as f:
         for n, ln in enumerate(f, 1):
             tok = ln.split("#", 1)[0].split()
             if not tok:
                 continue
-            if len(tok) != 3 or not tok[1].isdigit() or not tok[2].isdigit():
-                raise SystemExit("%s:%d: expected `name width height`, got %r" % (path, n, ln.rstrip()))
-            out.append((tok[0], int(tok[1]), int(tok[2])))
+            if not 3 <= len(tok) <= most or not all(t.isdigit() for t in tok[1:]):
+                raise SystemExit("%s:%d: expected %s, got %r" % (path, n, form, ln.rstrip()))
+            row = (tok[0], int(tok[1]), int(tok[2]))
+            if fmt is not None:
+                row += (int(tok[3]) if len(tok) > 3 else fmt[0], int(tok[4]) if len(tok) > 4 else fmt[1])
+                check_format(row[3], row[4], "%s:%d" % (path, n))
+            out.append(row)
     if not out:
         raise SystemExit("%s: no sequences" % path)
     return out
@@ -125,11 +143,12 @@ def resi_file(yuv_dir, name, qp):
     return find_one(yuv_dir, "resi*_%s_*qp%d*.yuv" % (name, qp))
 
 
-def select(sequences_file, index_lists, which):
-    """the (name, width, height) list of a set: rows of the table by the set's index list, or every row of a --sequences file"""
+def select(sequences_file, index_lists, which, fmt=None):
+    """the (name, width, height) list of a set: rows of the table by the set's index list, or every row of a --sequences file.
+    fmt = (bit_depth, chroma): rows go on with their source format (parse_sequences)"""
     if sequences_file:
-        return parse_sequences(sequences_file)
-    return [SEQUENCES[i] for i in index_lists[which]]
+        return parse_sequences(sequences_file, fmt)
+    return [SEQUENCES[i] + (() if fmt is None else tuple(fmt)) for i in index_lists[which]]
 
 
 def ctu_labels(path, w, h, first_frame=0):
@@ -144,6 +163,20 @@ def add_video_args(ap):
     ap.add_argument("--info-dir", help="directory of the Info*_<name>_*qp<QP>*CUDepth.dat label files (with --yuv-dir)")
     ap.add_argument("--sequences", metavar="FILE", help="`name width height` lines: the training sequences (default: the built-in lists)")
     ap.add_argument("--valid-sequences", metavar="FILE", help="the validation sequences (default: --sequences)")
+
+
+def add_format_args(ap):
+    """the All-Intra drivers: the source format of the YUVs (include/ethcnn.h "high-bit-depth and non-4:2:0 sources")"""
+    ap.add_argument("--input-bit-depth", type=int, default=8, metavar="N",
+                    help="bit depth of the YUVs, 8..16 (above 8: 16-bit little-endian samples); a --sequences line may override it")
+    ap.add_argument("--input-chroma-format", type=int, default=420, metavar="{400,420,422,444}",
+                    help="chroma format of the YUVs (only luma is read); a --sequences line may override it")
+
+
+def source_format(a):
+    """(bit_depth, chroma) of add_format_args' options; SystemExit on a bad value"""
+    check_format(a.input_bit_depth, a.input_chroma_format, "--input-bit-depth / --input-chroma-format")
+    return a.input_bit_depth, a.input_chroma_format
 
 
 def check_source(a):

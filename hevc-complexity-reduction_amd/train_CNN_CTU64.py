@@ -230,6 +230,7 @@ def parse_args(argv):
     ap.add_argument("--train", help="training sample file (4992-byte records)")
     ap.add_argument("--valid", help="validation sample file")
     sequence_table.add_video_args(ap)
+    sequence_table.add_format_args(ap)
     g = ap.add_mutually_exclusive_group()
     g.add_argument("--model-type", type=int, choices=sorted(MODEL_TYPES), default=1)
     g.add_argument("--qp", type=int, help="train one QP (model name qp<QP>)")
@@ -260,11 +261,12 @@ def main_group(a, pkg, ctx):
     labels = [dict() for _ in members]  # member -> set -> [samples, 16] depth bytes at the member's QP
     if a.yuv_dir:  # both sets cut in HBM with the label rows of every member's QPs, adopted by the group
         di = sequence_table
-        for which, lst, key in ((pkg.ethcnn.SET_TRAIN, a.sequences, "train"), (pkg.ethcnn.SET_VALID, a.valid_sequences or a.sequences, "valid")):
+        for which, key in ((pkg.ethcnn.SET_TRAIN, "train"), (pkg.ethcnn.SET_VALID, "valid")):
             rows = [[] for _ in members]
             with pkg.SampleSet(ctx, "ai", all_qps) as sset:
-                for sname, w, h in di.select(lst, di.AI_INDEX, key):
-                    sset.add_sequence(w, h, di.find_one(a.yuv_dir, sname + ".yuv"), [di.info_file(a.info_dir, sname, q) for q in all_qps])
+                for sname, w, h, depth, chroma in a.video_sets[key]:
+                    sset.add_sequence(w, h, di.find_one(a.yuv_dir, sname + ".yuv"), [di.info_file(a.info_dir, sname, q) for q in all_qps],
+                                      bit_depth=depth, chroma=chroma)
                     for m, (_, qps) in enumerate(members):
                         rows[m].append(di.ctu_labels(di.info_file(a.info_dir, sname, qps[0]), w, h))
                 grp.set_samples(which, sset.build(), take=True)
@@ -294,6 +296,12 @@ def main(argv=None):
     else:
         name, qps = MODEL_TYPES[a.model_type]
     sequence_table.check_source(a)
+    fmt = sequence_table.source_format(a)
+    if fmt != (8, 420) and not a.yuv_dir:
+        raise SystemExit("--input-bit-depth / --input-chroma-format describe the YUVs of --yuv-dir: sample files hold 8-bit records")
+    if a.yuv_dir:  # the sequence lists with their source formats, read (and refused) before a GPU is touched
+        a.video_sets = {"train": sequence_table.select(a.sequences, sequence_table.AI_INDEX, "train", fmt),
+                        "valid": sequence_table.select(a.valid_sequences or a.sequences, sequence_table.AI_INDEX, "valid", fmt)}
     os.makedirs(a.models, exist_ok=True)
     ctx = pkg.EthCnn(device=a.device)
     if a.model_types:
@@ -305,12 +313,12 @@ def main(argv=None):
     labels = {}  # set -> [samples, 16] depth bytes at the model's QP
     if a.yuv_dir:  # both sets cut in HBM and adopted by the trainer: no sample file, no host copy of a record
         di = sequence_table
-        for which, lst, key in ((pkg.ethcnn.SET_TRAIN, a.sequences, "train"), (pkg.ethcnn.SET_VALID, a.valid_sequences or a.sequences, "valid")):
+        for which, key in ((pkg.ethcnn.SET_TRAIN, "train"), (pkg.ethcnn.SET_VALID, "valid")):
             rows = []
             with pkg.SampleSet(ctx, "ai", qps) as sset:
-                for sname, w, h in di.select(lst, di.AI_INDEX, key):
+                for sname, w, h, depth, chroma in a.video_sets[key]:
                     info = [di.info_file(a.info_dir, sname, q) for q in qps]
-                    sset.add_sequence(w, h, di.find_one(a.yuv_dir, sname + ".yuv"), info)
+                    sset.add_sequence(w, h, di.find_one(a.yuv_dir, sname + ".yuv"), info, bit_depth=depth, chroma=chroma)
                     rows.append(di.ctu_labels(info[0], w, h))
                 tr.set_samples(which, sset.build(), take=True)
             labels[which] = np.concatenate(rows)

@@ -176,6 +176,9 @@ int ethcnn_predict_yuv_range(ethcnn_ctx* ctx, const char* yuv_path, int width, i
  *      holds 16-bit samples; bit_depth == 8: one byte per sample.  Planar, luma first; only luma is read.  A file whose size is not a
  *      multiple of the frame size fails with ETHCNN_ERR_FORMAT, the message names the format in force.  The Low-Delay-P entries
  *      (ethcnn_ldp_*) are NOT affected: HM's residual writer always emits 8-bit 4:2:0.
+ *   Sample sets ("sample sets" below) read the same formats for All-Intra sequences: ethcnn_samples_set_source_format per set, and
+ *      ethcnn_samples_cut16_device, the cut kernel over 16-bit planes in HBM.  Their records hold the picture narrowed by the rule, so a
+ *      model is trained on what the predictor entries above will show it.  Inter sets keep 8-bit 4:2:0, for the reason just given.
  *   ethcnn_source_frame_bytes    pure: bytes of the luma plane and of a whole frame.  Chroma share in samples: 0 (400), w h / 2 (420),
  *                                w h (422), 2 w h (444).  8-bit 4:2:0 is exactly the reference's w * h * 3 / 2 (integer division, odd
  *                                sizes included: video_to_cu_depth.py:136); 4:2:0 at other depths needs even w and h, 4:2:2 an even w,
@@ -747,6 +750,12 @@ const char* ethcnn_lstm_train_group_last_error(const ethcnn_lstm_train_group* gr
  *        until x < count; perm(j) = x
  *      (a four-round Feistel network over 2 h bits, cycle-walked into [0, count): a bijection fixed by (seed, count), computed per
  *      record; the reference's own shuffle is Python's unseeded random.sample and is not reproduced.)
+ *   Source format (All-Intra sets): a sequence's YUV is read in the format in force when it is added, "high-bit-depth and non-4:2:0
+ *      sources" above: planar, luma first, one byte per sample at bit depth 8 and an unsigned 16-bit little-endian container above,
+ *      chroma planes of the size the chroma format demands (never read).  The luma a record holds is min(s >> (bit_depth - 8), 255),
+ *      THE NARROWING RULE above, so a deep re-encoding s16 = s8 << (bit_depth - 8) | low bits of a file gives the 8-bit file's records
+ *      byte for byte.  The default {8, 420} is the reference's only format.  Inter sets refuse every other format: HM's residual
+ *      writer always emits 8-bit 4:2:0.
  *   A set belongs to a context (its device, stream and fill threads); ctx == NULL gives a set that validates and counts only. */
 typedef struct ethcnn_samples ethcnn_samples;
 enum { ETHCNN_SAMPLES_AI = 0, ETHCNN_SAMPLES_INTER = 1 };
@@ -757,9 +766,14 @@ int ethcnn_samples_create(ethcnn_ctx* ctx /* may be NULL */, int kind, const int
                           ethcnn_samples** out);
 void ethcnn_samples_destroy(ethcnn_samples* set); /* before ethcnn_destroy of its context */
 const char* ethcnn_samples_last_error(const ethcnn_samples* set);
+/* The source format of the sequences added AFTER this call (sticky: one set may mix 8-bit and 10-bit sequences; default {8, 420}).
+ * ETHCNN_ERR_ARG: an invalid format, anything but {8, 420} on an ETHCNN_SAMPLES_INTER set, a set that is built.  Works on a set
+ * without a context. */
+int ethcnn_samples_set_source_format(ethcnn_samples* set, const ethcnn_source_format* fmt);
 /* Validates and counts, nothing more.  nyuv = 1 (All-Intra) or 4 (inter: the residual file of each slot), nlabels = the QP count, label
  * paths in QP-list order.  ETHCNN_ERR_FORMAT, with the file named: width or height below 64 or not a multiple of 8, a YUV that is not a
- * whole number of 4:2:0 frames, residual files of different frame counts, a label file whose size is not frames x (h / 16) x (w / 16).
+ * whole number of frames of the source format in force (ethcnn_source_frame_bytes; the message names the format unless it is 8-bit
+ * 4:2:0), residual files of different frame counts, a label file whose size is not frames x (h / 16) x (w / 16).
  * ETHCNN_ERR_IO: a file that cannot be examined. */
 int ethcnn_samples_add_sequence(ethcnn_samples* set, int width, int height, const char* const* yuv_paths, int nyuv,
                                 const char* const* label_paths, int nlabels);
@@ -768,7 +782,9 @@ int ethcnn_samples_record_bytes(const ethcnn_samples* set);
 /* One allocation of count x record_bytes in HBM (ETHCNN_ERR_NOMEM, with the byte count, when it does not fit or exceeds max_bytes;
  * nothing is allocated then), filled sequence by sequence, a bounded number of frames at a time: luma and label planes are read by the
  * context's fill threads into page-locked staging (chroma is never read), copied to HBM and cut into records by the kernel while the next
- * frames are read.  Synchronous.  Once; sequences cannot be added afterwards. */
+ * frames are read.  Luma above 8 bits is uploaded as it is in the file, two bytes per sample, and narrowed by the cut kernel (the
+ * kernel of ethcnn_samples_cut16_device); 8-bit luma of any chroma format takes the kernel of ethcnn_samples_cut_device.
+ * Synchronous.  Once; sequences cannot be added afterwards. */
 int ethcnn_samples_build(ethcnn_samples* set);
 /* The kernel alone, on frames already in HBM: `nframes` frames of d_luma[p] (p = 0, or the four slots; `pitch[p]` bytes between rows,
  * `frame_stride[p]` between frames) and of d_labels[q] (one per QP of the list, frames packed) become records record_offset .. of
@@ -777,6 +793,15 @@ int ethcnn_samples_build(ethcnn_samples* set);
 int ethcnn_samples_cut_device(ethcnn_ctx* ctx, int kind, const int* qps, int nqps, int width, int height, int nframes,
                               const uint8_t* const* d_luma, const ptrdiff_t* pitch, const ptrdiff_t* frame_stride,
                               const uint8_t* const* d_labels, int frame_number, int seq_number, uint8_t* d_records, int64_t record_offset);
+/* The All-Intra cut over 16-bit luma: as ethcnn_samples_cut_device with kind ETHCNN_SAMPLES_AI, the frames being unsigned 16-bit
+ * little-endian planes at d_luma16 (any 2-byte aligned address; pitch_bytes even and >= 2 width; frame_stride_bytes even) and the luma
+ * of a record min(s >> (bit_depth - 8), 255), bit_depth 8..16.  One kernel: nothing is narrowed into memory first.  Every alignment
+ * gives the same bytes (bases, pitches and strides that are multiples of 16 take the wide loads).  Only whole CTUs are read: nothing
+ * outside rows [0, 64 (height / 64)) or columns [0, 64 (width / 64)) of a plane.  ETHCNN_ERR_ARG: a bit depth outside 8..16, an odd
+ * address, pitch or stride, and whatever ethcnn_samples_cut_device refuses.  Asynchronous on the context's stream. */
+int ethcnn_samples_cut16_device(ethcnn_ctx* ctx, const int* qps, int nqps, int width, int height, int nframes, const uint16_t* d_luma16,
+                                ptrdiff_t pitch_bytes, ptrdiff_t frame_stride_bytes, int bit_depth, const uint8_t* const* d_labels,
+                                uint8_t* d_records, int64_t record_offset);
 /* records [first, first + n) of the built set (permuted != 0: of its permutation by `seed`) -> host memory */
 int ethcnn_samples_read(ethcnn_samples* set, int64_t first, int64_t n, int permuted, uint64_t seed, uint8_t* out);
 /* the whole set as a sample file (temp file + rename: never a partial file); permuted != 0: the "_shuffled" form */

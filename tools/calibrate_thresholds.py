@@ -9,7 +9,7 @@ the largest `down` that wrongly stops at most --eps-down parts per million of th
 wrongly forces at most --eps-up parts per million of the truly unsplit ones.
 
     calibrate_thresholds.py [--eps-down E1 E2 E3] [--eps-up E1 E2 E3] [--out Thr_info.txt --order ai|ldp] [--hist FILE] [--json] [--device N]
-                            CASE...
+                            [--input-bit-depth N] [--input-chroma-format 400|420|422|444] CASE...
 
 Any number of cases, accumulated into one histogram:
 
@@ -30,6 +30,11 @@ Any number of cases, accumulated into one histogram:
         together on the GPU, in any record order, and predicted as the daemon would, gates open, with the models of D (as for --yuv
         --ldp).  Q selects the QP slot; a file without a slot of that QP is an error.  One line per sequence goes to stderr.
 
+--input-bit-depth (8..16; above 8 the file holds 16-bit little-endian samples) and --input-chroma-format give the source format of
+the All-Intra --yuv cases of the run (include/ethcnn.h "high-bit-depth and non-4:2:0 sources"); --ldp cases read HM's residual files,
+which are always 8-bit 4:2:0, and --case / --samples cases carry no video.  A format other than 8-bit 4:2:0 without an All-Intra
+--yuv case is an error.
+
 Budgets default to 50000 ppm (5 %).  --hist FILE also writes the accumulated histogram, uint64 little-endian [3 levels][2 truths][1025 bins].  --order ai writes "up1 down1 up2 down2 up3 down3" (HM-16.5_Test_AI, TEncCu.cpp:250), --order
 ldp writes "down1 up1 down2 up2 down3 up3" (HM-16.5_Test_LDP, TEncGOP.cpp:1449): the two encoders differ.  CTUs that are not wholly
 inside the picture are left out (HM forces their splits).
@@ -44,6 +49,7 @@ import numpy as np
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 LDP_CNN_FILE = "model_LDP_2000000_qp22~37.dat"
+DEFAULT_FORMAT = (8, 420)
 
 
 class Usage(Exception):
@@ -61,6 +67,7 @@ def parse(argv, labels_optional=False):
     simulation tool, which shares this command line's cases)"""
     opt = {"eps_down": [50000] * 3, "eps_up": [50000] * 3, "out": None, "order": None, "hist": None, "json": False, "device": 0}
     cases, i = [], 0
+    fmt = {"--input-bit-depth": DEFAULT_FORMAT[0], "--input-chroma-format": DEFAULT_FORMAT[1]}
     per_case = {"--skip-label-frames": ("skip", int, ("case",)), "--labels": ("labels", str, ("yuv",)), "--model-dir": ("model_dir", str, ("yuv", "samples")),
                 "--frame-begin": ("frame_begin", int, ("yuv",)), "--model": ("model", str, ("samples",)), "--qp": ("qp", int, ("samples",)),
                 "--net": ("net", str, ("samples",))}
@@ -77,6 +84,11 @@ def parse(argv, labels_optional=False):
             opt[a[2:]] = int(v[0]) if a == "--device" else v[0]
         elif a == "--json":
             opt["json"] = True
+        elif a in fmt:
+            v, i = _take(argv, i, 1, a)
+            if not v[0].isdigit():
+                raise Usage("%s takes a number" % a)
+            fmt[a] = int(v[0])
         elif a == "--case":
             v, i = _take(argv, i, 4, a)
             cases.append({"kind": "case", "labels": v[0], "probs": v[1], "w": int(v[2]), "h": int(v[3]), "skip": 0})
@@ -110,6 +122,18 @@ def parse(argv, labels_optional=False):
             raise Usage("--net is ai or ldp")
         if c["kind"] == "samples" and (("model" in c or c["net"] != "ai") if c["ldp"] else "model_dir" in c):
             raise Usage("a --samples case takes --model PREFIX [--net], or --ldp --model-dir D (a replay)")
+    # the source format of the run's All-Intra --yuv cases (checked here, before a GPU is touched; add_cases sets it on the context)
+    opt["source_format"] = (fmt["--input-bit-depth"], fmt["--input-chroma-format"])
+    if not 8 <= opt["source_format"][0] <= 16:
+        raise Usage("--input-bit-depth is 8..16")
+    if opt["source_format"][1] not in (400, 420, 422, 444):
+        raise Usage("--input-chroma-format is 400, 420, 422 or 444")
+    video = [c for c in cases if c["kind"] == "yuv" and not c["ldp"]]
+    if opt["source_format"] != DEFAULT_FORMAT and not video:
+        raise Usage("--input-bit-depth / --input-chroma-format describe All-Intra --yuv sources, and none is given "
+                    "(--ldp residual files are always 8-bit 4:2:0; --case and --samples carry no video)")
+    for c in video:
+        c["source_format"] = opt["source_format"]
     if (opt["out"] is None) != (opt["order"] is None) or opt["order"] not in (None, "ai", "ldp"):
         raise Usage("--out PATH and --order ai|ldp go together")
     for e in opt["eps_down"] + opt["eps_up"]:
@@ -179,13 +203,18 @@ def add_cases(pkg, ctx, cal, cases, note):
                     ctx.load_checkpoint(os.path.join(d, LDP_CNN_FILE))
                     ctx.load_lstm_checkpoint(os.path.join(d, pkg.ethcnn.lstm_model_name_for_qp(qp)))
                     ctx.set_thresholds(0.0, 0.0)  # open gates
+                    ctx.set_source_format(*DEFAULT_FORMAT)  # (the Low-Delay-P entries do not read it; nothing deep is left in force)
                     frames = os.path.getsize(c["yuv"]) // (w * h * 3 // 2)
                     ctx.ldp_predict_yuv_file(c["yuv"], w, h, qp, dat, c["frame_begin"], frames)
                     skip = c["frame_begin"]
                 else:
                     ctx.load_checkpoint(os.path.join(d, pkg.ethcnn.model_name_for_qp(qp)))
                     ctx.set_thresholds(0.0, 0.0)  # open gates
-                    ctx.predict_yuv_file(c["yuv"], w, h, qp, dat)
+                    ctx.set_source_format(*c.get("source_format", DEFAULT_FORMAT))
+                    try:
+                        ctx.predict_yuv_file(c["yuv"], w, h, qp, dat)
+                    finally:
+                        ctx.set_source_format(*DEFAULT_FORMAT)
                     skip = 0
                 _add_file_pair(cal, pkg, c.get("labels"), dat, w, h, skip, note)
         elif c["ldp"]:

@@ -22,7 +22,8 @@ cu_depth.dat (include/ethcnn.h "search budget").
                      with labels also the frame's bad and labelled CTUs under its rung.
   A frame whose cheapest rung is still above the budget takes that rung and is flagged over_budget.
 
-Cases and --weights are those of simulate_thresholds.py, but every case must come as frames of a picture (--case, --yuv).
+Cases, --weights and --input-bit-depth / --input-chroma-format are those of simulate_thresholds.py, but every case must come as
+frames of a picture (--case, --yuv).
 Predictions are made with open gates; a --case file is taken as what the encoder would read.  The summary (stderr) gives the achieved
 share over the whole input and the number of over-budget frames.
 

@@ -20,7 +20,8 @@ Outputs (at least one):
                      level-1 / level-2 gate is closed.  CTUs of a --samples case without --ldp have no frames: one row per case.
 
 --mid P (0..1, default 0.5, snapped to the grid k / 1024): where both choices are left open the preferred partition splits when
-p > P.  Cases, --gates and the rounding of the thresholds are those of simulate_thresholds.py.
+p > P.  Cases, --gates, --input-bit-depth / --input-chroma-format and the rounding of the thresholds are those of
+simulate_thresholds.py.
 """
 import importlib
 import importlib.util

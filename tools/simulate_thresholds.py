@@ -29,6 +29,9 @@ Cases are those of calibrate_thresholds.py, with labels optional:
   --samples FILE --ldp --model-dir D --qp Q          (an inter sample file replayed through the deployed Low-Delay-P chain; its
         CTUs come as frames, so the gates apply to them as to a --yuv case)
 
+--input-bit-depth N and --input-chroma-format 400|420|422|444 give the source format of the All-Intra --yuv cases, as in
+calibrate_thresholds.py (refused without such a case unless they say 8-bit 4:2:0).
+
 --gates defaults to --order: input predicted by this tool has open gates, and the simulator applies the gates that a predictor
 reading the candidate file would (tokens [1] and [3]).  CTUs of a --samples case without --ldp belong to no sub-batch and are never gated.
 --weights default to 64 16 4 1: cost proportional to the CU's area.
