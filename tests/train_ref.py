@@ -61,22 +61,58 @@ def _avgpool(x, k):
     return x.reshape(n, h // k, k, w // k, k, c).mean(dim=(2, 4))
 
 
-def net(flat, luma, labels, qp, mask1=None, mask2=None):
-    """net_CTU64.net with isdrop = (masks given): returns dict(probs [n,21], loss_list, accuracy_list, total_loss)."""
-    tv = views(flat)
-    n = luma.shape[0]
-    x = torch.as_tensor(np.asarray(luma), dtype=torch.float64).reshape(n, 64, 64, 1) * INV255
-    q = torch.as_tensor(np.broadcast_to(np.asarray(qp, dtype=np.float64), (n,)).copy()).reshape(n, 1) * INV51
-    y = torch.as_tensor(np.asarray(labels, dtype=np.float64)).reshape(n, 4, 4, 1)
-    relu = torch.relu
-    # labels (:99-111), literally
+def split_labels(y):
+    """labels (:99-111), literally: depths y [n,4,4,1] -> (y64 [n,1], y32 [n,4], y16 [n,16], v32 [n,4], v16 [n,16])"""
+    n, relu = y.shape[0], torch.relu
     y16 = relu(y - 2)
     y32 = relu(_avgpool(y, 2) - 1) - relu(_avgpool(y, 2) - 2)
     y64 = relu(_avgpool(y, 4) - 0) - relu(_avgpool(y, 4) - 1)
     v32 = relu(_avgpool(y, 2) - 0) - relu(_avgpool(y, 2) - 1)
     v16 = relu(y - 1) - relu(y - 2)
-    y16, y32, y64 = y16.reshape(n, 16), y32.reshape(n, 4), y64.reshape(n, 1)
-    v32, v16 = v32.reshape(n, 4), v16.reshape(n, 16)
+    return y64.reshape(n, 1), y32.reshape(n, 4), y16.reshape(n, 16), v32.reshape(n, 4), v16.reshape(n, 16)
+
+
+def _cnz(t):
+    return float((t != 0).sum())
+
+
+def _counts64(y64):
+    """count_nonzero of the level-64 positives and negatives (:178-180: no validity mask at this level)"""
+    return _cnz(y64), _cnz(1 - y64)
+
+
+def _denom(count):
+    return count + 1e-12
+
+
+def balanced_loss(labs, p64, p32, p16):
+    """loss (:178-190), is_balance = True, counts over the whole batch -> (l64, l32, l16).  Shared by the three restatements
+    (All-Intra, Low-Delay-P, ETH-LSTM: the same lines in each net_CTU64.py); split_labels, _counts64 and _denom are looked up when
+    called, so tests/train_edges.py can patch one of them to make a deliberately wrong restatement.  One function for three
+    references means one error would be in all three at once: its independent guard is the plain-numpy loop of
+    tests/test_train_lstm_cpu.py::test_loss_against_plain_numpy (fractional labels included), which shares no code with it."""
+    y64, y32, y16, v32, v16 = labs
+    eps = 1e-12
+    c64p, c64n = _counts64(y64)
+    l64 = (torch.sum(-(y64 * torch.log(p64 + eps))) / _denom(c64p) +
+           torch.sum(-((1 - y64) * torch.log((1 - p64) + eps))) / _denom(c64n)) / 2
+    l32 = (torch.sum(-(y32 * torch.log(p32 + eps)) * v32) / _denom(_cnz(y32 * v32)) +
+           torch.sum(-((1 - y32) * torch.log((1 - p32) + eps)) * v32) / _denom(_cnz((1 - y32) * v32))) / 2
+    l16 = (torch.sum(-(y16 * torch.log(p16 + eps)) * v16) / _denom(_cnz(y16 * v16)) +
+           torch.sum(-((1 - y16) * torch.log((1 - p16) + eps)) * v16) / _denom(_cnz((1 - y16) * v16))) / 2
+    return l64, l32, l16
+
+
+def net(flat, luma, labels, qp, mask1=None, mask2=None, dtype=torch.float64):
+    """net_CTU64.net with isdrop = (masks given): returns dict(probs [n,21], H1 [n,448] (leaky-ReLU FC1, before dropout), loss_list,
+    accuracy_list, total_loss).  dtype (that of `flat`): float64; float32 only to measure what fp32 arithmetic costs."""
+    tv = views(flat)
+    n = luma.shape[0]
+    x = torch.as_tensor(np.asarray(luma), dtype=dtype).reshape(n, 64, 64, 1) * INV255
+    q = torch.as_tensor(np.broadcast_to(np.asarray(qp, dtype=np.float64), (n,)).copy()).to(dtype).reshape(n, 1) * INV51
+    y = torch.as_tensor(np.asarray(labels, dtype=np.float64)).to(dtype).reshape(n, 4, 4, 1)
+    labs = split_labels(y)
+    y64, y32, y16, v32, v16 = labs
     # trunk (:117-156)
     f2, f3 = {}, {}
     for br, pool in (("L", 4), ("M", 2), ("S", 1)):
@@ -92,30 +128,21 @@ def net(flat, luma, labels, qp, mask1=None, mask2=None):
         f2[br], f3[br] = c2.reshape(n, -1), c3.reshape(n, -1)
     feat = torch.cat([f3["S"], f3["M"], f3["L"], f2["S"], f2["M"], f2["L"]], dim=1)
     # heads (:160-176); dropout = x / keep * mask (tf.nn.dropout) after FC1 (keep 0.5) and FC2 (keep 0.8)
-    probs, o1, o2 = [], 0, 0
+    probs, h1s, o1, o2 = [], [], 0, 0
     for tag, n1, n2, n3 in HEADS:
         h1 = _lrelu(feat @ tv["h_fc1__%s__w" % tag] + tv["h_fc1__%s__b" % tag])
+        h1s.append(h1)
         if mask1 is not None:
-            h1 = h1 / 0.5 * torch.as_tensor(mask1[:, o1:o1 + n1], dtype=torch.float64)
+            h1 = h1 / 0.5 * torch.as_tensor(mask1[:, o1:o1 + n1], dtype=dtype)
         h2 = _lrelu(torch.cat([h1, q], 1) @ tv["h_fc2__%s__w" % tag] + tv["h_fc2__%s__b" % tag])
         if mask2 is not None:
-            h2 = h2 / 0.8 * torch.as_tensor(mask2[:, o2:o2 + n2], dtype=torch.float64)
+            h2 = h2 / 0.8 * torch.as_tensor(mask2[:, o2:o2 + n2], dtype=dtype)
         z = torch.cat([h2, q], 1) @ tv["y_conv_flat__%s__w" % tag] + tv["y_conv_flat__%s__b" % tag]
         probs.append(torch.sigmoid(z))
         o1, o2 = o1 + n1, o2 + n2
     p64, p32, p16 = probs
     eps = 1e-12
-
-    def cnz(t):
-        return float((t != 0).sum())
-
-    # loss (:178-190)
-    l64 = (torch.sum(-(y64 * torch.log(p64 + eps))) / (cnz(y64) + eps) +
-           torch.sum(-((1 - y64) * torch.log((1 - p64) + eps))) / (cnz(1 - y64) + eps)) / 2
-    l32 = (torch.sum(-(y32 * torch.log(p32 + eps)) * v32) / (cnz(y32 * v32) + eps) +
-           torch.sum(-((1 - y32) * torch.log((1 - p32) + eps)) * v32) / (cnz((1 - y32) * v32) + eps)) / 2
-    l16 = (torch.sum(-(y16 * torch.log(p16 + eps)) * v16) / (cnz(y16 * v16) + eps) +
-           torch.sum(-((1 - y16) * torch.log((1 - p16) + eps)) * v16) / (cnz((1 - y16) * v16) + eps)) / 2
+    l64, l32, l16 = balanced_loss(labs, p64, p32, p16)   # loss (:178-190)
     total = l16 + l32 + l64
     # accuracy (:198-206)
     with torch.no_grad():
@@ -124,7 +151,7 @@ def net(flat, luma, labels, qp, mask1=None, mask2=None):
         a16 = torch.sum(v16 * c16) / (torch.sum(v16) + eps)
         a32 = torch.sum(v32 * c32) / (torch.sum(v32) + eps)
         a64 = torch.mean((torch.round(p64) == torch.round(y64)).double())
-    return {"probs": torch.cat([p64, p32, p16], 1), "loss_list": torch.stack([l64, l32, l16]),
+    return {"probs": torch.cat([p64, p32, p16], 1), "H1": torch.cat(h1s, 1), "loss_list": torch.stack([l64, l32, l16]),
             "accuracy_list": torch.stack([a64, a32, a16]), "total_loss": total}
 
 
@@ -145,13 +172,13 @@ def accuracy(probs, labels):
                      (torch.sum(v32 * c32) / (torch.sum(v32) + eps)).item(), (torch.sum(v16 * c16) / (torch.sum(v16) + eps)).item()])
 
 
-def loss_and_grad(blob, luma, labels, qp, mask1=None, mask2=None):
-    """-> (out dict with numpy values, gradient float64 [BLOB_FLOATS] in blob layout)"""
-    flat = torch.tensor(np.asarray(blob, dtype=np.float64), requires_grad=True)
-    out = net(flat, luma, labels, qp, mask1, mask2)
+def loss_and_grad(blob, luma, labels, qp, mask1=None, mask2=None, dtype=torch.float64):
+    """-> (out dict with numpy values, gradient [BLOB_FLOATS] in blob layout, as float64 numbers)"""
+    flat = torch.tensor(np.asarray(blob, dtype=np.float64), dtype=dtype, requires_grad=True)
+    out = net(flat, luma, labels, qp, mask1, mask2, dtype)
     out["total_loss"].backward()
     res = {k: v.detach().numpy() for k, v in out.items()}
-    return res, flat.grad.numpy()
+    return res, flat.grad.numpy().astype(np.float64)
 
 
 def lr_at(step, lr_init=0.01, decay_rate=0.3163, decay_steps=250000):

@@ -39,20 +39,15 @@ def slot_qps(buf):
     return [int(r[SLOT_BASE + SLOT_BYTES * s]) for s in range(4)]
 
 
-def net(flat, luma, labels, qp, mask1=None, mask2=None):
+def net(flat, luma, labels, qp, mask1=None, mask2=None, dtype=torch.float64):
     """LDP net_CTU64.net with isdrop = (masks given): dict(probs [n,21], H1 [n,448] (leaky-ReLU FC1, before dropout), loss_list,
-    accuracy_list, total_loss)."""
+    accuracy_list, total_loss).  dtype (that of `flat`): float64; float32 only to measure what fp32 arithmetic costs."""
     tv = views(flat)
     n = luma.shape[0]
-    x = (torch.as_tensor(np.asarray(luma), dtype=torch.float64).reshape(n, 64, 64, 1) - 128) / 255.0 * 10   # :102
-    q = torch.as_tensor(np.broadcast_to(np.asarray(qp, dtype=np.float64), (n,)).copy()).reshape(n, 1) / 51.0 * 0.18  # :103
-    y = torch.as_tensor(np.asarray(labels, dtype=np.float64)).reshape(n, 4, 4, 1)
-    relu = torch.relu
-    y16 = relu(y - 2).reshape(n, 16)
-    y32 = (relu(_avgpool(y, 2) - 1) - relu(_avgpool(y, 2) - 2)).reshape(n, 4)
-    y64 = (relu(_avgpool(y, 4) - 0) - relu(_avgpool(y, 4) - 1)).reshape(n, 1)
-    v32 = (relu(_avgpool(y, 2) - 0) - relu(_avgpool(y, 2) - 1)).reshape(n, 4)
-    v16 = (relu(y - 1) - relu(y - 2)).reshape(n, 16)
+    x = (torch.as_tensor(np.asarray(luma), dtype=dtype).reshape(n, 64, 64, 1) - 128) / 255.0 * 10   # :102
+    q = torch.as_tensor(np.broadcast_to(np.asarray(qp, dtype=np.float64), (n,)).copy()).to(dtype).reshape(n, 1) / 51.0 * 0.18  # :103
+    y = torch.as_tensor(np.asarray(labels, dtype=np.float64)).to(dtype).reshape(n, 4, 4, 1)
+    labs = train_ref.split_labels(y)
     f2, f3 = {}, {}
     for br, pool in (("L", 4), ("M", 2), ("S", 1)):
         xb = _avgpool(x, pool) if pool > 1 else x
@@ -71,25 +66,15 @@ def net(flat, luma, labels, qp, mask1=None, mask2=None):
         h1 = _lrelu(feat @ tv["h_fc1__%s__w" % tag] + tv["h_fc1__%s__b" % tag])
         h1s.append(h1)
         if mask1 is not None:
-            h1 = h1 / 0.5 * torch.as_tensor(mask1[:, o1:o1 + n1], dtype=torch.float64)
+            h1 = h1 / 0.5 * torch.as_tensor(mask1[:, o1:o1 + n1], dtype=dtype)
         h2 = _lrelu(torch.cat([h1, q], 1) @ tv["h_fc2__%s__w" % tag] + tv["h_fc2__%s__b" % tag])
         if mask2 is not None:
-            h2 = h2 / 0.8 * torch.as_tensor(mask2[:, o2:o2 + n2], dtype=torch.float64)
+            h2 = h2 / 0.8 * torch.as_tensor(mask2[:, o2:o2 + n2], dtype=dtype)
         z = torch.cat([h2, q], 1) @ tv["y_conv_flat__%s__w" % tag] + tv["y_conv_flat__%s__b" % tag]
         probs.append(torch.sigmoid(z))
         o1, o2 = o1 + n1, o2 + n2
     p64, p32, p16 = probs
-    eps = 1e-12
-
-    def cnz(t):
-        return float((t != 0).sum())
-
-    l64 = (torch.sum(-(y64 * torch.log(p64 + eps))) / (cnz(y64) + eps) +
-           torch.sum(-((1 - y64) * torch.log((1 - p64) + eps))) / (cnz(1 - y64) + eps)) / 2
-    l32 = (torch.sum(-(y32 * torch.log(p32 + eps)) * v32) / (cnz(y32 * v32) + eps) +
-           torch.sum(-((1 - y32) * torch.log((1 - p32) + eps)) * v32) / (cnz((1 - y32) * v32) + eps)) / 2
-    l16 = (torch.sum(-(y16 * torch.log(p16 + eps)) * v16) / (cnz(y16 * v16) + eps) +
-           torch.sum(-((1 - y16) * torch.log((1 - p16) + eps)) * v16) / (cnz((1 - y16) * v16) + eps)) / 2
+    l64, l32, l16 = train_ref.balanced_loss(labs, p64, p32, p16)
     with torch.no_grad():
         pr = torch.cat([p64, p32, p16], 1)
         acc = torch.as_tensor(train_ref.accuracy(pr.numpy(), labels))
@@ -97,12 +82,12 @@ def net(flat, luma, labels, qp, mask1=None, mask2=None):
             "accuracy_list": acc, "total_loss": l16 + l32 + l64}
 
 
-def loss_and_grad(blob, luma, labels, qp, mask1=None, mask2=None):
-    """-> (out dict with numpy values, gradient float64 [BLOB_FLOATS] in blob layout)"""
-    flat = torch.tensor(np.asarray(blob, dtype=np.float64), requires_grad=True)
-    out = net(flat, luma, labels, qp, mask1, mask2)
+def loss_and_grad(blob, luma, labels, qp, mask1=None, mask2=None, dtype=torch.float64):
+    """-> (out dict with numpy values, gradient [BLOB_FLOATS] in blob layout, as float64 numbers)"""
+    flat = torch.tensor(np.asarray(blob, dtype=np.float64), dtype=dtype, requires_grad=True)
+    out = net(flat, luma, labels, qp, mask1, mask2, dtype)
     out["total_loss"].backward()
-    return {k: v.detach().numpy() for k, v in out.items()}, flat.grad.numpy()
+    return {k: v.detach().numpy() for k, v in out.items()}, flat.grad.numpy().astype(np.float64)
 
 
 def tune_mask(tune):

@@ -43,9 +43,25 @@ def parse_samples(buf, idx):
     return f[:, :, 17:].copy(), f[:, :, 1:17].copy(), f[:, :, 0].copy(), np.mod(frames, 4)
 
 
+def _cell_clip(c):
+    return torch.clamp(c, -5.0, 5.0)   # LSTMCell(cell_clip = 5): clip_by_value, no gradient where c was clipped
+
+
+def _carry(cpre, c):
+    """the cell state the next unrolled step sees: the clipped one"""
+    return c
+
+
+def _forget(fg, c_prev, cpre_prev):
+    """f * c_prev (cpre_prev, the state before its clip, is there for a wrong restatement to use)"""
+    return fg * c_prev
+
+
 def net(flat, vec, labels, qps, gop, qp_scale=1.0, mask_h=None, mask_fc2=None):
     """net_CTU64.net with isdrop = (masks given; [20 n, 448] and [20 n, 336], rows 20 b + p).  dict(probs [20 n,21], C, H [20 n,448]
-    (c after the clip, h not dropped, computed with slot p as the input), loss_list, accuracy_list, total_loss)."""
+    (c after the clip, h not dropped, computed with slot p as the input), Cpre (c before the clip), loss_list, accuracy_list,
+    total_loss).  _cell_clip, _carry, _forget and train_ref._lrelu are looked up when called: tests/train_edges.py patches them to make
+    deliberately wrong restatements."""
     tv = views(flat)
     n, dt = vec.shape[0], flat.dtype   # float64; float32 only to measure what fp32 arithmetic costs (the GPU tests' bounds)
     x = torch.as_tensor(np.asarray(vec, dtype=np.float64)).to(dt)
@@ -56,6 +72,7 @@ def net(flat, vec, labels, qps, gop, qp_scale=1.0, mask_h=None, mask_fc2=None):
     P = [[None] * 3 for _ in range(STEPS)]
     Cs = [[None] * 3 for _ in range(STEPS)]
     Hs = [[None] * 3 for _ in range(STEPS)]
+    Ps = [[None] * 3 for _ in range(STEPS)]
     o2 = 0
     for ci, (tag, hid, n2, n3, col) in enumerate(CELLS):
         pre = "RNN%s/" % tag
@@ -63,50 +80,38 @@ def net(flat, vec, labels, qps, gop, qp_scale=1.0, mask_h=None, mask_fc2=None):
         W2, b2, W3, b3 = tv[pre + "fc2/full_connect_w"], tv[pre + "fc2/full_connect_b"], tv[pre + "fc3/full_connect_w"], tv[pre + "fc3/full_connect_b"]
         c = torch.zeros(n, hid, dtype=dt)
         h = torch.zeros(n, hid, dtype=dt)
+        cpre = torch.zeros(n, hid, dtype=dt)
         for ts in range(STEPS):
             p = STEPS - 1 - ts                                                           # cell_inputs.reverse()
             z = torch.cat([x[:, p, col:col + hid], h], 1) @ K + bK
             i, j, f, o = torch.split(z, hid, dim=1)
-            c = torch.clamp(torch.sigmoid(f + 1.0) * c + torch.sigmoid(i) * torch.tanh(j), -5.0, 5.0)
-            h = torch.sigmoid(o) * torch.tanh(c)
+            cpre = _forget(torch.sigmoid(f + 1.0), c, cpre) + torch.sigmoid(i) * torch.tanh(j)
+            cc = _cell_clip(cpre)
+            h = torch.sigmoid(o) * torch.tanh(cc)
+            c = _carry(cpre, cc)
             efs = torch.cat([qp[:, ts:ts + 1], onehot[:, ts]], 1)                        # :125: indexed by the unrolled step
             out = h if mh is None else h / 0.5 * mh[:, p, col:col + hid]                 # DropoutWrapper on the OUTPUT only
-            h2 = F.leaky_relu(torch.cat([out, efs], 1) @ W2 + b2, 0.2)
+            h2 = train_ref._lrelu(torch.cat([out, efs], 1) @ W2 + b2)                    # leaky_relu, alpha 0.2
             if m2 is not None:
                 h2 = h2 / 0.8 * m2[:, p, o2:o2 + n2]
             P[p][ci] = torch.sigmoid(torch.cat([h2, efs], 1) @ W3 + b3)
-            Cs[p][ci], Hs[p][ci] = c, h
+            Cs[p][ci], Hs[p][ci], Ps[p][ci] = cc, h, cpre
         o2 += n2
     probs = torch.stack([torch.cat(P[p], 1) for p in range(STEPS)], 1).reshape(n * STEPS, 21)
     C = torch.stack([torch.cat(Cs[p], 1) for p in range(STEPS)], 1).reshape(n * STEPS, 448)
     H = torch.stack([torch.cat(Hs[p], 1) for p in range(STEPS)], 1).reshape(n * STEPS, 448)
+    Cpre = torch.stack([torch.cat(Ps[p], 1) for p in range(STEPS)], 1).reshape(n * STEPS, 448)
     lab = np.asarray(labels, dtype=np.float64).reshape(n * STEPS, 16)
     l3 = loss_list(probs, lab.astype(np.float64 if dt == torch.float64 else np.float32))
-    return {"probs": probs, "C": C, "H": H, "loss_list": l3, "accuracy_list": torch.as_tensor(train_ref.accuracy(probs.detach().numpy(), lab)),
-            "total_loss": l3[2] + l3[1] + l3[0]}
+    return {"probs": probs, "C": C, "H": H, "Cpre": Cpre, "loss_list": l3,
+            "accuracy_list": torch.as_tensor(train_ref.accuracy(probs.detach().numpy(), lab)), "total_loss": l3[2] + l3[1] + l3[0]}
 
 
 def loss_list(probs, lab):
     """:160-176 labels per row and :220-233 (is_balance = True; counts over all rows at once) -> [loss_64, loss_32, loss_16]"""
     m = lab.shape[0]
     y = torch.as_tensor(lab).reshape(m, 4, 4, 1)
-    relu, ap, eps = torch.relu, train_ref._avgpool, 1e-12
-    y16 = relu(y - 2).reshape(m, 16)
-    y32 = (relu(ap(y, 2) - 1) - relu(ap(y, 2) - 2)).reshape(m, 4)
-    y64 = (relu(ap(y, 4) - 0) - relu(ap(y, 4) - 1)).reshape(m, 1)
-    v32 = (relu(ap(y, 2) - 0) - relu(ap(y, 2) - 1)).reshape(m, 4)
-    v16 = (relu(y - 1) - relu(y - 2)).reshape(m, 16)
-    p64, p32, p16 = probs[:, :1], probs[:, 1:5], probs[:, 5:]
-
-    def cnz(t):
-        return float((t != 0).sum())
-
-    l64 = (torch.sum(-(y64 * torch.log(p64 + eps))) / (cnz(y64) + eps) +
-           torch.sum(-((1 - y64) * torch.log((1 - p64) + eps))) / (cnz(1 - y64) + eps)) / 2
-    l32 = (torch.sum(-(y32 * torch.log(p32 + eps)) * v32) / (cnz(y32 * v32) + eps) +
-           torch.sum(-((1 - y32) * torch.log((1 - p32) + eps)) * v32) / (cnz((1 - y32) * v32) + eps)) / 2
-    l16 = (torch.sum(-(y16 * torch.log(p16 + eps)) * v16) / (cnz(y16 * v16) + eps) +
-           torch.sum(-((1 - y16) * torch.log((1 - p16) + eps)) * v16) / (cnz((1 - y16) * v16) + eps)) / 2
+    l64, l32, l16 = train_ref.balanced_loss(train_ref.split_labels(y), probs[:, :1], probs[:, 1:5], probs[:, 5:])
     return torch.stack([l64, l32, l16])
 
 
