@@ -1,8 +1,9 @@
-// ethcnn_lstm_train.cpp -- host side of the ETH-LSTM trainer (include/ethcnn.h "ETH-LSTM training"): buffers, the GEMM descriptor
-// tables, the step and evaluation sequences (kernels: ethcnn_lstm_train_kernels.hip, launch order: ethcnn_lstm_train.h).
+// ethcnn_lstm_train.cpp -- an ETH-LSTM trainer's state (include/ethcnn.h "ETH-LSTM training"): options, weight / accumulator /
+// gradient blobs, workspaces, the GEMM descriptors over them, the QP list, and the entry points that touch nothing else.  Everything
+// that enqueues a step, and the sample sets, are the engine's (ethcnn_lstm_train_group.cpp); the solo entry points at the end of this
+// file hand over to the trainer's own engine of K = 1.
 #include <algorithm>
 #include <cmath>
-#include <cstdarg>
 #include <cstdio>
 #include <cstring>
 #include <new>
@@ -10,11 +11,11 @@
 #include <vector>
 
 #include "ethcnn_ctx.h"
-#include "ethcnn_lstm_samples.h"
 #include "ethcnn_lstm_train.h"
 #include "ethcnn_lstm_train_host.h"
 
 using namespace ethcnn::lstm_train;
+using ethcnn::train::add_desc;
 using ethcnn::kLstmBlobFloats;
 using ethcnn::kLstmTensors;
 using ethcnn::kNumLstmTensors;
@@ -35,21 +36,6 @@ int lstm_tensor_off(const std::string& name) {
 }
 }  // namespace
 
-static int terr(ethcnn_lstm_trainer* t, int code, const char* fmt, ...) {
-    char buf[512];
-    va_list ap;
-    va_start(ap, fmt);
-    std::vsnprintf(buf, sizeof buf, fmt, ap);
-    va_end(ap);
-    t->err = buf;
-    return code;
-}
-#define TCHK(t, call)                                                                                           \
-    do {                                                                                                        \
-        hipError_t e_ = (call);                                                                                 \
-        if (e_ != hipSuccess) return terr((t), ETHCNN_ERR_DEVICE, "%s failed: %s", #call, hipGetErrorString(e_)); \
-    } while (0)
-
 template <typename T>
 static int talloc(ethcnn_lstm_trainer* t, T** p, size_t count) {
     void* q = nullptr;
@@ -60,16 +46,6 @@ static int talloc(ethcnn_lstm_trainer* t, T** p, size_t count) {
     t->allocs.push_back(q);
     *p = (T*)q;
     return 0;
-}
-
-static void add_desc(GemmGroup& g, GemmDesc d) {
-    d.tiles_n = (d.N + 63) / 64;
-    d.tile_begin = g.tiles;
-    g.tiles += ((d.M + 63) / 64) * d.tiles_n;
-    d.nseg = 1;
-    d.kseg[0] = 0;
-    if (d.msplit == 0) d.msplit = d.M;
-    g.d[g.n++] = d;
 }
 
 // input projections of `rows` rows: Z_cell = X[:, cell columns] x kernel[0:H, :]
@@ -119,62 +95,7 @@ GemmGroup lstm_grad_group(const ethcnn_lstm_trainer* t, int rows) {
     return g;
 }
 
-float lstm_lr_at(const ethcnn_lstm_trainer* t, int64_t step) {  // tf.train.exponential_decay(..., staircase=True)
-    const double p = std::floor((double)step / (double)t->opt.decay_steps);
-    return (float)((double)t->opt.lr_init * std::pow((double)t->opt.decay_rate, p));
-}
-
-// gather .. heads forward of nb samples; P / lab: where this piece's probabilities and labels go
-static void enqueue_forward(ethcnn_lstm_trainer* t, int set, int nb, const int32_t* d_idx, uint64_t step, int dropout, float* P,
-                            float* lab, const GemmGroup* grp, int tiles) {
-    hipStream_t s = t->c->stream;
-    GatherArgs a{};
-    a.data = t->data[set];
-    a.nrec = t->nrec[set];
-    a.idx_in = d_idx;
-    a.idx_out = t->idx;
-    a.seed = t->opt.seed;
-    a.step = step;
-    a.qp_scale = t->qp_scale;
-    LstmBufs u = t->u;
-    u.P = P;
-    u.lab = lab;
-    launch_gather(s, nb, a, u);
-    ethcnn::train::launch_gemm(s, grp, tiles);
-    launch_fwd(s, nb, u, t->W, t->o);
-    launch_heads_fwd(s, nb, u, t->W, t->o, t->opt.seed, step, dropout);
-    t->last_rows = nb * kSteps;
-}
-
-static int enqueue_step(ethcnn_lstm_trainer* t, int64_t step, bool explicit_batch) {
-    hipStream_t s = t->c->stream;
-    t->c->done_armed = 0;  // the context's completion word does not cover these launches
-    const int dropout = t->opt.dropout ? 1 : 0;
-    enqueue_forward(t, ETHCNN_TRAIN_SET_TRAIN, t->B, explicit_batch ? t->idx_in : nullptr, (uint64_t)step, dropout, t->u.P, t->u.lab,
-                    t->g_fwd, t->t_fwd);
-    ethcnn::train::launch_loss(s, t->u.P, t->u.lab, t->B * kSteps, t->stats, t->u.dZ3);
-    launch_heads_bwd(s, t->B, t->u, t->W, t->o, dropout);
-    launch_bwd(s, t->B, t->u, t->W, t->o);
-    ethcnn::train::launch_gemm(s, t->g_bwd, t->t_bwd);
-    launch_norm_update(s, t->W, t->acc, t->grad, t->part, t->opt.clip_norm, lstm_lr_at(t, step), t->opt.momentum, (long)kLstmBlobFloats,
-                       t->stats);
-    TCHK(t, hipGetLastError());
-    return 0;
-}
-
-static int read_stats(ethcnn_lstm_trainer* t, float* loss3, float* acc3) {
-    float st[8];
-    TCHK(t, hipMemcpyAsync(st, t->stats, sizeof st, hipMemcpyDeviceToHost, t->c->stream));
-    TCHK(t, hipStreamSynchronize(t->c->stream));
-    for (int i = 0; i < 3; ++i) {
-        if (loss3) loss3[i] = st[i];
-        if (acc3) acc3[i] = st[3 + i];
-    }
-    return 0;
-}
-
-extern "C" int ethcnn_lstm_train_create(ethcnn_ctx* c, const ethcnn_lstm_train_options* opt, ethcnn_lstm_trainer** out) {
-    if (!c || !opt || !out) return ETHCNN_ERR_ARG;
+int lstm_member_create(ethcnn_ctx* c, const ethcnn_lstm_train_options* opt, ethcnn_lstm_trainer** out) {
     *out = nullptr;
     if (opt->batch <= 0 || opt->batch > 4096) return set_err(c, ETHCNN_ERR_ARG, "batch must be in 1..4096, got %d", opt->batch);
     if (opt->decay_steps <= 0) return set_err(c, ETHCNN_ERR_ARG, "decay_steps must be positive");
@@ -229,12 +150,9 @@ extern "C" int ethcnn_lstm_train_create(ethcnn_ctx* c, const ethcnn_lstm_train_o
     rc = rc ? rc : talloc(t, &u.dZ3, R * kOut);
     rc = rc ? rc : talloc(t, &u.dZ2, R * kFc2);
     rc = rc ? rc : talloc(t, &u.dH, R * kVec);
-    rc = rc ? rc : talloc(t, &t->g_fwd, 1);
-    rc = rc ? rc : talloc(t, &t->g_bwd, 1);
-    rc = rc ? rc : talloc(t, &t->g_eval, 1);
     if (rc) {
         const std::string why = t->err;
-        ethcnn_lstm_train_destroy(t);
+        lstm_member_destroy(t);
         return set_err(c, rc, "%s", why.c_str());
     }
     // zeroed once: rows past a short evaluation piece are computed by the projection GEMM but never read
@@ -242,27 +160,19 @@ extern "C" int ethcnn_lstm_train_create(ethcnn_ctx* c, const ethcnn_lstm_train_o
     for (void* p : {(void*)t->W, (void*)t->acc, (void*)t->grad}) e = e ? e : hipMemsetAsync(p, 0, kLstmBlobFloats * 4, c->stream);
     e = e ? e : hipMemsetAsync(u.X, 0, R * kVec * 4, c->stream);
     e = e ? e : hipMemsetAsync(t->stats, 0, 32, c->stream);
-    const GemmGroup gf = lstm_proj_group(t, t->B * kSteps), gb = lstm_grad_group(t, t->B * kSteps), ge = lstm_proj_group(t, t->cap * kSteps);
-    t->t_fwd = gf.tiles; t->t_bwd = gb.tiles; t->t_eval = ge.tiles;
-    e = e ? e : hipMemcpy(t->g_fwd, &gf, sizeof gf, hipMemcpyHostToDevice);
-    e = e ? e : hipMemcpy(t->g_bwd, &gb, sizeof gb, hipMemcpyHostToDevice);
-    e = e ? e : hipMemcpy(t->g_eval, &ge, sizeof ge, hipMemcpyHostToDevice);
     e = e ? e : hipStreamSynchronize(c->stream);
     if (e != hipSuccess) {
-        ethcnn_lstm_train_destroy(t);
+        lstm_member_destroy(t);
         return set_err(c, ETHCNN_ERR_DEVICE, "LSTM trainer setup: %s", hipGetErrorString(e));
     }
     *out = t;
     return ETHCNN_OK;
 }
 
-extern "C" void ethcnn_lstm_train_destroy(ethcnn_lstm_trainer* t) {
-    if (!t) return;
+void lstm_member_destroy(ethcnn_lstm_trainer* t) {
     (void)hipSetDevice(t->c->device);
     (void)hipStreamSynchronize(t->c->stream);
     for (void* p : t->allocs) (void)hipFree(p);
-    for (int s = 0; s < 2; ++s)
-        if (t->data[s]) (void)hipFree(t->data[s]);
     delete t;
 }
 
@@ -321,240 +231,63 @@ extern "C" int ethcnn_lstm_train_set_qps(ethcnn_lstm_trainer* t, const int* qps,
     return 0;
 }
 
-// the pass every kept sample takes on the device (k_lstm_check): *first = the first sample that fails it, n when none does
-static hipError_t first_bad_sample(ethcnn_lstm_trainer* t, const uint8_t* p, size_t n, long* first) {
-    const int nblk = (int)std::min<size_t>(1024, n);
-    long* d_bad = nullptr;
-    std::vector<long> bad((size_t)nblk);
-    hipError_t e = hipMalloc(&d_bad, sizeof(long) * nblk);
-    if (e == hipSuccess) {
-        launch_check(t->c->stream, p, (long)n, d_bad, nblk);
-        e = hipGetLastError();
+extern "C" int64_t ethcnn_lstm_train_debug_rows(const ethcnn_lstm_trainer* t) { return t ? t->last_rows : -1; }
+
+// ---- the solo trainer: an engine of K = 1 over the trainer itself; its messages are the trainer's
+static int from_engine(ethcnn_lstm_trainer* t, int rc) {
+    if (rc) t->err = t->eng->err;
+    return rc;
+}
+
+extern "C" int ethcnn_lstm_train_create(ethcnn_ctx* c, const ethcnn_lstm_train_options* opt, ethcnn_lstm_trainer** out) {
+    if (!c || !opt || !out) return ETHCNN_ERR_ARG;
+    ethcnn_lstm_trainer* t = nullptr;
+    if (int rc = lstm_member_create(c, opt, &t)) return rc;
+    if (int rc = lstm_engine_create(c, {t}, false, &t->eng)) {
+        lstm_member_destroy(t);
+        return rc;
     }
-    if (e == hipSuccess) e = hipMemcpyAsync(bad.data(), d_bad, sizeof(long) * nblk, hipMemcpyDeviceToHost, t->c->stream);
-    if (e == hipSuccess) e = hipStreamSynchronize(t->c->stream);
-    (void)hipFree(d_bad);
-    if (e == hipSuccess) *first = *std::min_element(bad.begin(), bad.end());
-    return e;
+    t->solo = true;
+    *out = t;
+    return ETHCNN_OK;
+}
+
+extern "C" void ethcnn_lstm_train_destroy(ethcnn_lstm_trainer* t) {
+    if (!t) return;
+    (void)hipSetDevice(t->c->device);
+    (void)hipStreamSynchronize(t->c->stream);
+    if (t->solo) lstm_engine_destroy(t->eng);
+    lstm_member_destroy(t);
 }
 
 extern "C" int ethcnn_lstm_train_set_samples(ethcnn_lstm_trainer* t, int set, const uint8_t* rec, size_t nbytes) {
-    if (!t) return ETHCNN_ERR_ARG;
-    if (set != 0 && set != 1) return terr(t, ETHCNN_ERR_ARG, "set must be 0 (train) or 1 (valid), got %d", set);
-    if (!rec || nbytes == 0) return terr(t, ETHCNN_ERR_ARG, "no sample records");
-    if (nbytes % kRecBytes) return terr(t, ETHCNN_ERR_FORMAT, "%zu bytes is not a whole number of %d-byte samples", nbytes, kRecBytes);
-    const size_t nall = nbytes / kRecBytes;
-    // SELECT_QP_LIST (input_data.py:126-134): keep the samples whose qps[0] is in the list
-    std::vector<size_t> keep;
-    keep.reserve(nall);
-    for (size_t i = 0; i < nall; ++i) {
-        bool on = t->nqps == 0;
-        float q;
-        std::memcpy(&q, rec + i * kRecBytes + 64, 4);
-        for (int k = 0; k < t->nqps && !on; ++k) on = q == (float)t->qps[k];
-        if (on) keep.push_back(i);
-    }
-    if (keep.empty()) return terr(t, ETHCNN_ERR_FORMAT, "none of the %zu samples has a selected QP", nall);
-    if (keep.size() > 0x7fffffffull / kSteps) return terr(t, ETHCNN_ERR_ARG, "too many samples");
-    TCHK(t, hipSetDevice(t->c->device));
-    TCHK(t, hipStreamSynchronize(t->c->stream));
-    const size_t n = keep.size();
-    void* p = nullptr;
-    if (hipMalloc(&p, n * kRecBytes) != hipSuccess) {
-        (void)hipGetLastError();
-        return terr(t, ETHCNN_ERR_NOMEM, "%zu bytes of samples do not fit in device memory", n * kRecBytes);
-    }
-    hipError_t e = hipSuccess;
-    for (size_t j = 0; j < n && e == hipSuccess;) {  // runs of consecutive kept samples, one copy each
-        size_t k = j + 1;
-        while (k < n && keep[k] == keep[k - 1] + 1) ++k;
-        e = hipMemcpy((uint8_t*)p + j * kRecBytes, rec + keep[j] * kRecBytes, (k - j) * kRecBytes, hipMemcpyHostToDevice);
-        j = k;
-    }
-    long first = 0;
-    if (e == hipSuccess) e = first_bad_sample(t, (const uint8_t*)p, n, &first);
-    if (e != hipSuccess) {
-        (void)hipFree(p);
-        return terr(t, ETHCNN_ERR_DEVICE, "sample upload / check: %s", hipGetErrorString(e));
-    }
-    if (first < (long)n) {
-        (void)hipFree(p);
-        return terr(t, ETHCNN_ERR_FORMAT, "sample %zu: a QP outside 0..51, a label outside 0..3 or a non-finite vector element",
-                    keep[(size_t)first]);
-    }
-    if (t->data[set]) (void)hipFree(t->data[set]);
-    t->data[set] = (uint8_t*)p;
-    t->nrec[set] = (int64_t)n;
-    return 0;
+    return t ? from_engine(t, ethcnn_lstm_train_group_set_samples(t->eng, set, rec, nbytes)) : ETHCNN_ERR_ARG;
 }
 
-// the same from an ETH-LSTM sample set already in HBM (include/ethcnn.h "ETH-LSTM sample sets"): the QP selection on the slot-0 QP
-// floats (the only bytes that leave HBM), then the buffer adopted (take, everything kept) or a compacting device-to-device copy
 extern "C" int ethcnn_lstm_train_set_samples_from(ethcnn_lstm_trainer* t, int set, ethcnn_lstm_samples* sm, int take) {
-    namespace ls = ethcnn::lstm_samples;
-    if (!t) return ETHCNN_ERR_ARG;
-    if (set != 0 && set != 1) return terr(t, ETHCNN_ERR_ARG, "set must be 0 (train) or 1 (valid), got %d", set);
-    if (!sm || !sm->built || sm->count == 0) return terr(t, ETHCNN_ERR_ARG, "no sample records (the sample set is not built or empty)");
-    if (sm->c != t->c) return terr(t, ETHCNN_ERR_ARG, "the sample set and the trainer live on different contexts");
-    const size_t nall = (size_t)sm->count;
-    hipStream_t s = t->c->stream;
-    TCHK(t, hipSetDevice(t->c->device));
-    TCHK(t, hipStreamSynchronize(s));
-    // SELECT_QP_LIST, as in ethcnn_lstm_train_set_samples
-    std::vector<int64_t> keep;
-    if (t->nqps) {
-        float* d_q = nullptr;
-        std::vector<float> q(nall);
-        hipError_t e = hipMalloc((void**)&d_q, nall * 4);
-        if (e == hipSuccess) {
-            ls::launch_qp0(s, sm->data, (long)nall, d_q);
-            e = hipGetLastError();
-        }
-        if (e == hipSuccess) e = hipMemcpyAsync(q.data(), d_q, nall * 4, hipMemcpyDeviceToHost, s);
-        if (e == hipSuccess) e = hipStreamSynchronize(s);
-        (void)hipFree(d_q);
-        if (e != hipSuccess) return terr(t, ETHCNN_ERR_DEVICE, "sample selection: %s", hipGetErrorString(e));
-        for (size_t i = 0; i < nall; ++i) {
-            bool on = false;
-            for (int k = 0; k < t->nqps && !on; ++k) on = q[i] == (float)t->qps[k];
-            if (on) keep.push_back((int64_t)i);
-        }
-        if (keep.empty()) return terr(t, ETHCNN_ERR_FORMAT, "none of the %zu samples has a selected QP", nall);
-    }
-    const bool all = !t->nqps || keep.size() == nall;
-    const size_t n = all ? nall : keep.size();
-    if (n > 0x7fffffffull / kSteps) return terr(t, ETHCNN_ERR_ARG, "too many samples");
-    uint8_t* p = sm->data;
-    const bool adopt = all && take;
-    if (!adopt) {
-        if (hipMalloc((void**)&p, n * kRecBytes) != hipSuccess) {
-            (void)hipGetLastError();
-            return terr(t, ETHCNN_ERR_NOMEM, "%zu bytes of samples do not fit in device memory", n * kRecBytes);
-        }
-        hipError_t e = hipSuccess;
-        int64_t* d_keep = nullptr;
-        if (all) {
-            e = hipMemcpyAsync(p, sm->data, n * kRecBytes, hipMemcpyDeviceToDevice, s);
-        } else {
-            e = hipMalloc((void**)&d_keep, n * 8);
-            if (e == hipSuccess) e = hipMemcpyAsync(d_keep, keep.data(), n * 8, hipMemcpyHostToDevice, s);
-            if (e == hipSuccess) {
-                ls::launch_compact(s, sm->data, d_keep, (long)n, p, t->c->cus > 0 ? t->c->cus : 256);
-                e = hipGetLastError();
-            }
-        }
-        if (e == hipSuccess) e = hipStreamSynchronize(s);
-        if (d_keep) (void)hipFree(d_keep);
-        if (e != hipSuccess) {
-            (void)hipFree(p);
-            return terr(t, ETHCNN_ERR_DEVICE, "sample copy: %s", hipGetErrorString(e));
-        }
-    }
-    long first = 0;
-    const hipError_t e = first_bad_sample(t, p, n, &first);
-    if (e != hipSuccess || first < (long)n) {
-        if (!adopt) (void)hipFree(p);
-        if (e != hipSuccess) return terr(t, ETHCNN_ERR_DEVICE, "sample check: %s", hipGetErrorString(e));
-        return terr(t, ETHCNN_ERR_FORMAT, "sample %lld: a QP outside 0..51, a label outside 0..3 or a non-finite vector element",
-                    (long long)(all ? (int64_t)first : keep[(size_t)first]));
-    }
-    if (t->data[set]) (void)hipFree(t->data[set]);
-    t->data[set] = p;
-    t->nrec[set] = (int64_t)n;
-    if (take) {  // the set is empty afterwards: its buffer is the trainer's now, or (after a compacting copy) is freed
-        if (!adopt) (void)hipFree(sm->data);
-        sm->data = nullptr;
-        sm->count = sm->skipped = 0;
-        sm->built = false;
-    }
-    return 0;
+    return t ? from_engine(t, ethcnn_lstm_train_group_set_samples_from(t->eng, set, sm, take)) : ETHCNN_ERR_ARG;
 }
 
 extern "C" int64_t ethcnn_lstm_train_num_samples(const ethcnn_lstm_trainer* t, int set) {
-    return (t && (set == 0 || set == 1)) ? t->nrec[set] : -1;
-}
-
-extern "C" int64_t ethcnn_lstm_train_debug_rows(const ethcnn_lstm_trainer* t) { return t ? t->last_rows : -1; }
-
-static int ready(ethcnn_lstm_trainer* t) {
-    if (!t->data[ETHCNN_TRAIN_SET_TRAIN]) return terr(t, ETHCNN_ERR_ARG, "no training samples (ethcnn_lstm_train_set_samples)");
-    return 0;
+    return t ? ethcnn_lstm_train_group_num_samples(t->eng, 0, set) : -1;
 }
 
 extern "C" int ethcnn_lstm_train_run(ethcnn_lstm_trainer* t, int64_t first_step, int64_t nsteps) {
-    if (!t) return ETHCNN_ERR_ARG;
-    if (first_step < 0 || nsteps < 0) return terr(t, ETHCNN_ERR_ARG, "negative step");
-    if (int rc = ready(t)) return rc;
-    TCHK(t, hipSetDevice(t->c->device));
-    for (int64_t i = 0; i < nsteps; ++i)
-        if (int rc = enqueue_step(t, first_step + i, false)) return rc;
-    return 0;
+    return t ? from_engine(t, ethcnn_lstm_train_group_run(t->eng, first_step, nsteps)) : ETHCNN_ERR_ARG;
 }
 
 extern "C" int ethcnn_lstm_train_last_stats(ethcnn_lstm_trainer* t, float loss3[3], float acc3[3]) {
-    if (!t) return ETHCNN_ERR_ARG;
-    TCHK(t, hipSetDevice(t->c->device));
-    return read_stats(t, loss3, acc3);
+    return t ? from_engine(t, ethcnn_lstm_train_group_last_stats(t->eng, loss3, acc3)) : ETHCNN_ERR_ARG;
 }
 
 extern "C" int ethcnn_lstm_train_step_indices(ethcnn_lstm_trainer* t, int64_t step, const int32_t* idx, int n, float loss3[3],
                                               float acc3[3]) {
-    if (!t) return ETHCNN_ERR_ARG;
-    if (int rc = ready(t)) return rc;
-    if (!idx || n != t->B) return terr(t, ETHCNN_ERR_ARG, "an explicit batch needs %d indices", t->B);
-    if (step < 0) return terr(t, ETHCNN_ERR_ARG, "negative step");
-    for (int i = 0; i < n; ++i)
-        if (idx[i] < 0 || idx[i] >= t->nrec[0]) return terr(t, ETHCNN_ERR_ARG, "sample index %d outside 0..%lld", idx[i], (long long)t->nrec[0] - 1);
-    TCHK(t, hipSetDevice(t->c->device));
-    hipStream_t s = t->c->stream;
-    TCHK(t, hipMemcpyAsync(t->idx_in, idx, sizeof(int32_t) * n, hipMemcpyHostToDevice, s));
-    TCHK(t, hipStreamSynchronize(s));
-    if (int rc = enqueue_step(t, step, true)) return rc;
-    return read_stats(t, loss3, acc3);
+    return t ? from_engine(t, ethcnn_lstm_train_group_step_indices(t->eng, step, idx, n, loss3, acc3)) : ETHCNN_ERR_ARG;
 }
 
 extern "C" int ethcnn_lstm_train_evaluate(ethcnn_lstm_trainer* t, int set, const int32_t* idx, int64_t n, float loss3[3], float acc3[3],
                                           float* probs) {
-    if (!t) return ETHCNN_ERR_ARG;
-    if (set != 0 && set != 1) return terr(t, ETHCNN_ERR_ARG, "set must be 0 (train) or 1 (valid), got %d", set);
-    if (!t->data[set]) return terr(t, ETHCNN_ERR_ARG, "no samples in set %d", set);
-    if (n <= 0 || n > 0x7fffffffll / kOut / kSteps || (!idx && n > t->nrec[set])) return terr(t, ETHCNN_ERR_ARG, "bad sample count %lld", (long long)n);
-    if (idx)
-        for (int64_t i = 0; i < n; ++i)
-            if (idx[i] < 0 || idx[i] >= t->nrec[set]) return terr(t, ETHCNN_ERR_ARG, "sample index %d outside 0..%lld", idx[i], (long long)t->nrec[set] - 1);
-    TCHK(t, hipSetDevice(t->c->device));
-    hipStream_t s = t->c->stream;
-    t->c->done_armed = 0;
-    std::vector<int32_t> ids;
-    if (!idx) {
-        ids.resize((size_t)n);
-        for (int64_t i = 0; i < n; ++i) ids[(size_t)i] = (int32_t)i;
-        idx = ids.data();
-    }
-    const size_t rows = (size_t)n * kSteps;
-    float *Pn = nullptr, *Ln = nullptr;
-    int32_t* In = nullptr;
-    if (hipMalloc(&Pn, rows * kOut * 4) != hipSuccess || hipMalloc(&Ln, rows * 16 * 4) != hipSuccess ||
-        hipMalloc(&In, (size_t)n * 4) != hipSuccess) {
-        (void)hipGetLastError();
-        (void)hipFree(Pn); (void)hipFree(Ln); (void)hipFree(In);
-        return terr(t, ETHCNN_ERR_NOMEM, "cannot allocate the evaluation buffers of %lld samples", (long long)n);
-    }
-    hipError_t e = hipMemcpyAsync(In, idx, (size_t)n * 4, hipMemcpyHostToDevice, s);
-    for (int64_t c0 = 0; e == hipSuccess && c0 < n; c0 += t->cap) {
-        const int nb = (int)std::min<int64_t>(t->cap, n - c0);
-        enqueue_forward(t, set, nb, In + c0, 0, 0, Pn + c0 * kSteps * kOut, Ln + c0 * kSteps * 16, t->g_eval, t->t_eval);
-        e = hipGetLastError();
-    }
-    if (e == hipSuccess) {
-        ethcnn::train::launch_loss(s, Pn, Ln, (int)rows, t->stats, nullptr);  // ONE batch over all n x 20 rows
-        e = hipGetLastError();
-    }
-    if (e == hipSuccess && probs) e = hipMemcpyAsync(probs, Pn, rows * kOut * 4, hipMemcpyDeviceToHost, s);
-    if (e == hipSuccess) e = hipStreamSynchronize(s);
-    (void)hipFree(Pn); (void)hipFree(Ln); (void)hipFree(In);
-    if (e != hipSuccess) return terr(t, ETHCNN_ERR_DEVICE, "evaluation: %s", hipGetErrorString(e));
-    return read_stats(t, loss3, acc3);
+    return t ? from_engine(t, ethcnn_lstm_train_group_evaluate(t->eng, set, idx, n, loss3, acc3, probs)) : ETHCNN_ERR_ARG;
 }
 
 extern "C" int ethcnn_lstm_train_debug_fetch(ethcnn_lstm_trainer* t, int which, float* out, size_t nfloats) {

@@ -1,5 +1,6 @@
 // ethcnn_lstm_train.h -- shared between the ETH-LSTM training kernels (ethcnn_lstm_train_kernels.hip) and their host side
-// (ethcnn_lstm_train.cpp).  Graph: ETH-LSTM_Training_LDP/net_CTU64.py:85-276, samples: input_data.py:88-147, optimiser:
+// (ethcnn_lstm_train.cpp: a trainer's state; ethcnn_lstm_train_group.cpp: the step engine behind the solo and the group entry
+// points).  Graph: ETH-LSTM_Training_LDP/net_CTU64.py:85-276, samples: input_data.py:88-147, optimiser:
 // train_LSTM_CTU64.py:42-52.
 //
 // A sample is 37264 bytes: 64 info bytes, then 20 time slots of 465 float32 [qp | 16 depth labels | 448-vector]
@@ -11,25 +12,28 @@
 // reversed: unrolled step ts (input slot 19 - ts) is given qp_list[ts] and the GOP one-hot of slot ts (:125), so row (b, p) sees
 // the QP and the GOP position of slot 19 - p.  This is how the shipped models were trained; it is transcribed, not corrected.
 //
-// One training step is 10 launches on the context's stream:
-//   1 k_lstm_gather     one block per row: draw / read the sample index, copy the 448-vector and the 16 labels, form the five
-//                       external features [qp / 51 (* qp_scale) | one-hot(i_frame_in_GOP)] of slot 19 - p
-//   2 k_train_gemm      input projections of all 20 slots and all three cells: X[R, H] x kernel[0:H, :] -> Z [R, 4H], one grouped
-//                       launch of the CNN trainer's MFMA 32x32x2 GEMM (ethcnn_train_kernels.hip), three members
-//   3 k_lstm_fwd        recurrence: a block owns 16 batch samples of one cell and walks the 20 steps, h_prev x kernel[H:2H, :] as
-//                       v_mfma_f32_16x16x4_f32 chains (a wave owns hidden-unit tiles and their four gates, so the gate math needs no
-//                       exchange; h goes round through LDS); keeps gates, c before and after the clip, and h per row
-//   4 k_lstm_heads_fwd  one block per row: dropout on the cell output (keep 0.5; the carried h is not dropped), fc2 + leaky-ReLU +
-//                       dropout (keep 0.8), fc3 + sigmoid of the three cells
-//   5 k_train_loss      one block: batch-global counts over all R rows, loss / accuracy lists, dL/dlogit (the CNN trainer's kernel:
-//                       net_CTU64.py:160-176,220-233,263-271 are the CNN graph's labels, balanced loss and accuracy over R rows)
-//   6 k_lstm_heads_bwd  one block per row: dlogit -> d fc2 -> d(cell output)
-//   7 k_lstm_bwd        recurrence backwards (slot 0 first), same ownership as 3: d gates per row, dh carried through
-//                       kernel[H:2H, :]^T (MFMA 16x16x4), dc through the forget gate; zero where c was clipped
-//   8 k_train_gemm      every weight gradient as one grouped GEMM with K = R: [x | h_prev | 1]^T x dZ for the three kernels and
-//                       biases, [h (dropped) | ef | 1]^T x dZ2 and [h2 (dropped) | ef | 1]^T x dZ3 for the heads; blob layout
-//   9 k_lstm_norm       partial sums of squares of the 760078 gradient floats: 512 blocks, each a fixed range and a fixed order
-//  10 k_lstm_update     every block sums the 512 partials in index order -> global norm, clip_by_global_norm's factor, momentum update
+// There is ONE step path.  It trains K >= 1 models ("members") of one batch size at once; a solo trainer is the case K = 1.  One
+// training step is 10 launches on the context's stream, each over all K members (grids: "the member table" below):
+//   1 k_lstm_group_gather     one block per row: draw / read the sample index, copy the 448-vector and the 16 labels, form the five
+//                             external features [qp / 51 (* qp_scale) | one-hot(i_frame_in_GOP)] of slot 19 - p
+//   2 k_group_gemm            input projections of all 20 slots and all three cells: X[R, H] x kernel[0:H, :] -> Z [R, 4H], one
+//                             grouped launch of the CNN trainer's MFMA 32x32x2 GEMM (ethcnn_train_kernels.hip), three descriptors
+//   3 k_lstm_group_fwd        recurrence: a block owns 16 batch samples of one cell and walks the 20 steps, h_prev x kernel[H:2H, :]
+//                             as v_mfma_f32_16x16x4_f32 chains (a wave owns hidden-unit tiles and their four gates, so the gate math
+//                             needs no exchange; h goes round through LDS); keeps gates, c before and after the clip, and h per row
+//   4 k_lstm_group_heads_fwd  one block per row: dropout on the cell output (keep 0.5; the carried h is not dropped), fc2 +
+//                             leaky-ReLU + dropout (keep 0.8), fc3 + sigmoid of the three cells
+//   5 k_group_loss            one block per member: batch-global counts over all R rows, loss / accuracy lists, dL/dlogit (the CNN
+//                             trainer's kernel: net_CTU64.py:160-176,220-233,263-271 are the CNN graph's labels, balanced loss and
+//                             accuracy over R rows)
+//   6 k_lstm_group_heads_bwd  one block per row: dlogit -> d fc2 -> d(cell output)
+//   7 k_lstm_group_bwd        recurrence backwards (slot 0 first), same ownership as 3: d gates per row, dh carried through
+//                             kernel[H:2H, :]^T (MFMA 16x16x4), dc through the forget gate; zero where c was clipped
+//   8 k_group_gemm            every weight gradient as one grouped GEMM with K = R: [x | h_prev | 1]^T x dZ for the three kernels and
+//                             biases, [h (dropped) | ef | 1]^T x dZ2 and [h2 (dropped) | ef | 1]^T x dZ3 for the heads; blob layout
+//   9 k_lstm_group_norm       partial sums of squares of the 760078 gradient floats: 512 blocks, each a fixed range and a fixed order
+//  10 k_lstm_group_update     every block sums the 512 partials in index order -> global norm, clip_by_global_norm's factor, momentum
+//                             update
 // Evaluation runs launches 1-4 on chunks of samples (no dropout) into one probability / label array and then ONE launch 5 over all
 // of its rows.  Determinism: no atomics; every sum has one owner and a fixed order.
 #pragma once
@@ -70,30 +74,21 @@ struct LstmBufs {
     float* dZ[3];                        // [R][4H]
 };
 
-struct GatherArgs {
-    const uint8_t* data;
-    long nrec;
-    const int32_t* idx_in;  // NULL: drawn
-    int32_t* idx_out;       // [nb]
-    uint64_t seed, step;
-    float qp_scale;
-    const int64_t* keep;  // trainer group: sample i is record keep[i] of data; NULL (solo): record i
-};
-
-// ---- trainer group (include/ethcnn.h "ETH-LSTM training, several models at once"): K independent LSTM trainers of one batch size in
-// every launch of a step.  A step is still the 10 launches above; launch i covers all K members:
+// ---- the member table (include/ethcnn.h "ETH-LSTM training" and "ETH-LSTM training, several models at once"): K >= 1 independent
+// LSTM trainers of one batch size in every launch of a step.  Launch i of the 10 above covers all K members:
 //   gather / heads forward / heads backward     grid (20 B, K): block (r, m) is row r of member m
-//   GEMMs (projections, weight gradients)       the CNN group's k_group_gemm: K x T blocks, T = the tiles of one member's descriptors
+//   GEMMs (projections, weight gradients)       the CNN trainer's k_group_gemm: K x T blocks, T = the tiles of one member's descriptors
 //   recurrences                                 grid (ceil(B / 16), 3, K): block (s, cell, m)
-//   loss                                        the CNN group's k_group_loss: K blocks, block m owns member m's counts over 20 B rows
-//   norm / update                               grid (512, K) / (1024, K): gridDim.x is the solo kernel's, so are chunk and stride
-// Every block runs the solo kernel's body (ethcnn_lstm_train_kernels.hip) on its member's solo-shaped buffers, no sum crosses
-// members and nothing is atomic, so member m computes what a solo trainer with its options computes, bit for bit, whatever K and m.
+//   loss                                        the CNN trainer's k_group_loss: K blocks, block m owns member m's counts over 20 B rows
+//   norm / update                               grid (512, K) / (1024, K): gridDim.x, hence chunk and stride, do not depend on K
+// The member is the grid's last dimension, no sum crosses members and nothing is atomic.  There is no other path, so member m
+// computes the same bits whatever K and m are, a solo trainer (K = 1) included.
 // The members share the two sample sets: one copy each, and per member and set the list of the records its QP selection keeps, in
-// file order (keep NULL: all).  A member's sample index i is its i-th kept record -- what the solo trainer's index means after it
-// compacted its copy -- so the index draw over nkept gives the solo batches.
-// The table lives in device memory and changes only with the sample sets; what changes per launch goes by value (LstmGroupStep, and
-// train::GroupRates for the K learning rates of the step).
+// file order (keep NULL: all).  A member's sample index i is its i-th kept record, and its index draw is over nkept.  A solo trainer
+// holds only the records it keeps (its uploads compact them), so its keep lists are NULL.
+// The table lives in device memory and changes only with the sample sets; the host marks it stale then and uploads it again before
+// the next step, after waiting for the steps in flight.  What changes per launch goes by value (LstmGroupStep, and train::GroupRates
+// for the K learning rates of the step).  An evaluation works on tables of its own (one per piece), never on the step table.
 struct LstmMember {
     LstmBufs u;
     float *W, *acc, *grad;  // blob layout
@@ -116,15 +111,6 @@ struct LstmGroupStep {
 };
 
 // launchers (ethcnn_lstm_train_kernels.hip)
-void launch_gather(hipStream_t s, int nb, const GatherArgs& a, const LstmBufs& u);
-void launch_fwd(hipStream_t s, int nb, const LstmBufs& u, const float* W, const LstmOffsets& o);
-void launch_heads_fwd(hipStream_t s, int nb, const LstmBufs& u, const float* W, const LstmOffsets& o, uint64_t seed, uint64_t step,
-                      int dropout);
-void launch_heads_bwd(hipStream_t s, int nb, const LstmBufs& u, const float* W, const LstmOffsets& o, int dropout);
-void launch_bwd(hipStream_t s, int nb, const LstmBufs& u, const float* W, const LstmOffsets& o);
-void launch_norm_update(hipStream_t s, float* W, float* acc, const float* grad, double* part, float clip, float lr, float momentum, long n,
-                        float* stats);
-void launch_check(hipStream_t s, const uint8_t* data, long nrec, long* first_bad, int nblocks);
 void launch_check_list(hipStream_t s, const uint8_t* data, const int64_t* list, long n, uint8_t* bad, int nblocks);
 void launch_group_gather(hipStream_t s, int nb, int k, const LstmMember* tab, const LstmGroupStep& g);
 void launch_group_fwd(hipStream_t s, int nb, int k, const LstmMember* tab, const LstmOffsets& o);

@@ -1,13 +1,16 @@
-// ethcnn_lstm_train_group.cpp -- host side of the ETH-LSTM trainer group (include/ethcnn.h "ETH-LSTM training, several models at
-// once"): K trainers of ethcnn_lstm_train.cpp that share a context, a stream, the two sample sets and every launch of a step (kernels
-// and grid mapping: ethcnn_lstm_train.h "trainer group").  A member IS a solo trainer object: its buffers, weights, QP list and
-// options are the solo ones, so weights in and out, initialisation, descriptors, schedules and the debug buffers go through the solo
-// code.  The samples do not: the group holds ONE copy of each set and, per member, the list of the records its QP list keeps.
+// ethcnn_lstm_train_group.cpp -- the step engine of ETH-LSTM training and the trainer group's entry points (include/ethcnn.h
+// "ETH-LSTM training, several models at once").  The engine is K >= 1 trainers of ethcnn_lstm_train.cpp that share a context, a
+// stream, the two sample sets and every launch of a step (kernels and grid mapping: ethcnn_lstm_train.h "the member table").  A
+// trainer group is an engine over its K members; a solo trainer's entry points (ethcnn_lstm_train.cpp) call the ones below on an
+// engine over the trainer itself, so there is one step, one evaluation and one sample validation.  Weights in and out, initialisation,
+// the QP list and the debug buffers are the member's own business and go through its trainer entry points.  The engine holds ONE
+// copy of each sample set and, per member, the list of the records its QP list keeps.
 #include <algorithm>
 #include <cmath>
 #include <cstdarg>
 #include <cstring>
 #include <new>
+#include <numeric>
 #include <string>
 #include <vector>
 
@@ -16,13 +19,6 @@
 #include "ethcnn_lstm_train.h"
 #include "ethcnn_lstm_train_host.h"
 
-namespace ethcnn {
-namespace train {
-void launch_group_gemm(hipStream_t s, const GemmGroup* d_grps, int tiles_per, int k);
-void launch_group_loss(hipStream_t s, int k, const Member* tab, int n, int with_grad);
-}  // namespace train
-}  // namespace ethcnn
-
 using namespace ethcnn::lstm_train;
 using ethcnn::kLstmBlobFloats;
 using ethcnn::train::GemmGroup;
@@ -30,47 +26,17 @@ using ethcnn::train::GroupRates;
 using ethcnn::train::kMaxMembers;
 using ethcnn::train::launch_group_gemm;
 using ethcnn::train::launch_group_loss;
-typedef ethcnn::train::Member LossEntry;  // k_group_loss reads P, lab, stats and dZ3 of its table; the rest stays zero
-
-struct ethcnn_lstm_train_group {
-    ethcnn_ctx* c = nullptr;
-    int K = 0, B = 0, cap = 0;
-    std::vector<ethcnn_lstm_trainer*> m;  // their data[] stay NULL: the sets are the group's
-    LstmMember* d_tab = nullptr;          // the tables of a training step
-    LossEntry* d_loss = nullptr;
-    GemmGroup *d_fwd = nullptr, *d_bwd = nullptr, *d_eval = nullptr;  // [K] each, side by side
-    int t_fwd = 0, t_bwd = 0, t_eval = 0;                             // tiles of ONE member
-    uint8_t* data[2] = {nullptr, nullptr};  // the shared records of a set
-    int64_t nall[2] = {0, 0};
-    int64_t* d_keep[2][kMaxMembers] = {};  // a member's kept records, in file order; NULL: all nall of them
-    int64_t nkept[2][kMaxMembers] = {};
-    bool table_stale = true;  // a set changed since the table was uploaded
-    std::string err;
-};
-
-static int gerr(ethcnn_lstm_train_group* g, int code, const char* fmt, ...) {
-    char buf[640];
-    va_list ap;
-    va_start(ap, fmt);
-    std::vsnprintf(buf, sizeof buf, fmt, ap);
-    va_end(ap);
-    g->err = buf;
-    return code;
-}
-#define GCHK(g, call)                                                                                           \
-    do {                                                                                                        \
-        hipError_t e_ = (call);                                                                                 \
-        if (e_ != hipSuccess) return gerr((g), ETHCNN_ERR_DEVICE, "%s failed: %s", #call, hipGetErrorString(e_)); \
-    } while (0)
+typedef ethcnn::train::Member LossEntry;
 
 static int from_member(ethcnn_lstm_train_group* g, int i, int rc) {
     if (rc) g->err = "member " + std::to_string(i) + ": " + g->m[(size_t)i]->err;
     return rc;
 }
 static int member_index(ethcnn_lstm_train_group* g, int i) {
-    if (i < 0 || i >= g->K) return gerr(g, ETHCNN_ERR_ARG, "member %d outside 0..%d", i, g->K - 1);
+    if (i < 0 || i >= g->K) return terr(g, ETHCNN_ERR_ARG, "member %d outside 0..%d", i, g->K - 1);
     return 0;
 }
+static const char* api(const ethcnn_lstm_train_group* g) { return g->group ? "ethcnn_lstm_train_group" : "ethcnn_lstm_train"; }
 
 extern "C" int ethcnn_lstm_train_group_check(const ethcnn_lstm_train_options* opts, int k, char* err, size_t errcap) {
     char buf[256] = "";
@@ -148,17 +114,17 @@ static LossEntry loss_entry(const LstmMember& m) {
 }
 
 static int upload_table(ethcnn_lstm_train_group* g) {
-    if (!g->table_stale) return 0;
+    if (!g->stale) return 0;
     std::vector<LstmMember> tab;
     std::vector<LossEntry> loss;
     for (int i = 0; i < g->K; ++i) {
         tab.push_back(member_entry(g, i));
         loss.push_back(loss_entry(tab.back()));
     }
-    GCHK(g, hipStreamSynchronize(g->c->stream));  // steps in flight still read the old tables
-    GCHK(g, hipMemcpy(g->d_tab, tab.data(), sizeof(LstmMember) * tab.size(), hipMemcpyHostToDevice));
-    GCHK(g, hipMemcpy(g->d_loss, loss.data(), sizeof(LossEntry) * loss.size(), hipMemcpyHostToDevice));
-    g->table_stale = false;
+    TCHK(g, hipStreamSynchronize(g->c->stream));  // steps in flight still read the old tables
+    TCHK(g, hipMemcpy(g->d_tab, tab.data(), sizeof(LstmMember) * tab.size(), hipMemcpyHostToDevice));
+    TCHK(g, hipMemcpy(g->d_loss, loss.data(), sizeof(LossEntry) * loss.size(), hipMemcpyHostToDevice));
+    g->stale = false;
     return 0;
 }
 
@@ -184,32 +150,29 @@ static int enqueue_step(ethcnn_lstm_train_group* g, int64_t step, bool explicit_
     const LstmOffsets& o = g->m[0]->o;
     g->c->done_armed = 0;  // the context's completion word does not cover these launches
     GroupRates r{};
-    for (int i = 0; i < g->K; ++i) r.lr[i] = lstm_lr_at(g->m[(size_t)i], step);
+    for (int i = 0; i < g->K; ++i) {
+        const ethcnn_lstm_train_options& p = g->m[(size_t)i]->opt;
+        r.lr[i] = ethcnn::train::lr_at(p.lr_init, p.decay_rate, p.decay_steps, step);
+    }
     enqueue_forward(g, g->d_tab, ETHCNN_TRAIN_SET_TRAIN, g->B, (uint64_t)step, explicit_batch ? 0 : 1, 1, g->d_fwd, g->t_fwd);
     launch_group_loss(s, g->K, g->d_loss, g->B * kSteps, 1);
     launch_group_heads_bwd(s, g->B, g->K, g->d_tab, o);
     launch_group_bwd(s, g->B, g->K, g->d_tab, o);
     launch_group_gemm(s, g->d_bwd, g->t_bwd, g->K);
     launch_group_norm_update(s, g->K, g->d_tab, r, (long)kLstmBlobFloats);
-    GCHK(g, hipGetLastError());
+    TCHK(g, hipGetLastError());
     return 0;
 }
 
 static int read_stats(ethcnn_lstm_train_group* g, float* loss, float* acc) {
-    float st[kMaxMembers][8];
-    for (int i = 0; i < g->K; ++i)
-        GCHK(g, hipMemcpyAsync(st[i], g->m[(size_t)i]->stats, sizeof st[i], hipMemcpyDeviceToHost, g->c->stream));
-    GCHK(g, hipStreamSynchronize(g->c->stream));
-    for (int i = 0; i < g->K; ++i)
-        for (int l = 0; l < 3; ++l) {
-            if (loss) loss[3 * i + l] = st[i][l];
-            if (acc) acc[3 * i + l] = st[i][3 + l];
-        }
+    float* st[kMaxMembers];
+    for (int i = 0; i < g->K; ++i) st[i] = g->m[(size_t)i]->stats;
+    TCHK(g, ethcnn::train::read_stats(g->c->stream, st, g->K, loss, acc));
     return 0;
 }
 
 static int ready(ethcnn_lstm_train_group* g) {
-    if (!g->data[ETHCNN_TRAIN_SET_TRAIN]) return gerr(g, ETHCNN_ERR_ARG, "no training samples (ethcnn_lstm_train_group_set_samples)");
+    if (!g->data[ETHCNN_TRAIN_SET_TRAIN]) return terr(g, ETHCNN_ERR_ARG, "no training samples (%s_set_samples)", api(g));
     return 0;
 }
 
@@ -224,11 +187,8 @@ static void free_set(ethcnn_lstm_train_group* g, int set) {
     g->nall[set] = 0;
 }
 
-extern "C" void ethcnn_lstm_train_group_destroy(ethcnn_lstm_train_group* g) {
+void lstm_engine_destroy(ethcnn_lstm_train_group* g) {
     if (!g) return;
-    (void)hipSetDevice(g->c->device);
-    (void)hipStreamSynchronize(g->c->stream);
-    for (ethcnn_lstm_trainer* t : g->m) ethcnn_lstm_train_destroy(t);
     for (int s = 0; s < 2; ++s) free_set(g, s);
     (void)hipFree(g->d_tab);
     (void)hipFree(g->d_loss);
@@ -238,25 +198,16 @@ extern "C" void ethcnn_lstm_train_group_destroy(ethcnn_lstm_train_group* g) {
     delete g;
 }
 
-extern "C" int ethcnn_lstm_train_group_create(ethcnn_ctx* c, const ethcnn_lstm_train_options* opts, int k, ethcnn_lstm_train_group** out) {
-    if (!c || !out) return ETHCNN_ERR_ARG;
-    *out = nullptr;
-    char why[256];
-    if (int rc = ethcnn_lstm_train_group_check(opts, k, why, sizeof why)) return set_err(c, rc, "%s", why);
+int lstm_engine_create(ethcnn_ctx* c, const std::vector<ethcnn_lstm_trainer*>& members, bool group, ethcnn_lstm_train_group** out) {
     ethcnn_lstm_train_group* g = new (std::nothrow) ethcnn_lstm_train_group;
     if (!g) return set_err(c, ETHCNN_ERR_NOMEM, "out of memory");
+    const int k = (int)members.size();
     g->c = c;
+    g->m = members;
     g->K = k;
-    g->B = opts[0].batch;
-    for (int i = 0; i < k; ++i) {
-        ethcnn_lstm_trainer* t = nullptr;
-        if (int rc = ethcnn_lstm_train_create(c, &opts[i], &t)) {  // (the context holds the message)
-            ethcnn_lstm_train_group_destroy(g);
-            return rc;
-        }
-        g->m.push_back(t);
-    }
-    g->cap = g->m[0]->cap;
+    g->B = members[0]->B;
+    g->cap = members[0]->cap;
+    g->group = group;
     std::vector<GemmGroup> gf, gb, ge;
     for (const ethcnn_lstm_trainer* t : g->m) {
         gf.push_back(lstm_proj_group(t, g->B * kSteps));
@@ -275,11 +226,38 @@ extern "C" int ethcnn_lstm_train_group_create(ethcnn_ctx* c, const ethcnn_lstm_t
     e = e ? e : hipMemcpy(g->d_eval, ge.data(), gbytes, hipMemcpyHostToDevice);
     if (e != hipSuccess) {
         (void)hipGetLastError();
-        ethcnn_lstm_train_group_destroy(g);
-        return set_err(c, ETHCNN_ERR_DEVICE, "LSTM trainer group setup: %s", hipGetErrorString(e));
+        lstm_engine_destroy(g);
+        return set_err(c, ETHCNN_ERR_DEVICE, "LSTM %s setup: %s", group ? "trainer group" : "trainer", hipGetErrorString(e));
     }
+    for (ethcnn_lstm_trainer* t : g->m) t->eng = g;
     *out = g;
     return ETHCNN_OK;
+}
+
+extern "C" void ethcnn_lstm_train_group_destroy(ethcnn_lstm_train_group* g) {
+    if (!g) return;
+    (void)hipSetDevice(g->c->device);
+    (void)hipStreamSynchronize(g->c->stream);
+    for (ethcnn_lstm_trainer* t : g->m) lstm_member_destroy(t);
+    lstm_engine_destroy(g);
+}
+
+extern "C" int ethcnn_lstm_train_group_create(ethcnn_ctx* c, const ethcnn_lstm_train_options* opts, int k, ethcnn_lstm_train_group** out) {
+    if (!c || !out) return ETHCNN_ERR_ARG;
+    *out = nullptr;
+    char why[256];
+    if (int rc = ethcnn_lstm_train_group_check(opts, k, why, sizeof why)) return set_err(c, rc, "%s", why);
+    std::vector<ethcnn_lstm_trainer*> m;
+    int rc = 0;
+    for (int i = 0; i < k && !rc; ++i) {
+        ethcnn_lstm_trainer* t = nullptr;
+        rc = lstm_member_create(c, &opts[i], &t);  // (the context holds the message)
+        if (!rc) m.push_back(t);
+    }
+    rc = rc ? rc : lstm_engine_create(c, m, true, out);
+    if (rc)
+        for (ethcnn_lstm_trainer* t : m) lstm_member_destroy(t);
+    return rc;
 }
 
 extern "C" const char* ethcnn_lstm_train_group_last_error(const ethcnn_lstm_train_group* g) {
@@ -288,7 +266,7 @@ extern "C" const char* ethcnn_lstm_train_group_last_error(const ethcnn_lstm_trai
 
 extern "C" int ethcnn_lstm_train_group_init_weights(ethcnn_lstm_train_group* g, const uint64_t* seeds) {
     if (!g) return ETHCNN_ERR_ARG;
-    if (!seeds) return gerr(g, ETHCNN_ERR_ARG, "no seeds");
+    if (!seeds) return terr(g, ETHCNN_ERR_ARG, "no seeds");
     for (int i = 0; i < g->K; ++i)
         if (int rc = from_member(g, i, ethcnn_lstm_train_init_weights(g->m[(size_t)i], seeds[i]))) return rc;
     return 0;
@@ -313,9 +291,9 @@ extern "C" int ethcnn_lstm_train_group_set_qps(ethcnn_lstm_train_group* g, int i
 }
 
 // Installs `p` (nall records, already in HBM; `file_index`: the file record behind each of them, NULL = itself) as set `set` with the
-// members' keep lists `keep` (indices into p).  Before that, the solo trainer's device validation over the records at least one member
-// keeps; a bad record fails the upload for the first member that keeps one, with that member's first, as its own upload would.
-// On any failure p is NOT freed and the group is unchanged.
+// members' keep lists `keep` (indices into p).  Before that, the device validation over the records at least one member keeps; a bad
+// record fails the upload for the first member that keeps one, with that member's first.
+// On any failure p is NOT freed and the engine is unchanged.
 static int install_set(ethcnn_lstm_train_group* g, int set, uint8_t* p, size_t nall, const int64_t* file_index,
                        std::vector<std::vector<int64_t>>& keep) {
     hipStream_t s = g->c->stream;
@@ -344,15 +322,14 @@ static int install_set(ethcnn_lstm_train_group* g, int set, uint8_t* p, size_t n
         (void)hipFree(d_bad);
         if (e != hipSuccess) {
             (void)hipGetLastError();
-            return gerr(g, ETHCNN_ERR_DEVICE, "sample check: %s", hipGetErrorString(e));
+            return terr(g, ETHCNN_ERR_DEVICE, "sample check: %s", hipGetErrorString(e));
         }
     }
     for (size_t j = 0; j < nl; ++j) used[(size_t)list[j]] = bad[j] ? 2 : 1;
     for (int i = 0; i < K; ++i)
         for (int64_t r : keep[(size_t)i])
             if (used[(size_t)r] == 2)
-                return gerr(g, ETHCNN_ERR_FORMAT,
-                            "member %d: sample %lld: a QP outside 0..51, a label outside 0..3 or a non-finite vector element", i,
+                return gerr(g, i, ETHCNN_ERR_FORMAT, "sample %lld: a QP outside 0..51, a label outside 0..3 or a non-finite vector element",
                             (long long)(file_index ? file_index[r] : r));
     // the keep lists in HBM (a member that keeps everything reads the records directly)
     int64_t* d_keep[kMaxMembers] = {};
@@ -364,7 +341,7 @@ static int install_set(ethcnn_lstm_train_group* g, int set, uint8_t* p, size_t n
         if (e != hipSuccess) {
             (void)hipGetLastError();
             for (int j = 0; j <= i; ++j) (void)hipFree(d_keep[j]);
-            return gerr(g, ETHCNN_ERR_NOMEM, "cannot allocate a keep list of %zu samples", k.size());
+            return terr(g, ETHCNN_ERR_NOMEM, "cannot allocate a keep list of %zu samples", k.size());
         }
     }
     free_set(g, set);
@@ -374,27 +351,27 @@ static int install_set(ethcnn_lstm_train_group* g, int set, uint8_t* p, size_t n
         g->d_keep[set][i] = d_keep[i];
         g->nkept[set][i] = (int64_t)keep[(size_t)i].size();
     }
-    g->table_stale = true;
+    g->stale = true;
     return 0;
 }
 
-// the members' keep lists over n records with the slot-0 QPs q0; an empty one is the solo trainer's error, with the member named
+// the members' keep lists over n records with the slot-0 QPs q0; an empty one is an error
 static int member_keeps(ethcnn_lstm_train_group* g, const float* q0, size_t n, std::vector<std::vector<int64_t>>* keep) {
     keep->assign((size_t)g->K, std::vector<int64_t>());
     for (int i = 0; i < g->K; ++i) {
         const ethcnn_lstm_trainer* t = g->m[(size_t)i];
         select_qp(q0, n, t->qps, t->nqps, &(*keep)[(size_t)i]);
-        if ((*keep)[(size_t)i].empty()) return gerr(g, ETHCNN_ERR_FORMAT, "member %d: none of the %zu samples has a selected QP", i, n);
-        if ((*keep)[(size_t)i].size() > 0x7fffffffull / kSteps) return gerr(g, ETHCNN_ERR_ARG, "member %d: too many samples", i);
+        if ((*keep)[(size_t)i].empty()) return gerr(g, i, ETHCNN_ERR_FORMAT, "none of the %zu samples has a selected QP", n);
+        if ((*keep)[(size_t)i].size() > 0x7fffffffull / kSteps) return gerr(g, i, ETHCNN_ERR_ARG, "too many samples");
     }
     return 0;
 }
 
 extern "C" int ethcnn_lstm_train_group_set_samples(ethcnn_lstm_train_group* g, int set, const uint8_t* rec, size_t nbytes) {
     if (!g) return ETHCNN_ERR_ARG;
-    if (set != 0 && set != 1) return gerr(g, ETHCNN_ERR_ARG, "set must be 0 (train) or 1 (valid), got %d", set);
-    if (!rec || nbytes == 0) return gerr(g, ETHCNN_ERR_ARG, "no sample records");
-    if (nbytes % kRecBytes) return gerr(g, ETHCNN_ERR_FORMAT, "%zu bytes is not a whole number of %d-byte samples", nbytes, kRecBytes);
+    if (set != 0 && set != 1) return terr(g, ETHCNN_ERR_ARG, "set must be 0 (train) or 1 (valid), got %d", set);
+    if (!rec || nbytes == 0) return terr(g, ETHCNN_ERR_ARG, "no sample records");
+    if (nbytes % kRecBytes) return terr(g, ETHCNN_ERR_FORMAT, "%zu bytes is not a whole number of %d-byte samples", nbytes, kRecBytes);
     const size_t nfile = nbytes / kRecBytes;
     std::vector<float> q0(nfile);
     for (size_t i = 0; i < nfile; ++i) std::memcpy(&q0[i], rec + i * kRecBytes + 64, 4);
@@ -411,13 +388,13 @@ extern "C" int ethcnn_lstm_train_group_set_samples(ethcnn_lstm_train_group* g, i
         }
     for (std::vector<int64_t>& k : keep)
         for (int64_t& r : k) r = pos[(size_t)r];
-    GCHK(g, hipSetDevice(g->c->device));
-    GCHK(g, hipStreamSynchronize(g->c->stream));
+    TCHK(g, hipSetDevice(g->c->device));
+    TCHK(g, hipStreamSynchronize(g->c->stream));
     const size_t n = un.size();
     void* p = nullptr;
     if (hipMalloc(&p, n * kRecBytes) != hipSuccess) {
         (void)hipGetLastError();
-        return gerr(g, ETHCNN_ERR_NOMEM, "%zu bytes of samples do not fit in device memory", n * kRecBytes);
+        return terr(g, ETHCNN_ERR_NOMEM, "%zu bytes of samples do not fit in device memory", n * kRecBytes);
     }
     hipError_t e = hipSuccess;
     for (size_t j = 0; j < n && e == hipSuccess;) {  // runs of consecutive records, one copy each
@@ -429,7 +406,7 @@ extern "C" int ethcnn_lstm_train_group_set_samples(ethcnn_lstm_train_group* g, i
     if (e != hipSuccess) {
         (void)hipGetLastError();
         (void)hipFree(p);
-        return gerr(g, ETHCNN_ERR_DEVICE, "sample upload: %s", hipGetErrorString(e));
+        return terr(g, ETHCNN_ERR_DEVICE, "sample upload: %s", hipGetErrorString(e));
     }
     if (int rc = install_set(g, set, (uint8_t*)p, n, un.data(), keep)) {
         (void)hipFree(p);
@@ -441,15 +418,18 @@ extern "C" int ethcnn_lstm_train_group_set_samples(ethcnn_lstm_train_group* g, i
 extern "C" int ethcnn_lstm_train_group_set_samples_from(ethcnn_lstm_train_group* g, int set, ethcnn_lstm_samples* sm, int take) {
     namespace ls = ethcnn::lstm_samples;
     if (!g) return ETHCNN_ERR_ARG;
-    if (set != 0 && set != 1) return gerr(g, ETHCNN_ERR_ARG, "set must be 0 (train) or 1 (valid), got %d", set);
-    if (!sm || !sm->built || sm->count == 0) return gerr(g, ETHCNN_ERR_ARG, "no sample records (the sample set is not built or empty)");
-    if (sm->c != g->c) return gerr(g, ETHCNN_ERR_ARG, "the sample set and the trainer group live on different contexts");
+    if (set != 0 && set != 1) return terr(g, ETHCNN_ERR_ARG, "set must be 0 (train) or 1 (valid), got %d", set);
+    if (!sm || !sm->built || sm->count == 0) return terr(g, ETHCNN_ERR_ARG, "no sample records (the sample set is not built or empty)");
+    if (sm->c != g->c)
+        return terr(g, ETHCNN_ERR_ARG, "the sample set and the trainer%s live on different contexts", g->group ? " group" : "");
     const size_t nall = (size_t)sm->count;
     hipStream_t s = g->c->stream;
-    GCHK(g, hipSetDevice(g->c->device));
-    GCHK(g, hipStreamSynchronize(s));
-    std::vector<float> q0(nall);
-    {
+    TCHK(g, hipSetDevice(g->c->device));
+    TCHK(g, hipStreamSynchronize(s));
+    bool selecting = false;  // some member has a QP list: the slot-0 QPs are the only bytes that leave HBM
+    for (const ethcnn_lstm_trainer* t : g->m) selecting = selecting || t->nqps > 0;
+    std::vector<float> q0(selecting ? nall : 0);
+    if (selecting) {
         float* d_q = nullptr;
         hipError_t e = hipMalloc((void**)&d_q, nall * 4);
         if (e == hipSuccess) {
@@ -459,28 +439,53 @@ extern "C" int ethcnn_lstm_train_group_set_samples_from(ethcnn_lstm_train_group*
         if (e == hipSuccess) e = hipMemcpyAsync(q0.data(), d_q, nall * 4, hipMemcpyDeviceToHost, s);
         if (e == hipSuccess) e = hipStreamSynchronize(s);
         (void)hipFree(d_q);
-        if (e != hipSuccess) return gerr(g, ETHCNN_ERR_DEVICE, "sample selection: %s", hipGetErrorString(e));
+        if (e != hipSuccess) return terr(g, ETHCNN_ERR_DEVICE, "sample selection: %s", hipGetErrorString(e));
     }
     std::vector<std::vector<int64_t>> keep;
     if (int rc = member_keeps(g, q0.data(), nall, &keep)) return rc;
+    // A trainer group keeps the whole set once and reads it through the keep lists.  A solo trainer holds only the records it keeps:
+    // under a QP list that drops some, a compacted copy with everything kept (`file`: the set's record behind each of its records).
+    const bool compact = !g->group && keep[0].size() != nall;
+    std::vector<int64_t> file;
+    if (compact) {
+        file.swap(keep[0]);
+        keep[0].resize(file.size());
+        std::iota(keep[0].begin(), keep[0].end(), (int64_t)0);
+    }
+    const size_t n = compact ? file.size() : nall;
+    const bool copy = compact || !take;  // otherwise the set's buffer is adopted
     uint8_t* p = sm->data;
-    if (!take) {
-        if (hipMalloc((void**)&p, nall * kRecBytes) != hipSuccess) {
+    if (copy) {
+        if (hipMalloc((void**)&p, n * kRecBytes) != hipSuccess) {
             (void)hipGetLastError();
-            return gerr(g, ETHCNN_ERR_NOMEM, "%zu bytes of samples do not fit in device memory", nall * kRecBytes);
+            return terr(g, ETHCNN_ERR_NOMEM, "%zu bytes of samples do not fit in device memory", n * kRecBytes);
         }
-        hipError_t e = hipMemcpyAsync(p, sm->data, nall * kRecBytes, hipMemcpyDeviceToDevice, s);
+        hipError_t e = hipSuccess;
+        int64_t* d_file = nullptr;
+        if (!compact) {
+            e = hipMemcpyAsync(p, sm->data, n * kRecBytes, hipMemcpyDeviceToDevice, s);
+        } else {
+            e = hipMalloc((void**)&d_file, n * 8);
+            if (e == hipSuccess) e = hipMemcpyAsync(d_file, file.data(), n * 8, hipMemcpyHostToDevice, s);
+            if (e == hipSuccess) {
+                ls::launch_compact(s, sm->data, d_file, (long)n, p, g->c->cus > 0 ? g->c->cus : 256);
+                e = hipGetLastError();
+            }
+        }
         if (e == hipSuccess) e = hipStreamSynchronize(s);
+        (void)hipFree(d_file);
         if (e != hipSuccess) {
+            (void)hipGetLastError();
             (void)hipFree(p);
-            return gerr(g, ETHCNN_ERR_DEVICE, "sample copy: %s", hipGetErrorString(e));
+            return terr(g, ETHCNN_ERR_DEVICE, "sample copy: %s", hipGetErrorString(e));
         }
     }
-    if (int rc = install_set(g, set, p, nall, nullptr, keep)) {
-        if (!take) (void)hipFree(p);
+    if (int rc = install_set(g, set, p, n, compact ? file.data() : nullptr, keep)) {
+        if (copy) (void)hipFree(p);
         return rc;
     }
-    if (take) {  // the buffer is the group's now
+    if (take) {  // the set is empty afterwards: its buffer is the engine's now, or (after a compacting copy) is freed
+        if (copy) (void)hipFree(sm->data);
         sm->data = nullptr;
         sm->count = sm->skipped = 0;
         sm->built = false;
@@ -494,9 +499,9 @@ extern "C" int64_t ethcnn_lstm_train_group_num_samples(const ethcnn_lstm_train_g
 
 extern "C" int ethcnn_lstm_train_group_run(ethcnn_lstm_train_group* g, int64_t first_step, int64_t nsteps) {
     if (!g) return ETHCNN_ERR_ARG;
-    if (first_step < 0 || nsteps < 0) return gerr(g, ETHCNN_ERR_ARG, "negative step");
+    if (first_step < 0 || nsteps < 0) return terr(g, ETHCNN_ERR_ARG, "negative step");
     if (int rc = ready(g)) return rc;
-    GCHK(g, hipSetDevice(g->c->device));
+    TCHK(g, hipSetDevice(g->c->device));
     if (int rc = upload_table(g)) return rc;
     for (int64_t i = 0; i < nsteps; ++i)
         if (int rc = enqueue_step(g, first_step + i, false)) return rc;
@@ -505,7 +510,7 @@ extern "C" int ethcnn_lstm_train_group_run(ethcnn_lstm_train_group* g, int64_t f
 
 extern "C" int ethcnn_lstm_train_group_last_stats(ethcnn_lstm_train_group* g, float* loss, float* acc) {
     if (!g) return ETHCNN_ERR_ARG;
-    GCHK(g, hipSetDevice(g->c->device));
+    TCHK(g, hipSetDevice(g->c->device));
     return read_stats(g, loss, acc);
 }
 
@@ -513,17 +518,17 @@ extern "C" int ethcnn_lstm_train_group_step_indices(ethcnn_lstm_train_group* g, 
                                                     float* acc) {
     if (!g) return ETHCNN_ERR_ARG;
     if (int rc = ready(g)) return rc;
-    if (!idx || n != g->B) return gerr(g, ETHCNN_ERR_ARG, "an explicit batch needs %d indices per member", g->B);
-    if (step < 0) return gerr(g, ETHCNN_ERR_ARG, "negative step");
+    if (!idx || n != g->B) return terr(g, ETHCNN_ERR_ARG, "an explicit batch needs %d indices%s", g->B, g->group ? " per member" : "");
+    if (step < 0) return terr(g, ETHCNN_ERR_ARG, "negative step");
     for (int i = 0; i < g->K * n; ++i)
         if (idx[i] < 0 || idx[i] >= g->nkept[0][i / n])
-            return gerr(g, ETHCNN_ERR_ARG, "member %d: sample index %d outside 0..%lld", i / n, idx[i], (long long)g->nkept[0][i / n] - 1);
-    GCHK(g, hipSetDevice(g->c->device));
+            return gerr(g, i / n, ETHCNN_ERR_ARG, "sample index %d outside 0..%lld", idx[i], (long long)g->nkept[0][i / n] - 1);
+    TCHK(g, hipSetDevice(g->c->device));
     if (int rc = upload_table(g)) return rc;
     hipStream_t s = g->c->stream;
     for (int i = 0; i < g->K; ++i)
-        GCHK(g, hipMemcpyAsync(g->m[(size_t)i]->idx_in, idx + (size_t)i * n, sizeof(int32_t) * n, hipMemcpyHostToDevice, s));
-    GCHK(g, hipStreamSynchronize(s));
+        TCHK(g, hipMemcpyAsync(g->m[(size_t)i]->idx_in, idx + (size_t)i * n, sizeof(int32_t) * n, hipMemcpyHostToDevice, s));
+    TCHK(g, hipStreamSynchronize(s));
     if (int rc = enqueue_step(g, step, true)) return rc;
     return read_stats(g, loss, acc);
 }
@@ -531,19 +536,22 @@ extern "C" int ethcnn_lstm_train_group_step_indices(ethcnn_lstm_train_group* g, 
 extern "C" int ethcnn_lstm_train_group_evaluate(ethcnn_lstm_train_group* g, int set, const int32_t* idx, int64_t n, float* loss, float* acc,
                                                 float* probs) {
     if (!g) return ETHCNN_ERR_ARG;
-    if (set != 0 && set != 1) return gerr(g, ETHCNN_ERR_ARG, "set must be 0 (train) or 1 (valid), got %d", set);
-    if (!g->data[set]) return gerr(g, ETHCNN_ERR_ARG, "no samples in set %d", set);
+    if (set != 0 && set != 1) return terr(g, ETHCNN_ERR_ARG, "set must be 0 (train) or 1 (valid), got %d", set);
+    if (!g->data[set]) return terr(g, ETHCNN_ERR_ARG, "no samples in set %d", set);
     const int K = g->K;
-    if (n <= 0 || n > 0x7fffffffll / kOut / kSteps / K) return gerr(g, ETHCNN_ERR_ARG, "bad sample count %lld", (long long)n);
+    if (n <= 0 || n > 0x7fffffffll / kOut / kSteps / K) return terr(g, ETHCNN_ERR_ARG, "bad sample count %lld", (long long)n);
     for (int m = 0; m < K; ++m) {
         const int64_t cnt = g->nkept[set][m];
-        if (!idx && n > cnt) return gerr(g, ETHCNN_ERR_ARG, "member %d: bad sample count %lld (it keeps %lld)", m, (long long)n, (long long)cnt);
+        if (!idx && n > cnt) {
+            if (!g->group) return terr(g, ETHCNN_ERR_ARG, "bad sample count %lld", (long long)n);
+            return gerr(g, m, ETHCNN_ERR_ARG, "bad sample count %lld (it keeps %lld)", (long long)n, (long long)cnt);
+        }
         if (idx)
             for (int64_t i = 0; i < n; ++i)
                 if (idx[m * n + i] < 0 || idx[m * n + i] >= cnt)
-                    return gerr(g, ETHCNN_ERR_ARG, "member %d: sample index %d outside 0..%lld", m, idx[m * n + i], (long long)cnt - 1);
+                    return gerr(g, m, ETHCNN_ERR_ARG, "sample index %d outside 0..%lld", idx[m * n + i], (long long)cnt - 1);
     }
-    GCHK(g, hipSetDevice(g->c->device));
+    TCHK(g, hipSetDevice(g->c->device));
     hipStream_t s = g->c->stream;
     g->c->done_armed = 0;
     std::vector<int32_t> ids;
@@ -553,24 +561,27 @@ extern "C" int ethcnn_lstm_train_group_evaluate(ethcnn_lstm_train_group* g, int 
             for (int64_t i = 0; i < n; ++i) ids[(size_t)m * n + i] = (int32_t)i;
         idx = ids.data();
     }
-    // one member table per piece (launches 1-4) and one loss table for the single loss launch over all 20 n rows of each member
+    // one member table per piece (launches 1-4) and one loss table for the single loss launch over all 20 n rows of each member.
+    // Tables and indices share ONE allocation and ONE upload, staged in `host`: [member tables | loss table | indices].
     const int64_t pieces = (n + g->cap - 1) / g->cap;
     const size_t rows = (size_t)n * kSteps;
+    const size_t tab_bytes = sizeof(LstmMember) * (size_t)K * (size_t)pieces, loss_bytes = sizeof(LossEntry) * (size_t)K;
+    const size_t in_bytes = (size_t)K * (size_t)n * 4;
     float *Pn = nullptr, *Ln = nullptr;
-    int32_t* In = nullptr;
-    LstmMember* d_tabs = nullptr;
-    LossEntry* d_loss = nullptr;
-    const auto release = [&]() { (void)hipFree(Pn); (void)hipFree(Ln); (void)hipFree(In); (void)hipFree(d_tabs); (void)hipFree(d_loss); };
+    uint8_t* D = nullptr;
+    const auto release = [&]() { (void)hipFree(Pn); (void)hipFree(Ln); (void)hipFree(D); };
     if (hipMalloc((void**)&Pn, (size_t)K * rows * kOut * 4) != hipSuccess || hipMalloc((void**)&Ln, (size_t)K * rows * 16 * 4) != hipSuccess ||
-        hipMalloc((void**)&In, (size_t)K * n * 4) != hipSuccess ||
-        hipMalloc((void**)&d_tabs, sizeof(LstmMember) * (size_t)K * (size_t)pieces) != hipSuccess ||
-        hipMalloc((void**)&d_loss, sizeof(LossEntry) * (size_t)K) != hipSuccess) {
+        hipMalloc((void**)&D, tab_bytes + loss_bytes + in_bytes) != hipSuccess) {
         (void)hipGetLastError();
         release();
-        return gerr(g, ETHCNN_ERR_NOMEM, "cannot allocate the evaluation buffers of %d x %lld samples", K, (long long)n);
+        return terr(g, ETHCNN_ERR_NOMEM, "cannot allocate the evaluation buffers of %d x %lld samples", K, (long long)n);
     }
-    std::vector<LstmMember> tabs;
-    std::vector<LossEntry> losses;
+    LstmMember* d_tabs = (LstmMember*)D;
+    LossEntry* d_loss = (LossEntry*)(D + tab_bytes);
+    int32_t* In = (int32_t*)(D + tab_bytes + loss_bytes);
+    std::vector<uint8_t> host(tab_bytes + loss_bytes + in_bytes);
+    LstmMember* tabs = (LstmMember*)host.data();
+    LossEntry* losses = (LossEntry*)(host.data() + tab_bytes);
     for (int64_t p = 0; p < pieces; ++p) {
         const int64_t c0 = p * g->cap;
         for (int m = 0; m < K; ++m) {
@@ -578,7 +589,7 @@ extern "C" int ethcnn_lstm_train_group_evaluate(ethcnn_lstm_train_group* g, int 
             e.idx_in = In + (size_t)m * n + c0;
             e.u.P = Pn + ((size_t)m * rows + (size_t)c0 * kSteps) * kOut;
             e.u.lab = Ln + ((size_t)m * rows + (size_t)c0 * kSteps) * 16;
-            tabs.push_back(e);
+            tabs[p * K + m] = e;
         }
     }
     for (int m = 0; m < K; ++m) {
@@ -586,12 +597,10 @@ extern "C" int ethcnn_lstm_train_group_evaluate(ethcnn_lstm_train_group* g, int 
         e.P = Pn + (size_t)m * rows * kOut;
         e.lab = Ln + (size_t)m * rows * 16;
         e.stats = g->m[(size_t)m]->stats;
-        losses.push_back(e);
+        losses[m] = e;
     }
-    hipError_t e = hipMemcpyAsync(In, idx, (size_t)K * n * 4, hipMemcpyHostToDevice, s);
-    if (e == hipSuccess) e = hipMemcpyAsync(d_tabs, tabs.data(), sizeof(LstmMember) * tabs.size(), hipMemcpyHostToDevice, s);
-    if (e == hipSuccess) e = hipMemcpyAsync(d_loss, losses.data(), sizeof(LossEntry) * losses.size(), hipMemcpyHostToDevice, s);
-    if (e == hipSuccess) e = hipStreamSynchronize(s);  // the tables are pageable host memory that goes out of scope
+    std::memcpy(host.data() + tab_bytes + loss_bytes, idx, in_bytes);
+    hipError_t e = hipMemcpyAsync(D, host.data(), host.size(), hipMemcpyHostToDevice, s);  // (`host` lives until the last synchronisation)
     for (int64_t p = 0; e == hipSuccess && p < pieces; ++p) {
         const int nb = (int)std::min<int64_t>(g->cap, n - p * g->cap);
         enqueue_forward(g, d_tabs + p * K, set, nb, 0, 0, 0, g->d_eval, g->t_eval);
@@ -604,7 +613,7 @@ extern "C" int ethcnn_lstm_train_group_evaluate(ethcnn_lstm_train_group* g, int 
     if (e == hipSuccess && probs) e = hipMemcpyAsync(probs, Pn, (size_t)K * rows * kOut * 4, hipMemcpyDeviceToHost, s);
     if (e == hipSuccess) e = hipStreamSynchronize(s);
     release();
-    if (e != hipSuccess) return gerr(g, ETHCNN_ERR_DEVICE, "evaluation: %s", hipGetErrorString(e));
+    if (e != hipSuccess) return terr(g, ETHCNN_ERR_DEVICE, "evaluation: %s", hipGetErrorString(e));
     return read_stats(g, loss, acc);
 }
 

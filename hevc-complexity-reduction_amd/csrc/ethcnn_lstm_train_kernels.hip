@@ -28,23 +28,28 @@ __device__ inline float keep_mask(uint64_t seed, uint64_t step, int row, int uni
 }
 
 // ------------------------------------------------------------------------------------------------------------------ gather ---
-// a.keep (trainer group: the member's kept records of the shared set, file order): sample i is record keep[i]; NULL: record i
-__device__ __forceinline__ void gather_body(const GatherArgs& a, const LstmBufs& u) {
+// m: the block's entry of the member table; g: what changes from launch to launch.  keep (the member's kept records of the shared
+// set, file order): sample i is record keep[i]; NULL: record i
+__device__ __forceinline__ void gather_body(const LstmMember& m, const LstmGroupStep& g) {
+    const LstmBufs& u = m.u;
+    // (selects, not m.keep[g.set]: an index that is not a constant would put the kernel's copy of the entry into scratch memory)
+    const int64_t* keep = g.set ? m.keep[1] : m.keep[0];
+    const long nkept = g.set ? m.nkept[1] : m.nkept[0];
     const int row = blockIdx.x, b = row / kSteps, p = row % kSteps, t = threadIdx.x;
     long i;
-    if (a.idx_in) i = a.idx_in[b];
-    else i = (long)(((draw(a.seed, kStreamLstmIndex, a.step, (uint64_t)b, 0) >> 32) * (uint64_t)a.nrec) >> 32);
-    const uint8_t* rec = a.data + (a.keep ? (long)a.keep[i] : i) * kRecBytes;
+    if (!g.drawn) i = m.idx_in[b];
+    else i = (long)(((draw(m.seed, kStreamLstmIndex, g.step, (uint64_t)b, 0) >> 32) * (uint64_t)nkept) >> 32);
+    const uint8_t* rec = g.data + (keep ? (long)keep[i] : i) * kRecBytes;
     const float* slots = (const float*)(rec + 64);  // 64 and 37264 are multiples of 4
     const float* slot = slots + p * kSlotFloats;
     for (int k = t; k < kVec; k += 128) u.X[(long)row * kVec + k] = slot[17 + k];
     if (t < 16) u.lab[(long)row * 16 + t] = slot[1 + t];
     if (t == 0) {
-        if (p == 0) a.idx_out[b] = (int)i;
+        if (p == 0) m.idx[b] = (int)i;
         // the features of unrolled step ts = 19 - p, which computes this row's prediction (net_CTU64.py:125): slot ts
         const int ts = kSteps - 1 - p;
         float qf = slots[ts * kSlotFloats] / 51.0f;  // :149
-        if (a.qp_scale != 1.f) qf = qf * a.qp_scale;
+        if (m.qp_scale != 1.f) qf = qf * m.qp_scale;
         const long frame = (long)((uint32_t)rec[10] | (uint32_t)rec[11] << 8 | (uint32_t)rec[12] << 16 | (uint32_t)rec[13] << 24) - ts;
         const int gop = (int)(((frame % 4) + 4) % 4);  // input_data.py:113-120
         float* e = u.E + (long)row * kEf;
@@ -52,7 +57,6 @@ __device__ __forceinline__ void gather_body(const GatherArgs& a, const LstmBufs&
         for (int k = 0; k < 4; ++k) e[1 + k] = k == gop ? 1.f : 0.f;
     }
 }
-__global__ __launch_bounds__(128) void k_lstm_gather(GatherArgs a, LstmBufs u) { gather_body(a, u); }
 
 // ------------------------------------------------------------------------------------------------------ forward recurrence ---
 // 256 threads = 4 waves; wave w owns the hidden-unit tiles (w + 4 i) * 16 .. + 16 and, per tile, the four gate accumulators of
@@ -136,7 +140,6 @@ __device__ __forceinline__ void fwd_body(const LstmBufs& u, const float* __restr
     else if (cell == 1) fwd_cell<128>(u, W, o.kern[1], o.bias[1], 64, u.Z[1], u.HP[1], nb, hs);
     else fwd_cell<256>(u, W, o.kern[2], o.bias[2], 192, u.Z[2], u.HP[2], nb, hs);
 }
-__global__ __launch_bounds__(256) void k_lstm_fwd(LstmBufs u, const float* __restrict__ W, LstmOffsets o, int nb) { fwd_body(u, W, o, nb); }
 
 // ------------------------------------------------------------------------------------------------------------ heads forward ---
 __device__ __forceinline__ void heads_fwd_body(const LstmBufs& u, const float* __restrict__ W, const LstmOffsets& o, const uint64_t seed,
@@ -181,10 +184,6 @@ __device__ __forceinline__ void heads_fwd_body(const LstmBufs& u, const float* _
         u.P[(long)row * kOut + t] = sigm(acc + W[o.b3[cl] + j]);
     }
 }
-__global__ __launch_bounds__(256) void k_lstm_heads_fwd(LstmBufs u, const float* __restrict__ W, LstmOffsets o, uint64_t seed,
-                                                         uint64_t step, int dropout) {
-    heads_fwd_body(u, W, o, seed, step, dropout);
-}
 
 // ----------------------------------------------------------------------------------------------------------- heads backward ---
 __device__ __forceinline__ void heads_bwd_body(const LstmBufs& u, const float* __restrict__ W, const LstmOffsets& o, const int dropout) {
@@ -210,9 +209,6 @@ __device__ __forceinline__ void heads_bwd_body(const LstmBufs& u, const float* _
         for (int c = 0; c < n2; ++c) acc += w[j * n2 + c] * dz2[kN2Off[cl] + c];
         u.dH[(long)row * kVec + x] = dropout ? (acc * u.M1[(long)row * kVec + x]) / 0.5f : acc;
     }
-}
-__global__ __launch_bounds__(256) void k_lstm_heads_bwd(LstmBufs u, const float* __restrict__ W, LstmOffsets o, int dropout) {
-    heads_bwd_body(u, W, o, dropout);
 }
 
 // ----------------------------------------------------------------------------------------------------- backward recurrence ---
@@ -302,7 +298,6 @@ __device__ __forceinline__ void bwd_body(const LstmBufs& u, const float* __restr
     else if (cell == 1) bwd_cell<128>(u, W, o.kern[1], 64, u.Z[1], u.dZ[1], nb, dzs, dhs);
     else bwd_cell<256>(u, W, o.kern[2], 192, u.Z[2], u.dZ[2], nb, dzs, dhs);
 }
-__global__ __launch_bounds__(256) void k_lstm_bwd(LstmBufs u, const float* __restrict__ W, LstmOffsets o, int nb) { bwd_body(u, W, o, nb); }
 
 // ------------------------------------------------------------------------------------------------- global norm and update ---
 // level 1: block k sums the squares of floats [k chunk, (k + 1) chunk): thread t takes t, t + 256, ... in order, then a tree in LDS
@@ -318,9 +313,6 @@ __device__ __forceinline__ void norm_body(const float* __restrict__ grad, const 
         __syncthreads();
     }
     if (threadIdx.x == 0) part[blockIdx.x] = red[0];
-}
-__global__ __launch_bounds__(256) void k_lstm_norm(const float* __restrict__ grad, long n, double* __restrict__ part) {
-    norm_body(grad, n, part);
 }
 
 // level 2 (every block, the same order) + tf.clip_by_global_norm (scale = clip * min(1 / norm, 1 / clip)) + MomentumOptimizer.
@@ -345,76 +337,69 @@ __device__ __forceinline__ void update_body(float* __restrict__ W, float* __rest
         W[j] = W[j] - lr * a;
     }
 }
-__global__ __launch_bounds__(256) void k_lstm_update(float* __restrict__ W, float* __restrict__ acc, const float* __restrict__ grad,
-                                                      const double* __restrict__ part, int nparts, float clip, float lr, float momentum,
-                                                      long n, float* __restrict__ stats) {
-    update_body(W, acc, grad, part, nparts, clip, lr, momentum, n, stats);
-}
 
-// ------------------------------------------------------------------------------------------------------------ trainer group ---
-// K trainers in every launch of a step (ethcnn_lstm_train.h "trainer group").  tab: the device-resident member table.  The member is
-// the grid's last dimension; blockIdx.x (and, in the recurrences, blockIdx.y = the cell) and gridDim.x are what the solo launch gives
-// the body, so each block runs the solo kernel's instructions on its member's buffers.  The members share the sample records only.
+// -------------------------------------------------------------------------------------------------------------- the kernels ---
+// K >= 1 trainers in every launch of a step (ethcnn_lstm_train.h "the member table").  tab: the device-resident member table.  The
+// member is the grid's last dimension, so blockIdx.x (and, in the recurrences, blockIdx.y = the cell) and gridDim.x do not depend on
+// K or on the member; each block runs the body on its member's buffers.  The members share the sample records only.
+// member_of: the block's entry, fetched once (a uniform address: scalar loads), every pointer marked as device memory
+// (train::as_global), so the bodies' accesses are global_load / global_store and not FLAT ones, which would wait on the counter the
+// recurrences' LDS traffic uses.
+__device__ __forceinline__ LstmMember member_of(const LstmMember* __restrict__ tab, const unsigned i) {
+    using train::as_global;
+    const LstmMember& e = tab[i];  // in memory
+    LstmMember m = e;
+    LstmBufs& u = m.u;
+    u.X = as_global(e.u.X); u.lab = as_global(e.u.lab); u.E = as_global(e.u.E);
+    for (int c = 0; c < 3; ++c) {
+        u.Z[c] = as_global(e.u.Z[c]); u.HP[c] = as_global(e.u.HP[c]); u.dZ[c] = as_global(e.u.dZ[c]);
+    }
+    u.Cpre = as_global(e.u.Cpre); u.C = as_global(e.u.C); u.Hout = as_global(e.u.Hout);
+    u.M1 = as_global(e.u.M1); u.H1 = as_global(e.u.H1); u.A2 = as_global(e.u.A2); u.M2 = as_global(e.u.M2); u.H2 = as_global(e.u.H2);
+    u.P = as_global(e.u.P); u.dZ3 = as_global(e.u.dZ3); u.dZ2 = as_global(e.u.dZ2); u.dH = as_global(e.u.dH);
+    m.W = as_global(e.W); m.acc = as_global(e.acc); m.grad = as_global(e.grad); m.part = as_global(e.part);
+    m.stats = as_global(e.stats); m.idx_in = as_global(e.idx_in); m.idx = as_global(e.idx);
+    m.keep[0] = as_global(e.keep[0]); m.keep[1] = as_global(e.keep[1]);
+    return m;
+}
 __global__ __launch_bounds__(128) void k_lstm_group_gather(const LstmMember* __restrict__ tab, LstmGroupStep g) {
-    const LstmMember& m = tab[blockIdx.y];
-    const GatherArgs a{g.data, m.nkept[g.set], g.drawn ? nullptr : m.idx_in, m.idx, m.seed, g.step, m.qp_scale, m.keep[g.set]};
-    gather_body(a, m.u);
+    const LstmMember m = member_of(tab, blockIdx.y);
+    gather_body(m, g);
 }
 __global__ __launch_bounds__(256) void k_lstm_group_fwd(const LstmMember* __restrict__ tab, LstmOffsets o, int nb) {
-    const LstmMember& m = tab[blockIdx.z];
+    const LstmMember m = member_of(tab, blockIdx.z);
     fwd_body(m.u, m.W, o, nb);
 }
 __global__ __launch_bounds__(256) void k_lstm_group_heads_fwd(const LstmMember* __restrict__ tab, LstmOffsets o, uint64_t step, int train) {
-    const LstmMember& m = tab[blockIdx.y];
+    const LstmMember m = member_of(tab, blockIdx.y);
     heads_fwd_body(m.u, m.W, o, m.seed, step, train ? m.dropout : 0);
 }
 __global__ __launch_bounds__(256) void k_lstm_group_heads_bwd(const LstmMember* __restrict__ tab, LstmOffsets o) {
-    const LstmMember& m = tab[blockIdx.y];
+    const LstmMember m = member_of(tab, blockIdx.y);
     heads_bwd_body(m.u, m.W, o, m.dropout);
 }
 __global__ __launch_bounds__(256) void k_lstm_group_bwd(const LstmMember* __restrict__ tab, LstmOffsets o, int nb) {
-    const LstmMember& m = tab[blockIdx.z];
+    const LstmMember m = member_of(tab, blockIdx.z);
     bwd_body(m.u, m.W, o, nb);
 }
 __global__ __launch_bounds__(256) void k_lstm_group_norm(const LstmMember* __restrict__ tab, long n) {
-    const LstmMember& m = tab[blockIdx.y];
+    const LstmMember m = member_of(tab, blockIdx.y);
     norm_body(m.grad, n, m.part);
 }
 __global__ __launch_bounds__(256) void k_lstm_group_update(const LstmMember* __restrict__ tab, train::GroupRates r, long n) {
-    const LstmMember& m = tab[blockIdx.y];
+    const LstmMember m = member_of(tab, blockIdx.y);
     update_body(m.W, m.acc, m.grad, m.part, kNormBlocks, m.clip, r.lr[blockIdx.y], m.momentum, n, m.stats);
 }
 
 // ------------------------------------------------------------------------------------------------------------- sample check ---
-// first record (per block, over a contiguous range) with a QP that is not an integer in 0..51, a label that is not an integer in 0..3
-// or a vector element that is not finite; nrec when there is none.  The host takes the min over the blocks.
+// a record is bad when it holds a QP that is not an integer in 0..51, a label that is not an integer in 0..3 or a vector element that
+// is not finite
 __device__ inline bool sample_float_ok(int c, float v) {  // float c of a slot: [qp | 16 labels | 448 vector]
     return c == 0 ? (v >= 0.f && v <= 51.f && v == truncf(v)) : (c <= 16 ? (v >= 0.f && v <= 3.f && v == truncf(v)) : isfinite(v));
 }
-__global__ __launch_bounds__(256) void k_lstm_check(const uint8_t* __restrict__ data, long nrec, long* __restrict__ first_bad) {
-    __shared__ long red[256];
-    const long per = (nrec + gridDim.x - 1) / gridDim.x, r0 = (long)blockIdx.x * per, r1 = min(nrec, r0 + per);
-    constexpr int kF = kSlotFloats * kSteps;
-    long bad = nrec;
-    for (long i = r0; i < r1 && bad == nrec; ++i) {
-        const float* f = (const float*)(data + i * kRecBytes + 64);
-        for (int j = threadIdx.x; j < kF; j += 256) {
-            const int c = j % kSlotFloats;
-            const float v = f[j];
-            if (!sample_float_ok(c, v)) bad = i;
-        }
-    }
-    red[threadIdx.x] = bad;
-    __syncthreads();
-    for (int w = 128; w > 0; w >>= 1) {
-        if ((int)threadIdx.x < w) red[threadIdx.x] = min(red[threadIdx.x], red[threadIdx.x + w]);
-        __syncthreads();
-    }
-    if (threadIdx.x == 0) first_bad[blockIdx.x] = red[0];
-}
 
-// trainer group: the same test per listed record, bad[j] = 1 when record list[j] (NULL: j) fails it.  Every thread that finds a bad
-// float stores the same 1: no sum, no order.
+// per listed record: bad[j] = 1 when record list[j] (NULL: j) is bad.  Every thread that finds a bad float stores the same 1: no sum,
+// no order.
 __global__ __launch_bounds__(256) void k_lstm_check_list(const uint8_t* __restrict__ data, const int64_t* __restrict__ list, long n,
                                                           uint8_t* __restrict__ bad) {
     __shared__ int any;
@@ -433,35 +418,11 @@ __global__ __launch_bounds__(256) void k_lstm_check_list(const uint8_t* __restri
 }
 
 // --------------------------------------------------------------------------------------------------------------- launchers ---
-void launch_gather(hipStream_t s, int nb, const GatherArgs& a, const LstmBufs& u) {
-    hipLaunchKernelGGL(k_lstm_gather, dim3(nb * kSteps), dim3(128), 0, s, a, u);
-}
-void launch_fwd(hipStream_t s, int nb, const LstmBufs& u, const float* W, const LstmOffsets& o) {
-    hipLaunchKernelGGL(k_lstm_fwd, dim3((nb + 15) / 16, 3), dim3(256), 0, s, u, W, o, nb);
-}
-void launch_heads_fwd(hipStream_t s, int nb, const LstmBufs& u, const float* W, const LstmOffsets& o, uint64_t seed, uint64_t step,
-                      int dropout) {
-    hipLaunchKernelGGL(k_lstm_heads_fwd, dim3(nb * kSteps), dim3(256), 0, s, u, W, o, seed, step, dropout);
-}
-void launch_heads_bwd(hipStream_t s, int nb, const LstmBufs& u, const float* W, const LstmOffsets& o, int dropout) {
-    hipLaunchKernelGGL(k_lstm_heads_bwd, dim3(nb * kSteps), dim3(256), 0, s, u, W, o, dropout);
-}
-void launch_bwd(hipStream_t s, int nb, const LstmBufs& u, const float* W, const LstmOffsets& o) {
-    hipLaunchKernelGGL(k_lstm_bwd, dim3((nb + 15) / 16, 3), dim3(256), 0, s, u, W, o, nb);
-}
-void launch_norm_update(hipStream_t s, float* W, float* acc, const float* grad, double* part, float clip, float lr, float momentum, long n,
-                        float* stats) {
-    hipLaunchKernelGGL(k_lstm_norm, dim3(kNormBlocks), dim3(256), 0, s, grad, n, part);
-    hipLaunchKernelGGL(k_lstm_update, dim3(1024), dim3(256), 0, s, W, acc, grad, part, kNormBlocks, clip, lr, momentum, n, stats);
-}
-void launch_check(hipStream_t s, const uint8_t* data, long nrec, long* first_bad, int nblocks) {
-    hipLaunchKernelGGL(k_lstm_check, dim3(nblocks), dim3(256), 0, s, data, nrec, first_bad);
-}
 void launch_check_list(hipStream_t s, const uint8_t* data, const int64_t* list, long n, uint8_t* bad, int nblocks) {
     hipLaunchKernelGGL(k_lstm_check_list, dim3(nblocks), dim3(256), 0, s, data, list, n, bad);
 }
 
-// trainer group: the same launches, each over all k members
+// the launches of a step, each over all k members
 void launch_group_gather(hipStream_t s, int nb, int k, const LstmMember* tab, const LstmGroupStep& g) {
     hipLaunchKernelGGL(k_lstm_group_gather, dim3(nb * kSteps, k), dim3(128), 0, s, tab, g);
 }

@@ -1,5 +1,6 @@
-// ethcnn_train.cpp -- host side of the trainer (include/ethcnn.h "training"): buffers, the GEMM descriptor tables, the step and
-// evaluation sequences (kernels: ethcnn_train_kernels.hip, launch order: ethcnn_train.h).
+// ethcnn_train.cpp -- a trainer's state (include/ethcnn.h "training"): options, weight / accumulator / gradient blobs, workspaces, the
+// GEMM descriptors over them, the QP list, and the entry points that touch nothing else.  Everything that enqueues a step is the
+// engine's (ethcnn_train_group.cpp); the solo entry points at the end of this file hand over to the trainer's own engine of K = 1.
 #include <algorithm>
 #include <cmath>
 #include <new>
@@ -8,26 +9,8 @@
 #include <vector>
 
 #include "ethcnn_ctx.h"
-#include "ethcnn_samples.h"
 #include "ethcnn_train.h"
 #include "ethcnn_train_host.h"
-
-namespace ethcnn {
-namespace train {
-void launch_trunk_fwd(hipStream_t s, int nb, const StepArgs& a, const float* W, const NetOffsets& o, int net);
-void launch_gemm(hipStream_t s, const GemmGroup* d_grp, int tiles);
-void launch_heads_fwd(hipStream_t s, int nb, const float* Z1, float* A1, float* M1, float* H1, float* A2, float* M2, float* H2,
-                      float* P, const int32_t* qp, const float* W, const NetOffsets& o, uint64_t seed, uint64_t step, int dropout, int net);
-void launch_loss(hipStream_t s, const float* P, const float* lab, int n, float* stats, float* dZ);
-void launch_heads_bwd(hipStream_t s, int nb, const float* dZ3, const float* A1, const float* M1, const float* A2, const float* M2,
-                      float* dZ2, float* dZ1, const float* W, const NetOffsets& o, int dropout);
-void launch_trunk_bwd(hipStream_t s, int nb, const float* trunk, const float* F, const float* dF, const float* W, const NetOffsets& o,
-                      float* part);
-void launch_update(hipStream_t s, float* W, float* acc, float* grad, const float* part, int nb, float lr, float momentum, long n,
-                   const TuneMask& mask);
-void launch_check_slots(hipStream_t s, const uint8_t* data, long nrec, uint32_t want, long* first_bad, int nblocks);
-}  // namespace train
-}  // namespace ethcnn
 
 using namespace ethcnn::train;
 using ethcnn::kBlobFloats;
@@ -49,21 +32,6 @@ int tensor_off(const char* name) {
 }
 }  // namespace
 
-static int terr(ethcnn_trainer* t, int code, const char* fmt, ...) {
-    char buf[512];
-    va_list ap;
-    va_start(ap, fmt);
-    std::vsnprintf(buf, sizeof buf, fmt, ap);
-    va_end(ap);
-    t->err = buf;
-    return code;
-}
-#define TCHK(t, call)                                                                                           \
-    do {                                                                                                        \
-        hipError_t e_ = (call);                                                                                 \
-        if (e_ != hipSuccess) return terr((t), ETHCNN_ERR_DEVICE, "%s failed: %s", #call, hipGetErrorString(e_)); \
-    } while (0)
-
 template <typename T>
 static int talloc(ethcnn_trainer* t, T** p, size_t count) {
     void* q = nullptr;
@@ -74,18 +42,6 @@ static int talloc(ethcnn_trainer* t, T** p, size_t count) {
     t->allocs.push_back(q);
     *p = (T*)q;
     return 0;
-}
-
-static void add_desc(GemmGroup& g, GemmDesc d) {
-    d.tiles_n = (d.N + 63) / 64;
-    d.tile_begin = g.tiles;
-    g.tiles += ((d.M + 63) / 64) * d.tiles_n;
-    if (d.nseg == 0) {
-        d.nseg = 1;
-        d.kseg[0] = 0;
-    }
-    if (d.msplit == 0) d.msplit = d.M;
-    g.d[g.n++] = d;
 }
 
 // FC1 forward of m rows: Z1[:, head] = F[:, :2688] x W1_head
@@ -140,71 +96,7 @@ GemmGroup train_bwd_group(const ethcnn_trainer* t, int m) {
     return g;
 }
 
-float train_lr_at(const ethcnn_trainer* t, int64_t step) {  // tf.train.exponential_decay(..., staircase=True)
-    const double p = std::floor((double)step / (double)t->opt.decay_steps);
-    return (float)((double)t->opt.lr_init * std::pow((double)t->opt.decay_rate, p));
-}
-
-// trunk forward .. heads forward of nb rows (evaluation and training share it)
-static void enqueue_forward(ethcnn_trainer* t, int set, int nb, const int32_t* d_idx, const int32_t* d_qp, int qp_fixed, uint64_t step,
-                            int dropout, float* P, float* lab, const GemmGroup* grp, int tiles) {
-    hipStream_t s = t->c->stream;
-    StepArgs a{};
-    a.data = t->data[set];
-    a.nrec = t->nrec[set];
-    a.idx_in = d_idx;
-    a.qp_in = d_qp;
-    std::memcpy(a.qps, t->qps, sizeof a.qps);
-    a.nqps = t->nqps;
-    a.qp_fixed = qp_fixed;
-    std::memcpy(a.slot_of_qp, t->slot_of_qp[set], sizeof a.slot_of_qp);
-    a.seed = t->opt.seed;
-    a.step = step;
-    a.dropout = dropout;
-    a.idx_out = t->idx;
-    a.qp_out = t->qp;
-    a.labels = lab;
-    a.trunk = t->trunk;
-    a.F = t->F;
-    launch_trunk_fwd(s, nb, a, t->W, t->o, t->net);
-    launch_gemm(s, grp, tiles);
-    launch_heads_fwd(s, nb, t->Z1, t->A1, t->M1, t->H1, t->A2, t->M2, t->H2, P, t->qp, t->W, t->o, t->opt.seed, step, dropout, t->net);
-}
-
-static int enqueue_step(ethcnn_trainer* t, int64_t step, bool explicit_batch) {
-    hipStream_t s = t->c->stream;
-    t->c->done_armed = 0;  // the context's completion word does not cover these launches
-    const int dropout = t->opt.dropout ? 1 : 0;
-    enqueue_forward(t, ETHCNN_TRAIN_SET_TRAIN, t->B, explicit_batch ? t->idx_in : nullptr, explicit_batch ? t->qp_in : nullptr, -1,
-                    (uint64_t)step, dropout, t->P, t->lab, t->g_fwd, t->t_fwd);
-    launch_loss(s, t->P, t->lab, t->B, t->stats, t->dZ3);
-    launch_heads_bwd(s, t->B, t->dZ3, t->A1, t->M1, t->A2, t->M2, t->dZ2, t->dZ1, t->W, t->o, dropout);
-    launch_gemm(s, t->g_bwd, t->t_bwd);
-    if (!t->tune) launch_trunk_bwd(s, t->B, t->trunk, t->F, t->dF, t->W, t->o, t->part);
-    launch_update(s, t->W, t->acc, t->grad, t->part, t->B, train_lr_at(t, step), t->opt.momentum, (long)kBlobFloats, t->mask);
-    TCHK(t, hipGetLastError());
-    return 0;
-}
-
-static int read_stats(ethcnn_trainer* t, float* loss3, float* acc3) {
-    float st[8];
-    TCHK(t, hipMemcpyAsync(st, t->stats, sizeof st, hipMemcpyDeviceToHost, t->c->stream));
-    TCHK(t, hipStreamSynchronize(t->c->stream));
-    for (int i = 0; i < 3; ++i) {
-        if (loss3) loss3[i] = st[i];
-        if (acc3) acc3[i] = st[3 + i];
-    }
-    return 0;
-}
-
-static int ready(ethcnn_trainer* t) {
-    if (!t->data[ETHCNN_TRAIN_SET_TRAIN]) return terr(t, ETHCNN_ERR_ARG, "no training samples (ethcnn_train_set_samples)");
-    if (!t->nqps) return terr(t, ETHCNN_ERR_ARG, "no QP list (ethcnn_train_set_qps)");
-    return 0;
-}
-
-extern "C" int ethcnn_train_create(ethcnn_ctx* c, const ethcnn_train_options* opt, ethcnn_trainer** out) {
-    if (!c || !opt || !out) return ETHCNN_ERR_ARG;
+int train_member_create(ethcnn_ctx* c, const ethcnn_train_options* opt, ethcnn_trainer** out) {
     *out = nullptr;
     if (opt->batch <= 0 || opt->batch > 65536) return set_err(c, ETHCNN_ERR_ARG, "batch must be in 1..65536, got %d", opt->batch);
     if (opt->decay_steps <= 0) return set_err(c, ETHCNN_ERR_ARG, "decay_steps must be positive");
@@ -222,8 +114,6 @@ extern "C" int ethcnn_train_create(ethcnn_ctx* c, const ethcnn_train_options* op
     t->cap = std::max(t->B, kEvalChunk);
     t->net = opt->net;
     t->tune = opt->tune;
-    for (int s = 0; s < 2; ++s)
-        for (int q = 0; q < 52; ++q) t->slot_of_qp[s][q] = -1;
     for (int br = 0; br < 3; ++br) {  // conv variables in creation order L, M, S (net_CTU64.py:122-138): Variable_{6 br' + 2 l}
         const int bc = br == 0 ? 2 : (br == 1 ? 1 : 0);
         for (int l = 0; l < 3; ++l) {
@@ -282,12 +172,9 @@ extern "C" int ethcnn_train_create(ethcnn_ctx* c, const ethcnn_train_options* op
     rc = rc ? rc : talloc(t, &t->dF, R * kTF);
     rc = rc ? rc : talloc(t, &t->part, (size_t)t->B * kConvFloats);
     rc = rc ? rc : talloc(t, &t->stats, 8);
-    rc = rc ? rc : talloc(t, &t->g_fwd, 1);
-    rc = rc ? rc : talloc(t, &t->g_bwd, 1);
-    rc = rc ? rc : talloc(t, &t->g_eval, 1);
     if (rc) {
         const std::string why = t->err;
-        ethcnn_train_destroy(t);
+        train_member_destroy(t);
         return set_err(c, rc, "%s", why.c_str());
     }
     // zeroed once: rows past a short evaluation chunk are computed by the FC1 GEMM but never read
@@ -295,27 +182,19 @@ extern "C" int ethcnn_train_create(ethcnn_ctx* c, const ethcnn_train_options* op
     for (void* p : {(void*)t->W, (void*)t->acc, (void*)t->grad}) e = e ? e : hipMemsetAsync(p, 0, kBlobFloats * 4, c->stream);
     e = e ? e : hipMemsetAsync(t->F, 0, R * kLdF * 4, c->stream);
     e = e ? e : hipMemsetAsync(t->stats, 0, 32, c->stream);
-    const GemmGroup gf = train_fc1_group(t, t->B), gb = train_bwd_group(t, t->B), ge = train_fc1_group(t, t->cap);
-    t->t_fwd = gf.tiles; t->t_bwd = gb.tiles; t->t_eval = ge.tiles;
-    e = e ? e : hipMemcpy(t->g_fwd, &gf, sizeof gf, hipMemcpyHostToDevice);
-    e = e ? e : hipMemcpy(t->g_bwd, &gb, sizeof gb, hipMemcpyHostToDevice);
-    e = e ? e : hipMemcpy(t->g_eval, &ge, sizeof ge, hipMemcpyHostToDevice);
     e = e ? e : hipStreamSynchronize(c->stream);
     if (e != hipSuccess) {
-        ethcnn_train_destroy(t);
+        train_member_destroy(t);
         return set_err(c, ETHCNN_ERR_DEVICE, "trainer setup: %s", hipGetErrorString(e));
     }
     *out = t;
     return ETHCNN_OK;
 }
 
-extern "C" void ethcnn_train_destroy(ethcnn_trainer* t) {
-    if (!t) return;
+void train_member_destroy(ethcnn_trainer* t) {
     (void)hipSetDevice(t->c->device);
     (void)hipStreamSynchronize(t->c->stream);
     for (void* p : t->allocs) (void)hipFree(p);
-    for (int s = 0; s < 2; ++s)
-        if (t->data[s]) (void)hipFree(t->data[s]);
     delete t;
 }
 
@@ -370,232 +249,75 @@ extern "C" int ethcnn_train_get_blob(ethcnn_trainer* t, float* blob, float* accu
     return 0;
 }
 
-// the checks every record takes on the device, then the set's bookkeeping: `p` (n records in HBM) becomes set `set`.  LDP: every record
-// carries the slot QPs sq[4] (one pass on the device).  On failure `p` is left to the caller.
-static int install_samples(ethcnn_trainer* t, int set, uint8_t* p, int64_t n, const int sq[4]) {
-    if (t->net == ETHCNN_TRAIN_NET_LDP) {
-        const int nblk = (int)std::min<int64_t>(1024, (n + 255) / 256);
-        long* d_bad = nullptr;
-        std::vector<long> bad((size_t)nblk);
-        const uint32_t want = (uint32_t)sq[0] | (uint32_t)sq[1] << 8 | (uint32_t)sq[2] << 16 | (uint32_t)sq[3] << 24;
-        hipError_t e = hipMalloc(&d_bad, sizeof(long) * nblk);
-        if (e == hipSuccess) {
-            launch_check_slots(t->c->stream, p, (long)n, want, d_bad, nblk);
-            e = hipGetLastError();
-        }
-        if (e == hipSuccess) e = hipMemcpyAsync(bad.data(), d_bad, sizeof(long) * nblk, hipMemcpyDeviceToHost, t->c->stream);
-        if (e == hipSuccess) e = hipStreamSynchronize(t->c->stream);
-        (void)hipFree(d_bad);
-        if (e != hipSuccess) return terr(t, ETHCNN_ERR_DEVICE, "sample check: %s", hipGetErrorString(e));
-        const long first = *std::min_element(bad.begin(), bad.end());
-        if (first < n) {
-            uint8_t r[3 * kSlotBytes + 1] = {0};
-            (void)hipMemcpy(r, p + (size_t)first * kRecLdp + kSlotBase, sizeof r, hipMemcpyDeviceToHost);
-            return terr(t, ETHCNN_ERR_FORMAT, "record %ld: slot QPs %d %d %d %d differ from record 0's %d %d %d %d", first, r[0],
-                        r[kSlotBytes], r[2 * kSlotBytes], r[3 * kSlotBytes], sq[0], sq[1], sq[2], sq[3]);
-        }
-    }
-    if (t->data[set]) (void)hipFree(t->data[set]);
-    if (t->net == ETHCNN_TRAIN_NET_LDP) {
-        for (int q = 0; q < 52; ++q) t->slot_of_qp[set][q] = -1;
-        for (int q = 0; q < 4; ++q) {
-            t->slot_qps[set][q] = sq[q];
-            t->slot_of_qp[set][sq[q]] = q;
-        }
-        if (set == ETHCNN_TRAIN_SET_TRAIN) {  // the QP list defaults to the four slots (every MODEL_TYPE trains on all of them)
-            std::memcpy(t->qps, sq, sizeof(int) * 4);
-            t->nqps = 4;
-        }
-    }
-    t->data[set] = p;
-    t->nrec[set] = n;
-    return 0;
-}
-
-extern "C" int ethcnn_train_set_samples(ethcnn_trainer* t, int set, const uint8_t* rec, size_t nbytes) {
-    if (!t) return ETHCNN_ERR_ARG;
-    if (set != 0 && set != 1) return terr(t, ETHCNN_ERR_ARG, "set must be 0 (train) or 1 (valid), got %d", set);
-    if (!rec || nbytes == 0) return terr(t, ETHCNN_ERR_ARG, "no sample records");
-    const int rb = t->net == ETHCNN_TRAIN_NET_LDP ? kRecLdp : kRec;
-    if (nbytes % rb) return terr(t, ETHCNN_ERR_FORMAT, "%zu bytes is not a whole number of %d-byte records", nbytes, rb);
-    if (nbytes / rb > 0x7fffffffull) return terr(t, ETHCNN_ERR_ARG, "more than 2^31 - 1 records");
-    int sq[4] = {0, 0, 0, 0};
-    if (t->net == ETHCNN_TRAIN_NET_LDP) {  // record 0's slot QPs: four distinct values in 0..51
-        for (int q = 0; q < 4; ++q) {
-            sq[q] = rec[kSlotBase + kSlotBytes * q];
-            if (sq[q] > 51) return terr(t, ETHCNN_ERR_FORMAT, "record 0: slot %d holds QP %d, outside 0..51", q, sq[q]);
-            for (int k = 0; k < q; ++k)
-                if (sq[k] == sq[q]) return terr(t, ETHCNN_ERR_FORMAT, "record 0: slots %d and %d both hold QP %d", k, q, sq[q]);
-        }
-    }
-    TCHK(t, hipSetDevice(t->c->device));
-    TCHK(t, hipStreamSynchronize(t->c->stream));
-    if (t->data[set]) {
-        (void)hipFree(t->data[set]);
-        t->data[set] = nullptr;
-        t->nrec[set] = 0;
-    }
-    void* p = nullptr;
-    if (hipMalloc(&p, nbytes) != hipSuccess) {
-        (void)hipGetLastError();
-        return terr(t, ETHCNN_ERR_NOMEM, "%zu bytes of samples do not fit in device memory", nbytes);
-    }
-    if (hipMemcpy(p, rec, nbytes, hipMemcpyHostToDevice) != hipSuccess) {
-        (void)hipFree(p);
-        return terr(t, ETHCNN_ERR_DEVICE, "sample upload failed");
-    }
-    const int rc = install_samples(t, set, (uint8_t*)p, (int64_t)(nbytes / rb), sq);
-    if (rc) (void)hipFree(p);
-    return rc;
-}
-
-// the same from a sample set already in HBM (include/ethcnn.h "sample sets"): adopted (take) or copied device to device
-extern "C" int ethcnn_train_set_samples_from(ethcnn_trainer* t, int set, ethcnn_samples* sm, int take) {
-    if (!t) return ETHCNN_ERR_ARG;
-    if (set != 0 && set != 1) return terr(t, ETHCNN_ERR_ARG, "set must be 0 (train) or 1 (valid), got %d", set);
-    if (!sm || !sm->built || sm->count == 0) return terr(t, ETHCNN_ERR_ARG, "no sample records (the sample set is not built or empty)");
-    if (sm->c != t->c) return terr(t, ETHCNN_ERR_ARG, "the sample set and the trainer live on different contexts");
-    if (sm->kind != t->net)
-        return terr(t, ETHCNN_ERR_FORMAT, "a sample set of %d-byte records does not feed this trainer's net (%d-byte records)",
-                    sm->record_bytes(), t->net == ETHCNN_TRAIN_NET_LDP ? kRecLdp : kRec);
-    if (sm->count > 0x7fffffffll) return terr(t, ETHCNN_ERR_ARG, "more than 2^31 - 1 records");
-    TCHK(t, hipSetDevice(t->c->device));
-    TCHK(t, hipStreamSynchronize(t->c->stream));
-    const size_t nbytes = (size_t)sm->count * (size_t)sm->record_bytes();
-    uint8_t* p = sm->data;
-    if (!take) {
-        if (hipMalloc((void**)&p, nbytes) != hipSuccess) {
-            (void)hipGetLastError();
-            return terr(t, ETHCNN_ERR_NOMEM, "%zu bytes of samples do not fit in device memory", nbytes);
-        }
-        // (on the context's stream, which does not wait for the null stream: a device-to-device hipMemcpy there may still be
-        // running when the check below reads its destination)
-        if (hipMemcpyAsync(p, sm->data, nbytes, hipMemcpyDeviceToDevice, t->c->stream) != hipSuccess ||
-            hipStreamSynchronize(t->c->stream) != hipSuccess) {
-            (void)hipFree(p);
-            return terr(t, ETHCNN_ERR_DEVICE, "sample copy failed");
-        }
-    }
-    const int rc = install_samples(t, set, p, sm->count, sm->qps);
-    if (rc) {
-        if (!take) (void)hipFree(p);
-        return rc;
-    }
-    if (take) {  // the trainer owns the buffer now; the set is empty (and may take sequences again)
-        sm->data = nullptr;
-        sm->count = 0;
-        sm->seqs.clear();
-        sm->built = false;
-    }
-    return 0;
-}
-
+// the QP list is part of the engine's member table: it takes effect with the next step, whoever enqueues it
 extern "C" int ethcnn_train_set_qps(ethcnn_trainer* t, const int* qps, int n) {
     if (!t) return ETHCNN_ERR_ARG;
     if (!qps || n <= 0 || n > 52) return terr(t, ETHCNN_ERR_ARG, "the QP list must hold 1..52 entries");
     for (int i = 0; i < n; ++i)
         if (qps[i] < 0 || qps[i] > 51) return terr(t, ETHCNN_ERR_ARG, "QP %d outside 0..51", qps[i]);
     if (t->net == ETHCNN_TRAIN_NET_LDP) {
-        if (!t->data[ETHCNN_TRAIN_SET_TRAIN]) return terr(t, ETHCNN_ERR_ARG, "LDP: upload the training samples before the QP list");
+        if (!t->eng->data[ETHCNN_TRAIN_SET_TRAIN]) return terr(t, ETHCNN_ERR_ARG, "LDP: upload the training samples before the QP list");
         for (int i = 0; i < n; ++i)
-            if (t->slot_of_qp[ETHCNN_TRAIN_SET_TRAIN][qps[i]] < 0)
+            if (t->eng->slot_of_qp[ETHCNN_TRAIN_SET_TRAIN][qps[i]] < 0)
                 return terr(t, ETHCNN_ERR_ARG, "QP %d is not a slot QP of the training samples", qps[i]);
     }
     std::memcpy(t->qps, qps, sizeof(int) * n);
     t->nqps = n;
+    t->eng->stale = true;
     return 0;
+}
+
+// ---- the solo trainer: an engine of K = 1 over the trainer itself; its messages are the trainer's
+static int from_engine(ethcnn_trainer* t, int rc) {
+    if (rc) t->err = t->eng->err;
+    return rc;
+}
+
+extern "C" int ethcnn_train_create(ethcnn_ctx* c, const ethcnn_train_options* opt, ethcnn_trainer** out) {
+    if (!c || !opt || !out) return ETHCNN_ERR_ARG;
+    ethcnn_trainer* t = nullptr;
+    if (int rc = train_member_create(c, opt, &t)) return rc;
+    if (int rc = train_engine_create(c, {t}, false, &t->eng)) {
+        train_member_destroy(t);
+        return rc;
+    }
+    t->solo = true;
+    *out = t;
+    return ETHCNN_OK;
+}
+
+extern "C" void ethcnn_train_destroy(ethcnn_trainer* t) {
+    if (!t) return;
+    (void)hipSetDevice(t->c->device);
+    (void)hipStreamSynchronize(t->c->stream);
+    if (t->solo) train_engine_destroy(t->eng);
+    train_member_destroy(t);
+}
+
+extern "C" int ethcnn_train_set_samples(ethcnn_trainer* t, int set, const uint8_t* rec, size_t nbytes) {
+    return t ? from_engine(t, ethcnn_train_group_set_samples(t->eng, set, rec, nbytes)) : ETHCNN_ERR_ARG;
+}
+
+extern "C" int ethcnn_train_set_samples_from(ethcnn_trainer* t, int set, ethcnn_samples* sm, int take) {
+    return t ? from_engine(t, ethcnn_train_group_set_samples_from(t->eng, set, sm, take)) : ETHCNN_ERR_ARG;
 }
 
 extern "C" int ethcnn_train_run(ethcnn_trainer* t, int64_t first_step, int64_t nsteps) {
-    if (!t) return ETHCNN_ERR_ARG;
-    if (first_step < 0 || nsteps < 0) return terr(t, ETHCNN_ERR_ARG, "negative step");
-    if (int rc = ready(t)) return rc;
-    TCHK(t, hipSetDevice(t->c->device));
-    for (int64_t i = 0; i < nsteps; ++i)
-        if (int rc = enqueue_step(t, first_step + i, false)) return rc;
-    return 0;
+    return t ? from_engine(t, ethcnn_train_group_run(t->eng, first_step, nsteps)) : ETHCNN_ERR_ARG;
 }
 
 extern "C" int ethcnn_train_last_stats(ethcnn_trainer* t, float loss3[3], float acc3[3]) {
-    if (!t) return ETHCNN_ERR_ARG;
-    TCHK(t, hipSetDevice(t->c->device));
-    return read_stats(t, loss3, acc3);
+    return t ? from_engine(t, ethcnn_train_group_last_stats(t->eng, loss3, acc3)) : ETHCNN_ERR_ARG;
 }
 
 extern "C" int ethcnn_train_step_indices(ethcnn_trainer* t, int64_t step, const int32_t* idx, const int* qp, int n, float loss3[3],
                                          float acc3[3]) {
-    if (!t) return ETHCNN_ERR_ARG;
-    if (int rc = ready(t)) return rc;
-    if (!idx || !qp || n != t->B) return terr(t, ETHCNN_ERR_ARG, "an explicit batch needs %d indices and QPs", t->B);
-    if (step < 0) return terr(t, ETHCNN_ERR_ARG, "negative step");
-    for (int i = 0; i < n; ++i) {
-        if (idx[i] < 0 || idx[i] >= t->nrec[0]) return terr(t, ETHCNN_ERR_ARG, "sample index %d outside 0..%lld", idx[i], (long long)t->nrec[0] - 1);
-        if (qp[i] < 0 || qp[i] > 51) return terr(t, ETHCNN_ERR_ARG, "QP %d outside 0..51", qp[i]);
-        if (t->net == ETHCNN_TRAIN_NET_LDP && t->slot_of_qp[ETHCNN_TRAIN_SET_TRAIN][qp[i]] < 0)
-            return terr(t, ETHCNN_ERR_ARG, "QP %d is not a slot QP of the training samples", qp[i]);
-    }
-    TCHK(t, hipSetDevice(t->c->device));
-    hipStream_t s = t->c->stream;
-    TCHK(t, hipMemcpyAsync(t->idx_in, idx, sizeof(int32_t) * n, hipMemcpyHostToDevice, s));
-    TCHK(t, hipMemcpyAsync(t->qp_in, qp, sizeof(int32_t) * n, hipMemcpyHostToDevice, s));
-    TCHK(t, hipStreamSynchronize(s));
-    if (int rc = enqueue_step(t, step, true)) return rc;
-    return read_stats(t, loss3, acc3);
+    return t ? from_engine(t, ethcnn_train_group_step_indices(t->eng, step, idx, qp, n, loss3, acc3)) : ETHCNN_ERR_ARG;
 }
 
 extern "C" int ethcnn_train_evaluate(ethcnn_trainer* t, int set, const int32_t* idx, int64_t n, int qp, float loss3[3], float acc3[3],
                                      float* probs) {
-    if (!t) return ETHCNN_ERR_ARG;
-    if (set != 0 && set != 1) return terr(t, ETHCNN_ERR_ARG, "set must be 0 (train) or 1 (valid), got %d", set);
-    if (!t->data[set]) return terr(t, ETHCNN_ERR_ARG, "no samples in set %d", set);
-    const bool ldp = t->net == ETHCNN_TRAIN_NET_LDP;
-    if (!(qp >= 0 && qp <= 51) && !(ldp && qp == -1))
-        return terr(t, ETHCNN_ERR_ARG, ldp ? "QP %d is neither a slot QP nor -1" : "QP %d outside 0..51", qp);
-    if (ldp && qp >= 0 && t->slot_of_qp[set][qp] < 0) return terr(t, ETHCNN_ERR_ARG, "QP %d is not a slot QP of set %d", qp, set);
-    if (n <= 0 || n > 0x7fffffffll || (!idx && n > t->nrec[set])) return terr(t, ETHCNN_ERR_ARG, "bad sample count %lld", (long long)n);
-    if (idx)
-        for (int64_t i = 0; i < n; ++i)
-            if (idx[i] < 0 || idx[i] >= t->nrec[set]) return terr(t, ETHCNN_ERR_ARG, "sample index %d outside 0..%lld", idx[i], (long long)t->nrec[set] - 1);
-    TCHK(t, hipSetDevice(t->c->device));
-    hipStream_t s = t->c->stream;
-    t->c->done_armed = 0;
-    std::vector<int32_t> ids;
-    if (!idx) {
-        ids.resize((size_t)n);
-        for (int64_t i = 0; i < n; ++i) ids[(size_t)i] = (int32_t)i;
-        idx = ids.data();
-    }
-    std::vector<int32_t> mixed;  // qp == -1: sample i at the slot draw(2, 0, i, 0) picks among the four
-    if (qp < 0) {
-        mixed.resize((size_t)n);
-        for (int64_t i = 0; i < n; ++i)
-            mixed[(size_t)i] = t->slot_qps[set][((draw(t->opt.seed, kStreamQp, 0, (uint64_t)i, 0) >> 32) * 4ull) >> 32];
-    }
-    float *Pn = nullptr, *Ln = nullptr;
-    int32_t *In = nullptr, *Qn = nullptr;
-    if (hipMalloc(&Pn, (size_t)n * kTOut * 4) != hipSuccess || hipMalloc(&Ln, (size_t)n * 16 * 4) != hipSuccess ||
-        hipMalloc(&In, (size_t)n * 4) != hipSuccess || (qp < 0 && hipMalloc(&Qn, (size_t)n * 4) != hipSuccess)) {
-        (void)hipGetLastError();
-        (void)hipFree(Pn); (void)hipFree(Ln); (void)hipFree(In); (void)hipFree(Qn);
-        return terr(t, ETHCNN_ERR_NOMEM, "cannot allocate the evaluation buffers of %lld samples", (long long)n);
-    }
-    hipError_t e = hipMemcpyAsync(In, idx, (size_t)n * 4, hipMemcpyHostToDevice, s);
-    if (e == hipSuccess && Qn) e = hipMemcpyAsync(Qn, mixed.data(), (size_t)n * 4, hipMemcpyHostToDevice, s);
-    for (int64_t c0 = 0; e == hipSuccess && c0 < n; c0 += t->cap) {
-        const int nb = (int)std::min<int64_t>(t->cap, n - c0);
-        enqueue_forward(t, set, nb, In + c0, Qn ? Qn + c0 : nullptr, qp, 0, 0, Pn + c0 * kTOut, Ln + c0 * 16, t->g_eval, t->t_eval);
-        e = hipGetLastError();
-    }
-    if (e == hipSuccess) {
-        float* st = t->stats;
-        launch_loss(s, Pn, Ln, (int)n, st, nullptr);  // ONE batch over all n samples
-        e = hipGetLastError();
-    }
-    if (e == hipSuccess && probs) e = hipMemcpyAsync(probs, Pn, (size_t)n * kTOut * 4, hipMemcpyDeviceToHost, s);
-    if (e == hipSuccess) e = hipStreamSynchronize(s);
-    (void)hipFree(Pn); (void)hipFree(Ln); (void)hipFree(In); (void)hipFree(Qn);
-    if (e != hipSuccess) return terr(t, ETHCNN_ERR_DEVICE, "evaluation: %s", hipGetErrorString(e));
-    return read_stats(t, loss3, acc3);
+    return t ? from_engine(t, ethcnn_train_group_evaluate(t->eng, set, idx, n, &qp, loss3, acc3, probs)) : ETHCNN_ERR_ARG;
 }
 
 extern "C" int ethcnn_train_debug_fetch(ethcnn_trainer* t, int which, float* out, size_t nfloats) {

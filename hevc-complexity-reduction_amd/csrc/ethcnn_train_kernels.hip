@@ -28,41 +28,42 @@ __device__ inline float keep_mask(uint64_t seed, uint64_t step, int slot, int un
 
 // ------------------------------------------------------------------------------------------------------------ trunk forward ---
 // NET = kNetAi: a 4992-byte record, luma * (1/255), the label row of QP q at 4160 + 16 q.  NET = kNetLdp: a 16516-byte record, the
-// slot of QP q (a.slot_of_qp) holds [qp | 16 labels | 4096 residual bytes] at 64 + 4113 slot, residual (x - 128) / 255 * 10.
-// The step kernels' bodies are device functions: the solo kernels (one trainer) and the group kernels (K trainers in one launch,
-// "trainer group" below) are thin wrappers that only decide whose buffers a block works on, so a group member's arithmetic is the
-// solo trainer's, operation for operation.
-// A: StepArgs, or MemberArgs (the same fields, the QP list and slot table behind pointers).
-template <int NET, class A>
-__device__ __forceinline__ void trunk_fwd_body(const int b, const A& a, const float* __restrict__ W, const NetOffsets& o) {
+// slot of QP q (g.slot_of_qp) holds [qp | 16 labels | 4096 residual bytes] at 64 + 4113 slot, residual (x - 128) / 255 * 10.
+// The step kernels' bodies are device functions; the kernels ("the kernels" below) only decide whose buffers a block works on.
+// m: the block's entry of the member table; g: what changes from launch to launch.
+template <int NET>
+__device__ __forceinline__ void trunk_fwd_body(const int b, const Member& m, const GroupStep& g, const NetOffsets& o) {
     __shared__ float rec[kTrunkRec];  // images then conv1 outputs (trunk record layout)
     __shared__ float feat[kTF];
     __shared__ float mean[21];
     __shared__ int sidx, sqp;
+    // the table's pointers are device memory (as_global, ethcnn_train.h)
+    const float* __restrict__ W = as_global(m.W);
+    float* const lab = as_global(m.lab);
     const int t = threadIdx.x;
     if (t == 0) {
         int64_t i;
-        if (a.idx_in) i = a.idx_in[b];
-        else i = (int64_t)(((draw(a.seed, kStreamIndex, a.step, (uint64_t)b, 0) >> 32) * (uint64_t)a.nrec) >> 32);
+        if (!g.drawn) i = as_global(m.idx_in)[b];
+        else i = (int64_t)(((draw(m.seed, kStreamIndex, g.step, (uint64_t)b, 0) >> 32) * (uint64_t)g.nrec) >> 32);
         int q;
-        if (a.qp_fixed >= 0) q = a.qp_fixed;
-        else if (a.qp_in) q = a.qp_in[b];
-        else q = a.qps[((draw(a.seed, kStreamQp, a.step, (uint64_t)b, 0) >> 32) * (uint64_t)a.nqps) >> 32];
+        if (m.qp_fixed >= 0) q = m.qp_fixed;
+        else if (!g.drawn && m.qp_in) q = as_global(m.qp_in)[b];
+        else q = m.qps[((draw(m.seed, kStreamQp, g.step, (uint64_t)b, 0) >> 32) * (uint64_t)m.nqps) >> 32];
         sidx = (int)i;
         sqp = q;
-        a.idx_out[b] = (int)i;
-        a.qp_out[b] = q;
+        as_global(m.idx)[b] = (int)i;
+        as_global(m.qp)[b] = q;
     }
     __syncthreads();
     if (NET == kNetAi) {
-        const uint8_t* r = a.data + (int64_t)sidx * kRec;
-        if (t < 16) a.labels[b * 16 + t] = (float)r[kLabelBase + 16 * sqp + t];
+        const uint8_t* r = g.data + (int64_t)sidx * kRec;
+        if (t < 16) lab[b * 16 + t] = (float)r[kLabelBase + 16 * sqp + t];
         const float inv255 = (float)(1.0 / 255.0);  // tf.scalar_mul(1.0 / 255.0, x)
         for (int p = t; p < 4096; p += 256) rec[p] = (float)r[p] * inv255;
     } else {
         // the slot base is odd (64 + 4113 slot), so the residual at +17 has no alignment: byte loads only
-        const uint8_t* r = a.data + (int64_t)sidx * kRecLdp + kSlotBase + (int64_t)kSlotBytes * a.slot_of_qp[sqp];
-        if (t < 16) a.labels[b * 16 + t] = (float)r[1 + t];
+        const uint8_t* r = g.data + (int64_t)sidx * kRecLdp + kSlotBase + (int64_t)kSlotBytes * g.slot_of_qp[sqp];
+        if (t < 16) lab[b * 16 + t] = (float)r[1 + t];
         for (int p = t; p < 4096; p += 256) rec[p] = (((float)r[17 + p] - 128.f) / 255.f) * 10.f;  // net_CTU64.py:102, in TF's order
     }
     __syncthreads();
@@ -131,15 +132,11 @@ __device__ __forceinline__ void trunk_fwd_body(const int b, const A& a, const fl
         feat[kF3Off[br] + q] = lrelu(acc + W[o.convb[br][2] + co]);
     }
     __syncthreads();
-    float* tr = a.trunk + (int64_t)b * kTrunkRec;
+    float* tr = as_global(m.trunk) + (int64_t)b * kTrunkRec;
     for (int p = t; p < kTrunkRec; p += 256) tr[p] = rec[p];
-    float* f = a.F + (int64_t)b * kLdF;
+    float* f = as_global(m.F) + (int64_t)b * kLdF;
     for (int p = t; p < kTF; p += 256) f[p] = feat[p];
     if (t == 0) f[kTF] = 1.f;  // ones column: the bias row of dW1 = F_aug^T dZ1
-}
-template <int NET>
-__global__ __launch_bounds__(256) void k_train_trunk_fwd(StepArgs a, const float* __restrict__ W, NetOffsets o) {
-    trunk_fwd_body<NET>(blockIdx.x, a, W, o);
 }
 
 // ------------------------------------------------------------------------------------------------------------ grouped GEMM ---
@@ -191,7 +188,6 @@ __device__ __forceinline__ void gemm_body(const GemmGroup* __restrict__ grp, con
         }
     }
 }
-__global__ __launch_bounds__(256) void k_train_gemm(const GemmGroup* __restrict__ grp) { gemm_body(grp, blockIdx.x); }
 
 // ------------------------------------------------------------------------------------------------------------ heads forward ---
 struct HeadBufs {
@@ -250,11 +246,6 @@ __device__ __forceinline__ void heads_fwd_body(const int b, const HeadBufs& h, c
         const float z = acc + W[o.b3[hd] + j];
         h.P[(long)b * kTOut + t] = 1.f / (1.f + expf(-z));
     }
-}
-template <int NET>
-__global__ __launch_bounds__(256) void k_train_heads_fwd(HeadBufs h, const float* __restrict__ W, NetOffsets o, uint64_t seed,
-                                                          uint64_t step, int dropout) {
-    heads_fwd_body<NET>(blockIdx.x, h, W, o, seed, step, dropout);
 }
 
 // ------------------------------------------------------------------------------------------------------------ loss ---
@@ -345,10 +336,6 @@ __device__ __forceinline__ void loss_body(const float* __restrict__ P, const flo
         dZ[i] = gp * p * (1.f - p);  // SigmoidGrad: dy * y * (1 - y)
     }
 }
-__global__ __launch_bounds__(256) void k_train_loss(const float* __restrict__ P, const float* __restrict__ lab, int n, float* stats,
-                                                     float* dZ) {
-    loss_body(P, lab, n, stats, dZ);
-}
 
 // ------------------------------------------------------------------------------------------------------------ heads backward ---
 struct HeadGrads {
@@ -381,9 +368,6 @@ __device__ __forceinline__ void heads_bwd_body(const int b, const HeadGrads& g, 
         const float da = dropout ? (acc * g.M1[(long)b * kTV + u]) / 0.5f : acc;
         g.dZ1[(long)b * kTV + u] = da * lrelu_grad(g.A1[(long)b * kTV + u]);
     }
-}
-__global__ __launch_bounds__(256) void k_train_heads_bwd(HeadGrads g, const float* __restrict__ W, NetOffsets o, int dropout) {
-    heads_bwd_body(blockIdx.x, g, W, o, dropout);
 }
 
 // ------------------------------------------------------------------------------------------------------------ trunk backward ---
@@ -472,11 +456,6 @@ __device__ __forceinline__ void trunk_bwd_body(const int b, const float* __restr
         }
     }
 }
-__global__ __launch_bounds__(256) void k_train_trunk_bwd(const float* __restrict__ trunk, const float* __restrict__ F,
-                                                          const float* __restrict__ dF, const float* __restrict__ W, NetOffsets o,
-                                                          float* __restrict__ part) {
-    trunk_bwd_body(blockIdx.x, trunk, F, dF, W, o, part);
-}
 
 // ------------------------------------------------------------------------------------------------------------ update ---
 // MomentumOptimizer (use_nesterov=False): accum = accum * momentum + grad; var -= lr * accum.  Conv gradients: sum of the
@@ -504,34 +483,16 @@ __device__ __forceinline__ void update_body(float* __restrict__ W, float* __rest
         W[j] = W[j] - lr * a;
     }
 }
-__global__ __launch_bounds__(256) void k_train_update(float* __restrict__ W, float* __restrict__ acc, float* __restrict__ grad,
-                                                       const float* __restrict__ part, int nb, float lr, float momentum, long n,
-                                                       TuneMask mask) {
-    update_body(W, acc, grad, part, nb, lr, momentum, n, mask);
-}
 
-// ------------------------------------------------------------------------------------------------------------ trainer group ---
-// K trainers in every launch of a step (ethcnn_train.h "trainer group").  tab: the device-resident member table; grid (B, K) for
-// the per-sample kernels, K blocks for the loss, K x tiles for the GEMMs, (1024, K) for the update.  Each block runs the solo body
-// on its member's buffers; the members share only the sample records.
-struct MemberArgs {  // the fields trunk_fwd_body reads, as in StepArgs
-    const uint8_t* data;
-    long nrec;
-    const int32_t *idx_in, *qp_in;
-    const int* qps;
-    int nqps, qp_fixed;
-    const int* slot_of_qp;
-    uint64_t seed, step;
-    int32_t *idx_out, *qp_out;
-    float *labels, *trunk, *F;
-};
-
+// ------------------------------------------------------------------------------------------------------------ the kernels ---
+// K >= 1 trainers in every launch of a step (ethcnn_train.h "the member table").  tab: the device-resident member table; grid (B, K)
+// for the per-sample kernels, K blocks for the loss, K x tiles for the GEMMs, (1024, K) for the update.  Each block runs the body on
+// its member's buffers; the members share only the sample records.  G: a pointer read from the table is device memory (as_global,
+// ethcnn_train.h), so the bodies get global_load / global_store as they would for a by-value argument, not FLAT accesses.
+#define G(p) as_global(p)
 template <int NET>
 __global__ __launch_bounds__(256) void k_group_trunk_fwd(const Member* __restrict__ tab, GroupStep g, NetOffsets o) {
-    const Member& m = tab[blockIdx.y];
-    const MemberArgs a{g.data,       g.nrec, g.drawn ? nullptr : m.idx_in, g.drawn ? nullptr : m.qp_in, m.qps, m.nqps, m.qp_fixed,
-                       g.slot_of_qp, m.seed, g.step, m.idx, m.qp, m.lab, m.trunk, m.F};
-    trunk_fwd_body<NET>(blockIdx.x, a, m.W, o);
+    trunk_fwd_body<NET>(blockIdx.x, tab[blockIdx.y], g, o);
 }
 // the members' descriptor groups side by side: every member has the same shapes, hence the same tile count
 __global__ __launch_bounds__(256) void k_group_gemm(const GemmGroup* __restrict__ grps, int tiles_per) {
@@ -540,26 +501,27 @@ __global__ __launch_bounds__(256) void k_group_gemm(const GemmGroup* __restrict_
 template <int NET>
 __global__ __launch_bounds__(256) void k_group_heads_fwd(const Member* __restrict__ tab, NetOffsets o, uint64_t step) {
     const Member& m = tab[blockIdx.y];
-    const HeadBufs h{m.Z1, m.A1, m.M1, m.H1, m.A2, m.M2, m.H2, m.P, m.qp};
-    heads_fwd_body<NET>(blockIdx.x, h, m.W, o, m.seed, step, m.dropout);
+    const HeadBufs h{G(m.Z1), G(m.A1), G(m.M1), G(m.H1), G(m.A2), G(m.M2), G(m.H2), G(m.P), G(m.qp)};
+    heads_fwd_body<NET>(blockIdx.x, h, G(m.W), o, m.seed, step, m.dropout);
 }
 __global__ __launch_bounds__(256) void k_group_loss(const Member* __restrict__ tab, int n, int with_grad) {
     const Member& m = tab[blockIdx.x];
-    loss_body(m.P, m.lab, n, m.stats, with_grad ? m.dZ3 : nullptr);
+    loss_body(G(m.P), G(m.lab), n, G(m.stats), with_grad ? G(m.dZ3) : nullptr);
 }
 __global__ __launch_bounds__(256) void k_group_heads_bwd(const Member* __restrict__ tab, NetOffsets o) {
     const Member& m = tab[blockIdx.y];
-    const HeadGrads g{m.dZ3, m.A1, m.M1, m.A2, m.M2, m.dZ2, m.dZ1};
-    heads_bwd_body(blockIdx.x, g, m.W, o, m.dropout);
+    const HeadGrads g{G(m.dZ3), G(m.A1), G(m.M1), G(m.A2), G(m.M2), G(m.dZ2), G(m.dZ1)};
+    heads_bwd_body(blockIdx.x, g, G(m.W), o, m.dropout);
 }
 __global__ __launch_bounds__(256) void k_group_trunk_bwd(const Member* __restrict__ tab, NetOffsets o) {
     const Member& m = tab[blockIdx.y];
-    trunk_bwd_body(blockIdx.x, m.trunk, m.F, m.dF, m.W, o, m.part);
+    trunk_bwd_body(blockIdx.x, G(m.trunk), G(m.F), G(m.dF), G(m.W), o, G(m.part));
 }
 __global__ __launch_bounds__(256) void k_group_update(const Member* __restrict__ tab, int nb, GroupRates r, long n, TuneMask mask) {
     const Member& m = tab[blockIdx.y];
-    update_body(m.W, m.acc, m.grad, m.part, nb, r.lr[blockIdx.y], m.momentum, n, mask);
+    update_body(G(m.W), G(m.acc), G(m.grad), G(m.part), nb, r.lr[blockIdx.y], m.momentum, n, mask);
 }
+#undef G
 
 // ------------------------------------------------------------------------------------------------------------ LDP set check ---
 // first record (per block, over a contiguous range of records) whose four slot QP bytes differ from `want` (record 0's, packed
@@ -585,40 +547,11 @@ __global__ __launch_bounds__(256) void k_train_check_slots(const uint8_t* __rest
 }
 
 // ------------------------------------------------------------------------------------------------------------ launchers ---
-void launch_trunk_fwd(hipStream_t s, int nb, const StepArgs& a, const float* W, const NetOffsets& o, int net) {
-    if (net == kNetLdp) hipLaunchKernelGGL(k_train_trunk_fwd<kNetLdp>, dim3(nb), dim3(256), 0, s, a, W, o);
-    else hipLaunchKernelGGL(k_train_trunk_fwd<kNetAi>, dim3(nb), dim3(256), 0, s, a, W, o);
-}
-void launch_gemm(hipStream_t s, const GemmGroup* d_grp, int tiles) {
-    hipLaunchKernelGGL(k_train_gemm, dim3(tiles), dim3(256), 0, s, d_grp);
-}
-void launch_heads_fwd(hipStream_t s, int nb, const float* Z1, float* A1, float* M1, float* H1, float* A2, float* M2, float* H2,
-                      float* P, const int32_t* qp, const float* W, const NetOffsets& o, uint64_t seed, uint64_t step, int dropout, int net) {
-    HeadBufs h{Z1, A1, M1, H1, A2, M2, H2, P, qp};
-    if (net == kNetLdp) hipLaunchKernelGGL(k_train_heads_fwd<kNetLdp>, dim3(nb), dim3(256), 0, s, h, W, o, seed, step, dropout);
-    else hipLaunchKernelGGL(k_train_heads_fwd<kNetAi>, dim3(nb), dim3(256), 0, s, h, W, o, seed, step, dropout);
-}
-void launch_loss(hipStream_t s, const float* P, const float* lab, int n, float* stats, float* dZ) {
-    hipLaunchKernelGGL(k_train_loss, dim3(1), dim3(256), 0, s, P, lab, n, stats, dZ);
-}
-void launch_heads_bwd(hipStream_t s, int nb, const float* dZ3, const float* A1, const float* M1, const float* A2, const float* M2,
-                      float* dZ2, float* dZ1, const float* W, const NetOffsets& o, int dropout) {
-    HeadGrads g{dZ3, A1, M1, A2, M2, dZ2, dZ1};
-    hipLaunchKernelGGL(k_train_heads_bwd, dim3(nb), dim3(256), 0, s, g, W, o, dropout);
-}
-void launch_trunk_bwd(hipStream_t s, int nb, const float* trunk, const float* F, const float* dF, const float* W, const NetOffsets& o,
-                      float* part) {
-    hipLaunchKernelGGL(k_train_trunk_bwd, dim3(nb), dim3(256), 0, s, trunk, F, dF, W, o, part);
-}
-void launch_update(hipStream_t s, float* W, float* acc, float* grad, const float* part, int nb, float lr, float momentum, long n,
-                   const TuneMask& mask) {
-    hipLaunchKernelGGL(k_train_update, dim3(1024), dim3(256), 0, s, W, acc, grad, part, nb, lr, momentum, n, mask);
-}
 void launch_check_slots(hipStream_t s, const uint8_t* data, long nrec, uint32_t want, long* first_bad, int nblocks) {
     hipLaunchKernelGGL(k_train_check_slots, dim3(nblocks), dim3(256), 0, s, data, nrec, want, first_bad);
 }
 
-// trainer group: the same eight launches, each over all k members
+// the eight launches of a step, each over all k members
 void launch_group_trunk_fwd(hipStream_t s, int nb, int k, const Member* tab, const GroupStep& g, const NetOffsets& o, int net) {
     if (net == kNetLdp) hipLaunchKernelGGL(k_group_trunk_fwd<kNetLdp>, dim3(nb, k), dim3(256), 0, s, tab, g, o);
     else hipLaunchKernelGGL(k_group_trunk_fwd<kNetAi>, dim3(nb, k), dim3(256), 0, s, tab, g, o);
