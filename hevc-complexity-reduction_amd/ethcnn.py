@@ -294,6 +294,10 @@ SIGNATURES = {
     "ethcnn_pacer_frame_device": (_i, [_vp, _vp, _i, _i, _vp, _vp]),
     "ethcnn_pacer_frame": (_i, [_vp, _vp, _i, _i, _vp, _vp]),
     "ethcnn_pacer_last": (_i, [_vp, _vp]),
+    "ethcnn_ladder_check": (_i, [_vp, _i, ctypes.c_int64, ctypes.c_uint32]),
+    "ethcnn_ladder_build": (_i, [_vp, _vp, _i, ctypes.c_int64, ctypes.c_uint32, _vp, _vp]),
+    "ethcnn_ladder_thin": (_i, [_vp, ctypes.c_int64, ctypes.c_int64, _vp, _vp]),
+    "ethcnn_ladder_write": (_i, [ctypes.c_char_p, _vp, ctypes.c_int64, _i]),
     "ethcnn_replay_plan": (_i, [_vp, _sz, _vp, _i, ctypes.POINTER(_i), _vp, ctypes.c_char_p, _sz]),
     "ethcnn_replay_uncut_device": (_i, [_vp, _vp, ctypes.c_int64, _vp, ctypes.c_int64, _i, _i, _i, _vp, _vp]),
     "ethcnn_replay_create": (_i, [_vp, ctypes.c_uint64, ctypes.POINTER(_vp)]),
@@ -2249,6 +2253,69 @@ class PartitionSim(object):
                                                  first, int(width), int(height), nf, ptr("probs"), ptr("rung"), ptr("over"), ptr("cost"), ptr("full")))
         out["over"] = out["over"].astype(bool)
         return out
+
+    def build_ladder(self, weights=None, grid=8, max_rungs=4096, max_bad_ppm=10 ** 6):
+        """a ladder for the search budget built from this set's labels (include/ethcnn.h "search budget: building a ladder"): a greedy
+        walk from the full search, one threshold moved per rung, one launch per step -> dict of numpy arrays over the rungs: thr
+        (SIM_THR records), coord int32 (-1 for rung 0), value int32, checked uint64 [n, 4], bad_ctus uint64, cost (Python integers)"""
+        w = None if weights is None else (ctypes.c_uint64 * 4)(*[int(x) for x in weights])
+        ladder_check(weights, grid, max_rungs, max_bad_ppm, self.lib)  # (sizes the output: a bad max_rungs never reaches np.zeros)
+        rungs, n = np.zeros(int(max_rungs), LADDER_RUNG), ctypes.c_int64(0)
+        self._chk(self.lib.ethcnn_ladder_build(self.h, w, int(grid), int(max_rungs), int(max_bad_ppm), rungs.ctypes.data, ctypes.byref(n)))
+        rungs = rungs[:n.value]
+        wt = [int(x) for x in (BUDGET_WEIGHTS if weights is None else weights)]
+        cost = np.array([sum(a * int(b) for a, b in zip(wt, row)) for row in rungs["checked"]], dtype=object)
+        return {"thr": np.ascontiguousarray(rungs["thr"]), "coord": rungs["coord"].copy(), "value": rungs["value"].copy(),
+                "checked": rungs["checked"].copy(), "bad_ctus": rungs["bad_ctus"].copy(), "cost": cost}
+
+
+# search budget: building a ladder (include/ethcnn.h).  ethcnn_ladder_rung as a numpy record: 72 bytes, no padding
+LADDER_RUNG = np.dtype([("thr", SIM_THR), ("coord", "<i4"), ("value", "<i4"), ("checked", "<u8", (4,)), ("bad_ctus", "<u8")])
+
+
+def _int_arg(x, lo, hi):
+    """an integer argument of a C entry, clamped into [lo, hi] so that ctypes takes it; the library names a value outside its rules"""
+    return max(lo, min(hi, int(x)))
+
+
+def ladder_check(weights=None, grid=8, max_rungs=4096, max_bad_ppm=10 ** 6, lib=None):
+    """ethcnn_ladder_check (host only): the argument rules of PartitionSim.build_ladder; EthCnnError where the library says ETHCNN_ERR_ARG"""
+    lib = lib or load_library()
+    w = None
+    if weights is not None:
+        if len(weights) != 4 or min(int(x) for x in weights) < 0:
+            raise ValueError("weights are four non-negative integers W64 W32 W16 W8, got %r" % (weights,))
+        w = (ctypes.c_uint64 * 4)(*[min(int(x), 2 ** 64 - 1) for x in weights])
+    rc = lib.ethcnn_ladder_check(w, _int_arg(grid, -1, 2 ** 31 - 1), _int_arg(max_rungs, -1, 2 ** 63 - 1), _int_arg(max_bad_ppm, 0, 2 ** 32 - 1))
+    if rc or int(max_bad_ppm) < 0:
+        raise EthCnnError(rc or ERR_ARG, lib.ethcnn_last_error(None).decode() if rc else "max_bad_ppm is negative")
+
+
+def ladder_thin(cost, K, lib=None):
+    """ethcnn_ladder_thin (host only): the indices of at most K of the rungs whose costs (strictly falling integers below 2^64) are
+    given, evenly spaced in cost; rungs 0 and n - 1 are always kept -> int32 array"""
+    lib = lib or load_library()
+    cost = [int(x) for x in cost]
+    if cost and (min(cost) < 0 or max(cost) >= 2 ** 64):
+        raise ValueError("costs lie in 0..2^64-1")
+    c = np.array(cost, dtype=np.uint64)
+    idx, k = np.zeros(max(1, min(len(cost), max(int(K), 1))), np.int32), ctypes.c_int64(0)
+    rc = lib.ethcnn_ladder_thin(c.ctypes.data if c.size else None, c.size, _int_arg(K, -1, 2 ** 63 - 1), idx.ctypes.data, ctypes.byref(k))
+    if rc:
+        raise EthCnnError(rc, lib.ethcnn_last_error(None).decode())
+    return idx[:k.value]
+
+
+def ladder_write(path, thr, order, lib=None):
+    """ethcnn_ladder_write (host only): SIM_THR records as a ladder file, one rung per line in the token order "ai" or "ldp" -- what
+    tools/control_budget.py --ladder and ETHCNN_SEARCH_BUDGET_LADDER read"""
+    lib = lib or load_library()
+    if order not in _THR_ORDERS:
+        raise ValueError("order is 'ai' or 'ldp', got %r" % (order,))
+    thr = _sim_cands(thr)
+    rc = lib.ethcnn_ladder_write(os.fsencode(path), thr.ctypes.data if thr.size else None, thr.size, _THR_ORDERS[order])
+    if rc:
+        raise EthCnnError(rc, lib.ethcnn_last_error(None).decode())
 
 
 # search budget, online (include/ethcnn.h "search budget, online")

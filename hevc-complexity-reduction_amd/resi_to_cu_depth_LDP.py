@@ -28,7 +28,8 @@ step + heads + gates on the GPU).  Differences from the reference, none in the n
     ETHCNN_SYNTHETIC_SEED=<n> opts into seeded synthetic CNN weights, otherwise it is an error;
   * ETHCNN_SEARCH_BUDGET=<share, 0..1> [ETHCNN_SEARCH_BUDGET_MODE=frame|carry] [ETHCNN_SEARCH_BUDGET_WEIGHTS="64 16 4 1"] holds every
     frame's pruned search under that share of the full search's weighted checks (include/ethcnn.h "search budget, online"): the daemon
-    predicts with open gates, whatever Thr_info.txt says, and a pacer (ethcnn.Pacer) picks a rung of the default ladder per frame and
+    predicts with open gates, whatever Thr_info.txt says, and a pacer (ethcnn.Pacer) picks a rung of the default ladder (or of the
+    ladder file ETHCNN_SEARCH_BUDGET_LADDER, in Low-Delay-P token order: tools/build_ladder.py --out FILE --order ldp) per frame and
     bakes the picked decisions into cu_depth.dat (values 0, 0.5, 1) inside the handshake.  The encoder reads Thr_info.txt itself, so the
     daemon refuses at start-up (status 1, before a GPU is touched, no signal file) unless that file is the companion line in
     Low-Delay-P token order, "0.25 0.75 0.25 0.75 0.25 0.75".  A frame with i_frame <= 1 or another geometry starts a new allowance.
@@ -213,8 +214,9 @@ def serve(workdir='.', max_frames=None, idle_timeout=None, poll_s=2e-4, device=0
     state.dat as it is, or restart the encode -- unless accept_stale is set, in which case the file is used as it is after
     a warning.  (HM then keeps spinning on pred_end.sig, exactly as it does when the reference's daemon dies.)"""
     p = lambda name: os.path.join(workdir, name)
-    budget = _sb.from_env()   # (ValueError for a bad value: before a GPU is touched)
+    budget, ladder = _sb.from_env(), None   # (ValueError for a bad value: before a GPU is touched)
     if budget is not None:
+        ladder = _sb.ladder_from_env('ldp')
         _sb.check_companion_thr_file(p(THR_FILE), _sb.COMPANION_LINE_LDP)
     ctx = _e.EthCnn(device=device)
     pacer, paced_geom, paced = None, None, [0, 0, 0, 0]   # frames, over budget, sum of cost, sum of full
@@ -222,7 +224,7 @@ def serve(workdir='.', max_frames=None, idle_timeout=None, poll_s=2e-4, device=0
         ctx.load_thresholds(p(THR_FILE))
         if budget is not None:
             ctx.set_thresholds(0.0, 0.0)    # open gates, whatever Thr_info.txt says: the baked file is what the encoder reads
-            pacer = _e.Pacer(ctx, budget[0], budget[1], weights=budget[2])
+            pacer = _e.Pacer(ctx, budget[0], budget[1], ladder=None if ladder is None else _e.sim_thr(*ladder), weights=budget[2])
         restore_cnn(ctx, workdir)
         if verbose:
             print('Python: predictor initialized on %s.' % ctx.device_name)
@@ -314,6 +316,7 @@ def main(argv):
             return 2
     try:  # a bad ETHCNN_SEARCH_BUDGET* value, or a Thr_info.txt that is not the companion line: refused before a GPU is touched
         if _sb.from_env() is not None:
+            _sb.ladder_from_env('ldp')
             _sb.check_companion_thr_file(THR_FILE, _sb.COMPANION_LINE_LDP)
     except ValueError as err:
         sys.stderr.write('resi_to_cu_depth_LDP: %s\n' % err)

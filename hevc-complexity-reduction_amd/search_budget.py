@@ -1,10 +1,12 @@
 """The environment of the search budget (include/ethcnn.h "search budget"), shared by the launchers that take one: the All-Intra
 launcher (video_to_cu_depth.py) and the Low-Delay-P daemon (resi_to_cu_depth_LDP.py).  ETHCNN_SEARCH_BUDGET=<share, 0..1>,
-ETHCNN_SEARCH_BUDGET_MODE=frame|carry (default frame), ETHCNN_SEARCH_BUDGET_WEIGHTS="64 16 4 1".  Nothing here touches a GPU."""
+ETHCNN_SEARCH_BUDGET_MODE=frame|carry (default frame), ETHCNN_SEARCH_BUDGET_WEIGHTS="64 16 4 1", ETHCNN_SEARCH_BUDGET_LADDER=<ladder file>
+(default: the default ladder; read only when a budget is set).  Nothing here touches a GPU."""
 import os
 
 COMPANION_LINE_AI = '0.75 0.25 0.75 0.25 0.75 0.25'    # ethcnn_budget_companion_thr in All-Intra token order: up down ...
 COMPANION_LINE_LDP = '0.25 0.75 0.25 0.75 0.25 0.75'   # ... and in Low-Delay-P token order: down up ...
+MAX_RUNGS = 4096                                       # ETHCNN_BUDGET_MAX_RUNGS
 
 
 def from_env():
@@ -43,3 +45,43 @@ def check_companion_thr_file(path, line):
     if tokens != [float(t) for t in line.split()]:
         raise ValueError("ETHCNN_SEARCH_BUDGET is set, so the encoder must read the companion thresholds: put the line\n    %s\ninto %s "
                          "(found: %s)" % (line, path, 'no readable file' if tokens is None else ' '.join('%g' % t for t in tokens)))
+
+
+def read_ladder(path, order):
+    """a ladder file (ethcnn_ladder_write, tools/build_ladder.py --out): one rung per line, six values in the token order `order`
+    ('ai': up down ..., 'ldp': down up ...), the most thorough first -> (up_k [K][3], down_k [K][3]) on the grid; ValueError names the
+    line, OSError a file that cannot be read"""
+    up, down = [], []
+    for no, line in enumerate(open(path).read().splitlines(), 1):
+        tok = line.split()
+        if not tok:
+            continue
+        try:
+            k = [int(round(float(t) * 1024)) for t in tok]
+        except (ValueError, OverflowError):
+            k = []
+        if len(k) != 6:
+            raise ValueError("%s, line %d: a rung is six values" % (path, no))
+        a, b = k[0::2], k[1::2]
+        u, d = (a, b) if order == "ai" else (b, a)
+        if min(u) < 0 or max(u) > 1024 or min(d) < -1 or max(d) > 1024:
+            raise ValueError("%s, line %d: thresholds outside [0, 1] (down: [-1/1024, 1])" % (path, no))
+        up.append(u)
+        down.append(d)
+    if not 1 <= len(up) <= MAX_RUNGS:
+        raise ValueError("%s: a ladder has 1..%d rungs, got %d" % (path, MAX_RUNGS, len(up)))
+    return up, down
+
+
+def ladder_from_env(order):
+    """None when ETHCNN_SEARCH_BUDGET_LADDER is unset or empty (the default ladder), else read_ladder of that file in the token order
+    of the launcher that asks; ValueError names a file that is missing or malformed or holds more than 4096 rungs"""
+    path = os.environ.get('ETHCNN_SEARCH_BUDGET_LADDER')
+    if not path:
+        return None
+    try:
+        return read_ladder(path, order)
+    except OSError as err:
+        raise ValueError("ETHCNN_SEARCH_BUDGET_LADDER='%s' cannot be read: %s" % (path, err.strerror or err))
+    except ValueError as err:
+        raise ValueError("ETHCNN_SEARCH_BUDGET_LADDER: %s" % err)

@@ -14,7 +14,8 @@ Differences from the reference, all outside the numbers it produces:
     InputBitDepth; above 8 the file holds 16-bit samples) and ETHCNN_INPUT_CHROMA_FORMAT=400|420|422|444 (InputChromaFormat).  Unset:
     the reference's 8-bit 4:2:0.  A bad value is a non-zero exit with a message.
   * ETHCNN_SEARCH_BUDGET=<share, 0..1> holds every frame's pruned search under that share of the full search's weighted checks
-    (include/ethcnn.h "search budget"): the launcher predicts with open gates, picks a rung of the default ladder per frame and
+    (include/ethcnn.h "search budget"): the launcher predicts with open gates, picks a rung of the default ladder (or of the ladder
+    file ETHCNN_SEARCH_BUDGET_LADDER, in All-Intra token order: tools/build_ladder.py --out FILE --order ai) per frame and
     writes a BAKED cu_depth.dat (values 0, 0.5, 1).  HM reads Thr_info.txt afterwards, so the launcher refuses (exit status 1, no
     cu_depth.dat) unless that file is the companion line "0.75 0.25 0.75 0.25 0.75 0.25".  ETHCNN_SEARCH_BUDGET_MODE=frame|carry
     (default frame) and ETHCNN_SEARCH_BUDGET_WEIGHTS="64 16 4 1" are optional.  One GPU only: ETHCNN_DEVICES with a budget is refused.
@@ -81,11 +82,19 @@ def check_companion_thr_file(path=THR_FILE):
     _sb.check_companion_thr_file(path, COMPANION_LINE)
 
 
-def write_budgeted(ctx, yuv_name, qp_seq, frame_width, frame_height, budget, save_file):
-    """budget mode: every frame of the file predicted with open gates, one rung of the default ladder picked per frame under the
-    budget, the picked decisions baked into save_file (temp file + rename).  -> (frames, achieved share, over-budget frames)"""
+def search_ladder_from_env():
+    """None (the default ladder) when ETHCNN_SEARCH_BUDGET_LADDER is unset or empty, else that ladder file read in All-Intra token order
+    -> (up_k, down_k); ValueError names a bad file"""
+    return _sb.ladder_from_env('ai')
+
+
+def write_budgeted(ctx, yuv_name, qp_seq, frame_width, frame_height, budget, save_file, ladder=None):
+    """budget mode: every frame of the file predicted with open gates, one rung of the ladder (None: the default one) picked per frame
+    under the budget, the picked decisions baked into save_file (temp file + rename).  -> (frames, achieved share, over-budget frames)"""
     import numpy as np
     share, mode, weights = budget
+    if ladder is not None:
+        ladder = _e.sim_thr(*ladder)
     tmp = '%s.tmp.%d' % (save_file, os.getpid())
     try:
         ctx.set_thresholds(0.0, 0.0)    # open gates, whatever Thr_info.txt says: the baked file is what the encoder reads
@@ -93,7 +102,7 @@ def write_budgeted(ctx, yuv_name, qp_seq, frame_width, frame_height, budget, sav
         probs = np.fromfile(tmp, dtype='<f4')
         with _e.PartitionSim(ctx) as sim:
             sim.add_frames(probs, None, frame_width, frame_height, nframes=n_frames)
-            out = sim.budget_control(share, mode, weights=weights, width=frame_width, height=frame_height, nframes=n_frames)
+            out = sim.budget_control(share, mode, ladder=ladder, weights=weights, width=frame_width, height=frame_height, nframes=n_frames)
         out['probs'].astype('<f4').tofile(tmp)
         os.replace(tmp, save_file)
     finally:
@@ -202,7 +211,9 @@ def main(argv=None):
         fmt = source_format_from_env()
         frame_bytes = _e.source_frame_bytes(width, height, *fmt)[1]         # :136 width * height * 3 // 2 unless the environment says otherwise
         budget = search_budget_from_env()
+        ladder = None
         if budget is not None:
+            ladder = search_ladder_from_env()
             check_companion_thr_file()
     except (ValueError, _e.EthCnnError) as err:
         sys.stderr.write('video_to_cu_depth: %s\n' % err)
@@ -226,7 +237,7 @@ def main(argv=None):
         stamps.append(('thresholds + weights + plan guard', time.perf_counter()))
         t1 = time.time()                       # the reference times get_prob only (:142-145)
         if budget is not None:
-            n_frames, share, over = write_budgeted(ctx, yuv_file, qp_seq, width, height, budget, SAVE_FILE)
+            n_frames, share, over = write_budgeted(ctx, yuv_file, qp_seq, width, height, budget, SAVE_FILE, ladder)
             sys.stderr.write('video_to_cu_depth: search budget %g (%s): %.6f of the full search over %d frames, %d over budget\n'
                              % (budget[0], budget[1], share, n_frames, over))
         else:

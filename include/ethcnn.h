@@ -1212,6 +1212,60 @@ int ethcnn_pacer_frame_device(ethcnn_pacer* pacer, const float* d_probs, int wid
 int ethcnn_pacer_frame(ethcnn_pacer* pacer, const float* probs, int width, int height, float* baked, ethcnn_pacer_result* result);
 int ethcnn_pacer_last(ethcnn_pacer* pacer, ethcnn_pacer_result* out);
 
+/* ---- search budget: building a ladder.  The two sections above pick a rung of a LADDER per frame; how well they hold a budget depends on
+ *      that ladder, and the default one is the same on every level and never looks at a label.  These entries turn a simulator's set
+ *      with labels into a ladder by a greedy walk from the full search: every step moves ONE of the six thresholds to the nearest grid
+ *      value that lowers the weighted check count, and of the six possible moves takes the one that costs the fewest newly bad CTUs per
+ *      unit of cost saved.  One launch per step; the choice is made on the device.  No reference counterpart.
+ *   Inputs: a simulator set with at least one labelled CTU; weight[4] under the rules of "search budget" (NULL: 64 16 4 1); grid, a power
+ *      of two in 1..1024; max_rungs in 1..ETHCNN_BUDGET_MAX_RUNGS; max_bad_ppm <= 10^6.  The gates are always ETHCNN_SIM_GATES_NONE, as
+ *      for every budget entry.  Throughout, cost = sum_d weight[d] * checked[d] and bad = bad_ctus, both of ethcnn_sim_counts over the
+ *      WHOLE set.
+ *   Rung 0 is the full search (up_k = 1024, down_k = -1 on all levels), with coord = -1 and value = 0.
+ *   A step from the rung with thresholds t, cost C and bad CTUs B.  Coordinates are taken in the sweep order c = 0..5 = down0, up0, down1,
+ *      up1, down2, up2 (ethcnn_sim_sweep), d = c >> 1 is the level.  Each coordinate has at most one move:
+ *        1. its candidate values v are the multiples of grid with   down_k[d] < v <= up_k[d]            for a down,
+ *                                                                   max(down_k[d], 0) <= v < up_k[d]    for an up
+ *           (so down_k <= up_k holds on every rung);
+ *        2. they are walked from the one nearest to the coordinate's current value outwards (rising for a down, falling for an up);
+ *        3. the move is the FIRST v with cost(v) < C, where cost(v) is the cost of t with that one coordinate set to v; without one the
+ *           coordinate has no move;
+ *        4. if that v has bad(v) * 10^6 > max_bad_ppm * labelled_ctus the coordinate has no move: nothing further is looked at.
+ *      Of the moves, the one with the smallest (bad(v) - B) / (C - cost(v)) is taken, compared exactly by signed 128-bit cross products
+ *      (bad(v) - B may be negative); at a tie the larger saving C - cost(v), at a further tie the smaller c.
+ *      The walk stops when no coordinate has a move, or at max_rungs rungs.  Costs fall strictly along the path.
+ *   Result: ethcnn_ladder_rung[*nrungs_out], 72 bytes each, little-endian, no padding: thr at 0, coord int32 at 24 (the coordinate that
+ *      moved), value int32 at 28 (where to), checked uint64[4] at 32 and bad_ctus uint64 at 64: exactly what ethcnn_sim_eval gives for thr
+ *      under gates none.
+ *   Refusals, each ETHCNN_ERR_ARG with the outputs untouched and before anything is launched: a set without a labelled CTU; a grid
+ *      that is no power of two in 1..1024; max_rungs outside 1..ETHCNN_BUDGET_MAX_RUNGS; max_bad_ppm > 10^6; a weight of 2^32 or more; a
+ *      cost bound ctus * (weight[0] + 4 weight[1] + 16 weight[2] + 64 weight[3]) that does not fit in 64 bits.  ethcnn_ladder_check
+ *      applies the rules of the four plain arguments alone (host only, pure; the message is read with ethcnn_last_error(NULL)).
+ *   ethcnn_ladder_build is synchronous on the context's stream.  Per call it holds in HBM a table uint64 [6][1025 / grid + 1][5], a state
+ *      block and max_rungs rungs (ETHCNN_ERR_NOMEM when they do not fit).  Integers only: nothing depends on the launch grid or on the
+ *      order in which blocks finish, and a second build on the same set gives the same bytes.
+ *   ethcnn_ladder_thin (host only, pure): cost[n] must fall strictly (else ETHCNN_ERR_ARG); picks at most K of the n rungs, evenly spaced
+ *      in COST.  n <= K: the identity.  K = 1: rung 0.  Otherwise for j = 0..K-1, target_j = cost[0] - floor(j * (cost[0] - cost[n-1]) /
+ *      (K - 1)) with a 128-bit product, and idx_j is the smallest i with cost[i] <= target_j; the output is the distinct idx_j in rising
+ *      order (rungs 0 and n - 1 are always among them).  idx_out holds min(n, K) entries, *k_out says how many were written.  NULL, n < 1
+ *      or K < 1: ETHCNN_ERR_ARG, outputs untouched.
+ *   ethcnn_ladder_write (host only): K rungs (1..ETHCNN_BUDGET_MAX_RUNGS, each in the simulator's ranges), one per line, six values k / 1024
+ *      with ten decimals in the token order `order` (ETHCNN_THR_ORDER_AI / _LDP), to a temp file that is then renamed: the ladder file
+ *      that tools/control_budget.py --ladder and ETHCNN_SEARCH_BUDGET_LADDER read.  Every grid value, down_k = -1 included, reads back
+ *      exactly. */
+typedef struct ethcnn_ladder_rung {
+    ethcnn_sim_thr thr;
+    int32_t coord;
+    int32_t value;
+    uint64_t checked[4];
+    uint64_t bad_ctus;
+} ethcnn_ladder_rung;
+int ethcnn_ladder_check(const uint64_t weight[4], int grid, int64_t max_rungs, uint32_t max_bad_ppm);
+int ethcnn_ladder_build(ethcnn_sim* sim, const uint64_t weight[4], int grid, int64_t max_rungs, uint32_t max_bad_ppm, ethcnn_ladder_rung* rungs_out,
+                        int64_t* nrungs_out);
+int ethcnn_ladder_thin(const uint64_t* cost, int64_t n, int64_t K, int32_t* idx_out, int64_t* k_out);
+int ethcnn_ladder_write(const char* path, const ethcnn_sim_thr* thr, int64_t K, int order);
+
 /* ---- sample-set replay: an inter sample set (LDP_Valid.dat, LDP_Test.dat, plain or _shuffled: the 16516-byte records of "sample sets"
  *      above) put back together into the residual pictures and label planes it was cut from, and run through the deployed Low-Delay-P
  *      chain, ethcnn_ldp_sequence_device: forward in time, i_frame % 4 features, the state carried over the whole sequence.  The inverse

@@ -42,31 +42,16 @@ sim_tool = importlib.util.module_from_spec(_spec)
 _spec.loader.exec_module(sim_tool)
 cal_tool = sim_tool.cal_tool
 Usage = sim_tool.Usage
-MAX_RUNGS = 4096
+_spec = importlib.util.spec_from_file_location("search_budget", os.path.join(ROOT, "hevc-complexity-reduction_amd", "search_budget.py"))
+_sb = importlib.util.module_from_spec(_spec)   # (by path: the package itself is imported only when a GPU is about to be used)
+_spec.loader.exec_module(_sb)
+MAX_RUNGS = _sb.MAX_RUNGS
 
 
 def read_ladder(path, order):
-    """one rung per line, six values in `order` -> (up_k [K][3], down_k [K][3]) on the grid; ValueError names the line"""
-    up, down = [], []
-    for no, line in enumerate(open(path).read().splitlines(), 1):
-        tok = line.split()
-        if not tok:
-            continue
-        try:
-            k = [int(round(float(t) * 1024)) for t in tok]
-        except ValueError:
-            k = []
-        if len(k) != 6:
-            raise ValueError("%s, line %d: a rung is six values" % (path, no))
-        a, b = k[0::2], k[1::2]
-        u, d = (a, b) if order == "ai" else (b, a)
-        if min(u) < 0 or max(u) > 1024 or min(d) < -1 or max(d) > 1024:
-            raise ValueError("%s, line %d: thresholds outside [0, 1] (down: [-1/1024, 1])" % (path, no))
-        up.append(u)
-        down.append(d)
-    if not 1 <= len(up) <= MAX_RUNGS:
-        raise ValueError("%s: a ladder has 1..%d rungs, got %d" % (path, MAX_RUNGS, len(up)))
-    return up, down
+    """one rung per line, six values in `order` -> (up_k [K][3], down_k [K][3]) on the grid; ValueError names the line (the parser is
+    the launchers': hevc-complexity-reduction_amd/search_budget.py)"""
+    return _sb.read_ladder(path, order)
 
 
 def parse(argv):

@@ -33,8 +33,9 @@
  *
  * Environment as the Python daemon: ETHCNN_SYNTHETIC_SEED / ETHCNN_HEAD_GAIN (seeded weights when a trained blob is absent:
  * model_LDP_2000000_qp22~37.dat.data is not in the reference repository), ETHCNN_DEVICE, and the search budget:
- * ETHCNN_SEARCH_BUDGET=<share, 0..1> [ETHCNN_SEARCH_BUDGET_MODE=frame|carry] [ETHCNN_SEARCH_BUDGET_WEIGHTS="64 16 4 1"] (names, value
- * rules and error texts of the All-Intra launcher).  With it the daemon predicts with open gates, whatever Thr_info.txt says, and a pacer
+ * ETHCNN_SEARCH_BUDGET=<share, 0..1> [ETHCNN_SEARCH_BUDGET_MODE=frame|carry] [ETHCNN_SEARCH_BUDGET_WEIGHTS="64 16 4 1"]
+ * [ETHCNN_SEARCH_BUDGET_LADDER=<ladder file in Low-Delay-P token order; default: the default ladder>] (names, value rules and error texts
+ * of the Python launchers).  With it the daemon predicts with open gates, whatever Thr_info.txt says, and a pacer
  * (include/ethcnn.h "search budget, online") bakes each frame's picked decisions into the page-locked buffer cu_depth.dat is written from,
  * in place, once the frame's step has succeeded.  It refuses at start-up (status 1, before a GPU is touched, no signal file) unless
  * Thr_info.txt is the companion line in Low-Delay-P token order, "0.25 0.75 0.25 0.75 0.25 0.75".  A frame with i_frame <= 1 or another
@@ -379,6 +380,101 @@ static int budget_from_env(int* on, uint32_t* ppm, int* mode, uint64_t weight[4]
     *on = 1;
     return 0;
 }
+/* ETHCNN_SEARCH_BUDGET_LADDER (read only when a budget is set): a ladder file in Low-Delay-P token order, one rung per line as
+ * ethcnn_ladder_write and tools/build_ladder.py --out FILE --order ldp write it -> 0 with *out = NULL (unset or empty: the default ladder) or
+ * a malloc'ed ladder of *K rungs, or -1 with the message printed: the rules and texts of search_budget.py (read_ladder, ladder_from_env) */
+static long long round_half_even(double v) { /* |v| < 2^53 */
+    long long k = (long long)v;
+    if ((double)k > v) --k;
+    const double r = v - (double)k;
+    if (r > 0.5 || (r == 0.5 && (k & 1))) ++k;
+    return k;
+}
+/* one line -> 0: blank, 1: a rung, -1: not six values, -2: values outside the grid's range */
+static int ladder_line(char* q, char* end_of_line, ethcnn_sim_thr* t) {
+    long long k[6];
+    int n = 0;
+    const char saved = *end_of_line;
+    *end_of_line = 0;
+    int rc = 0;
+    for (;;) {
+        while (is_space(*q)) ++q;
+        if (!*q) break;
+        char* end = NULL;
+        const double x = strtod(q, &end);
+        int hex = 0;
+        for (const char* h = q; h < end; ++h) hex |= *h == 'x' || *h == 'X';
+        if (end == q || (*end && !is_space(*end)) || hex || !(x - x == 0.0)) { rc = -1; break; } /* (x - x is not 0 for an infinity or a NaN) */
+        if (n < 6) k[n] = x > 1e9 ? 1 << 30 : x < -1e9 ? -(1 << 30) : round_half_even(x * 1024.0);
+        ++n;
+        q = end;
+    }
+    *end_of_line = saved;
+    if (rc == 0 && n == 0) return 0;
+    if (rc != 0 || n != 6) return -1;
+    for (int l = 0; l < 3; ++l) { /* down up down up down up */
+        const long long d = k[2 * l], u = k[2 * l + 1];
+        if (u < 0 || u > 1024 || d < -1 || d > 1024) return -2;
+        t->down_k[l] = (int32_t)d;
+        t->up_k[l] = (int32_t)u;
+    }
+    return 1;
+}
+static int ladder_from_env(ethcnn_sim_thr** out, int64_t* K) {
+    const char* path = getenv("ETHCNN_SEARCH_BUDGET_LADDER");
+    *out = NULL;
+    *K = 0;
+    if (!path || !*path) return 0;
+    FILE* f = fopen(path, "rb");
+    char* text = NULL;
+    size_t len = 0, cap = 0;
+    int io_errno = f ? 0 : errno;
+    while (f && !io_errno) {
+        if (len + 65536 + 1 > cap) {
+            cap = cap ? cap * 2 : 1 << 17;
+            char* grown = (char*)realloc(text, cap);
+            if (!grown) { io_errno = ENOMEM; break; }
+            text = grown;
+        }
+        const size_t got = fread(text + len, 1, 65536, f);
+        len += got;
+        if (got < 65536) { if (ferror(f)) io_errno = errno ? errno : EIO; break; }
+    }
+    if (f) fclose(f);
+    if (io_errno) {
+        fprintf(stderr, "resi_to_cu_depth_ldp: ETHCNN_SEARCH_BUDGET_LADDER='%s' cannot be read: %s\n", path, strerror(io_errno));
+        free(text);
+        return -1;
+    }
+    if (!text) text = (char*)malloc(1);
+    if (!text) return -1;
+    text[len] = 0;
+    ethcnn_sim_thr* lad = (ethcnn_sim_thr*)malloc(sizeof(ethcnn_sim_thr) * ETHCNN_BUDGET_MAX_RUNGS);
+    if (!lad) { free(text); return -1; }
+    long rungs = 0;
+    int line_no = 0, rc = 0;
+    size_t at = 0;
+    while (at < len && rc == 0) {
+        size_t e = at;
+        while (e < len && text[e] != '\n' && text[e] != '\r' && text[e] != '\v' && text[e] != '\f') ++e;
+        ++line_no;
+        ethcnn_sim_thr t;
+        const int got = ladder_line(text + at, text + e, &t);
+        if (got == -1) { fprintf(stderr, "resi_to_cu_depth_ldp: ETHCNN_SEARCH_BUDGET_LADDER: %s, line %d: a rung is six values\n", path, line_no); rc = -1; }
+        else if (got == -2) { fprintf(stderr, "resi_to_cu_depth_ldp: ETHCNN_SEARCH_BUDGET_LADDER: %s, line %d: thresholds outside [0, 1] (down: [-1/1024, 1])\n", path, line_no); rc = -1; }
+        else if (got == 1) { if (rungs < ETHCNN_BUDGET_MAX_RUNGS) lad[rungs] = t; ++rungs; }
+        at = e < len && text[e] == '\r' && e + 1 < len && text[e + 1] == '\n' ? e + 2 : e + 1;
+    }
+    free(text);
+    if (rc == 0 && (rungs < 1 || rungs > ETHCNN_BUDGET_MAX_RUNGS)) {
+        fprintf(stderr, "resi_to_cu_depth_ldp: ETHCNN_SEARCH_BUDGET_LADDER: %s: a ladder has 1..%d rungs, got %ld\n", path, ETHCNN_BUDGET_MAX_RUNGS, rungs);
+        rc = -1;
+    }
+    if (rc != 0) { free(lad); return -1; }
+    *out = lad;
+    *K = rungs;
+    return 0;
+}
 /* the encoder reads Thr_info.txt itself: a baked cu_depth.dat means what it says only under the companion thresholds */
 static int check_companion_thr_file(void) {
     static const double want[6] = {0.25, 0.75, 0.25, 0.75, 0.25, 0.75};
@@ -446,7 +542,10 @@ int main(int argc, char** argv) {
     uint32_t budget_ppm = 0;
     uint64_t budget_weight[4] = {64, 16, 4, 1};
     if (budget_from_env(&budget_on, &budget_ppm, &budget_mode, budget_weight) != 0) return 1;
-    if (budget_on && check_companion_thr_file() != 0) return 1;
+    ethcnn_sim_thr* budget_ladder = NULL; /* NULL: the default ladder */
+    int64_t budget_rungs = 0;
+    if (budget_on && ladder_from_env(&budget_ladder, &budget_rungs) != 0) return 1;
+    if (budget_on && check_companion_thr_file() != 0) { free(budget_ladder); return 1; }
     ethcnn_pacer* pacer = NULL;
     int paced_w = -1, paced_h = -1;
     long paced_frames = 0, paced_over = 0;
@@ -456,7 +555,7 @@ int main(int argc, char** argv) {
     memset(&opt, 0, sizeof opt);
     const char* dev = getenv("ETHCNN_DEVICE");
     opt.device = dev ? atoi(dev) : 0;
-    if (ethcnn_create(&ctx, &opt) != ETHCNN_OK) { fprintf(stderr, "resi_to_cu_depth_ldp: create: %s\n", ethcnn_last_error(NULL)); return 1; }
+    if (ethcnn_create(&ctx, &opt) != ETHCNN_OK) { fprintf(stderr, "resi_to_cu_depth_ldp: create: %s\n", ethcnn_last_error(NULL)); free(budget_ladder); return 1; }
     int rc = 1;
     uint8_t* luma = NULL;
     float* probs = NULL;
@@ -466,9 +565,9 @@ int main(int argc, char** argv) {
         fprintf(stderr, "resi_to_cu_depth_ldp: %s\n", ethcnn_last_error(ctx));
         goto out;
     }
-    /* open gates, whatever Thr_info.txt says: the baked file is what the encoder reads; one pacer with the default ladder */
+    /* open gates, whatever Thr_info.txt says: the baked file is what the encoder reads; one pacer with the default ladder or the file's */
     if (budget_on && (ethcnn_set_thresholds(ctx, 0.0f, 0.0f) != ETHCNN_OK ||
-                      ethcnn_pacer_create(ctx, NULL, 0, budget_weight, budget_ppm, budget_mode, &pacer) != ETHCNN_OK)) {
+                      ethcnn_pacer_create(ctx, budget_ladder, budget_rungs, budget_weight, budget_ppm, budget_mode, &pacer) != ETHCNN_OK)) {
         fprintf(stderr, "resi_to_cu_depth_ldp: search budget: %s\n", ethcnn_last_error(ctx));
         goto out;
     }
@@ -667,6 +766,7 @@ out:
     unlink(".pred_end.sig.ethcnn");
     if (sig_pending) unlink("pred_start.sig"); /* an error exit in between: the request counts as taken, as with the reference's daemon */
     free(state);
+    free(budget_ladder);
     ethcnn_destroy(ctx); /* frees the page-locked buffers with the context */
     return rc;
 }
