@@ -4,7 +4,6 @@ drivers and the threshold tool with what the 8-bit 4:2:0 form of the same pictur
 the fixture written by the reference's own scripts (extract16_cases.py: how a deep file narrows back to it)."""
 import importlib.util
 import os
-import re
 import sys
 
 import numpy as np
@@ -12,6 +11,7 @@ import pytest
 
 import extract16_cases as e16
 import extract_cases as ec
+import grid_caps
 from conftest import ROOT
 
 pytestmark = pytest.mark.gpu
@@ -23,15 +23,6 @@ ALIGNMENTS = ((0, 0), (16, 32), (4, 4), (2, 6))  # base offset and pitch padding
 @pytest.fixture(scope="module")
 def golden():
     return ec.load_golden()
-
-
-def _cus(ctx):
-    """compute units of the device in hand (the cut kernels launch at most 8 blocks per CU, two records per block and trip)"""
-    m = re.search(r"(\d+) CUs", ctx.device_name)  # "... (gfx950:sramecc+:xnack-, 256 CUs)"
-    if m:
-        return int(m.group(1))
-    import torch
-    return torch.cuda.get_device_properties(0).multi_processor_count
 
 
 def _deep_planes(rng, F, h, w, depth):
@@ -63,8 +54,9 @@ def test_cut16_device_against_numpy(pkg, ctx, w, h, frames, depth):
     E = pkg.ethcnn
     per = (h // 64) * (w // 64)
     if frames is None:
-        frames = 2 * 8 * _cus(ctx) // per + 1
-        assert frames * per > 2 * 8 * _cus(ctx)  # MI355X: 9 frames, 4320 records > 4096
+        cap = grid_caps.cut_ai(grid_caps.cus(ctx))  # (the cut kernels launch at most 8 blocks per CU, two records per block and trip)
+        frames = cap // per + 1
+        assert frames * per > cap  # MI355X: 9 frames, 4320 records > 4096
     else:
         assert frames * per == {(128, 64): 2, (200, 136): 18, (192, 64): 9}[(w, h)]
     nrec = frames * per

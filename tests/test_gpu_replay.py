@@ -12,15 +12,15 @@ import pytest
 
 import extract_cases
 import replay_ref
+import replay_world
+from replay_world import QPS, REC, SEQS
+from replay_world import context as _context
 
 pytestmark = pytest.mark.gpu
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 CAL_TOOL = os.path.join(ROOT, "tools", "calibrate_thresholds.py")
 SIM_TOOL = os.path.join(ROOT, "tools", "simulate_thresholds.py")
-REC = 16516
-QPS = [22, 27, 32, 37]
-SEQS = (("a", 200, 136, 5), ("b", 128, 64, 4))  # name, width, height, frames of the files (frame 0 is the intra picture: not cut)
 ERR_ARG, ERR_FORMAT, ERR_NOWEIGHTS, ERR_NOMEM = -1, -3, -5, -6
 
 
@@ -28,46 +28,12 @@ def _bits(a):
     return np.ascontiguousarray(a).view(np.uint32)
 
 
-def _context(pkg):
-    c = pkg.EthCnn(device=0)
-    c.load_synthetic(31, 8.0)
-    c.load_lstm_synthetic(32, 3.0)
-    c.set_thresholds(0.0, 0.0)  # open gates
-    return c
-
-
-class World(object):
-    pass
-
-
 @pytest.fixture(scope="module")
 def W(pkg, tmp_path_factory):
-    """the context, the files, the set cut from them, its records and the planes the records came from"""
-    w = World()
-    w.dir = tmp_path_factory.mktemp("replay")
-    w.ctx = _context(pkg)
-    rng = np.random.default_rng(77)
-    w.set = pkg.SampleSet(w.ctx, kind="inter", qps=QPS)
-    w.luma, w.labels = [], []  # [sequence][slot] -> [frames, h, w] / [frames, h / 16, w / 16], frame 0 included
-    for name, wd, ht, frames in SEQS:
-        yuvs, labs = [], []
-        for q in QPS:
-            yuvs.append(str(w.dir / ("resi_%s_qp%d.yuv" % (name, q))))
-            labs.append(str(w.dir / ("%s_qp%d_CUDepth.dat" % (name, q))))
-            with open(yuvs[-1], "wb") as f:
-                f.write(extract_cases.synth_yuv(rng, wd, ht, frames))
-            with open(labs[-1], "wb") as f:
-                f.write(rng.integers(0, 4, int(np.prod(extract_cases.label_shape(wd, ht, frames))), dtype=np.uint8).tobytes())
-        w.set.add_sequence(wd, ht, yuvs, labs)
-        w.luma.append([extract_cases.read_luma(p, wd, ht) for p in yuvs])
-        w.labels.append([np.fromfile(p, dtype=np.uint8).reshape(extract_cases.label_shape(wd, ht, frames)) for p in labs])
-    w.set.build()
-    w.records = w.set.read()
-    assert w.records.shape == (4 * 6 + 3 * 2, REC)
-    w.plan = replay_ref.plan(w.records)
+    """the context, the files, the set cut from them, its records and the planes the records came from (tests/replay_world.py)"""
+    w = replay_world.build(pkg, tmp_path_factory.mktemp("replay"))
     yield w
-    w.set.close()
-    w.ctx.close()
+    w.close()
 
 
 def crop(W, iseq, slot, first=1):
