@@ -37,17 +37,12 @@ void launch_tile(const uint8_t* d_luma, const FrameGeom& g, long ctu0, int n, co
                  hipStream_t s, int max_blocks = 0, const unsigned* wait_rows = nullptr, unsigned wait_seq = 0, unsigned* gave_up = nullptr);
 // k1: xs/xm/xl -> feat (fc1_plan 2: -> featb, every feature as two fp16 pieces in the 16-bit MFMA's operand order)
 void launch_trunk(const Workspace& ws, const DeviceWeights& w, int n, bool resi, hipStream_t s, int fc1_plan = 0);
-// k1 with the CTU-load stage folded in (A/B form, experiments build: ethcnn_trunk.hip); needs small_pass_ok-style 16-byte alignment
-void launch_trunk_direct(const uint8_t* d_luma, const FrameGeom& g, long ctu0, const Workspace& ws, const DeviceWeights& w, int n, hipStream_t s);
 // k1, plan 3 (ethcnn_trunk_fast.hip): the same trunk with its convolutions on the 16-bit matrix pipe (fp16 x 2 splits) -> featb in plan 2's form
-void launch_trunk_f16(const Workspace& ws, const DeviceWeights& w, int n, hipStream_t s, bool ml_only = false);
-// plan 3 with the CTU-load stage folded in: S tasks straight from the luma frames + the XM / XL records of the M / L tasks
-// (which follow as launch_trunk_f16(..., ml_only = true)); clears the pass's n_flags sync words like launch_tile
-void launch_trunk_f16_fold(const uint8_t* d_luma, const FrameGeom& g, long ctu0, int n, const Workspace& ws, const DeviceWeights& w, int n_flags,
-                           hipStream_t s);
-// the whole plan-3 trunk behind one pass over the frames (S, M and L tasks of a group in one block; no pixel records in HBM at all)
+void launch_trunk_f16(const Workspace& ws, const DeviceWeights& w, int n, hipStream_t s);
+// the whole plan-3 trunk behind one pass over the frames (S, M and L tasks of a group in one block; no tile launch, no pixel records in
+// HBM at all); clears the pass's n_flags sync words like launch_tile
 void launch_trunk_f16_foldall(const uint8_t* d_luma, const FrameGeom& g, long ctu0, int n, const Workspace& ws, const DeviceWeights& w, int n_flags,
-                              hipStream_t s, int blocks_per_cu = 2);
+                              hipStream_t s);
 // k2: feat -> h1 (bias + leaky-ReLU fused); out may be ws.h1 or a caller buffer (resi vectors)
 void launch_fc1(const Workspace& ws, const DeviceWeights& w, int n, float* out, hipStream_t s);
 // k2, plans 2 / 3 (ethcnn_fc1_fast.hip): featb -> h1 on the 16-bit matrix pipe: three fp16 products per fp32 product (two-way splits of

@@ -83,6 +83,21 @@ int run_small_pass(ethcnn_ctx* c, const uint8_t* d_luma, const FrameGeom& g, lon
 
 // one pass over CTUs [ctu0, ctu0+n) of the sequence; ctu0 is sub-batch aligned.  input_ready: event after which d_luma
 // may be read (nullptr: the caller ordered it before the call).  Asynchronous; the pass ends on the main stream.
+//
+// One launch sequence per plan:
+//
+//   pass                                 | tile stage            | trunk                    | FC1                    | heads
+//   -------------------------------------+-----------------------+--------------------------+------------------------+-----------------
+//   small_launch on, small_pass_ok,      | --                    | run_small_pass: ONE launch, exact under any plan
+//     not pipelined                      |                       |
+//   plan 0                               | launch_tile (*)       | launch_trunk(.., 0)      | launch_fc1             | launch_heads
+//   plan 2                               | launch_tile (*)       | launch_trunk(.., 2)      | launch_fc1_fast(.., 2) | launch_heads
+//   plan 3, tile_wait_rows == nullptr    | none                  | launch_trunk_f16_foldall | launch_fc1_fast(.., 2) | launch_heads_f16
+//   plan 3, streamed picture             | launch_tile, main     | launch_trunk_f16         | launch_fc1_fast(.., 2) |   if dw.heads16_w,
+//                                        |   stream              |                          |                        |   else launch_heads
+//   (*) on the side stream when overlap && n >= kPipelineMinCtus ("pipelined"); fold-all leaves nothing to put there
+//
+// launch_gate follows the heads in every multi-launch row.
 int run_pass(ethcnn_ctx* c, const uint8_t* d_luma, const FrameGeom& g, long ctu0, int n, int qp, float* d_probs_pass,
              hipEvent_t input_ready) {
     const int cpf = chunks_per_frame(g.nctu);
@@ -98,121 +113,95 @@ int run_pass(ethcnn_ctx* c, const uint8_t* d_luma, const FrameGeom& g, long ctu0
     rc = ensure_workspace(c, n, (int)nchunks);
     if (rc) return rc;
     const float qn = (float)qp * (1.0f / 51.0f);  // net_CNN.py:106
+    const int fast = c->fc1_plan;  // plans 2 / 3: trunk -> 16-bit feature pieces -> FC1 on the 16-bit matrix pipe
+    // Plan 3 with the picture in memory: the whole trunk behind one pass over the frames (k1_trunk_f16_foldall) -- no tile launch,
+    // nothing for a side stream to run.  A streamed picture keeps the tile stage: it is the one that waits for the rows.
+    const bool foldall = fast == 3 && c->tile_wait_rows == nullptr;
     // Small passes (a frame or a few: the in-process encoder hook, the LDP-sized calls) stay on one stream: there is no FC1 of
     // a previous pass long enough to hide anything under, and the cross-stream event costs ~10 us of a 75 us call
-    // Plan 3 (round 5): the CTU-load stage is folded into the trunk's S branch (k1_trunk_f16_fold) -- no tile launch, nothing for a
-    // side stream to run.  (Experiments build: ETHCNN_PLAN3_FOLD=0 keeps round 4's tile stage beside FC1 for the A/B.)
-    // 2 (default): the whole trunk behind one pass over the frames (k1_trunk_f16_foldall); 1: S branch folded, M / L as a second launch
-    static const int fold3_knob = [] { const char* e = dev_env("ETHCNN_PLAN3_FOLD"); return e ? std::atoi(e) : 2; }();
-    const bool fold3 = c->fc1_plan == 3 && fold3_knob != 0 && c->tile_wait_rows == nullptr;
-    const bool side_tile = c->overlap != 0 && n >= kPipelineMinCtus && !fold3;
+    const bool side_tile = c->overlap != 0 && n >= kPipelineMinCtus && !foldall;
     const int p = side_tile ? (int)(c->pass_idx++ & 1) : 0;
     const Workspace w = ws_view(c, p);
     if (side_tile && !c->s_tile && (rc = ensure_side_streams(c)) != 0) return rc;
     hipStream_t s_tile = side_tile ? c->s_tile : c->stream;
     if (input_ready) HIPCHK(c, hipStreamWaitEvent(s_tile, input_ready, 0));
-    if (!side_tile && c->small_launch && small_pass_ok(d_luma, g, n)) {
+    Workspace wv = w;  // what the heads may capture for the debug entry points
+    if (!c->debug_capture) wv.h2 = wv.logits = wv.raw = nullptr;
+    const bool small = !side_tile && c->small_launch && small_pass_ok(d_luma, g, n);
+    if (small) {
         // one picture (the in-process encoder hook, the reference's own 768x512 case): CTU load + trunk -> FC1 -> heads -> gates
         // as ONE launch instead of five dependent ones
-        Workspace wv = w;
-        if (!c->debug_capture) wv.h2 = wv.logits = wv.raw = nullptr;
         rc = run_small_pass(c, d_luma, g, ctu0, n, false, wv, w.h1, qn, d_probs_pass, (int)nchunks, c->luma_over_pcie,
                             c->luma_over_pcie ? c->tile_wait_rows : nullptr);
         if (rc) return rc;
-        c->main_dirty = true;  // a later pipelined tile stage must wait for this pass
-        c->times.ctus += n;
-        c->last_n = n;
-        c->last_parity = p;
-        c->last_fast = 0;  // (the single-launch pass always computes FC1 exactly)
-        return 0;
-    }
-    if (side_tile) {
-        // tile(i) overwrites the tile outputs and gate flags of buffer set p: last read by trunk(i-2) / gate(i-2).  Both are
-        // ordered before trunk(i-1) on the main stream, so the wait for e_trunk[p ^ 1] below covers them; a main-stream
-        // pass in between (small pass, LDP call) records e_main behind its last kernel instead.  Every event RECORD on the
-        // main stream is a barrier packet between two kernels (~7 us of idle GPU, rocprofv3 kernel trace): there is exactly
-        // one per pipelined pass (e_trunk).  A never-recorded event is a no-op.
-        HIPCHK(c, hipStreamWaitEvent(s_tile, c->e_trunk[p], 0));
-        if (c->main_dirty) {  // main-stream users of the workspace since the last pipelined pass (small passes, LDP steps)
-            HIPCHK(c, hipEventRecord(c->e_main, c->stream));
-            c->main_dirty = false;
+    } else {
+        if (side_tile) {
+            // tile(i) overwrites the tile outputs and gate flags of buffer set p: last read by trunk(i-2) / gate(i-2).  Both are
+            // ordered before trunk(i-1) on the main stream, so the wait for e_trunk[p ^ 1] below covers them; a main-stream
+            // pass in between (small pass, LDP call) records e_main behind its last kernel instead.  Every event RECORD on the
+            // main stream is a barrier packet between two kernels (~7 us of idle GPU, rocprofv3 kernel trace): there is exactly
+            // one per pipelined pass (e_trunk).  A never-recorded event is a no-op.
+            HIPCHK(c, hipStreamWaitEvent(s_tile, c->e_trunk[p], 0));
+            if (c->main_dirty) {  // main-stream users of the workspace since the last pipelined pass (small passes, LDP steps)
+                HIPCHK(c, hipEventRecord(c->e_main, c->stream));
+                c->main_dirty = false;
+            }
+            HIPCHK(c, hipStreamWaitEvent(s_tile, c->e_main, 0));
+            // ... and it should run beside FC1(i-1), not beside trunk(i-1): with the trunk it competes for VALU issue and HBM
+            // (measured: trunk 556 -> 819 us, tile 180 -> 511 us, step period 2.60 -> 2.73 ms; profiles/r02_overlap_trace.txt)
+            const bool behind_fc1 = c->tile_after_fc1 != 0 && fast != 0;
+            HIPCHK(c, hipStreamWaitEvent(s_tile, behind_fc1 ? c->e_fc1[p ^ 1] : c->e_trunk[p ^ 1], 0));
         }
-        HIPCHK(c, hipStreamWaitEvent(s_tile, c->e_main, 0));
-        // ... and it should run beside FC1(i-1), not beside trunk(i-1): with the trunk it competes for VALU issue and HBM
-        // (measured: trunk 556 -> 819 us, tile 180 -> 511 us, step period 2.60 -> 2.73 ms; profiles/r02_overlap_trace.txt)
-        const bool behind_fc1 = c->tile_after_fc1 != 0 && c->fc1_plan != 0;
-        HIPCHK(c, hipStreamWaitEvent(s_tile, behind_fc1 ? c->e_fc1[p ^ 1] : c->e_trunk[p ^ 1], 0));
-    }
-    // A/B knob (experiments build): CTU-load stage folded into the trunk for big exact passes (profiles/r04_tile_fold.txt)
-    static const bool fold_knob = [] { const char* e = dev_env("ETHCNN_TILE_FOLD"); return e && std::atoi(e) != 0; }();
-    const bool fold = fold_knob && c->fc1_plan == 0 && (g.width % 16 == 0) && (g.pitch % 16 == 0) && (g.frame_stride % 16 == 0) &&
-                      (reinterpret_cast<uintptr_t>(d_luma) % 16 == 0);
-    (void)hipGetLastError();  // launch errors below are reported per stage; drop anything stale first
+        (void)hipGetLastError();  // launch errors below are reported per stage; drop anything stale first
 #define LAUNCH_OK(name)                                                                                            \
     do {                                                                                                           \
         const hipError_t le_ = hipGetLastError();                                                                  \
         if (le_ != hipSuccess) return set_err(c, ETHCNN_ERR_DEVICE, "launch of the %s stage failed: %s", name, hipGetErrorString(le_)); \
     } while (0)
-    // experiments build only (scripts/plan3_power.py): ONE stage of the pass, launched alone over and over (outputs meaningless) -- socket
-    // power and shader clock of each stage at steady state.  1 trunk (+ CTU-load stage), 2 FC1, 3 heads + gate
-    // (the first three passes of the process run whole: the stage then loops on the REAL features / h1 they left -- FC1's power depends on its data)
-    static const int only_knob = [] { const char* e = dev_env("ETHCNN_STAGE_ONLY"); return e ? std::atoi(e) : 0; }();
-    static int passes_seen = 0;
-    const int only = (only_knob != 0 && ++passes_seen > 3) ? only_knob : 0;
-    // the tile stage also zeroes the pass's gate predicates
-    if (fold3 || (only != 0 && only != 1)) {
-        // (no tile launch; the folded trunk below clears the sync area itself)
-    } else if (fold) {  // no tile launch: only the pass's sync area is cleared (what the tile stage does on the way)
-        HIPCHK(c, hipMemsetAsync(w.flags, 0, (size_t)sync_words((int)nchunks) * sizeof(int), s_tile));
-    } else {
-        StageTimer t(c, ETHCNN_STAGE_TILE, n, s_tile);
-        launch_tile(d_luma, g, ctu0, n, w, sync_words((int)nchunks), s_tile, side_tile ? c->tile_blocks : 0,
-                    side_tile ? nullptr : c->tile_wait_rows, c->rows_seq, c->h_done + 1);  // (streamed input: a single main-stream pass)
-    }
-    LAUNCH_OK("tile");
-    if (side_tile) {
-        HIPCHK(c, hipEventRecord(c->e_tile[p], s_tile));
-        HIPCHK(c, hipStreamWaitEvent(c->stream, c->e_tile[p], 0));
-    }
-    const int fast = c->fc1_plan;  // plans 2 / 3: trunk -> 16-bit feature pieces -> FC1 on the 16-bit matrix pipe
-    if (only == 0 || only == 1)
-    { StageTimer t(c, ETHCNN_STAGE_TRUNK);
-      if (fold) launch_trunk_direct(d_luma, g, ctu0, w, c->dw, n, c->stream);
-      else if (fold3 && fold3_knob == 1) {
-          launch_trunk_f16_fold(d_luma, g, ctu0, n, w, c->dw, sync_words((int)nchunks), c->stream);
-          launch_trunk_f16(w, c->dw, n, c->stream, /*ml_only=*/true);
-      } else if (fold3) {
-          static const int bpc = [] { const char* e = dev_env("ETHCNN_PLAN3_FOLD_BLOCKS"); return e ? std::atoi(e) : 2; }();
-          launch_trunk_f16_foldall(d_luma, g, ctu0, n, w, c->dw, sync_words((int)nchunks), c->stream, bpc);
-      } else if (fast == 3) launch_trunk_f16(w, c->dw, n, c->stream);
-      else launch_trunk(w, c->dw, n, false, c->stream, fast); }
-    LAUNCH_OK("trunk");
-    if (side_tile) HIPCHK(c, hipEventRecord(c->e_trunk[p], c->stream));
-    Workspace wv = w;
-    if (!c->debug_capture) wv.h2 = wv.logits = wv.raw = nullptr;
-    if (fast) {
-        if (only == 0 || only == 2) { StageTimer t(c, ETHCNN_STAGE_FC1, n); launch_fc1_fast(w, c->dw, n, w.h1, fast == 3 ? 2 : fast, c->stream, c->cus); }
-        LAUNCH_OK("FC1 (16-bit pipe)");
-        if (side_tile && c->tile_after_fc1) HIPCHK(c, hipEventRecord(c->e_fc1[p], c->stream));
-        // plan 3: the heads on the 16-bit pipe as well (experiments build: ETHCNN_PLAN3_HEADS=0 keeps the exact heads for the A/B)
-        static const bool heads16_knob = [] { const char* e = dev_env("ETHCNN_PLAN3_HEADS"); return !e || std::atoi(e) != 0; }();
-        if (only == 0 || only == 3) { StageTimer t(c, ETHCNN_STAGE_HEADS);
-          if (fast == 3 && heads16_knob && c->dw.heads16_w)
-              launch_heads_f16(wv, c->dw, n, qn, g.nctu, ctu0, c->thr1, c->thr2, d_probs_pass, c->stream);
-          else launch_heads(wv, c->dw, n, qn, g.nctu, ctu0, c->thr1, c->thr2, d_probs_pass, c->stream); }
-    } else {
-        if (only == 0 || only == 2) { StageTimer t(c, ETHCNN_STAGE_FC1, n); launch_fc1(w, c->dw, n, w.h1, c->stream); }
-        LAUNCH_OK("FC1");
-        if (only == 0 || only == 3) { StageTimer t(c, ETHCNN_STAGE_HEADS); launch_heads(wv, c->dw, n, qn, g.nctu, ctu0, c->thr1, c->thr2, d_probs_pass, c->stream); }
-    }
-    if (only == 0 || only == 3) { StageTimer t(c, ETHCNN_STAGE_GATE); launch_gate(w, n, g.nctu, ctu0, c->thr2, d_probs_pass, c->stream); }
-    LAUNCH_OK("heads / gate");
+        // ---- tile stage: the trunk's pixel records; it also zeroes the pass's gate predicates (the fold-all trunk does both itself)
+        if (!foldall) {
+            StageTimer t(c, ETHCNN_STAGE_TILE, n, s_tile);
+            launch_tile(d_luma, g, ctu0, n, w, sync_words((int)nchunks), s_tile, side_tile ? c->tile_blocks : 0,
+                        side_tile ? nullptr : c->tile_wait_rows, c->rows_seq, c->h_done + 1);  // (streamed input: a single main-stream pass)
+        }
+        LAUNCH_OK("tile");
+        if (side_tile) {
+            HIPCHK(c, hipEventRecord(c->e_tile[p], s_tile));
+            HIPCHK(c, hipStreamWaitEvent(c->stream, c->e_tile[p], 0));
+        }
+        // ---- trunk
+        {
+            StageTimer t(c, ETHCNN_STAGE_TRUNK);
+            if (foldall) launch_trunk_f16_foldall(d_luma, g, ctu0, n, w, c->dw, sync_words((int)nchunks), c->stream);
+            else if (fast == 3) launch_trunk_f16(w, c->dw, n, c->stream);
+            else launch_trunk(w, c->dw, n, false, c->stream, fast);
+        }
+        LAUNCH_OK("trunk");
+        if (side_tile) HIPCHK(c, hipEventRecord(c->e_trunk[p], c->stream));
+        // ---- FC1
+        if (fast) {
+            { StageTimer t(c, ETHCNN_STAGE_FC1, n); launch_fc1_fast(w, c->dw, n, w.h1, 2, c->stream, c->cus); }  // (plan 3: plan 2's FC1)
+            LAUNCH_OK("FC1 (16-bit pipe)");
+            if (side_tile && c->tile_after_fc1) HIPCHK(c, hipEventRecord(c->e_fc1[p], c->stream));
+        } else {
+            { StageTimer t(c, ETHCNN_STAGE_FC1, n); launch_fc1(w, c->dw, n, w.h1, c->stream); }
+            LAUNCH_OK("FC1");
+        }
+        // ---- heads (plan 3: on the 16-bit pipe as well), then the gate
+        {
+            StageTimer t(c, ETHCNN_STAGE_HEADS);
+            if (fast == 3 && c->dw.heads16_w) launch_heads_f16(wv, c->dw, n, qn, g.nctu, ctu0, c->thr1, c->thr2, d_probs_pass, c->stream);
+            else launch_heads(wv, c->dw, n, qn, g.nctu, ctu0, c->thr1, c->thr2, d_probs_pass, c->stream);
+        }
+        { StageTimer t(c, ETHCNN_STAGE_GATE); launch_gate(w, n, g.nctu, ctu0, c->thr2, d_probs_pass, c->stream); }
+        LAUNCH_OK("heads / gate");
 #undef LAUNCH_OK
+    }
     if (!side_tile) c->main_dirty = true;  // a later pipelined tile stage must wait for this pass
     c->times.ctus += n;
     c->last_n = n;
     c->last_parity = p;
-    c->last_fast = fast;
+    c->last_fast = small ? 0 : fast;  // (the single-launch pass always computes FC1 exactly)
     return 0;
 }
 

@@ -67,7 +67,7 @@ __device__ __forceinline__ void tile_wait_rows(const TileWait& tw, long ctu0, in
 }
 
 // ---- the pieces of a group's work, shared by tile_group (below) and by the plan-3 trunk that consumes the S records straight out
-// of LDS (ethcnn_trunk_fast.hip, k1_trunk_f16_fold).  `tile`: 16 * kSlabCtuPitch dwords of LDS = one 16-row slab of the group.
+// of LDS (ethcnn_trunk_fast.hip, k1_trunk_f16_foldall). `tile`: 16 * kSlabCtuPitch dwords of LDS = one 16-row slab of the group.
 #define ETHCNN_PXS(tile, c, Y, Xd) (tile)[(c) * kSlabCtuPitch + (Y) * kRowPitch + (Xd)]
 
 // loader role of a 256-thread block: lane -> (CTU c, 16-B segment), wave -> 4 of the slab's 16 rows: one wave instruction covers a
@@ -90,8 +90,8 @@ struct SlabLoader {
             if (lx < width) lbase = luma + f * frame_stride + lx;
         }
     }
-    // the same with the pass's first CTU given as (frame f0, CTU r0 inside it): 32-bit arithmetic only (the folded trunk re-derives
-    // the geometry for every slab item it walks)
+    // the same with the pass's first CTU given as (frame f0, CTU r0 inside it): 32-bit arithmetic only (the fold-all trunk re-derives
+    // the geometry for every group it walks)
     __device__ __forceinline__ void init32(int t, const uint8_t* __restrict__ luma, int width, long frame_stride, int cw, int nctu, int f0, int r0,
                                            int n_total, int n0) {
         lc = (t >> 2) & 15; lseg = t & 3; lrow0 = (t >> 6) * 4;

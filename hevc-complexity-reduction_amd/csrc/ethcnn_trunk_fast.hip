@@ -336,80 +336,18 @@ __global__ __launch_bounds__(256) void k1_trunk_f16(const uint4* __restrict__ XS
                        sc.C1[2], sc.U2[2], sc.U3[2], F, N, lds);
 }
 
-// ---- plan 3 with the CTU-load stage FOLDED IN (round 5).  Under plan 3 a step moves ~4.6 GB through HBM (profiles/r04_pmc_c3.txt),
-// 1.36 GB of it the pixel records' round trip (k0_tile_slab writes 6,656 B per CTU, the trunk reads them back), and the tile stage
-// beside FC1 costs the 16-bit FC1 0.15 ms.  Here the S branch (16 of a group's 21 tasks, 4,096 of the 6,656 record bytes) takes its
-// records straight out of the LDS slab the loader role fills -- the same coalesced 1 KiB-per-wave-instruction frame reads and the
-// same exact integer record words as k0_tile_slab (ethcnn_tile_group.h) -- and the block writes only the slab's XM / XL records
-// (2,560 B per CTU) for the M / L tasks, which run as a second, small launch (k1_trunk_f16 with bS = 0).  No XS buffer, no tile
-// launch, no side stream.
-//   work item = one 16-row slab of one group (4 per group): load -> LDS -> barrier -> wave w reads the record of unit (uy = slab,
-//   ux = w), the block emits the slab's 2.5 KiB of XM / XL records -> barrier -> S task; the next item's pixels are requested at the
-//   task's mid point into the dead record registers.
-template <bool FAST>
-__global__ __launch_bounds__(256) void k1_trunk_f16_fold(const uint8_t* __restrict__ luma, int width, int height, long pitch, long frame_stride,
-                                                         int cw, int nctu, int f0, int r0, int N, uint4* __restrict__ XM, uint4* __restrict__ XL,
-                                                         int* __restrict__ gate_flags, int n_flags, const uint16_t* __restrict__ wimg,
-                                                         const float* __restrict__ cfrag, Trunk16Scalars sc, char* __restrict__ F) {
-    __shared__ __attribute__((aligned(16))) char lds[20 * 1024];
-    __shared__ uint32_t tile[16 * kSlabCtuPitch];
-    if (blockIdx.x == 0)  // (what the tile stage does on the way: the pass's sync area, read by the heads / gate launches behind us)
-        for (int i = threadIdx.x; i < n_flags; i += 256) gate_flags[i] = 0;
-    const int t = threadIdx.x;
-    const int w = __builtin_amdgcn_readfirstlane(t >> 6);
-    Trunk16<0> tk;
-    tk.setup(wimg, cfrag, sc.C1[0], sc.U2[0], sc.U3[0], F, N, lds);
-    const int nitems = ((N + 15) >> 4) * 4;
-    int it = blockIdx.x;
-    if (it >= nitems) return;
-    const __amdgpu_buffer_rsrc_t rM = __builtin_amdgcn_make_buffer_rsrc(XM, 0, -1, 0x00020000);
-    const __amdgpu_buffer_rsrc_t rL = __builtin_amdgcn_make_buffer_rsrc(XL, 0, -1, 0x00020000);
-    SlabLoader L;
-    uint4 pre[4];
-    L.init32(t, luma, width, frame_stride, cw, nctu, f0, r0, N, (it >> 2) * 16);
-    L.template load<FAST>(it & 3, pre, width, height, pitch);
-#pragma unroll 1
-    for (; it < nitems; it += gridDim.x) {
-        const int grp = it >> 2, s = it & 3;
-        L.to_lds(tile, pre);
-        __syncthreads();
-        uint4 raw[4];
-#pragma unroll
-        for (int j = 0; j < 4; ++j) raw[j] = slab_xs_record(tile, tk.col, tk.g, j, w);
-        // the slab's XM / XL records (same index arithmetic as tile_group): 512 + 128 uint4, 2.5 per thread
-#pragma unroll
-        for (int rep = 0; rep < 2; ++rep) {
-            const int e = t + 256 * rep;
-            const int lane = e & 63, jj = (e >> 6) & 3, ux = e >> 8;
-            const int j = 4 * (s & 1) + jj, unit = 2 * (s >> 1) + ux;
-            const uint4 v = slab_xm_record(tile, lane & 15, lane >> 4, j, ux);
-            // (whole offset in the VGPR, soffset = 0: see the store-hazard remark in ethcnn_trunk_task.h)
-            __builtin_amdgcn_raw_buffer_store_b128((u32x4_t){v.x, v.y, v.z, v.w}, rM, (grp * 2048 + 512 * unit + 64 * j + lane) * 16, 0, 0);
-        }
-        if (t < 128) {
-            const int lane = t & 63, m = t >> 6;
-            const int j = 4 * (s >> 1) + 2 * m + (s & 1);
-            const uint4 v = slab_xl_record(tile, lane & 15, lane >> 4, j);
-            __builtin_amdgcn_raw_buffer_store_b128((u32x4_t){v.x, v.y, v.z, v.w}, rL, (grp * 512 + 64 * j + lane) * 16, 0, 0);
-        }
-        __syncthreads();  // the slab is consumed: the next item may overwrite it
-        tk.task(raw, grp * 16 + 4 * s + w, [&]() {
-            const int nx = it + (int)gridDim.x;
-            if (nx < nitems) {
-                L.init32(t, luma, width, frame_stride, cw, nctu, f0, r0, N, (nx >> 2) * 16);
-                L.template load<FAST>(nx & 3, pre, width, height, pitch);
-            }
-        });
-    }
-}
-
-// ---- the whole trunk of plan 3 behind ONE pass over the luma frames (round 5).  k1_trunk_f16_fold above still writes and re-reads
-// 2,560 B of XM / XL records per CTU and pays a second launch for the M / L tasks.  Here a block takes a whole GROUP: it walks the four
-// slabs, every wave runs the slab's S task of its unit column, and the pooled records of the M / L units are built from the same LDS slab
-// straight into the registers of the wave that will run that task -- waves 0 / 1 the M units (uy, ux = w) after slabs 1 and 3, wave 2
-// the L unit after slab 3.  HBM traffic of the trunk: 4,096 B in, 10,752 B of feature pieces out per CTU (1.51 GB per C3 step against
-// 2.87 GB for tile stage + trunk in round 4).  21 tasks in 24 wave slots per group; 77.5 KB of LDS (three branches' fragments + the
-// slab), 255 VGPRs: two blocks per CU.
+// ---- the whole trunk of plan 3 behind ONE pass over the luma frames (round 5): no tile launch, no pixel records in HBM, no side
+// stream.  Under plan 3 a step moved ~4.6 GB through HBM (profiles/r04_pmc_c3.txt), 1.36 GB of it the pixel records' round trip
+// (k0_tile_slab writes 6,656 B per CTU, the trunk reads them back), and the tile stage beside FC1 cost the 16-bit FC1 0.15 ms.  Here a
+// block takes a whole GROUP: the loader role fills an LDS slab with the same coalesced 1 KiB-per-wave-instruction frame reads and the
+// same exact integer record words as k0_tile_slab (ethcnn_tile_group.h), the block walks the four slabs, every wave runs the slab's
+// S task of its unit column (the next slab's pixels are requested at the task's mid point into the dead record registers), and the
+// pooled records of the M / L units are built from the same LDS slab straight into the registers of the wave that will run that task
+// -- waves 0 / 1 the M units (uy, ux = w) after slabs 1 and 3, wave 2 the L unit after slab 3.  HBM traffic of the trunk: 4,096 B in,
+// 10,752 B of feature pieces out per CTU (1.51 GB per C3 step against 2.87 GB for tile stage + trunk in round 4).  21 tasks in 24
+// wave slots per group; 77.5 KB of LDS (three branches' fragments + the slab), 255 VGPRs: two blocks per CU.
+// (Measured and not kept, profiles/r05_plan3_fold.txt: the S branch alone behind the slab loader, the slab's XM / XL records written to
+// HBM for a second, small launch of the M / L tasks.)
 // (Measured and not kept, profiles/r05_plan3_fold.txt: one M task per wave -- 20 tasks in 20 slots -- with the L unit's records written
 // to XL and its tasks as a small second launch: the second launch costs more than the idle slots, trunk 0.436 against 0.410 ms.)
 template <bool FAST>
@@ -505,23 +443,21 @@ __global__ __launch_bounds__(256, 2) void k1_trunk_f16_foldall(const uint8_t* __
     }
 }
 
-void launch_trunk_f16(const Workspace& ws, const DeviceWeights& w, int n, hipStream_t s, bool ml_only) {
+void launch_trunk_f16(const Workspace& ws, const DeviceWeights& w, int n, hipStream_t s) {
     // tasks per group: 16 S, 4 M, 1 L; blocks per CU by registers (see the resource remark of the build); same branch shares as k1_trunk
     const int groups = (n + 15) / 16, tS = groups * 16, tM = groups * 4, tL = groups;
     auto blocks = [](int tasks, int budget) { int b = (tasks + 3) / 4; return b < budget ? b : budget; };
     constexpr int per_cu = 4;
-    // ml_only (the S branch ran in k1_trunk_f16_fold): the whole grid to the M / L tasks, 4 : 1, three resident blocks per CU (~8 tasks
-    // per wave: a fourth, non-resident block per CU would be a second round for a quarter of the work)
-    const int bS = ml_only ? 0 : blocks(tS, 193 * per_cu), bM = blocks(tM, ml_only ? 205 * 3 : 50 * per_cu), bL = blocks(tL, ml_only ? 51 * 3 : 13 * per_cu);
+    const int bS = blocks(tS, 193 * per_cu), bM = blocks(tM, 50 * per_cu), bL = blocks(tL, 13 * per_cu);
     hipLaunchKernelGGL(k1_trunk_f16, dim3(bS + bM + bL), dim3(256), 0, s, ws.xs, ws.xm, ws.xl, n, bS, bM, w.trunk16_w, w.trunk16_c, w.trunk16_s,
                        reinterpret_cast<char*>(ws.featb));
 }
 
 void launch_trunk_f16_foldall(const uint8_t* d_luma, const FrameGeom& g, long ctu0, int n, const Workspace& ws, const DeviceWeights& w, int n_flags,
-                              hipStream_t s, int blocks_per_cu) {
+                              hipStream_t s) {
     const int groups = (n + 15) / 16;
-    const int cap = 256 * (blocks_per_cu > 0 ? blocks_per_cu : 2);
-    const int blocks = groups < cap ? groups : cap;
+    const int blocks = groups < 512 ? groups : 512;  // 2 per CU (LDS, registers), persistent over the groups
+    // 16-byte aligned rows: one 128-bit load per thread and row; anything else goes byte by byte (SlabLoader::load)
     const bool fast = (g.width % 16 == 0) && (g.pitch % 16 == 0) && (g.frame_stride % 16 == 0) && (reinterpret_cast<uintptr_t>(d_luma) % 16 == 0);
     const int f0 = (int)(ctu0 / g.nctu), r0 = (int)(ctu0 % g.nctu);
     if (fast)
@@ -530,20 +466,6 @@ void launch_trunk_f16_foldall(const uint8_t* d_luma, const FrameGeom& g, long ct
     else
         hipLaunchKernelGGL(k1_trunk_f16_foldall<false>, dim3(blocks), dim3(256), 0, s, d_luma, g.width, g.height, g.pitch, g.frame_stride, g.cw, g.nctu,
                            f0, r0, n, ws.flags, n_flags, w.trunk16_w, w.trunk16_c, w.trunk16_s, reinterpret_cast<char*>(ws.featb));
-}
-
-void launch_trunk_f16_fold(const uint8_t* d_luma, const FrameGeom& g, long ctu0, int n, const Workspace& ws, const DeviceWeights& w, int n_flags,
-                           hipStream_t s) {
-    const int items = ((n + 15) / 16) * 4;
-    const int blocks = items < 768 ? items : 768;  // 3 per CU (registers), persistent over the slab items
-    const bool fast = (g.width % 16 == 0) && (g.pitch % 16 == 0) && (g.frame_stride % 16 == 0) && (reinterpret_cast<uintptr_t>(d_luma) % 16 == 0);
-    const int f0 = (int)(ctu0 / g.nctu), r0 = (int)(ctu0 % g.nctu);  // first frame of the pass / first CTU inside it: 32-bit geometry in the kernel
-    if (fast)
-        hipLaunchKernelGGL(k1_trunk_f16_fold<true>, dim3(blocks), dim3(256), 0, s, d_luma, g.width, g.height, g.pitch, g.frame_stride, g.cw, g.nctu,
-                           f0, r0, n, ws.xm, ws.xl, ws.flags, n_flags, w.trunk16_w, w.trunk16_c, w.trunk16_s, reinterpret_cast<char*>(ws.featb));
-    else
-        hipLaunchKernelGGL(k1_trunk_f16_fold<false>, dim3(blocks), dim3(256), 0, s, d_luma, g.width, g.height, g.pitch, g.frame_stride, g.cw, g.nctu,
-                           f0, r0, n, ws.xm, ws.xl, ws.flags, n_flags, w.trunk16_w, w.trunk16_c, w.trunk16_s, reinterpret_cast<char*>(ws.featb));
 }
 
 }  // namespace ethcnn

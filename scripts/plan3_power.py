@@ -2,8 +2,9 @@
 
     python scripts/plan3_power.py [seconds per setting]     -> bench_out/plan3_overlap.txt (profiles/r06_plan3_overlap.txt)
 
-1. Socket power and shader clock (hwmon, 20 ms samples, steady state) of a C3 step looped under plan 3 and plan 0, and of EACH STAGE of
-   plan 3 looped alone (experiments build, ETHCNN_STAGE_ONLY): which stages sit at the 1400 W cap, what a step costs in joules.
+1. Socket power and shader clock (hwmon, 20 ms samples, steady state) of a C3 step looped under plan 3 and plan 0: how close a step
+   sits to the 1400 W cap, what it costs in joules.  (The per-stage figures of profiles/r06_plan3_overlap.txt came from a stage-alone
+   launch form that has been removed since; that file is their record.)
 2. The overlap itself, with the kernels as they are: TWO contexts on the one GPU, each looping plan-3 steps from its own thread on its own
    streams -- the trunk of one runs beside FC1 / heads of the other (CU by CU: neither kernel leaves room for the other inside a CU,
    255 + 2 x 231 VGPRs, 77 + 96 KB LDS; across CUs they share the chip, its clock and its power budget).  Aggregate CTU/s against one
@@ -88,11 +89,9 @@ def worker(args):
     print(json.dumps({"steps": sum(steps), "seconds": dt, "ms_per_step": dt / max(1, sum(steps)) * 1e3, "ctus_per_s": sum(steps) * NCTU / dt}))
 
 
-def measure(label, plan, contexts, env_extra=None):
+def measure(label, plan, contexts):
     mine, hw = hwmon_of_device0()
-    env = dict(os.environ)
-    env.update(env_extra or {})
-    p = subprocess.Popen([sys.executable, os.path.abspath(__file__), "--worker", str(plan), str(contexts), str(SECONDS)], stdout=subprocess.PIPE, stderr=subprocess.PIPE, text=True, env=env)
+    p = subprocess.Popen([sys.executable, os.path.abspath(__file__), "--worker", str(plan), str(contexts), str(SECONDS)], stdout=subprocess.PIPE, stderr=subprocess.PIPE, text=True)
     rows = []
     t0 = time.time()
     while p.poll() is None:
@@ -114,23 +113,17 @@ def measure(label, plan, contexts, env_extra=None):
 
 
 def main():
-    exp = os.path.join(ROOT, "hevc-complexity-reduction_amd", "lib_exp", "libethcnn.so")
     mine, hw = hwmon_of_device0()
     cap = rd((mine or hw[0]) + "/power1_cap")
     lines = ["# scripts/plan3_power.py: C3 steps (102,000 CTUs) looped for %.0f s per setting; socket power / shader clock = median of the hwmon samples (20 ms apart)" % SECONDS,
              "# of the loop's steady state; power cap %.0f W" % ((cap or 0) / 1e6), ""]
     res = {}
-    for label, plan, nctx, extra in (("plan 0 (exact), one context", 0, 1, None),
-                                     ("plan 3, one context", 3, 1, None),
-                                     ("plan 3, TWO contexts interleaved", 3, 2, None),
-                                     ("plan 3, FOUR contexts interleaved", 3, 4, None),
-                                     ("plan 0 (exact), TWO contexts interleaved", 0, 2, None),
-                                     ("plan 3, trunk stage alone, looped", 3, 1, {"ETHCNN_LIB": exp, "ETHCNN_STAGE_ONLY": "1"}),
-                                     ("plan 3, FC1 stage alone, looped", 3, 1, {"ETHCNN_LIB": exp, "ETHCNN_STAGE_ONLY": "2"}),
-                                     ("plan 3, heads + gate alone, looped", 3, 1, {"ETHCNN_LIB": exp, "ETHCNN_STAGE_ONLY": "3"}),
-                                     ("plan 0, trunk (+ CTU load) alone, looped", 0, 1, {"ETHCNN_LIB": exp, "ETHCNN_STAGE_ONLY": "1"}),
-                                     ("plan 0, FC1 stage alone, looped", 0, 1, {"ETHCNN_LIB": exp, "ETHCNN_STAGE_ONLY": "2"})):
-        r = measure(label, plan, nctx, extra)
+    for label, plan, nctx in (("plan 0 (exact), one context", 0, 1),
+                              ("plan 3, one context", 3, 1),
+                              ("plan 3, TWO contexts interleaved", 3, 2),
+                              ("plan 3, FOUR contexts interleaved", 3, 4),
+                              ("plan 0 (exact), TWO contexts interleaved", 0, 2)):
+        r = measure(label, plan, nctx)
         if isinstance(r, str):
             lines.append(r)
         else:

@@ -1,7 +1,8 @@
 // Development probe: do the heads stage of pass i and the trunk of pass i+1 gain from running at the same time
-// (two streams), or is it a wash?  Links against libethcnn.so's internal launchers (ethcnn::launch_*).
-//   hipcc --offload-arch=gfx950 -O2 -std=c++17 -I../../include -I../../hevc-complexity-reduction_amd/csrc overlap_probe.cpp \
-//         -L../../hevc-complexity-reduction_amd/lib -lethcnn -Wl,-rpath,'$ORIGIN/../../hevc-complexity-reduction_amd/lib' -o overlap_probe
+// (two streams), or is it a wash?  Calls the library's internal launchers (ethcnn::launch_*), which libethcnn.so does not export:
+// it is compiled together with the kernel files that define them.
+//   C=../../hevc-complexity-reduction_amd/csrc; hipcc --offload-arch=gfx950 -O3 -std=c++17 -ffp-contract=off -fno-fast-math \
+//         -mllvm -amdgpu-mfma-vgpr-form -w -I../../include -I$C overlap_probe.cpp $C/ethcnn_trunk.hip $C/ethcnn_heads.hip $C/ethcnn_kernels.hip -o overlap_probe
 #include <hip/hip_runtime.h>
 
 #include <algorithm>

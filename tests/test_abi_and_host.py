@@ -226,6 +226,25 @@ def test_development_knobs_are_compiled_out_of_the_shipped_library():
     blob = open(exp, "rb").read()
     for k in dev:
         assert k + b"\0" in blob, k
+    # the launch forms that were measured and rejected left run_pass together with their switches: in neither build
+    gone = [b"ETHCNN_" + k for k in (b"TILE_FOLD", b"PLAN3_FOLD", b"PLAN3_FOLD_BLOCKS", b"PLAN3_HEADS", b"STAGE_ONLY")]
+    for k in gone:
+        assert k + b"\0" not in shipped and k + b"\0" not in blob, k
+
+
+def test_only_the_c_abi_is_exported(pkg):
+    """The library is linked into the encoder's process (in-process hook): its dynamic symbol table holds the ethcnn_* functions of
+    include/ethcnn.h and nothing else (csrc/ethcnn.map), in the shipped and in the experiments build, and every bound name resolves."""
+    import ctypes
+    for d in ("lib", "lib_exp"):
+        path = os.path.join(ROOT, "hevc-complexity-reduction_amd", d, "libethcnn.so")
+        out = subprocess.check_output(["nm", "-D", "--defined-only", path]).decode()
+        names = [l.split()[-1] for l in out.splitlines() if l.strip()]
+        assert len(names) >= len(pkg.ethcnn.SIGNATURES)
+        assert [n for n in names if not n.startswith("ethcnn_")] == [], d
+        lib = ctypes.CDLL(path)
+        for n in pkg.ethcnn.SIGNATURES:
+            assert getattr(lib, n) is not None, "%s/libethcnn.so lacks %s" % (d, n)
 
 
 def test_hook_row_conversion_sse2_equals_scalar(tmp_path):
