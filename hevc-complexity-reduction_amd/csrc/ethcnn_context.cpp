@@ -251,7 +251,7 @@ extern "C" void ethcnn_destroy(ethcnn_ctx* c) {
     if (c->dw_trunk16) (void)hipFree(c->dw_trunk16);
     if (c->dw_heads16) (void)hipFree(c->dw_heads16);
     {
-        void* lp[] = {c->d_lstm, c->d_vec, c->d_state[0], c->d_state[1], c->d_lprobs, c->d_lgate, c->d_ssync, c->seq_vec, c->seq_probs, c->narrow_buf};
+        void* lp[] = {c->d_lstm, c->d_vec, c->d_state[0], c->d_state[1], c->d_lprobs, c->d_lgate, c->d_ssync, c->seq_vec, c->seq_probs, c->narrow_buf, c->d_compare};
         for (void* p : lp)
             if (p) (void)hipFree(p);
     }

@@ -227,6 +227,9 @@ struct ethcnn_ctx {
     double guard_measured[4] = {-1, -1, -1, -1}; // max |dp| vs the exact plan on the calibration picture; < 0: not measured (the bound sufficed)
     FastGuard guard_info[4] = {};
     int last_fast = 0;       // the FC1 plan of the last pass (debug_fetch reads the features of plans 1 / 2 from ws.featb)
+    unsigned long passes = 0, fast_passes = 0;  // passes enqueued by run_pass / of those, the ones with last_fast != 0 (ethcnn_audit.cpp reads the difference)
+    bool ws_foreign = false;                    // the workspace holds an audit's last pass, not the caller's: ethcnn_debug_fetch refuses until the next pass
+    unsigned long long* d_compare = nullptr;    // the call state of ethcnn_compare_* (ethcnn_audit.h), allocated on first use
     // completion word (page-locked host memory): the last block of a latency-path launch stores the launch's sequence number
     // there and the host spins on it instead of calling hipStreamSynchronize (~5 us sooner, scripts/ubench/launch_rtt.hip)
     unsigned* h_done = nullptr;  // (word 1: "a tile block of streamed picture <seq> gave up waiting for its rows", ethcnn_tile.hip)

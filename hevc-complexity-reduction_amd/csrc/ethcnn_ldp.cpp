@@ -25,6 +25,7 @@ extern "C" int ethcnn_resi_vectors_device(ethcnn_ctx* c, const uint8_t* d_luma, 
             if (rc) return rc;
             c->times.ctus += n;
             c->last_n = n;
+    c->ws_foreign = false;
             c->last_parity = 0;
             continue;
         }
@@ -34,6 +35,7 @@ extern "C" int ethcnn_resi_vectors_device(ethcnn_ctx* c, const uint8_t* d_luma, 
         HIPCHK(c, hipGetLastError());
         c->times.ctus += n;
         c->last_n = n;
+    c->ws_foreign = false;
         c->last_parity = 0;
     }
     return serial_end(c);
@@ -125,6 +127,7 @@ extern "C" int ethcnn_lstm_step_device(ethcnn_ctx* c, const float* d_vec, const 
     c->lgate_clean = true;
     c->done_armed = seq;
     c->last_n = n;
+    c->ws_foreign = false;
     return serial_end(c);
 }
 
@@ -403,6 +406,7 @@ int seq_front(ethcnn_ctx* c, const uint8_t* d_luma, const FrameGeom& g, int nf, 
         HIPCHK(c, hipGetLastError());
         c->times.ctus += p.n;
         c->last_n = p.n;
+        c->ws_foreign = false;
         c->last_parity = 0;
     }
     return ETHCNN_OK;

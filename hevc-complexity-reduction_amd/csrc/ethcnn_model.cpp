@@ -291,6 +291,8 @@ extern "C" int ethcnn_debug_fetch(ethcnn_ctx* c, int which, float* out, size_t n
     if (!c || !out) return ETHCNN_ERR_ARG;
     if (which >= ETHCNN_DBG_FC2 && which <= ETHCNN_DBG_RAW_PROBS && !c->debug_capture)
         return set_err(c, ETHCNN_ERR_ARG, "debug_fetch(%d): call ethcnn_set_debug_capture(ctx, 1) before the pass", which);
+    if (c->ws_foreign)
+        return set_err(c, ETHCNN_ERR_ARG, "debug_fetch(%d): the last passes on this context were a plan audit's; the intermediates of the pass before it are gone", which);
     const float* src = nullptr;
     size_t per = 0;
     switch (which) {

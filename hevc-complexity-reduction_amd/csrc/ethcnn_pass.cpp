@@ -202,6 +202,9 @@ int run_pass(ethcnn_ctx* c, const uint8_t* d_luma, const FrameGeom& g, long ctu0
     c->last_n = n;
     c->last_parity = p;
     c->last_fast = small ? 0 : fast;  // (the single-launch pass always computes FC1 exactly)
+    ++c->passes;
+    c->ws_foreign = false;
+    if (c->last_fast) ++c->fast_passes;
     return 0;
 }
 

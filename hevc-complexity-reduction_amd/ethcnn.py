@@ -298,6 +298,13 @@ SIGNATURES = {
     "ethcnn_ladder_build": (_i, [_vp, _vp, _i, ctypes.c_int64, ctypes.c_uint32, _vp, _vp]),
     "ethcnn_ladder_thin": (_i, [_vp, ctypes.c_int64, ctypes.c_int64, _vp, _vp]),
     "ethcnn_ladder_write": (_i, [ctypes.c_char_p, _vp, ctypes.c_int64, _i]),
+    "ethcnn_compare_probs_device": (_i, [_vp, _vp, _vp, ctypes.c_int64, ctypes.c_float, _vp, _vp, _vp]),
+    "ethcnn_compare_frames_device": (_i, [_vp, _vp, _vp, _i, _i, ctypes.c_int64, ctypes.c_float, _vp, _vp, _vp]),
+    "ethcnn_compare_probs": (_i, [_vp, _vp, _vp, ctypes.c_int64, ctypes.c_float, _vp, _vp, _vp]),
+    "ethcnn_compare_frames": (_i, [_vp, _vp, _vp, _i, _i, ctypes.c_int64, ctypes.c_float, _vp, _vp, _vp]),
+    "ethcnn_audit_plan_bytes": (ctypes.c_int64, [_i, _i, _i]),
+    "ethcnn_audit_plan_device": (_i, [_vp, _vp, _i, _i, _pd, _pd, _i, _i, _i, ctypes.c_float, _vp, _vp]),
+    "ethcnn_audit_plan_yuv_file": (_i, [_vp, _cp, _i, _i, _i, _i, ctypes.c_int64, ctypes.c_int64, ctypes.c_int64, ctypes.c_float, _vp, _vp]),
     "ethcnn_replay_plan": (_i, [_vp, _sz, _vp, _i, ctypes.POINTER(_i), _vp, ctypes.c_char_p, _sz]),
     "ethcnn_replay_uncut_device": (_i, [_vp, _vp, ctypes.c_int64, _vp, ctypes.c_int64, _i, _i, _i, _vp, _vp]),
     "ethcnn_replay_create": (_i, [_vp, ctypes.c_uint64, ctypes.POINTER(_vp)]),
@@ -452,6 +459,29 @@ def narrow_rows_host(src16, bit_depth):
     if rc:
         raise EthCnnError(rc, "narrow_rows_host: bit depth %d (8..16)" % bit_depth)
     return out
+
+
+# ethcnn_compare_stats (200 bytes) and ethcnn_audit_result (216 bytes); the candidate is an ethcnn_sim_thr
+COMPARE_THR = np.dtype([("up_k", "<i4", (3,)), ("down_k", "<i4", (3,))])
+COMPARE_STATS = np.dtype([("ctus", "<u8"), ("rejected_ctus", "<u8"), ("over_tol", "<u8", (3,)), ("bits_diff", "<u8", (3,)), ("class_diff", "<u8", (3,)),
+                          ("search_diff_ctus", "<u8"), ("checked_a", "<u8", (4,)), ("checked_b", "<u8", (4,)), ("worst_ctu", "<i8", (3,)),
+                          ("max_abs", "<f4", (3,)), ("with_thr", "<u4")])
+AUDIT_RESULT = np.dtype([("stats", COMPARE_STATS), ("plan", "<i4"), ("passes", "<i4"), ("fast_passes", "<i4"), ("reserved", "<i4")])
+COMPARE_FLAG_REJECTED, COMPARE_FLAG_OVER_TOL, COMPARE_FLAG_CLASS, COMPARE_FLAG_SEARCH = 1, 2, 4, 8
+
+
+def read_thr_info_k(path, order="ai"):
+    """the six values of a Thr_info.txt on the k / 1024 grid (the nearest k each) -> (up_k [3], down_k [3]); order "ai": up1 down1 up2
+    down2 up3 down3, "ldp": down1 up1 ...; ValueError for fewer than six numbers or a value outside the simulator's ranges"""
+    tok = open(path).read().split()
+    if len(tok) < 6:
+        raise ValueError("%s: a Thr_info file holds six values" % path)
+    k = [int(np.floor(float(t) * 1024 + 0.5)) for t in tok[:6]]
+    a, b = k[0::2], k[1::2]
+    up, down = (a, b) if order == "ai" else (b, a)
+    if min(up) < 0 or max(up) > 1024 or min(down) < -1 or max(down) > 1024:
+        raise ValueError("%s: thresholds outside [0, 1] (down: [-1/1024, 1])" % path)
+    return up, down
 
 
 def ctus_per_frame(width, height):
@@ -895,6 +925,127 @@ class EthCnn(object):
             self._chk(rc)
         return {"accepted": rc == 0, "apriori_bound": b.value, "measured": None if m.value < 0 else m.value,
                 "message": "" if rc == 0 else self.lib.ethcnn_last_error(self.h).decode()}
+
+    # -- comparing two predictions, auditing a plan (include/ethcnn.h "comparing two predictions")
+    @staticmethod
+    def _compare_thr(thr):
+        """None, or one candidate as a SIM_THR record / (up_k, down_k) -> (keep-alive array or None, pointer or None)"""
+        if thr is None:
+            return None, None
+        t = np.zeros(1, COMPARE_THR)
+        if isinstance(thr, np.ndarray) and thr.dtype == COMPARE_THR:
+            t[0] = thr.reshape(-1)[0]
+        else:
+            t["up_k"][0], t["down_k"][0] = thr[0], thr[1]
+        return t, t.ctypes.data
+
+    @staticmethod
+    def _stats_dict(rec):
+        out = {}
+        for name in rec.dtype.names:
+            v = rec[name]
+            if isinstance(v, np.void):
+                out.update(EthCnn._stats_dict(v))
+            elif name != "reserved":
+                out[name] = v.tolist() if isinstance(v, np.ndarray) else v.item()
+        return out
+
+    @staticmethod
+    def _pair(a, b):
+        a, b = np.asarray(a), np.asarray(b)
+        if a.dtype != np.float32 or b.dtype != np.float32 or not a.flags["C_CONTIGUOUS"] or not b.flags["C_CONTIGUOUS"]:
+            a, b = np.ascontiguousarray(a, np.float32), np.ascontiguousarray(b, np.float32)
+        if a.size != b.size or a.size % NOUT:
+            raise ValueError("two arrays of the same number of CTUs x 21 are required")
+        return a, b
+
+    def _compare_host(self, a, b, width, height, nframes, tol, thr, want_flags):
+        a, b = self._pair(a, b)
+        n = a.size // NOUT
+        keep, tp = self._compare_thr(thr)
+        st = np.zeros(1, COMPARE_STATS)
+        flags = None
+        if want_flags is not False and want_flags is not None:
+            flags = want_flags if isinstance(want_flags, np.ndarray) else np.zeros(n, np.uint8)
+            assert flags.dtype == np.uint8 and flags.size == n and flags.flags["C_CONTIGUOUS"]
+        fp = flags.ctypes.data if flags is not None and n else None
+        if width is None:
+            rc = self.lib.ethcnn_compare_probs(self.h, a.ctypes.data, b.ctypes.data, n, float(tol), tp, st.ctypes.data, fp)
+        else:
+            per = ctus_per_frame(width, height)
+            nframes = n // per if nframes is None else int(nframes)
+            if nframes * per != n:
+                raise ValueError("%d CTUs are not %d frames of %d x %d" % (n, nframes, width, height))
+            rc = self.lib.ethcnn_compare_frames(self.h, a.ctypes.data, b.ctypes.data, int(width), int(height), nframes, float(tol), tp, st.ctypes.data, fp)
+        self._chk(rc)
+        out = self._stats_dict(st[0])
+        if flags is not None:
+            out["flags"] = flags
+        return out
+
+    def compare_probs(self, a, b, tol, thr=None, want_flags=False):
+        """two host arrays float32 [n, 21] (per-CTU layout) -> dict of the fields of ethcnn_compare_stats (+ "flags" uint8 [n] with
+        want_flags: True, or a uint8 array to fill, which may lie in a host_buffer())"""
+        return self._compare_host(a, b, None, None, None, tol, thr, want_flags)
+
+    def compare_frames(self, a, b, width, height, tol, thr=None, want_flags=False, nframes=None):
+        """the frame layout: whole frames of width x height (multiples of 8)"""
+        return self._compare_host(a, b, width, height, nframes, tol, thr, want_flags)
+
+    def compare_probs_device(self, d_a, d_b, n, tol, thr=None, d_flags=None):
+        """pointers in HBM (ints or DeviceBuffer), 4-byte aligned; synchronous"""
+        keep, tp = self._compare_thr(thr)
+        st = np.zeros(1, COMPARE_STATS)
+        ptr = lambda x: None if x is None else x.ptr if isinstance(x, DeviceBuffer) else int(x)
+        self._chk(self.lib.ethcnn_compare_probs_device(self.h, ptr(d_a), ptr(d_b), int(n), float(tol), tp, st.ctypes.data, ptr(d_flags)))
+        return self._stats_dict(st[0])
+
+    def compare_frames_device(self, d_a, d_b, width, height, nframes, tol, thr=None, d_flags=None):
+        keep, tp = self._compare_thr(thr)
+        st = np.zeros(1, COMPARE_STATS)
+        ptr = lambda x: None if x is None else x.ptr if isinstance(x, DeviceBuffer) else int(x)
+        self._chk(self.lib.ethcnn_compare_frames_device(self.h, ptr(d_a), ptr(d_b), int(width), int(height), int(nframes), float(tol), tp,
+                                                        st.ctypes.data, ptr(d_flags)))
+        return self._stats_dict(st[0])
+
+    def audit_plan_bytes(self, width, height, nframes):
+        return int(self.lib.ethcnn_audit_plan_bytes(int(width), int(height), int(nframes)))
+
+    def audit_plan(self, lumas, width, height, nframes, qp, plan, tol=1e-4, thr=None, pitch=None, frame_stride=None):
+        """plan 2 / 3 against the exact plan over the caller's frames, open gates (ethcnn_audit_plan_device) -> dict of the fields of
+        ethcnn_audit_result.  lumas: a device pointer (int or DeviceBuffer), or a host uint8 array that is uploaded for the call."""
+        pitch = width if pitch is None else pitch
+        frame_stride = pitch * height if frame_stride is None else frame_stride
+        keep, tp = self._compare_thr(thr)
+        res = np.zeros(1, AUDIT_RESULT)
+        own = None
+        if isinstance(lumas, DeviceBuffer):
+            src = lumas.ptr
+        elif isinstance(lumas, (int, np.integer)):
+            src = int(lumas)
+        else:
+            lumas = np.ascontiguousarray(lumas, dtype=np.uint8)
+            need = (nframes - 1) * frame_stride + (height - 1) * pitch + width if nframes else 0
+            if lumas.size < need:
+                raise ValueError("luma buffer too small: %d < %d" % (lumas.size, need))
+            own = self.alloc(max(1, lumas.nbytes))
+            own.upload(lumas)
+            src = own.ptr
+        try:
+            self._chk(self.lib.ethcnn_audit_plan_device(self.h, src, int(width), int(height), pitch, frame_stride, int(nframes), int(qp), int(plan),
+                                                        float(tol), tp, res.ctypes.data))
+        finally:
+            if own is not None:
+                own.free()
+        return self._stats_dict(res[0])
+
+    def audit_plan_yuv_file(self, yuv_path, width, height, qp, plan, first=0, step=1, count=1, tol=1e-4, thr=None):
+        """frames first + i * step, i < count, of an 8-bit 4:2:0 file (ethcnn_audit_plan_yuv_file)"""
+        keep, tp = self._compare_thr(thr)
+        res = np.zeros(1, AUDIT_RESULT)
+        self._chk(self.lib.ethcnn_audit_plan_yuv_file(self.h, os.fsencode(yuv_path), int(width), int(height), int(qp), int(plan), int(first), int(step),
+                                                      int(count), float(tol), tp, res.ctypes.data))
+        return self._stats_dict(res[0])
 
     def set_small_pass_launch(self, on=True):
         """one picture (<= 2304 CTUs, 16-byte aligned rows) as ONE launch (default on); off = five launches.  Same results."""

@@ -19,10 +19,17 @@ Differences from the reference, all outside the numbers it produces:
     writes a BAKED cu_depth.dat (values 0, 0.5, 1).  HM reads Thr_info.txt afterwards, so the launcher refuses (exit status 1, no
     cu_depth.dat) unless that file is the companion line "0.75 0.25 0.75 0.25 0.75 0.25".  ETHCNN_SEARCH_BUDGET_MODE=frame|carry
     (default frame) and ETHCNN_SEARCH_BUDGET_WEIGHTS="64 16 4 1" are optional.  One GPU only: ETHCNN_DEVICES with a budget is refused.
+  * ETHCNN_FC1_PLAN_AUDIT=<N> (read only when ETHCNN_FC1_PLAN is set and the guard accepted the plan) audits the plan on min(N, frames)
+    evenly spaced frames of THIS file before it is trusted (include/ethcnn.h "comparing two predictions"): plan against exact plan at
+    the run's QP, open gates, Thr_info.txt as the candidate, with the single-launch pass off (the audited frames take the 16-bit path that
+    the run over the whole file takes).  One line with the numbers goes to stderr; anything over 1e-4, or an audit that fails, and the
+    run continues with the exact plan, as after a guard refusal.  A malformed value, or a source that is not 8-bit 4:2:0, is refused at
+    start-up (exit status 1, nothing written).
 """
 from __future__ import print_function
 
 import os
+import re
 import sys
 import time
 
@@ -137,6 +144,60 @@ def restore_model(ctx, qp_seq, model_dir='.'):
     return 'synthetic(seed=%s)' % seed
 
 
+AUDIT_TOL = 1e-4   # the plans' contract: within 1e-4 of the exact plan
+
+
+def plan_audit_from_env(fmt=(8, 420)):
+    """frames to audit: 0 unless ETHCNN_FC1_PLAN and ETHCNN_FC1_PLAN_AUDIT are both set; ValueError names a malformed value"""
+    text = os.environ.get('ETHCNN_FC1_PLAN_AUDIT')
+    if not os.environ.get('ETHCNN_FC1_PLAN') or text is None or text == '':
+        return 0
+    if not re.match(r'^[0-9]{1,6}$', text) or text.endswith('\n'):   # no sign, no blank: the native launcher's rule
+        raise ValueError("ETHCNN_FC1_PLAN_AUDIT='%s' (a number of frames of one to six digits, 0 = no audit)" % text)
+    if int(text) and tuple(fmt) != (8, 420):
+        raise ValueError('ETHCNN_FC1_PLAN_AUDIT reads 8-bit 4:2:0 files only (the audit of other sources is not built)')
+    if int(text) and ',' in os.environ.get('ETHCNN_DEVICES', ''):
+        raise ValueError('ETHCNN_FC1_PLAN_AUDIT runs on one GPU: unset ETHCNN_DEVICES (ETHCNN_DEVICE picks the GPU)')
+    return int(text)
+
+
+def audit_fast_plan(ctx, yuv_file, width, height, qp_seq, n_audit):
+    """the accepted plan against the exact plan on min(n_audit, frames) evenly spaced frames of the file itself; one line on stderr;
+    anything over AUDIT_TOL, or an audit that fails: the run continues with the exact plan, as after a refusal"""
+    plan = ctx.fc1_plan()
+    frames = get_file_size(yuv_file) // (width * height * 3 // 2)
+    count = min(int(n_audit), frames)
+    if not plan or count <= 0:
+        return
+    try:
+        thr = _e.read_thr_info_k(THR_FILE, 'ai')
+    except ValueError:
+        thr = None   # (values off the simulator's ranges: the differences are still measured, the search is not compared)
+    step = frames // count
+    # with the single-launch pass off: a few frames would run as that pass, which computes exactly under every plan, while the run over the
+    # whole file takes the 16-bit path; the audit must take the path it audits
+    ctx.set_small_pass_launch(False)
+    try:
+        r = ctx.audit_plan_yuv_file(yuv_file, width, height, qp_seq, plan, 0, step, count, AUDIT_TOL, thr)
+    except _e.EthCnnError as err:   # an audit that cannot run (memory, a read error) is no reason to fail the encode
+        sys.stderr.write('video_to_cu_depth: plan %d audit failed: %s\nvideo_to_cu_depth: continuing with the exact plan (0)\n' % (plan, err))
+        ctx.set_fc1_plan(0)
+        return
+    finally:
+        ctx.set_small_pass_launch(True)
+    over = sum(r['over_tol'])
+    if r['fast_passes'] == 0:
+        verdict = 'these frames run as single-launch passes, which compute exactly under every plan: nothing to audit, plan kept'
+    else:
+        verdict = 'continuing with the exact plan (0)' if over else 'plan kept'
+    sys.stderr.write('video_to_cu_depth: plan %d audit over %d frames (step %d): max |dp| %s, values over %g: %d, classes that differ: %s, '
+                     'CTUs whose search differs: %s, fast passes %d/%d: %s\n'
+                     % (plan, count, step, ' '.join('%.3g' % v for v in r['max_abs']), AUDIT_TOL, over,
+                        sum(r['class_diff']) if thr else 'n/a', r['search_diff_ctus'] if thr else 'n/a', r['fast_passes'], r['passes'], verdict))
+    if over:
+        ctx.set_fc1_plan(0)
+
+
 def guard_fast_plan(ctx):
     """ETHCNN_FC1_PLAN=2|3 is an opt-in; the encoder asserts a zero exit status (TAppEncCfg.cpp:2321).  The library REFUSES a plan
     whose load-time accuracy guard fails for the restored checkpoint (include/ethcnn.h, ethcnn_check_fc1_plan); the launcher then says
@@ -211,6 +272,7 @@ def main(argv=None):
         fmt = source_format_from_env()
         frame_bytes = _e.source_frame_bytes(width, height, *fmt)[1]         # :136 width * height * 3 // 2 unless the environment says otherwise
         budget = search_budget_from_env()
+        n_audit = plan_audit_from_env(fmt)
         ladder = None
         if budget is not None:
             ladder = search_ladder_from_env()
@@ -234,6 +296,8 @@ def main(argv=None):
         ctx.set_source_format(*fmt)
         restore_model(ctx, qp_seq)
         guard_fast_plan(ctx)
+        if n_audit:
+            audit_fast_plan(ctx, yuv_file, width, height, qp_seq, n_audit)
         stamps.append(('thresholds + weights + plan guard', time.perf_counter()))
         t1 = time.time()                       # the reference times get_prob only (:142-145)
         if budget is not None:

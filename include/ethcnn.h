@@ -427,6 +427,8 @@ int ethcnn_get_fc1_plan(const ethcnn_ctx* ctx);
  * gradient, noise, edge and texture tiles) through the exact plan and through the plan at QP 22 and QP 37, gates open; max |dp| <= 2.5e-5 accepts, anything
  * else REFUSES: the pass returns ETHCNN_ERR_PLAN_REFUSED with the numbers in ethcnn_last_error, nothing is computed, the context stays
  * usable (ethcnn_set_fc1_plan(ctx, 0 or 2)).  Never a silent loss of accuracy, never a silent fallback.  ~3 ms, once per weight load.
+ * The measured stage is empirical -- one synthetic picture -- so a deployment checks a plan on its OWN content with ethcnn_audit_plan_device
+ * / ethcnn_audit_plan_yuv_file ("comparing two predictions" below).
  *   ethcnn_check_fc1_plan   ETHCNN_OK / ETHCNN_ERR_PLAN_REFUSED for the loaded weights; *apriori_bound, *measured (may be NULL; measured
  *                           < 0: the bound sufficed and nothing was run).
  * The launchers (video_to_cu_depth.py, tools/video_to_cu_depth.c) call it when ETHCNN_FC1_PLAN is set and continue with plan 0 after
@@ -1265,6 +1267,91 @@ int ethcnn_ladder_build(ethcnn_sim* sim, const uint64_t weight[4], int grid, int
                         int64_t* nrungs_out);
 int ethcnn_ladder_thin(const uint64_t* cost, int64_t n, int64_t K, int32_t* idx_out, int64_t* k_out);
 int ethcnn_ladder_write(const char* path, const ethcnn_sim_thr* thr, int64_t K, int order);
+
+/* ---- comparing two predictions: how far two sets of probabilities are apart, and whether the encoder's pruned search changes (no
+ *      reference counterpart).  The questions behind every "byte-identical" and "within tolerance" of this project: a 16-bit plan against
+ *      the exact plan, one daemon against another, a retrained model against the one before it, a sharded run against a single one.  One
+ *      kernel reads both sets once and answers in the terms of "partition-search simulation" above.
+ *   Inputs: a and b, float32 [n][21] in the layout the predictors write; tol >= 0 (a NaN or a negative tol: ETHCNN_ERR_ARG); optionally ONE
+ *      candidate thr in the simulator's ranges (else ETHCNN_ERR_ARG; NULL: none).  Layouts as for the calibrator and the simulator:
+ *      per-CTU (no geometry, every node is a decided node) and frame (nframes frames of width x height, both multiples of 8 up to 65536,
+ *      else ETHCNN_ERR_ARG; rule lines 1-4 of the simulation block apply, frame-edge nodes included).  Gates: none, the probabilities are
+ *      compared as given.  n, or nframes x CTUs per frame, of 2^31 or more: ETHCNN_ERR_ARG.
+ *   Per value (level 0: p[0]; level 1: p[1..4]; level 2: p[5..20]; all 21 values of a CTU, wherever the CTU lies in the picture):
+ *      d = |a - b|, ONE fp32 subtraction with IEEE results for subnormals.
+ *      over_tol[level]   values with d > tol
+ *      bits_diff[level]  values whose bit patterns differ (-0.0 against 0.0 counts here and nowhere else)
+ *      max_abs[level]    the maximum of d;  worst_ctu[level]  the LOWEST CTU index that attains it, -1 when nothing was compared
+ *   With thr, bin = ceil(p * 1024) in fp32 with the bit tests of the calibration block, on both sides:
+ *      class_diff[level]  values whose outcome (SPLIT ONLY / CURRENT ONLY / BOTH, rule line 4) differs between a and b, visited or not
+ *      search_diff_ctus   CTUs whose pruned search differs: the set of (visited node, outcome) pairs of a is not that of b -- another
+ *                         node is visited, or a visited decided node has another outcome.  THE number that decides whether HM's
+ *                         bitstream can change: 0 means the encoder checks the same CUs under a and under b.
+ *      checked_a[4], checked_b[4]  the simulator's checked[] of each side under thr, gates none
+ *      Without thr all these fields are 0 and with_thr is 0.
+ *   A CTU with a NaN, a negative or a > 1 value among its 42 numbers is left out of everything and counted in rejected_ctus.
+ *   ethcnn_compare_stats, 200 bytes, little-endian, no padding: ctus uint64 at 0 (CTUs given, the rejected ones included), rejected_ctus
+ *      uint64 at 8, over_tol uint64[3] at 16, bits_diff uint64[3] at 40, class_diff uint64[3] at 64, search_diff_ctus uint64 at 88,
+ *      checked_a uint64[4] at 96, checked_b uint64[4] at 128, worst_ctu int64[3] at 160, max_abs float32[3] at 184, with_thr uint32 at 196.
+ *   flags (may be NULL), uint8 [n], per CTU: bit 0 rejected (then no other bit), bit 1 a value over tol, bit 2 a class differs, bit 3 the
+ *      search differs.
+ *   Every field is independent of the launch grid and of how a set is split over calls: integers and fp32 compares only.  Sums add
+ *      across calls; a maximum combines by (value, lowest index, the second call's indices moved by the first call's ctus).
+ *   The _device entries take pointers in HBM, 4-byte aligned (else ETHCNN_ERR_ARG; no other alignment is needed).  The host entries
+ *      read or write a pointer in place when its whole range lies in an ethcnn_host_alloc buffer and stage anything else in pieces of
+ *      2^20 CTUs through one device buffer (ETHCNN_ERR_NOMEM with the byte count when it does not fit).  All four are synchronous on the
+ *      context's stream and return the stats to the host.  n == 0 / nframes == 0 is a no-op that gives zeros and worst_ctu = -1. */
+typedef struct ethcnn_compare_stats {
+    uint64_t ctus;
+    uint64_t rejected_ctus;
+    uint64_t over_tol[3];
+    uint64_t bits_diff[3];
+    uint64_t class_diff[3];
+    uint64_t search_diff_ctus;
+    uint64_t checked_a[4], checked_b[4];
+    int64_t worst_ctu[3];
+    float max_abs[3];
+    uint32_t with_thr;
+} ethcnn_compare_stats;
+int ethcnn_compare_probs_device(ethcnn_ctx* ctx, const float* d_a, const float* d_b, int64_t n, float tol, const ethcnn_sim_thr* thr /* may be NULL */,
+                                ethcnn_compare_stats* out, uint8_t* d_flags /* may be NULL */);
+int ethcnn_compare_frames_device(ethcnn_ctx* ctx, const float* d_a, const float* d_b, int width, int height, int64_t nframes, float tol,
+                                 const ethcnn_sim_thr* thr /* may be NULL */, ethcnn_compare_stats* out, uint8_t* d_flags /* may be NULL */);
+int ethcnn_compare_probs(ethcnn_ctx* ctx, const float* a, const float* b, int64_t n, float tol, const ethcnn_sim_thr* thr /* may be NULL */,
+                         ethcnn_compare_stats* out, uint8_t* flags /* may be NULL */);
+int ethcnn_compare_frames(ethcnn_ctx* ctx, const float* a, const float* b, int width, int height, int64_t nframes, float tol,
+                          const ethcnn_sim_thr* thr /* may be NULL */, ethcnn_compare_stats* out, uint8_t* flags /* may be NULL */);
+/* The audit of a 16-bit plan on the caller's own pictures: the frames go through ethcnn_predict_luma_device under plan 0 and then under
+ * `plan` (2 or 3, else ETHCNN_ERR_ARG), both with open gates (thresholds -1, -1: a gate's knife edge cannot pass for an arithmetic
+ * error), and the two results are compared in the frame layout (width, height multiples of 8).  Synchronous.
+ *   ethcnn_audit_result, 216 bytes, no padding: the stats at 0, plan int32 at 200, passes int32 at 204 (passes of the audited run),
+ *      fast_passes int32 at 208 (of those, the passes that took the 16-bit path), reserved int32 at 212 (0).  A geometry that runs as
+ *      single-launch passes computes exactly under every plan: the result then says fast_passes == 0, and its zero differences say
+ *      nothing about the plan.
+ *   The context's plan, thresholds, profiling counters and the intermediates' bookkeeping that ethcnn_debug_fetch reads are what they
+ *      were afterwards, on every error path too.  The workspace itself holds the audit's last pass, so ethcnn_debug_fetch is refused
+ *      (ETHCNN_ERR_ARG) from an audit that ran a pass until the caller's next pass: stale intermediates never look valid.  A plan that the load-time guard
+ *      refuses: ETHCNN_ERR_PLAN_REFUSED, nothing changed, `out` untouched.  An open streamed call: ETHCNN_ERR_ARG.
+ *   Memory: 2 x nframes x nctu x 84 bytes of scratch, the first set rounded up to 16 bytes so that the second one starts aligned and the
+ *      comparison keeps its 16-byte loads (at most 12 bytes more; ethcnn_audit_plan_bytes reports the sum; negative: bad arguments), checked against the free device
+ *      memory before it is allocated (ETHCNN_ERR_NOMEM, the byte count in the message).
+ *   The file entry reads the luma planes of frames first + i step, i < count (first >= 0, step >= 1, count >= 0), of an 8-bit 4:2:0 file
+ *      into one contiguous device buffer (count x width x height bytes more) and calls the device entry.  A frame index past the end of the
+ *      file is ETHCNN_ERR_ARG before anything runs; a context whose source format is not the default is refused with ETHCNN_ERR_ARG.
+ *   Not built: deep or non-4:2:0 sources in the file entry; the Low-Delay-P path (it always computes exactly); multi-GPU; any change to
+ *      the guard's own decision; a periodic check inside the passes. */
+typedef struct ethcnn_audit_result {
+    ethcnn_compare_stats stats;
+    int32_t plan;
+    int32_t passes;
+    int32_t fast_passes;
+    int32_t reserved;
+} ethcnn_audit_result;
+int64_t ethcnn_audit_plan_bytes(int width, int height, int nframes);
+int ethcnn_audit_plan_device(ethcnn_ctx* ctx, const uint8_t* d_luma, int width, int height, ptrdiff_t pitch, ptrdiff_t frame_stride, int nframes, int qp,
+                             int plan, float tol, const ethcnn_sim_thr* thr /* may be NULL */, ethcnn_audit_result* out);
+int ethcnn_audit_plan_yuv_file(ethcnn_ctx* ctx, const char* path, int width, int height, int qp, int plan, int64_t first, int64_t step, int64_t count,
+                               float tol, const ethcnn_sim_thr* thr /* may be NULL */, ethcnn_audit_result* out);
 
 /* ---- sample-set replay: an inter sample set (LDP_Valid.dat, LDP_Test.dat, plain or _shuffled: the 16516-byte records of "sample sets"
  *      above) put back together into the residual pictures and label planes it was cut from, and run through the deployed Low-Delay-P

@@ -20,12 +20,20 @@
  * plan -- the encoder asserts a zero exit status.  ETHCNN_INPUT_BIT_DEPTH=8..16 and
  * ETHCNN_INPUT_CHROMA_FORMAT=400|420|422|444 name the source format of the file (HM's InputBitDepth
  * and InputChromaFormat; the command line is fixed); unset: 8-bit 4:2:0; a bad value is exit 1 with a
- * message.  ETHCNN_TIMING=1 prints where the command's
+ * message.  ETHCNN_FC1_PLAN_AUDIT=<N> (read only when ETHCNN_FC1_PLAN is set and the guard accepted
+ * the plan) audits the plan on min(N, frames) evenly spaced frames of this file before it is trusted
+ * (ethcnn_audit_plan_yuv_file: plan against exact plan at the run's QP, Thr_info.txt as the candidate),
+ * with the single-launch pass off so that the audited frames take the 16-bit path of the whole run),
+ * prints one line with the numbers and continues with the exact plan when anything is over 1e-4 or
+ * the audit itself fails; a
+ * malformed value, a source that is not 8-bit 4:2:0 or more than one device is exit 1 before anything
+ * runs.  ETHCNN_TIMING=1 prints where the command's
  * wall time goes (stderr): the blocking system() of the caller sees all of it.
  */
 #include <stdio.h>
 #include <stdlib.h>
 #include <string.h>
+#include <sys/stat.h>
 #include <time.h>
 #include <unistd.h>
 
@@ -61,13 +69,77 @@ static int env_int(const char* name, int* value) {
     return 0;
 }
 
+/* Thr_info.txt in All-Intra token order (up1 down1 up2 down2 up3 down3) on the k / 1024 grid, the nearest k each; 0 when the file does
+ * not hold six values inside the simulator's ranges (the audit then compares no search) */
+static int read_thr_k(const char* path, ethcnn_sim_thr* thr) {
+    FILE* f = fopen(path, "r");
+    double v[6];
+    int i, n = 0;
+    if (!f) return 0;
+    while (n < 6 && fscanf(f, "%lf", &v[n]) == 1) ++n;
+    fclose(f);
+    if (n < 6) return 0;
+    for (i = 0; i < 6; ++i) {
+        const double x = v[i] * 1024.0;
+        int k;
+        if (!(x >= -1.5 && x <= 1024.5)) return 0;
+        k = (int)(x + 1.5) - 1; /* floor(x + 0.5) for x >= -1.5 */
+        if (i & 1) thr->down_k[i >> 1] = k;
+        else thr->up_k[i >> 1] = k;
+    }
+    for (i = 0; i < 3; ++i)
+        if (thr->up_k[i] < 0 || thr->up_k[i] > 1024 || thr->down_k[i] < -1 || thr->down_k[i] > 1024) return 0;
+    return 1;
+}
+
+/* the accepted plan against the exact plan on min(n_audit, frames) evenly spaced frames of the file itself; always 0: a failure of the
+ * audit itself is printed and takes the fallback of a refusal */
+static int audit_plan(ethcnn_ctx* ctx, const char* yuv, int width, int height, int qp, int n_audit) {
+    const int plan = ethcnn_get_fc1_plan(ctx);
+    const float tol = 1e-4f; /* the plans' contract */
+    struct stat st;
+    ethcnn_sim_thr thr;
+    ethcnn_audit_result r;
+    int64_t frames, count, step;
+    uint64_t over, classes;
+    int have_thr, rc;
+    if (stat(yuv, &st) != 0 || width <= 0 || height <= 0) return 0; /* (the prediction reports a file it cannot read) */
+    frames = (int64_t)st.st_size / ((int64_t)width * height * 3 / 2);
+    count = n_audit < frames ? n_audit : frames;
+    if (plan == 0 || count <= 0) return 0;
+    step = frames / count;
+    have_thr = read_thr_k("Thr_info.txt", &thr);
+    /* with the single-launch pass off: a few frames would run as that pass, which computes exactly under every plan, while the run over
+     * the whole file takes the 16-bit path; the audit must take the path it audits */
+    (void)ethcnn_set_small_pass_launch(ctx, 0);
+    rc = ethcnn_audit_plan_yuv_file(ctx, yuv, width, height, qp, plan, 0, step, count, tol, have_thr ? &thr : NULL, &r);
+    (void)ethcnn_set_small_pass_launch(ctx, 1);
+    if (rc != ETHCNN_OK) { /* an audit that cannot run (memory, a read error) is no reason to fail the encode: the exact plan is always right */
+        fprintf(stderr, "video_to_cu_depth: plan %d audit failed: %s\nvideo_to_cu_depth: continuing with the exact plan (0)\n", plan, ethcnn_last_error(ctx));
+        (void)ethcnn_set_fc1_plan(ctx, 0);
+        return 0;
+    }
+    over = r.stats.over_tol[0] + r.stats.over_tol[1] + r.stats.over_tol[2];
+    classes = r.stats.class_diff[0] + r.stats.class_diff[1] + r.stats.class_diff[2];
+    fprintf(stderr, "video_to_cu_depth: plan %d audit over %lld frames (step %lld): max |dp| %.3g %.3g %.3g, values over %g: %llu, ", plan, (long long)count,
+            (long long)step, (double)r.stats.max_abs[0], (double)r.stats.max_abs[1], (double)r.stats.max_abs[2], (double)tol, (unsigned long long)over);
+    if (have_thr) fprintf(stderr, "classes that differ: %llu, CTUs whose search differs: %llu, ", (unsigned long long)classes, (unsigned long long)r.stats.search_diff_ctus);
+    else fprintf(stderr, "classes that differ: n/a, CTUs whose search differs: n/a, ");
+    fprintf(stderr, "fast passes %d/%d: %s\n", (int)r.fast_passes, (int)r.passes,
+            r.fast_passes == 0 ? "these frames run as single-launch passes, which compute exactly under every plan: nothing to audit, plan kept"
+                               : over ? "continuing with the exact plan (0)" : "plan kept");
+    if (over && r.fast_passes) (void)ethcnn_set_fc1_plan(ctx, 0);
+    return 0;
+}
+
 int main(int argc, char** argv) {
     ethcnn_ctx* ctx = NULL;
     ethcnn_options opt;
     char model[64], data[96];
     int64_t nframes = 0;
     ethcnn_source_format fmt = {8, 420};
-    int width, height, qp, rc, ndev = 0, devices[64];
+    int width, height, qp, rc, ndev = 0, devices[64], n_audit = 0;
+    const char* plan_env = getenv("ETHCNN_FC1_PLAN");
     const char* seed = getenv("ETHCNN_SYNTHETIC_SEED");
     const char* dev = getenv("ETHCNN_DEVICE");
     const char* devs = getenv("ETHCNN_DEVICES");
@@ -100,6 +172,19 @@ int main(int argc, char** argv) {
         }
     }
     if (ndev == 0) devices[ndev++] = dev ? atoi(dev) : 0;
+    if (plan_env && *plan_env) { /* ETHCNN_FC1_PLAN_AUDIT is read only beside an opted-in plan */
+        /* one to six decimal digits and nothing else (no sign, no blank): the Python launcher's rule */
+        const char* text = getenv("ETHCNN_FC1_PLAN_AUDIT");
+        if (text && *text && strspn(text, "0123456789") == strlen(text) && strlen(text) <= 6) n_audit = atoi(text);
+        else if (text && *text) {
+            fprintf(stderr, "video_to_cu_depth: bad ETHCNN_FC1_PLAN_AUDIT (a number of frames of one to six digits, 0 = no audit)\n");
+            return 1;
+        }
+        if (n_audit > 0 && (fmt.bit_depth != 8 || fmt.chroma_format != 420 || ndev > 1)) {
+            fprintf(stderr, "video_to_cu_depth: ETHCNN_FC1_PLAN_AUDIT reads 8-bit 4:2:0 files on one GPU only (anything else is not built)\n");
+            return 1;
+        }
+    }
     memset(&opt, 0, sizeof opt);
     opt.device = devices[0];
     if (ethcnn_create(&ctx, &opt) != ETHCNN_OK) return fail(NULL, "create");
@@ -124,6 +209,7 @@ int main(int argc, char** argv) {
             fprintf(stderr, "video_to_cu_depth: %s\nvideo_to_cu_depth: continuing with the exact plan (0)\n", ethcnn_last_error(ctx));
             (void)ethcnn_set_fc1_plan(ctx, 0);
         } else if (g != ETHCNN_OK) { rc = fail(ctx, "plan check"); goto out; }
+        else if (n_audit > 0 && audit_plan(ctx, argv[1], width, height, qp, n_audit) != 0) { rc = 1; goto out; }
     }
     t_guard = now_ms();
     if (ethcnn_predict_yuv_file_sharded(ctx, devices, ndev, argv[1], width, height, qp, "cu_depth.dat", &nframes) != ETHCNN_OK) {
