@@ -222,6 +222,7 @@ extern "C" void ethcnn_sim_destroy(ethcnn_sim* k) {
     if (k->d_out) (void)hipFree(k->d_out);
     for (int* p : k->d_budget_thr)
         if (p) (void)hipFree(p);
+    if (k->d_rel) (void)hipFree(k->d_rel);
     if (k->h_call) (void)hipHostFree(k->h_call);
     delete k;
 }

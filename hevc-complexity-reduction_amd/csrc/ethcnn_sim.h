@@ -90,4 +90,5 @@ struct ethcnn_sim {
     int64_t decide_piece = 0;                 // CTUs per staged piece of ethcnn_decide and ethcnn_budget_bake; 0 = the default
     int* d_budget_thr[2] = {nullptr, nullptr};  // search budget: the ladder and the per-frame thresholds, grown on demand
     int64_t cap_budget_thr[2] = {0, 0};         // (in rows of six ints)
+    unsigned* d_rel = nullptr;                  // expected wrong decisions: the reliability table [3][1025] (ethcnn_risk.h); made on first use
 };

@@ -298,6 +298,13 @@ SIGNATURES = {
     "ethcnn_ladder_build": (_i, [_vp, _vp, _i, ctypes.c_int64, ctypes.c_uint32, _vp, _vp]),
     "ethcnn_ladder_thin": (_i, [_vp, ctypes.c_int64, ctypes.c_int64, _vp, _vp]),
     "ethcnn_ladder_write": (_i, [ctypes.c_char_p, _vp, ctypes.c_int64, _i]),
+    "ethcnn_risk_set_reliability": (_i, [_vp, _vp]),
+    "ethcnn_risk_eval": (_i, [_vp, _vp, ctypes.c_int64, _vp]),
+    "ethcnn_risk_identity": (_i, [_vp]),
+    "ethcnn_risk_from_hist": (_i, [_vp, _vp]),
+    "ethcnn_risk_write": (_i, [ctypes.c_char_p, _vp]),
+    "ethcnn_risk_read": (_i, [ctypes.c_char_p, _vp]),
+    "ethcnn_risk_ladder_build": (_i, [_vp, _vp, _i, ctypes.c_int64, ctypes.c_uint64, _vp, _vp]),
     "ethcnn_compare_probs_device": (_i, [_vp, _vp, _vp, ctypes.c_int64, ctypes.c_float, _vp, _vp, _vp]),
     "ethcnn_compare_frames_device": (_i, [_vp, _vp, _vp, _i, _i, ctypes.c_int64, ctypes.c_float, _vp, _vp, _vp]),
     "ethcnn_compare_probs": (_i, [_vp, _vp, _vp, ctypes.c_int64, ctypes.c_float, _vp, _vp, _vp]),
@@ -2419,9 +2426,101 @@ class PartitionSim(object):
         return {"thr": np.ascontiguousarray(rungs["thr"]), "coord": rungs["coord"].copy(), "value": rungs["value"].copy(),
                 "checked": rungs["checked"].copy(), "bad_ctus": rungs["bad_ctus"].copy(), "cost": cost}
 
+    # ------------------------------------------------------------------------------------------- expected wrong decisions ---
+    def set_reliability(self, rel=None):
+        """the reliability table the expected wrong decisions are read from: uint32 [3, 1025] with values in 0..RISK_ONE (risk_from_hist,
+        risk_read), or None for the identity table, which a simulator starts with"""
+        if rel is not None:
+            rel = _risk_table(rel)
+        self._chk(self.lib.ethcnn_risk_set_reliability(self.h, None if rel is None else rel.ctypes.data))
+
+    def eval_risk(self, cands):
+        """the expected wrong_split[] / wrong_stop[] of every candidate under gates "none", from the probabilities alone (include/ethcnn.h
+        "partition-search simulation: expected wrong decisions"): cands as for eval -> SIM_RISK records [K], in units of 1 / RISK_ONE"""
+        cands = _sim_cands(cands)
+        out = np.zeros(cands.size, SIM_RISK)
+        self._chk(self.lib.ethcnn_risk_eval(self.h, cands.ctypes.data if cands.size else None, cands.size, out.ctypes.data if cands.size else None))
+        return out
+
+    def build_ladder_risk(self, weights=None, grid=8, max_rungs=4096, max_risk_ppm=2 ** 64 - 1):
+        """build_ladder without labels: the same walk with the expected wrong decisions in place of the bad CTUs.  max_risk_ppm caps the
+        expected wrong nodes per million counted CTUs (the default is no cap) -> dict of numpy arrays over the rungs: thr, coord, value,
+        checked uint64 [n, 4], exp_wrong_split / exp_wrong_stop uint64 [n, 3], and risk and cost as Python integers"""
+        w = None if weights is None else (ctypes.c_uint64 * 4)(*[int(x) for x in weights])
+        ladder_check(weights, grid, max_rungs, 0, self.lib)  # (sizes the output: a bad max_rungs never reaches np.zeros)
+        if not 0 <= int(max_risk_ppm) < 2 ** 64:
+            raise EthCnnError(ERR_ARG, "max_risk_ppm lies in 0..2^64-1, got %r" % (max_risk_ppm,))
+        rungs, n = np.zeros(int(max_rungs), LADDER_RUNG_RISK), ctypes.c_int64(0)
+        self._chk(self.lib.ethcnn_risk_ladder_build(self.h, w, int(grid), int(max_rungs), int(max_risk_ppm), rungs.ctypes.data, ctypes.byref(n)))
+        rungs = rungs[:n.value]
+        wt = [int(x) for x in (BUDGET_WEIGHTS if weights is None else weights)]
+        cost = np.array([sum(a * int(b) for a, b in zip(wt, row)) for row in rungs["checked"]], dtype=object)
+        risk = np.array([sum(int(x) for x in a) + sum(int(x) for x in b) for a, b in zip(rungs["exp_wrong_split"], rungs["exp_wrong_stop"])], dtype=object)
+        return {"thr": np.ascontiguousarray(rungs["thr"]), "coord": rungs["coord"].copy(), "value": rungs["value"].copy(), "checked": rungs["checked"].copy(),
+                "exp_wrong_split": rungs["exp_wrong_split"].copy(), "exp_wrong_stop": rungs["exp_wrong_stop"].copy(), "risk": risk, "cost": cost}
+
 
 # search budget: building a ladder (include/ethcnn.h).  ethcnn_ladder_rung as a numpy record: 72 bytes, no padding
 LADDER_RUNG = np.dtype([("thr", SIM_THR), ("coord", "<i4"), ("value", "<i4"), ("checked", "<u8", (4,)), ("bad_ctus", "<u8")])
+
+# expected wrong decisions (include/ethcnn.h "partition-search simulation: expected wrong decisions"): the unit, ethcnn_sim_risk and
+# ethcnn_ladder_rung_risk (112 bytes, no padding) as numpy records
+RISK_ONE = 1 << 20
+RISK_BINS = 1025
+SIM_RISK = np.dtype([("exp_wrong_split", "<u8", (3,)), ("exp_wrong_stop", "<u8", (3,))])
+LADDER_RUNG_RISK = np.dtype([("thr", SIM_THR), ("coord", "<i4"), ("value", "<i4"), ("checked", "<u8", (4,)), ("exp_wrong_split", "<u8", (3,)),
+                             ("exp_wrong_stop", "<u8", (3,))])
+
+
+def _risk_table(rel):
+    """a reliability table as contiguous uint32 [3, 1025]; ValueError for another shape or a value that uint32 cannot hold"""
+    a = np.asarray(rel)
+    if a.size != 3 * RISK_BINS or (a.size and (a.min() < 0 or a.max() >= 2 ** 32)):
+        raise ValueError("a reliability table is [3, %d] integers in 0..%d" % (RISK_BINS, RISK_ONE))
+    return np.ascontiguousarray(a, dtype=np.uint32).reshape(3, RISK_BINS)
+
+
+def risk_identity(lib=None):
+    """ethcnn_risk_identity (host only): the table rel[l][b] = b * 1024 that takes the model at its word -> uint32 [3, 1025]"""
+    lib = lib or load_library()
+    rel = np.zeros((3, RISK_BINS), np.uint32)
+    rc = lib.ethcnn_risk_identity(rel.ctypes.data)
+    if rc:
+        raise EthCnnError(rc, lib.ethcnn_last_error(None).decode())
+    return rel
+
+
+def risk_from_hist(hist, lib=None):
+    """ethcnn_risk_from_hist (host only): the non-decreasing table fitted to a calibrator's histogram uint64 [3, 2, 1025]
+    (Calibrator.histogram) by pool-adjacent-violators -> uint32 [3, 1025]"""
+    lib = lib or load_library()
+    hist = np.ascontiguousarray(hist, dtype=np.uint64)
+    if hist.size != 3 * 2 * RISK_BINS:
+        raise ValueError("the histogram is [3, 2, %d], got %d words" % (RISK_BINS, hist.size))
+    rel = np.zeros((3, RISK_BINS), np.uint32)
+    rc = lib.ethcnn_risk_from_hist(hist.ctypes.data, rel.ctypes.data)
+    if rc:
+        raise EthCnnError(rc, lib.ethcnn_last_error(None).decode())
+    return rel
+
+
+def risk_write(path, rel, lib=None):
+    """ethcnn_risk_write (host only): the table as a text file (temp file + rename)"""
+    lib = lib or load_library()
+    rel = _risk_table(rel)
+    rc = lib.ethcnn_risk_write(os.fsencode(path), rel.ctypes.data)
+    if rc:
+        raise EthCnnError(rc, lib.ethcnn_last_error(None).decode())
+
+
+def risk_read(path, lib=None):
+    """ethcnn_risk_read (host only): a table file -> uint32 [3, 1025]; EthCnnError (ERR_FORMAT, ERR_IO) names what is wrong with it"""
+    lib = lib or load_library()
+    rel = np.zeros((3, RISK_BINS), np.uint32)
+    rc = lib.ethcnn_risk_read(os.fsencode(path), rel.ctypes.data)
+    if rc:
+        raise EthCnnError(rc, lib.ethcnn_last_error(None).decode())
+    return rel
 
 
 def _int_arg(x, lo, hi):

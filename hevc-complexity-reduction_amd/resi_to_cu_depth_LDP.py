@@ -33,6 +33,8 @@ step + heads + gates on the GPU).  Differences from the reference, none in the n
     bakes the picked decisions into cu_depth.dat (values 0, 0.5, 1) inside the handshake.  The encoder reads Thr_info.txt itself, so the
     daemon refuses at start-up (status 1, before a GPU is touched, no signal file) unless that file is the companion line in
     Low-Delay-P token order, "0.25 0.75 0.25 0.75 0.25 0.75".  A frame with i_frame <= 1 or another geometry starts a new allowance.
+    ETHCNN_SEARCH_BUDGET_LADDER=auto, which lets the All-Intra launcher build the ladder from the sequence it predicts, is refused at
+    start-up with the reason: this loop sees one frame at a time.
 """
 from __future__ import print_function
 
@@ -46,6 +48,9 @@ from . import ethcnn as _e
 from . import net_CNN as nt
 from . import search_budget as _sb
 
+# ETHCNN_SEARCH_BUDGET_LADDER=auto builds a ladder from the predictions of the whole sequence; this daemon predicts frame by frame
+NO_AUTO_LADDER = ('the Low-Delay-P loop predicts one frame at a time and cannot see the sequence in advance; build the ladder offline '
+                  '(tools/build_ladder.py --no-labels --out FILE --order ldp) and name the file')
 IMAGE_SIZE = nt.IMAGE_SIZE
 NUM_CHANNELS = nt.NUM_CHANNELS
 NUM_EXT_FEATURES = 2      # QP and POC (resi_to_cu_depth_LDP.py:19)
@@ -216,7 +221,7 @@ def serve(workdir='.', max_frames=None, idle_timeout=None, poll_s=2e-4, device=0
     p = lambda name: os.path.join(workdir, name)
     budget, ladder = _sb.from_env(), None   # (ValueError for a bad value: before a GPU is touched)
     if budget is not None:
-        ladder = _sb.ladder_from_env('ldp')
+        ladder = _sb.ladder_from_env('ldp', auto=NO_AUTO_LADDER)
         _sb.check_companion_thr_file(p(THR_FILE), _sb.COMPANION_LINE_LDP)
     ctx = _e.EthCnn(device=device)
     pacer, paced_geom, paced = None, None, [0, 0, 0, 0]   # frames, over budget, sum of cost, sum of full
@@ -316,7 +321,7 @@ def main(argv):
             return 2
     try:  # a bad ETHCNN_SEARCH_BUDGET* value, or a Thr_info.txt that is not the companion line: refused before a GPU is touched
         if _sb.from_env() is not None:
-            _sb.ladder_from_env('ldp')
+            _sb.ladder_from_env('ldp', auto=NO_AUTO_LADDER)
             _sb.check_companion_thr_file(THR_FILE, _sb.COMPANION_LINE_LDP)
     except ValueError as err:
         sys.stderr.write('resi_to_cu_depth_LDP: %s\n' % err)

@@ -1,12 +1,17 @@
 """The environment of the search budget (include/ethcnn.h "search budget"), shared by the launchers that take one: the All-Intra
 launcher (video_to_cu_depth.py) and the Low-Delay-P daemon (resi_to_cu_depth_LDP.py).  ETHCNN_SEARCH_BUDGET=<share, 0..1>,
 ETHCNN_SEARCH_BUDGET_MODE=frame|carry (default frame), ETHCNN_SEARCH_BUDGET_WEIGHTS="64 16 4 1", ETHCNN_SEARCH_BUDGET_LADDER=<ladder file>
-(default: the default ladder; read only when a budget is set).  Nothing here touches a GPU."""
+(default: the default ladder; read only when a budget is set).  ETHCNN_SEARCH_BUDGET_LADDER=auto asks a launcher that sees the whole
+sequence before the encoder starts to build the ladder itself, without labels, from its own predictions (include/ethcnn.h
+"partition-search simulation: expected wrong decisions"); ETHCNN_SEARCH_BUDGET_RELIABILITY=<table file> is then optional.  Nothing here
+touches a GPU."""
 import os
 
 COMPANION_LINE_AI = '0.75 0.25 0.75 0.25 0.75 0.25'    # ethcnn_budget_companion_thr in All-Intra token order: up down ...
 COMPANION_LINE_LDP = '0.25 0.75 0.25 0.75 0.25 0.75'   # ... and in Low-Delay-P token order: down up ...
 MAX_RUNGS = 4096                                       # ETHCNN_BUDGET_MAX_RUNGS
+AUTO = 'auto'                                          # ETHCNN_SEARCH_BUDGET_LADDER=auto: a ladder built from the sequence itself
+AUTO_GRID = 8                                          # ... on this grid, up to MAX_RUNGS rungs, without a cap
 
 
 def from_env():
@@ -73,15 +78,33 @@ def read_ladder(path, order):
     return up, down
 
 
-def ladder_from_env(order):
+def ladder_from_env(order, auto=None):
     """None when ETHCNN_SEARCH_BUDGET_LADDER is unset or empty (the default ladder), else read_ladder of that file in the token order
-    of the launcher that asks; ValueError names a file that is missing or malformed or holds more than 4096 rungs"""
+    of the launcher that asks; ValueError names a file that is missing or malformed or holds more than 4096 rungs.  The value "auto"
+    gives AUTO to a launcher that can build a ladder from the sequence it is about to predict (auto=True); every other launcher
+    passes the reason why it cannot, and the ValueError carries it"""
     path = os.environ.get('ETHCNN_SEARCH_BUDGET_LADDER')
     if not path:
         return None
+    if path == AUTO and auto is not None:
+        if auto is True:
+            return AUTO
+        raise ValueError("ETHCNN_SEARCH_BUDGET_LADDER='auto' cannot be read: %s" % auto)
     try:
         return read_ladder(path, order)
     except OSError as err:
         raise ValueError("ETHCNN_SEARCH_BUDGET_LADDER='%s' cannot be read: %s" % (path, err.strerror or err))
     except ValueError as err:
         raise ValueError("ETHCNN_SEARCH_BUDGET_LADDER: %s" % err)
+
+
+def reliability_from_env(read):
+    """None when ETHCNN_SEARCH_BUDGET_RELIABILITY is unset or empty (the identity table), else read(path) -- the binding's risk_read,
+    host only; ValueError names a file that cannot be read or is no reliability table"""
+    path = os.environ.get('ETHCNN_SEARCH_BUDGET_RELIABILITY')
+    if not path:
+        return None
+    try:
+        return read(path)
+    except (OSError, RuntimeError) as err:   # (libethcnn errors are RuntimeErrors)
+        raise ValueError("ETHCNN_SEARCH_BUDGET_RELIABILITY='%s' cannot be read: %s" % (path, err))

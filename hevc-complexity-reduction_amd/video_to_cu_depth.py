@@ -19,6 +19,10 @@ Differences from the reference, all outside the numbers it produces:
     writes a BAKED cu_depth.dat (values 0, 0.5, 1).  HM reads Thr_info.txt afterwards, so the launcher refuses (exit status 1, no
     cu_depth.dat) unless that file is the companion line "0.75 0.25 0.75 0.25 0.75 0.25".  ETHCNN_SEARCH_BUDGET_MODE=frame|carry
     (default frame) and ETHCNN_SEARCH_BUDGET_WEIGHTS="64 16 4 1" are optional.  One GPU only: ETHCNN_DEVICES with a budget is refused.
+    ETHCNN_SEARCH_BUDGET_LADDER=auto builds the ladder from THIS file's open-gate predictions, without labels: the walk of
+    tools/build_ladder.py --no-labels (include/ethcnn.h "partition-search simulation: expected wrong decisions") on grid 8, up to
+    4096 rungs, no cap, under the run's weights.  ETHCNN_SEARCH_BUDGET_RELIABILITY=<table of calibrate_thresholds.py --reliability-out>
+    is optional (default: the identity table); an unreadable one is refused at start-up (exit status 1, nothing written).
   * ETHCNN_FC1_PLAN_AUDIT=<N> (read only when ETHCNN_FC1_PLAN is set and the guard accepted the plan) audits the plan on min(N, frames)
     evenly spaced frames of THIS file before it is trusted (include/ethcnn.h "comparing two predictions"): plan against exact plan at
     the run's QP, open gates, Thr_info.txt as the candidate, with the single-launch pass off (the audited frames take the 16-bit path that
@@ -91,8 +95,12 @@ def check_companion_thr_file(path=THR_FILE):
 
 def search_ladder_from_env():
     """None (the default ladder) when ETHCNN_SEARCH_BUDGET_LADDER is unset or empty, else that ladder file read in All-Intra token order
-    -> (up_k, down_k); ValueError names a bad file"""
-    return _sb.ladder_from_env('ai')
+    -> (up_k, down_k); "auto" -> (AUTO, reliability table or None): the ladder is built from the file's own predictions; ValueError
+    names a bad file"""
+    ladder = _sb.ladder_from_env('ai', auto=True)
+    if ladder == _sb.AUTO:
+        return _sb.AUTO, _sb.reliability_from_env(_e.risk_read)
+    return ladder
 
 
 def write_budgeted(ctx, yuv_name, qp_seq, frame_width, frame_height, budget, save_file, ladder=None):
@@ -100,7 +108,8 @@ def write_budgeted(ctx, yuv_name, qp_seq, frame_width, frame_height, budget, sav
     under the budget, the picked decisions baked into save_file (temp file + rename).  -> (frames, achieved share, over-budget frames)"""
     import numpy as np
     share, mode, weights = budget
-    if ladder is not None:
+    auto = ladder is not None and ladder[0] == _sb.AUTO
+    if ladder is not None and not auto:
         ladder = _e.sim_thr(*ladder)
     tmp = '%s.tmp.%d' % (save_file, os.getpid())
     try:
@@ -109,6 +118,10 @@ def write_budgeted(ctx, yuv_name, qp_seq, frame_width, frame_height, budget, sav
         probs = np.fromfile(tmp, dtype='<f4')
         with _e.PartitionSim(ctx) as sim:
             sim.add_frames(probs, None, frame_width, frame_height, nframes=n_frames)
+            if auto:   # the ladder of this very sequence: no labels exist before the encode
+                sim.set_reliability(ladder[1])
+                ladder = sim.build_ladder_risk(weights, _sb.AUTO_GRID, _sb.MAX_RUNGS)['thr']
+                sys.stderr.write('video_to_cu_depth: ladder of %d rungs built from the predictions of %d frames\n' % (len(ladder), n_frames))
             out = sim.budget_control(share, mode, ladder=ladder, weights=weights, width=frame_width, height=frame_height, nframes=n_frames)
         out['probs'].astype('<f4').tofile(tmp)
         os.replace(tmp, save_file)

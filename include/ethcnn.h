@@ -1268,6 +1268,81 @@ int ethcnn_ladder_build(ethcnn_sim* sim, const uint64_t weight[4], int grid, int
 int ethcnn_ladder_thin(const uint64_t* cost, int64_t n, int64_t K, int32_t* idx_out, int64_t* k_out);
 int ethcnn_ladder_write(const char* path, const ethcnn_sim_thr* thr, int64_t K, int order);
 
+/* ---- partition-search simulation: expected wrong decisions.  wrong_split[] / wrong_stop[] / bad_ctus above need labels, and labels need
+ *      the full-search encode this project exists to avoid.  The model prices a forced decision itself: a node forced CURRENT ONLY whose
+ *      split probability is p is wrong with probability p, a node forced SPLIT ONLY with probability 1 - p.  Summed over the decided
+ *      nodes of the pruned search that gives the EXPECTED values of wrong_stop[] and wrong_split[], from the bins the simulator's records
+ *      already hold and without a label.  No reference counterpart.
+ *   Unit and table.  ETHCNN_RISK_ONE = 2^20 stands for probability 1.  A RELIABILITY TABLE is uint32_t rel[3][1025] (level, bin), every
+ *      value in 0..ETHCNN_RISK_ONE: rel[l][b] estimates the share of the level-l nodes with bin b whose truth flag (those of the
+ *      calibration block) is "split".  The IDENTITY table is rel[l][b] = b * 1024, that is p rounded up to its bin edge b / 1024: it
+ *      takes the model at its word.  A simulator starts with the identity table.  ethcnn_risk_set_reliability validates and uploads a
+ *      table (NULL: the identity); a value above ETHCNN_RISK_ONE is ETHCNN_ERR_ARG and changes nothing.  The table belongs to the
+ *      simulator, not to the set: ethcnn_sim_reset keeps it.
+ *   Counter.  Under ETHCNN_SIM_GATES_NONE only (the probabilities are what the encoder will read), over every CTU that is not rejected,
+ *      labelled or not, wholly inside the picture or not.  Each DECIDED NODE (rule line 4 of "partition-search simulation") of level l
+ *      and bin b contributes by its outcome:
+ *        CURRENT ONLY   exp_wrong_stop[l]  += rel[l][b]
+ *        SPLIT ONLY     exp_wrong_split[l] += ETHCNN_RISK_ONE - rel[l][b]
+ *        BOTH           nothing
+ *      risk = the sum of the six fields: expected wrong nodes in units of 1 / ETHCNN_RISK_ONE.  The sums are exact integers, so they do
+ *      not depend on the launch grid, on the order of adds or on how a set is split over adds.  Bound: a CTU has 21 nodes, so 2^31 CTUs
+ *      x 16 nodes of a level x 2^20 = 2^55 per field, and the sum of six fields stays below 2^58: everything fits in 64 bits.
+ *   ethcnn_risk_eval: out[c] = the counter of candidate cand[c] over the whole set.  ncand == 0 is a no-op, an empty set gives zeros,
+ *      a candidate outside the simulator's ranges is ETHCNN_ERR_ARG.  Synchronous on the context's stream.
+ *   Tables (host only, pure, no context; errors are read with ethcnn_last_error(NULL)):
+ *      ethcnn_risk_identity(rel) writes the identity table.
+ *      ethcnn_risk_from_hist(hist, rel) fits a table to the ETHCNN_CALIB_HIST_WORDS words of ethcnn_calib_get, NON-DECREASING in the bin,
+ *        by pool-adjacent-violators.  Per level, s_b = hist[l][1][b] and t_b = s_b + hist[l][0][b].  Walk b = 0..1024 with a stack of
+ *        blocks (S, T, first, last): push (s_b, t_b, b, b); then, while there are two blocks and (top.T == 0 or below.T == 0 or
+ *        below.S * top.T > top.S * below.T, in 128-bit products), merge the top block into the one below (S and T add, last = top.last).
+ *        So empty bins join the block on their left, and leading empty bins join the first block that has samples.  Every bin of a
+ *        block gets floor(S * 2^20 / T).  A level without any sample gets the identity.
+ *      ethcnn_risk_write(path, rel) / ethcnn_risk_read(path, rel): a text file, first line "ethcnn-reliability 1", then three lines
+ *        (levels 0, 1, 2) of 1025 decimal integers separated by blanks.  Written to a temp file that is then renamed (a table with a
+ *        value above ETHCNN_RISK_ONE: ETHCNN_ERR_ARG, nothing written).  On reading,
+ *        anything else -- another first line, a missing or a further token, a token that is no decimal integer -- or a value above
+ *        ETHCNN_RISK_ONE is ETHCNN_ERR_FORMAT and rel is untouched; a file that cannot be opened is ETHCNN_ERR_IO.
+ *   ethcnn_risk_ladder_build: the walk of "search budget: building a ladder" on a set WITHOUT labels.  It is that walk word for word --
+ *      rung 0, the candidate values of a coordinate, nearest first, the FIRST value with cost(v) < C, the sweep order -- with bad
+ *      replaced by risk: B becomes R, the risk of the current rung, and bad(v) becomes risk(v) of ethcnn_risk_eval under the
+ *      simulator's table.  Rule 4 becomes: if risk(v) * 10^6 > max_risk_ppm * counted_ctus * ETHCNN_RISK_ONE (128-bit products) the
+ *      coordinate has no move, with counted_ctus = ctus - rejected_ctus of ethcnn_sim_info; so the cap reads "expected wrong nodes per
+ *      million CTUs" (max_risk_ppm is a uint64_t: UINT64_MAX, like any value from 21 * 10^6 on, is no cap).  Of the moves, the one
+ *      with the smallest (risk(v) - R) / (C - cost(v)) is taken, compared exactly by signed 128-bit cross products; ties break as in
+ *      the labelled walk (the larger saving, then the smaller c).  No labelled CTU is needed; a set with counted_ctus == 0 is
+ *      ETHCNN_ERR_ARG, as are the refusals of the labelled build for weight, grid, max_rungs and the cost bound.
+ *      A rung is an ethcnn_ladder_rung_risk, 112 bytes, little-endian, no padding: thr at 0, coord int32 at 24, value int32 at 28,
+ *      checked uint64[4] at 32, exp_wrong_split uint64[3] at 64, exp_wrong_stop uint64[3] at 88: exactly what ethcnn_sim_eval (gates
+ *      none) and ethcnn_risk_eval give for thr.  Synchronous; per call a table uint64 [6][1025 / grid + 1][10], a state block and
+ *      max_rungs rungs in HBM.  A second build on the same set and table gives the same bytes.  ethcnn_ladder_check (with max_bad_ppm
+ *      0), ethcnn_ladder_thin and ethcnn_ladder_write serve both kinds of ladder.
+ *   What this is not.  The identity table ASSUMES A CALIBRATED MODEL: where the model is over-confident the figure is too low, and only
+ *      a table fitted on labelled material (ethcnn_risk_from_hist) corrects that, for material like the one it was fitted on.  The
+ *      level-1 and level-2 probabilities come from a model trained under teacher forcing -- on nodes whose parents were truly split --
+ *      while the counter also asks them on nodes the pruned search reaches for other reasons.  The figure counts nodes, not CTUs, and
+ *      nothing relates it to encoding time or to BD-rate. */
+#define ETHCNN_RISK_ONE (1u << 20)
+#define ETHCNN_RISK_REL_WORDS (3 * ETHCNN_CALIB_BINS)
+typedef struct ethcnn_sim_risk {
+    uint64_t exp_wrong_split[3], exp_wrong_stop[3];
+} ethcnn_sim_risk;
+typedef struct ethcnn_ladder_rung_risk {
+    ethcnn_sim_thr thr;
+    int32_t coord;
+    int32_t value;
+    uint64_t checked[4];
+    uint64_t exp_wrong_split[3], exp_wrong_stop[3];
+} ethcnn_ladder_rung_risk;
+int ethcnn_risk_set_reliability(ethcnn_sim* sim, const uint32_t* rel_or_null);
+int ethcnn_risk_eval(ethcnn_sim* sim, const ethcnn_sim_thr* cand, int64_t ncand, ethcnn_sim_risk* out);
+int ethcnn_risk_identity(uint32_t* rel);
+int ethcnn_risk_from_hist(const uint64_t* hist, uint32_t* rel);
+int ethcnn_risk_write(const char* path, const uint32_t* rel);
+int ethcnn_risk_read(const char* path, uint32_t* rel);
+int ethcnn_risk_ladder_build(ethcnn_sim* sim, const uint64_t weight[4], int grid, int64_t max_rungs, uint64_t max_risk_ppm,
+                             ethcnn_ladder_rung_risk* rungs_out, int64_t* nrungs_out);
+
 /* ---- comparing two predictions: how far two sets of probabilities are apart, and whether the encoder's pruned search changes (no
  *      reference counterpart).  The questions behind every "byte-identical" and "within tolerance" of this project: a 16-bit plan against
  *      the exact plan, one daemon against another, a retrained model against the one before it, a sharded run against a single one.  One

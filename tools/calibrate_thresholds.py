@@ -8,7 +8,7 @@ runs.  This tool counts, on the GPU, where the probabilities of truly split and 
 the largest `down` that wrongly stops at most --eps-down parts per million of the truly split samples and the smallest `up` that
 wrongly forces at most --eps-up parts per million of the truly unsplit ones.
 
-    calibrate_thresholds.py [--eps-down E1 E2 E3] [--eps-up E1 E2 E3] [--out Thr_info.txt --order ai|ldp] [--hist FILE] [--json] [--device N]
+    calibrate_thresholds.py [--eps-down E1 E2 E3] [--eps-up E1 E2 E3] [--out Thr_info.txt --order ai|ldp] [--hist FILE] [--reliability-out FILE] [--json] [--device N]
                             [--input-bit-depth N] [--input-chroma-format 400|420|422|444] CASE...
 
 Any number of cases, accumulated into one histogram:
@@ -35,7 +35,10 @@ the All-Intra --yuv cases of the run (include/ethcnn.h "high-bit-depth and non-4
 which are always 8-bit 4:2:0, and --case / --samples cases carry no video.  A format other than 8-bit 4:2:0 without an All-Intra
 --yuv case is an error.
 
-Budgets default to 50000 ppm (5 %).  --hist FILE also writes the accumulated histogram, uint64 little-endian [3 levels][2 truths][1025 bins].  --order ai writes "up1 down1 up2 down2 up3 down3" (HM-16.5_Test_AI, TEncCu.cpp:250), --order
+Budgets default to 50000 ppm (5 %).  --hist FILE also writes the accumulated histogram, uint64 little-endian [3 levels][2 truths][1025 bins].
+--reliability-out FILE writes the reliability table of that histogram (include/ethcnn.h "partition-search simulation: expected wrong
+decisions": per level and bin the share of truly split samples, made non-decreasing), which simulate_thresholds.py --reliability,
+build_ladder.py --no-labels --reliability and ETHCNN_SEARCH_BUDGET_RELIABILITY read.  --order ai writes "up1 down1 up2 down2 up3 down3" (HM-16.5_Test_AI, TEncCu.cpp:250), --order
 ldp writes "down1 up1 down2 up2 down3 up3" (HM-16.5_Test_LDP, TEncGOP.cpp:1449): the two encoders differ.  CTUs that are not wholly
 inside the picture are left out (HM forces their splits).
 """
@@ -65,7 +68,7 @@ def _take(argv, i, n, what):
 def parse(argv, labels_optional=False):
     """-> (options, cases); the options after a case belong to it.  labels_optional: a --yuv case may come without --labels (the
     simulation tool, which shares this command line's cases)"""
-    opt = {"eps_down": [50000] * 3, "eps_up": [50000] * 3, "out": None, "order": None, "hist": None, "json": False, "device": 0}
+    opt = {"eps_down": [50000] * 3, "eps_up": [50000] * 3, "out": None, "order": None, "hist": None, "reliability_out": None, "json": False, "device": 0}
     cases, i = [], 0
     fmt = {"--input-bit-depth": DEFAULT_FORMAT[0], "--input-chroma-format": DEFAULT_FORMAT[1]}
     per_case = {"--skip-label-frames": ("skip", int, ("case",)), "--labels": ("labels", str, ("yuv",)), "--model-dir": ("model_dir", str, ("yuv", "samples")),
@@ -79,9 +82,9 @@ def parse(argv, labels_optional=False):
         elif a in ("--eps-down", "--eps-up"):
             v, i = _take(argv, i, 3, a)
             opt[a[2:].replace("-", "_")] = [int(x) for x in v]
-        elif a in ("--out", "--order", "--hist", "--device"):
+        elif a in ("--out", "--order", "--hist", "--reliability-out", "--device"):
             v, i = _take(argv, i, 1, a)
-            opt[a[2:]] = int(v[0]) if a == "--device" else v[0]
+            opt[a[2:].replace("-", "_")] = int(v[0]) if a == "--device" else v[0]
         elif a == "--json":
             opt["json"] = True
         elif a in fmt:
@@ -258,6 +261,9 @@ def run(opt, cases, out=sys.stdout, err=sys.stderr):
             cal.write_thr_info(opt["out"], rep, opt["order"])
         if opt["hist"]:
             hist.astype("<u8").tofile(opt["hist"])
+        if opt["reliability_out"]:
+            pkg.ethcnn.risk_write(opt["reliability_out"], pkg.ethcnn.risk_from_hist(hist))
+            note("wrote %s: the reliability table of %d samples" % (opt["reliability_out"], int(hist.sum())))
     finally:
         ctx.close()
     result = {"levels": levels, "rejected": [int(x) for x in rejected], "skipped_partial": skipped,

@@ -425,6 +425,12 @@ static int ladder_from_env(ethcnn_sim_thr** out, int64_t* K) {
     *out = NULL;
     *K = 0;
     if (!path || !*path) return 0;
+    if (strcmp(path, "auto") == 0) { /* the All-Intra launcher's value: a ladder built from the whole sequence's predictions */
+        fprintf(stderr, "resi_to_cu_depth_ldp: ETHCNN_SEARCH_BUDGET_LADDER='auto' cannot be read: the Low-Delay-P loop predicts one frame at a time "
+                        "and cannot see the sequence in advance; build the ladder offline (tools/build_ladder.py --no-labels --out FILE --order ldp) "
+                        "and name the file\n");
+        return -1;
+    }
     FILE* f = fopen(path, "rb");
     char* text = NULL;
     size_t len = 0, cap = 0;
