@@ -3,17 +3,14 @@
 // audited plan, compared in the frame layout).
 #include <fcntl.h>
 
-#include "ethcnn_ctx.h"
+#include "ethcnn_analysis.h"
 #include "ethcnn_audit.h"
-#include "ethcnn_sim.h"
 
 using namespace ethcnn::audit;
+using ethcnn::sim::kStageCtus;
 
 namespace {
-constexpr int64_t kStageCtus = 1 << 20;  // CTUs per staged piece of the host entries
-constexpr int kRow = kNOut * 4;          // bytes of a CTU's probabilities
-
-int cus_of(const ethcnn_ctx* c) { return c->cus > 0 ? c->cus : 256; }
+constexpr int kRow = kNOut * 4;  // bytes of a CTU's probabilities
 
 void zero_stats(ethcnn_compare_stats* s) {
     std::memset(s, 0, sizeof *s);
@@ -29,10 +26,10 @@ int check_rules(ethcnn_ctx* c, int width, int height, int64_t units, bool frames
     *g = Geom{0, 0, 64, 64};
     int64_t per = 1;
     if (frames) {
-        if (width <= 0 || height <= 0 || width > 65536 || height > 65536 || width % 8 || height % 8)
-            return set_err(c, ETHCNN_ERR_ARG, "HM pictures have sizes that are multiples of 8 (up to 65536): got %d x %d", width, height);
-        *g = Geom{(width + 63) / 64, (height + 63) / 64, width, height};
-        per = (int64_t)g->ctus_w * g->ctus_h;
+        ethcnn::sim::PicSize s;
+        if (int rc = ethcnn::sim::check_size(c, width, height, 8, &s)) return rc;
+        *g = Geom{s.ctus_w, s.ctus_h, width, height};
+        per = s.ctus();
     }
     if (units > (((int64_t)1 << 31) - 1) / per) return set_err(c, ETHCNN_ERR_ARG, "compare: 2^31 CTUs or more in one call");
     *n = units * per;
@@ -149,17 +146,12 @@ int compare_host(ethcnn_ctx* c, const float* a, const float* b, int64_t n, const
     const int64_t piece = (a_direct && b_direct && f_direct) ? n : std::min(n, kStageCtus);
     const size_t bytes = (size_t)piece * ((a_direct ? 0 : kRow) + (b_direct ? 0 : kRow) + (f_direct ? 0 : 1));
     if (int rc = begin_call(c)) return rc;
-    uint8_t* d_stage = nullptr;
-    if (bytes) {
-        size_t free_b = 0, total_b = 0;
-        if (hipMemGetInfo(&free_b, &total_b) != hipSuccess || bytes > free_b || hipMalloc((void**)&d_stage, bytes) != hipSuccess) {
-            (void)hipGetLastError();
-            return set_err(c, ETHCNN_ERR_NOMEM, "compare: %llu bytes of staging do not fit in device memory", (unsigned long long)bytes);
-        }
-    }
-    float* d_a = reinterpret_cast<float*>(d_stage);
-    float* d_b = reinterpret_cast<float*>(d_stage + (a_direct ? 0 : (size_t)piece * kRow));
-    uint8_t* d_f = d_stage + (size_t)piece * ((a_direct ? 0 : kRow) + (b_direct ? 0 : kRow));
+    Scratch stage;
+    if (bytes)
+        if (int rc = stage.alloc(c, bytes, "compare", true)) return rc;
+    float* d_a = stage.at<float>();
+    float* d_b = stage.at<float>(a_direct ? 0 : (size_t)piece * kRow);
+    uint8_t* d_f = stage.at((size_t)piece * ((a_direct ? 0 : kRow) + (b_direct ? 0 : kRow)));
     hipError_t e = hipSuccess;
     for (int64_t at = 0; at < n && e == hipSuccess; at += piece) {
         const int64_t m = std::min(piece, n - at);
@@ -174,7 +166,6 @@ int compare_host(ethcnn_ctx* c, const float* a, const float* b, int64_t n, const
     }
     int rc = e == hipSuccess ? end_call(c, n, thr != nullptr, out) : set_err(c, ETHCNN_ERR_DEVICE, "compare: %s", hipGetErrorString(e));
     if (e != hipSuccess) (void)hipStreamSynchronize(c->stream);
-    if (d_stage) (void)hipFree(d_stage);
     return rc;
 }
 }  // namespace
@@ -251,13 +242,12 @@ extern "C" int ethcnn_audit_plan_device(ethcnn_ctx* c, const uint8_t* d_luma, in
         return ETHCNN_OK;
     }
     const size_t bytes = (size_t)ethcnn_audit_plan_bytes(width, height, nframes);
-    size_t free_b = 0, total_b = 0;
-    float* d_p = nullptr;
-    if (hipMemGetInfo(&free_b, &total_b) != hipSuccess || bytes > free_b || hipMalloc((void**)&d_p, bytes) != hipSuccess) {
-        (void)hipGetLastError();
+    Scratch probs;  // the two sets of probabilities
+    if (int rc = probs.alloc(c, bytes, "audit", true)) {
         saved.restore();
-        return set_err(c, ETHCNN_ERR_NOMEM, "audit: %llu bytes for two sets of probabilities do not fit in device memory", (unsigned long long)bytes);
+        return rc;
     }
+    float* const d_p = probs.at<float>();
     c->thr1 = c->thr2 = -1.0f;  // gates open: a gate's knife edge is not an arithmetic error
     c->fc1_plan = 0;
     float* const d_q = d_p + ((size_t)n * kNOut + 3) / 4 * 4;  // side b, 16-byte aligned
@@ -272,7 +262,6 @@ extern "C" int ethcnn_audit_plan_device(ethcnn_ctx* c, const uint8_t* d_luma, in
     saved.restore();
     if (rc == 0) rc = compare_device(c, d_p, d_q, n, g, tol, thr, &out->stats, nullptr);
     else (void)hipStreamSynchronize(c->stream);
-    (void)hipFree(d_p);
     return rc;
 }
 
@@ -284,8 +273,8 @@ extern "C" int ethcnn_audit_plan_yuv_file(ethcnn_ctx* c, const char* path, int w
         return set_err(c, ETHCNN_ERR_ARG, "audit: the file entry reads 8-bit 4:2:0 only (the context's source format is %d-bit %d)", c->src_fmt.bit_depth,
                        c->src_fmt.chroma_format);
     if (plan != 2 && plan != 3) return set_err(c, ETHCNN_ERR_ARG, "audit: plan must be 2 or 3, got %d", plan);
-    if (width <= 0 || height <= 0 || width % 8 || height % 8 || width > 65536 || height > 65536)
-        return set_err(c, ETHCNN_ERR_ARG, "HM pictures have sizes that are multiples of 8 (up to 65536): got %d x %d", width, height);
+    ethcnn::sim::PicSize size;
+    if (int rc = ethcnn::sim::check_size(c, width, height, 8, &size)) return rc;
     if (first < 0 || step < 1 || count < 0 || count > 0x7fffffff) return set_err(c, ETHCNN_ERR_ARG, "audit: first >= 0, step >= 1 and count >= 0 are required");
     const int fd = open(path, O_RDONLY);
     if (fd < 0) return set_err(c, ETHCNN_ERR_IO, "cannot open %s: %s", path, std::strerror(errno));

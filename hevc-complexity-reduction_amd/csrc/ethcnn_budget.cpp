@@ -1,33 +1,27 @@
 // ethcnn_budget.cpp -- host side of the search budget (include/ethcnn.h "search budget"): the entries around the two kernels of
 // ethcnn_budget.hip over a simulator's set, and the host-only ladder, companion thresholds and per-frame choice.
-#include "ethcnn_ctx.h"
+#include "ethcnn_analysis.h"
 #include "ethcnn_budget.h"
-#include "ethcnn_sim.h"
 
 using namespace ethcnn::budget;
+using ethcnn::sim::kStageCtus;
 
 namespace {
-constexpr int64_t kStageCtus = 1 << 20;  // CTUs per staged piece of the host form of the bake
-typedef unsigned __int128 u128;
-const uint64_t kDefaultWeight[4] = {64, 16, 4, 1};
-
-int cus_of(const ethcnn_ctx* c) { return c->cus > 0 ? c->cus : 256; }
-
 int check_ladder(ethcnn_ctx* c, const ethcnn_sim_thr* ladder, int64_t K) {
     if (!ladder) return set_err(c, ETHCNN_ERR_ARG, "null ladder");
-    if (K < 1 || K > kMaxRungs) return set_err(c, ETHCNN_ERR_ARG, "a ladder has 1..%d rungs: got %lld", kMaxRungs, (long long)K);
+    if (int rc = sim::check_rung_count(c, K)) return rc;
     for (int64_t i = 0; i < K; ++i)
-        if (int rc = ethcnn::sim::check_cand(c, ladder[i], (long long)i)) return rc;
+        if (int rc = sim::check_cand(c, ladder[i], (long long)i)) return rc;
     return 0;
 }
 
 // the window of whole frames; *per = CTUs a frame
 int check_window(ethcnn_sim* k, int64_t first, int width, int height, int64_t nframes, int64_t* per) {
     ethcnn_ctx* c = k->c;
-    if (width <= 0 || height <= 0 || width > 65536 || height > 65536 || width % 8 || height % 8)
-        return set_err(c, ETHCNN_ERR_ARG, "HM pictures have sizes that are multiples of 8 (up to 65536): got %d x %d", width, height);
+    sim::PicSize s;
+    if (int rc = sim::check_size(c, width, height, 8, &s)) return rc;
     if (first < 0 || nframes < 0) return set_err(c, ETHCNN_ERR_ARG, "negative first CTU or frame count");
-    *per = (int64_t)((width + 63) / 64) * ((height + 63) / 64);
+    *per = s.ctus();
     if (*per >= kMaxFrameCtus) return set_err(c, ETHCNN_ERR_ARG, "a frame of %lld CTUs does not count in 32 bits (fewer than 2^24)", (long long)*per);
     return ethcnn::sim::check_frame_run(k, first, width, height, nframes);
 }
@@ -64,7 +58,7 @@ int run_cost(ethcnn_sim* k, const ethcnn_sim_thr* ladder, int64_t K, int64_t fir
     std::vector<int> rows;
     rows.reserve((size_t)(K + 1) * 6);
     for (int64_t i = 0; i < K; ++i) push(rows, ladder[i]);
-    push(rows, ethcnn_sim_thr{{1024, 1024, 1024}, {-1, -1, -1}});  // column K: the full search
+    push(rows, sim::kFullSearch);  // column K
     if (int rc = upload_thr(k, 0, rows)) return rc;
     HIPCHK(c, hipMemsetAsync(d_out, 0, (size_t)(nframes * (K + 1)) * 16, c->stream));
     launch_cost(c->stream, k->d_recs + first * ethcnn::sim::kRecDwords, (long)per, (long)nframes, k->d_budget_thr[0], (int)(K + 1), d_out, cus_of(c));
@@ -103,27 +97,20 @@ int bake_staged(ethcnn_sim* k, const ethcnn_sim_thr* ladder, const int32_t* rung
     const int64_t n = nframes * per, row = kNout * 4;
     HIPCHK(c, hipSetDevice(c->device));
     const int64_t piece = std::min(n, k->decide_piece > 0 ? k->decide_piece : kStageCtus);
-    size_t free_b = 0, total_b = 0;
-    HIPCHK(c, hipMemGetInfo(&free_b, &total_b));
-    float* d = nullptr;
-    if ((uint64_t)(piece * row) > free_b || hipMalloc((void**)&d, (size_t)(piece * row)) != hipSuccess) {
-        (void)hipGetLastError();
-        return set_err(c, ETHCNN_ERR_NOMEM, "search budget: %lld bytes of staging for %lld CTUs do not fit in device memory (%llu free)", (long long)(piece * row),
-                       (long long)piece, (unsigned long long)free_b);
-    }
+    Scratch d;
+    if (int rc = d.alloc(c, (size_t)(piece * row), "search budget", true)) return rc;
     int rc = upload_frame_thr(k, ladder, rung, nframes);
     for (int64_t at = 0; at < n && !rc; at += piece) {
         const int64_t cur = std::min(piece, n - at);
-        rc = run_bake(k, first, per, at, cur, d);
+        rc = run_bake(k, first, per, at, cur, d.at<float>());
         hipError_t e = hipSuccess;
-        if (!rc) e = hipMemcpyAsync(probs_out + at * kNout, d, (size_t)(cur * row), hipMemcpyDeviceToHost, c->stream);
+        if (!rc) e = hipMemcpyAsync(probs_out + at * kNout, d.at(), (size_t)(cur * row), hipMemcpyDeviceToHost, c->stream);
         if (!rc && e == hipSuccess) e = hipStreamSynchronize(c->stream);
         if (!rc && e != hipSuccess) {
             (void)hipGetLastError();
             rc = set_err(c, ETHCNN_ERR_DEVICE, "search budget: %s", hipGetErrorString(e));
         }
     }
-    (void)hipFree(d);
     return rc;
 }
 
@@ -132,21 +119,17 @@ int cost_to_host(ethcnn_sim* k, const ethcnn_sim_thr* ladder, int64_t K, int64_t
     ethcnn_ctx* c = k->c;
     HIPCHK(c, hipSetDevice(c->device));
     const size_t bytes = (size_t)(nframes * (K + 1)) * 16;
-    uint32_t* d = nullptr;
-    if (hipMalloc((void**)&d, bytes) != hipSuccess) {
-        (void)hipGetLastError();
-        return set_err(c, ETHCNN_ERR_NOMEM, "search budget: %llu bytes of counters do not fit in device memory", (unsigned long long)bytes);
-    }
-    int rc = run_cost(k, ladder, K, first, per, nframes, d);
+    Scratch d;
+    if (int rc = d.alloc(c, bytes, "search budget")) return rc;
+    int rc = run_cost(k, ladder, K, first, per, nframes, d.at<uint32_t>());
     if (!rc) {
-        hipError_t e = hipMemcpyAsync(checked_out, d, bytes, hipMemcpyDeviceToHost, c->stream);
+        hipError_t e = hipMemcpyAsync(checked_out, d.at(), bytes, hipMemcpyDeviceToHost, c->stream);
         if (e == hipSuccess) e = hipStreamSynchronize(c->stream);
         if (e != hipSuccess) {
             (void)hipGetLastError();
             rc = set_err(c, ETHCNN_ERR_DEVICE, "search budget: %s", hipGetErrorString(e));
         }
     }
-    (void)hipFree(d);
     return rc;
 }
 }  // namespace
@@ -167,12 +150,11 @@ extern "C" int ethcnn_budget_companion_thr(ethcnn_sim_thr* out) {
 extern "C" int ethcnn_budget_choose(const uint32_t* checked, int64_t nframes, int64_t K, const uint64_t weight[4], uint32_t budget_ppm, int mode,
                                     int32_t* rung_out, uint8_t* over_out, uint64_t* cost_out, uint64_t* full_out) {
     if (nframes < 0 || (nframes && !checked) || !weight) return set_err(nullptr, ETHCNN_ERR_ARG, "ethcnn_budget_choose: null argument or negative frame count");
-    if (K < 1 || K > kMaxRungs) return set_err(nullptr, ETHCNN_ERR_ARG, "ethcnn_budget_choose: a ladder has 1..%d rungs: got %lld", kMaxRungs, (long long)K);
+    if (int rc = sim::check_rung_count(nullptr, K, "ethcnn_budget_choose: ")) return rc;
     if (budget_ppm > 1000000u) return set_err(nullptr, ETHCNN_ERR_ARG, "ethcnn_budget_choose: the budget is in parts per million, 0..1000000: got %u", budget_ppm);
     if (mode != ETHCNN_BUDGET_FRAME && mode != ETHCNN_BUDGET_CARRY)
         return set_err(nullptr, ETHCNN_ERR_ARG, "ethcnn_budget_choose: mode %d is neither ETHCNN_BUDGET_FRAME nor ETHCNN_BUDGET_CARRY", mode);
-    for (int d = 0; d < 4; ++d)
-        if (weight[d] >> 32) return set_err(nullptr, ETHCNN_ERR_ARG, "ethcnn_budget_choose: weight[%d] = %llu is not below 2^32", d, (unsigned long long)weight[d]);
+    if (int rc = sim::check_weights(nullptr, weight, "ethcnn_budget_choose: ")) return rc;
     std::vector<int32_t> rung((size_t)nframes);
     std::vector<uint8_t> over((size_t)nframes);
     std::vector<uint64_t> cost((size_t)nframes), full((size_t)nframes);
@@ -269,7 +251,7 @@ extern "C" int ethcnn_budget_control(ethcnn_sim* k, const ethcnn_sim_thr* ladder
         ladder = dflt.data();
         K = kDefaultRungs;
     }
-    if (!weight) weight = kDefaultWeight;
+    if (!weight) weight = sim::kDefaultWeight;
     int64_t per = 0;
     if (int rc = check_ladder(c, ladder, K)) return rc;
     if (int rc = check_window(k, first, width, height, nframes, &per)) return rc;

@@ -1,13 +1,13 @@
 // ethcnn_calib.cpp -- host side of the threshold calibrator (include/ethcnn.h "threshold calibration"): the calibrator object and its
 // add / get entries around the kernel of ethcnn_calib.hip, and the two context-free entries: the choice of the six thresholds from a
 // histogram and the Thr_info.txt writer.
-#include "ethcnn_ctx.h"
+#include "ethcnn_analysis.h"
 #include "ethcnn_calib.h"
 
 using namespace ethcnn::calib;
+using ethcnn::sim::kStageCtus;
 
 namespace {
-constexpr int64_t kStageCtus = 1 << 20;  // CTUs per staged piece of the host entries (100 MB of device memory)
 constexpr size_t kStateBytes = (size_t)(2 * kWords + 1) * 8;
 
 unsigned long long* acc_of(ethcnn_calib* k) { return k->d_state; }
@@ -43,8 +43,6 @@ int finish(ethcnn_calib* k) {
     return ETHCNN_OK;
 }
 
-int cus_of(const ethcnn_ctx* c) { return c->cus > 0 ? c->cus : 256; }
-
 // launches over n CTUs (per-CTU layout) or nframes frames (frame layout) that are in HBM
 hipError_t count_device(ethcnn_calib* k, const float* d_probs, const uint8_t* d_labels, int64_t n, const Geom& g) {
     ethcnn_ctx* c = k->c;
@@ -60,46 +58,23 @@ hipError_t count_device(ethcnn_calib* k, const float* d_probs, const uint8_t* d_
 }
 
 int calib_geom(ethcnn_ctx* c, int width, int height, Geom* g) {
-    if (width <= 0 || height <= 0 || width > 65536 || height > 65536 || width % 16 || height % 16)
-        return set_err(c, ETHCNN_ERR_ARG, "label files exist for sizes that are multiples of 16 (up to 65536): got %d x %d", width, height);
-    g->ctus_w = (width + 63) / 64;
-    g->ctus_h = (height + 63) / 64;
-    g->whole_w = width / 64;
-    g->whole_h = height / 64;
-    g->w16 = width / 16;
-    g->h16 = height / 16;
+    ethcnn::sim::PicSize s;
+    if (int rc = ethcnn::sim::check_size(c, width, height, 16, &s)) return rc;
+    *g = Geom{s.ctus_w, s.ctus_h, width / 64, height / 64, s.w16, s.h16};
     return 0;
 }
 
-// host pointers: pieces of `units` (CTUs, or frames) go through two device buffers; pb / lb = bytes of probabilities / labels per unit
+// host pointers: pieces of `units` (CTUs, or frames) go through a device buffer; pb / lb = bytes of probabilities / labels per unit
 int add_staged(ethcnn_calib* k, const float* probs, const uint8_t* labels, int64_t units, int64_t piece, int64_t pb, int64_t lb, const Geom& g) {
     ethcnn_ctx* c = k->c;
     if (int rc = begin(k)) return rc;
-    piece = std::min(piece, units);
-    uint8_t *d_p = nullptr, *d_l = nullptr;
-    if (hipMalloc((void**)&d_p, (size_t)(piece * pb)) != hipSuccess || hipMalloc((void**)&d_l, (size_t)(piece * lb)) != hipSuccess) {
-        (void)hipGetLastError();
-        if (d_p) (void)hipFree(d_p);
-        return set_err(c, ETHCNN_ERR_NOMEM, "calibration: %lld bytes of staging do not fit in device memory", (long long)(piece * (pb + lb)));
-    }
-    hipError_t e = hipSuccess;
-    for (int64_t at = 0; at < units && e == hipSuccess; at += piece) {
-        const int64_t m = std::min(piece, units - at);
-        // (the copies of the next piece wait, in stream order, for the launches that read this one)
-        e = hipMemcpyAsync(d_p, (const uint8_t*)probs + at * pb, (size_t)(m * pb), hipMemcpyHostToDevice, c->stream);
-        if (e == hipSuccess) e = hipMemcpyAsync(d_l, labels + at * lb, (size_t)(m * lb), hipMemcpyHostToDevice, c->stream);
-        if (e == hipSuccess) e = count_device(k, (const float*)d_p, d_l, m, g);
-    }
-    int rc = 0;
-    if (e != hipSuccess) {
-        discard(k);
-        rc = set_err(c, ETHCNN_ERR_DEVICE, "calibration: %s", hipGetErrorString(e));
-    } else {
-        rc = finish(k);
-    }
-    (void)hipFree(d_p);
-    (void)hipFree(d_l);
-    return rc;
+    Scratch stage;
+    const int rc = stage_pieces(c, stage, "calibration", probs, labels, units, piece, pb, lb, [&](const float* d_p, const uint8_t* d_l, int64_t m) {
+        const hipError_t e = count_device(k, d_p, d_l, m, g);
+        return e == hipSuccess ? 0 : set_err(c, ETHCNN_ERR_DEVICE, "calibration: %s", hipGetErrorString(e));
+    });
+    if (rc == ETHCNN_ERR_DEVICE) discard(k);
+    return rc ? rc : finish(k);
 }
 }  // namespace
 
@@ -221,7 +196,6 @@ extern "C" int ethcnn_calib_choose(const uint64_t* hist, const uint32_t eps_down
         if (eps_down_ppm[l] > 1000000u || eps_up_ppm[l] > 1000000u)
             return set_err(nullptr, ETHCNN_ERR_ARG, "ethcnn_calib_choose: a budget is in parts per million, 0..1000000 (level %d: %u / %u)", l + 1,
                            eps_down_ppm[l], eps_up_ppm[l]);
-    typedef unsigned __int128 u128;
     for (int l = 0; l < 3; ++l) {
         const uint64_t *h0 = hist + (size_t)(l * 2) * kBins, *h1 = h0 + kBins;
         // c0[k + 1] / c1[k + 1] = samples with bin <= k, k = -1 .. 1024
@@ -261,28 +235,13 @@ extern "C" int ethcnn_calib_choose(const uint64_t* hist, const uint32_t eps_down
     return ETHCNN_OK;
 }
 
-// HM-16.5_Test_AI/source/Lib/TLibEncoder/TEncCu.cpp:250       fscanf("%f %f %f %f %f %f", &fUp[0], &fDown[0], &fUp[1], &fDown[1], &fUp[2], &fDown[2])
-// HM-16.5_Test_LDP/source/Lib/TLibEncoder/TEncGOP.cpp:1449    fscanf("%f %f %f %f %f %f", &fDown[0], &fUp[0], &fDown[1], &fUp[1], &fDown[2], &fUp[2])
 int ethcnn::calib::write_thr_line(const char* path, const int32_t down_k[3], const int32_t up_k[3], int order, const char* entry) {
     if (order != ETHCNN_THR_ORDER_AI && order != ETHCNN_THR_ORDER_LDP)
         return set_err(nullptr, ETHCNN_ERR_ARG, "%s: order %d is neither ETHCNN_THR_ORDER_AI nor ETHCNN_THR_ORDER_LDP", entry, order);
-    double v[6];
-    for (int l = 0; l < 3; ++l) {
+    for (int l = 0; l < 3; ++l)
         if (down_k[l] < -1 || down_k[l] > 1024 || up_k[l] < 0 || up_k[l] > 1024)
             return set_err(nullptr, ETHCNN_ERR_ARG, "%s: level %d holds k = %d / %d outside -1..1024 / 0..1024", entry, l + 1, down_k[l], up_k[l]);
-        v[2 * l + (order == ETHCNN_THR_ORDER_AI ? 1 : 0)] = down_k[l] / 1024.0;
-        v[2 * l + (order == ETHCNN_THR_ORDER_AI ? 0 : 1)] = up_k[l] / 1024.0;
-    }
-    const std::string tmp = std::string(path) + ".tmp." + std::to_string((long)getpid());  // never a partial Thr_info.txt
-    FILE* f = std::fopen(tmp.c_str(), "w");
-    if (!f) return set_err(nullptr, ETHCNN_ERR_IO, "cannot open %s for writing: %s", tmp.c_str(), std::strerror(errno));
-    int rc = 0;
-    if (std::fprintf(f, "%.10f %.10f %.10f %.10f %.10f %.10f\n", v[0], v[1], v[2], v[3], v[4], v[5]) < 0)
-        rc = set_err(nullptr, ETHCNN_ERR_IO, "write to %s failed: %s", tmp.c_str(), std::strerror(errno));
-    if (std::fclose(f) != 0 && !rc) rc = set_err(nullptr, ETHCNN_ERR_IO, "close of %s failed", tmp.c_str());
-    if (!rc && std::rename(tmp.c_str(), path) != 0) rc = set_err(nullptr, ETHCNN_ERR_IO, "rename %s -> %s failed: %s", tmp.c_str(), path, std::strerror(errno));
-    if (rc) std::remove(tmp.c_str());
-    return rc;
+    return write_text_atomic(path, thr_line(down_k, up_k, order));
 }
 
 extern "C" int ethcnn_calib_write_thr_info(const char* path, const ethcnn_calib_report* rep, int order) {

@@ -1,14 +1,12 @@
 // ethcnn_decide.cpp -- host side of the partition decisions (include/ethcnn.h "partition decisions"): the entries around the kernel of
 // ethcnn_decide.hip over a simulator's set, and the host-only counters of a slice of codes.
-#include "ethcnn_ctx.h"
+#include "ethcnn_analysis.h"
 #include "ethcnn_decide.h"
-#include "ethcnn_sim.h"
 
 using namespace ethcnn::decide;
+using ethcnn::sim::kStageCtus;
 
 namespace {
-constexpr int64_t kStageCtus = 1 << 20;  // CTUs per staged piece of the host entry
-
 // everything of a call that does not depend on the layout: 0, or ETHCNN_ERR_ARG with the message set
 int check_call(ethcnn_sim* k, const ethcnn_sim_thr* thr, int gate_order, int mid_k, Cand* cand) {
     ethcnn_ctx* c = k->c;
@@ -71,18 +69,11 @@ extern "C" int ethcnn_decide(ethcnn_sim* k, const ethcnn_sim_thr* thr, int gate_
     HIPCHK(c, hipSetDevice(c->device));
     const int64_t piece = std::min(n, k->decide_piece > 0 ? k->decide_piece : kStageCtus);
     // a piece's outputs side by side in one buffer (each part a multiple of 16 bytes long but for the codes, which come last)
-    const int64_t need = piece * per;
-    size_t free_b = 0, total_b = 0;
-    HIPCHK(c, hipMemGetInfo(&free_b, &total_b));
-    uint8_t* d = nullptr;
-    if ((uint64_t)need > free_b || hipMalloc((void**)&d, (size_t)need) != hipSuccess) {
-        (void)hipGetLastError();
-        return set_err(c, ETHCNN_ERR_NOMEM, "partition decisions: %lld bytes of staging for %lld CTUs do not fit in device memory (%llu free)", (long long)need,
-                       (long long)piece, (unsigned long long)free_b);
-    }
-    uint8_t* d_reach = reach ? d : nullptr;
-    uint8_t* d_depth = depth ? d + (reach ? piece * kBlockBytes : 0) : nullptr;
-    uint8_t* d_codes = codes ? d + piece * (per - kCodeBytes) : nullptr;
+    Scratch d;
+    if (int rc = d.alloc(c, (size_t)(piece * per), "partition decisions", true)) return rc;
+    uint8_t* d_reach = reach ? d.at() : nullptr;
+    uint8_t* d_depth = depth ? d.at(reach ? piece * kBlockBytes : 0) : nullptr;
+    uint8_t* d_codes = codes ? d.at(piece * (per - kCodeBytes)) : nullptr;
     int rc = 0;
     for (int64_t at = 0; at < n && !rc; at += piece) {
         const int64_t cur = std::min(piece, n - at);
@@ -97,7 +88,6 @@ extern "C" int ethcnn_decide(ethcnn_sim* k, const ethcnn_sim_thr* thr, int gate_
             rc = set_err(c, ETHCNN_ERR_DEVICE, "partition decisions: %s", hipGetErrorString(e));
         }
     }
-    (void)hipFree(d);
     return rc;
 }
 
@@ -107,17 +97,15 @@ extern "C" int ethcnn_decide_frames_device(ethcnn_sim* k, const ethcnn_sim_thr* 
     ethcnn_ctx* c = k->c;
     Cand cand;
     if (int rc = check_call(k, thr, gate_order, mid_k, &cand)) return rc;
-    if (width <= 0 || height <= 0 || width > 65536 || height > 65536 || width % 8 || height % 8)
-        return set_err(c, ETHCNN_ERR_ARG, "HM pictures have sizes that are multiples of 8 (up to 65536): got %d x %d", width, height);
+    ethcnn::sim::PicSize s;
+    if (int rc = ethcnn::sim::check_size(c, width, height, 8, &s)) return rc;
     if (d_planes && (width % 16 || height % 16))
         return set_err(c, ETHCNN_ERR_ARG, "label planes exist for sizes that are multiples of 16: got %d x %d", width, height);
     if (first < 0 || nframes < 0) return set_err(c, ETHCNN_ERR_ARG, "negative first CTU or frame count");
     if (((uintptr_t)d_codes | (uintptr_t)d_reach) % 4) return set_err(c, ETHCNN_ERR_ARG, "device buffer not 4-byte aligned");
-    const int ctus_w = (width + 63) / 64, ctus_h = (height + 63) / 64;
-    const int64_t per = (int64_t)ctus_w * ctus_h;
     if (int rc = ethcnn::sim::check_frame_run(k, first, width, height, nframes)) return rc;
     if (nframes == 0) return ETHCNN_OK;
-    return run(k, cand, first, nframes * per, Planes{d_planes, ctus_w, ctus_h, width / 16, height / 16}, d_codes, d_reach, nullptr);
+    return run(k, cand, first, nframes * s.ctus(), Planes{d_planes, s.ctus_w, s.ctus_h, s.w16, s.h16}, d_codes, d_reach, nullptr);
 }
 
 extern "C" int ethcnn_decide_counts_from_codes(const uint8_t* codes, int64_t n, ethcnn_sim_counts* counts_out) {

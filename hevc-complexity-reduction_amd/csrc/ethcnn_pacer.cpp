@@ -1,20 +1,18 @@
 // ethcnn_pacer.cpp -- host side of the online search budget (include/ethcnn.h "search budget, online"): the pacer object around
 // k_pacer_frame (ethcnn_pacer.hip) and k_budget_bake (ethcnn_budget.hip), two launches a frame on the context's stream.
-#include "ethcnn_ctx.h"
+#include "ethcnn_analysis.h"
 #include "ethcnn_budget.h"
 #include "ethcnn_pacer.h"
-#include "ethcnn_sim.h"
 
 using namespace ethcnn::pacer;
 using ethcnn::budget::kDefaultRungs;
 using ethcnn::budget::kMaxFrameCtus;
-using ethcnn::budget::kMaxRungs;
 using ethcnn::budget::kNout;
 
 struct ethcnn_pacer {
     ethcnn_ctx* c = nullptr;
     int64_t K = 0;
-    uint64_t weight[4] = {64, 16, 4, 1};
+    uint64_t weight[4] = {};  // (set by ethcnn_pacer_create)
     uint32_t budget_ppm = 0;
     int mode = 0;
     int* d_thr = nullptr;          // [K + 1][6]: the ladder, then the full search
@@ -29,19 +27,14 @@ struct ethcnn_pacer {
 };
 
 namespace {
-typedef unsigned __int128 u128;
-const uint64_t kDefaultWeight[4] = {64, 16, 4, 1};
-
 // the rules of the ladder, the weights, the budget and the mode; c may be NULL (the message then goes where ethcnn_last_error(NULL) reads)
 int check_rules(ethcnn_ctx* c, const ethcnn_sim_thr* ladder, int64_t K, const uint64_t* weight, uint32_t budget_ppm, int mode) {
     if (ladder) {
-        if (K < 1 || K > kMaxRungs) return set_err(c, ETHCNN_ERR_ARG, "a ladder has 1..%d rungs: got %lld", kMaxRungs, (long long)K);
+        if (int rc = sim::check_rung_count(c, K)) return rc;
         for (int64_t i = 0; i < K; ++i)
-            if (int rc = ethcnn::sim::check_cand(c, ladder[i], (long long)i)) return rc;
+            if (int rc = sim::check_cand(c, ladder[i], (long long)i)) return rc;
     }
-    if (weight)
-        for (int d = 0; d < 4; ++d)
-            if (weight[d] >> 32) return set_err(c, ETHCNN_ERR_ARG, "weight[%d] = %llu is not below 2^32", d, (unsigned long long)weight[d]);
+    if (int rc = sim::check_weights(c, weight)) return rc;
     if (budget_ppm > 1000000u) return set_err(c, ETHCNN_ERR_ARG, "the budget is in parts per million, 0..1000000: got %u", budget_ppm);
     if (mode != ETHCNN_BUDGET_FRAME && mode != ETHCNN_BUDGET_CARRY)
         return set_err(c, ETHCNN_ERR_ARG, "mode %d is neither ETHCNN_BUDGET_FRAME nor ETHCNN_BUDGET_CARRY", mode);
@@ -51,13 +44,11 @@ int check_rules(ethcnn_ctx* c, const ethcnn_sim_thr* ladder, int64_t K, const ui
 // W, H and the cost bound of a frame; *per = its CTUs
 int check_frame(ethcnn_pacer* p, int width, int height, int64_t* per) {
     ethcnn_ctx* c = p->c;
-    if (width <= 0 || height <= 0 || width > 65536 || height > 65536 || width % 8 || height % 8)
-        return set_err(c, ETHCNN_ERR_ARG, "HM pictures have sizes that are multiples of 8 (up to 65536): got %d x %d", width, height);
-    *per = (int64_t)((width + 63) / 64) * ((height + 63) / 64);
+    sim::PicSize s;
+    if (int rc = sim::check_size(c, width, height, 8, &s)) return rc;
+    *per = s.ctus();
     if (*per >= kMaxFrameCtus) return set_err(c, ETHCNN_ERR_ARG, "a frame of %lld CTUs does not count in 32 bits (fewer than 2^24)", (long long)*per);
-    // a CTU has at most 1, 4, 16 and 64 checked CUs of the four sizes: the largest cost any rung can have on this frame
-    const u128 bound = (u128)*per * ((u128)p->weight[0] + (u128)4 * p->weight[1] + (u128)16 * p->weight[2] + (u128)64 * p->weight[3]);
-    if (bound >> 64) return set_err(c, ETHCNN_ERR_ARG, "the cost of a frame of %lld CTUs may not fit in 64 bits under these weights", (long long)*per);
+    if (!sim::cost_fits(*per, p->weight)) return set_err(c, ETHCNN_ERR_ARG, "the cost of a frame of %lld CTUs may not fit in 64 bits under these weights", (long long)*per);
     return 0;
 }
 
@@ -126,7 +117,7 @@ extern "C" int ethcnn_pacer_create(ethcnn_ctx* c, const ethcnn_sim_thr* ladder, 
         lad.resize(kDefaultRungs);
         ethcnn_budget_default_ladder(lad.data());
     }
-    lad.push_back(ethcnn_sim_thr{{1024, 1024, 1024}, {-1, -1, -1}});  // rung K: the full search
+    lad.push_back(sim::kFullSearch);  // rung K
     std::vector<int> rows;
     for (const ethcnn_sim_thr& t : lad) {
         for (int l = 0; l < 3; ++l) rows.push_back(t.up_k[l]);
@@ -136,7 +127,7 @@ extern "C" int ethcnn_pacer_create(ethcnn_ctx* c, const ethcnn_sim_thr* ladder, 
     ethcnn_pacer* p = new ethcnn_pacer;
     p->c = c;
     p->K = (int64_t)lad.size() - 1;
-    for (int d = 0; d < 4; ++d) p->weight[d] = (weight ? weight : kDefaultWeight)[d];
+    for (int d = 0; d < 4; ++d) p->weight[d] = (weight ? weight : sim::kDefaultWeight)[d];
     p->budget_ppm = budget_ppm;
     p->mode = mode;
     const size_t n = lad.size();

@@ -1,12 +1,11 @@
 // ethcnn_replay.cpp -- host side of the sample-set replay (include/ethcnn.h "sample-set replay"): the plan (runs, their validation, the
 // source table), the replay object (open, memory plan, the chunk loop uncut -> ethcnn_ldp_sequence_device) and the two hand-offs to the
 // calibrator and the partition-search simulator.  Kernels: ethcnn_replay.hip.
-#include "ethcnn_ctx.h"
+#include "ethcnn_analysis.h"
 #include "ethcnn_calib.h"
 #include "ethcnn_ldp_group.h"
 #include "ethcnn_replay.h"
 #include "ethcnn_samples.h"
-#include "ethcnn_sim.h"
 
 #include <unordered_map>
 
@@ -193,8 +192,6 @@ int rerr(ethcnn_replay* p, int code, const char* fmt, ...) {
     p->err = buf;
     return code;
 }
-
-int cus_of(const ethcnn_ctx* c) { return c->cus > 0 ? c->cus : 256; }
 
 void fill_run(const Run& r, ethcnn_replay_run* o) {
     o->seq = r.seq;

@@ -1,17 +1,12 @@
 // ethcnn_sim.cpp -- host side of the partition-search simulator (include/ethcnn.h "partition-search simulation"): the set object, its
 // add / eval entries around the kernels of ethcnn_sim.hip, and the sweep and the coordinate-descent search built from evaluations.
-#include "ethcnn_ctx.h"
+#include "ethcnn_analysis.h"
 #include "ethcnn_calib.h"
-#include "ethcnn_sim.h"
 
 using namespace ethcnn::sim;
 
 namespace {
-constexpr int64_t kStageCtus = 1 << 20;  // CTUs per staged piece of the host entries
 constexpr int64_t kMaxCand = 1 << 26;
-typedef unsigned __int128 u128;
-
-int cus_of(const ethcnn_ctx* c) { return c->cus > 0 ? c->cus : 256; }
 
 // room for `ctus` more records and `subs` more sub-batches; the set's content moves to the new buffers, nothing else changes
 int reserve(ethcnn_sim* k, int64_t ctus, int64_t subs) {
@@ -113,42 +108,20 @@ struct Add {
     }
 };
 
-// host pointers: pieces of `piece` units go through two device buffers; pb / lb = bytes of probabilities / labels per unit
+// host pointers: pieces of `piece` units go through a device buffer; pb / lb = bytes of probabilities / labels per unit
 int add_staged(Add& a, const float* probs, const uint8_t* labels, int64_t units, int64_t piece, int64_t pb, int64_t lb) {
-    ethcnn_ctx* c = a.k->c;
     if (int rc = a.begin(units)) return rc;
-    piece = std::min(piece, units);
-    uint8_t *d_p = nullptr, *d_l = nullptr;
-    if (hipMalloc((void**)&d_p, (size_t)(piece * pb)) != hipSuccess || (labels && hipMalloc((void**)&d_l, (size_t)(piece * lb)) != hipSuccess)) {
-        (void)hipGetLastError();
-        if (d_p) (void)hipFree(d_p);
-        return set_err(c, ETHCNN_ERR_NOMEM, "simulation: %lld bytes of staging do not fit in device memory", (long long)(piece * (pb + (labels ? lb : 0))));
-    }
-    int rc = 0;
-    for (int64_t at = 0; at < units && !rc; at += piece) {
-        const int64_t m = std::min(piece, units - at);
-        hipError_t e = hipMemcpyAsync(d_p, (const uint8_t*)probs + at * pb, (size_t)(m * pb), hipMemcpyHostToDevice, c->stream);
-        if (e == hipSuccess && labels) e = hipMemcpyAsync(d_l, labels + at * lb, (size_t)(m * lb), hipMemcpyHostToDevice, c->stream);
-        rc = e != hipSuccess ? set_err(c, ETHCNN_ERR_DEVICE, "simulation: %s", hipGetErrorString(e)) : a.pack((const float*)d_p, d_l, m);
-    }
-    if (!rc) rc = a.commit();
-    (void)hipFree(d_p);
-    if (d_l) (void)hipFree(d_l);
-    return rc;
+    Scratch stage;
+    if (int rc = stage_pieces(a.k->c, stage, "simulation", probs, labels, units, piece, pb, lb,
+                              [&](const float* d_p, const uint8_t* d_l, int64_t m) { return a.pack(d_p, d_l, m); }))
+        return rc;
+    return a.commit();
 }
 
 int sim_geom(ethcnn_ctx* c, int width, int height, bool labels, Geom* g) {
-    const int unit = labels ? 16 : 8;
-    if (width <= 0 || height <= 0 || width > 65536 || height > 65536 || width % unit || height % unit)
-        return set_err(c, ETHCNN_ERR_ARG, "%s (up to 65536): got %d x %d",
-                       labels ? "label files exist for sizes that are multiples of 16" : "HM pictures have sizes that are multiples of 8", width, height);
-    g->ctus_w = (width + 63) / 64;
-    g->ctus_h = (height + 63) / 64;
-    g->width = width;
-    g->height = height;
-    g->w16 = width / 16;
-    g->h16 = height / 16;
-    g->subs = (g->ctus_w * g->ctus_h + 1023) / 1024;
+    PicSize s;
+    if (int rc = check_size(c, width, height, labels ? 16 : 8, &s)) return rc;
+    *g = Geom{s.ctus_w, s.ctus_h, width, height, s.w16, s.h16, (s.ctus_w * s.ctus_h + 1023) / 1024};
     return 0;
 }
 
@@ -160,33 +133,6 @@ u128 cost_of(const ethcnn_sim_counts& n, const uint64_t weight[4]) {
     return v;
 }
 }  // namespace
-
-namespace ethcnn {
-namespace sim {
-int check_cand(ethcnn_ctx* c, const ethcnn_sim_thr& t, long long at) {
-    for (int l = 0; l < 3; ++l)
-        if (t.up_k[l] < 0 || t.up_k[l] > 1024 || t.down_k[l] < -1 || t.down_k[l] > 1024)
-            return set_err(c, ETHCNN_ERR_ARG, "candidate %lld, level %d: up_k = %d / down_k = %d outside 0..1024 / -1..1024", at, l + 1, t.up_k[l], t.down_k[l]);
-    return 0;
-}
-
-int check_gates(ethcnn_ctx* c, int gate_order) {
-    if (gate_order != ETHCNN_SIM_GATES_NONE && gate_order != ETHCNN_SIM_GATES_AI && gate_order != ETHCNN_SIM_GATES_LDP)
-        return set_err(c, ETHCNN_ERR_ARG, "gate order %d is none of ETHCNN_SIM_GATES_NONE / _AI / _LDP", gate_order);
-    return 0;
-}
-
-int check_frame_run(ethcnn_sim* k, int64_t first, int width, int height, int64_t nframes) {
-    const int64_t per = (int64_t)((width + 63) / 64) * ((height + 63) / 64);
-    for (const FrameRun& r : k->runs)
-        if (r.width == width && r.height == height && first >= r.first && (first - r.first) % per == 0 && (first - r.first) / per <= r.nframes &&
-            nframes <= r.nframes - (first - r.first) / per)
-            return 0;
-    return set_err(k->c, ETHCNN_ERR_ARG, "CTU %lld + %lld frames do not lie on the frame boundaries of CTUs added as %d x %d frames", (long long)first,
-                   (long long)nframes, width, height);
-}
-}  // namespace sim
-}  // namespace ethcnn
 
 extern "C" int ethcnn_sim_create(ethcnn_ctx* c, ethcnn_sim** out) {
     if (!c) return ETHCNN_ERR_ARG;

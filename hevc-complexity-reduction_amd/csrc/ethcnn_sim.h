@@ -57,24 +57,7 @@ struct FrameRun {
 }  // namespace ethcnn
 
 struct ethcnn_ctx;
-struct ethcnn_sim_thr;
-namespace ethcnn {
-namespace sim {
-// the argument rules of a candidate and of a gate order (ethcnn_sim.cpp); 0, or ETHCNN_ERR_ARG with the message set
-int check_cand(ethcnn_ctx* c, const ethcnn_sim_thr& t, long long at);
-int check_gates(ethcnn_ctx* c, int gate_order);
-}  // namespace sim
-}  // namespace ethcnn
-
-struct ethcnn_sim;
-namespace ethcnn {
-namespace sim {
-// the window rule of the frame forms (ethcnn_decide_frames_device, ethcnn_budget_*): nframes whole frames from CTU `first` on lie
-// inside one run of width x height frames, `first` on a frame boundary of it; 0, or ETHCNN_ERR_ARG with the message set
-int check_frame_run(ethcnn_sim* k, int64_t first, int width, int height, int64_t nframes);
-}  // namespace sim
-}  // namespace ethcnn
-
+// (the argument rules of the host side: ethcnn_analysis.h)
 struct ethcnn_sim {
     ethcnn_ctx* c = nullptr;
     unsigned* d_recs = nullptr;  // [cap_ctus][16]

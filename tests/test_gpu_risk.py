@@ -259,6 +259,24 @@ def test_the_small_set_whole_path_and_short_ladders(pkg, sim):
     _same(sim.build_ladder_risk(weights, grid=64), _want("small", "identity", weights, 64))
 
 
+def test_both_walks_back_to_back_on_one_simulator_share_no_state(pkg, sim):
+    """The two builds run through one host walk.  Same weights, grid 8 and 65 rungs (one past a batch of 64 steps, so each build looks at
+    the state block twice): the labelled ladder, the ladder by risk and the labelled one again on one simulator.  Anything one walk left
+    behind for the other -- state words, table rows of the other width, rungs of the other size -- would change a rung."""
+    _fill(sim, "frames")
+    _table(pkg, "identity")
+    first = sim.build_ladder(grid=8, max_rungs=65)
+    by_risk = sim.build_ladder_risk(grid=8, max_rungs=65)
+    again = sim.build_ladder(grid=8, max_rungs=65)
+    for k in ("thr", "coord", "value", "checked", "bad_ctus"):
+        assert first[k].tobytes() == again[k].tobytes(), k
+    assert [int(x) for x in first["cost"]] == [int(x) for x in again["cost"]]
+    tl._same(first, tl._want("frames", None, 8, 65))
+    tl._same(again, tl._want("frames", None, 8, 65))
+    _same(by_risk, _want("frames", "identity", None, 8, 65))
+    assert len(first["cost"]) == len(by_risk["cost"]) == 65                          # both paths are longer: the cut is the second batch's
+
+
 def test_the_cap_takes_moves_away(pkg, sim):
     s = _fill(sim, "frames")
     _table(pkg, "identity")
