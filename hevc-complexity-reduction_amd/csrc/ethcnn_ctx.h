@@ -226,6 +226,8 @@ struct ethcnn_ctx {
     double guard_bound[4] = {0, 0, 0, 0};       // a-priori worst case of a probability's error (ethcnn_spec.h::fast_plan_floor_bound)
     double guard_measured[4] = {-1, -1, -1, -1}; // max |dp| vs the exact plan on the calibration picture; < 0: not measured (the bound sufficed)
     FastGuard guard_info[4] = {};
+    long guard_nonfinite = -1;                  // index of the first weight that is not finite, found by the guard (-1: none): such weights are refused unmeasured
+    const char* guard_bad_scale[4] = {nullptr, nullptr, nullptr, nullptr};  // the plan's scale that is not a normal float (static text), or null: refused unmeasured
     int last_fast = 0;       // the FC1 plan of the last pass (debug_fetch reads the features of plans 1 / 2 from ws.featb)
     unsigned long passes = 0, fast_passes = 0;  // passes enqueued by run_pass / of those, the ones with last_fast != 0 (ethcnn_audit.cpp reads the difference)
     bool ws_foreign = false;                    // the workspace holds an audit's last pass, not the caller's: ethcnn_debug_fetch refuses until the next pass

@@ -142,10 +142,10 @@ __device__ __forceinline__ void head_pass_f16(char* smem, const float* __restric
     for (int j = 0; j < NT; ++j) {
         const f32x4 wq = __builtin_bit_cast(f32x4, __builtin_amdgcn_raw_buffer_load_b128(rW2, 16 * g, (D::N1 * D::N2 + 16 * j) * 4, 0));
         const f32x4 bv = __builtin_bit_cast(f32x4, __builtin_amdgcn_raw_buffer_load_b128(rB2, 16 * g, 64 * j, 0));
-        acc[j][0] = lrelu_h(fmaf(fmaf(cor[j][0], kResidualUnscale, acc[j][0]), U2, fmaf(qn, wq.x, bv.x)));
-        acc[j][1] = lrelu_h(fmaf(fmaf(cor[j][1], kResidualUnscale, acc[j][1]), U2, fmaf(qn, wq.y, bv.y)));
-        acc[j][2] = lrelu_h(fmaf(fmaf(cor[j][2], kResidualUnscale, acc[j][2]), U2, fmaf(qn, wq.z, bv.z)));
-        acc[j][3] = lrelu_h(fmaf(fmaf(cor[j][3], kResidualUnscale, acc[j][3]), U2, fmaf(qn, wq.w, bv.w)));
+        acc[j][0] = canon_lrelu(fmaf(fmaf(cor[j][0], kResidualUnscale, acc[j][0]), U2, fmaf(qn, wq.x, bv.x)));
+        acc[j][1] = canon_lrelu(fmaf(fmaf(cor[j][1], kResidualUnscale, acc[j][1]), U2, fmaf(qn, wq.y, bv.y)));
+        acc[j][2] = canon_lrelu(fmaf(fmaf(cor[j][2], kResidualUnscale, acc[j][2]), U2, fmaf(qn, wq.z, bv.z)));
+        acc[j][3] = canon_lrelu(fmaf(fmaf(cor[j][3], kResidualUnscale, acc[j][3]), U2, fmaf(qn, wq.w, bv.w)));
         if (valid && h2row) *reinterpret_cast<f32x4*>(h2row + D::O2 + 16 * j + 4 * g) = acc[j];
     }
     // FC3^T: rows = outputs (n3 of 16 used), columns = CTUs; step p consumes the quads of tiles 2 p, 2 p + 1
@@ -169,7 +169,7 @@ __device__ __forceinline__ void head_pass_f16(char* smem, const float* __restric
         const int o = 4 * g + r;
         if (o < D::N3 && valid) {
             const float zz = fmaf(z[r], U3, fmaf(qn, W3[D::N2 * D::N3 + o], hp.b3[H][o]));
-            const float p = 1.0f / (1.0f + expf_canonical_h(-zz));
+            const float p = canon_sigmoid(zz);
             const size_t idx = (size_t)ctu * kNOut + D::O3 + o;
             if (logits) logits[idx] = zz;  // introspection copies (ethcnn_set_debug_capture), null in production
             if (raw) raw[idx] = p;

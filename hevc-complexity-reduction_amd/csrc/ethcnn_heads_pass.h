@@ -4,31 +4,13 @@
 #pragma once
 #include <hip/hip_runtime.h>
 
+#include "ethcnn_canon_math.h"  // canon_lrelu, canon_sigmoid
 #include "ethcnn_fc1_tile.h"  // typedefs, MFMA16, kAuxSc1
 #include "ethcnn_kernels.h"
 
 namespace ethcnn {
 
 typedef unsigned int u32x4 __attribute__((ext_vector_type(4)));
-
-__device__ __forceinline__ float lrelu_h(float h) { return fmaxf(0.2f * h, h); }
-
-__device__ __forceinline__ float expf_canonical_h(float x) {
-    x = fminf(x, 80.0f);
-    x = fmaxf(x, -86.0f);
-    const float n = rintf(x * 1.44269504088896341f);
-    float r = fmaf(n, -0.693145751953125f, x);
-    r = fmaf(n, -1.42860682030941723212e-6f, r);
-    float p = 1.0f / 5040.0f;
-    p = fmaf(p, r, 1.0f / 720.0f);
-    p = fmaf(p, r, 1.0f / 120.0f);
-    p = fmaf(p, r, 1.0f / 24.0f);
-    p = fmaf(p, r, 1.0f / 6.0f);
-    p = fmaf(p, r, 0.5f);
-    p = fmaf(p, r, 1.0f);
-    p = fmaf(p, r, 1.0f);
-    return __int_as_float(__float_as_int(p) + (((int)n) << 23));
-}
 
 #ifdef HEADS_STAMPS
 // development probe (scripts/ubench/heads_probe.hip): stamps of wave 0 of every block -- s_memtime (shader clock, per
@@ -195,10 +177,10 @@ __device__ __forceinline__ void head_pass(float* smem, const float* __restrict__
         const int n = 16 * j + 4 * g;
         const f32x4 wq = __builtin_bit_cast(f32x4, __builtin_amdgcn_raw_buffer_load_b128(rW2, 16 * g, (D::N1 * D::N2 + 16 * j) * 4, 0));
         const f32x4 bv = __builtin_bit_cast(f32x4, __builtin_amdgcn_raw_buffer_load_b128(rB2, 16 * g, 64 * j, 0));
-        acc[j][0] = lrelu_h(fmaf(qn, wq.x, acc[j][0]) + bv.x);
-        acc[j][1] = lrelu_h(fmaf(qn, wq.y, acc[j][1]) + bv.y);
-        acc[j][2] = lrelu_h(fmaf(qn, wq.z, acc[j][2]) + bv.z);
-        acc[j][3] = lrelu_h(fmaf(qn, wq.w, acc[j][3]) + bv.w);
+        acc[j][0] = canon_lrelu(fmaf(qn, wq.x, acc[j][0]) + bv.x);
+        acc[j][1] = canon_lrelu(fmaf(qn, wq.y, acc[j][1]) + bv.y);
+        acc[j][2] = canon_lrelu(fmaf(qn, wq.z, acc[j][2]) + bv.z);
+        acc[j][3] = canon_lrelu(fmaf(qn, wq.w, acc[j][3]) + bv.w);
         if (valid && h2row) *reinterpret_cast<f32x4*>(h2row + D::O2 + n) = acc[j];
     }
     // FC3^T: rows = outputs (N3 of 16 used), columns = CTUs; step (j, r) consumes k = 16 j + 4 g + r
@@ -228,7 +210,7 @@ __device__ __forceinline__ void head_pass(float* smem, const float* __restrict__
         const int o = 4 * g + r;
         if (o < D::N3 && valid) {
             const float zz = fmaf(qn, W3[D::N2 * D::N3 + o], z[r]) + hp.b3[H][o];
-            const float p = 1.0f / (1.0f + expf_canonical_h(-zz));
+            const float p = canon_sigmoid(zz);
             const size_t idx = (size_t)ctu * kNOut + D::O3 + o;
             if (logits) logits[idx] = zz;  // introspection copies (ethcnn_set_debug_capture), null in production
             if (raw) raw[idx] = p;
@@ -334,10 +316,10 @@ __device__ __forceinline__ void head_pass_regs(float* smem, const float* __restr
         const int j = j0 + jj;
         if (j < D::NT) {  // wave-uniform
             f32x4 a = acc[jj];
-            a[0] = lrelu_h(fmaf(qn, wq[jj].x, a[0]) + bv[jj].x);
-            a[1] = lrelu_h(fmaf(qn, wq[jj].y, a[1]) + bv[jj].y);
-            a[2] = lrelu_h(fmaf(qn, wq[jj].z, a[2]) + bv[jj].z);
-            a[3] = lrelu_h(fmaf(qn, wq[jj].w, a[3]) + bv[jj].w);
+            a[0] = canon_lrelu(fmaf(qn, wq[jj].x, a[0]) + bv[jj].x);
+            a[1] = canon_lrelu(fmaf(qn, wq[jj].y, a[1]) + bv[jj].y);
+            a[2] = canon_lrelu(fmaf(qn, wq[jj].z, a[2]) + bv[jj].z);
+            a[3] = canon_lrelu(fmaf(qn, wq[jj].w, a[3]) + bv[jj].w);
             if (valid && h2row) *reinterpret_cast<f32x4*>(h2row + D::O2 + 16 * j + 4 * g) = a;
             h2T[j * 64 + lane] = a;
         }
@@ -356,7 +338,7 @@ __device__ __forceinline__ void head_pass_regs(float* smem, const float* __restr
         const int o = 4 * g + r;
         if (o < D::N3 && valid) {
             const float zz = fmaf(qn, w3p[r], z[r]) + b3v[r];
-            const float p = 1.0f / (1.0f + expf_canonical_h(-zz));
+            const float p = canon_sigmoid(zz);
             const size_t idx = (size_t)ctu * kNOut + D::O3 + o;
             if (logits) logits[idx] = zz;
             if (raw) raw[idx] = p;
@@ -477,10 +459,10 @@ __device__ __forceinline__ void head_pass_split(float* smem, const float* __rest
             const f32x4 wq = __builtin_bit_cast(f32x4, __builtin_amdgcn_raw_buffer_load_b128(rW2, 16 * g, (D::N1 * D::N2 + 16 * j) * 4, 0));
             const f32x4 bv = __builtin_bit_cast(f32x4, __builtin_amdgcn_raw_buffer_load_b128(rB2, 16 * g, 64 * j, 0));
             f32x4 a = acc[jj];
-            a[0] = lrelu_h(fmaf(qn, wq.x, a[0]) + bv.x);
-            a[1] = lrelu_h(fmaf(qn, wq.y, a[1]) + bv.y);
-            a[2] = lrelu_h(fmaf(qn, wq.z, a[2]) + bv.z);
-            a[3] = lrelu_h(fmaf(qn, wq.w, a[3]) + bv.w);
+            a[0] = canon_lrelu(fmaf(qn, wq.x, a[0]) + bv.x);
+            a[1] = canon_lrelu(fmaf(qn, wq.y, a[1]) + bv.y);
+            a[2] = canon_lrelu(fmaf(qn, wq.z, a[2]) + bv.z);
+            a[3] = canon_lrelu(fmaf(qn, wq.w, a[3]) + bv.w);
             if (valid && h2row) *reinterpret_cast<f32x4*>(h2row + D::O2 + 16 * j + 4 * g) = a;
             h2T[j * 64 + lane] = a;
         }
@@ -499,7 +481,7 @@ __device__ __forceinline__ void head_pass_split(float* smem, const float* __rest
         const int o = 4 * g + r;
         if (o < D::N3 && valid) {
             const float zz = fmaf(qn, W3[D::N2 * D::N3 + o], z[r]) + hp.b3[H][o];
-            const float p = 1.0f / (1.0f + expf_canonical_h(-zz));
+            const float p = canon_sigmoid(zz);
             const size_t idx = (size_t)ctu * kNOut + D::O3 + o;
             if (logits) logits[idx] = zz;
             if (raw) raw[idx] = p;

@@ -19,6 +19,7 @@
 
 #include <cstdlib>
 
+#include "ethcnn_canon_math.h"  // canon_lrelu / canon_sigmoid / canon_tanh: the canonical functions of DESIGN.md section 2
 #include "ethcnn_kernels.h"
 
 namespace ethcnn {
@@ -38,29 +39,6 @@ __device__ __forceinline__ void lstm_stamp(int kernel, int slot) {
 #else
 #define LSTM_STAMP(k, i)
 #endif
-
-__device__ __forceinline__ float lrelu_l(float h) { return fmaxf(0.2f * h, h); }
-__device__ __forceinline__ float expf_l(float x) {  // the canonical exp of DESIGN.md
-    x = fminf(x, 80.0f);
-    x = fmaxf(x, -86.0f);
-    const float n = rintf(x * 1.44269504088896341f);
-    float r = fmaf(n, -0.693145751953125f, x);
-    r = fmaf(n, -1.42860682030941723212e-6f, r);
-    float p = 1.0f / 5040.0f;
-    p = fmaf(p, r, 1.0f / 720.0f);
-    p = fmaf(p, r, 1.0f / 120.0f);
-    p = fmaf(p, r, 1.0f / 24.0f);
-    p = fmaf(p, r, 1.0f / 6.0f);
-    p = fmaf(p, r, 0.5f);
-    p = fmaf(p, r, 1.0f);
-    p = fmaf(p, r, 1.0f);
-    return __int_as_float(__float_as_int(p) + (((int)n) << 23));
-}
-__device__ __forceinline__ float sigmoid_l(float z) { return 1.0f / (1.0f + expf_l(-z)); }
-__device__ __forceinline__ float tanh_l(float x) {
-    const float e = expf_l(2.0f * x);
-    return (e - 1.0f) / (e + 1.0f);
-}
 
 struct LstmParams {
     const float* blob;  // the TF-V2 .data payload of model_LDP_200000_qpXX.dat, as stored
@@ -176,9 +154,9 @@ __device__ __forceinline__ void lstm_cell(const LstmParams& lp, const float* __r
         const float* xf = reinterpret_cast<const float*>(xch + c * 256) + lane * 4 + q;
         const float gi = xf[0] + b_i, gj = xf[256] + b_j, gf = xf[512] + b_f, go = xf[768] + b_o;
         const float cp = cprev[c];
-        float cc = sigmoid_l(gf + 1.0f) * cp + sigmoid_l(gi) * tanh_l(gj);
+        float cc = canon_sigmoid(gf + 1.0f) * cp + canon_sigmoid(gi) * canon_tanh(gj);
         cc = fminf(fmaxf(cc, -5.0f), 5.0f);
-        const float hn = sigmoid_l(go) * tanh_l(cc);
+        const float hn = canon_sigmoid(go) * canon_tanh(cc);
         if (valid[c]) {
             float* so = state_out + row[c] * 2 * kNVec;
             if (COH) {
@@ -282,7 +260,7 @@ __device__ __forceinline__ void lstm_heads(const LstmParams& lp, const float* __
             float v = a2[r];
 #pragma unroll
             for (int e = 0; e < 5; ++e) v = fmaf(lp.efs[e], we[r][e], v);
-            a2[r] = lrelu_l(v + b2v[r]);
+            a2[r] = canon_lrelu(v + b2v[r]);
         }
         h2T[(j * 4 + g) * 16 + col] = a2;
     }
@@ -307,7 +285,7 @@ __device__ __forceinline__ void lstm_heads(const LstmParams& lp, const float* __
                 float zz = z[r];
 #pragma unroll
                 for (int e = 0; e < 5; ++e) zz = fmaf(lp.efs[e], w3e[r][e], zz);
-                const float p = sigmoid_l(zz + b3v[r]);
+                const float p = canon_sigmoid(zz + b3v[r]);
                 const size_t idx = (size_t)ctu * kNOut + O3 + o;
                 if (raw) raw[idx] = p;
                 // agent-scope store (written through the XCD's L2): the block that applies the gates may run on another XCD
@@ -628,7 +606,7 @@ __device__ __forceinline__ void lstm_frame_heads(const LstmFrameParams& P, const
                 float v = a[r];
 #pragma unroll
                 for (int e = 0; e < 5; ++e) v = fmaf(P.lp.efs[e], sE[e * N2 + idx], v);
-                a[r] = lrelu_l(v + sB2[idx]);
+                a[r] = canon_lrelu(v + sB2[idx]);
             }
             h2T[(j * 4 + gq) * 16 + col] = a;
         }
@@ -652,7 +630,7 @@ __device__ __forceinline__ void lstm_frame_heads(const LstmFrameParams& P, const
                 float zz = z[r];
 #pragma unroll
                 for (int e = 0; e < 5; ++e) zz = fmaf(P.lp.efs[e], sW3[(N2 + e) * N3 + o], zz);
-                const float p = sigmoid_l(zz + sB3[o]);
+                const float p = canon_sigmoid(zz + sB3[o]);
                 const size_t idx = (size_t)ctu * kNOut + O3 + o;
                 if (P.raw) P.raw[idx] = p;
                 __hip_atomic_store(&P.probs[idx], p, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);

@@ -15,6 +15,7 @@
 // Per frame: three workgroup barriers, no flag, no spin-wait, no claim word, no atomic.  Bit-identical to the per-frame path.
 #include <hip/hip_runtime.h>
 
+#include "ethcnn_canon_math.h"
 #include "ethcnn_kernels.h"
 #include "ethcnn_lstm_seq.h"
 #include "ethcnn_spec.h"
@@ -24,32 +25,8 @@ namespace ethcnn {
 typedef float f32x4 __attribute__((ext_vector_type(4)));
 #define MFMA16(a, b, c) __builtin_amdgcn_mfma_f32_16x16x4f32((a), (b), (c), 0, 0, 0)
 
-// ---- TWINS of ethcnn_lstm.hip (which this change leaves untouched, so they are not yet shared through a header): lrelu_l / expf_l /
-// sigmoid_l / tanh_l, kLstmOff and LstmDims there are the same code as sq_* / kSeqOff / SeqDims here.  The operation sequence is the
-// contract with the oracle: whoever changes one copy changes the other; tests/test_gpu_ldp_sequence.py compares
-// the two paths bit for bit on every level.
-__device__ __forceinline__ float sq_lrelu(float h) { return fmaxf(0.2f * h, h); }
-__device__ __forceinline__ float sq_exp(float x) {
-    x = fminf(x, 80.0f);
-    x = fmaxf(x, -86.0f);
-    const float n = rintf(x * 1.44269504088896341f);
-    float r = fmaf(n, -0.693145751953125f, x);
-    r = fmaf(n, -1.42860682030941723212e-6f, r);
-    float p = 1.0f / 5040.0f;
-    p = fmaf(p, r, 1.0f / 720.0f);
-    p = fmaf(p, r, 1.0f / 120.0f);
-    p = fmaf(p, r, 1.0f / 24.0f);
-    p = fmaf(p, r, 1.0f / 6.0f);
-    p = fmaf(p, r, 0.5f);
-    p = fmaf(p, r, 1.0f);
-    p = fmaf(p, r, 1.0f);
-    return __int_as_float(__float_as_int(p) + (((int)n) << 23));
-}
-__device__ __forceinline__ float sq_sigmoid(float z) { return 1.0f / (1.0f + sq_exp(-z)); }
-__device__ __forceinline__ float sq_tanh(float x) {
-    const float e = sq_exp(2.0f * x);
-    return (e - 1.0f) / (e + 1.0f);
-}
+// The activation functions are the shared canonical ones (ethcnn_canon_math.h).  ---- TWINS of ethcnn_lstm.hip: kLstmOff and LstmDims
+// there are the same tables as kSeqOff / SeqDims here; tests/test_gpu_ldp_sequence.py compares the two paths bit for bit on every level.
 
 // float offsets into the blob per level (64, 32, 16): fc2_b, fc2_w, fc3_b, fc3_w, bias (the table of ethcnn_lstm.hip)
 __device__ __constant__ int kSeqOff[3][5] = {{723640, 723688, 727000, 727001, 727054},
@@ -188,10 +165,10 @@ __device__ __forceinline__ void lstm_seq_level(const SeqParams& P, int blk, f32x
 #pragma unroll
         for (int r = 0; r < 4; ++r) {
             const float gi = acc[0][r] + bias[0][r], gj = acc[1][r] + bias[1][r], gf = acc[2][r] + bias[2][r], go = acc[3][r] + bias[3][r];
-            float cc = sq_sigmoid(gf + 1.0f) * cst[r] + sq_sigmoid(gi) * sq_tanh(gj);
+            float cc = canon_sigmoid(gf + 1.0f) * cst[r] + canon_sigmoid(gi) * canon_tanh(gj);
             cc = fminf(fmaxf(cc, -5.0f), 5.0f);
             cst[r] = cc;
-            hlast[r] = sq_sigmoid(go) * sq_tanh(cc);
+            hlast[r] = canon_sigmoid(go) * canon_tanh(cc);
         }
         hnew[t * 64 + lane] = hlast;
 
@@ -228,7 +205,7 @@ __device__ __forceinline__ void lstm_seq_level(const SeqParams& P, int blk, f32x
                 float v = a2[r];
 #pragma unroll
                 for (int e = 0; e < 5; ++e) v = fmaf(e == 0 ? efs[0] : (e - 1 == phase ? 1.0f : 0.0f), we[r][e], v);
-                a2[r] = sq_lrelu(v + b2v[r]);
+                a2[r] = canon_lrelu(v + b2v[r]);
             }
             h2T[t * 64 + lane] = a2;
         }
@@ -250,7 +227,7 @@ __device__ __forceinline__ void lstm_seq_level(const SeqParams& P, int blk, f32x
                     float zz = z[r];
 #pragma unroll
                     for (int e = 0; e < 5; ++e) zz = fmaf(e == 0 ? efs[0] : (e - 1 == phase ? 1.0f : 0.0f), sW3[(N2 + e) * N3 + o], zz);
-                    out[o] = sq_sigmoid(zz + sB3[o]);
+                    out[o] = canon_sigmoid(zz + sB3[o]);
                 }
             }
         }

@@ -74,10 +74,31 @@ static int upload_weights(ethcnn_ctx* c) {
 //      benign weights has a bound of 0.1 and a measured error of 7e-6), so the plan is MEASURED: a seeded calibration picture (flat,
 //      low-contrast, gradient, noise, edge and texture macro tiles, 640 CTUs) through the exact plan and through the plan with the
 //      loaded weights, gates open; max |dp| <= kFastGuardTol: accepted; else refused with both numbers.
+//   0. before either: a weight that is NaN or +-Inf has no fp16 scale and no bound, and some tensors (the FC3 biases) enter neither, so
+//      a NaN there passed both stages; such weights are refused unmeasured.  Plan 0 computes them as the oracle does.  Likewise weights
+//      whose power-of-two scales are not normal floats (ethcnn_weights.cpp::fast_plan_scales_ok): the bound of stage 1 is computed in
+//      double and does not see a float scale overflow.
+static long first_nonfinite(const float* blob, size_t n) {
+    for (size_t i = 0; i < n; ++i)
+        if (!std::isfinite(blob[i])) return (long)i;
+    return -1;
+}
 static int build_fast_weights(ethcnn_ctx* c, int plan);
 static int check_fast_plan(ethcnn_ctx* c, int plan) {
     if (plan != 2 && plan != 3) return set_err(c, ETHCNN_ERR_ARG, "plan must be 2 or 3, got %d", plan);
     if (!c->have_weights) return set_err(c, ETHCNN_ERR_NOWEIGHTS, "no weights loaded");
+    if (c->guard_state[plan] == 0) {  // stage 0
+        c->guard_nonfinite = first_nonfinite(c->blob.data(), c->blob.size());
+        c->guard_bad_scale[plan] = nullptr;
+        if (c->guard_nonfinite < 0) fast_plan_scales_ok(c->blob.data(), plan, &c->guard_bad_scale[plan]);
+        if (c->guard_nonfinite >= 0 || c->guard_bad_scale[plan]) {
+            c->guard_bound[plan] = INFINITY;
+            c->guard_info[plan] = FastGuard{};
+            c->guard_info[plan].prob_err = INFINITY;
+            c->guard_measured[plan] = -1.0;
+            c->guard_state[plan] = 2;
+        }
+    }
     if (c->guard_state[plan] == 0) {
         const FastGuard g = fast_plan_floor_bound(c->blob.data(), plan, /*heads16=*/true);
         c->guard_bound[plan] = g.prob_err;
@@ -98,6 +119,15 @@ static int check_fast_plan(ethcnn_ctx* c, int plan) {
         }
     }
     if (c->guard_state[plan] == 3) return ETHCNN_OK;
+    if (c->guard_state[plan] != 1 && c->guard_nonfinite >= 0)
+        return set_err(c, ETHCNN_ERR_PLAN_REFUSED,
+                       "FC1 plan %d is refused for these weights: weight %ld of the blob is not a finite number (%g), so the plan's fp16 scales and "
+                       "error bounds do not exist: use plan 0, which computes with such weights exactly as the reference arithmetic does",
+                       plan, c->guard_nonfinite, (double)c->blob[(size_t)c->guard_nonfinite]);
+    if (c->guard_state[plan] != 1 && c->guard_bad_scale[plan])
+        return set_err(c, ETHCNN_ERR_PLAN_REFUSED,
+                       "FC1 plan %d is refused for these weights: %s is not a normal float (the weights are too small or too large for a power-of-two "
+                       "scale to bring them to fp16's range): use plan %s", plan, c->guard_bad_scale[plan], plan == 3 ? "2 or 0" : "0");
     if (c->guard_state[plan] != 1) {
         const FastGuard& g = c->guard_info[plan];
         return set_err(c, ETHCNN_ERR_PLAN_REFUSED,
@@ -113,7 +143,9 @@ static int check_fast_plan(ethcnn_ctx* c, int plan) {
 // bound alone accepts the plan; ETHCNN_ERR_PLAN_REFUSED: it does not (a context would go on to measure)
 extern "C" int ethcnn_fast_plan_bound(const float* blob, size_t nfloats, int plan, double* prob_err_bound, double* feature_bound) {
     if (!blob || nfloats != kBlobFloats || (plan != 2 && plan != 3) || !prob_err_bound) return ETHCNN_ERR_ARG;
-    const FastGuard g = fast_plan_floor_bound(blob, plan, /*heads16=*/true);
+    FastGuard g = fast_plan_floor_bound(blob, plan, /*heads16=*/true);
+    const char* which = nullptr;
+    if (first_nonfinite(blob, nfloats) >= 0 || !fast_plan_scales_ok(blob, plan, &which)) g.prob_err = INFINITY;  // (stage 0 of the guard)
     *prob_err_bound = g.prob_err;
     if (feature_bound) *feature_bound = g.feature_bound;
     return g.prob_err <= kFastGuardTol ? ETHCNN_OK : ETHCNN_ERR_PLAN_REFUSED;

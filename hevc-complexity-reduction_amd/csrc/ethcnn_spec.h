@@ -56,6 +56,8 @@ int fast_feature_k(int chunk, int kh, int idx);
 // plan 2: a bound no feature of an All-Intra CTU can exceed (|input| <= 1 after mean removal; per-channel bounds pushed through
 // the three conv layers of every branch) -- the feature scale 2^s is chosen from it so that no fp16 piece can overflow
 float fast_feature_bound(const float* blob);
+// stage 0 of the 16-bit plans' guard: every scale the plan derives from these weights is a normal float (ethcnn_weights.cpp)
+bool fast_plan_scales_ok(const float* blob, int plan, const char** which);
 // ---- plan 3: the trunk's three conv layers on the 16-bit matrix pipe as well (fp16 x 2 splits; ethcnn_trunk_fast.hip).
 // Per branch, A operands as fp16 pieces in MFMA order (halves): [conv1: 4 fragments x 64 lanes x 4 = piece 0, piece 1, 16 x piece 0,
 // 16 x piece 1 (the last two for the L branch's high pixel-sum digits)][conv2: (t, s, piece) 8 fragments x 64 x 8][conv3: (t, s,

@@ -300,6 +300,57 @@ static void f16x2(float x, uint16_t* hi, uint16_t* lo) {
 static float pow2_scale(double maxabs) {  // the power of two that puts maxabs at <= 2^14 (fp16 overflows at 65504)
     return std::exp2f(14.0f - std::ceil(std::log2((float)maxabs)));
 }
+// Every power-of-two scale of a 16-bit plan, and every product or reciprocal of scales its kernels multiply by, must be a NORMAL float.
+// Weights so small (or bounds so large) that 2^14 / max leaves the float range make a scale Inf or 0 and the plan's output NaN, while
+// the a-priori error bound -- computed in double -- stays tiny and accepts the plan (found with tests/edge_values.py: FC1 weights
+// x 2^-125 gave NaN probabilities under plans 2 and 3).  ADVICE r05 fixed the side beyond FLT_MAX for the heads' scales; this is both
+// sides for the scales of FC1 (ethcnn_model.cpp::build_fast_weights) and of the trunk (pack_trunk_f16 below) -- the same formulae.
+bool fast_plan_scales_ok(const float* blob, int plan, const char** which) {
+    auto bad = [&](float v, const char* name) {
+        if (std::isnormal(v)) return false;
+        *which = name;
+        return true;
+    };
+    float wmax = 0.0f;
+    for (int h = 0; h < 3; ++h)
+        for (size_t i = 0; i < (size_t)kNFeat * kN1[h]; ++i) wmax = std::max(wmax, std::fabs(blob[kOffFc1W[h] + i]));
+    const float fmax = fast_feature_bound(blob);
+    if (!(wmax > 0.0f) || !(fmax > 0.0f) || !std::isfinite(wmax) || !std::isfinite(fmax)) {
+        *which = "max |W1| or the feature bound is zero or not finite";
+        return false;
+    }
+    const float sw = pow2_scale(wmax), sa = pow2_scale(fmax);
+    if (bad(sw, "the scale of W1") || bad(sa, "the scale of the features") || bad(sa * sw, "the product of FC1's scales") ||
+        bad(1.0f / (sa * sw), "the reciprocal of FC1's scales"))
+        return false;
+    if (plan != 3) return true;
+    for (int br = 0; br < 3; ++br) {  // the trunk's scales, as pack_trunk_f16 derives them
+        const float* W1 = blob + kOffConvW[br][0];
+        const float* B1 = blob + kOffConvB[br][0];
+        const float* W2 = blob + kOffConvW[br][1];
+        const float* W3 = blob + kOffConvW[br][2];
+        double m2 = 0, m3 = 0, bound1 = 0;
+        for (int i = 0; i < 64 * 24; ++i) m2 = std::max(m2, (double)std::fabs(W2[i]));
+        for (int i = 0; i < 96 * 32; ++i) m3 = std::max(m3, (double)std::fabs(W3[i]));
+        for (int co = 0; co < 16; ++co) {
+            double sabs = std::fabs((double)B1[co]);
+            for (int t = 0; t < 16; ++t) sabs += std::fabs((double)W1[t * 16 + co]);
+            bound1 = std::max(bound1, sabs);
+        }
+        if (!(m2 > 0) || !(m3 > 0) || !(bound1 > 0) || !std::isfinite(m2) || !std::isfinite(m3) || !std::isfinite(bound1)) {
+            *which = "a conv layer's largest weight or bound is zero or not finite";
+            return false;
+        }
+        const float s2w = pow2_scale(m2), s3w = pow2_scale(m3), S1 = pow2_scale(bound1 * 1.0001);
+        const int pool = br == 0 ? 1 : (br == 1 ? 2 : 4);
+        if (bad(s2w, "the scale of a conv2 kernel") || bad(s3w, "the scale of a conv3 kernel") || bad(S1, "the scale of conv1's outputs") ||
+            bad((1.0f / 255.0f) * (1.0f / (float)(pool * pool)) * S1, "conv1's input constant") || bad(S1 * s2w, "the product of conv2's scales") ||
+            bad(sa / (S1 * s2w), "conv2's unscale factor") || bad(1.0f / s3w, "conv3's unscale factor"))
+            return false;
+    }
+    return true;
+}
+
 void pack_trunk_f16(const float* blob, float scale_a, uint16_t* w_out, float* c_out, Trunk16Scalars* sc) {
     for (int br = 0; br < 3; ++br) {
         const float* W1 = blob + kOffConvW[br][0];  // [4][4][1][16]

@@ -429,7 +429,10 @@ int ethcnn_get_fc1_plan(const ethcnn_ctx* ctx);
  * usable (ethcnn_set_fc1_plan(ctx, 0 or 2)).  Never a silent loss of accuracy, never a silent fallback.  ~3 ms, once per weight load.
  * The measured stage is empirical -- one synthetic picture -- so a deployment checks a plan on its OWN content with ethcnn_audit_plan_device
  * / ethcnn_audit_plan_yuv_file ("comparing two predictions" below).
- *   ethcnn_check_fc1_plan   ETHCNN_OK / ETHCNN_ERR_PLAN_REFUSED for the loaded weights; *apriori_bound, *measured (may be NULL; measured
+ * Weights that are not finite (a NaN or an infinity anywhere in the blob, e.g. a diverged training run's export) are REFUSED before
+ * either stage, unmeasured (*apriori_bound = +Inf, *measured < 0): they have no fp16 scale.  Plan 0 computes them as the reference
+ * arithmetic does (NaN probabilities, which the analysis tools reject).
+ *   ethcnn_check_fc1_plan  ETHCNN_OK / ETHCNN_ERR_PLAN_REFUSED for the loaded weights; *apriori_bound, *measured (may be NULL; measured
  *                           < 0: the bound sufficed and nothing was run).
  * The launchers (video_to_cu_depth.py, tools/video_to_cu_depth.c) call it when ETHCNN_FC1_PLAN is set and continue with plan 0 after
  * printing the refusal. */

@@ -152,6 +152,7 @@ def lib():
         L.oracle_set_threads(_usable_cpus())  # never more OpenMP threads than the cgroup lets run (CFS throttling otherwise)
         L.oracle_expf_export.argtypes = [ctypes.c_float]
         L.oracle_expf_export.restype = ctypes.c_float
+        L.oracle_canon_math.argtypes = [ctypes.c_int, fp, ctypes.c_long, fp]
         _lib = L
     return _lib
 
@@ -167,6 +168,15 @@ def _u(a):
 def set_threads(n):
     """OpenMP team size of the C oracle; returns the previous maximum."""
     return int(lib().oracle_set_threads(int(n)))
+
+
+def canon_math(which, x):
+    """the canonical exp / sigmoid / tanh (oracle_expf, sigmoidf, tanhf_c) of a float32 array"""
+    x = np.ascontiguousarray(x, dtype=np.float32)
+    y = np.empty_like(x)
+    rc = lib().oracle_canon_math({"exp": 0, "sigmoid": 1, "tanh": 2}[which], _f(x), x.size, _f(y))
+    assert rc == 0
+    return y
 
 
 def _blob(blob):

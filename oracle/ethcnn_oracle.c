@@ -103,10 +103,16 @@ static inline float c51(void) { return 1.0f / 51.0f; }    /* 0x3ca0a0a1, .meta '
 static inline float lrelu(float h) { return fmaxf(0.2f * h, h); }
 
 /* exp() with a fully specified operation sequence (only fmaf / mul / rint / exponent
- * arithmetic) so that the HIP kernel can reproduce it bit-for-bit.  ~1 ulp. */
+ * arithmetic) so that the HIP kernel can reproduce it bit-for-bit.  Measured against float64 over [-86, 80]
+ * (tests/test_edge_values_cpu.py): <= 0.88 ulp.
+ * Outside the clamps and at non-finite arguments: x > 80 (+Inf included) gives exp(80), x < -86
+ * (-Inf included) gives exp(-86); the clamps are COMPARISONS, which a NaN fails, so a NaN stays a NaN -- TensorFlow's exp,
+ * sigmoid and tanh of NaN are NaN, and the reference's graphs put no clamp in front of them (net_CNN.py:160,168,181,
+ * net_CNN_LSTM_one_step.py lstm()).  The NaN is returned before the float -> int conversion, which C leaves undefined for it. */
 static inline float oracle_expf(float x) {
     if (x > 80.0f) x = 80.0f;   /* keeps 2^n * p normal; sigmoid is saturated far earlier */
     if (x < -86.0f) x = -86.0f;
+    if (x != x) return x;
     const float n = rintf(x * 1.44269504088896341f);
     float r = fmaf(n, -0.693145751953125f, x);           /* ln2 hi (exact in 12 bits) */
     r = fmaf(n, -1.42860682030941723212e-6f, r);         /* ln2 lo */
@@ -521,6 +527,13 @@ int oracle_lstm_blob_floats(void) { return LSTM_BLOB_FLOATS; }
 static inline float tanhf_c(float x) {
     const float e = oracle_expf(2.0f * x);
     return (e - 1.0f) / (e + 1.0f);
+}
+
+/* the canonical functions over an array, for the tests that measure them against float64: which = 0 exp, 1 sigmoid, 2 tanh */
+int oracle_canon_math(int which, const float* x, long n, float* y) {
+    if (which < 0 || which > 2) return -1;
+    for (long i = 0; i < n; ++i) y[i] = which == 0 ? oracle_expf(x[i]) : which == 1 ? sigmoidf(x[i]) : tanhf_c(x[i]);
+    return 0;
 }
 
 static void ctu_lstm(const float* lb, const float* vec, const float* st_in, float qpn, int phase, int mode,
