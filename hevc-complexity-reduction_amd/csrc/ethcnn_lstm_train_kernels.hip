@@ -325,7 +325,14 @@ __device__ __forceinline__ void update_body(float* __restrict__ W, float* __rest
         double s = 0.0;
         for (int k = 0; k < nparts; ++k) s += part[k];
         const float norm = (float)sqrt(s);
-        s_scale = clip > 0.f ? clip * fminf(1.f / norm, 1.f / clip) : 1.f;
+        // minimum(1 / norm, 1 / clip) as a comparison that keeps its first operand: a NaN norm gives a NaN scale and so a NaN
+        // update (fminf would return 1 / clip: scale 1, and the finite part of the weights would move as if nothing had happened)
+        float scale = 1.f;
+        if (clip > 0.f) {
+            const float a = 1.f / norm, b = 1.f / clip;
+            scale = clip * ((b < a) ? b : a);
+        }
+        s_scale = scale;
         if (blockIdx.x == 0) stats[7] = norm;
     }
     __syncthreads();

@@ -104,7 +104,8 @@ def balanced_loss(labs, p64, p32, p16):
 
 
 def net(flat, luma, labels, qp, mask1=None, mask2=None, dtype=torch.float64):
-    """net_CTU64.net with isdrop = (masks given): returns dict(probs [n,21], H1 [n,448] (leaky-ReLU FC1, before dropout), loss_list,
+    """net_CTU64.net with isdrop = (masks given): returns dict(probs [n,21], H1 [n,448] (leaky-ReLU FC1, before dropout), X3 [n,49+97+193]
+    (the rows FC3 multiplies: [h_fc2 after dropout, qp] per head), loss_list,
     accuracy_list, total_loss).  dtype (that of `flat`): float64; float32 only to measure what fp32 arithmetic costs."""
     tv = views(flat)
     n = luma.shape[0]
@@ -128,7 +129,7 @@ def net(flat, luma, labels, qp, mask1=None, mask2=None, dtype=torch.float64):
         f2[br], f3[br] = c2.reshape(n, -1), c3.reshape(n, -1)
     feat = torch.cat([f3["S"], f3["M"], f3["L"], f2["S"], f2["M"], f2["L"]], dim=1)
     # heads (:160-176); dropout = x / keep * mask (tf.nn.dropout) after FC1 (keep 0.5) and FC2 (keep 0.8)
-    probs, h1s, o1, o2 = [], [], 0, 0
+    probs, h1s, x3s, o1, o2 = [], [], [], 0, 0
     for tag, n1, n2, n3 in HEADS:
         h1 = _lrelu(feat @ tv["h_fc1__%s__w" % tag] + tv["h_fc1__%s__b" % tag])
         h1s.append(h1)
@@ -137,7 +138,8 @@ def net(flat, luma, labels, qp, mask1=None, mask2=None, dtype=torch.float64):
         h2 = _lrelu(torch.cat([h1, q], 1) @ tv["h_fc2__%s__w" % tag] + tv["h_fc2__%s__b" % tag])
         if mask2 is not None:
             h2 = h2 / 0.8 * torch.as_tensor(mask2[:, o2:o2 + n2], dtype=dtype)
-        z = torch.cat([h2, q], 1) @ tv["y_conv_flat__%s__w" % tag] + tv["y_conv_flat__%s__b" % tag]
+        x3s.append(torch.cat([h2, q], 1))
+        z = x3s[-1] @ tv["y_conv_flat__%s__w" % tag] + tv["y_conv_flat__%s__b" % tag]
         probs.append(torch.sigmoid(z))
         o1, o2 = o1 + n1, o2 + n2
     p64, p32, p16 = probs
@@ -151,7 +153,7 @@ def net(flat, luma, labels, qp, mask1=None, mask2=None, dtype=torch.float64):
         a16 = torch.sum(v16 * c16) / (torch.sum(v16) + eps)
         a32 = torch.sum(v32 * c32) / (torch.sum(v32) + eps)
         a64 = torch.mean((torch.round(p64) == torch.round(y64)).double())
-    return {"probs": torch.cat([p64, p32, p16], 1), "H1": torch.cat(h1s, 1), "loss_list": torch.stack([l64, l32, l16]),
+    return {"probs": torch.cat([p64, p32, p16], 1), "H1": torch.cat(h1s, 1), "X3": torch.cat(x3s, 1), "loss_list": torch.stack([l64, l32, l16]),
             "accuracy_list": torch.stack([a64, a32, a16]), "total_loss": total}
 
 

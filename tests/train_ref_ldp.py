@@ -40,7 +40,7 @@ def slot_qps(buf):
 
 
 def net(flat, luma, labels, qp, mask1=None, mask2=None, dtype=torch.float64):
-    """LDP net_CTU64.net with isdrop = (masks given): dict(probs [n,21], H1 [n,448] (leaky-ReLU FC1, before dropout), loss_list,
+    """LDP net_CTU64.net with isdrop = (masks given): dict(probs [n,21], H1 [n,448] (leaky-ReLU FC1, before dropout), X3 (the rows FC3 multiplies, as in train_ref.net), loss_list,
     accuracy_list, total_loss).  dtype (that of `flat`): float64; float32 only to measure what fp32 arithmetic costs."""
     tv = views(flat)
     n = luma.shape[0]
@@ -61,7 +61,7 @@ def net(flat, luma, labels, qp, mask1=None, mask2=None, dtype=torch.float64):
         c3 = _conv(c2, tv[_var(bb + 4)], tv[_var(bb + 5)], 2)
         f2[br], f3[br] = c2.reshape(n, -1), c3.reshape(n, -1)
     feat = torch.cat([f3["S"], f3["M"], f3["L"], f2["S"], f2["M"], f2["L"]], dim=1)
-    probs, h1s, o1, o2 = [], [], 0, 0
+    probs, h1s, x3s, o1, o2 = [], [], [], 0, 0
     for tag, n1, n2, n3 in train_ref.HEADS:
         h1 = _lrelu(feat @ tv["h_fc1__%s__w" % tag] + tv["h_fc1__%s__b" % tag])
         h1s.append(h1)
@@ -70,7 +70,8 @@ def net(flat, luma, labels, qp, mask1=None, mask2=None, dtype=torch.float64):
         h2 = _lrelu(torch.cat([h1, q], 1) @ tv["h_fc2__%s__w" % tag] + tv["h_fc2__%s__b" % tag])
         if mask2 is not None:
             h2 = h2 / 0.8 * torch.as_tensor(mask2[:, o2:o2 + n2], dtype=dtype)
-        z = torch.cat([h2, q], 1) @ tv["y_conv_flat__%s__w" % tag] + tv["y_conv_flat__%s__b" % tag]
+        x3s.append(torch.cat([h2, q], 1))
+        z = x3s[-1] @ tv["y_conv_flat__%s__w" % tag] + tv["y_conv_flat__%s__b" % tag]
         probs.append(torch.sigmoid(z))
         o1, o2 = o1 + n1, o2 + n2
     p64, p32, p16 = probs
@@ -78,8 +79,8 @@ def net(flat, luma, labels, qp, mask1=None, mask2=None, dtype=torch.float64):
     with torch.no_grad():
         pr = torch.cat([p64, p32, p16], 1)
         acc = torch.as_tensor(train_ref.accuracy(pr.numpy(), labels))
-    return {"probs": torch.cat([p64, p32, p16], 1), "H1": torch.cat(h1s, 1), "loss_list": torch.stack([l64, l32, l16]),
-            "accuracy_list": acc, "total_loss": l16 + l32 + l64}
+    return {"probs": torch.cat([p64, p32, p16], 1), "H1": torch.cat(h1s, 1), "X3": torch.cat(x3s, 1),
+            "loss_list": torch.stack([l64, l32, l16]), "accuracy_list": acc, "total_loss": l16 + l32 + l64}
 
 
 def loss_and_grad(blob, luma, labels, qp, mask1=None, mask2=None, dtype=torch.float64):

@@ -44,7 +44,9 @@ def parse_samples(buf, idx):
 
 
 def _cell_clip(c):
-    return torch.clamp(c, -5.0, 5.0)   # LSTMCell(cell_clip = 5): clip_by_value, no gradient where c was clipped
+    """LSTMCell(cell_clip = 5): clip_by_value, no gradient where c was clipped.  A NaN cell becomes -5 and gets no gradient (DESIGN
+    section 9: fminf(fmaxf(NaN, -5), 5) = -5; torch.clamp alone would return the NaN)"""
+    return torch.where(torch.isnan(c), torch.full_like(c, -5.0), torch.clamp(c, -5.0, 5.0))
 
 
 def _carry(cpre, c):
@@ -59,7 +61,8 @@ def _forget(fg, c_prev, cpre_prev):
 
 def net(flat, vec, labels, qps, gop, qp_scale=1.0, mask_h=None, mask_fc2=None):
     """net_CTU64.net with isdrop = (masks given; [20 n, 448] and [20 n, 336], rows 20 b + p).  dict(probs [20 n,21], C, H [20 n,448]
-    (c after the clip, h not dropped, computed with slot p as the input), Cpre (c before the clip), loss_list, accuracy_list,
+    (c after the clip, h not dropped, computed with slot p as the input), Cpre (c before the clip), X3 [20 n, 53+101+197] (the rows FC3
+    multiplies: [fc2 after dropout, qp, one-hot] per cell), G [20 n, 4, 448] (the gate values i, j, f, o), loss_list, accuracy_list,
     total_loss).  _cell_clip, _carry, _forget and train_ref._lrelu are looked up when called: tests/train_edges.py patches them to make
     deliberately wrong restatements."""
     tv = views(flat)
@@ -73,6 +76,8 @@ def net(flat, vec, labels, qps, gop, qp_scale=1.0, mask_h=None, mask_fc2=None):
     Cs = [[None] * 3 for _ in range(STEPS)]
     Hs = [[None] * 3 for _ in range(STEPS)]
     Ps = [[None] * 3 for _ in range(STEPS)]
+    X3 = [[None] * 3 for _ in range(STEPS)]
+    Gs = [[None] * 3 for _ in range(STEPS)]
     o2 = 0
     for ci, (tag, hid, n2, n3, col) in enumerate(CELLS):
         pre = "RNN%s/" % tag
@@ -85,16 +90,19 @@ def net(flat, vec, labels, qps, gop, qp_scale=1.0, mask_h=None, mask_fc2=None):
             p = STEPS - 1 - ts                                                           # cell_inputs.reverse()
             z = torch.cat([x[:, p, col:col + hid], h], 1) @ K + bK
             i, j, f, o = torch.split(z, hid, dim=1)
-            cpre = _forget(torch.sigmoid(f + 1.0), c, cpre) + torch.sigmoid(i) * torch.tanh(j)
+            ig, jg, fg, og = torch.sigmoid(i), torch.tanh(j), torch.sigmoid(f + 1.0), torch.sigmoid(o)
+            cpre = _forget(fg, c, cpre) + ig * jg
             cc = _cell_clip(cpre)
-            h = torch.sigmoid(o) * torch.tanh(cc)
+            h = og * torch.tanh(cc)
+            Gs[p][ci] = torch.stack([ig, jg, fg, og], 1).detach()
             c = _carry(cpre, cc)
             efs = torch.cat([qp[:, ts:ts + 1], onehot[:, ts]], 1)                        # :125: indexed by the unrolled step
             out = h if mh is None else h / 0.5 * mh[:, p, col:col + hid]                 # DropoutWrapper on the OUTPUT only
             h2 = train_ref._lrelu(torch.cat([out, efs], 1) @ W2 + b2)                    # leaky_relu, alpha 0.2
             if m2 is not None:
                 h2 = h2 / 0.8 * m2[:, p, o2:o2 + n2]
-            P[p][ci] = torch.sigmoid(torch.cat([h2, efs], 1) @ W3 + b3)
+            X3[p][ci] = torch.cat([h2, efs], 1)
+            P[p][ci] = torch.sigmoid(X3[p][ci] @ W3 + b3)
             Cs[p][ci], Hs[p][ci], Ps[p][ci] = cc, h, cpre
         o2 += n2
     probs = torch.stack([torch.cat(P[p], 1) for p in range(STEPS)], 1).reshape(n * STEPS, 21)
@@ -103,7 +111,9 @@ def net(flat, vec, labels, qps, gop, qp_scale=1.0, mask_h=None, mask_fc2=None):
     Cpre = torch.stack([torch.cat(Ps[p], 1) for p in range(STEPS)], 1).reshape(n * STEPS, 448)
     lab = np.asarray(labels, dtype=np.float64).reshape(n * STEPS, 16)
     l3 = loss_list(probs, lab.astype(np.float64 if dt == torch.float64 else np.float32))
-    return {"probs": probs, "C": C, "H": H, "Cpre": Cpre, "loss_list": l3,
+    x3 = torch.stack([torch.cat(X3[p], 1) for p in range(STEPS)], 1).reshape(n * STEPS, -1)
+    gates = torch.stack([torch.cat(Gs[p], 2) for p in range(STEPS)], 1).reshape(n * STEPS, 4, 448)
+    return {"probs": probs, "C": C, "H": H, "Cpre": Cpre, "X3": x3, "G": gates, "loss_list": l3,
             "accuracy_list": torch.as_tensor(train_ref.accuracy(probs.detach().numpy(), lab)), "total_loss": l3[2] + l3[1] + l3[0]}
 
 
