@@ -305,6 +305,8 @@ SIGNATURES = {
     "ethcnn_risk_write": (_i, [ctypes.c_char_p, _vp]),
     "ethcnn_risk_read": (_i, [ctypes.c_char_p, _vp]),
     "ethcnn_risk_ladder_build": (_i, [_vp, _vp, _i, ctypes.c_int64, ctypes.c_uint64, _vp, _vp]),
+    "ethcnn_reach_hist": (_i, [_vp, _vp, ctypes.c_int64, _i, _vp]),
+    "ethcnn_reach_calibrate": (_i, [_vp, ctypes.POINTER(ctypes.c_uint32), ctypes.POINTER(ctypes.c_uint32), _i, _vp, _vp, _vp]),
     "ethcnn_compare_probs_device": (_i, [_vp, _vp, _vp, ctypes.c_int64, ctypes.c_float, _vp, _vp, _vp]),
     "ethcnn_compare_frames_device": (_i, [_vp, _vp, _vp, _i, _i, ctypes.c_int64, ctypes.c_float, _vp, _vp, _vp]),
     "ethcnn_compare_probs": (_i, [_vp, _vp, _vp, ctypes.c_int64, ctypes.c_float, _vp, _vp, _vp]),
@@ -2073,6 +2075,7 @@ SIM_THR = np.dtype([("up_k", "<i4", (3,)), ("down_k", "<i4", (3,))])
 SIM_COUNTS = np.dtype([("checked", "<u8", (4,)), ("split_only", "<u8", (3,)), ("current_only", "<u8", (3,)), ("both", "<u8", (3,)),
                        ("edge_split", "<u8", (3,)), ("wrong_split", "<u8", (3,)), ("wrong_stop", "<u8", (3,)), ("bad_ctus", "<u8")])
 SIM_FULL_SEARCH = ((1024, 1024, 1024), (-1, -1, -1))
+REACH_MAX_CAND = 256
 # partition decisions: bytes of a codes row, and its flag bits (byte 21)
 SIM_CODE_BYTES = 24
 SIM_FLAG_BAD, SIM_FLAG_LABELLED, SIM_FLAG_REJECTED, SIM_FLAG_GATE1_CLOSED, SIM_FLAG_GATE2_CLOSED = 1, 2, 4, 8, 16
@@ -2458,6 +2461,26 @@ class PartitionSim(object):
         risk = np.array([sum(int(x) for x in a) + sum(int(x) for x in b) for a, b in zip(rungs["exp_wrong_split"], rungs["exp_wrong_stop"])], dtype=object)
         return {"thr": np.ascontiguousarray(rungs["thr"]), "coord": rungs["coord"].copy(), "value": rungs["value"].copy(), "checked": rungs["checked"].copy(),
                 "exp_wrong_split": rungs["exp_wrong_split"].copy(), "exp_wrong_stop": rungs["exp_wrong_stop"].copy(), "risk": risk, "cost": cost}
+
+    # ---------------------------------------------------------------------------- threshold calibration on reached nodes ---
+    def reach_hist(self, cands, gates="none"):
+        """the histogram of the decided nodes of the labelled CTUs under every candidate, in the calibrator's layout (include/ethcnn.h
+        "threshold calibration on reached nodes"): cands as for eval, at most REACH_MAX_CAND -> uint64 [K, 3, 2, 1025] = [candidate, level,
+        truth, bin].  calib_choose, risk_from_hist and write_thr_info take a candidate's histogram as they take Calibrator.histogram()"""
+        cands = _sim_cands(cands)
+        out = np.zeros((cands.size, CALIB_LEVELS, 2, CALIB_BINS), np.uint64)
+        self._chk(self.lib.ethcnn_reach_hist(self.h, cands.ctypes.data if cands.size else None, cands.size, _SIM_GATES[gates],
+                                             out.ctypes.data if cands.size else None))
+        return out
+
+    def calibrate_reached(self, eps_down_ppm, eps_up_ppm, gates="none"):
+        """the six thresholds chosen top-down on the nodes the pruned search reaches: level l by calib_choose on the reach histogram under
+        the levels above it.  Budgets in parts per million (three values, or one for all levels) -> (CalibReport, SIM_THR record,
+        SIM_COUNTS record of that record under `gates`)"""
+        rep, thr, counts = CalibReport(), np.zeros(1, SIM_THR), np.zeros(1, SIM_COUNTS)
+        self._chk(self.lib.ethcnn_reach_calibrate(self.h, _ppm3(eps_down_ppm), _ppm3(eps_up_ppm), _SIM_GATES[gates], ctypes.byref(rep), thr.ctypes.data,
+                                                  counts.ctypes.data))
+        return rep, thr[0], counts[0]
 
 
 # search budget: building a ladder (include/ethcnn.h).  ethcnn_ladder_rung as a numpy record: 72 bytes, no padding

@@ -1323,7 +1323,8 @@ int ethcnn_ladder_write(const char* path, const ethcnn_sim_thr* thr, int64_t K, 
  *   What this is not.  The identity table ASSUMES A CALIBRATED MODEL: where the model is over-confident the figure is too low, and only
  *      a table fitted on labelled material (ethcnn_risk_from_hist) corrects that, for material like the one it was fitted on.  The
  *      level-1 and level-2 probabilities come from a model trained under teacher forcing -- on nodes whose parents were truly split --
- *      while the counter also asks them on nodes the pruned search reaches for other reasons.  The figure counts nodes, not CTUs, and
+ *      while the counter also asks them on nodes the pruned search reaches for other reasons ("threshold calibration on reached nodes"
+ *      below gives the histogram of those nodes, in the layout ethcnn_risk_from_hist takes).  The figure counts nodes, not CTUs, and
  *      nothing relates it to encoding time or to BD-rate. */
 #define ETHCNN_RISK_ONE (1u << 20)
 #define ETHCNN_RISK_REL_WORDS (3 * ETHCNN_CALIB_BINS)
@@ -1345,6 +1346,48 @@ int ethcnn_risk_write(const char* path, const uint32_t* rel);
 int ethcnn_risk_read(const char* path, uint32_t* rel);
 int ethcnn_risk_ladder_build(ethcnn_sim* sim, const uint64_t weight[4], int grid, int64_t max_rungs, uint64_t max_risk_ppm,
                              ethcnn_ladder_rung_risk* rungs_out, int64_t* nrungs_out);
+
+/* ---- threshold calibration on reached nodes.  The calibrator of "threshold calibration" counts TEACHER-FORCED populations: a 32 x 32
+ *      block only when its CTU is labelled split, a 16 x 16 block only when both ancestors are.  HM does not visit those populations: it
+ *      visits a 32 x 32 node whenever the decision above it was SPLIT ONLY, BOTH or a frame edge, whether or not the label agrees.  So
+ *      the calibrator's budgets hold for nodes the encoder never sees, and a reliability table fitted to its histogram is applied (by
+ *      the expected wrong decisions above) to nodes it was not fitted on.  The two entries here count and choose on the nodes the pruned
+ *      search REACHES, from the records a simulator already holds.  No reference counterpart.
+ *   ethcnn_reach_hist.  Over the LABELLED CTUs of the simulator's set (those of labelled_ctus: not rejected, wholly inside the picture,
+ *      with labels), for candidate c: every DECIDED NODE (rule line 4 of "partition-search simulation") of level l adds one to
+ *      hist[c][l][t][b], in the calibrator's layout [3 levels][2 truths][1025 bins], where
+ *        t = the node's own truth flag, the simulator's: judged whatever happened above it;
+ *        b = the bin AS THE ENCODER READS IT: the record's bin, or 0 where a closed batch gate of gate_order zeroed it.
+ *      The gates are those of the simulator's evaluation under the same gate_order; CTUs added in the per-CTU layout are never gated.
+ *      Unlabelled and rejected CTUs add nothing.  Counts are exact integers and do not depend on the grid, on the order of adds or on
+ *      how a set is split over adds.  ncand == 0 is a no-op; an empty set, or one without labelled CTUs, gives zeros.  A candidate
+ *      outside the simulator's ranges, ncand > ETHCNN_REACH_MAX_CAND, a gate_order that is none of the three or a NULL pointer is
+ *      ETHCNN_ERR_ARG, and nothing is written.  Synchronous on the context's stream; per call ncand x 49,200 bytes of device memory.
+ *   Identities.  For every candidate and gate order, with ev = the simulator's evaluation counters of the same arguments and hist the
+ *      candidate's histogram:
+ *        ev.wrong_split[l] == sum_{b > up_k[l]} hist[l][0][b]
+ *        ev.wrong_stop[l]  == sum_{b <= min(down_k[l], up_k[l])} hist[l][1][b]      (HM tests "split only" first)
+ *        hist[l] depends only on the thresholds of the levels < l (through the descent and the gates) and on nothing deeper;
+ *        hist[0] is the same for every candidate;
+ *        under the full search with ETHCNN_SIM_GATES_NONE hist[l] counts EVERY level-l node of every labelled CTU;
+ *        when no probability of the data is out of range, hist[0] equals level 0 of ethcnn_calib_get over the same data.
+ *   ethcnn_reach_calibrate.  Top-down, three histograms, the choices on the host.  Starting from thr = the full search, for l = 0, 1, 2:
+ *        H = the histogram of thr;  report->level[l] = level l of ethcnn_calib_choose(H, eps_down_ppm, eps_up_ppm);
+ *        thr.up_k[l], thr.down_k[l] = that level's up_k, down_k.
+ *      thr_out is the result; counts_out (may be NULL) the simulator's evaluation of it under gate_order.  So n0 / n1 of a level are the
+ *      unsplit / split nodes the pruned search reaches under the levels above, and the budgets are shares of those.  For the result,
+ *      counts.wrong_stop[l] == report.level[l].miss and counts.wrong_split[l] == report.level[l].fsplit exactly, crossed levels
+ *      included.  No labelled CTU, a budget above 10^6, a bad gate_order or a NULL eps_down_ppm / eps_up_ppm / report / thr_out:
+ *      ETHCNN_ERR_ARG, and no output is written.
+ *   The layout is the calibrator's on purpose: ethcnn_risk_from_hist, ethcnn_calib_choose and ethcnn_calib_write_thr_info take a reach
+ *      histogram or report unchanged.  The table to fit for the expected wrong decisions is the one of the FULL-SEARCH candidate under
+ *      ETHCNN_SIM_GATES_NONE: it covers all nodes of the labelled CTUs, the population that counter meets at rung 0 and thins from there.
+ *   What this is not.  The choice is greedy: level l is fixed before the cost of level l + 1 is seen.  One table for all QPs. */
+#define ETHCNN_REACH_HIST_WORDS ETHCNN_CALIB_HIST_WORDS
+#define ETHCNN_REACH_MAX_CAND 256
+int ethcnn_reach_hist(ethcnn_sim* sim, const ethcnn_sim_thr* cand, int64_t ncand, int gate_order, uint64_t* hist /* [ncand][ETHCNN_REACH_HIST_WORDS] */);
+int ethcnn_reach_calibrate(ethcnn_sim* sim, const uint32_t eps_down_ppm[3], const uint32_t eps_up_ppm[3], int gate_order, ethcnn_calib_report* report,
+                           ethcnn_sim_thr* thr_out, ethcnn_sim_counts* counts_out /* may be NULL */);
 
 /* ---- comparing two predictions: how far two sets of probabilities are apart, and whether the encoder's pruned search changes (no
  *      reference counterpart).  The questions behind every "byte-identical" and "within tolerance" of this project: a 16-bit plan against

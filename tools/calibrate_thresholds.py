@@ -9,7 +9,7 @@ the largest `down` that wrongly stops at most --eps-down parts per million of th
 wrongly forces at most --eps-up parts per million of the truly unsplit ones.
 
     calibrate_thresholds.py [--eps-down E1 E2 E3] [--eps-up E1 E2 E3] [--out Thr_info.txt --order ai|ldp] [--hist FILE] [--reliability-out FILE] [--json] [--device N]
-                            [--input-bit-depth N] [--input-chroma-format 400|420|422|444] CASE...
+                            [--reached [--gates none|ai|ldp]] [--input-bit-depth N] [--input-chroma-format 400|420|422|444] CASE...
 
 Any number of cases, accumulated into one histogram:
 
@@ -41,6 +41,15 @@ decisions": per level and bin the share of truly split samples, made non-decreas
 build_ladder.py --no-labels --reliability and ETHCNN_SEARCH_BUDGET_RELIABILITY read.  --order ai writes "up1 down1 up2 down2 up3 down3" (HM-16.5_Test_AI, TEncCu.cpp:250), --order
 ldp writes "down1 up1 down2 up2 down3 up3" (HM-16.5_Test_LDP, TEncGOP.cpp:1449): the two encoders differ.  CTUs that are not wholly
 inside the picture are left out (HM forces their splits).
+
+--reached calibrates on the nodes HM's pruned search REACHES instead (include/ethcnn.h "threshold calibration on reached nodes").  The
+populations above are teacher-forced: a 32x32 block counts only under a CTU that is labelled split, a 16x16 block only when both
+ancestors are.  The encoder visits a block whenever the decision above it was "split only", "both" or a frame edge, whatever the label
+says.  With --reached the cases go into a partition-search simulator and the levels are chosen top-down: 64x64 first, then 32x32 on the
+blocks reached under the chosen 64x64 thresholds, then 16x16; the budgets are shares of the reached split / unsplit nodes, and the
+report adds the RD checks that remain per CU size and their weighted share (weights 64 16 4 1) of the full search.  --gates none|ai|ldp
+applies the predictors' batch gates as simulate_thresholds.py does; it defaults to --order's value when --out is given, else none.
+--hist and --reliability-out then take the histogram of the full search under gates none: every node of every labelled CTU.
 """
 import importlib
 import json
@@ -87,6 +96,11 @@ def parse(argv, labels_optional=False):
             opt[a[2:].replace("-", "_")] = int(v[0]) if a == "--device" else v[0]
         elif a == "--json":
             opt["json"] = True
+        elif a == "--reached":
+            opt["reached"] = True
+        elif a == "--gates":
+            v, i = _take(argv, i, 1, a)
+            opt["gates"] = v[0]
         elif a in fmt:
             v, i = _take(argv, i, 1, a)
             if not v[0].isdigit():
@@ -142,6 +156,12 @@ def parse(argv, labels_optional=False):
     for e in opt["eps_down"] + opt["eps_up"]:
         if not 0 <= e <= 1000000:
             raise Usage("budgets are parts per million, 0..1000000")
+    if "gates" in opt and not opt.get("reached"):
+        raise Usage("--gates goes with --reached")
+    if opt.get("reached"):  # (a run without --reached carries neither key)
+        opt.setdefault("gates", opt["order"] if opt["out"] else "none")
+        if opt["gates"] not in ("none", "ai", "ldp"):
+            raise Usage("--gates is none, ai or ldp")
     return opt, cases
 
 
@@ -245,11 +265,63 @@ def add_cases(pkg, ctx, cal, cases, note):
             cal.add(probs, depth)
 
 
+def run_reached(pkg, opt, cases, out, note):
+    """--reached: the cases go into a PartitionSim, the levels are chosen top-down on the nodes the pruned search reaches"""
+    e = pkg.ethcnn
+    sizes, weights = ("64x64", "32x32", "16x16", "8x8"), e.BUDGET_WEIGHTS
+    ctx = pkg.EthCnn(device=opt["device"])
+    try:
+        sim = pkg.PartitionSim(ctx)
+        add_cases(pkg, ctx, sim, cases, note)
+        info = sim.info()
+        if info["labelled_ctus"] == 0:
+            raise ValueError("no labelled CTU among the %d of the cases (labels are used on CTUs wholly inside the picture)" % info["ctus"])
+        rep, thr, counts = sim.calibrate_reached(opt["eps_down"], opt["eps_up"], opt["gates"])
+        levels = rep.as_dicts()
+        full = sim.eval(e.sim_thr(*e.SIM_FULL_SEARCH), opt["gates"])[0]
+        if opt["out"]:
+            e.write_thr_info(opt["out"], rep, opt["order"])
+        if opt["hist"] or opt["reliability_out"]:
+            hist = sim.reach_hist(e.sim_thr(*e.SIM_FULL_SEARCH), "none")[0]  # every node of every labelled CTU
+            if opt["hist"]:
+                hist.astype("<u8").tofile(opt["hist"])
+            if opt["reliability_out"]:
+                e.risk_write(opt["reliability_out"], e.risk_from_hist(hist))
+                note("wrote %s: the reliability table of %d reached nodes (full search, gates none)" % (opt["reliability_out"], int(hist.sum())))
+    finally:
+        ctx.close()
+    cost = lambda c: sum(w * int(x) for w, x in zip(weights, c["checked"]))
+    share = cost(counts) / cost(full) if cost(full) else 0.0
+    result = {"levels": levels, "eps_down_ppm": opt["eps_down"], "eps_up_ppm": opt["eps_up"], "out": opt["out"], "order": opt["order"], "reached": True,
+              "gates": opt["gates"], "thr": {"up_k": [int(x) for x in thr["up_k"]], "down_k": [int(x) for x in thr["down_k"]]},
+              "counts": {f: [int(x) for x in np.atleast_1d(counts[f])] for f in e.SIM_COUNTS.names}, "checked_full": [int(x) for x in full["checked"]],
+              "share_of_full_search": share, "ctus": info["ctus"], "labelled_ctus": info["labelled_ctus"], "rejected_ctus": info["rejected_ctus"]}
+    if opt["json"]:
+        out.write(json.dumps(result) + "\n")
+        return result
+    out.write("reached nodes of %d labelled CTUs (of %d; %d rejected), gates %s\n" % (info["labelled_ctus"], info["ctus"], info["rejected_ctus"], opt["gates"]))
+    for name, lv, ed, eu in zip(sizes, levels, opt["eps_down"], opt["eps_up"]):
+        out.write("%s  reached unsplit %d  reached split %d%s%s\n" % (name, lv["n0"], lv["n1"], "  EMPTY CLASS" if lv["empty_class"] else "",
+                                                                    "  CROSSED (one threshold for both)" if lv["crossed"] else ""))
+        out.write("    down %.10f (k %d)  wrongly stopped %d of %d split (budget %d ppm)\n" % (lv["down"], lv["down_k"], lv["miss"], lv["n1"], ed))
+        out.write("    up   %.10f (k %d)  wrongly forced  %d of %d unsplit (budget %d ppm)\n" % (lv["up"], lv["up_k"], lv["fsplit"], lv["n0"], eu))
+        out.write("    full search remains for %d (%.4f); accuracy at 0.5: %.4f\n" % (lv["uncertain"], lv["uncertain_share"], lv["accuracy_512"]))
+    for d, name in enumerate(sizes):
+        out.write("%-5s  checked %d of %d\n" % (name, int(counts["checked"][d]), int(full["checked"][d])))
+    out.write("%.6f of the full search (weights %s); bad CTUs %d of %d labelled\n" % (share, " ".join(str(w) for w in weights), int(counts["bad_ctus"]),
+                                                                                     info["labelled_ctus"]))
+    if opt["out"]:
+        out.write("wrote %s (%s order): %s" % (opt["out"], opt["order"], open(opt["out"]).read()))
+    return result
+
+
 def run(opt, cases, out=sys.stdout, err=sys.stderr):
     if ROOT not in sys.path:
         sys.path.insert(0, ROOT)
     pkg = importlib.import_module("hevc-complexity-reduction_amd")
     note = lambda s: err.write(s + "\n")
+    if opt.get("reached"):
+        return run_reached(pkg, opt, cases, out, note)
     ctx = pkg.EthCnn(device=opt["device"])
     try:
         cal = pkg.Calibrator(ctx)
