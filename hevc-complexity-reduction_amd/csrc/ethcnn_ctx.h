@@ -329,6 +329,29 @@ int pinned_pread(int fd, uint8_t* dst, size_t want, off_t off);  // file bytes -
 // ethcnn_ldp.cpp: the residual vectors of nf frames by the throughput stages, over passes of whole frames (the front-end of the
 // offline sequence calls and of ethcnn_ldp_group.cpp)
 int seq_front(ethcnn_ctx* c, const uint8_t* d_luma, const FrameGeom& g, int nf, float* d_vec);
+// ethcnn_ldp.cpp: recurrence + heads + gates of one chunk of nf frames (the first one carries i_frame i0) of k sequences; member m
+// brings its vectors d_vec[m], bundle image d_lstm[m], QP and probabilities d_probs[m].  sin[m]: the state in front of the first
+// frame (null = zeros); afterwards the state behind the last one, which is in sout[m].  The state is zeroed in front of every frame
+// with i_frame <= 1, so a run of frames that carries its state starts there: one recurrence launch per run, then one gate launch.
+// Returns hipGetLastError() behind them: every caller words its own message.
+hipError_t seq_recur(ethcnn_ctx* c, int k, const float* const* d_vec, const float** sin, float* const* sout, const float* const* d_lstm,
+                     const int* qp, float* const* d_probs, int nctu, int nf, int i0);
+// frames per chunk of k sequences: the caller's figure, else what keeps the vectors of all k within 256 MB.  With k = 1 this is
+// the solo formula, 256 MB / (nctu * 448 * 4) and at least one frame: seq_chunk_frames(nctu, nframes, chunk, 1) == min(nframes,
+// chunk > 0 ? chunk : max(1, (256 << 20) / (nctu * kNVec * 4))).
+inline int64_t seq_chunk_frames(int64_t nctu, int64_t nframes, int chunk, int k) {
+    return std::min<int64_t>(nframes, chunk > 0 ? (int64_t)chunk : std::max<int64_t>(1, (int64_t)(256 << 20) / ((int64_t)k * nctu * kNVec * 4)));
+}
+// a device buffer that has to hold `bytes`: nothing to do when *cap suffices; else frees *p and allocates anew.  false, with nothing
+// held, when they do not fit (the caller has summed what must grow, refused with the whole sum and synchronised before)
+inline bool seq_grow(float** p, size_t* cap, size_t bytes) {
+    if (bytes <= *cap) return true;
+    if (*p) (void)hipFree(*p);
+    *p = nullptr, *cap = 0;
+    if (hipMalloc((void**)p, bytes) != hipSuccess) { (void)hipGetLastError(); return false; }
+    *cap = bytes;
+    return true;
+}
 
 struct StageTimer {
     ethcnn_ctx* c;

@@ -319,16 +319,11 @@ extern "C" int ethcnn_ldp_predict_frame(ethcnn_ctx* c, const uint8_t* luma, int 
 // The result of nframes successive ethcnn_ldp_step calls (frame t: i_frame = i_frame_first + t), computed the way an offline job
 // should be: the front-end of a chunk of frames in the big multi-launch passes, then ONE recurrence launch per run of frames that
 // carries its state on chip (ethcnn_lstm_seq.hip), then the gate post-pass.  Chunks only bound the memory: the state goes from one
-// chunk to the next through the resident buffer, and the results do not depend on the chunk size.
-static int64_t seq_default_chunk(int nctu) { return std::max<int64_t>(1, (int64_t)(256 << 20) / ((int64_t)nctu * kNVec * 4)); }  // 256 MB of vectors
-static int64_t seq_chunk_frames(int nctu, int64_t nframes, int chunk) {
-    return std::min<int64_t>(nframes, chunk > 0 ? (int64_t)chunk : seq_default_chunk(nctu));
-}
-
+// chunk to the next through the resident buffer, and the results do not depend on the chunk size (seq_chunk_frames, ethcnn_ctx.h).
 extern "C" int64_t ethcnn_ldp_sequence_bytes(int w, int h, int nframes, int chunk_frames) {
     if (w <= 0 || h <= 0 || nframes <= 0 || chunk_frames < 0) return ETHCNN_ERR_ARG;
     const int64_t nctu = (int64_t)((w + 63) / 64) * ((h + 63) / 64), cap = (nctu + 15) / 16 * 16;
-    const int64_t F = seq_chunk_frames((int)nctu, nframes, chunk_frames);
+    const int64_t F = seq_chunk_frames(nctu, nframes, chunk_frames, 1);
     // vectors + probabilities of a chunk, the two resident (c, h) buffers; no projection scratch (the recurrence runs the x half itself)
     return F * nctu * kNVec * 4 + F * nctu * kNOut * 4 + 2 * cap * 2 * kNVec * 4;
 }
@@ -376,18 +371,8 @@ static int seq_ensure(ethcnn_ctx* c, int w, int h, int64_t nframes, int64_t F, b
                            (long long)F, (long long)ethcnn_ldp_sequence_bytes(w, h, (int)std::min<int64_t>(nframes, INT32_MAX), (int)F), free_b + back);
         HIPCHK(c, hipStreamSynchronize(c->stream));
     }
-    if (vb > c->seq_vec_cap) {
-        if (c->seq_vec) (void)hipFree(c->seq_vec);
-        c->seq_vec = nullptr, c->seq_vec_cap = 0;
-        if (hipMalloc((void**)&c->seq_vec, vb) != hipSuccess) { (void)hipGetLastError(); return set_err(c, ETHCNN_ERR_NOMEM, "ethcnn_ldp_sequence: %zu bytes of vectors do not fit", vb); }
-        c->seq_vec_cap = vb;
-    }
-    if (pb > c->seq_probs_cap) {
-        if (c->seq_probs) (void)hipFree(c->seq_probs);
-        c->seq_probs = nullptr, c->seq_probs_cap = 0;
-        if (hipMalloc((void**)&c->seq_probs, pb) != hipSuccess) { (void)hipGetLastError(); return set_err(c, ETHCNN_ERR_NOMEM, "ethcnn_ldp_sequence: %zu bytes of probabilities do not fit", pb); }
-        c->seq_probs_cap = pb;
-    }
+    if (!seq_grow(&c->seq_vec, &c->seq_vec_cap, vb)) return set_err(c, ETHCNN_ERR_NOMEM, "ethcnn_ldp_sequence: %zu bytes of vectors do not fit", vb);
+    if (!seq_grow(&c->seq_probs, &c->seq_probs_cap, pb)) return set_err(c, ETHCNN_ERR_NOMEM, "ethcnn_ldp_sequence: %zu bytes of probabilities do not fit", pb);
     if (nctu > c->lstm_cap) {  // (seq_check has made sure that no resident state is needed then: it belongs to another CTU count)
         c->state_cur = -1;
         *in = -1;
@@ -412,21 +397,30 @@ int seq_front(ethcnn_ctx* c, const uint8_t* d_luma, const FrameGeom& g, int nf, 
     return ETHCNN_OK;
 }
 
-// recurrence + heads + gates of nf frames whose vectors are in d_vec.  *sin: the state in front of the first frame (null = zeros);
-// afterwards the state behind the last one, which is in `sout`.  The state is zeroed in front of every frame with i_frame <= 1, so
-// a run of frames that carries its state starts there.
-static int seq_recur(ethcnn_ctx* c, const float* d_vec, int nctu, int nf, int qp, int i0, const float** sin, float* sout, float* d_probs) {
+// recurrence + heads + gates of a chunk for k sequences (ethcnn_ctx.h)
+hipError_t seq_recur(ethcnn_ctx* c, int k, const float* const* d_vec, const float** sin, float* const* sout, const float* const* d_lstm,
+                     const int* qp, float* const* d_probs, int nctu, int nf, int i0) {
     for (int f = 0; f < nf;) {
         const int i = i0 + f, run = (i <= 0) ? 1 : nf - f;
-        StageTimer t(c, ETHCNN_STAGE_HEADS, (long)nctu * run);
-        if (i <= 1) *sin = nullptr;
-        launch_lstm_seq(d_vec + (size_t)f * nctu * kNVec, *sin, sout, c->d_lstm, nctu, run, qp, i, d_probs + (size_t)f * nctu * kNOut, c->stream);
-        *sin = sout;
+        StageTimer t(c, ETHCNN_STAGE_HEADS, (long)nctu * run * k);
+        SeqMember mem[kLstmSeqGroupMax];
+        for (int m = 0; m < k; ++m) {
+            if (i <= 1) sin[m] = nullptr;
+            mem[m] = {d_vec[m] + (size_t)f * nctu * kNVec, sin[m], sout[m], d_lstm[m], d_probs[m] + (size_t)f * nctu * kNOut, lstm_seq_efs0(qp[m])};
+            sin[m] = sout[m];
+        }
+        launch_lstm_seq(mem, k, nctu, run, i, c->stream);
         f += run;
     }
-    { StageTimer tg(c, ETHCNN_STAGE_GATE); launch_lstm_seq_gates(d_probs, nctu, nf, c->thr1, c->thr2, c->stream); }
-    HIPCHK(c, hipGetLastError());
-    return ETHCNN_OK;
+    { StageTimer tg(c, ETHCNN_STAGE_GATE); launch_lstm_seq_gates(d_probs, k, nctu, nf, c->thr1, c->thr2, c->stream); }
+    return hipGetLastError();
+}
+
+// the solo calls: a group of one on the context's bundle and the chunk's vectors in c->seq_vec
+static int seq_recur_solo(ethcnn_ctx* c, int nctu, int nf, int qp, int i0, const float** sin, float* sout, float* d_probs) {
+    const float* const vec = c->seq_vec;
+    const hipError_t e = seq_recur(c, 1, &vec, sin, &sout, &c->d_lstm, &qp, &d_probs, nctu, nf, i0);
+    return e == hipSuccess ? ETHCNN_OK : set_err(c, ETHCNN_ERR_DEVICE, "hipGetLastError() failed: %s", hipGetErrorString(e));
 }
 
 extern "C" int ethcnn_ldp_sequence_device(ethcnn_ctx* c, const uint8_t* d_luma, int w, int h, ptrdiff_t pitch, ptrdiff_t fstride, int nframes,
@@ -439,7 +433,7 @@ extern "C" int ethcnn_ldp_sequence_device(ethcnn_ctx* c, const uint8_t* d_luma, 
     FrameGeom g;
     rc = make_geom(c, w, h, pitch, fstride, &g);
     if (rc) return rc;
-    const int64_t F = seq_chunk_frames(g.nctu, nframes, c->seq_chunk);
+    const int64_t F = seq_chunk_frames(g.nctu, nframes, c->seq_chunk, 1);
     rc = seq_ensure(c, w, h, nframes, F, false, &in);
     if (rc) return rc;
     const int out = in >= 0 ? in : 0;  // the resident state is advanced in place: a block stores only its own columns (ethcnn_lstm_seq.h)
@@ -448,7 +442,7 @@ extern "C" int ethcnn_ldp_sequence_device(ethcnn_ctx* c, const uint8_t* d_luma, 
     for (int64_t f0 = 0; f0 < nframes; f0 += F) {
         const int nf = (int)std::min<int64_t>(F, nframes - f0);
         rc = seq_front(c, d_luma + f0 * fstride, g, nf, c->seq_vec);
-        if (rc == 0) rc = seq_recur(c, c->seq_vec, g.nctu, nf, qp, i_first + (int)f0, &sin, c->d_state[out], d_probs + (size_t)f0 * g.nctu * kNOut);
+        if (rc == 0) rc = seq_recur_solo(c, g.nctu, nf, qp, i_first + (int)f0, &sin, c->d_state[out], d_probs + (size_t)f0 * g.nctu * kNOut);
         if (rc) return rc;
     }
     c->state_cur = out;
@@ -470,7 +464,7 @@ static int seq_host_run(ethcnn_ctx* c, const uint8_t* luma, int w, int h, ptrdif
     FrameGeom g;
     rc = make_geom(c, w, h, pitch, fstride, &g);
     if (rc) return rc;
-    const int64_t F = seq_chunk_frames(g.nctu, nframes, c->seq_chunk);
+    const int64_t F = seq_chunk_frames(g.nctu, nframes, c->seq_chunk, 1);
     rc = seq_ensure(c, w, h, nframes, F, true, &in);
     if (rc) return rc;
     const size_t last = (size_t)(h - 1) * pitch + w;  // the meaningful bytes of the last frame of a piece
@@ -511,7 +505,7 @@ static int seq_host_run(ethcnn_ctx* c, const uint8_t* luma, int w, int h, ptrdif
             SEQCHK(hipEventRecord(c->ev_in[b], c->stream));
             used[b] = true;
         }
-        if (rc == 0) rc = seq_recur(c, c->seq_vec, g.nctu, nf, qp, i_first + (int)f0, &sin, c->d_state[out], c->seq_probs);
+        if (rc == 0) rc = seq_recur_solo(c, g.nctu, nf, qp, i_first + (int)f0, &sin, c->d_state[out], c->seq_probs);
         if (rc == 0) rc = sink(c->seq_probs, f0, nf, pf);
     }
 #undef SEQCHK

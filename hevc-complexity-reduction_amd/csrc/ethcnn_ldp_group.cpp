@@ -1,7 +1,7 @@
 // ethcnn_ldp_group.cpp -- config #5 offline, group form (include/ethcnn.h): K residual sequences of one geometry, each with its own
 // ETH-LSTM bundle, QP, state and output, through ONE recurrence launch per run of frames.  Member m's result is what
-// ethcnn_ldp_sequence_device gives on a context that holds m's bundle, bit for bit: the blocks of a member run the solo kernel's body
-// on the member's pointers (ethcnn_lstm_seq.hip), the front-end is the solo call's (seq_front, per member).
+// ethcnn_ldp_sequence_device gives on a context that holds m's bundle, bit for bit: that call is a group of one through the same
+// front-end (seq_front, per member), run loop (seq_recur) and kernels (ethcnn_lstm_seq.hip).
 #include "ethcnn_ctx.h"
 #include "ethcnn_ldp_group.h"
 
@@ -23,11 +23,6 @@ int gerr(ethcnn_ldp_group* g, int code, const char* fmt, ...) {
 
 constexpr int64_t kStateFloats = 2 * kNVec;  // (c, h) of a CTU
 
-int64_t group_default_chunk(int64_t nctu, int k) { return std::max<int64_t>(1, (int64_t)(256 << 20) / ((int64_t)k * nctu * kNVec * 4)); }
-int64_t group_chunk_frames(int64_t nctu, int64_t nframes, int chunk, int k) {
-    return std::min<int64_t>(nframes, chunk > 0 ? (int64_t)chunk : group_default_chunk(nctu, k));
-}
-
 int check_member(ethcnn_ldp_group* g, int m, const char* who) {
     if (m < 0 || m >= g->k) return gerr(g, ETHCNN_ERR_ARG, "%s: member %d outside 0..%d", who, m, g->k - 1);
     return 0;
@@ -48,7 +43,7 @@ int upload_member(ethcnn_ldp_group* g, int m) {
 extern "C" int64_t ethcnn_ldp_group_bytes(int w, int h, int nframes, int chunk_frames, int k) {
     if (w <= 0 || h <= 0 || nframes <= 0 || chunk_frames < 0 || k < 1 || k > kLstmSeqGroupMax) return ETHCNN_ERR_ARG;
     const int64_t nctu = (int64_t)((w + 63) / 64) * ((h + 63) / 64), cap = (nctu + 15) / 16 * 16;
-    const int64_t F = group_chunk_frames(nctu, nframes, chunk_frames, k);
+    const int64_t F = seq_chunk_frames(nctu, nframes, chunk_frames, k);
     return k * F * nctu * kNVec * 4 + k * cap * kStateFloats * 4;
 }
 
@@ -171,7 +166,7 @@ extern "C" int ethcnn_ldp_group_sequence_device(ethcnn_ldp_group* g, const uint8
     FrameGeom geom;
     if (int rc = make_geom(c, w, h, pitch, fstride, &geom)) return gerr(g, rc, "%s", c->err.c_str());
     // ---- buffers: refused with the whole sum before anything is allocated
-    const int64_t F = group_chunk_frames(nctu, nframes, g->chunk, K);
+    const int64_t F = seq_chunk_frames(nctu, nframes, g->chunk, K);
     const int cap = (nctu + 15) / 16 * 16;
     const size_t slice = (size_t)F * nctu * kNVec, vb = (size_t)K * slice * 4, sb = (size_t)K * cap * kStateFloats * 4;
     GCHK(g, hipSetDevice(c->device));
@@ -185,25 +180,24 @@ extern "C" int ethcnn_ldp_group_sequence_device(ethcnn_ldp_group* g, const uint8
             return gerr(g, ETHCNN_ERR_NOMEM, "ethcnn_ldp_group_sequence: %d members in chunks of %lld frames hold %lld bytes on the device (ethcnn_ldp_group_bytes); %zu are free",
                         K, (long long)F, (long long)ethcnn_ldp_group_bytes(w, h, (int)F, (int)F, K), free_b + back);
         GCHK(g, hipStreamSynchronize(c->stream));
-        if (vb > g->vec_cap) {
-            if (g->d_vec) (void)hipFree(g->d_vec);
-            g->d_vec = nullptr, g->vec_cap = 0;
-            if (hipMalloc((void**)&g->d_vec, vb) != hipSuccess) { (void)hipGetLastError(); return gerr(g, ETHCNN_ERR_NOMEM, "ethcnn_ldp_group_sequence: %zu bytes of vectors do not fit", vb); }
-            g->vec_cap = vb;
-        }
+        if (!seq_grow(&g->d_vec, &g->vec_cap, vb)) return gerr(g, ETHCNN_ERR_NOMEM, "ethcnn_ldp_group_sequence: %zu bytes of vectors do not fit", vb);
         if (cap > g->state_cap) {  // (no member continues from a resident state then: it would belong to a smaller CTU count)
-            if (g->d_state) (void)hipFree(g->d_state);
-            g->d_state = nullptr, g->state_cap = 0;
+            size_t held = 0;  // (state_cap counts CTUs per member, not bytes)
+            g->state_cap = 0;
             for (int m = 0; m < K; ++m) g->m[m].state_nctu = -1;
-            if (hipMalloc((void**)&g->d_state, sb) != hipSuccess) { (void)hipGetLastError(); return gerr(g, ETHCNN_ERR_NOMEM, "ethcnn_ldp_group_sequence: %zu bytes of states do not fit", sb); }
+            if (!seq_grow(&g->d_state, &held, sb)) return gerr(g, ETHCNN_ERR_NOMEM, "ethcnn_ldp_group_sequence: %zu bytes of states do not fit", sb);
             g->state_cap = cap;
         }
     }
     // ---- the chunk loop.  A member's resident state is advanced in place: a block stores only its own columns (ethcnn_lstm_seq.h)
     c->done_armed = 0;
     const float* sin[kLstmSeqGroupMax];
+    const float* vec[kLstmSeqGroupMax];
+    const float* lstm[kLstmSeqGroupMax];
     float* sout[kLstmSeqGroupMax];
     for (int m = 0; m < K; ++m) {
+        vec[m] = g->d_vec + (size_t)m * slice;
+        lstm[m] = g->m[m].d_lstm;
         sout[m] = g->d_state + (size_t)m * g->state_cap * kStateFloats;
         sin[m] = i_first > 1 ? ((d_state_in && d_state_in[m]) ? d_state_in[m] : sout[m]) : nullptr;
         g->m[m].state_nctu = -1;  // until every frame has been enqueued
@@ -213,28 +207,9 @@ extern "C" int ethcnn_ldp_group_sequence_device(ethcnn_ldp_group* g, const uint8
         for (int m = 0; m < K; ++m)
             if (int rc = seq_front(c, d_luma[m] + f0 * fstride, geom, nf, g->d_vec + (size_t)m * slice))
                 return gerr(g, rc, "member %d: %s (the resident states of the group were dropped)", m, c->err.c_str());
-        // the runs of the solo call (seq_recur): the state is zeroed in front of every frame with i_frame <= 1
         float* probs[kLstmSeqGroupMax];
         for (int m = 0; m < K; ++m) probs[m] = d_probs[m] + (size_t)f0 * nctu * kNOut;
-        for (int f = 0; f < nf;) {
-            const int i = i_first + (int)f0 + f, run = (i <= 0) ? 1 : nf - f;
-            StageTimer t(c, ETHCNN_STAGE_HEADS, (long)nctu * run * K);
-            SeqMember mem[kLstmSeqGroupMax];
-            for (int m = 0; m < K; ++m) {
-                if (i <= 1) sin[m] = nullptr;
-                mem[m].vec = g->d_vec + (size_t)m * slice + (size_t)f * nctu * kNVec;
-                mem[m].state_in = sin[m];
-                mem[m].state_out = sout[m];
-                mem[m].blob = g->m[m].d_lstm;
-                mem[m].probs = probs[m] + (size_t)f * nctu * kNOut;
-                mem[m].efs0 = lstm_seq_efs0(qp[m]);
-                sin[m] = sout[m];
-            }
-            launch_lstm_seq_group(mem, K, nctu, run, i, c->stream);
-            f += run;
-        }
-        { StageTimer tg(c, ETHCNN_STAGE_GATE); launch_lstm_seq_gates_group(probs, K, nctu, nf, c->thr1, c->thr2, c->stream); }
-        const hipError_t e = hipGetLastError();
+        const hipError_t e = seq_recur(c, K, vec, sin, sout, lstm, qp, probs, nctu, nf, i_first + (int)f0);
         if (e != hipSuccess) return gerr(g, ETHCNN_ERR_DEVICE, "launch failed: %s (the resident states of the group were dropped)", hipGetErrorString(e));
     }
     for (int m = 0; m < K; ++m) g->m[m].state_nctu = nctu;

@@ -1,7 +1,7 @@
 // ethcnn_ldp_group.h -- internal: the object behind ethcnn_ldp_group_* (include/ethcnn.h "config #5 offline, group form").
 // K sequences of one geometry go through the offline Low-Delay-P chain together: the front-end per member (seq_front into the member's
 // slice of the vector buffer), then ONE recurrence launch per run of frames and ONE gate launch per chunk for all members
-// (ethcnn_lstm_seq.h, group form).  The context's own bundle, resident state and sequence buffers are neither used nor changed.
+// (seq_recur in ethcnn_ctx.h, ethcnn_lstm_seq.h).  The context's own bundle, resident state and sequence buffers are neither used nor changed.
 #pragma once
 #include <string>
 #include <vector>

@@ -45,10 +45,9 @@ struct LstmParams {
     float efs[5];       // [qp/51*0.18, onehot4(i_frame % 4)]
 };
 
-// float offsets into the blob per level (64, 32, 16): fc2_b, fc2_w, fc3_b, fc3_w, bias, kernel
-__device__ __constant__ int kLstmOff[3][6] = {{723640, 723688, 727000, 727001, 727054, 727310},
-                                              {578784, 578880, 591648, 591652, 592056, 592568},
-                                              {0, 192, 50304, 50320, 53472, 54496}};
+// the level table of ethcnn_spec.h in constant memory: with the offsets as immediates k_lstm_frame<2> and k_lstm_cell<2> take one
+// VGPR more each
+__device__ __constant__ LstmOffTable kLstmOffMem = kLstmOff;
 
 // Two launches per frame, both latency-oriented (few hundred CTUs, lock-step with the encoder):
 //   k_lstm_cell : one block per (16 CG CTUs, hidden tile of 16 units), one wave per gate: its accumulator is a
@@ -60,15 +59,6 @@ __device__ __constant__ int kLstmOff[3][6] = {{723640, 723688, 727000, 727001, 7
 //                 state_out (L2) as the B operand; h2 crosses waves through LDS in [tile][g][ctu][r]
 //                 order (the writer's C-layout quad and the reader's B-operand quad of lane (ctu, g)
 //                 are the same float4 slot); wave 0 finishes fc3 + sigmoid + gate predicates.
-template <int LV>
-struct LstmDims {
-    static constexpr int N = (LV == 0) ? 64 : (LV == 1 ? 128 : 256);
-    static constexpr int N2 = (LV == 0) ? 48 : (LV == 1 ? 96 : 192);
-    static constexpr int N3 = (LV == 0) ? 1 : (LV == 1 ? 4 : 16);
-    static constexpr int O1 = (LV == 0) ? 0 : (LV == 1 ? 64 : 192);
-    static constexpr int O3 = (LV == 0) ? 0 : (LV == 1 ? 1 : 5);
-    static constexpr int NT = N / 16, NT2 = N2 / 16;
-};
 
 // One gate (wave q) of hidden tile t for CG column groups of 16 CTUs: the kernel rows fetched once feed CG MFMAs.  What
 // set this kernel's time was not bandwidth but one exposed memory latency per prefetch window (a 4- or 8-chunk-deep
@@ -82,7 +72,7 @@ __device__ __forceinline__ void lstm_cell(const LstmParams& lp, const float* __r
     using D = LstmDims<LV>;
     constexpr int N = D::N, O1 = D::O1, NC = 2 * N / 16;
     const int col = lane & 15, g = lane >> 4;
-    const float* bk = lp.blob + kLstmOff[LV][4];
+    const float* bk = lp.blob + kLstmOffMem.v[LV][4];
     // wave q owns gate q (i, j, f, o) of the tile: ONE accumulator per column group, the same chain as ever (k = 16 c + 4 g + e);
     // its A operands come from the packed copy of the kernel (ethcnn_spec.h): one dwordx4 per lane per chunk, 1 KB runs
     const float* kpk = lp.blob + kLstmBlobFloats + kLstmPackOff[LV] + (size_t)((t * 4 + q) * NC) * 256 + lane * 4;
@@ -195,10 +185,10 @@ __device__ __forceinline__ void lstm_heads(const LstmParams& lp, const float* __
     using D = LstmDims<LV>;
     constexpr int N = D::N, N2 = D::N2, N3 = D::N3, O1 = D::O1, O3 = D::O3, NT = D::NT, NT2 = D::NT2;
     const int col = lane & 15, g = lane >> 4;
-    const float* b2 = lp.blob + kLstmOff[LV][0];
-    const float* W2 = lp.blob + kLstmOff[LV][1];
-    const float* b3 = lp.blob + kLstmOff[LV][2];
-    const float* W3 = lp.blob + kLstmOff[LV][3];
+    const float* b2 = lp.blob + kLstmOffMem.v[LV][0];
+    const float* W2 = lp.blob + kLstmOffMem.v[LV][1];
+    const float* b3 = lp.blob + kLstmOffMem.v[LV][2];
+    const float* W3 = lp.blob + kLstmOffMem.v[LV][3];
     // fc2^T: wave j owns output tile j; step (t, r) consumes k = 16 t + 4 g + r.  Latency form: ALL operands of the tile (64 W2
     // values and 16 h quads per lane at level 16) are requested before the first MFMA -- fetched a step ahead, the loop paid
     // one L2 round trip per step with the GPU otherwise idle (round 3: 1080p LSTM heads 17 -> see profiles/r03_latency_ldp.txt)
@@ -506,8 +496,8 @@ __device__ __forceinline__ void lstm_frame_heads(const LstmFrameParams& P, const
     const int wave = __builtin_amdgcn_readfirstlane((int)(threadIdx.x >> 6));
     const int col = lane & 15, gq = lane >> 4;
     const float* blob = P.lp.blob;
-    const float* W2 = blob + kLstmOff[LV][1];
-    const float* W3 = blob + kLstmOff[LV][3];
+    const float* W2 = blob + kLstmOffMem.v[LV][1];
+    const float* W3 = blob + kLstmOffMem.v[LV][3];
     // LDS: [h2 exchange NT2 x 256][efs rows of W2: 5 x N2][b2: N2][W3 incl. its efs rows: (N2 + 5) x N3][b3: N3]
     f32x4* const h2T = reinterpret_cast<f32x4*>(smem);
     float* const sE = smem + NT2 * 256;
@@ -533,9 +523,9 @@ __device__ __forceinline__ void lstm_frame_heads(const LstmFrameParams& P, const
             _Pragma("unroll") for (int jj = 0; jj < TPW; ++jj)                                                          \
                 wr[t][jj] = __builtin_bit_cast(f32x4, __builtin_amdgcn_raw_buffer_load_b128(rWl, voff, tile_off[jj] + t * 1024, 0)); \
         for (int i = threadIdx.x; i < 5 * N2; i += 256) sE[i] = W2[N * N2 + i];                                         \
-        for (int i = threadIdx.x; i < N2; i += 256) sB2[i] = blob[kLstmOff[LV][0] + i];                                 \
+        for (int i = threadIdx.x; i < N2; i += 256) sB2[i] = blob[kLstmOffMem.v[LV][0] + i];                                 \
         for (int i = threadIdx.x; i < (N2 + 5) * N3; i += 256) sW3[i] = W3[i];                                          \
-        if (threadIdx.x < N3) sB3[threadIdx.x] = blob[kLstmOff[LV][2] + threadIdx.x];                                   \
+        if (threadIdx.x < N3) sB3[threadIdx.x] = blob[kLstmOffMem.v[LV][2] + threadIdx.x];                                   \
     }
 #define LF_WAIT(budget, result)                                                                                         \
     {                                                                                                                   \

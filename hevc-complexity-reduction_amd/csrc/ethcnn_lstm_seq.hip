@@ -25,24 +25,10 @@ namespace ethcnn {
 typedef float f32x4 __attribute__((ext_vector_type(4)));
 #define MFMA16(a, b, c) __builtin_amdgcn_mfma_f32_16x16x4f32((a), (b), (c), 0, 0, 0)
 
-// The activation functions are the shared canonical ones (ethcnn_canon_math.h).  ---- TWINS of ethcnn_lstm.hip: kLstmOff and LstmDims
-// there are the same tables as kSeqOff / SeqDims here; tests/test_gpu_ldp_sequence.py compares the two paths bit for bit on every level.
+// The activation functions are the shared canonical ones (ethcnn_canon_math.h), the level tables (kLstmOff, LstmDims) those of
+// ethcnn_spec.h, as in ethcnn_lstm.hip.
 
-// float offsets into the blob per level (64, 32, 16): fc2_b, fc2_w, fc3_b, fc3_w, bias (the table of ethcnn_lstm.hip)
-__device__ __constant__ int kSeqOff[3][5] = {{723640, 723688, 727000, 727001, 727054},
-                                             {578784, 578880, 591648, 591652, 592056},
-                                             {0, 192, 50304, 50320, 53472}};
-
-template <int LV>
-struct SeqDims {
-    static constexpr int N = (LV == 0) ? 64 : (LV == 1 ? 128 : 256);
-    static constexpr int N2 = (LV == 0) ? 48 : (LV == 1 ? 96 : 192);
-    static constexpr int N3 = (LV == 0) ? 1 : (LV == 1 ? 4 : 16);
-    static constexpr int O1 = (LV == 0) ? 0 : (LV == 1 ? 64 : 192);
-    static constexpr int O3 = (LV == 0) ? 0 : (LV == 1 ? 1 : 5);
-    static constexpr int NT = N / 16, NT2 = N2 / 16;
-};
-
+// what the body below works on: one member's row of the launch's table and the launch's scalars
 struct SeqParams {
     const float* vec;       // [F][n][448]
     const float* state_in;  // [n][2][448] or null
@@ -59,7 +45,7 @@ constexpr int kSeqWaves = 16;   // per block
 
 template <int LV>
 __device__ __forceinline__ void lstm_seq_level(const SeqParams& P, int blk, f32x4* smem) {
-    using D = SeqDims<LV>;
+    using D = LstmDims<LV>;
     constexpr int N = D::N, N2 = D::N2, N3 = D::N3, O1 = D::O1, O3 = D::O3, NT = D::NT, NT2 = D::NT2, NC = 2 * NT;
     constexpr int SL = kSeqWaves / NT;  // column groups of the block
     const int lane = threadIdx.x & 63;
@@ -80,11 +66,11 @@ __device__ __forceinline__ void lstm_seq_level(const SeqParams& P, int blk, f32x
     f32x4* const hb1 = hb0 + NT * 64;
 
     const float* const blob = P.blob;
-    const float* const bk = blob + kSeqOff[LV][4];
-    const float* const b2_0 = blob + kSeqOff[LV][0];
-    const float* const W2_0 = blob + kSeqOff[LV][1];
-    const float* const b3_0 = blob + kSeqOff[LV][2];
-    const float* const W3_0 = blob + kSeqOff[LV][3];
+    const float* const bk = blob + kLstmOff.v[LV][4];
+    const float* const b2_0 = blob + kLstmOff.v[LV][0];
+    const float* const W2_0 = blob + kLstmOff.v[LV][1];
+    const float* const b3_0 = blob + kLstmOff.v[LV][2];
+    const float* const W3_0 = blob + kLstmOff.v[LV][3];
     // gate q, chunk kc of tile t: one 1 KB run, a dwordx4 per lane (ethcnn_spec.h)
     // buffer loads: wave-uniform base + scalar offset of the (gate, chunk) run + lane * 16 -- no address registers per load (the runs lie
     // up to 128 KB apart, far beyond the immediate offset of a global load)
@@ -243,52 +229,27 @@ __device__ __forceinline__ void lstm_seq_level(const SeqParams& P, int blk, f32x
     }
 }
 
-// blocks [0, G): level 16, one column group each (the long chains first); then ceil(G / 2) of level 32; then ceil(G / 4) of level 64
-__global__ __launch_bounds__(1024) void k_lstm_seq(SeqParams P) {
-    __shared__ f32x4 smem[kSeqWaves * 3 * 64 + ((192 + 5) * 16 + 16) / 4];  // 48 KB of quads + the fc3 operands (12.4 KB at level 16)
-    const int b = (int)blockIdx.x, n2 = P.groups, n1 = (P.groups + 1) / 2;
-    if (b < n2) lstm_seq_level<2>(P, b, smem);
-    else if (b < n2 + n1) lstm_seq_level<1>(P, b - n2, smem);
-    else lstm_seq_level<0>(P, b - n2 - n1, smem);
-}
-
-void launch_lstm_seq(const float* d_vec, const float* d_state_in, float* d_state_out, const float* d_lstm_blob, int n, int nframes,
-                     int qp, int i_frame0, float* d_probs, hipStream_t s) {
-    SeqParams P;
-    P.vec = d_vec;
-    P.state_in = d_state_in;
-    P.state_out = d_state_out;
-    P.blob = d_lstm_blob;
-    P.probs = d_probs;
-    P.n = n;
-    P.groups = (n + 15) / 16;
-    P.F = nframes;
-    P.i_frame0 = i_frame0;
-    P.efs0 = ((float)qp / 51.0f) * 0.18f;  // net():283  qp / 51.0 * 0.18
-    const unsigned blocks = (unsigned)(P.groups + (P.groups + 1) / 2 + (P.groups + 3) / 4);
-    hipLaunchKernelGGL(k_lstm_seq, dim3(blocks), dim3(64 * kSeqWaves), 0, s, P);
-}
-
-// ---- group form: K independent sequences of one geometry in the same launch.  The kernel only chooses whose SeqParams a block works
-// on and calls the body above.  Linear grid, level-major, the member index fastest: [level 16: G x K][level 32: ceil(G / 2) x K]
-// [level 64: ceil(G / 4) x K] -- when K x blocks exceeds the compute units every member's long chains are dispatched first, as in the
-// solo kernel.  The member table travels by value in the kernel arguments (404 bytes; the member index is block-uniform, so a block
-// reads its row with scalar loads): no device copy that would have to be kept current with bundles and buffers.  No block reads
-// what another member's block writes; a member's state_in and state_out may be the same buffer under the rule of ethcnn_lstm_seq.h.
+// K independent sequences of one geometry in one launch (a solo sequence is K = 1).  The kernel only chooses whose row of the member
+// table a block works on and calls the body above.  Linear grid, level-major, the member index fastest: [level 16: G x K, one column
+// group each (the long chains first)][level 32: ceil(G / 2) x K][level 64: ceil(G / 4) x K] -- when K x blocks exceeds the compute
+// units every member's long chains are dispatched first.  The member table travels by value in the kernel arguments (404 bytes; the
+// member index is block-uniform, so a block reads its row with scalar loads): no device copy that would have to be kept current with
+// bundles and buffers.  No block reads what another member's block writes; a member's state_in and state_out may be the same buffer
+// under the rule of ethcnn_lstm_seq.h.
 struct SeqGroupParams {
     SeqMember m[kLstmSeqGroupMax];
     int k, n, groups, F;
     int i_frame0;
 };
 
-__global__ __launch_bounds__(1024) void k_lstm_seq_group(SeqGroupParams G) {
-    __shared__ f32x4 smem[kSeqWaves * 3 * 64 + ((192 + 5) * 16 + 16) / 4];
+__global__ __launch_bounds__(1024) void k_lstm_seq(SeqGroupParams G) {
+    __shared__ f32x4 smem[kSeqWaves * 3 * 64 + ((192 + 5) * 16 + 16) / 4];  // 48 KB of quads + the fc3 operands (12.4 KB at level 16)
     const int K = G.k, n2 = G.groups * K, n1 = ((G.groups + 1) / 2) * K;
     const int b = (int)blockIdx.x;
     const int r = b < n2 ? b : (b < n2 + n1 ? b - n2 : b - n2 - n1);  // position inside the level
     const int blk = r / K;
     const SeqMember& M = G.m[r - blk * K];
-    SeqParams P;
+    SeqParams P;  // (a local copy of the row, not a reference into the arguments: the body keeps its fields in registers)
     P.vec = M.vec;
     P.state_in = M.state_in;
     P.state_out = M.state_out;
@@ -304,7 +265,7 @@ __global__ __launch_bounds__(1024) void k_lstm_seq_group(SeqGroupParams G) {
     else lstm_seq_level<0>(P, blk, smem);
 }
 
-void launch_lstm_seq_group(const SeqMember* members, int k, int n, int nframes, int i_frame0, hipStream_t s) {
+void launch_lstm_seq(const SeqMember* members, int k, int n, int nframes, int i_frame0, hipStream_t s) {
     SeqGroupParams G;
     for (int m = 0; m < kLstmSeqGroupMax; ++m) G.m[m] = members[m < k ? m : 0];
     G.k = k;
@@ -313,7 +274,7 @@ void launch_lstm_seq_group(const SeqMember* members, int k, int n, int nframes, 
     G.F = nframes;
     G.i_frame0 = i_frame0;
     const unsigned blocks = (unsigned)(k * (G.groups + (G.groups + 1) / 2 + (G.groups + 3) / 4));
-    hipLaunchKernelGGL(k_lstm_seq_group, dim3(blocks), dim3(64 * kSeqWaves), 0, s, G);
+    hipLaunchKernelGGL(k_lstm_seq, dim3(blocks), dim3(64 * kSeqWaves), 0, s, G);
 }
 
 // ---- gates: the tf.cond pair of net():305,317 per (frame, mini-batch of 1024 CTUs).  One block owns the mini-batch: it reduces the
@@ -339,28 +300,20 @@ __device__ __forceinline__ void lstm_seq_gates_body(float* __restrict__ probs, i
     }
 }
 
-__global__ __launch_bounds__(256) void k_lstm_seq_gates(float* __restrict__ probs, int n, int chunks, float thr1, float thr2) {
-    lstm_seq_gates_body(probs, n, chunks, thr1, thr2);
-}
-
-// group form: grid (frames x mini-batches, K); the member is blockIdx.y, the body above runs over its probabilities
+// grid (frames x mini-batches, K): the member is blockIdx.y, the body above runs over its probabilities (as a function of its own, with
+// a __restrict__ pointer: written into the kernel it costs two more registers)
 struct SeqGateGroup {
     float* probs[kLstmSeqGroupMax];
 };
-__global__ __launch_bounds__(256) void k_lstm_seq_gates_group(SeqGateGroup Q, int n, int chunks, float thr1, float thr2) {
+__global__ __launch_bounds__(256) void k_lstm_seq_gates(SeqGateGroup Q, int n, int chunks, float thr1, float thr2) {
     lstm_seq_gates_body(Q.probs[blockIdx.y], n, chunks, thr1, thr2);
 }
 
-void launch_lstm_seq_gates(float* d_probs, int n, int nframes, float thr1, float thr2, hipStream_t s) {
-    const unsigned chunks = (unsigned)((n + kSubBatch - 1) / kSubBatch);
-    hipLaunchKernelGGL(k_lstm_seq_gates, dim3(chunks * (unsigned)nframes), dim3(256), 0, s, d_probs, n, (int)chunks, thr1, thr2);
-}
-
-void launch_lstm_seq_gates_group(float* const* d_probs, int k, int n, int nframes, float thr1, float thr2, hipStream_t s) {
+void launch_lstm_seq_gates(float* const* d_probs, int k, int n, int nframes, float thr1, float thr2, hipStream_t s) {
     SeqGateGroup Q;
     for (int m = 0; m < kLstmSeqGroupMax; ++m) Q.probs[m] = d_probs[m < k ? m : 0];
     const unsigned chunks = (unsigned)((n + kSubBatch - 1) / kSubBatch);
-    hipLaunchKernelGGL(k_lstm_seq_gates_group, dim3(chunks * (unsigned)nframes, (unsigned)k), dim3(256), 0, s, Q, n, (int)chunks, thr1, thr2);
+    hipLaunchKernelGGL(k_lstm_seq_gates, dim3(chunks * (unsigned)nframes, (unsigned)k), dim3(256), 0, s, Q, n, (int)chunks, thr1, thr2);
 }
 
 }  // namespace ethcnn

@@ -131,14 +131,30 @@ extern const TensorDesc kTensors[kNumTensors];  // bundle (sorted-key) order
 constexpr int kNumLstmTensors = 18;
 extern const TensorDesc kLstmTensors[kNumLstmTensors];
 constexpr size_t kLstmBlobFloats = 760078;  // 3,040,312-byte .data payload
+// float offsets into the blob per level (64, 32, 16): fc2_b, fc2_w [N + 5][N2], fc3_b, fc3_w, LSTMCell bias, LSTMCell kernel
+// (a struct, so that a translation unit can hold a copy-initialised image of it in device memory: ethcnn_lstm.hip)
+struct LstmOffTable {
+    int v[3][6];
+};
+constexpr LstmOffTable kLstmOff = {{{723640, 723688, 727000, 727001, 727054, 727310},
+                                    {578784, 578880, 591648, 591652, 592056, 592568},
+                                    {0, 192, 50304, 50320, 53472, 54496}}};
+// widths of level LV: LSTM units (= fc1 slice), fc2, fc3; the level's first column in the 448-float vector and in the 21 outputs
+template <int LV>
+struct LstmDims {
+    static constexpr int N = (LV == 0) ? 64 : (LV == 1 ? 128 : 256);
+    static constexpr int N2 = (LV == 0) ? 48 : (LV == 1 ? 96 : 192);
+    static constexpr int N3 = (LV == 0) ? 1 : (LV == 1 ? 4 : 16);
+    static constexpr int O1 = (LV == 0) ? 0 : (LV == 1 ? 64 : 192);
+    static constexpr int O3 = (LV == 0) ? 0 : (LV == 1 ? 1 : 5);
+    static constexpr int NT = N / 16, NT2 = N2 / 16;
+};
 // LSTMCell kernels [2N][4N] re-laid for the gate-per-wave cell kernel (ethcnn_lstm.hip), appended to the blob on the device:
 // level LV (N = 64 / 128 / 256): [tile N/16][gate 4][chunk 2N/16][lane 64][e 4] = K[16 chunk + 4 g + e][gate N + 16 tile + col],
 // lane = col + 16 g -- one contiguous 1 KB run per (tile, gate, chunk), a dwordx4 per lane
-constexpr int kLstmKernelOff[3] = {727310, 592568, 54496};    // float offsets of the three kernels inside the blob
 constexpr int kLstmPackOff[3] = {0, 32768, 163840};           // float offsets inside the packed area
 // ... followed by the fc2 matrices' first N rows in MFMA-operand order (the one-launch LDP frame kernel's heads, ethcnn_lstm.hip):
 // level LV: [tile N2/16][chunk N/16][lane 64][r 4] = W2[16 chunk + 4 g + r][16 tile + col]
-constexpr int kLstmFc2Off[3] = {723688, 578880, 192};         // float offsets of the fc2 matrices [N + 5][N2] inside the blob
 constexpr int kLstmPackFc2Off[3] = {688128, 691200, 703488};  // 64 x 48, 128 x 96, 256 x 192 floats
 constexpr size_t kLstmPackFloats = 752640;
 

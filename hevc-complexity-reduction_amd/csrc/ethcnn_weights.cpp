@@ -629,7 +629,7 @@ void pack_fc2_lane_image(const float* w2, int n1, int n2, float* img) {
 void pack_lstm_kernels(const float* blob, float* out) {
     for (int lv = 0; lv < 3; ++lv) {
         const int N = 64 << lv, NC = 2 * N / 16;
-        const float* K = blob + kLstmKernelOff[lv];  // [2N][4N], gate order i, j, f, o
+        const float* K = blob + kLstmOff.v[lv][5];  // [2N][4N], gate order i, j, f, o
         float* o = out + kLstmPackOff[lv];
         for (int t = 0; t < N / 16; ++t)
             for (int q = 0; q < 4; ++q)
@@ -641,7 +641,7 @@ void pack_lstm_kernels(const float* blob, float* out) {
                         }
         // fc2, rows 0 .. N-1 (the 5 efs rows stay where they are)
         const int N2 = 48 << lv;
-        const float* W2 = blob + kLstmFc2Off[lv];
+        const float* W2 = blob + kLstmOff.v[lv][1];
         float* o2 = out + kLstmPackFc2Off[lv];
         for (int j = 0; j < N2 / 16; ++j)
             for (int t = 0; t < N / 16; ++t)

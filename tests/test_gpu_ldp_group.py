@@ -1,7 +1,8 @@
 """-m gpu: K Low-Delay-P residual sequences through one recurrence launch (include/ethcnn.h "config #5 offline, group form") against
 the definition: member m's probabilities and resident state are what ethcnn_ldp_sequence_device gives on a context loaded with m's
 bundle, for m's input and QP.  Every comparison is array_equal on the raw 32-bit words.  Bundles are seeded, with a seed, head gain
-and QP of their own per member; one member of one case is the reference's real QP-32 bundle.
+and QP of their own per member; one member of one case is the reference's real QP-32 bundle.  That call runs the group's kernels as
+a group of one, so the block and member arithmetic is also held to the per-frame ethcnn_ldp_step loop and to the CPU oracle.
 
 Shapes: the smallest at which a part of the block mapping can go wrong -- 1 CTU; 12 CTUs (one ragged 16-CTU group); 17 (a full group
 and a ragged one: the level-32 block owns both, the level-64 block has two surplus groups); 65 (a second level-64 block with one
@@ -131,6 +132,35 @@ def test_every_member_equals_its_solo_call(pkg, ctx, w, h, nf, first, bundles):
         for m in range(k):
             _same(got[m], want[m][0], "member %d: probabilities" % m)
             _same(g.get_state(m), want[m][1], "member %d: state" % m)
+
+
+_LOOPS = {}  # (width, height, member) -> (frames, probabilities, final state) of the per-frame loop: computed once, never changed
+
+
+def _loop(c, w, h, m):
+    """the definition, independent of the sequence kernels: ethcnn_ldp_step frame after frame from i_frame 0 on the context loaded
+    with member m's bundle (tests/test_gpu_ldp_sequence.py) -> (frames, probabilities, final state)"""
+    if (w, h, m) not in _LOOPS:
+        b, lum = BUNDLES[m], _frames(2000 + 10 * w + m, w, h, 5)
+        _load_ctx(c, b)
+        probs = np.stack([c.ldp_step(lum[t], w, h, b[2], t).copy() for t in range(5)])
+        _LOOPS[(w, h, m)] = (lum, probs, c.ldp_get_state(w, h))
+    return _LOOPS[(w, h, m)]
+
+
+@pytest.mark.parametrize("k", [1, 3])
+@pytest.mark.parametrize("w,h", [(64, 64), (1088, 64)])
+def test_every_member_equals_its_per_frame_loop(pkg, ctx, w, h, k):
+    """The solo call runs the group's kernel as a group of one, so "member equals solo" does not hold the kernel's member and block
+    arithmetic to anything of its own: this does.  64x64: 1 CTU, one ragged column group, every level's block has surplus slots;
+    1088x64: 17 CTUs, a second column group with one valid column, surplus column groups in the level-32 and level-64 blocks.  Five
+    frames from i_frame 0: runs of 1 + 4 frames, the state zeroed twice."""
+    loops = [_loop(ctx, w, h, m) for m in range(k)]
+    with _group(pkg, ctx, BUNDLES[:k]) as g:
+        got = g.sequence([lp[0] for lp in loops], w, h, [b[2] for b in BUNDLES[:k]], i_frame_first=0)
+        for m in range(k):
+            _same(got[m], loops[m][1], "member %d of %d: probabilities" % (m, k))
+            _same(g.get_state(m), loops[m][2], "member %d of %d: state" % (m, k))
 
 
 def test_a_member_moved_and_four_equal_members(pkg, ctx):
