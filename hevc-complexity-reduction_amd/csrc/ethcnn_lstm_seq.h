@@ -35,6 +35,24 @@ void launch_lstm_seq(const SeqMember* members, int k, int n, int nframes, int i_
 // the gate pass over every member's probabilities [nframes][n][21]
 void launch_lstm_seq_gates(float* const* d_probs, int k, int n, int nframes, float thr1, float thr2, hipStream_t s);
 
+// ---- batch form: up to kLstmSeqBatchMax sequences of DIFFERENT sizes through the same two launches.  These are THE kernels: the two
+// launchers above fill K uniform rows and call the two below.  A row is a member plus what the group keeps common: its CTU count, its frames of this launch and the frame number of the first one.  The rules above hold per row
+// with the row's own n (surplus lanes read row n - 1 of that member).  Every row is one run: the caller never passes a frame with
+// i_frame <= 0, and zeroes the state (state_in = null) only in front of the first frame.
+constexpr int kLstmSeqBatchMax = 32;
+struct SeqBatchRow {
+    SeqMember m;
+    int n, F, i_frame0;
+};
+// recurrence blocks of a sequence of n CTUs at level 16, 32, 64: G, ceil(G / 2), ceil(G / 4) with G = ceil(n / 16) column groups
+inline void lstm_seq_blocks(int64_t n, int64_t out[3]) {
+    const int64_t G = (n + 15) / 16;
+    out[0] = G, out[1] = (G + 1) / 2, out[2] = (G + 3) / 4;
+}
+// rows in any order: the launch deals the blocks of a level to the rows with the most frames first (scheduling only)
+void launch_lstm_seq_batch(const SeqBatchRow* rows, int k, hipStream_t s);
+void launch_lstm_seq_gates_batch(float* const* d_probs, const int* n, const int* nframes, int k, float thr1, float thr2, hipStream_t s);
+
 // dependent v_mfma_f32_16x16x4_f32 links per frame of the wave that owns a hidden tile (its four gate chains are interleaved), and of
 // the head waves, per level (64, 32, 16): what scripts/ldp_sequence_rate.py holds against the measured link latency
 constexpr int kLstmSeqChainLinks[3] = {2 * 64 / 4, 2 * 128 / 4, 2 * 256 / 4};

@@ -15,6 +15,8 @@
 // Per frame: three workgroup barriers, no flag, no spin-wait, no claim word, no atomic.  Bit-identical to the per-frame path.
 #include <hip/hip_runtime.h>
 
+#include <algorithm>
+
 #include "ethcnn_canon_math.h"
 #include "ethcnn_kernels.h"
 #include "ethcnn_lstm_seq.h"
@@ -229,52 +231,74 @@ __device__ __forceinline__ void lstm_seq_level(const SeqParams& P, int blk, f32x
     }
 }
 
-// K independent sequences of one geometry in one launch (a solo sequence is K = 1).  The kernel only chooses whose row of the member
-// table a block works on and calls the body above.  Linear grid, level-major, the member index fastest: [level 16: G x K, one column
-// group each (the long chains first)][level 32: ceil(G / 2) x K][level 64: ceil(G / 4) x K] -- when K x blocks exceeds the compute
-// units every member's long chains are dispatched first.  The member table travels by value in the kernel arguments (404 bytes; the
-// member index is block-uniform, so a block reads its row with scalar loads): no device copy that would have to be kept current with
-// bundles and buffers.  No block reads what another member's block writes; a member's state_in and state_out may be the same buffer
-// under the rule of ethcnn_lstm_seq.h.
-struct SeqGroupParams {
-    SeqMember m[kLstmSeqGroupMax];
-    int k, n, groups, F;
-    int i_frame0;
+// ONE kernel for every form of the call.  Up to 32 independent sequences in one launch; a row of the table is a sequence with its own
+// n, F and i_frame0, and the solo and group calls are the uniform case: K rows with the same three.  The kernel only chooses whose
+// row a block works on and calls the body above.  The block -> (level, row, block of the row) mapping comes from one prefix array per
+// level over the rows' block counts (ethcnn_lstm_seq.h::lstm_seq_blocks).  Linear, level-major grid, level 16 first (the long chains
+// first); inside a level the rows stand in the order of the table, which the launcher sorts by frames of this launch,
+// most first: a block lasts as long as its row has frames, so the long ones are dispatched first.  A block finds its row by a scan of
+// the level's prefix sums -- block-uniform, scalar loads from the kernel arguments (2448 bytes: 32 rows of 64, 3 x 33 ints) -- and
+// then runs the same body with the row's own n.  No block waits for another one; which block computes what is fixed by the table.
+struct SeqBatchParams {
+    SeqBatchRow r[kLstmSeqBatchMax];
+    int pre[3][kLstmSeqBatchMax + 1];  // [level 16, 32, 64][row]: blocks of the rows in front of it; [k]: the level's total
+    int k;
 };
+static_assert(sizeof(SeqBatchParams) <= 4096, "the table travels in the kernel arguments");
 
-__global__ __launch_bounds__(1024) void k_lstm_seq(SeqGroupParams G) {
+__global__ __launch_bounds__(1024) void k_lstm_seq_batch(SeqBatchParams B) {
     __shared__ f32x4 smem[kSeqWaves * 3 * 64 + ((192 + 5) * 16 + 16) / 4];  // 48 KB of quads + the fc3 operands (12.4 KB at level 16)
-    const int K = G.k, n2 = G.groups * K, n1 = ((G.groups + 1) / 2) * K;
+    const int K = B.k, n2 = B.pre[0][K], n1 = B.pre[1][K];
     const int b = (int)blockIdx.x;
+    const int lv = b < n2 ? 0 : (b < n2 + n1 ? 1 : 2);
     const int r = b < n2 ? b : (b < n2 + n1 ? b - n2 : b - n2 - n1);  // position inside the level
-    const int blk = r / K;
-    const SeqMember& M = G.m[r - blk * K];
-    SeqParams P;  // (a local copy of the row, not a reference into the arguments: the body keeps its fields in registers)
-    P.vec = M.vec;
-    P.state_in = M.state_in;
-    P.state_out = M.state_out;
-    P.blob = M.blob;
-    P.probs = M.probs;
-    P.n = G.n;
-    P.groups = G.groups;
-    P.F = G.F;
-    P.i_frame0 = G.i_frame0;
-    P.efs0 = M.efs0;
-    if (b < n2) lstm_seq_level<2>(P, blk, smem);
-    else if (b < n2 + n1) lstm_seq_level<1>(P, blk, smem);
+    int j = 0;
+    while (j + 1 < K && B.pre[lv][j + 1] <= r) ++j;
+    const int blk = r - B.pre[lv][j];
+    const SeqBatchRow& R = B.r[j];
+    SeqParams P;
+    P.vec = R.m.vec;
+    P.state_in = R.m.state_in;
+    P.state_out = R.m.state_out;
+    P.blob = R.m.blob;
+    P.probs = R.m.probs;
+    P.n = R.n;
+    P.groups = (R.n + 15) / 16;
+    P.F = R.F;
+    P.i_frame0 = R.i_frame0;
+    P.efs0 = R.m.efs0;
+    if (lv == 0) lstm_seq_level<2>(P, blk, smem);
+    else if (lv == 1) lstm_seq_level<1>(P, blk, smem);
     else lstm_seq_level<0>(P, blk, smem);
 }
 
+void launch_lstm_seq_batch(const SeqBatchRow* rows, int k, hipStream_t s) {
+    SeqBatchParams B;
+    int order[kLstmSeqBatchMax];
+    for (int j = 0; j < k; ++j) order[j] = j;
+    std::stable_sort(order, order + k, [&](int a, int b) { return rows[a].F > rows[b].F; });
+    for (int j = 0; j < kLstmSeqBatchMax; ++j) B.r[j] = rows[order[j < k ? j : 0]];
+    for (int lv = 0; lv < 3; ++lv) {
+        int at = 0;
+        for (int j = 0; j <= kLstmSeqBatchMax; ++j) {
+            B.pre[lv][j] = at;
+            if (j < k) {
+                int64_t blocks[3];
+                lstm_seq_blocks(B.r[j].n, blocks);
+                at += (int)blocks[lv];
+            }
+        }
+    }
+    B.k = k;
+    const unsigned blocks = (unsigned)(B.pre[0][k] + B.pre[1][k] + B.pre[2][k]);
+    hipLaunchKernelGGL(k_lstm_seq_batch, dim3(blocks), dim3(64 * kSeqWaves), 0, s, B);
+}
+
+// the solo and group calls: K rows of one geometry, run of frames and first frame number
 void launch_lstm_seq(const SeqMember* members, int k, int n, int nframes, int i_frame0, hipStream_t s) {
-    SeqGroupParams G;
-    for (int m = 0; m < kLstmSeqGroupMax; ++m) G.m[m] = members[m < k ? m : 0];
-    G.k = k;
-    G.n = n;
-    G.groups = (n + 15) / 16;
-    G.F = nframes;
-    G.i_frame0 = i_frame0;
-    const unsigned blocks = (unsigned)(k * (G.groups + (G.groups + 1) / 2 + (G.groups + 3) / 4));
-    hipLaunchKernelGGL(k_lstm_seq, dim3(blocks), dim3(64 * kSeqWaves), 0, s, G);
+    SeqBatchRow rows[kLstmSeqGroupMax];
+    for (int m = 0; m < k; ++m) rows[m] = {members[m], n, nframes, i_frame0};
+    launch_lstm_seq_batch(rows, k, s);
 }
 
 // ---- gates: the tf.cond pair of net():305,317 per (frame, mini-batch of 1024 CTUs).  One block owns the mini-batch: it reduces the
@@ -300,20 +324,32 @@ __device__ __forceinline__ void lstm_seq_gates_body(float* __restrict__ probs, i
     }
 }
 
-// grid (frames x mini-batches, K): the member is blockIdx.y, the body above runs over its probabilities (as a function of its own, with
-// a __restrict__ pointer: written into the kernel it costs two more registers)
-struct SeqGateGroup {
-    float* probs[kLstmSeqGroupMax];
+// grid (max over rows of frames x mini-batches, rows); a block behind its row's last (frame, mini-batch) returns at once
+struct SeqGateBatch {
+    float* probs[kLstmSeqBatchMax];
+    int n[kLstmSeqBatchMax], F[kLstmSeqBatchMax];
 };
-__global__ __launch_bounds__(256) void k_lstm_seq_gates(SeqGateGroup Q, int n, int chunks, float thr1, float thr2) {
+__global__ __launch_bounds__(256) void k_lstm_seq_gates_batch(SeqGateBatch Q, float thr1, float thr2) {
+    const int n = Q.n[blockIdx.y], chunks = (n + kSubBatch - 1) / kSubBatch;
+    if ((int)blockIdx.x >= chunks * Q.F[blockIdx.y]) return;
     lstm_seq_gates_body(Q.probs[blockIdx.y], n, chunks, thr1, thr2);
 }
 
+void launch_lstm_seq_gates_batch(float* const* d_probs, const int* n, const int* nframes, int k, float thr1, float thr2, hipStream_t s) {
+    SeqGateBatch Q;
+    unsigned gx = 1;
+    for (int j = 0; j < kLstmSeqBatchMax; ++j) {
+        const int m = j < k ? j : 0;
+        Q.probs[j] = d_probs[m], Q.n[j] = n[m], Q.F[j] = nframes[m];
+        gx = std::max(gx, (unsigned)((n[m] + kSubBatch - 1) / kSubBatch) * (unsigned)nframes[m]);
+    }
+    hipLaunchKernelGGL(k_lstm_seq_gates_batch, dim3(gx, (unsigned)k), dim3(256), 0, s, Q, thr1, thr2);
+}
+
 void launch_lstm_seq_gates(float* const* d_probs, int k, int n, int nframes, float thr1, float thr2, hipStream_t s) {
-    SeqGateGroup Q;
-    for (int m = 0; m < kLstmSeqGroupMax; ++m) Q.probs[m] = d_probs[m < k ? m : 0];
-    const unsigned chunks = (unsigned)((n + kSubBatch - 1) / kSubBatch);
-    hipLaunchKernelGGL(k_lstm_seq_gates, dim3(chunks * (unsigned)nframes, (unsigned)k), dim3(256), 0, s, Q, n, (int)chunks, thr1, thr2);
+    int ns[kLstmSeqGroupMax], fs[kLstmSeqGroupMax];
+    for (int m = 0; m < k; ++m) ns[m] = n, fs[m] = nframes;
+    launch_lstm_seq_gates_batch(d_probs, ns, fs, k, thr1, thr2, s);
 }
 
 }  // namespace ethcnn

@@ -3,6 +3,7 @@
 // calibrator and the partition-search simulator.  Kernels: ethcnn_replay.hip.
 #include "ethcnn_analysis.h"
 #include "ethcnn_calib.h"
+#include "ethcnn_ldp_batch.h"
 #include "ethcnn_ldp_group.h"
 #include "ethcnn_replay.h"
 #include "ethcnn_samples.h"
@@ -257,15 +258,13 @@ int check_run(ethcnn_replay* p, int run, int slot) {
     return 0;
 }
 
-// the object's buffers at exactly the sizes of `nd` (what is held is what was checked), and the run's source table in HBM; refuses
-// with the whole sum before it allocates what it cannot get
-int ensure_run(ethcnn_replay* p, int run, const Need& nd) {
+// the object's buffers at exactly the sizes of `nd` (what is held is what was checked); refuses with the whole sum before it allocates
+// what it cannot get.  what: "run 3 (5 frames of 12 CTUs)", for the messages
+int ensure_buffers(ethcnn_replay* p, const Need& nd, const char* what) {
     ethcnn_ctx* c = p->c;
-    const Run& r = p->plan.runs[(size_t)run];
     const unsigned long long total = nd.total();
     if (p->max_bytes && total > p->max_bytes)
-        return rerr(p, ETHCNN_ERR_NOMEM, "run %d (%lld frames of %lld CTUs) needs %llu bytes on the device, above the object's limit of %llu", run, (long long)r.F,
-                    (long long)r.nctu, total, (unsigned long long)p->max_bytes);
+        return rerr(p, ETHCNN_ERR_NOMEM, "%s needs %llu bytes on the device, above the object's limit of %llu", what, total, (unsigned long long)p->max_bytes);
     // buffers of exactly this run's sizes: what is held is what was checked
     const size_t want[5] = {nd.resi, nd.src, nd.probs, nd.labels, nd.zero};
     size_t* cap[5] = {&p->resi_cap, &p->src_cap, &p->probs_cap, &p->labels_cap, &p->zero_cap};
@@ -277,8 +276,7 @@ int ensure_run(ethcnn_replay* p, int run, const Need& nd) {
         size_t free_b = 0, total_b = 0;
         if (hipMemGetInfo(&free_b, &total_b) != hipSuccess) return rerr(p, ETHCNN_ERR_DEVICE, "hipMemGetInfo failed");
         if (grow > free_b + back)
-            return rerr(p, ETHCNN_ERR_NOMEM, "run %d (%lld frames of %lld CTUs) needs %llu bytes on the device; %zu are free", run, (long long)r.F,
-                        (long long)r.nctu, total, free_b + back);
+            return rerr(p, ETHCNN_ERR_NOMEM, "%s needs %llu bytes on the device; %zu are free", what, total, free_b + back);
         if (hipStreamSynchronize(c->stream) != hipSuccess) return rerr(p, ETHCNN_ERR_DEVICE, "hipStreamSynchronize failed");
         for (int k = 0; k < 5; ++k)
             if (*cap[k] != want[k]) {
@@ -292,13 +290,22 @@ int ensure_run(ethcnn_replay* p, int run, const Need& nd) {
                 if (hipMalloc(buf[k], want[k]) != hipSuccess) {
                     (void)hipGetLastError();
                     *buf[k] = nullptr;
-                    return rerr(p, ETHCNN_ERR_NOMEM, "run %d (%lld frames of %lld CTUs) needs %llu bytes on the device: %zu of them do not fit", run,
-                                (long long)r.F, (long long)r.nctu, total, want[k]);
+                    return rerr(p, ETHCNN_ERR_NOMEM, "%s needs %llu bytes on the device: %zu of them do not fit", what, total, want[k]);
                 }
                 *cap[k] = want[k];
                 if (k == 4 && hipMemsetAsync(*buf[k], 0, want[k], c->stream) != hipSuccess) return rerr(p, ETHCNN_ERR_DEVICE, "hipMemsetAsync failed");
             }
     }
+    return 0;
+}
+
+// the buffers of a run, and its source table in HBM
+int ensure_run(ethcnn_replay* p, int run, const Need& nd) {
+    ethcnn_ctx* c = p->c;
+    const Run& r = p->plan.runs[(size_t)run];
+    char what[96];
+    std::snprintf(what, sizeof what, "run %d (%lld frames of %lld CTUs)", run, (long long)r.F, (long long)r.nctu);
+    if (int rc = ensure_buffers(p, nd, what)) return rc;
     c->done_armed = 0;
     if (p->src_run != run) {
         p->src_run = -1;
@@ -575,4 +582,151 @@ extern "C" int ethcnn_replay_feed_sim(ethcnn_replay* p, int run, int slot, ethcn
     const Run& r = p->plan.runs[(size_t)run];
     const int rc = ethcnn_sim_add_frames_device(sim, p->d_probs, p->d_labels, 64 * r.C, 64 * r.R, r.F, 0);
     return rc ? rerr(p, rc, "run %d: %s", run, ethcnn_last_error(p->c)) : ETHCNN_OK;
+}
+
+// ---- several runs through an ethcnn_ldp_batch (config #5 offline, batch form): item j = run runs[j] at slot slots[j] with bundle
+// bundles[j].  The items go to the batch in the order of their lengths, longest first (stable), so that the items which still have
+// frames are always the first ones of the list and every item keeps its sequence index -- and with it its resident state -- from
+// chunk to chunk.  No result depends on that order.
+namespace {
+struct BatchLayout {
+    int order[kLstmSeqBatchMax];        // position in the batch call -> item
+    size_t plane_at[kLstmSeqBatchMax];  // bytes into d_resi, by item
+    size_t src_at[kLstmSeqBatchMax];    // entries into d_src, by item
+    size_t out_at[kLstmSeqBatchMax];    // CTU-frames into the object's own probabilities and labels, by item
+    int64_t Fc, longest;
+    Need nd;
+};
+
+int batch_layout(ethcnn_replay* p, ethcnn_ldp_batch* b, int nitems, const int* runs, bool own_out, BatchLayout* L) {
+    if (p->plan.runs.empty()) return rerr(p, ETHCNN_ERR_ARG, "nothing is open (ethcnn_replay_open_set / ethcnn_replay_open_records)");
+    if (!b || !runs) return rerr(p, ETHCNN_ERR_ARG, "ethcnn_replay_batch: null pointer");
+    if (b->c != p->c) return rerr(p, ETHCNN_ERR_ARG, "the batch lives on another context");
+    if (nitems < 1 || nitems > kLstmSeqBatchMax) return rerr(p, ETHCNN_ERR_ARG, "%d items (1..%d)", nitems, kLstmSeqBatchMax);
+    int64_t sum = 0;
+    for (int j = 0; j < nitems; ++j) {
+        if (int rc = check_run(p, runs[j], 0)) return rc;
+        sum += p->plan.runs[(size_t)runs[j]].nctu;
+    }
+    L->Fc = p->chunk > 0 ? (int64_t)p->chunk : std::max<int64_t>(1, kChunkBytes / (sum * 4096));
+    L->longest = 0;
+    Need& n = L->nd;
+    n.rec = p->own ? (size_t)p->nrec * kRec : 0;
+    n.resi = n.src = n.probs = n.labels = n.zero = 0;
+    size_t ctu_frames = 0;
+    for (int j = 0; j < nitems; ++j) {
+        const Run& r = p->plan.runs[(size_t)runs[j]];
+        L->order[j] = j;
+        L->plane_at[j] = n.resi, L->src_at[j] = ctu_frames, L->out_at[j] = ctu_frames;
+        n.resi += (size_t)(std::min<int64_t>(r.F, L->Fc) * r.nctu) * 4096;
+        ctu_frames += (size_t)(r.F * r.nctu);
+        if (r.f0 > 1) n.zero = std::max(n.zero, (size_t)r.nctu * 2 * kNVec * 4);
+        L->longest = std::max(L->longest, r.F);
+    }
+    n.src = ctu_frames * 8;
+    if (own_out) n.probs = ctu_frames * kNOut * 4, n.labels = ctu_frames * 16;
+    std::stable_sort(L->order, L->order + nitems, [&](int x, int y) { return p->plan.runs[(size_t)runs[x]].F > p->plan.runs[(size_t)runs[y]].F; });
+    return 0;
+}
+
+// d_probs / d_labels null: into the object's own buffers at out_at
+int batch_replay(ethcnn_replay* p, ethcnn_ldp_batch* b, int nitems, const int* runs, const int* slots, const int* bundles, float* const* d_probs,
+                 uint8_t* const* d_labels, BatchLayout* L) {
+    const bool own_out = d_probs == nullptr;
+    if (int rc = batch_layout(p, b, nitems, runs, own_out, L)) return rc;
+    if (!slots || !bundles) return rerr(p, ETHCNN_ERR_ARG, "ethcnn_replay_batch: null pointer");
+    ethcnn_ctx* c = p->c;
+    if (!c->have_weights) return rerr(p, ETHCNN_ERR_NOWEIGHTS, "the context has no residual CNN loaded (ethcnn_load_checkpoint / ethcnn_load_blob)");
+    for (int j = 0; j < nitems; ++j) {
+        if (int rc = check_run(p, runs[j], slots[j])) return rc;
+        if (bundles[j] < 0 || bundles[j] >= b->nb || !b->b[bundles[j]].have)
+            return rerr(p, ETHCNN_ERR_NOWEIGHTS, "item %d: bundle %d of the batch holds no ETH-LSTM bundle for QP %d of slot %d", j, bundles[j],
+                        p->plan.runs[(size_t)runs[j]].qp[slots[j]], slots[j]);
+        if (!own_out) {
+            if (!d_labels || !d_probs[j] || !d_labels[j]) return rerr(p, ETHCNN_ERR_ARG, "ethcnn_replay_batch_device: null output buffer (item %d)", j);
+            if (((uintptr_t)d_probs[j] | (uintptr_t)d_labels[j]) % 4) return rerr(p, ETHCNN_ERR_ARG, "output buffers are 4-byte aligned");
+        }
+    }
+    if (hipSetDevice(c->device) != hipSuccess) return rerr(p, ETHCNN_ERR_DEVICE, "hipSetDevice(%d) failed", c->device);
+    char what[96];
+    std::snprintf(what, sizeof what, "a batch of %d runs (chunks of %lld frames)", nitems, (long long)L->Fc);
+    if (int rc = ensure_buffers(p, L->nd, what)) return rc;
+    c->done_armed = 0;
+    p->src_run = -1;  // the table buffer holds the items' tables, one behind the other
+    for (int j = 0; j < nitems; ++j) {
+        const Run& r = p->plan.runs[(size_t)runs[j]];
+        const hipError_t e = hipMemcpyAsync(p->d_src + L->src_at[j], p->plan.src.data() + r.src_at, (size_t)(r.F * r.nctu) * 8, hipMemcpyHostToDevice, c->stream);
+        if (e != hipSuccess) return rerr(p, ETHCNN_ERR_DEVICE, "upload of the source table: %s", hipGetErrorString(e));
+    }
+    for (int64_t at = 0; at < L->longest; at += L->Fc) {
+        ethcnn_ldp_batch_seq seqs[kLstmSeqBatchMax];
+        int k = 0;
+        for (; k < nitems; ++k) {
+            const int j = L->order[k];
+            const Run& r = p->plan.runs[(size_t)runs[j]];
+            if (at >= r.F) break;  // (sorted by length: everything behind it has ended as well)
+            const int nf = (int)std::min<int64_t>(L->Fc, r.F - at), W = 64 * r.C, H = 64 * r.R;
+            float* const probs = own_out ? p->d_probs + L->out_at[j] * kNOut : d_probs[j];
+            uint8_t* const labels = own_out ? p->d_labels + L->out_at[j] * 16 : d_labels[j];
+            launch_uncut(c->stream, p->rec, (long)p->nrec, p->d_src + L->src_at[j] + at * r.nctu, nf, r.R, r.C, slots[j], p->d_resi + L->plane_at[j],
+                         labels + at * r.nctu * 16, cus_of(c));
+            // the first chunk starts from zeros (the object's zero state when the frame number is above 1); the following ones from the
+            // state the call before left resident at this position of the batch
+            seqs[k] = {p->d_resi + L->plane_at[j], W, H, (ptrdiff_t)W, (ptrdiff_t)W * H, nf, r.qp[slots[j]], (int)(r.f0 + (uint32_t)at), bundles[j],
+                       at == 0 && r.f0 > 1 ? p->d_zero : nullptr, probs + at * r.nctu * kNOut};
+        }
+        const hipError_t e = hipGetLastError();
+        if (e != hipSuccess) return rerr(p, ETHCNN_ERR_DEVICE, "uncut: %s", hipGetErrorString(e));
+        const int rc = ethcnn_ldp_batch_run_device(b, seqs, k);
+        if (rc) return rerr(p, rc, "batch of %d runs, frames %lld.. of each: %s", nitems, (long long)at, ethcnn_ldp_batch_last_error(b));
+    }
+    return ETHCNN_OK;
+}
+
+template <typename Add>
+int batch_feed(ethcnn_replay* p, ethcnn_ldp_batch* b, int nitems, const int* runs, const int* slots, const int* bundles, Add add) {
+    BatchLayout L;
+    if (int rc = batch_replay(p, b, nitems, runs, slots, bundles, nullptr, nullptr, &L)) return rc;
+    for (int j = 0; j < nitems; ++j) {  // in list order: the consumer ends as the per-run feeds in that order leave it
+        const Run& r = p->plan.runs[(size_t)runs[j]];
+        const int rc = add(p->d_probs + L.out_at[j] * kNOut, p->d_labels + L.out_at[j] * 16, 64 * r.C, 64 * r.R, r.F);
+        if (rc) return rerr(p, rc, "run %d: %s", runs[j], ethcnn_last_error(p->c));
+    }
+    return ETHCNN_OK;
+}
+}  // namespace
+
+extern "C" int64_t ethcnn_replay_batch_bytes(ethcnn_replay* p, ethcnn_ldp_batch* b, int nitems, const int* runs) {
+    if (!p) return ETHCNN_ERR_ARG;
+    BatchLayout L;
+    if (int rc = batch_layout(p, b, nitems, runs, false, &L)) return rc;
+    return (int64_t)L.nd.total();
+}
+
+extern "C" int ethcnn_replay_batch_device(ethcnn_replay* p, ethcnn_ldp_batch* b, int nitems, const int* runs, const int* slots, const int* bundles,
+                                          float* const* d_probs, uint8_t* const* d_labels) {
+    if (!p) return ETHCNN_ERR_ARG;
+    if (!d_probs || !d_labels) return rerr(p, ETHCNN_ERR_ARG, "ethcnn_replay_batch_device: null pointer");
+    BatchLayout L;
+    return batch_replay(p, b, nitems, runs, slots, bundles, d_probs, d_labels, &L);
+}
+
+extern "C" int ethcnn_replay_batch_feed_calib(ethcnn_replay* p, ethcnn_ldp_batch* b, int nitems, const int* runs, const int* slots, const int* bundles,
+                                              ethcnn_calib* cal) {
+    if (!p) return ETHCNN_ERR_ARG;
+    if (!cal) return rerr(p, ETHCNN_ERR_ARG, "null calibrator");
+    if (cal->c != p->c) return rerr(p, ETHCNN_ERR_ARG, "the calibrator lives on another context");
+    return batch_feed(p, b, nitems, runs, slots, bundles, [&](const float* probs, const uint8_t* labels, int w, int h, int64_t F) {
+        return ethcnn_calib_add_frames_device(cal, probs, labels, w, h, F, 0);
+    });
+}
+
+extern "C" int ethcnn_replay_batch_feed_sim(ethcnn_replay* p, ethcnn_ldp_batch* b, int nitems, const int* runs, const int* slots, const int* bundles,
+                                            ethcnn_sim* sim) {
+    if (!p) return ETHCNN_ERR_ARG;
+    if (!sim) return rerr(p, ETHCNN_ERR_ARG, "null simulator");
+    if (sim->c != p->c) return rerr(p, ETHCNN_ERR_ARG, "the simulator lives on another context");
+    return batch_feed(p, b, nitems, runs, slots, bundles, [&](const float* probs, const uint8_t* labels, int w, int h, int64_t F) {
+        return ethcnn_sim_add_frames_device(sim, probs, labels, w, h, F, 0);
+    });
 }

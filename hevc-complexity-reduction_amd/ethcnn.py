@@ -17,6 +17,7 @@ LIB_PATH = os.environ.get("ETHCNN_LIB", LIB_PATH)  # development knob: A/B build
 NOUT, NFEAT, NVEC, NFC2, SUB_BATCH = 21, 2688, 448, 336, 1024
 BLOB_FLOATS = 1288210
 LSTM_BLOB_FLOATS = 760078
+LDP_BATCH_MAX, LDP_BATCH_BUNDLES = 32, 8  # sequences per LdpBatch call, bundles per LdpBatch
 
 STAGES = ("tile", "trunk", "fc1", "heads", "gate")
 DBG_FEATURES, DBG_FC1, DBG_FC2, DBG_LOGITS, DBG_RAW_PROBS = range(5)
@@ -118,6 +119,20 @@ SIGNATURES = {
     "ethcnn_ldp_group_state_ctus": (ctypes.c_int64, [_vp, _i]),
     "ethcnn_ldp_group_set_chunk": (_i, [_vp, _i]),
     "ethcnn_ldp_group_bytes": (ctypes.c_int64, [_i, _i, _i, _i, _i]),
+    "ethcnn_ldp_batch_create": (_i, [_vp, _i, ctypes.POINTER(_vp)]),
+    "ethcnn_ldp_batch_destroy": (None, [_vp]),
+    "ethcnn_ldp_batch_last_error": (_cp, [_vp]),
+    "ethcnn_ldp_batch_bundles": (_i, [_vp]),
+    "ethcnn_ldp_batch_load_lstm_checkpoint": (_i, [_vp, _i, _cp]),
+    "ethcnn_ldp_batch_load_lstm_blob": (_i, [_vp, _i, _fp, _sz]),
+    "ethcnn_ldp_batch_load_lstm_synthetic": (_i, [_vp, _i, ctypes.c_uint64, ctypes.c_double]),
+    "ethcnn_ldp_batch_get_lstm_blob": (_i, [_vp, _i, _fp, _sz]),
+    "ethcnn_ldp_batch_run_device": (_i, [_vp, _vp, _i]),
+    "ethcnn_ldp_batch_get_state": (_i, [_vp, _i, _fp, _sz]),
+    "ethcnn_ldp_batch_state_ctus": (ctypes.c_int64, [_vp, _i]),
+    "ethcnn_ldp_batch_set_chunk": (_i, [_vp, _i]),
+    "ethcnn_ldp_batch_bytes": (ctypes.c_int64, [ctypes.POINTER(_i), ctypes.POINTER(_i), ctypes.POINTER(_i), _i, _i]),
+    "ethcnn_ldp_batch_plan": (_i, [ctypes.POINTER(_i), ctypes.POINTER(_i), _i, _i, ctypes.POINTER(_i), ctypes.POINTER(_i), ctypes.POINTER(_i), _i]),
     "ethcnn_ldp_step_begin": (_i, [_vp, _vp, _i, _i, _pd, _i, _i, _vp, _fp]),
     "ethcnn_rows_ready": (_i, [_vp, _i, _i]),
     "ethcnn_predict_luma_begin": (_i, [_vp, _vp, _i, _i, _i, _fp]),
@@ -330,6 +345,10 @@ SIGNATURES = {
     "ethcnn_replay_run_group_device": (_i, [_vp, _i, _i, ctypes.POINTER(_i), _vp, _vp, _vp]),
     "ethcnn_replay_feed_calib": (_i, [_vp, _i, _i, _vp]),
     "ethcnn_replay_feed_sim": (_i, [_vp, _i, _i, _vp]),
+    "ethcnn_replay_batch_bytes": (ctypes.c_int64, [_vp, _vp, _i, ctypes.POINTER(_i)]),
+    "ethcnn_replay_batch_device": (_i, [_vp, _vp, _i, ctypes.POINTER(_i), ctypes.POINTER(_i), ctypes.POINTER(_i), _vp, _vp]),
+    "ethcnn_replay_batch_feed_calib": (_i, [_vp, _vp, _i, ctypes.POINTER(_i), ctypes.POINTER(_i), ctypes.POINTER(_i), _vp]),
+    "ethcnn_replay_batch_feed_sim": (_i, [_vp, _vp, _i, ctypes.POINTER(_i), ctypes.POINTER(_i), ctypes.POINTER(_i), _vp]),
 }
 
 _lib = None
@@ -442,6 +461,38 @@ def host_thread_budget(local_workers=1, usable_cpus=0):
 def ldp_sequence_bytes(width, height, nframes, chunk_frames=0):
     """device bytes an ldp_sequence call holds for that chunk size (ethcnn_ldp_sequence_bytes; host only); negative = bad arguments"""
     return int(load_library().ethcnn_ldp_sequence_bytes(int(width), int(height), int(nframes), int(chunk_frames)))
+
+
+def _int_array(vals):
+    vals = [int(v) for v in vals]
+    return (ctypes.c_int * max(len(vals), 1))(*vals)
+
+
+def ldp_batch_bytes(widths, heights, nframes, chunk_frames=0):
+    """device bytes an LdpBatch.run_device call over sequences of these sizes and frame counts holds for that chunk size
+    (ethcnn_ldp_batch_bytes; host only), the bundle images apart; negative for bad arguments"""
+    if not (len(widths) == len(heights) == len(nframes)):
+        raise ValueError("ldp_batch_bytes takes one width, height and frame count per sequence")
+    return int(load_library().ethcnn_ldp_batch_bytes(_int_array(widths), _int_array(heights), _int_array(nframes), len(widths), int(chunk_frames)))
+
+
+def ldp_batch_plan(nctus, nframes, chunk_frames=0):
+    """the chunks of an LdpBatch.run_device call over sequences of these CTU and frame counts (ethcnn_ldp_batch_plan; host only) ->
+    {"chunk_frames": Fc, "chunks": [{"members", "blocks": (level 16, level 32, level 64)}]}; raises EthCnnError for bad arguments"""
+    if len(nctus) != len(nframes):
+        raise ValueError("ldp_batch_plan takes one CTU count and one frame count per sequence")
+    lib = load_library()
+    fc, nchunks = ctypes.c_int(0), ctypes.c_int(0)
+    args = (_int_array(nctus), _int_array(nframes), len(nctus), int(chunk_frames))
+    rc = lib.ethcnn_ldp_batch_plan(*args, ctypes.byref(fc), ctypes.byref(nchunks), None, 0)
+    if rc:
+        raise EthCnnError(rc, "ethcnn_ldp_batch_plan: bad arguments")
+    rows = (ctypes.c_int * (4 * max(nchunks.value, 1)))()
+    rc = lib.ethcnn_ldp_batch_plan(*args, ctypes.byref(fc), ctypes.byref(nchunks), rows, nchunks.value)
+    if rc:
+        raise EthCnnError(rc, "ethcnn_ldp_batch_plan: bad arguments")
+    return {"chunk_frames": fc.value,
+            "chunks": [{"members": rows[4 * t], "blocks": (rows[4 * t + 1], rows[4 * t + 2], rows[4 * t + 3])} for t in range(nchunks.value)]}
 
 
 def ldp_group_bytes(width, height, nframes, chunk_frames=0, k=1):
@@ -2805,6 +2856,126 @@ class LdpGroup(object):
                 b.free()
 
 
+# ------------------------------------------------------------------------------------- config #5 offline, batch form ---
+class LdpBatchSeq(ctypes.Structure):
+    """ethcnn_ldp_batch_seq"""
+    _fields_ = [("d_luma", ctypes.c_void_p), ("width", ctypes.c_int), ("height", ctypes.c_int), ("pitch", ctypes.c_ssize_t),
+                ("frame_stride", ctypes.c_ssize_t), ("nframes", ctypes.c_int), ("qp", ctypes.c_int), ("i_frame_first", ctypes.c_int),
+                ("bundle", ctypes.c_int), ("d_state_in", ctypes.c_void_p), ("d_probs", ctypes.c_void_p)]
+
+
+class LdpBatch(object):
+    """Up to 32 Low-Delay-P residual sequences of different geometry, length and first frame number through one recurrence launch
+    per chunk (include/ethcnn.h "config #5 offline, batch form").  The object holds nbundles = 1..8 ETH-LSTM bundles; a sequence names
+    its bundle by index, and its result equals EthCnn.ldp_sequence_device on a context that holds that bundle, bit for bit.  The
+    residual CNN and the thresholds are the context's; the context's own LSTM bundle and resident state are not touched."""
+
+    def __init__(self, ctx, nbundles):
+        self.ctx, self.lib = ctx, ctx.lib
+        h = ctypes.c_void_p()
+        ctx._chk(self.lib.ethcnn_ldp_batch_create(ctx.h, int(nbundles), ctypes.byref(h)))
+        self.h = h
+        if not hasattr(ctx, "_trainers"):
+            ctx._trainers = weakref.WeakSet()
+        ctx._trainers.add(self)  # closed with the context, before it
+
+    def _chk(self, rc):
+        if rc:
+            raise EthCnnError(rc, self.lib.ethcnn_ldp_batch_last_error(self.h).decode())
+
+    def close(self):
+        if getattr(self, "h", None):
+            self.lib.ethcnn_ldp_batch_destroy(self.h)
+            self.h = None
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+    def __enter__(self):
+        return self
+
+    def __exit__(self, *a):
+        self.close()
+
+    @property
+    def nbundles(self):
+        return max(0, int(self.lib.ethcnn_ldp_batch_bundles(self.h)))
+
+    def load_lstm_checkpoint(self, bundle, prefix):
+        self._chk(self.lib.ethcnn_ldp_batch_load_lstm_checkpoint(self.h, int(bundle), os.fsencode(prefix)))
+
+    def load_lstm_blob(self, bundle, blob):
+        blob = np.ascontiguousarray(blob, dtype=np.float32)
+        self._chk(self.lib.ethcnn_ldp_batch_load_lstm_blob(self.h, int(bundle), blob.ctypes.data_as(_fp), blob.size))
+
+    def load_lstm_synthetic(self, bundle, seed=1, head_gain=1.0):
+        self._chk(self.lib.ethcnn_ldp_batch_load_lstm_synthetic(self.h, int(bundle), int(seed), float(head_gain)))
+
+    def get_lstm_blob(self, bundle):
+        out = np.empty(LSTM_BLOB_FLOATS, dtype=np.float32)
+        self._chk(self.lib.ethcnn_ldp_batch_get_lstm_blob(self.h, int(bundle), out.ctypes.data_as(_fp), out.size))
+        return out
+
+    def set_chunk(self, frames):
+        self._chk(self.lib.ethcnn_ldp_batch_set_chunk(self.h, int(frames)))
+
+    def state_ctus(self, j):
+        """the CTU count of the resident state of sequence index j (0: none)"""
+        n = int(self.lib.ethcnn_ldp_batch_state_ctus(self.h, int(j)))
+        self._chk(n if n < 0 else 0)
+        return n
+
+    def get_state(self, j):
+        """the resident (c, h) state of sequence index j -> float32 [nctu, 2, 448]"""
+        state = np.empty((self.state_ctus(j), 2, NVEC), dtype=np.float32)
+        self._chk(self.lib.ethcnn_ldp_batch_get_state(self.h, int(j), state.ctypes.data_as(_fp), state.size))
+        return state
+
+    def run_device(self, seqs):
+        """asynchronous on the context's stream (ethcnn_ldp_batch_run_device).  seqs: one dict per sequence with d_luma, width, height,
+        nframes, qp, d_probs (DeviceBuffers or raw device addresses) and optionally i_frame_first (1), bundle (0), d_state_in (None),
+        pitch (width), frame_stride (pitch * height)"""
+        ptr = lambda b: None if b is None else getattr(b, "ptr", b)
+        arr = (LdpBatchSeq * max(len(seqs), 1))()
+        for j, q in enumerate(seqs[:len(arr)]):
+            pitch = int(q.get("pitch") or q["width"])
+            arr[j] = LdpBatchSeq(ptr(q["d_luma"]), int(q["width"]), int(q["height"]), pitch, int(q.get("frame_stride") or pitch * int(q["height"])),
+                                 int(q["nframes"]), int(q["qp"]), int(q.get("i_frame_first", 1)), int(q.get("bundle", 0)), ptr(q.get("d_state_in")),
+                                 ptr(q["d_probs"]))
+        self._chk(self.lib.ethcnn_ldp_batch_run_device(self.h, arr, len(seqs)))
+
+    def run(self, seqs):
+        """seqs: one dict per sequence with luma (uint8 [nframes, height, width], host memory), width, height, qp and optionally
+        i_frame_first, bundle, state_in (float32 [nctu, 2, 448]) -> a list of probs [nframes, nctu, 21].  The inputs are uploaded to
+        DeviceBuffers and the results downloaded (a convenience for small inputs: a job keeps its frames in HBM and calls run_device)."""
+        bufs, dev, shapes = [], [], []
+        alloc = lambda nbytes: bufs.append(DeviceBuffer(self.ctx, max(int(nbytes), 4))) or bufs[-1]
+        try:
+            for q in seqs:
+                w, h = int(q["width"]), int(q["height"])
+                n = ctus_per_frame(w, h)
+                luma = np.ascontiguousarray(q["luma"], dtype=np.uint8).reshape(-1, h, w)
+                d = {k: q[k] for k in ("width", "height", "qp", "i_frame_first", "bundle") if k in q}
+                d["nframes"] = luma.shape[0]
+                d["d_luma"] = alloc(luma.nbytes)
+                d["d_luma"].upload(luma)
+                d["d_probs"] = alloc(luma.shape[0] * n * NOUT * 4)
+                if q.get("state_in") is not None:
+                    d["d_state_in"] = alloc(n * 2 * NVEC * 4)
+                    d["d_state_in"].upload(np.ascontiguousarray(q["state_in"], dtype=np.float32).reshape(n, 2, NVEC))
+                dev.append(d)
+                shapes.append((luma.shape[0], n))
+            self.run_device(dev)
+            return [d["d_probs"].download(np.float32, nf * n * NOUT).reshape(nf, n, NOUT) for d, (nf, n) in zip(dev, shapes)]
+        finally:
+            self.ctx.synchronize()
+            for b in bufs:
+                b.free()
+
+
 # ------------------------------------------------------------------------------------------------------ sample-set replay ---
 class ReplayRun(ctypes.Structure):
     _fields_ = [("seq", ctypes.c_int32), ("w", ctypes.c_int32), ("h", ctypes.c_int32), ("rows", ctypes.c_int32), ("cols", ctypes.c_int32),
@@ -2858,7 +3029,7 @@ class Replay(object):
     daemon would run them.  max_bytes: the most device memory a replay may hold (0 = no limit of its own)."""
 
     def __init__(self, ctx, max_bytes=0):
-        self.ctx, self.lib = ctx, ctx.lib
+        self.ctx, self.lib, self.max_bytes = ctx, ctx.lib, int(max_bytes)
         h = ctypes.c_void_p()
         ctx._chk(self.lib.ethcnn_replay_create(ctx.h, int(max_bytes), ctypes.byref(h)))
         self.h = h
@@ -2982,16 +3153,72 @@ class Replay(object):
                 dp.free()
                 dl.free()
 
-    def feed(self, consumer, runs=None, slot=None, qp=None):
+    def run_batch_bytes(self, runs, batch):
+        """device bytes run_batch_device holds for these runs replayed together (the batch's own memory apart)"""
+        n = int(self.lib.ethcnn_replay_batch_bytes(self.h, batch.h, len(runs), _int_array(runs)))
+        self._chk(n if n < 0 else 0)
+        return n
+
+    def run_batch_device(self, items, batch, d_probs, d_labels):
+        """asynchronous on the context's stream: items = [(run, slot, bundle)], up to 32, through an LdpBatch in one recurrence launch
+        per chunk; d_probs[j] float32 [frames, nctu, 21] and d_labels[j] uint8 [frames, 4 rows, 4 cols] of item j in HBM"""
+        if len(d_probs) != len(items) or len(d_labels) != len(items):
+            raise ValueError("run_batch_device takes one probability and one label buffer per item")
+        self._chk(self.lib.ethcnn_replay_batch_device(self.h, batch.h, len(items), _int_array([it[0] for it in items]), _int_array([it[1] for it in items]),
+                                                      _int_array([it[2] for it in items]), _ptr_array(d_probs), _ptr_array(d_labels)))
+
+    def run_batch(self, items, batch):
+        """items = [(run, slot, bundle)] -> [(probs float32 [frames, nctu, 21], labels uint8 [frames, 4 rows, 4 cols])] in host memory"""
+        info = [self.run_info(it[0]) for it in items]
+        bufs = []
+        try:
+            for r in info:
+                n = r["frames"] * r["nctu"]
+                bufs.append((DeviceBuffer(self.ctx, n * NOUT * 4), DeviceBuffer(self.ctx, n * 16)))
+            self.run_batch_device(items, batch, [b[0] for b in bufs], [b[1] for b in bufs])
+            return [(dp.download(np.float32, r["frames"] * r["nctu"] * NOUT).reshape(r["frames"], r["nctu"], NOUT),
+                     dl.download(np.uint8, r["frames"] * r["nctu"] * 16).reshape(r["frames"], 4 * r["rows"], 4 * r["cols"]))
+                    for r, (dp, dl) in zip(info, bufs)]
+        finally:
+            self.ctx.synchronize()
+            for dp, dl in bufs:
+                dp.free()
+                dl.free()
+
+    def _pack(self, runs, batch):
+        """the runs, in order, in lists of at most 32 whose memory sum as a feed holds it (ethcnn_replay_batch_bytes and the object's own
+        outputs, 100 bytes per CTU) stays within the object's limit; a run that exceeds it alone goes alone, and is refused with the
+        sum by the call"""
+        packs, cur = [], []
+        own = lambda lst: sum(r["frames"] * r["nctu"] * (NOUT * 4 + 16) for r in (self.run_info(i) for i in lst))
+        for i in runs:
+            if cur and (len(cur) == LDP_BATCH_MAX or (self.max_bytes and self.run_batch_bytes(cur + [i], batch) + own(cur + [i]) > self.max_bytes)):
+                packs.append(cur)
+                cur = []
+            cur.append(int(i))
+        return packs + ([cur] if cur else [])
+
+    def feed(self, consumer, runs=None, slot=None, qp=None, batch=None, bundle_of=None):
         """replays the listed runs (None: all) at `slot`, or at the slot of each run that holds `qp`, into a Calibrator or a
-        PartitionSim without leaving HBM.  The context's gates should be open (set_thresholds(0, 0)), as for any input of those two."""
+        PartitionSim without leaving HBM.  The context's gates should be open (set_thresholds(0, 0)), as for any input of those two.
+        batch: an LdpBatch; the runs are then packed in order into batches of at most 32 that stay within max_bytes and go through one
+        recurrence launch per chunk each, with bundle bundle_of(run, slot) of the batch (None: bundle 0) in place of the context's;
+        the consumer ends in the state the per-run feeds leave."""
         if (slot is None) == (qp is None):
             raise ValueError("feed takes slot= or qp=")
         if isinstance(consumer, Calibrator):
-            fn = self.lib.ethcnn_replay_feed_calib
+            fn, bfn = self.lib.ethcnn_replay_feed_calib, self.lib.ethcnn_replay_batch_feed_calib
         elif isinstance(consumer, PartitionSim):
-            fn = self.lib.ethcnn_replay_feed_sim
+            fn, bfn = self.lib.ethcnn_replay_feed_sim, self.lib.ethcnn_replay_batch_feed_sim
         else:
             raise TypeError("feed takes a Calibrator or a PartitionSim")
-        for i in (range(len(self)) if runs is None else runs):
-            self._chk(fn(self.h, int(i), int(slot) if slot is not None else self.slot_of(i, qp), consumer.h))
+        runs = list(range(len(self)) if runs is None else runs)
+        slot_for = lambda i: int(slot) if slot is not None else self.slot_of(i, qp)
+        if batch is None:
+            for i in runs:
+                self._chk(fn(self.h, int(i), slot_for(i), consumer.h))
+            return
+        for pack in self._pack(runs, batch):
+            slots = [slot_for(i) for i in pack]
+            bundles = [0 if bundle_of is None else int(bundle_of(i, s)) for i, s in zip(pack, slots)]
+            self._chk(bfn(self.h, batch.h, len(pack), _int_array(pack), _int_array(slots), _int_array(bundles), consumer.h))

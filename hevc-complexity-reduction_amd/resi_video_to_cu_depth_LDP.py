@@ -3,6 +3,7 @@
     resi_video_to_cu_depth_LDP.py <resi.yuv> <width> <height> <qp> [--first-frame 1] [--frames N] [--out cu_depth.dat]
                                   [--state-out state.dat] [--model-dir DIR] [--device 0] [--chunk FRAMES]
                                   [--also RESI_YUV QP OUT]... [--piece-frames FRAMES]
+    resi_video_to_cu_depth_LDP.py --list FILE [--model-dir DIR] [--device 0] [--chunk FRAMES] [--piece-frames FRAMES]
 
 <resi.yuv> is the whole-sequence 4:2:0 residual file HM-16.5_Resi_Pre writes per QP: frame k of the file is POC k.  POC 0 is the intra
 picture and has no residual, so the first frame is 1 unless a later one is asked for (--first-frame > 1 needs the state of the frames
@@ -20,6 +21,14 @@ read in pieces of --piece-frames frames (default 0: as many frames as hold 64 MB
 from piece to piece.  --state-out is the first sequence's.  Every output is written to a temp file; when all sequences are done the
 temp files are renamed one after another and --state-out is written last, so a rename that fails (status 1) leaves the outputs renamed
 before it in place and complete, the others and --state-out absent.
+
+--list FILE predicts up to 32 residual files of ANY frame sizes and frame counts in one run (an evaluation set): one sequence per line,
+RESI_YUV WIDTH HEIGHT QP OUT, empty lines and lines that begin with # apart; relative paths are taken from the working directory.  Every
+sequence is predicted from frame 1 to its end.  One model_LDP_200000_qpXX.dat per QP band in use is loaded once and shared by the
+sequences of that band; all sequences share every recurrence launch (LdpBatch), and each OUT is byte for byte what a run of its own
+writes.  Luma is uploaded in pieces of --piece-frames frames of every sequence (default 0: as many as hold 256 MB of luma over all
+sequences).  Outputs are written to temp files and renamed at the end, as with --also.  The positional arguments, --also, --first-frame,
+--frames, --out and --state-out do not go with --list.
 """
 import argparse
 import os
@@ -58,6 +67,103 @@ def group_members(a):
     if len(set(outs)) != len(outs):
         raise ValueError("two sequences write the same output file")
     return members
+
+
+def parse_list(path):
+    """[(yuv, width, height, qp, out, frames)] of a --list file; ValueError with the line for whatever cannot be run"""
+    if not os.path.isfile(path):
+        raise ValueError("cannot read %s" % path)
+    seqs = []
+    with open(path) as f:
+        for no, line in enumerate(f, 1):
+            words = line.split()
+            if not words or words[0].startswith("#"):
+                continue
+            where = "%s:%d" % (path, no)
+            if len(seqs) == _e.LDP_BATCH_MAX:
+                raise ValueError("%s: more than %d sequences" % (path, _e.LDP_BATCH_MAX))
+            if len(words) != 5:
+                raise ValueError("%s: a line holds RESI_YUV WIDTH HEIGHT QP OUT, not %d words" % (where, len(words)))
+            try:
+                w, h, qp = int(words[1]), int(words[2]), int(words[3])
+            except ValueError:
+                raise ValueError("%s: WIDTH, HEIGHT and QP are numbers" % where)
+            if w < 64 or h < 64:
+                raise ValueError("%s: frame size %dx%d is below one 64x64 CTU" % (where, w, h))
+            if not os.path.isfile(words[0]):
+                raise ValueError("%s: cannot read %s" % (where, words[0]))
+            frame_bytes, size = w * h * 3 // 2, os.path.getsize(words[0])
+            if size % frame_bytes != 0 or size // frame_bytes < 2:
+                raise ValueError("%s: %s: size %d is not the intra picture and one or more %dx%d 4:2:0 residual frames of %d bytes"
+                                 % (where, words[0], size, w, h, frame_bytes))
+            seqs.append((words[0], w, h, qp, words[4], size // frame_bytes - 1))
+    if not seqs:
+        raise ValueError("%s lists no sequence" % path)
+    outs = [os.path.abspath(q[4]) for q in seqs]
+    if len(set(outs)) != len(outs):
+        raise ValueError("%s: two sequences write the same output file" % path)
+    if len(set(_e.lstm_model_name_for_qp(q[3]) for q in seqs)) > _e.LDP_BATCH_BUNDLES:
+        raise ValueError("%s: more than %d QP bands" % (path, _e.LDP_BATCH_BUNDLES))
+    return seqs
+
+
+def run_list(ctx, a, seqs):
+    """the sequences of a --list file through one LdpBatch: one bundle per QP band, luma uploaded a piece of frames at a time, the
+    resident states carry each sequence from piece to piece.  The sequences go to the batch longest first, so those that still have
+    frames are always the first of the list and each keeps its sequence index (its resident state)."""
+    seqs = sorted(seqs, key=lambda q: -q[5])  # (stable)
+    bands = sorted(set(_e.lstm_model_name_for_qp(q[3]) for q in seqs))
+    planes = [q[1] * q[2] for q in seqs]
+    longest = seqs[0][5]
+    piece = max(1, min(longest, a.piece_frames if a.piece_frames > 0 else (256 << 20) // sum(planes)))
+    tmps = ["%s.tmp.%d" % (q[4], os.getpid()) for q in seqs]
+    files, bufs = [], []
+    try:
+        with _e.LdpBatch(ctx, len(bands)) as batch:
+            for i, name in enumerate(bands):
+                qp = next(q[3] for q in seqs if _e.lstm_model_name_for_qp(q[3]) == name)
+                print("LSTM model %d (%s): %s" % (i, name, restore_member_lstm(batch, i, qp, a.model_dir)))
+            batch.set_chunk(a.chunk)
+            maps = [np.memmap(q[0], dtype=np.uint8, mode="r") for q in seqs]
+            files = [open(t, "wb") for t in tmps]
+            nctu = [_e.ctus_per_frame(q[1], q[2]) for q in seqs]
+            d_l = [ctx.alloc(min(piece, q[5]) * pl) for q, pl in zip(seqs, planes)]
+            bufs += d_l
+            d_p = [ctx.alloc(min(piece, q[5]) * n * _e.NOUT * 4) for q, n in zip(seqs, nctu)]
+            bufs += d_p
+            t0 = time.time()
+            for f0 in range(0, longest, piece):
+                call = []
+                for j, (yuv, w, h, qp, out, frames) in enumerate(seqs):
+                    if f0 >= frames:
+                        break
+                    nf, frame_bytes = min(piece, frames - f0), planes[j] * 3 // 2
+                    luma = np.empty((nf, planes[j]), np.uint8)
+                    for t in range(nf):  # luma only: the chroma planes are never read
+                        at = (1 + f0 + t) * frame_bytes
+                        luma[t] = maps[j][at: at + planes[j]]
+                    d_l[j].upload(luma)
+                    call.append({"d_luma": d_l[j], "width": w, "height": h, "nframes": nf, "qp": qp, "i_frame_first": 1 + f0,
+                                 "bundle": bands.index(_e.lstm_model_name_for_qp(qp)), "d_probs": d_p[j]})
+                batch.run_device(call)
+                for j, q in enumerate(call):
+                    d_p[j].download(np.float32, q["nframes"] * nctu[j] * _e.NOUT).astype("<f4").tofile(files[j])
+            dt = time.time() - t0
+            print("Predicting Time: %.3f sec. (%d sequences, %d frames, %d CTUs a frame in all)" % (dt, len(seqs), sum(q[5] for q in seqs), sum(nctu)))
+        for f in files:
+            f.close()
+        files = []
+        for t, q in zip(tmps, seqs):
+            os.replace(t, q[4])
+    finally:
+        ctx.synchronize()
+        for b in bufs:
+            b.free()
+        for f in files:
+            f.close()
+        for t in tmps:
+            if os.path.exists(t):
+                os.remove(t)
 
 
 def restore_member_lstm(group, m, qp, model_dir):
@@ -121,12 +227,37 @@ def run_group(ctx, a, members, nframes):
                 os.remove(t)
 
 
+def main_list(a):
+    """--list FILE: everything that can be refused without a GPU is refused before one is opened"""
+    if a.yuv is not None or a.also or a.state_out or a.frames is not None or a.first_frame != 1:
+        return _fail("--list takes its sequences from the file: no positional arguments, --also, --first-frame, --frames or --state-out")
+    if a.chunk < 0:
+        return _fail("--chunk %d" % a.chunk)
+    if a.piece_frames < 0:
+        return _fail("--piece-frames %d" % a.piece_frames)
+    try:
+        seqs = parse_list(a.list)
+        ctx = _e.EthCnn(device=a.device)
+        try:
+            print("CNN  model: %s" % restore_cnn(ctx, a.model_dir))
+            thr = os.path.join(a.model_dir, "Thr_info.txt")
+            if os.path.exists(thr):
+                ctx.load_thresholds(thr)
+            run_list(ctx, a, seqs)
+        finally:
+            ctx.close()
+    except (_e.EthCnnError, OSError, ValueError) as e:
+        return _fail(str(e))
+    return 0
+
+
 def main(argv):
     ap = argparse.ArgumentParser(prog="resi_video_to_cu_depth_LDP.py", description=__doc__, formatter_class=argparse.RawDescriptionHelpFormatter)
-    ap.add_argument("yuv")
-    ap.add_argument("width", type=int)
-    ap.add_argument("height", type=int)
-    ap.add_argument("qp", type=int)
+    ap.add_argument("yuv", nargs="?")
+    ap.add_argument("width", type=int, nargs="?")
+    ap.add_argument("height", type=int, nargs="?")
+    ap.add_argument("qp", type=int, nargs="?")
+    ap.add_argument("--list", default=None, metavar="FILE")
     ap.add_argument("--first-frame", type=int, default=1)
     ap.add_argument("--frames", type=int, default=None)
     ap.add_argument("--out", default="cu_depth.dat")
@@ -138,8 +269,12 @@ def main(argv):
     ap.add_argument("--piece-frames", type=int, default=0)
     try:
         a = ap.parse_args(argv[1:])
+        if a.list is None and a.qp is None:
+            ap.error("the following arguments are required: yuv, width, height, qp (or --list FILE)")
     except SystemExit as e:
         return int(e.code or 0)
+    if a.list is not None:
+        return main_list(a)
     # everything that can be refused without a GPU is refused before one is opened
     if a.width <= 0 or a.height <= 0:
         return _fail("bad frame size %dx%d" % (a.width, a.height))

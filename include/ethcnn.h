@@ -336,6 +336,66 @@ int ethcnn_ldp_group_get_state(ethcnn_ldp_group* grp, int m, float* state_out, s
 int64_t ethcnn_ldp_group_state_ctus(ethcnn_ldp_group* grp, int m);
 int ethcnn_ldp_group_set_chunk(ethcnn_ldp_group* grp, int frames);
 int64_t ethcnn_ldp_group_bytes(int width, int height, int nframes, int chunk_frames, int k);
+/* ---- config #5 offline, batch form: up to 32 residual sequences of DIFFERENT geometry, length and first frame number through the chain
+ *      together (an evaluation set, or the runs of an inter sample file), on one GPU.  The object holds up to 8 ETH-LSTM bundles; every
+ *      sequence names its bundle by index, so several sequences of one QP band share one device image.
+ *      DEFINITION: for every j, seqs[j].d_probs and the resident state left for sequence index j EQUAL what ethcnn_ldp_sequence_device
+ *      gives with the same remaining arguments on a context that holds bundle seqs[j].bundle, bit for bit, gates and their zero patterns
+ *      (per frame and 1024-CTU mini-batch of that sequence's own picture) included.  The residual CNN, the thresholds and the stream are
+ *      the context's; the context's own LSTM bundle, resident LDP state and sequence buffers are neither used nor changed.
+ *      What differs is the schedule: a call is cut into chunks of Fc frames common to all sequences; chunk t holds frames
+ *      [t Fc, min((t + 1) Fc, nframes_j)) of every sequence that still has frames.  Per chunk the front-end runs per sequence as in the
+ *      solo call, then ONE recurrence launch and ONE gate launch serve all sequences of the chunk (level-major block order; inside a
+ *      level the sequences with most frames in the launch first).  A launch lasts as long as its longest member.
+ *   ethcnn_ldp_batch_create       nbundles bundle places on ctx (ETHCNN_ERR_ARG outside 1..8; text: ethcnn_last_error of the context).
+ *                                 Destroy the batch before its context.  Errors of every other entry: ethcnn_ldp_batch_last_error.
+ *   ethcnn_ldp_batch_load_lstm_checkpoint / _load_lstm_blob / _load_lstm_synthetic / _get_lstm_blob   bundle i, as the group's take member m's
+ *   ethcnn_ldp_batch_run_device   nseqs = 1..32 sequences.  Device pointers, asynchronous on the context's stream.  i_frame_first >= 1 per
+ *                                 sequence (0, the intra picture, is ETHCNN_ERR_ARG here; the solo and group calls keep accepting it).
+ *                                 With i_frame_first == 1 the start state is zero; above 1 it is d_state_in when given, else the resident
+ *                                 state of index j (the error of ethcnn_ldp_step, ETHCNN_ERR_ARG, if that is empty or belongs to another
+ *                                 CTU count).  Inside a sequence the state is always carried.  Each sequence index has ONE resident state
+ *                                 buffer of its own roundup16(nctu) CTUs, owned by the batch and advanced in place.  Refused before anything
+ *                                 is allocated or enqueued, every state left as it was: an open streamed call, no CNN weights, a bundle
+ *                                 index that is out of range or empty (ETHCNN_ERR_NOWEIGHTS, the text names sequence and bundle), a null
+ *                                 pointer, bad geometry, nframes <= 0, nseqs outside 1..32, a d_probs that overlaps another sequence's
+ *                                 d_probs or d_state_in (ETHCNN_ERR_ARG).  NOT checked, the caller's to keep apart: a d_probs against
+ *                                 the same sequence's d_state_in and against any d_luma.  A failure after that point drops every
+ *                                 resident state.
+ *   ethcnn_ldp_batch_get_state    the resident state of sequence index j, float32 [nctu][2][448]; synchronous
+ *   ethcnn_ldp_batch_state_ctus   its CTU count; 0: none; negative: bad arguments
+ *   ethcnn_ldp_batch_set_chunk    Fc; 0 = default: max(1, floor(256 MB / sum_j nctu_j x 1792)).  Results do not depend on it.
+ *   ethcnn_ldp_batch_bytes        host only, no context: sum_j min(nframes_j, Fc) nctu_j 1792 (vectors) + sum_j roundup16(nctu_j) 3584 (the
+ *                                 resident states); negative for bad arguments.  Beside it, from load time: the bundle images.  A call that
+ *                                 cannot get its buffers fails with ETHCNN_ERR_NOMEM and this sum in the message, before anything is
+ *                                 allocated or enqueued.
+ *   ethcnn_ldp_batch_plan         host only: for CTU counts and frame counts, Fc, the number of chunks, and per chunk four ints
+ *                                 {sequences that take part, recurrence blocks at level 16, 32, 64} (sequence j: G_j, ceil(G_j / 2),
+ *                                 ceil(G_j / 4) with G_j = ceil(nctu_j / 16)); at most max_chunks rows are written. */
+typedef struct ethcnn_ldp_batch ethcnn_ldp_batch;
+typedef struct ethcnn_ldp_batch_seq {
+    const uint8_t* d_luma;
+    int width, height;
+    ptrdiff_t pitch, frame_stride;
+    int nframes, qp, i_frame_first, bundle;
+    const float* d_state_in; /* may be NULL */
+    float* d_probs;          /* [nframes][nctu][21] */
+} ethcnn_ldp_batch_seq;
+int ethcnn_ldp_batch_create(ethcnn_ctx* ctx, int nbundles, ethcnn_ldp_batch** out);
+void ethcnn_ldp_batch_destroy(ethcnn_ldp_batch* b);
+const char* ethcnn_ldp_batch_last_error(const ethcnn_ldp_batch* b);
+int ethcnn_ldp_batch_bundles(const ethcnn_ldp_batch* b);
+int ethcnn_ldp_batch_load_lstm_checkpoint(ethcnn_ldp_batch* b, int bundle, const char* prefix);
+int ethcnn_ldp_batch_load_lstm_blob(ethcnn_ldp_batch* b, int bundle, const float* blob, size_t nfloats);
+int ethcnn_ldp_batch_load_lstm_synthetic(ethcnn_ldp_batch* b, int bundle, uint64_t seed, double head_gain);
+int ethcnn_ldp_batch_get_lstm_blob(ethcnn_ldp_batch* b, int bundle, float* out, size_t nfloats);
+int ethcnn_ldp_batch_run_device(ethcnn_ldp_batch* b, const ethcnn_ldp_batch_seq* seqs, int nseqs);
+int ethcnn_ldp_batch_get_state(ethcnn_ldp_batch* b, int j, float* state_out, size_t nfloats /* nctu * 896 */);
+int64_t ethcnn_ldp_batch_state_ctus(ethcnn_ldp_batch* b, int j);
+int ethcnn_ldp_batch_set_chunk(ethcnn_ldp_batch* b, int frames);
+int64_t ethcnn_ldp_batch_bytes(const int* widths, const int* heights, const int* nframes, int nseqs, int chunk_frames);
+int ethcnn_ldp_batch_plan(const int* nctus, const int* nframes, int nseqs, int chunk_frames, int* fc_out, int* nchunks_out,
+                          int* chunks_out /* [max_chunks][4] */, int max_chunks);
 /* Pinned (page-locked) host memory: buffers a caller fills itself (file reads) and hands to the host entry points are
  * DMA-able directly, without the runtime's pageable staging copy.  ethcnn_ldp_step goes further: a luma / probs pointer that
  * lies inside such a buffer is read / written by the kernels IN PLACE (no copy launch at all); so does ethcnn_predict_luma for ONE
@@ -1575,6 +1635,27 @@ int ethcnn_replay_run_group_device(ethcnn_replay* rp, int run, int nslots, const
  * width = 64 C, height = 64 R, skip_label_frames = 0: nothing goes through the host.  Synchronous, as those entries are. */
 int ethcnn_replay_feed_calib(ethcnn_replay* rp, int run, int slot, ethcnn_calib* cal);
 int ethcnn_replay_feed_sim(ethcnn_replay* rp, int run, int slot, ethcnn_sim* sim);
+/* Several runs through an ethcnn_ldp_batch (config #5 offline, batch form) of the same context: item j = run runs[j] at slot slots[j]
+ * with bundle bundles[j] of the batch, nitems = 1..32.  The runs may differ in geometry, length and first frame; a run may be listed more
+ * than once, with different slots.  Per chunk the uncut kernel runs once per item that still has frames, then ONE batch call runs on
+ * the chunk's planes.  Per item the outputs equal ethcnn_replay_run_device(rp, runs[j], slots[j], ...) on a context with that item's
+ * bundle, word for word (the start state is zero, also when f0 > 1); chunked equals unchunked.  The chunk is Fc frames for all items:
+ * ethcnn_replay_set_chunk_frames, else max(1, floor(256 MB / sum_j nctu_j 4096)).  The states travel in the batch's resident buffers
+ * (the items are handed to the batch longest first, so the sequence indices they use are an implementation matter: do not mix these
+ * entries with calls of ethcnn_ldp_batch_run_device that continue from resident states).
+ * Memory: ethcnn_replay_batch_bytes = sum_j (min(F_j, Fc) nctu_j 4096 + F_j nctu_j 8) + 3584 x the largest nctu_j of the items with
+ * f0 > 1 + the copy of the records; the feed entries hold sum_j F_j nctu_j (84 + 16) more for the object's own outputs.  What a call
+ * holds is checked against max_bytes and the free device memory before anything is allocated.  Outside the sum: what the batch holds
+ * (ethcnn_ldp_batch_bytes).  ethcnn_replay_batch_device: d_probs[j], d_labels[j] in HBM, all given; asynchronous on the context's stream.
+ * The feed entries replay into the object's own buffers and then add the items to the consumer in list order with the arguments of
+ * ethcnn_replay_feed_calib / _feed_sim: the consumer ends in exactly the state the per-run feeds in that order leave.  Synchronous. */
+int64_t ethcnn_replay_batch_bytes(ethcnn_replay* rp, ethcnn_ldp_batch* b, int nitems, const int* runs);
+int ethcnn_replay_batch_device(ethcnn_replay* rp, ethcnn_ldp_batch* b, int nitems, const int* runs, const int* slots, const int* bundles,
+                               float* const* d_probs, uint8_t* const* d_labels);
+int ethcnn_replay_batch_feed_calib(ethcnn_replay* rp, ethcnn_ldp_batch* b, int nitems, const int* runs, const int* slots, const int* bundles,
+                                   ethcnn_calib* cal);
+int ethcnn_replay_batch_feed_sim(ethcnn_replay* rp, ethcnn_ldp_batch* b, int nitems, const int* runs, const int* slots, const int* bundles,
+                                 ethcnn_sim* sim);
 
 #ifdef __cplusplus
 }

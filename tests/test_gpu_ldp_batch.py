@@ -1,0 +1,367 @@
+"""-m gpu: Low-Delay-P residual sequences of different sizes, lengths and first frame numbers through one recurrence launch per chunk
+(include/ethcnn.h "config #5 offline, batch form") against the definition: sequence j's probabilities and resident state are what
+ethcnn_ldp_sequence_device gives on a context loaded with j's bundle, for j's input, QP and first frame.  Every comparison is
+array_equal on the raw 32-bit words.  Bundles are seeded, with a seed, head gain and QP of their own; one is the reference's real QP-32
+bundle.
+
+Shapes: the smallest at which a part of the block mapping can go wrong -- 1 CTU; 12 CTUs (one ragged 16-CTU group); 17 (a full group
+and a ragged one); 28 (416x240: partial CTUs at the right and bottom edge); 65 (a second level-64 block); 1056 (the gates' second
+1024-CTU mini-batch).  Different frame counts and first frame numbers in one launch: the row's own F and i_frame % 4."""
+import os
+import subprocess
+import sys
+
+import numpy as np
+import pytest
+
+pytestmark = pytest.mark.gpu
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+REAL = os.path.join(ROOT, "tests", "golden", "model_LDP_200000_qp32.dat")
+DRIVER = os.path.join(ROOT, "hevc-complexity-reduction_amd", "resi_video_to_cu_depth_LDP.py")
+ERR_ARG, ERR_NOWEIGHTS = -1, -5
+# (LSTM seed, head gain, QP) per bundle; "real" stands for the reference's bundle.  Gains chosen on the CPU (oracle lstm_step on the
+# frames of CASE1 with open gates): with bundle 0 the y64 of the 1-CTU member is 0.488 and the y64 maximum of the 28-CTU member's first
+# frame 0.494 -- first gate closed at 0.5 --, its later frames reach 0.507 and 0.528; bundle 2 saturates (0.98 and more)
+BUNDLES = [(42, 0.5, 37), ("real", None, 32), (41, 3.0, 22)]
+# (width, height, frames, i_frame_first, bundle): CTU counts 1, 12, 17, 28, 65
+CASE1 = [(64, 64, 1, 1, 0), (768, 64, 2, 2, 1), (1088, 64, 5, 3, 2), (416, 240, 3, 1, 0), (4160, 64, 2, 5, 2)]
+
+
+def _bits(a):
+    return np.ascontiguousarray(a, dtype=np.float32).view(np.uint32)
+
+
+def _same(got, want, what):
+    assert got.shape == want.shape, what
+    assert np.array_equal(_bits(got), _bits(want)), "%s: %d words differ, max |d| = %g" % (what, int((_bits(got) != _bits(want)).sum()), np.abs(got - want).max())
+
+
+def _frames(seed, w, h, nf):
+    """residual-like luma with quieter bands that move from frame to frame (tests/test_gpu_ldp_sequence.py)"""
+    rng = np.random.default_rng(seed)
+    out = rng.integers(0, 256, size=(nf, h, w), dtype=np.uint8)
+    for t in range(nf):
+        r0 = (t * h // nf) // 2
+        out[t, r0: r0 + h // 2] = (out[t, r0: r0 + h // 2] // (8 << (t % 3)) + 120).astype(np.uint8)
+    return out
+
+
+def _state(seed, n):
+    rng = np.random.default_rng(seed)
+    return np.stack([rng.uniform(-5, 5, (n, 448)), rng.uniform(-1, 1, (n, 448))], 1).astype(np.float32)
+
+
+def _nctu(w, h):
+    return ((w + 63) // 64) * ((h + 63) // 64)
+
+
+def _load_ctx(c, b):
+    if b[0] == "real":
+        c.load_lstm_checkpoint(REAL)
+    else:
+        c.load_lstm_synthetic(b[0], b[1])
+
+
+@pytest.fixture(scope="module")
+def ctx(pkg, oracle):
+    c = pkg.EthCnn(device=0)
+    c.load_blob(oracle.synth_blob(21, 1.0))
+    c.set_thresholds(0.5, 0.5)
+    yield c
+    c.close()
+
+
+def _solo(c, b, lum, w, h, first, state_in=None, load=True):
+    """the reference: ldp_sequence_device on the context loaded with the bundle -> (probs, final state)"""
+    nf, n = lum.shape[0], _nctu(w, h)
+    if load:
+        _load_ctx(c, b)
+    d_l, d_p = c.alloc(lum.size), c.alloc(nf * n * 21 * 4)
+    d_s = None
+    try:
+        d_l.upload(lum)
+        if state_in is not None:
+            d_s = c.alloc(state_in.nbytes)
+            d_s.upload(state_in)
+        c.ldp_sequence_device(d_l, w, h, nf, b[2], first, d_p, d_state_in=d_s)
+        return d_p.download(np.float32, nf * n * 21).reshape(nf, n, 21), c.ldp_get_state(w, h)
+    finally:
+        c.synchronize()
+        for x in (d_l, d_p, d_s):
+            if x is not None:
+                x.free()
+
+
+def _batch(pkg, c, bundles=BUNDLES, places=None):
+    b = pkg.LdpBatch(c, places or len(bundles))
+    for i, bd in enumerate(bundles):
+        if bd[0] == "real":
+            b.load_lstm_checkpoint(i, REAL)
+        else:
+            b.load_lstm_synthetic(i, bd[0], bd[1])
+    return b
+
+
+def _seqs(case, lums, sins, bundles=BUNDLES):
+    return [{"luma": lums[j], "width": w, "height": h, "qp": bundles[bi][2], "i_frame_first": first, "bundle": bi, "state_in": sins[j]}
+            for j, (w, h, nf, first, bi) in enumerate(case)]
+
+
+_CASE1 = {}  # the inputs and solo results of CASE1: computed once, never changed
+
+
+def _case1(c):
+    if not _CASE1:
+        lums = [_frames(3000 + j, w, h, nf) for j, (w, h, nf, first, bi) in enumerate(CASE1)]
+        sins = [_state(80 + j, _nctu(w, h)) if first > 1 else None for j, (w, h, nf, first, bi) in enumerate(CASE1)]
+        want = [_solo(c, BUNDLES[bi], lums[j], w, h, first, sins[j]) for j, (w, h, nf, first, bi) in enumerate(CASE1)]
+        _CASE1.update(lums=lums, sins=sins, want=want)
+    return _CASE1["lums"], _CASE1["sins"], _CASE1["want"]
+
+
+def _check_case1(b, got, want, what=""):
+    for j in range(len(CASE1)):
+        _same(got[j], want[j][0], "%ssequence %d: probabilities" % (what, j))
+        _same(b.get_state(j), want[j][1], "%ssequence %d: state" % (what, j))
+
+
+def test_mixed_batch_equals_the_solo_calls(pkg, ctx):
+    lums, sins, want = _case1(ctx)
+    # the solo results alone hold a (frame, mini-batch) with a closed first gate and one with an open one (every frame here is one
+    # mini-batch): a gate launch that does nothing, or zeroes everything, cannot pass
+    closed = [(j, t) for j in range(5) for t in range(CASE1[j][2]) if (want[j][0][t][:, 1:] == 0).all()]
+    opened = [(j, t) for j in range(5) for t in range(CASE1[j][2]) if (want[j][0][t][:, 1:5] != 0).any()]
+    assert (0, 0) in closed and (3, 0) in closed and (3, 1) in opened and (2, 0) in opened, (closed, opened)
+    for j, t in closed:
+        assert (want[j][0][t][:, 0] <= 0.5).all() and (want[j][0][t][:, 0] > 0).all()
+    with _batch(pkg, ctx) as b:
+        got = b.run(_seqs(CASE1, lums, sins))
+        _check_case1(b, got, want)
+        assert [b.state_ctus(j) for j in range(6)] == [1, 12, 17, 28, 65, 0]
+
+
+@pytest.mark.parametrize("thr", [(0.0, 0.0), (0.5, 0.5)])
+def test_second_gate_mini_batch_beside_a_foreign_member(pkg, ctx, thr):
+    case = [(2112, 2048, 2, 1, 2), (64, 64, 5, 1, 0)]
+    lums = [_frames(3100 + j, w, h, nf) for j, (w, h, nf, first, bi) in enumerate(case)]
+    ctx.set_thresholds(*thr)
+    try:
+        want = [_solo(ctx, BUNDLES[bi], lums[j], w, h, first) for j, (w, h, nf, first, bi) in enumerate(case)]
+        with _batch(pkg, ctx) as b:
+            got = b.run(_seqs(case, lums, [None, None]))
+            for j in range(2):
+                _same(got[j], want[j][0], "sequence %d: probabilities" % j)
+                _same(b.get_state(j), want[j][1], "sequence %d: state" % j)
+    finally:
+        ctx.set_thresholds(0.5, 0.5)
+
+
+def test_results_do_not_depend_on_the_chunk(pkg, ctx):
+    lums, sins, want = _case1(ctx)
+    # with chunks of 2 frames the one-frame member (and the two-frame ones) are absent from the second and third launch
+    plan = pkg.ethcnn.ldp_batch_plan([_nctu(c[0], c[1]) for c in CASE1], [c[2] for c in CASE1], 2)
+    assert [c["members"] for c in plan["chunks"]] == [5, 2, 1]
+    with _batch(pkg, ctx) as b:
+        for chunk in (1, 2, 0):
+            b.set_chunk(chunk)
+            _check_case1(b, b.run(_seqs(CASE1, lums, sins)), want, "chunk %d, " % chunk)
+
+
+def test_a_second_call_continues_from_the_resident_states(pkg, ctx):
+    case = [(1088, 64, 6, 1, 2), (200, 136, 6, 1, 1)]
+    lums = [_frames(3200 + j, w, h, nf) for j, (w, h, nf, first, bi) in enumerate(case)]
+    want = [_solo(ctx, BUNDLES[bi], lums[j], w, h, 1) for j, (w, h, nf, first, bi) in enumerate(case)]
+
+    def part(lo, hi, first, order=(0, 1)):
+        return [{"luma": lums[j][lo:hi], "width": case[j][0], "height": case[j][1], "qp": BUNDLES[case[j][4]][2], "i_frame_first": first,
+                 "bundle": case[j][4]} for j in order]
+
+    with _batch(pkg, ctx) as b:
+        with pytest.raises(pkg.EthCnnError) as e:  # nothing resident yet
+            b.run(part(3, 6, 4))
+        assert e.value.code == ERR_ARG and "sequence 0" in str(e.value)
+        head = b.run(part(0, 3, 1))
+        tail = b.run(part(3, 6, 4))
+        for j in range(2):
+            _same(np.concatenate([head[j], tail[j]]), want[j][0], "sequence %d: two calls" % j)
+            _same(b.get_state(j), want[j][1], "sequence %d: state after two calls" % j)
+        # another geometry at an index: its resident state (17 CTUs at index 0, 12 at index 1) is refused, and kept
+        with pytest.raises(pkg.EthCnnError) as e:
+            b.run(part(3, 6, 4, order=(1, 0)))
+        assert e.value.code == ERR_ARG and "12 CTUs" in str(e.value)
+        for j in range(2):
+            _same(b.get_state(j), want[j][1], "sequence %d: state behind the refusal" % j)
+        b.run(part(0, 3, 1, order=(1, 0)))  # from frame 1 the indices take the other geometry ...
+        assert [b.state_ctus(j) for j in range(2)] == [12, 17]
+        with pytest.raises(pkg.EthCnnError) as e:  # ... and the old one cannot continue there
+            b.run(part(3, 6, 4))
+        assert e.value.code == ERR_ARG
+        tail = b.run(part(3, 6, 4, order=(1, 0)))
+        for pos, j in enumerate((1, 0)):
+            _same(tail[pos], want[j][0][3:], "sequence %d at index %d" % (j, pos))
+
+
+def test_thirty_two_members_and_not_one_more(pkg, ctx):
+    bundles = [BUNDLES[0], BUNDLES[2]]
+    lums = [_frames(3300 + j, 64, 64, 1 + j % 3) for j in range(33)]
+    firsts = [1 + j % 2 for j in range(33)]
+    sins = [_state(90 + j, 1) if firsts[j] > 1 else None for j in range(33)]
+    want = [None] * 32
+    for bi in range(2):  # (one bundle load per bundle)
+        _load_ctx(ctx, bundles[bi])
+        for j in range(bi, 32, 2):
+            want[j] = _solo(ctx, bundles[bi], lums[j], 64, 64, firsts[j], sins[j], load=False)
+    seqs = [{"luma": lums[j], "width": 64, "height": 64, "qp": bundles[j % 2][2], "i_frame_first": firsts[j], "bundle": j % 2, "state_in": sins[j]}
+            for j in range(33)]
+    with _batch(pkg, ctx, bundles) as b:
+        with pytest.raises(pkg.EthCnnError) as e:
+            b.run(seqs)
+        assert e.value.code == ERR_ARG and "33" in str(e.value)
+        got = b.run(seqs[:32])
+        for j in range(32):
+            _same(got[j], want[j][0], "sequence %d: probabilities" % j)
+            _same(b.get_state(j), want[j][1], "sequence %d: state" % j)
+
+
+def test_uniform_members_equal_the_group_call(pkg, ctx):
+    w, h, nf, first = 1088, 64, 3, 3
+    n = _nctu(w, h)
+    members = [BUNDLES[0], BUNDLES[2], BUNDLES[1], BUNDLES[0]]
+    lums = [_frames(3400 + m, w, h, nf) for m in range(4)]
+    sins = [_state(60 + m, n) for m in range(4)]
+    with pkg.LdpGroup(ctx, 4) as g:
+        for m, bd in enumerate(members):
+            if bd[0] == "real":
+                g.load_lstm_checkpoint(m, REAL)
+            else:
+                g.load_lstm_synthetic(m, bd[0], bd[1])
+        want = g.sequence(lums, w, h, [bd[2] for bd in members], i_frame_first=first, state_ins=sins)
+        states = [g.get_state(m) for m in range(4)]
+    with _batch(pkg, ctx) as b:
+        got = b.run([{"luma": lums[m], "width": w, "height": h, "qp": members[m][2], "i_frame_first": first, "bundle": BUNDLES.index(members[m]),
+                      "state_in": sins[m]} for m in range(4)])
+        for m in range(4):
+            _same(got[m], want[m], "member %d: probabilities" % m)
+            _same(b.get_state(m), states[m], "member %d: state" % m)
+
+
+def test_refusals_enqueue_nothing_and_keep_the_states(pkg, ctx):
+    lums, sins, want = _case1(ctx)
+    for k in (0, 9):
+        with pytest.raises(pkg.EthCnnError) as e:
+            pkg.LdpBatch(ctx, k)
+        assert e.value.code == ERR_ARG
+    bufs = []
+    alloc = lambda nbytes: bufs.append(ctx.alloc(nbytes)) or bufs[-1]
+    mark = [np.full(nf * _nctu(w, h) * 21, 7.0, np.float32) for (w, h, nf, first, bi) in CASE1]
+    try:
+        seqs = []
+        for j, (w, h, nf, first, bi) in enumerate(CASE1):
+            q = {"d_luma": alloc(lums[j].size), "width": w, "height": h, "nframes": nf, "qp": BUNDLES[bi][2], "i_frame_first": first, "bundle": bi,
+                 "d_probs": alloc(mark[j].nbytes)}
+            q["d_luma"].upload(lums[j])
+            if sins[j] is not None:
+                q["d_state_in"] = alloc(sins[j].nbytes)
+                q["d_state_in"].upload(sins[j])
+            seqs.append(q)
+
+        def run_case1(b):
+            b.run_device(seqs)
+            ctx.synchronize()
+            return [seqs[j]["d_probs"].download(np.float32, mark[j].size).reshape(want[j][0].shape) for j in range(5)]
+
+        def changed(j, **kw):
+            return [dict(q, **kw) if i == j else q for i, q in enumerate(seqs)]
+
+        with _batch(pkg, ctx, places=4) as b:  # (bundle 3 stays empty)
+            _check_case1(b, run_case1(b), want)
+            refusals = [("i_frame_first 0", changed(3, i_frame_first=0), ERR_ARG, "sequence 3"),
+                        ("an empty bundle", changed(2, bundle=3), ERR_NOWEIGHTS, "sequence 2: bundle 3"),
+                        ("a bundle out of range", changed(4, bundle=4), ERR_NOWEIGHTS, "sequence 4: bundle 4"),
+                        ("d_probs on another's d_probs", changed(1, d_probs=seqs[2]["d_probs"].ptr + 84), ERR_ARG, "overlaps"),
+                        ("d_probs on another's d_state_in", changed(0, d_probs=seqs[4]["d_state_in"]), ERR_ARG, "overlaps"),
+                        ("null luma", changed(2, d_luma=None), ERR_ARG, "sequence 2"),
+                        ("null probs", changed(4, d_probs=None), ERR_ARG, "sequence 4"),
+                        ("no frames", changed(1, nframes=0), ERR_ARG, "sequence 1"),
+                        ("a pitch below the width", changed(3, pitch=415), ERR_ARG, "sequence 3"),
+                        ("no sequences", [], ERR_ARG, "0 sequences")]
+            for what, bad, code, text in refusals:
+                for j in range(5):
+                    seqs[j]["d_probs"].upload(mark[j])
+                with pytest.raises(pkg.EthCnnError) as e:
+                    b.run_device(bad)
+                assert e.value.code == code and text in str(e.value), (what, str(e.value))
+                ctx.synchronize()
+                for j in range(5):
+                    assert np.array_equal(seqs[j]["d_probs"].download(np.float32, mark[j].size), mark[j]), (what, j)
+                    _same(b.get_state(j), want[j][1], "%s: state of sequence %d behind the refusal" % (what, j))
+                _check_case1(b, run_case1(b), want, "behind %s: " % what)
+            with pytest.raises(pkg.EthCnnError) as e:
+                b.get_lstm_blob(3)
+            assert e.value.code == ERR_NOWEIGHTS
+            with pytest.raises(pkg.EthCnnError) as e:
+                b.get_state(5)
+            assert e.value.code == ERR_ARG
+    finally:
+        ctx.synchronize()
+        for x in bufs:
+            x.free()
+
+
+def test_the_context_keeps_its_bundle_and_state(pkg, ctx):
+    lums, sins, want = _case1(ctx)
+    w, h = 200, 136
+    own = (48, 5.0, 40)
+    lum = _frames(3500, w, h, 5)
+    whole, _ = _solo(ctx, own, lum, w, h, 1)
+    head, state2 = _solo(ctx, own, lum[:2], w, h, 1)
+    blob = ctx.get_lstm_blob()
+    with _batch(pkg, ctx) as b:
+        b.run(_seqs(CASE1, lums, sins))
+        _same(ctx.ldp_get_state(w, h), state2, "the context's resident state behind a batch call")
+        assert np.array_equal(_bits(ctx.get_lstm_blob()), _bits(blob))
+        d_l, d_p = ctx.alloc(lum[2:].size), ctx.alloc(3 * 12 * 21 * 4)
+        try:
+            d_l.upload(lum[2:])
+            ctx.ldp_sequence_device(d_l, w, h, 3, own[2], 3, d_p)  # continues from the context's own resident state
+            tail = d_p.download(np.float32, 3 * 12 * 21).reshape(3, 12, 21)
+        finally:
+            ctx.synchronize()
+            d_l.free()
+            d_p.free()
+    _same(np.concatenate([head, tail]), whole, "solo calls around a batch call")
+
+
+# ---------------------------------------------------------------------------------------------------------------------- driver ---
+def _write_resi(path, lum):
+    nf, h, w = lum.shape
+    with open(path, "wb") as f:
+        for k in range(nf + 1):  # frame 0 is the intra picture
+            f.write((lum[k - 1] if k else np.zeros((h, w), np.uint8)).tobytes())
+            f.write(np.full(w * h // 2, 128, np.uint8).tobytes())
+
+
+def test_driver_with_a_list_of_three_sequences(tmp_path):
+    import shutil
+    files = [("a", 200, 136, 32, 4), ("b", 128, 64, 22, 2), ("c", 416, 240, 32, 3)]  # name, width, height, QP, residual frames
+    for name, w, h, qp, nf in files:
+        _write_resi(str(tmp_path / (name + ".yuv")), _frames(40 + nf, w, h, nf))
+    for ext in (".index", ".data-00000-of-00001"):
+        shutil.copy(REAL + ext, str(tmp_path / ("model_LDP_200000_qp32.dat" + ext)))  # QP 32: the real bundle; QP 22: seeded
+    env = dict(os.environ, ETHCNN_SYNTHETIC_SEED="21")
+
+    def run(*args):
+        return subprocess.run([sys.executable, DRIVER] + [str(x) for x in args] + ["--model-dir", str(tmp_path)], capture_output=True, text=True,
+                              env=env, timeout=300)
+
+    lst = tmp_path / "set.txt"
+    lst.write_text("".join("%s %d %d %d %s\n" % (tmp_path / (name + ".yuv"), w, h, qp, tmp_path / (name + ".list.dat")) for name, w, h, qp, nf in files))
+    runs = [run(tmp_path / (name + ".yuv"), w, h, qp, "--out", tmp_path / (name + ".solo.dat")) for name, w, h, qp, nf in files]
+    runs.append(run("--list", lst, "--piece-frames", 2))
+    for r in runs:
+        assert r.returncode == 0, r.stderr[-800:]
+    for name, w, h, qp, nf in files:
+        solo = open(str(tmp_path / (name + ".solo.dat")), "rb").read()
+        assert len(solo) == nf * _nctu(w, h) * 21 * 4
+        assert open(str(tmp_path / (name + ".list.dat")), "rb").read() == solo, name
+    assert not [f for f in os.listdir(str(tmp_path)) if ".tmp." in f]

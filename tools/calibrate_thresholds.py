@@ -24,11 +24,13 @@ Any number of cases, accumulated into one histogram:
   --samples FILE --model PREFIX --qp Q [--net ai|ldp]
         a trainer's evaluation (forward only, no gates in that graph) of a validation sample file with the checkpoint PREFIX; the
         truth is the 16 label bytes of QP row Q (All-Intra records: byte 4160 + 16 Q) or of the slot whose QP byte is Q (LDP records).
-  --samples FILE --ldp --model-dir D --qp Q
+  --samples FILE --ldp --model-dir D --qp Q [--batch]
         an inter sample file (LDP_Valid.dat, LDP_Test.dat, plain or _shuffled) replayed through the deployed Low-Delay-P chain
         (include/ethcnn.h "sample-set replay"): the residual pictures and label planes of every sequence the file holds are put back
         together on the GPU, in any record order, and predicted as the daemon would, gates open, with the models of D (as for --yuv
         --ldp).  Q selects the QP slot; a file without a slot of that QP is an error.  One line per sequence goes to stderr.
+        --batch sends the sequences of the file through the chain together, up to 32 at a time in one recurrence launch per chunk
+        (include/ethcnn.h "config #5 offline, batch form"); the output is the same, byte for byte.
 
 --input-bit-depth (8..16; above 8 the file holds 16-bit little-endian samples) and --input-chroma-format give the source format of
 the All-Intra --yuv cases of the run (include/ethcnn.h "high-bit-depth and non-4:2:0 sources"); --ldp cases read HM's residual files,
@@ -119,6 +121,10 @@ def parse(argv, labels_optional=False):
             if not cases or cases[-1]["kind"] not in ("yuv", "samples"):
                 raise Usage("--ldp follows a --yuv or a --samples case")
             cases[-1]["ldp"] = True
+        elif a == "--batch":
+            if not cases or cases[-1]["kind"] != "samples" or not cases[-1]["ldp"]:
+                raise Usage("--batch follows a --samples FILE --ldp case")
+            cases[-1]["batch"] = True
         elif a in per_case:
             key, conv, kinds = per_case[a]
             if not cases or cases[-1]["kind"] not in kinds:
@@ -254,7 +260,12 @@ def add_cases(pkg, ctx, cal, cases, note):
                 for r in runs:
                     note("sequence %d: %dx%d (%d x %d whole CTUs), frames %d..%d, %d CTUs" % (r["seq"], r["w"], r["h"], r["cols"], r["rows"], r["f0"],
                                                                                             r["f0"] + r["frames"] - 1, r["frames"] * r["nctu"]))
-                rp.feed(cal, qp=qp)
+                if c.get("batch"):  # the sequences of the file together, one recurrence launch per chunk: the same counts
+                    with pkg.LdpBatch(ctx, 1) as batch:
+                        batch.load_lstm_blob(0, ctx.get_lstm_blob())
+                        rp.feed(cal, qp=qp, batch=batch)
+                else:
+                    rp.feed(cal, qp=qp)
         else:
             records = np.fromfile(c["file"], dtype=np.uint8)
             n, depth = _sample_labels(records, c["net"], c["qp"], pkg)

@@ -31,7 +31,7 @@ Cases are those of calibrate_thresholds.py, with labels optional:
         made.  With --gates none the probabilities are taken as what the encoder will read.
   --yuv SEQ W H QP [--labels L] --model-dir D [--ldp [--frame-begin 1]]
   --samples FILE --model PREFIX --qp Q [--net ai|ldp]
-  --samples FILE --ldp --model-dir D --qp Q          (an inter sample file replayed through the deployed Low-Delay-P chain; its
+  --samples FILE --ldp --model-dir D --qp Q [--batch]  (an inter sample file replayed through the deployed Low-Delay-P chain; its
         CTUs come as frames, so the gates apply to them as to a --yuv case)
 
 --input-bit-depth N and --input-chroma-format 400|420|422|444 give the source format of the All-Intra --yuv cases, as in
