@@ -7,6 +7,8 @@
 extern "C" int ethcnn_resi_vectors_device(ethcnn_ctx* c, const uint8_t* d_luma, int w, int h, ptrdiff_t pitch, float* d_vec) {
     if (c) c->done_armed = 0;
     if (!c || !d_luma || !d_vec) return c ? set_err(c, ETHCNN_ERR_ARG, "null pointer") : ETHCNN_ERR_ARG;
+    // (FC1's epilogue stores d_vec dword by dword; the tile stage reads d_luma at any alignment, wide loads only where they fit)
+    if ((uintptr_t)d_vec % 4) return set_err(c, ETHCNN_ERR_ARG, "ethcnn_resi_vectors_device: d_vec is not 4-byte aligned");
     if (!c->have_weights) return set_err(c, ETHCNN_ERR_NOWEIGHTS, "no weights loaded");
     FrameGeom g;
     int rc = make_geom(c, w, h, pitch, (ptrdiff_t)pitch * h, &g);
@@ -100,6 +102,11 @@ static int ensure_lgate(ethcnn_ctx* c, int n) {
 extern "C" int ethcnn_lstm_step_device(ethcnn_ctx* c, const float* d_vec, const float* d_state_in, int n, int qp,
                                        int i_frame, float* d_state_out, float* d_probs) {
     if (!c || !d_vec || !d_state_out || !d_probs) return c ? set_err(c, ETHCNN_ERR_ARG, "null pointer") : ETHCNN_ERR_ARG;
+    // lstm_cell reads d_vec and d_state_in as float4, the heads read d_state_out as float4 / dwordx4; d_probs is stored dword by dword
+    if ((uintptr_t)d_vec % 16) return set_err(c, ETHCNN_ERR_ARG, "ethcnn_lstm_step_device: d_vec is not 16-byte aligned");
+    if ((uintptr_t)d_state_in % 16) return set_err(c, ETHCNN_ERR_ARG, "ethcnn_lstm_step_device: d_state_in is not 16-byte aligned");
+    if ((uintptr_t)d_state_out % 16) return set_err(c, ETHCNN_ERR_ARG, "ethcnn_lstm_step_device: d_state_out is not 16-byte aligned");
+    if ((uintptr_t)d_probs % 4) return set_err(c, ETHCNN_ERR_ARG, "ethcnn_lstm_step_device: d_probs is not 4-byte aligned");
     c->done_armed = 0;
     if (n <= 0) return set_err(c, ETHCNN_ERR_ARG, "n must be positive");
     if (!c->have_lstm) return set_err(c, ETHCNN_ERR_NOWEIGHTS, "no LSTM weights loaded");
@@ -426,6 +433,9 @@ static int seq_recur_solo(ethcnn_ctx* c, int nctu, int nf, int qp, int i0, const
 extern "C" int ethcnn_ldp_sequence_device(ethcnn_ctx* c, const uint8_t* d_luma, int w, int h, ptrdiff_t pitch, ptrdiff_t fstride, int nframes,
                                           int qp, int i_first, const float* d_state_in, float* d_probs) {
     if (!c || !d_luma || !d_probs) return c ? set_err(c, ETHCNN_ERR_ARG, "null pointer") : ETHCNN_ERR_ARG;
+    // lstm_seq_level reads d_state_in as float4; the recurrence and the gate pass touch d_probs dword by dword
+    if ((uintptr_t)d_state_in % 16) return set_err(c, ETHCNN_ERR_ARG, "ethcnn_ldp_sequence_device: d_state_in is not 16-byte aligned");
+    if ((uintptr_t)d_probs % 4) return set_err(c, ETHCNN_ERR_ARG, "ethcnn_ldp_sequence_device: d_probs is not 4-byte aligned");
     c->done_armed = 0;
     int in = -1;
     int rc = seq_check(c, w, h, pitch, nframes, i_first, d_state_in != nullptr, &in);

@@ -212,6 +212,9 @@ extern "C" int ethcnn_ldp_batch_run_device(ethcnn_ldp_batch* b, const ethcnn_ldp
             return berr(b, ETHCNN_ERR_NOWEIGHTS, "sequence %d: bundle %d is %s (ethcnn_ldp_batch_load_lstm_*)", j, q.bundle,
                         q.bundle < 0 || q.bundle >= b->nb ? "outside the batch's bundles" : "empty");
         if (!q.d_luma || !q.d_probs) return berr(b, ETHCNN_ERR_ARG, "null pointer (sequence %d)", j);
+        // lstm_seq_level reads a state as float4; d_probs is touched dword by dword
+        if ((uintptr_t)q.d_state_in % 16) return berr(b, ETHCNN_ERR_ARG, "ethcnn_ldp_batch_run: d_state_in of sequence %d is not 16-byte aligned", j);
+        if ((uintptr_t)q.d_probs % 4) return berr(b, ETHCNN_ERR_ARG, "ethcnn_ldp_batch_run: d_probs of sequence %d is not 4-byte aligned", j);
         if (q.width <= 0 || q.height <= 0 || q.pitch < q.width) return berr(b, ETHCNN_ERR_ARG, "bad geometry (sequence %d)", j);
         if (q.nframes <= 0) return berr(b, ETHCNN_ERR_ARG, "ethcnn_ldp_batch_run: nframes must be positive (sequence %d)", j);
         if (q.i_frame_first < 1)

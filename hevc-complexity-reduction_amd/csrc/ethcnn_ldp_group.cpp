@@ -154,6 +154,10 @@ extern "C" int ethcnn_ldp_group_sequence_device(ethcnn_ldp_group* g, const uint8
     if (!d_luma || !qp || !d_probs) return gerr(g, ETHCNN_ERR_ARG, "null pointer");
     for (int m = 0; m < K; ++m)
         if (!d_luma[m] || !d_probs[m]) return gerr(g, ETHCNN_ERR_ARG, "null pointer (member %d)", m);
+    for (int m = 0; m < K; ++m) {  // lstm_seq_level reads a state as float4; d_probs is touched dword by dword
+        if (d_state_in && (uintptr_t)d_state_in[m] % 16) return gerr(g, ETHCNN_ERR_ARG, "ethcnn_ldp_group_sequence: d_state_in[%d] is not 16-byte aligned", m);
+        if ((uintptr_t)d_probs[m] % 4) return gerr(g, ETHCNN_ERR_ARG, "ethcnn_ldp_group_sequence: d_probs[%d] is not 4-byte aligned", m);
+    }
     if (w <= 0 || h <= 0 || pitch < w) return gerr(g, ETHCNN_ERR_ARG, "bad geometry");
     if (nframes <= 0) return gerr(g, ETHCNN_ERR_ARG, "ethcnn_ldp_group_sequence: nframes must be positive");
     if (i_first < 0) return gerr(g, ETHCNN_ERR_ARG, "ethcnn_ldp_group_sequence: i_frame_first must not be negative");

@@ -201,7 +201,10 @@ int ethcnn_get_source_format(const ethcnn_ctx* ctx, ethcnn_source_format* fmt);
 int ethcnn_source_frame_bytes(const ethcnn_source_format* fmt, int width, int height, int64_t* luma_bytes, int64_t* frame_bytes);
 
 /* ---- config #5 front-end: resi_cnn (HM-16.5_Test_LDP/bin/net_CNN_LSTM_one_step.py:151-199)
- *      fed as in resi_to_cu_depth_LDP.py:72-101.  One frame; vec = float32 [nctu][448]. */
+ *      fed as in resi_to_cu_depth_LDP.py:72-101.  One frame; vec = float32 [nctu][448].
+ *      Alignment of the device pointers: d_luma none (any byte address and pitch give the same vectors; rows that are 16-byte aligned
+ *      -- address, width and pitch -- take the wide loads); d_vec 4 bytes (stored dword by dword, exactly nctu x 448 floats), else
+ *      ETHCNN_ERR_ARG before anything is enqueued. */
 int ethcnn_resi_vectors_device(ethcnn_ctx* ctx, const uint8_t* d_luma, int width, int height,
                                ptrdiff_t pitch, float* d_vec);
 int ethcnn_resi_vectors(ethcnn_ctx* ctx, const uint8_t* luma, int width, int height,
@@ -215,7 +218,11 @@ int ethcnn_resi_vectors(ethcnn_ctx* ctx, const uint8_t* luma, int width, int hei
  *      model_LDP_200000_qp{22,27,32,37}.dat, reloaded when the QP band changes (:166-179).
  *      state: float32 [nctu][2][448] = (c, h) per CTU, the layout of state.dat (:103-106,131-137);
  *      state_in NULL = zeros (i_frame <= 1).  efs = [qp/51*0.18, onehot4(i_frame % 4)].
- *      Gates are per 1024-CTU mini-batch of the frame (:118). */
+ *      Gates are per 1024-CTU mini-batch of the frame (:118).
+ *      ethcnn_lstm_step_device: device pointers to exactly nctu rows each (the kernels work in groups of 16 CTUs, and keep the
+ *      surplus lanes of the last group off the caller's memory).  Alignment: d_vec, d_state_in (when given) and d_state_out 16 bytes
+ *      (read as float4 / dwordx4), d_probs 4 bytes (stored dword by dword).  A pointer below its alignment is refused with
+ *      ETHCNN_ERR_ARG before anything is allocated or enqueued; the text names the argument. */
 #define ETHCNN_LSTM_BLOB_FLOATS 760078 /* 3,040,312-byte TF-V2 .data payload, fp32 */
 int ethcnn_load_lstm_checkpoint(ethcnn_ctx* ctx, const char* prefix);
 int ethcnn_load_lstm_blob(ethcnn_ctx* ctx, const float* blob, size_t nfloats);
@@ -270,6 +277,13 @@ int ethcnn_ldp_step_end(ethcnn_ctx* ctx);
  *      multi-launch passes, the recurrence of a chunk is one launch whose blocks own their CTUs for all frames and keep (c, h) on
  *      chip, a small post-pass applies the gates.  Results do not depend on the chunk size.
  *   ethcnn_ldp_sequence_device   device pointers, asynchronous on the context's stream; d_probs float32 [nframes][nctu][21]
+ *                                Row y of frame t starts at d_luma + t frame_stride + y pitch; nothing outside the width x height
+ *                                pixels of a frame is read, d_state_in is read as exactly nctu rows, and nothing outside
+ *                                [nframes][nctu][21] is written.  Alignment: d_luma, pitch and frame_stride none (16-byte aligned
+ *                                rows take the wide loads, the result is the same); d_state_in 16 bytes when given (read as float4);
+ *                                d_probs 4 bytes (touched dword by dword).  A pointer below its alignment is refused with
+ *                                ETHCNN_ERR_ARG before anything is allocated or enqueued, the resident state left as it was; the
+ *                                text names the argument.  frame_stride is the caller's to get right (not checked here).
  *   ethcnn_ldp_sequence          host pointers (pageable or from ethcnn_host_alloc), synchronous
  *   ethcnn_ldp_predict_yuv_file  a 4:2:0 file of residual frames (HM-16.5_Resi_Pre's resi_XX.yuv): frame k of the file is POC k, so
  *                                i_frame = k; frames [frame_begin, frame_end) are processed and out_path holds exactly those as
@@ -312,7 +326,10 @@ int64_t ethcnn_ldp_sequence_bytes(int width, int height, int nframes, int chunk_
  *                                 may overlap another's d_probs.  Refused before anything is allocated or enqueued, states left as
  *                                 they were: an open streamed call (ETHCNN_ERR_ARG), no CNN weights, a member without a bundle
  *                                 (ETHCNN_ERR_NOWEIGHTS, the text names the member), a null pointer, bad geometry, nframes <= 0,
- *                                 i_frame_first < 0 (ETHCNN_ERR_ARG).  A failure after that point drops every member's resident state.
+ *                                 i_frame_first < 0, a d_state_in[m] that is not 16-byte aligned or a d_probs[m] that is not 4-byte
+ *                                 aligned (ETHCNN_ERR_ARG, the text names argument and member; d_luma[m], pitch and frame_stride need
+ *                                 no alignment, as in the solo call).  A failure after that point drops every member's resident state.
+ *                                 Buffers that lie back to back (member m + 1's at the end of member m's) do not overlap.
  *   ethcnn_ldp_group_get_state    member m's resident state, float32 [nctu][2][448]; synchronous
  *   ethcnn_ldp_group_state_ctus   the CTU count of member m's resident state; 0: none; negative: bad arguments
  *   ethcnn_ldp_group_set_chunk    frames per chunk; 0 = default (256 MB of vectors for the whole group).  Results do not depend on it.
@@ -359,7 +376,9 @@ int64_t ethcnn_ldp_group_bytes(int width, int height, int nframes, int chunk_fra
  *                                 is allocated or enqueued, every state left as it was: an open streamed call, no CNN weights, a bundle
  *                                 index that is out of range or empty (ETHCNN_ERR_NOWEIGHTS, the text names sequence and bundle), a null
  *                                 pointer, bad geometry, nframes <= 0, nseqs outside 1..32, a d_probs that overlaps another sequence's
- *                                 d_probs or d_state_in (ETHCNN_ERR_ARG).  NOT checked, the caller's to keep apart: a d_probs against
+ *                                 d_probs or d_state_in (buffers that lie back to back do not overlap), a d_state_in that is not 16-byte
+ *                                 aligned or a d_probs that is not 4-byte aligned (ETHCNN_ERR_ARG, the text names argument and sequence;
+ *                                 d_luma, pitch and frame_stride need no alignment).  NOT checked, the caller's to keep apart: a d_probs against
  *                                 the same sequence's d_state_in and against any d_luma.  A failure after that point drops every
  *                                 resident state.
  *   ethcnn_ldp_batch_get_state    the resident state of sequence index j, float32 [nctu][2][448]; synchronous

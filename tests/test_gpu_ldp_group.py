@@ -15,6 +15,8 @@ import sys
 import numpy as np
 import pytest
 
+from ldp_buffers import frames as _frames
+
 import replay_ref
 
 pytestmark = pytest.mark.gpu
@@ -34,16 +36,6 @@ def _bits(a):
 def _same(got, want, what):
     assert got.shape == want.shape, what
     assert np.array_equal(_bits(got), _bits(want)), "%s: %d words differ, max |d| = %g" % (what, int((_bits(got) != _bits(want)).sum()), np.abs(got - want).max())
-
-
-def _frames(seed, w, h, nf):
-    """residual-like luma with quieter bands that move from frame to frame (tests/test_gpu_ldp_sequence.py)"""
-    rng = np.random.default_rng(seed)
-    out = rng.integers(0, 256, size=(nf, h, w), dtype=np.uint8)
-    for t in range(nf):
-        r0 = (t * h // nf) // 2
-        out[t, r0: r0 + h // 2] = (out[t, r0: r0 + h // 2] // (8 << (t % 3)) + 120).astype(np.uint8)
-    return out
 
 
 def _state(seed, n):

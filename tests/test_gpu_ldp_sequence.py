@@ -8,6 +8,8 @@ import sys
 import numpy as np
 import pytest
 
+from ldp_buffers import frames as _frames
+
 pytestmark = pytest.mark.gpu
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 REAL = os.path.join(ROOT, "tests", "golden", "model_LDP_200000_qp32.dat")
@@ -16,16 +18,6 @@ QP = 32
 
 def _bits(a):
     return np.ascontiguousarray(a, dtype=np.float32).view(np.uint32)
-
-
-def _frames(seed, w, h, nf):
-    """residual-like luma with quieter bands that move from frame to frame, so that mini-batches and frames differ"""
-    rng = np.random.default_rng(seed)
-    out = rng.integers(0, 256, size=(nf, h, w), dtype=np.uint8)
-    for t in range(nf):
-        r0 = (t * h // nf) // 2
-        out[t, r0: r0 + h // 2] = (out[t, r0: r0 + h // 2] // (8 << (t % 3)) + 120).astype(np.uint8)
-    return out
 
 
 @pytest.fixture(scope="module")
