@@ -5,7 +5,8 @@
 //   ethcnn_host.cpp     host / file entry points: staging ring, worker pool, latency path, streamed pictures, sharded file driver
 //   ethcnn_narrow.cpp   high-bit-depth and non-4:2:0 sources: the source format, the narrowing rule on the host, the device entries
 //   ethcnn_ldp.cpp      config #5: resi vectors, ETH-LSTM step, the per-frame LDP calls, the offline whole-sequence calls
-//   ethcnn_ldp_group.cpp   config #5 offline, group form: K sequences of one geometry through one recurrence launch
+//   ethcnn_ldp_set.cpp  config #5 offline, group and batch form: several sequences through one recurrence launch (the object and
+//                       the run behind ethcnn_ldp_group.cpp and ethcnn_ldp_batch.cpp, which hold the entries and their checks)
 // Mirrors /root/reference/HM-16.5_Test_AI/bin/video_to_cu_depth.py (driver) around net_CNN.py (network).  There is no CPU
 // compute path in this library.
 #pragma once
@@ -327,20 +328,20 @@ HostPool* host_pool(ethcnn_ctx* c);  // the context's fill threads (created on f
 int pinned_pread(int fd, uint8_t* dst, size_t want, off_t off);  // file bytes -> page-locked memory; 0 or ETHCNN_ERR_IO
 
 // ethcnn_ldp.cpp: the residual vectors of nf frames by the throughput stages, over passes of whole frames (the front-end of the
-// offline sequence calls and of ethcnn_ldp_group.cpp)
+// offline sequence calls and of ethcnn_ldp_set.cpp)
 int seq_front(ethcnn_ctx* c, const uint8_t* d_luma, const FrameGeom& g, int nf, float* d_vec);
-// ethcnn_ldp.cpp: recurrence + heads + gates of one chunk of nf frames (the first one carries i_frame i0) of k sequences; member m
-// brings its vectors d_vec[m], bundle image d_lstm[m], QP and probabilities d_probs[m].  sin[m]: the state in front of the first
-// frame (null = zeros); afterwards the state behind the last one, which is in sout[m].  The state is zeroed in front of every frame
-// with i_frame <= 1, so a run of frames that carries its state starts there: one recurrence launch per run, then one gate launch.
+// ethcnn_ldp.cpp: recurrence + heads + gates of one chunk of k sequences (solo: k = 1).  chunk[j] describes sequence j's frames of
+// the chunk as a row of ethcnn_lstm_seq.h does: F frames of vec and probs, the first one numbered i_frame0; state_in: the state in
+// front of it (null = zeros); state_out: where the state behind the last one goes (may be state_in).  The state is zeroed in front of
+// every frame with i_frame <= 1, so a row's run of frames that carries its state starts there: a recurrence launch takes the next
+// run of every row that has frames left (uniform rows from frame 1 on: one launch), then one gate launch takes the chunk.
 // Returns hipGetLastError() behind them: every caller words its own message.
-hipError_t seq_recur(ethcnn_ctx* c, int k, const float* const* d_vec, const float** sin, float* const* sout, const float* const* d_lstm,
-                     const int* qp, float* const* d_probs, int nctu, int nf, int i0);
-// frames per chunk of k sequences: the caller's figure, else what keeps the vectors of all k within 256 MB.  With k = 1 this is
-// the solo formula, 256 MB / (nctu * 448 * 4) and at least one frame: seq_chunk_frames(nctu, nframes, chunk, 1) == min(nframes,
-// chunk > 0 ? chunk : max(1, (256 << 20) / (nctu * kNVec * 4))).
-inline int64_t seq_chunk_frames(int64_t nctu, int64_t nframes, int chunk, int k) {
-    return std::min<int64_t>(nframes, chunk > 0 ? (int64_t)chunk : std::max<int64_t>(1, (int64_t)(256 << 20) / ((int64_t)k * nctu * kNVec * 4)));
+namespace ethcnn { struct SeqBatchRow; }
+hipError_t seq_launch(ethcnn_ctx* c, const SeqBatchRow* chunk, int k);
+// frames per chunk, common to all sequences of a call with sum_nctu CTUs per frame between them: the caller's figure, else what
+// keeps a chunk's vectors within 256 MB, and at least one frame.  A sequence of nframes has min(nframes, this) frames in a chunk.
+inline int64_t seq_chunk_frames(int64_t sum_nctu, int chunk) {
+    return chunk > 0 ? (int64_t)chunk : std::max<int64_t>(1, (int64_t)(256 << 20) / (sum_nctu * kNVec * 4));
 }
 // a device buffer that has to hold `bytes`: nothing to do when *cap suffices; else frees *p and allocates anew.  false, with nothing
 // held, when they do not fit (the caller has summed what must grow, refused with the whole sum and synchronised before)

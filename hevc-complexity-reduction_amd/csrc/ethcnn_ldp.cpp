@@ -330,7 +330,7 @@ extern "C" int ethcnn_ldp_predict_frame(ethcnn_ctx* c, const uint8_t* luma, int 
 extern "C" int64_t ethcnn_ldp_sequence_bytes(int w, int h, int nframes, int chunk_frames) {
     if (w <= 0 || h <= 0 || nframes <= 0 || chunk_frames < 0) return ETHCNN_ERR_ARG;
     const int64_t nctu = (int64_t)((w + 63) / 64) * ((h + 63) / 64), cap = (nctu + 15) / 16 * 16;
-    const int64_t F = seq_chunk_frames(nctu, nframes, chunk_frames, 1);
+    const int64_t F = std::min<int64_t>(nframes, seq_chunk_frames(nctu, chunk_frames));
     // vectors + probabilities of a chunk, the two resident (c, h) buffers; no projection scratch (the recurrence runs the x half itself)
     return F * nctu * kNVec * 4 + F * nctu * kNOut * 4 + 2 * cap * 2 * kNVec * 4;
 }
@@ -404,29 +404,38 @@ int seq_front(ethcnn_ctx* c, const uint8_t* d_luma, const FrameGeom& g, int nf, 
     return ETHCNN_OK;
 }
 
-// recurrence + heads + gates of a chunk for k sequences (ethcnn_ctx.h)
-hipError_t seq_recur(ethcnn_ctx* c, int k, const float* const* d_vec, const float** sin, float* const* sout, const float* const* d_lstm,
-                     const int* qp, float* const* d_probs, int nctu, int nf, int i0) {
-    for (int f = 0; f < nf;) {
-        const int i = i0 + f, run = (i <= 0) ? 1 : nf - f;
-        StageTimer t(c, ETHCNN_STAGE_HEADS, (long)nctu * run * k);
-        SeqMember mem[kLstmSeqGroupMax];
-        for (int m = 0; m < k; ++m) {
-            if (i <= 1) sin[m] = nullptr;
-            mem[m] = {d_vec[m] + (size_t)f * nctu * kNVec, sin[m], sout[m], d_lstm[m], d_probs[m] + (size_t)f * nctu * kNOut, lstm_seq_efs0(qp[m])};
-            sin[m] = sout[m];
+// recurrence + heads + gates of a chunk for k sequences (ethcnn_ctx.h): every row has a frame cursor; its next run is one frame if
+// that frame's number is <= 0 and the rest of its chunk otherwise, with no state in front of a frame numbered <= 1
+hipError_t seq_launch(ethcnn_ctx* c, const SeqBatchRow* chunk, int k) {
+    int at[kLstmSeqBatchMax] = {};
+    for (;;) {
+        SeqBatchRow rows[kLstmSeqBatchMax];
+        int nr = 0;
+        long ctu_frames = 0;
+        for (int j = 0; j < k; ++j) {
+            const SeqBatchRow& q = chunk[j];
+            const int f = at[j];
+            if (f >= q.F) continue;
+            const int i = q.i_frame0 + f, run = (i <= 0) ? 1 : q.F - f;
+            rows[nr++] = {q.vec + (size_t)f * q.n * kNVec, i <= 1 ? nullptr : (f ? q.state_out : q.state_in), q.state_out, q.blob,
+                          q.probs + (size_t)f * q.n * kNOut, q.efs0, q.n, run, i};
+            ctu_frames += (long)q.n * run;
+            at[j] += run;
         }
-        launch_lstm_seq(mem, k, nctu, run, i, c->stream);
-        f += run;
+        if (!nr) break;
+        StageTimer t(c, ETHCNN_STAGE_HEADS, ctu_frames);
+        launch_lstm_seq_batch(rows, nr, c->stream);
     }
-    { StageTimer tg(c, ETHCNN_STAGE_GATE); launch_lstm_seq_gates(d_probs, k, nctu, nf, c->thr1, c->thr2, c->stream); }
+    { StageTimer tg(c, ETHCNN_STAGE_GATE); launch_lstm_seq_gates_batch(chunk, k, c->thr1, c->thr2, c->stream); }
     return hipGetLastError();
 }
 
-// the solo calls: a group of one on the context's bundle and the chunk's vectors in c->seq_vec
-static int seq_recur_solo(ethcnn_ctx* c, int nctu, int nf, int qp, int i0, const float** sin, float* sout, float* d_probs) {
-    const float* const vec = c->seq_vec;
-    const hipError_t e = seq_recur(c, 1, &vec, sin, &sout, &c->d_lstm, &qp, &d_probs, nctu, nf, i0);
+// the solo calls: one row on the context's bundle and the chunk's vectors in c->seq_vec; *sin: the state in front of the chunk,
+// afterwards the one behind it
+static int seq_launch_solo(ethcnn_ctx* c, int nctu, int nf, int qp, int i0, const float** sin, float* sout, float* d_probs) {
+    const SeqBatchRow row = {c->seq_vec, *sin, sout, c->d_lstm, d_probs, lstm_seq_efs0(qp), nctu, nf, i0};
+    const hipError_t e = seq_launch(c, &row, 1);
+    *sin = sout;
     return e == hipSuccess ? ETHCNN_OK : set_err(c, ETHCNN_ERR_DEVICE, "hipGetLastError() failed: %s", hipGetErrorString(e));
 }
 
@@ -443,7 +452,7 @@ extern "C" int ethcnn_ldp_sequence_device(ethcnn_ctx* c, const uint8_t* d_luma, 
     FrameGeom g;
     rc = make_geom(c, w, h, pitch, fstride, &g);
     if (rc) return rc;
-    const int64_t F = seq_chunk_frames(g.nctu, nframes, c->seq_chunk, 1);
+    const int64_t F = std::min<int64_t>(nframes, seq_chunk_frames(g.nctu, c->seq_chunk));
     rc = seq_ensure(c, w, h, nframes, F, false, &in);
     if (rc) return rc;
     const int out = in >= 0 ? in : 0;  // the resident state is advanced in place: a block stores only its own columns (ethcnn_lstm_seq.h)
@@ -452,7 +461,7 @@ extern "C" int ethcnn_ldp_sequence_device(ethcnn_ctx* c, const uint8_t* d_luma, 
     for (int64_t f0 = 0; f0 < nframes; f0 += F) {
         const int nf = (int)std::min<int64_t>(F, nframes - f0);
         rc = seq_front(c, d_luma + f0 * fstride, g, nf, c->seq_vec);
-        if (rc == 0) rc = seq_recur_solo(c, g.nctu, nf, qp, i_first + (int)f0, &sin, c->d_state[out], d_probs + (size_t)f0 * g.nctu * kNOut);
+        if (rc == 0) rc = seq_launch_solo(c, g.nctu, nf, qp, i_first + (int)f0, &sin, c->d_state[out], d_probs + (size_t)f0 * g.nctu * kNOut);
         if (rc) return rc;
     }
     c->state_cur = out;
@@ -474,7 +483,7 @@ static int seq_host_run(ethcnn_ctx* c, const uint8_t* luma, int w, int h, ptrdif
     FrameGeom g;
     rc = make_geom(c, w, h, pitch, fstride, &g);
     if (rc) return rc;
-    const int64_t F = seq_chunk_frames(g.nctu, nframes, c->seq_chunk, 1);
+    const int64_t F = std::min<int64_t>(nframes, seq_chunk_frames(g.nctu, c->seq_chunk));
     rc = seq_ensure(c, w, h, nframes, F, true, &in);
     if (rc) return rc;
     const size_t last = (size_t)(h - 1) * pitch + w;  // the meaningful bytes of the last frame of a piece
@@ -515,7 +524,7 @@ static int seq_host_run(ethcnn_ctx* c, const uint8_t* luma, int w, int h, ptrdif
             SEQCHK(hipEventRecord(c->ev_in[b], c->stream));
             used[b] = true;
         }
-        if (rc == 0) rc = seq_recur_solo(c, g.nctu, nf, qp, i_first + (int)f0, &sin, c->d_state[out], c->seq_probs);
+        if (rc == 0) rc = seq_launch_solo(c, g.nctu, nf, qp, i_first + (int)f0, &sin, c->d_state[out], c->seq_probs);
         if (rc == 0) rc = sink(c->seq_probs, f0, nf, pf);
     }
 #undef SEQCHK

@@ -30,14 +30,15 @@ typedef float f32x4 __attribute__((ext_vector_type(4)));
 // The activation functions are the shared canonical ones (ethcnn_canon_math.h), the level tables (kLstmOff, LstmDims) those of
 // ethcnn_spec.h, as in ethcnn_lstm.hip.
 
-// what the body below works on: one member's row of the launch's table and the launch's scalars
+// what the body below works on: the block's row of the launch's table (SeqBatchRow), copied out of the kernel arguments.  Kept
+// beside the row type because a body that reads the row in place compiles to other device code (another register allocation)
 struct SeqParams {
     const float* vec;       // [F][n][448]
     const float* state_in;  // [n][2][448] or null
     float* state_out;       // [n][2][448]
     const float* blob;      // the LSTM bundle's payload + the packed images behind it
     float* probs;           // [F][n][21], ungated
-    int n, groups, F;
+    int n, F;
     int i_frame0;
     float efs0;             // qp / 51 * 0.18
 };
@@ -244,7 +245,7 @@ struct SeqBatchParams {
     int pre[3][kLstmSeqBatchMax + 1];  // [level 16, 32, 64][row]: blocks of the rows in front of it; [k]: the level's total
     int k;
 };
-static_assert(sizeof(SeqBatchParams) <= 4096, "the table travels in the kernel arguments");
+static_assert(sizeof(SeqBatchRow) == 64 && sizeof(SeqBatchParams) <= 4096, "the table travels in the kernel arguments");
 
 __global__ __launch_bounds__(1024) void k_lstm_seq_batch(SeqBatchParams B) {
     __shared__ f32x4 smem[kSeqWaves * 3 * 64 + ((192 + 5) * 16 + 16) / 4];  // 48 KB of quads + the fc3 operands (12.4 KB at level 16)
@@ -257,16 +258,15 @@ __global__ __launch_bounds__(1024) void k_lstm_seq_batch(SeqBatchParams B) {
     const int blk = r - B.pre[lv][j];
     const SeqBatchRow& R = B.r[j];
     SeqParams P;
-    P.vec = R.m.vec;
-    P.state_in = R.m.state_in;
-    P.state_out = R.m.state_out;
-    P.blob = R.m.blob;
-    P.probs = R.m.probs;
+    P.vec = R.vec;
+    P.state_in = R.state_in;
+    P.state_out = R.state_out;
+    P.blob = R.blob;
+    P.probs = R.probs;
     P.n = R.n;
-    P.groups = (R.n + 15) / 16;
     P.F = R.F;
     P.i_frame0 = R.i_frame0;
-    P.efs0 = R.m.efs0;
+    P.efs0 = R.efs0;
     if (lv == 0) lstm_seq_level<2>(P, blk, smem);
     else if (lv == 1) lstm_seq_level<1>(P, blk, smem);
     else lstm_seq_level<0>(P, blk, smem);
@@ -292,13 +292,6 @@ void launch_lstm_seq_batch(const SeqBatchRow* rows, int k, hipStream_t s) {
     B.k = k;
     const unsigned blocks = (unsigned)(B.pre[0][k] + B.pre[1][k] + B.pre[2][k]);
     hipLaunchKernelGGL(k_lstm_seq_batch, dim3(blocks), dim3(64 * kSeqWaves), 0, s, B);
-}
-
-// the solo and group calls: K rows of one geometry, run of frames and first frame number
-void launch_lstm_seq(const SeqMember* members, int k, int n, int nframes, int i_frame0, hipStream_t s) {
-    SeqBatchRow rows[kLstmSeqGroupMax];
-    for (int m = 0; m < k; ++m) rows[m] = {members[m], n, nframes, i_frame0};
-    launch_lstm_seq_batch(rows, k, s);
 }
 
 // ---- gates: the tf.cond pair of net():305,317 per (frame, mini-batch of 1024 CTUs).  One block owns the mini-batch: it reduces the
@@ -335,21 +328,15 @@ __global__ __launch_bounds__(256) void k_lstm_seq_gates_batch(SeqGateBatch Q, fl
     lstm_seq_gates_body(Q.probs[blockIdx.y], n, chunks, thr1, thr2);
 }
 
-void launch_lstm_seq_gates_batch(float* const* d_probs, const int* n, const int* nframes, int k, float thr1, float thr2, hipStream_t s) {
+void launch_lstm_seq_gates_batch(const SeqBatchRow* rows, int k, float thr1, float thr2, hipStream_t s) {
     SeqGateBatch Q;
     unsigned gx = 1;
     for (int j = 0; j < kLstmSeqBatchMax; ++j) {
-        const int m = j < k ? j : 0;
-        Q.probs[j] = d_probs[m], Q.n[j] = n[m], Q.F[j] = nframes[m];
-        gx = std::max(gx, (unsigned)((n[m] + kSubBatch - 1) / kSubBatch) * (unsigned)nframes[m]);
+        const SeqBatchRow& R = rows[j < k ? j : 0];
+        Q.probs[j] = R.probs, Q.n[j] = R.n, Q.F[j] = R.F;
+        gx = std::max(gx, (unsigned)((R.n + kSubBatch - 1) / kSubBatch) * (unsigned)R.F);
     }
     hipLaunchKernelGGL(k_lstm_seq_gates_batch, dim3(gx, (unsigned)k), dim3(256), 0, s, Q, thr1, thr2);
-}
-
-void launch_lstm_seq_gates(float* const* d_probs, int k, int n, int nframes, float thr1, float thr2, hipStream_t s) {
-    int ns[kLstmSeqGroupMax], fs[kLstmSeqGroupMax];
-    for (int m = 0; m < k; ++m) ns[m] = n, fs[m] = nframes;
-    launch_lstm_seq_gates_batch(d_probs, ns, fs, k, thr1, thr2, s);
 }
 
 }  // namespace ethcnn

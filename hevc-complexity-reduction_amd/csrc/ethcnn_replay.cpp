@@ -3,8 +3,7 @@
 // calibrator and the partition-search simulator.  Kernels: ethcnn_replay.hip.
 #include "ethcnn_analysis.h"
 #include "ethcnn_calib.h"
-#include "ethcnn_ldp_batch.h"
-#include "ethcnn_ldp_group.h"
+#include "ethcnn_ldp_set.h"
 #include "ethcnn_replay.h"
 #include "ethcnn_samples.h"
 
@@ -523,7 +522,7 @@ extern "C" int ethcnn_replay_run_group_device(ethcnn_replay* p, int run, int nsl
     if (int rc = check_run(p, run, 0)) return rc;
     if (!grp || !slots || !d_probs || !d_labels) return rerr(p, ETHCNN_ERR_ARG, "ethcnn_replay_run_group_device: null pointer");
     if (grp->c != p->c) return rerr(p, ETHCNN_ERR_ARG, "the group lives on another context");
-    if (nslots != grp->k) return rerr(p, ETHCNN_ERR_ARG, "%d slots for a group of %d members", nslots, grp->k);
+    if (nslots != grp->nb) return rerr(p, ETHCNN_ERR_ARG, "%d slots for a group of %d members", nslots, grp->nb);
     for (int j = 0; j < nslots; ++j) {
         if (int rc = check_run(p, run, slots[j])) return rc;
         if (!d_probs[j] || !d_labels[j]) return rerr(p, ETHCNN_ERR_ARG, "ethcnn_replay_run_group_device: null output buffer (slot %d)", slots[j]);
@@ -533,7 +532,7 @@ extern "C" int ethcnn_replay_run_group_device(ethcnn_replay* p, int run, int nsl
     const Run& r = p->plan.runs[(size_t)run];
     if (!c->have_weights) return rerr(p, ETHCNN_ERR_NOWEIGHTS, "the context has no residual CNN loaded (ethcnn_load_checkpoint / ethcnn_load_blob)");
     for (int j = 0; j < nslots; ++j)
-        if (!grp->m[j].have)
+        if (!grp->b[j].have)
             return rerr(p, ETHCNN_ERR_NOWEIGHTS, "member %d of the group has no ETH-LSTM bundle loaded for QP %d of slot %d", j, r.qp[slots[j]], slots[j]);
     if (hipSetDevice(c->device) != hipSuccess) return rerr(p, ETHCNN_ERR_DEVICE, "hipSetDevice(%d) failed", c->device);
     if (int rc = ensure_run(p, run, need_of(p, r, false, false, nslots))) return rc;

@@ -2743,16 +2743,18 @@ def _ptr_array(bufs):
     return (ctypes.c_void_p * max(len(vals), 1))(*vals)
 
 
-class LdpGroup(object):
-    """K = 1..8 Low-Delay-P residual sequences of one geometry through one recurrence launch (include/ethcnn.h "config #5 offline,
-    group form"): each member has its own ETH-LSTM bundle, QP, resident state and output, and its result equals
-    EthCnn.ldp_sequence_device on a context that holds its bundle, bit for bit.  The residual CNN and the thresholds are the
-    context's; the context's own LSTM bundle and resident state are not touched."""
+class _LdpSet(object):
+    """what LdpGroup and LdpBatch share: the handle behind ethcnn_<_PREFIX>_*, its bundles (i: a group's member, a batch's bundle
+    index) and its resident states (j: a group's member, a batch's sequence index)"""
+    _PREFIX = None  # "ldp_group" or "ldp_batch"
 
-    def __init__(self, ctx, k):
+    def _fn(self, name):
+        return getattr(self.lib, "ethcnn_%s_%s" % (self._PREFIX, name))
+
+    def __init__(self, ctx, count):
         self.ctx, self.lib = ctx, ctx.lib
         h = ctypes.c_void_p()
-        ctx._chk(self.lib.ethcnn_ldp_group_create(ctx.h, int(k), ctypes.byref(h)))
+        ctx._chk(self._fn("create")(ctx.h, int(count), ctypes.byref(h)))
         self.h = h
         if not hasattr(ctx, "_trainers"):
             ctx._trainers = weakref.WeakSet()
@@ -2760,11 +2762,11 @@ class LdpGroup(object):
 
     def _chk(self, rc):
         if rc:
-            raise EthCnnError(rc, self.lib.ethcnn_ldp_group_last_error(self.h).decode())
+            raise EthCnnError(rc, self._fn("last_error")(self.h).decode())
 
     def close(self):
         if getattr(self, "h", None):
-            self.lib.ethcnn_ldp_group_destroy(self.h)
+            self._fn("destroy")(self.h)
             self.h = None
 
     def __del__(self):
@@ -2779,38 +2781,51 @@ class LdpGroup(object):
     def __exit__(self, *a):
         self.close()
 
-    def __len__(self):
-        return max(0, int(self.lib.ethcnn_ldp_group_count(self.h)))
+    def load_lstm_checkpoint(self, i, prefix):
+        self._chk(self._fn("load_lstm_checkpoint")(self.h, int(i), os.fsencode(prefix)))
 
-    def load_lstm_checkpoint(self, m, prefix):
-        self._chk(self.lib.ethcnn_ldp_group_load_lstm_checkpoint(self.h, int(m), os.fsencode(prefix)))
-
-    def load_lstm_blob(self, m, blob):
+    def load_lstm_blob(self, i, blob):
         blob = np.ascontiguousarray(blob, dtype=np.float32)
-        self._chk(self.lib.ethcnn_ldp_group_load_lstm_blob(self.h, int(m), blob.ctypes.data_as(_fp), blob.size))
+        self._chk(self._fn("load_lstm_blob")(self.h, int(i), blob.ctypes.data_as(_fp), blob.size))
 
-    def load_lstm_synthetic(self, m, seed=1, head_gain=1.0):
-        self._chk(self.lib.ethcnn_ldp_group_load_lstm_synthetic(self.h, int(m), int(seed), float(head_gain)))
+    def load_lstm_synthetic(self, i, seed=1, head_gain=1.0):
+        self._chk(self._fn("load_lstm_synthetic")(self.h, int(i), int(seed), float(head_gain)))
 
-    def get_lstm_blob(self, m):
+    def get_lstm_blob(self, i):
         out = np.empty(LSTM_BLOB_FLOATS, dtype=np.float32)
-        self._chk(self.lib.ethcnn_ldp_group_get_lstm_blob(self.h, int(m), out.ctypes.data_as(_fp), out.size))
+        self._chk(self._fn("get_lstm_blob")(self.h, int(i), out.ctypes.data_as(_fp), out.size))
         return out
 
-    def set_chunk_frames(self, frames):
-        self._chk(self.lib.ethcnn_ldp_group_set_chunk(self.h, int(frames)))
+    def _set_chunk(self, frames):
+        self._chk(self._fn("set_chunk")(self.h, int(frames)))
 
-    def state_ctus(self, m):
-        """the CTU count of member m's resident state (0: none)"""
-        n = int(self.lib.ethcnn_ldp_group_state_ctus(self.h, int(m)))
+    def state_ctus(self, j):
+        """the CTU count of the resident state of member / sequence index j (0: none)"""
+        n = int(self._fn("state_ctus")(self.h, int(j)))
         self._chk(n if n < 0 else 0)
         return n
 
-    def get_state(self, m):
-        """member m's resident (c, h) state -> float32 [nctu, 2, 448]"""
-        state = np.empty((self.state_ctus(m), 2, NVEC), dtype=np.float32)
-        self._chk(self.lib.ethcnn_ldp_group_get_state(self.h, int(m), state.ctypes.data_as(_fp), state.size))
+    def get_state(self, j):
+        """the resident (c, h) state of member / sequence index j -> float32 [nctu, 2, 448]"""
+        state = np.empty((self.state_ctus(j), 2, NVEC), dtype=np.float32)
+        self._chk(self._fn("get_state")(self.h, int(j), state.ctypes.data_as(_fp), state.size))
         return state
+
+
+class LdpGroup(_LdpSet):
+    """K = 1..8 Low-Delay-P residual sequences of one geometry through one recurrence launch (include/ethcnn.h "config #5 offline,
+    group form"): each member has its own ETH-LSTM bundle, QP, resident state and output, and its result equals
+    EthCnn.ldp_sequence_device on a context that holds its bundle, bit for bit.  The residual CNN and the thresholds are the
+    context's; the context's own LSTM bundle and resident state are not touched."""
+    _PREFIX = "ldp_group"
+
+    def __init__(self, ctx, k):
+        _LdpSet.__init__(self, ctx, k)
+
+    def __len__(self):
+        return max(0, int(self.lib.ethcnn_ldp_group_count(self.h)))
+
+    set_chunk_frames = _LdpSet._set_chunk
 
     def sequence_device(self, d_lumas, width, height, nframes, qps, i_frame_first, d_probs, d_state_ins=None, pitch=None, frame_stride=None):
         """asynchronous on the context's stream (ethcnn_ldp_group_sequence_device): one luma buffer, QP and probability buffer per
@@ -2864,75 +2879,21 @@ class LdpBatchSeq(ctypes.Structure):
                 ("bundle", ctypes.c_int), ("d_state_in", ctypes.c_void_p), ("d_probs", ctypes.c_void_p)]
 
 
-class LdpBatch(object):
+class LdpBatch(_LdpSet):
     """Up to 32 Low-Delay-P residual sequences of different geometry, length and first frame number through one recurrence launch
     per chunk (include/ethcnn.h "config #5 offline, batch form").  The object holds nbundles = 1..8 ETH-LSTM bundles; a sequence names
     its bundle by index, and its result equals EthCnn.ldp_sequence_device on a context that holds that bundle, bit for bit.  The
     residual CNN and the thresholds are the context's; the context's own LSTM bundle and resident state are not touched."""
+    _PREFIX = "ldp_batch"
 
     def __init__(self, ctx, nbundles):
-        self.ctx, self.lib = ctx, ctx.lib
-        h = ctypes.c_void_p()
-        ctx._chk(self.lib.ethcnn_ldp_batch_create(ctx.h, int(nbundles), ctypes.byref(h)))
-        self.h = h
-        if not hasattr(ctx, "_trainers"):
-            ctx._trainers = weakref.WeakSet()
-        ctx._trainers.add(self)  # closed with the context, before it
-
-    def _chk(self, rc):
-        if rc:
-            raise EthCnnError(rc, self.lib.ethcnn_ldp_batch_last_error(self.h).decode())
-
-    def close(self):
-        if getattr(self, "h", None):
-            self.lib.ethcnn_ldp_batch_destroy(self.h)
-            self.h = None
-
-    def __del__(self):
-        try:
-            self.close()
-        except Exception:
-            pass
-
-    def __enter__(self):
-        return self
-
-    def __exit__(self, *a):
-        self.close()
+        _LdpSet.__init__(self, ctx, nbundles)
 
     @property
     def nbundles(self):
         return max(0, int(self.lib.ethcnn_ldp_batch_bundles(self.h)))
 
-    def load_lstm_checkpoint(self, bundle, prefix):
-        self._chk(self.lib.ethcnn_ldp_batch_load_lstm_checkpoint(self.h, int(bundle), os.fsencode(prefix)))
-
-    def load_lstm_blob(self, bundle, blob):
-        blob = np.ascontiguousarray(blob, dtype=np.float32)
-        self._chk(self.lib.ethcnn_ldp_batch_load_lstm_blob(self.h, int(bundle), blob.ctypes.data_as(_fp), blob.size))
-
-    def load_lstm_synthetic(self, bundle, seed=1, head_gain=1.0):
-        self._chk(self.lib.ethcnn_ldp_batch_load_lstm_synthetic(self.h, int(bundle), int(seed), float(head_gain)))
-
-    def get_lstm_blob(self, bundle):
-        out = np.empty(LSTM_BLOB_FLOATS, dtype=np.float32)
-        self._chk(self.lib.ethcnn_ldp_batch_get_lstm_blob(self.h, int(bundle), out.ctypes.data_as(_fp), out.size))
-        return out
-
-    def set_chunk(self, frames):
-        self._chk(self.lib.ethcnn_ldp_batch_set_chunk(self.h, int(frames)))
-
-    def state_ctus(self, j):
-        """the CTU count of the resident state of sequence index j (0: none)"""
-        n = int(self.lib.ethcnn_ldp_batch_state_ctus(self.h, int(j)))
-        self._chk(n if n < 0 else 0)
-        return n
-
-    def get_state(self, j):
-        """the resident (c, h) state of sequence index j -> float32 [nctu, 2, 448]"""
-        state = np.empty((self.state_ctus(j), 2, NVEC), dtype=np.float32)
-        self._chk(self.lib.ethcnn_ldp_batch_get_state(self.h, int(j), state.ctypes.data_as(_fp), state.size))
-        return state
+    set_chunk = _LdpSet._set_chunk
 
     def run_device(self, seqs):
         """asynchronous on the context's stream (ethcnn_ldp_batch_run_device).  seqs: one dict per sequence with d_luma, width, height,

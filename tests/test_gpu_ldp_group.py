@@ -226,6 +226,30 @@ def test_states_given_resident_continued_and_chunked(pkg, ctx):
             _same(g.get_state(m), whole[m][1], "member %d: state, chunk 2" % m)
 
 
+def test_a_chunked_group_from_frame_zero_and_its_continuation(pkg, ctx):
+    """K = 3 from i_frame_first 0, four frames in chunks of 3: the recurrence launches fall at frame 0 (a run of its own), at frame 1
+    (the state zeroed again) and at the chunk boundary (frame 3, from the resident state).  200x136: 12 CTUs, one ragged column
+    group; then, in the same group (its state buffers grow), 1088x64: 17 CTUs, two column groups with the second ragged.  Then the
+    group goes on at frame 4 from its resident states.  The reference is the solo call per member: of the first four frames for
+    the first call, frames 4 onward of a run of six for the second."""
+    bundles = BUNDLES[:3]
+    qps = [b[2] for b in bundles]
+    with _group(pkg, ctx, bundles) as g:
+        g.set_chunk_frames(3)
+        for w, h in ((200, 136), (1088, 64)):
+            lums = [_frames(1200 + 10 * w + m, w, h, 6) for m in range(3)]
+            head = [_solo(ctx, b, lums[m][:4], w, h, 0) for m, b in enumerate(bundles)]
+            whole = [_solo(ctx, b, lums[m], w, h, 0) for m, b in enumerate(bundles)]
+            got = g.sequence([a[:4] for a in lums], w, h, qps, i_frame_first=0)
+            for m in range(3):
+                _same(got[m], head[m][0], "%dx%d, member %d: frames 0..3" % (w, h, m))
+                _same(g.get_state(m), head[m][1], "%dx%d, member %d: state behind frame 3" % (w, h, m))
+            got = g.sequence([a[4:] for a in lums], w, h, qps, i_frame_first=4)
+            for m in range(3):
+                _same(got[m], whole[m][0][4:], "%dx%d, member %d: frames 4..5 from the resident state" % (w, h, m))
+                _same(g.get_state(m), whole[m][1], "%dx%d, member %d: state behind frame 5" % (w, h, m))
+
+
 def test_the_context_keeps_its_bundle_and_state(pkg, ctx):
     w, h = 200, 136
     own = BUNDLES[7]
