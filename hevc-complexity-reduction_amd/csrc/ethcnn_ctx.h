@@ -7,6 +7,8 @@
 //   ethcnn_ldp.cpp      config #5: resi vectors, ETH-LSTM step, the per-frame LDP calls, the offline whole-sequence calls
 //   ethcnn_ldp_set.cpp  config #5 offline, group and batch form: several sequences through one recurrence launch (the object and
 //                       the run behind ethcnn_ldp_group.cpp and ethcnn_ldp_batch.cpp, which hold the entries and their checks)
+//   ethcnn_ldp_sessions.cpp  config #5 online, several live encoders: sessions with a resident state each, one shared front-end
+//                       (ethcnn_tile_table.hip) and one recurrence launch per step; ethcnn_ldp_sessions_plan.cpp: its host-only entries
 // Mirrors /root/reference/HM-16.5_Test_AI/bin/video_to_cu_depth.py (driver) around net_CNN.py (network).  There is no CPU
 // compute path in this library.
 #pragma once

@@ -35,6 +35,23 @@ struct FrameGeom {
 // CTU rows hold wait_seq (ethcnn_tile.hip, TileWait); *gave_up = wait_seq if a block waited ~1 s in vain
 void launch_tile(const uint8_t* d_luma, const FrameGeom& g, long ctu0, int n, const Workspace& ws, int n_flags,
                  hipStream_t s, int max_blocks = 0, const unsigned* wait_rows = nullptr, unsigned wait_seq = 0, unsigned* gave_up = nullptr);
+// k0 over a table of pictures (ethcnn_tile_table.hip): segment j is ONE picture region of n_total CTUs that owns the global 16-CTU groups
+// [first_group, first_group + ceil(n_total / 16)), so every segment starts on a group boundary; the rows of a short last group are
+// padding (zero pixel records).  fast: launch_tile's rule for the 16-byte load form, per segment.
+constexpr int kTileTableMax = 32;
+struct TileSeg {
+    const uint8_t* luma;
+    int width, height;
+    long pitch, frame_stride;
+    int cw, nctu, n_total, first_group, fast;
+};
+struct TileTable {
+    TileSeg seg[kTileTableMax];  // in rising first_group
+    int nseg;
+};
+TileSeg tile_seg(const uint8_t* d_luma, const FrameGeom& g, int n_total, int first_group);
+// the global groups [group0, group0 + ngroups) -> the records of groups 0.. of ws.xs / xm / xl (ngroups * 16 <= ws.cap)
+void launch_tile_table(const TileTable& t, int group0, int ngroups, const Workspace& ws, hipStream_t s);
 // k1: xs/xm/xl -> feat (fc1_plan 2: -> featb, every feature as two fp16 pieces in the 16-bit MFMA's operand order)
 void launch_trunk(const Workspace& ws, const DeviceWeights& w, int n, bool resi, hipStream_t s, int fc1_plan = 0);
 // k1, plan 3 (ethcnn_trunk_fast.hip): the same trunk with its convolutions on the 16-bit matrix pipe (fp16 x 2 splits) -> featb in plan 2's form

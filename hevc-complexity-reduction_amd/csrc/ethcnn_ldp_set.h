@@ -4,7 +4,8 @@
 // recurrence and gate launches of a chunk for all sequences that still have frames (seq_launch, ethcnn_ctx.h).  A group is a batch
 // of K rows of one geometry, length and first frame number in which sequence m uses bundle m.  Bundles are held apart from the
 // sequences: several sequences of one QP band name the same image.  The context's own bundle, resident state and sequence buffers
-// are neither used nor changed.
+// are neither used nor changed.  ethcnn_ldp_sessions (ethcnn_ldp_sessions.cpp, the online form) is a set as well: its state indices are
+// session ids, and it has a run of its own (one frame per session through a shared front-end).
 #pragma once
 #include "ethcnn_ctx.h"
 #include "ethcnn_lstm_seq.h"

@@ -133,6 +133,22 @@ SIGNATURES = {
     "ethcnn_ldp_batch_set_chunk": (_i, [_vp, _i]),
     "ethcnn_ldp_batch_bytes": (ctypes.c_int64, [ctypes.POINTER(_i), ctypes.POINTER(_i), ctypes.POINTER(_i), _i, _i]),
     "ethcnn_ldp_batch_plan": (_i, [ctypes.POINTER(_i), ctypes.POINTER(_i), _i, _i, ctypes.POINTER(_i), ctypes.POINTER(_i), ctypes.POINTER(_i), _i]),
+    "ethcnn_ldp_sessions_create": (_i, [_vp, _i, ctypes.POINTER(_vp)]),
+    "ethcnn_ldp_sessions_destroy": (None, [_vp]),
+    "ethcnn_ldp_sessions_last_error": (_cp, [_vp]),
+    "ethcnn_ldp_sessions_bundles": (_i, [_vp]),
+    "ethcnn_ldp_sessions_load_lstm_checkpoint": (_i, [_vp, _i, _cp]),
+    "ethcnn_ldp_sessions_load_lstm_blob": (_i, [_vp, _i, _fp, _sz]),
+    "ethcnn_ldp_sessions_load_lstm_synthetic": (_i, [_vp, _i, ctypes.c_uint64, ctypes.c_double]),
+    "ethcnn_ldp_sessions_get_lstm_blob": (_i, [_vp, _i, _fp, _sz]),
+    "ethcnn_ldp_sessions_open": (_i, [_vp, _i, _i, ctypes.POINTER(_i)]),
+    "ethcnn_ldp_sessions_close": (_i, [_vp, _i]),
+    "ethcnn_ldp_sessions_step_device": (_i, [_vp, _vp, _i]),
+    "ethcnn_ldp_sessions_step": (_i, [_vp, _vp, _i]),
+    "ethcnn_ldp_sessions_get_state": (_i, [_vp, _i, _fp, _sz]),
+    "ethcnn_ldp_sessions_state_ctus": (ctypes.c_int64, [_vp, _i]),
+    "ethcnn_ldp_sessions_bytes": (ctypes.c_int64, [ctypes.POINTER(_i), ctypes.POINTER(_i), _i]),
+    "ethcnn_ldp_sessions_plan": (_i, [ctypes.POINTER(_i), _i, _i, ctypes.POINTER(_i), ctypes.POINTER(_i), ctypes.POINTER(_i), _i]),
     "ethcnn_ldp_step_begin": (_i, [_vp, _vp, _i, _i, _pd, _i, _i, _vp, _fp]),
     "ethcnn_rows_ready": (_i, [_vp, _i, _i]),
     "ethcnn_predict_luma_begin": (_i, [_vp, _vp, _i, _i, _i, _fp]),
@@ -493,6 +509,31 @@ def ldp_batch_plan(nctus, nframes, chunk_frames=0):
         raise EthCnnError(rc, "ethcnn_ldp_batch_plan: bad arguments")
     return {"chunk_frames": fc.value,
             "chunks": [{"members": rows[4 * t], "blocks": (rows[4 * t + 1], rows[4 * t + 2], rows[4 * t + 3])} for t in range(nchunks.value)]}
+
+
+def ldp_sessions_bytes(widths, heights):
+    """device bytes the sessions of these picture sizes hold when they step together (ethcnn_ldp_sessions_bytes; host only), the bundle
+    images apart; negative for bad arguments"""
+    if len(widths) != len(heights):
+        raise ValueError("ldp_sessions_bytes takes one width and one height per session")
+    return int(load_library().ethcnn_ldp_sessions_bytes(_int_array(widths), _int_array(heights), len(widths)))
+
+
+def ldp_sessions_plan(nctus, max_ctus_per_pass=0):
+    """the layout of an LdpSessions step over pictures of these CTU counts, in this order (ethcnn_ldp_sessions_plan; host only) ->
+    {"first_group": [...], "pass_groups": [...]}: picture j owns the 16-CTU groups from first_group[j] on, pass p holds pass_groups[p]
+    groups; raises EthCnnError for bad arguments"""
+    lib = load_library()
+    first, npasses = (ctypes.c_int * max(len(nctus), 1))(), ctypes.c_int(0)
+    args = (_int_array(nctus), len(nctus), int(max_ctus_per_pass), first, ctypes.byref(npasses))
+    rc = lib.ethcnn_ldp_sessions_plan(*args, None, 0)
+    if rc:
+        raise EthCnnError(rc, "ethcnn_ldp_sessions_plan: bad arguments")
+    passes = (ctypes.c_int * max(npasses.value, 1))()
+    rc = lib.ethcnn_ldp_sessions_plan(*args, passes, npasses.value)
+    if rc:
+        raise EthCnnError(rc, "ethcnn_ldp_sessions_plan: bad arguments")
+    return {"first_group": [first[j] for j in range(len(nctus))], "pass_groups": [passes[p] for p in range(npasses.value)]}
 
 
 def ldp_group_bytes(width, height, nframes, chunk_frames=0, k=1):
@@ -947,6 +988,14 @@ class EthCnn(object):
         self._pinned = getattr(self, "_pinned", [])
         self._pinned.append(p.value)
         return arr[:nbytes]
+
+    def free_host_buffer(self, arr):
+        """frees one host_buffer() (the array it returned, or a view that starts at its first byte)"""
+        ptr = arr.ctypes.data
+        if ptr not in getattr(self, "_pinned", []):
+            raise ValueError("not a host_buffer() of this context")
+        self.lib.ethcnn_host_free(self.h, ptr)
+        self._pinned.remove(ptr)
 
     def free_host_buffers(self):
         for ptr in getattr(self, "_pinned", []):
@@ -2935,6 +2984,89 @@ class LdpBatch(_LdpSet):
             self.ctx.synchronize()
             for b in bufs:
                 b.free()
+
+
+# ------------------------------------------------------------------------------- config #5 online, several live encoders ---
+class LdpSessionFrame(ctypes.Structure):
+    """ethcnn_ldp_session_frame"""
+    _fields_ = [("session", ctypes.c_int), ("luma", ctypes.c_void_p), ("pitch", ctypes.c_ssize_t), ("qp", ctypes.c_int), ("i_frame", ctypes.c_int),
+                ("bundle", ctypes.c_int), ("state_in", ctypes.c_void_p), ("probs", ctypes.c_void_p)]
+
+
+class LdpSessions(_LdpSet):
+    """Up to 32 live Low-Delay-P encoders on one context (include/ethcnn.h "config #5 online, several live encoders"): a session has a
+    picture size and a resident recurrent state, a step advances any subset of the sessions by one frame through one shared front-end
+    and one recurrence launch.  The object holds nbundles = 1..8 ETH-LSTM bundles; a frame names its bundle by index, and its result
+    equals EthCnn.ldp_step on a context of its own that holds that bundle, bit for bit.  The residual CNN and the thresholds are the
+    context's; the context's own LSTM bundle and resident state are not touched."""
+    _PREFIX = "ldp_sessions"
+
+    def __init__(self, ctx, nbundles):
+        _LdpSet.__init__(self, ctx, nbundles)
+        self._size = {}  # session id -> (width, height)
+
+    @property
+    def nbundles(self):
+        return max(0, int(self.lib.ethcnn_ldp_sessions_bundles(self.h)))
+
+    def open(self, width, height):
+        """-> the id of a new session for width x height pictures (ids are reused after close)"""
+        sid = ctypes.c_int(-1)
+        self._chk(self.lib.ethcnn_ldp_sessions_open(self.h, int(width), int(height), ctypes.byref(sid)))
+        self._size[sid.value] = (int(width), int(height))
+        return sid.value
+
+    def close_session(self, session):
+        self._chk(self.lib.ethcnn_ldp_sessions_close(self.h, int(session)))
+        self._size.pop(int(session), None)
+
+    def close(self, session=None):
+        """close(session): forget that session; close(): destroy the object (as the other handles' close does)"""
+        if session is None:
+            _LdpSet.close(self)
+        else:
+            self.close_session(session)
+
+    def step_device(self, frames):
+        """asynchronous on the context's stream (ethcnn_ldp_sessions_step_device).  frames: one dict per frame with session, d_luma, qp,
+        i_frame, d_probs (DeviceBuffers or raw device addresses) and optionally bundle (0), d_state_in (None), pitch (the width)"""
+        ptr = lambda b: None if b is None else getattr(b, "ptr", b)
+        arr = (LdpSessionFrame * max(len(frames), 1))()
+        for j, f in enumerate(frames[:len(arr)]):
+            pitch = f.get("pitch") or self._size.get(int(f["session"]), (0, 0))[0]
+            arr[j] = LdpSessionFrame(int(f["session"]), ptr(f["d_luma"]), int(pitch), int(f["qp"]), int(f["i_frame"]), int(f.get("bundle", 0)),
+                                     ptr(f.get("d_state_in")), ptr(f["d_probs"]))
+        self._chk(self.lib.ethcnn_ldp_sessions_step_device(self.h, arr, len(frames)))
+
+    def step(self, frames):
+        """synchronous, host memory (ethcnn_ldp_sessions_step).  frames: one dict per frame with session, luma (uint8 [height, width], or
+        [height, pitch] with pitch given), qp, i_frame and optionally bundle (0), state_in (float32 [nctu, 2, 448]), probs_out (a
+        float32 array of nctu x 21 to write into) -> a list of probs [nctu, 21]"""
+        arr = (LdpSessionFrame * max(len(frames), 1))()
+        keep, outs = [], []
+        for j, f in enumerate(frames[:len(arr)]):
+            w, h = self._size.get(int(f["session"]), (0, 0))
+            n = ctus_per_frame(w, h) if w else 0
+            luma = np.ascontiguousarray(f["luma"], dtype=np.uint8)
+            pitch = int(f.get("pitch") or w)
+            if w and luma.size < (h - 1) * pitch + w:
+                raise ValueError("frame %d: the luma buffer is smaller than a %dx%d picture at pitch %d" % (j, w, h, pitch))
+            sin = f.get("state_in")
+            if sin is not None:
+                sin = np.ascontiguousarray(sin, dtype=np.float32)
+                if sin.size != n * 2 * NVEC:
+                    raise ValueError("frame %d: state_in must hold %d floats" % (j, n * 2 * NVEC))
+            out = f.get("probs_out")
+            if out is None:
+                out = np.empty((n, NOUT), dtype=np.float32)
+            elif out.dtype != np.float32 or not out.flags["C_CONTIGUOUS"] or out.size != n * NOUT:
+                raise ValueError("frame %d: probs_out must be a contiguous float32 array of %d values" % (j, n * NOUT))
+            keep.append((luma, sin))
+            outs.append(out)
+            arr[j] = LdpSessionFrame(int(f["session"]), luma.ctypes.data, pitch, int(f["qp"]), int(f["i_frame"]), int(f.get("bundle", 0)),
+                                     None if sin is None else sin.ctypes.data, out.ctypes.data)
+        self._chk(self.lib.ethcnn_ldp_sessions_step(self.h, arr, len(frames)))
+        return [o.reshape(-1, NOUT) for o in outs]
 
 
 # ------------------------------------------------------------------------------------------------------ sample-set replay ---

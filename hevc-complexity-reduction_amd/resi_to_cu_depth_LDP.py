@@ -168,26 +168,36 @@ def _write_atomic(path, arr):
     os.rename(tmp, path)
 
 
-def save_cu_depth_and_state(depth_out, state_out, save_file, state_file, end_file, num_vectors, tag=None):
-    """:131-145 writes state.dat, cu_depth.dat, then the (empty) ending signal.  Here cu_depth.dat and the ending
-    signal come FIRST (they are what HM waits for) and state.dat is refreshed afterwards, while HM is already
-    encoding: `state_out` may be a callable that fetches the state from the GPU at that point.  Returns the state."""
+def save_cu_depth(depth_out, save_file, state_file, end_file, num_vectors, tag=None):
+    """The half of save_cu_depth_and_state that the encoder waits for: the "pending" sidecar (tag = (i_frame, w, h)), cu_depth.dat, the
+    ending signal.  Returns the other half as a function of the state: state.dat, then the sidecar in its final form."""
     assert depth_out.size == num_vectors * (1 + 4 + 16)
 
-    def sidecar(text):  # tag = (i_frame, w, h)
+    def sidecar(text):
         tmp = '%s%s.tmp.%d' % (state_file, STATE_INDEX_SUFFIX, os.getpid())
         with open(tmp, 'w') as f:
             f.write(text + '\n')
         os.rename(tmp, state_file + STATE_INDEX_SUFFIX)
+
+    def finish(state_out):
+        _write_atomic(state_file, state_out)
+        if tag is not None:
+            sidecar('%d %d %d' % tuple(tag))
     if tag is not None:
-        sidecar('pending %d %d %d' % tuple(tag))  # from here until the state write below, state.dat is an earlier frame's
+        sidecar('pending %d %d %d' % tuple(tag))  # from here until finish(), state.dat is an earlier frame's
     _write_atomic(save_file, depth_out)
     open(end_file, 'wb').close()
+    return finish
+
+
+def save_cu_depth_and_state(depth_out, state_out, save_file, state_file, end_file, num_vectors, tag=None):
+    """:131-145 writes state.dat, cu_depth.dat, then the (empty) ending signal.  Here cu_depth.dat and the ending
+    signal come FIRST (they are what HM waits for) and state.dat is refreshed afterwards, while HM is already
+    encoding: `state_out` may be a callable that fetches the state from the GPU at that point.  Returns the state."""
+    finish = save_cu_depth(depth_out, save_file, state_file, end_file, num_vectors, tag)
     if callable(state_out):
         state_out = state_out()
-    _write_atomic(state_file, state_out)
-    if tag is not None:
-        sidecar('%d %d %d' % tuple(tag))
+    finish(state_out)
     return state_out
 
 
@@ -302,23 +312,197 @@ def serve(workdir='.', max_frames=None, idle_timeout=None, poll_s=2e-4, device=0
         ctx.close()
 
 
+MAX_SESSIONS = 32   # ethcnn_ldp_sessions: sessions open at once
+MAX_BUNDLES = 8     # ... and its bundle places
+
+
+def check_sessions(workdirs):
+    """What `--sessions` refuses at start-up, as ValueError, before a GPU is touched and with nothing written -> the gate thresholds
+    all directories share.  The gates are the context's: every Thr_info.txt must give the first directory's gate tokens [1] and [3]."""
+    budget = sorted(k for k in os.environ if k.startswith('ETHCNN_SEARCH_BUDGET'))
+    if budget:
+        raise ValueError('--sessions does not pace: %s is set, and the search budget is held per sequence (one daemon per encoder does that)'
+                         % ', '.join(budget))
+    if not workdirs:
+        raise ValueError('--sessions needs at least one directory')
+    if len(workdirs) > MAX_SESSIONS:
+        raise ValueError('--sessions: %d directories, one server holds at most %d sessions' % (len(workdirs), MAX_SESSIONS))
+    seen = {}
+    for d in workdirs:
+        real = os.path.realpath(d)
+        if real in seen:
+            raise ValueError('--sessions: %s is listed twice (as %s and %s)' % (real, seen[real], d))
+        seen[real] = d
+    gates = None
+    for d in workdirs:
+        path = os.path.join(d, THR_FILE)
+        try:
+            g = _e.parse_thresholds(path)
+        except _e.EthCnnError:
+            raise ValueError('--sessions: cannot read the thresholds of %s' % path)
+        if gates is None:
+            gates = g
+        elif g != gates:
+            raise ValueError('--sessions: the gate thresholds of %s (%g %g) differ from those of %s (%g %g); one server has one pair of gates'
+                             % (path, g[0], g[1], os.path.join(workdirs[0], THR_FILE), gates[0], gates[1]))
+    return gates
+
+
+class _BundlePlace(object):
+    """bundle i of an LdpSessions object behind the two loaders restore_lstm calls"""
+
+    def __init__(self, sessions, i):
+        self.sessions, self.i = sessions, i
+
+    def load_lstm_checkpoint(self, prefix):
+        self.sessions.load_lstm_checkpoint(self.i, prefix)
+
+    def load_lstm_synthetic(self, seed, head_gain):
+        self.sessions.load_lstm_synthetic(self.i, seed, head_gain)
+
+
+class _Dir(object):
+    """one working directory of serve_many: its session, its page-locked buffers and what serve keeps per daemon"""
+
+    def __init__(self, workdir):
+        self.workdir = workdir
+        self.session, self.geom = None, None
+        self.last_key, self.state_sig = None, None
+        self.pinned, self.pinned_probs = None, None
+
+    def p(self, name):
+        return os.path.join(self.workdir, name)
+
+
+def _host_buffer_again(ctx, old, nbytes):
+    """a page-locked buffer of nbytes in place of `old` (None: a first one)"""
+    if old is not None:
+        ctx.free_host_buffer(old)
+    return ctx.host_buffer(nbytes)
+
+
+def serve_many(workdirs, max_frames=None, idle_timeout=None, poll_s=2e-4, device=0, verbose=True, accept_stale=False):
+    """One server for several HM working directories: one context, one LdpSessions object, the unchanged file handshake per directory.
+    A poll round takes every directory with pred_start.sig and a complete command.dat, reads their resi.yuv, advances all of them
+    in ONE step, writes cu_depth.dat and pred_end.sig per directory and then refreshes every served state.dat and its sidecar.  State
+    continuity per directory is serve's rule.  max_frames and idle_timeout count over all directories.  Returns the frames predicted."""
+    check_sessions(workdirs)
+    dirs = [_Dir(d) for d in workdirs]
+    ctx = _e.EthCnn(device=device)
+    sessions = None
+    try:
+        ctx.load_thresholds(dirs[0].p(THR_FILE))   # (the gates check_sessions compared)
+        restore_cnn(ctx, workdirs[0])
+        sessions = _e.LdpSessions(ctx, MAX_BUNDLES)
+        bundles = {}  # model name of a QP band -> bundle index
+        if verbose:
+            print('Python: predictor initialized on %s for %d directories.' % (ctx.device_name, len(dirs)))
+        n_frame_total = 0
+        idle_since = time.time()
+        while max_frames is None or n_frame_total < max_frames:
+            ready = []
+            for d in dirs:
+                if max_frames is not None and n_frame_total + len(ready) >= max_frames:
+                    break
+                if not os.path.isfile(d.p(START_FILE)):
+                    continue
+                cmd = get_command(d.p(COMMAND_FILE))
+                if cmd[0] >= 0:
+                    ready.append((d, cmd))
+            if not ready:
+                if idle_timeout is not None and time.time() - idle_since > idle_timeout:
+                    break
+                time.sleep(poll_s)
+                continue
+            frames = []
+            for d, (i_frame, w, h, qp) in ready:
+                os.remove(d.p(START_FILE))
+                name = _e.lstm_model_name_for_qp(qp)
+                if name not in bundles:
+                    if len(bundles) == MAX_BUNDLES:
+                        raise IOError('--sessions: more than %d QP bands in use' % MAX_BUNDLES)
+                    loaded = restore_lstm(_BundlePlace(sessions, len(bundles)), qp, d.workdir)
+                    bundles[name] = len(bundles)
+                    if verbose:
+                        print('LSTM model loaded for QP %d (%s).' % (qp, loaded))
+                if d.geom != (w, h):  # a new sequence in this directory: a new session
+                    if d.session is not None:
+                        sessions.close(d.session)
+                    d.session, d.geom, d.last_key = sessions.open(w, h), (w, h), None
+                num_vectors = _e.ctus_per_frame(w, h)
+                if d.pinned is None or d.pinned.size < w * h:
+                    d.pinned = _host_buffer_again(ctx, d.pinned, w * h)
+                if d.pinned_probs is None or d.pinned_probs.size < num_vectors * 21:
+                    d.pinned_probs = _host_buffer_again(ctx, d.pinned_probs, num_vectors * 21 * 4).view(np.float32)
+                luma, _ = get_images_from_one_file(d.p(YUV_FILE), w, h, IMAGE_SIZE, into=d.pinned)
+                resident = i_frame > 1 and d.last_key == (w, h, i_frame - 1) and d.state_sig == _file_sig(d.p(STATE_FILE))
+                try:
+                    state_in = None if (resident or i_frame <= 1) else get_state_in_from_one_file(d.p(STATE_FILE), num_vectors, i_frame, (w, h))
+                except StaleStateError as exc:
+                    sys.stderr.write('resi_to_cu_depth_LDP: %s\n' % exc)
+                    if not accept_stale:
+                        raise
+                    os.remove(d.p(STATE_FILE) + STATE_INDEX_SUFFIX)
+                    state_in = get_state_in_from_one_file(d.p(STATE_FILE), num_vectors, i_frame, (w, h))
+                if state_in is not None:
+                    state_in = np.asarray(state_in, dtype=np.float32).reshape(num_vectors, 2, VECTOR_LENGTH)
+                frames.append({'session': d.session, 'luma': luma, 'qp': qp, 'i_frame': i_frame, 'bundle': bundles[name], 'state_in': state_in,
+                               'probs_out': d.pinned_probs[:num_vectors * 21]})
+            depths = sessions.step(frames)
+            # what the encoders wait for first, for every directory; the state files afterwards, while they are encoding
+            late = [save_cu_depth(depth, d.p(SAVE_FILE), d.p(STATE_FILE), d.p(END_FILE), _e.ctus_per_frame(w, h), (i_frame, w, h))
+                    for depth, (d, (i_frame, w, h, qp)) in zip(depths, ready)]
+            for finish, (d, (i_frame, w, h, qp)) in zip(late, ready):
+                finish(sessions.get_state(d.session).reshape(-1, LSTM_DEPTH, 2, VECTOR_LENGTH))
+                d.last_key, d.state_sig = (w, h, i_frame), _file_sig(d.p(STATE_FILE))
+            n_frame_total += len(ready)
+            idle_since = time.time()
+            if verbose:
+                print('%d frames predicted (%d in this step).' % (n_frame_total, len(ready)))
+        return n_frame_total
+    finally:
+        if sessions is not None:
+            sessions.close()
+        ctx.close()
+
+
+USAGE = ('usage: resi_to_cu_depth_LDP.py [--max-frames N] [--idle-timeout S] [--accept-stale]\n'
+         '       resi_to_cu_depth_LDP.py --sessions DIR [DIR ...] [--max-frames N] [--idle-timeout S] [--accept-stale]\n')
+
+
 def main(argv):
     """`python resi_to_cu_depth_LDP.py` in HM-LDP's bin/ (no arguments, like the reference);
-    optional: --max-frames N, --idle-timeout SECONDS."""
+    optional: --max-frames N, --idle-timeout SECONDS; --sessions DIR [DIR ...]: one server for several working directories."""
     max_frames = idle = None
     accept_stale = False
+    workdirs = None
     args = list(argv[1:])
     while args:
         a = args.pop(0)
-        if a == '--max-frames':
+        if a == '--max-frames' and args:
             max_frames = int(args.pop(0))
-        elif a == '--idle-timeout':
+        elif a == '--idle-timeout' and args:
             idle = float(args.pop(0))
         elif a == '--accept-stale':
             accept_stale = True
+        elif a == '--sessions' and workdirs is None:
+            workdirs = []
+            while args and not args[0].startswith('--'):
+                workdirs.append(args.pop(0))
         else:
-            sys.stderr.write('usage: resi_to_cu_depth_LDP.py [--max-frames N] [--idle-timeout S] [--accept-stale]\n')
+            sys.stderr.write(USAGE)
             return 2
+    if workdirs is not None:
+        try:
+            check_sessions(workdirs)
+        except ValueError as err:
+            sys.stderr.write('resi_to_cu_depth_LDP: %s\n' % err)
+            return 1
+        try:
+            serve_many(workdirs, max_frames=max_frames, idle_timeout=idle, accept_stale=accept_stale)
+        except StaleStateError:
+            return 1
+        return 0
     try:  # a bad ETHCNN_SEARCH_BUDGET* value, or a Thr_info.txt that is not the companion line: refused before a GPU is touched
         if _sb.from_env() is not None:
             _sb.ladder_from_env('ldp', auto=NO_AUTO_LADDER)

@@ -415,6 +415,74 @@ int ethcnn_ldp_batch_set_chunk(ethcnn_ldp_batch* b, int frames);
 int64_t ethcnn_ldp_batch_bytes(const int* widths, const int* heights, const int* nframes, int nseqs, int chunk_frames);
 int ethcnn_ldp_batch_plan(const int* nctus, const int* nframes, int nseqs, int chunk_frames, int* fc_out, int* nchunks_out,
                           int* chunks_out /* [max_chunks][4] */, int max_chunks);
+/* ---- config #5 online, several live encoders: up to 32 SESSIONS on one context, each with a picture size and a resident recurrent state of
+ *      its own; one call advances any subset of them by one frame.  The object holds up to 8 ETH-LSTM bundles, named by index per frame.
+ *      DEFINITION: for every frame of a call, probs and the session's resident state EQUAL what ethcnn_ldp_step gives on a context of its
+ *      own that holds the same CNN, the same thresholds and that bundle, bit for bit, gates and their zero patterns (per 1024-CTU
+ *      mini-batch of that session's own picture) included.  State rules of ethcnn_ldp_step: state_in is used when given, at ANY frame
+ *      number (i_frame <= 1 included: the frame number then only carries the phase); without it a frame with i_frame <= 1 starts from
+ *      zeros and a later one from the session's resident state (none resident: ETHCNN_ERR_ARG, in the wording of ethcnn_ldp_step).  Sessions that are not in a call keep their state.  The residual CNN, the thresholds and the stream
+ *      are the context's; the context's own LSTM bundle and resident LDP state are neither used nor changed.
+ *      What differs is the schedule: the CTU-load stage runs ONCE over a table of the call's pictures, in which picture j owns the 16-CTU
+ *      groups [first_group_j, first_group_j + ceil(nctu_j / 16)) (rows of a short last group are padding that nothing reads), then trunk
+ *      and FC1 run once over all groups -- cut at group boundaries into passes of at most the context's max_ctus_per_pass rows --, then
+ *      ONE recurrence launch and ONE gate launch serve all frames of the call.
+ *   ethcnn_ldp_sessions_create    nbundles bundle places on ctx (ETHCNN_ERR_ARG outside 1..8; text: ethcnn_last_error of the context).
+ *                                 Destroy the object before its context.  Errors of every other entry: ethcnn_ldp_sessions_last_error.
+ *   ethcnn_ldp_sessions_load_lstm_checkpoint / _load_lstm_blob / _load_lstm_synthetic / _get_lstm_blob   bundle i, as the batch's
+ *   ethcnn_ldp_sessions_open      a session for width x height pictures; *session: its id, the lowest free one of 0..31 (ids are reused
+ *                                 after ethcnn_ldp_sessions_close).  Allocates the session's state, roundup16(nctu) x 3584 bytes; may wait
+ *                                 for the stream.  A 33rd open session is ETHCNN_ERR_ARG.
+ *   ethcnn_ldp_sessions_close     forgets the session and its state.  Waits for nothing: work already enqueued for it completes.
+ *   ethcnn_ldp_sessions_step_device   n = 1..32 frames, each of another session.  Device pointers, asynchronous on the context's stream.
+ *                                 Refused before anything is allocated or enqueued, every state left as it was: an open streamed call,
+ *                                 no CNN weights, a bundle index that is out of range or empty (ETHCNN_ERR_NOWEIGHTS), a session that is
+ *                                 not open or named twice, n outside 1..32, a null pointer, a pitch below the width, a state_in that is not
+ *                                 16-byte aligned or a probs that is not 4-byte aligned, a probs that overlaps another frame's probs or
+ *                                 any frame's state_in or picture, its own included (ETHCNN_ERR_ARG; the text names the frame).  luma and
+ *                                 pitch need no alignment.  A call whose vectors do not fit fails with ETHCNN_ERR_NOMEM, states kept.  A
+ *                                 failure after that point drops the states of the sessions in the call, and of no other.
+ *   ethcnn_ldp_sessions_step      the same with HOST pointers (no alignment asked), synchronous: pictures and states are copied to the
+ *                                 device, the probabilities back.  Every refusal above, ETHCNN_ERR_NOMEM included, comes before a
+ *                                 caller's state is copied into the session's buffer.
+ *   ethcnn_ldp_sessions_get_state the resident state of a session, float32 [nctu][2][448]; synchronous
+ *   ethcnn_ldp_sessions_state_ctus   its CTU count; 0: none; negative: bad arguments
+ *   ethcnn_ldp_sessions_bytes     host only, no context: what n open sessions that step together hold on the device,
+ *                                 sum_j roundup16(nctu_j) x (1792 (vectors) + 3584 (state)); negative for bad arguments,
+ *                                 a picture of more than 2^27 - 1 CTUs (what ethcnn_ldp_sessions_open refuses) among them.  Beside it: the
+ *                                 bundle images and, for ethcnn_ldp_sessions_step, the staged pictures and probabilities.
+ *   ethcnn_ldp_sessions_plan      host only: the layout of a call over pictures of these CTU counts, in the order given.
+ *                                 first_group_out[j] = sum_{i<j} ceil(nctus_i / 16); the G = sum_j ceil(nctus_j / 16) groups are cut into
+ *                                 *npasses_out passes of floor(cap / 16) groups, the last one shorter; pass_groups_out[p] (at most
+ *                                 max_passes are written) is the group count of pass p.  cap = max_ctus_per_pass, 0 = the default of
+ *                                 ethcnn_options (131072); below 16, n outside 1..32 or a CTU count below 1: ETHCNN_ERR_ARG.  Output
+ *                                 pointers may be NULL. */
+typedef struct ethcnn_ldp_sessions ethcnn_ldp_sessions;
+typedef struct ethcnn_ldp_session_frame {
+    int session;              /* id from ethcnn_ldp_sessions_open; at most once per call */
+    const uint8_t* luma;      /* device (step_device) or host (step) */
+    ptrdiff_t pitch;
+    int qp, i_frame, bundle;
+    const float* state_in;    /* may be NULL; 16-byte aligned on the device */
+    float* probs;             /* [nctu][21] */
+} ethcnn_ldp_session_frame;
+int ethcnn_ldp_sessions_create(ethcnn_ctx* ctx, int nbundles, ethcnn_ldp_sessions** out);
+void ethcnn_ldp_sessions_destroy(ethcnn_ldp_sessions* s);
+const char* ethcnn_ldp_sessions_last_error(const ethcnn_ldp_sessions* s);
+int ethcnn_ldp_sessions_bundles(const ethcnn_ldp_sessions* s);
+int ethcnn_ldp_sessions_load_lstm_checkpoint(ethcnn_ldp_sessions* s, int bundle, const char* prefix);
+int ethcnn_ldp_sessions_load_lstm_blob(ethcnn_ldp_sessions* s, int bundle, const float* blob, size_t nfloats);
+int ethcnn_ldp_sessions_load_lstm_synthetic(ethcnn_ldp_sessions* s, int bundle, uint64_t seed, double head_gain);
+int ethcnn_ldp_sessions_get_lstm_blob(ethcnn_ldp_sessions* s, int bundle, float* out, size_t nfloats);
+int ethcnn_ldp_sessions_open(ethcnn_ldp_sessions* s, int width, int height, int* session);
+int ethcnn_ldp_sessions_close(ethcnn_ldp_sessions* s, int session);
+int ethcnn_ldp_sessions_step_device(ethcnn_ldp_sessions* s, const ethcnn_ldp_session_frame* frames, int n);
+int ethcnn_ldp_sessions_step(ethcnn_ldp_sessions* s, const ethcnn_ldp_session_frame* frames, int n);
+int ethcnn_ldp_sessions_get_state(ethcnn_ldp_sessions* s, int session, float* state_out, size_t nfloats /* nctu * 896 */);
+int64_t ethcnn_ldp_sessions_state_ctus(ethcnn_ldp_sessions* s, int session);
+int64_t ethcnn_ldp_sessions_bytes(const int* widths, const int* heights, int n);
+int ethcnn_ldp_sessions_plan(const int* nctus, int n, int max_ctus_per_pass, int* first_group_out, int* npasses_out, int* pass_groups_out,
+                             int max_passes);
 /* Pinned (page-locked) host memory: buffers a caller fills itself (file reads) and hands to the host entry points are
  * DMA-able directly, without the runtime's pageable staging copy.  ethcnn_ldp_step goes further: a luma / probs pointer that
  * lies inside such a buffer is read / written by the kernels IN PLACE (no copy launch at all); so does ethcnn_predict_luma for ONE
