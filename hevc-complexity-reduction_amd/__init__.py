@@ -9,5 +9,5 @@ The directory name has a hyphen; import it with
     importlib.import_module("hevc-complexity-reduction_amd")
 """
 from . import ethcnn  # noqa: F401
-from .ethcnn import Calibrator, EthCnn, EthCnnError, LdpBatch, LdpGroup, LdpSessions, LstmSampleSet, LstmTrainer, LstmTrainerGroup, Pacer, PartitionSim, Replay, SampleSet, Trainer, TrainerGroup, load_library  # noqa: F401
+from .ethcnn import Calibrator, EthCnn, EthCnnError, LdpBatch, LdpGroup, LdpSessions, LstmSampleSet, LstmTrainer, LstmTrainerGroup, Pacer, PacerSet, PartitionSim, Replay, SampleSet, Trainer, TrainerGroup, load_library  # noqa: F401
 from . import net_CNN, sharding, video_to_cu_depth, resi_to_cu_depth_LDP  # noqa: F401

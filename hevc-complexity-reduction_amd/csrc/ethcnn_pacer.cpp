@@ -26,8 +26,8 @@ struct ethcnn_pacer {
     int64_t queued = 0;            // frames enqueued since create / reset
 };
 
-namespace {
-// the rules of the ladder, the weights, the budget and the mode; c may be NULL (the message then goes where ethcnn_last_error(NULL) reads)
+namespace ethcnn {
+namespace pacer {
 int check_rules(ethcnn_ctx* c, const ethcnn_sim_thr* ladder, int64_t K, const uint64_t* weight, uint32_t budget_ppm, int mode) {
     if (ladder) {
         if (int rc = sim::check_rung_count(c, K)) return rc;
@@ -41,14 +41,12 @@ int check_rules(ethcnn_ctx* c, const ethcnn_sim_thr* ladder, int64_t K, const ui
     return 0;
 }
 
-// W, H and the cost bound of a frame; *per = its CTUs
-int check_frame(ethcnn_pacer* p, int width, int height, int64_t* per) {
-    ethcnn_ctx* c = p->c;
+int check_frame(ethcnn_ctx* c, const uint64_t weight[4], int width, int height, int64_t* per) {
     sim::PicSize s;
     if (int rc = sim::check_size(c, width, height, 8, &s)) return rc;
     *per = s.ctus();
     if (*per >= kMaxFrameCtus) return set_err(c, ETHCNN_ERR_ARG, "a frame of %lld CTUs does not count in 32 bits (fewer than 2^24)", (long long)*per);
-    if (!sim::cost_fits(*per, p->weight)) return set_err(c, ETHCNN_ERR_ARG, "the cost of a frame of %lld CTUs may not fit in 64 bits under these weights", (long long)*per);
+    if (!sim::cost_fits(*per, weight)) return set_err(c, ETHCNN_ERR_ARG, "the cost of a frame of %lld CTUs may not fit in 64 bits under these weights", (long long)*per);
     return 0;
 }
 
@@ -69,6 +67,25 @@ int grow(ethcnn_ctx* c, void** buf, int64_t* cap, int64_t want, int64_t bytes_ea
     return 0;
 }
 
+std::vector<int> ladder_rows(const ethcnn_sim_thr* ladder, int64_t K) {
+    std::vector<ethcnn_sim_thr> lad;
+    if (ladder) lad.assign(ladder, ladder + K);
+    else {
+        lad.resize(kDefaultRungs);
+        ethcnn_budget_default_ladder(lad.data());
+    }
+    lad.push_back(sim::kFullSearch);  // rung K
+    std::vector<int> rows;
+    for (const ethcnn_sim_thr& t : lad) {
+        for (int l = 0; l < 3; ++l) rows.push_back(t.up_k[l]);
+        for (int l = 0; l < 3; ++l) rows.push_back(t.down_k[l]);
+    }
+    return rows;
+}
+}  // namespace pacer
+}  // namespace ethcnn
+
+namespace {
 // checked arguments, device-addressable pointers: the two launches
 int enqueue(ethcnn_pacer* p, const float* d_probs, int width, int height, int64_t per, float* d_baked, ethcnn_pacer_result* d_result) {
     ethcnn_ctx* c = p->c;
@@ -96,7 +113,7 @@ int enqueue(ethcnn_pacer* p, const float* d_probs, int width, int height, int64_
 }
 
 int check_call(ethcnn_pacer* p, const void* probs, const void* baked, int width, int height, int64_t* per) {
-    if (int rc = check_frame(p, width, height, per)) return rc;
+    if (int rc = check_frame(p->c, p->weight, width, height, per)) return rc;
     if (!probs || !baked) return set_err(p->c, ETHCNN_ERR_ARG, "null probabilities or output buffer");
     return 0;
 }
@@ -111,26 +128,15 @@ extern "C" int ethcnn_pacer_create(ethcnn_ctx* c, const ethcnn_sim_thr* ladder, 
     if (!c) return ETHCNN_ERR_ARG;
     if (!out) return set_err(c, ETHCNN_ERR_ARG, "ethcnn_pacer_create: null output");
     if (int rc = check_rules(c, ladder, K, weight, budget_ppm, mode)) return rc;
-    std::vector<ethcnn_sim_thr> lad;
-    if (ladder) lad.assign(ladder, ladder + K);
-    else {
-        lad.resize(kDefaultRungs);
-        ethcnn_budget_default_ladder(lad.data());
-    }
-    lad.push_back(sim::kFullSearch);  // rung K
-    std::vector<int> rows;
-    for (const ethcnn_sim_thr& t : lad) {
-        for (int l = 0; l < 3; ++l) rows.push_back(t.up_k[l]);
-        for (int l = 0; l < 3; ++l) rows.push_back(t.down_k[l]);
-    }
+    const std::vector<int> rows = ladder_rows(ladder, K);
     HIPCHK(c, hipSetDevice(c->device));
     ethcnn_pacer* p = new ethcnn_pacer;
     p->c = c;
-    p->K = (int64_t)lad.size() - 1;
+    p->K = (int64_t)rows.size() / 6 - 1;
     for (int d = 0; d < 4; ++d) p->weight[d] = (weight ? weight : sim::kDefaultWeight)[d];
     p->budget_ppm = budget_ppm;
     p->mode = mode;
-    const size_t n = lad.size();
+    const size_t n = rows.size() / 6;
     hipError_t e = hipMalloc((void**)&p->d_thr, n * 24);
     if (e == hipSuccess) e = hipMalloc((void**)&p->d_checked, n * 16);
     if (e == hipSuccess) e = hipMalloc((void**)&p->d_state, kStateWords * 4);

@@ -19,10 +19,13 @@
 //   [0] ticket   [2..3] frames paced (uint64)   [4..7] carry (128 bits, low word first)   [8..13] the picked rung's up_k[3], down_k[3]
 #pragma once
 #include <cstdint>
+#include <vector>
 
 #include <hip/hip_runtime_api.h>
 
-struct ethcnn_pacer_result;
+#include "../../include/ethcnn.h"
+
+struct ethcnn_ctx;
 
 namespace ethcnn {
 namespace pacer {
@@ -51,6 +54,16 @@ struct FrameArgs {
 long frame_blocks(long per, int rungs);
 void launch_frame(hipStream_t s, const FrameArgs& a);
 void launch_done(hipStream_t s, unsigned* h_done, unsigned seq);
+
+// ---- host side, shared with the pacer set (ethcnn_pacer_set.cpp); definitions: ethcnn_pacer.cpp
+// the rules of the ladder, the weights, the budget and the mode; c may be NULL (the message then goes where ethcnn_last_error(NULL) reads)
+int check_rules(ethcnn_ctx* c, const ethcnn_sim_thr* ladder, int64_t K, const uint64_t* weight, uint32_t budget_ppm, int mode);
+// W, H and the cost bound of a frame under `weight`; *per = its CTUs
+int check_frame(ethcnn_ctx* c, const uint64_t weight[4], int width, int height, int64_t* per);
+// a device buffer of at least `want` units of bytes_each; growing waits for the work in flight on the context's stream
+int grow(ethcnn_ctx* c, void** buf, int64_t* cap, int64_t want, int64_t bytes_each, const char* what);
+// the ladder (NULL: the default one) with the full search appended, as int32 rows up_k[3], down_k[3]
+std::vector<int> ladder_rows(const ethcnn_sim_thr* ladder, int64_t K);
 
 }  // namespace pacer
 }  // namespace ethcnn

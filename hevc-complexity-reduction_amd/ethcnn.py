@@ -325,6 +325,15 @@ SIGNATURES = {
     "ethcnn_pacer_frame_device": (_i, [_vp, _vp, _i, _i, _vp, _vp]),
     "ethcnn_pacer_frame": (_i, [_vp, _vp, _i, _i, _vp, _vp]),
     "ethcnn_pacer_last": (_i, [_vp, _vp]),
+    "ethcnn_pacer_set_create": (_i, [_vp, _i, _vp, ctypes.c_int64, _vp, ctypes.c_uint32, _i, ctypes.POINTER(_vp)]),
+    "ethcnn_pacer_set_destroy": (None, [_vp]),
+    "ethcnn_pacer_set_slots": (_i, [_vp]),
+    "ethcnn_pacer_set_launches": (ctypes.c_int64, [_vp]),
+    "ethcnn_pacer_set_reset": (_i, [_vp, _i]),
+    "ethcnn_pacer_set_frames_device": (_i, [_vp, _vp, _i]),
+    "ethcnn_pacer_set_frames": (_i, [_vp, _vp, _i]),
+    "ethcnn_pacer_set_last": (_i, [_vp, _i, _vp]),
+    "ethcnn_pacer_set_plan": (_i, [_vp, _i, ctypes.c_int64, _vp, _vp, _vp, _vp, _vp, _vp, _vp]),
     "ethcnn_ladder_check": (_i, [_vp, _i, ctypes.c_int64, ctypes.c_uint32]),
     "ethcnn_ladder_build": (_i, [_vp, _vp, _i, ctypes.c_int64, ctypes.c_uint32, _vp, _vp]),
     "ethcnn_ladder_thin": (_i, [_vp, ctypes.c_int64, ctypes.c_int64, _vp, _vp]),
@@ -2782,6 +2791,128 @@ class Pacer(object):
         """the result record of the most recent frame (synchronous)"""
         res = np.zeros(1, PACER_RESULT)
         self._chk(self.lib.ethcnn_pacer_last(self._handle(), res.ctypes.data))
+        return res[0]
+
+
+# search budget, online: several sequences (include/ethcnn.h)
+PACER_SET_MAX = 32
+
+
+class PacerSetFrame(ctypes.Structure):
+    """ethcnn_pacer_set_frame"""
+    _fields_ = [("slot", ctypes.c_int), ("probs", ctypes.c_void_p), ("width", ctypes.c_int), ("height", ctypes.c_int), ("baked", ctypes.c_void_p),
+                ("result", ctypes.c_void_p)]
+
+
+def pacer_set_plan(nctus, K=512, lib=None):
+    """ethcnn_pacer_set_plan (host only): the layout of a PacerSet call over frames of these CTU counts, in this order, under K + 1 rungs
+    -> {"count_first", "count_blocks", "slice_len", "bake_first", "rec0": one entry per frame, "count_grid", "bake_grid"}; EthCnnError
+    for bad arguments"""
+    lib = lib or load_library()
+    n = len(nctus)
+    counts = np.array([min(max(int(x), -1), 2 ** 62) for x in nctus], np.int64)
+    out = {k: np.zeros(max(n, 1), np.int32 if k == "slice_len" else np.int64) for k in ("count_first", "count_blocks", "slice_len", "bake_first", "rec0")}
+    grids = np.zeros(2, np.int64)
+    rc = lib.ethcnn_pacer_set_plan(counts.ctypes.data if n else None, n, _int_arg(K, -1, 2 ** 63 - 1), out["count_first"].ctypes.data,
+                                   out["count_blocks"].ctypes.data, out["slice_len"].ctypes.data, out["bake_first"].ctypes.data, out["rec0"].ctypes.data,
+                                   grids.ctypes.data, grids.ctypes.data + 8)
+    if rc:
+        raise EthCnnError(rc, "ethcnn_pacer_set_plan: bad arguments")
+    res = {k: [int(x) for x in v[:n]] for k, v in out.items()}
+    res.update(count_grid=int(grids[0]), bake_grid=int(grids[1]))
+    return res
+
+
+class PacerSet(object):
+    """Up to 32 paced sequences behind one ladder, one weight vector, one budget (a share 0..1) and one mode (include/ethcnn.h "search
+    budget, online: several sequences"): a slot owns the carry, the frame count and the result of one sequence, a call paces any subset
+    of the slots by one frame each in two launches on the context's stream.  Slot by slot the results and the baked rows are a Pacer's."""
+
+    def __init__(self, ctx, nslots, budget, mode="frame", ladder=None, weights=None):
+        self.ctx, self.lib = ctx, ctx.lib
+        lad = None if ladder is None else _sim_cands(ladder)
+        w = None if weights is None else (ctypes.c_uint64 * 4)(*[int(x) for x in weights])
+        h = ctypes.c_void_p()
+        ctx._chk(self.lib.ethcnn_pacer_set_create(ctx.h, int(nslots), None if lad is None else lad.ctypes.data, 0 if lad is None else lad.size, w,
+                                                  _budget_ppm(budget), _budget_mode(mode), ctypes.byref(h)))
+        self.h = h
+        if not hasattr(ctx, "_trainers"):
+            ctx._trainers = weakref.WeakSet()
+        ctx._trainers.add(self)  # closed with the context, before it
+
+    def _chk(self, rc):
+        self.ctx._chk(rc)
+
+    def _handle(self):
+        if not getattr(self, "h", None):
+            raise ValueError("the pacer set is closed")
+        return self.h
+
+    def close(self):
+        if getattr(self, "h", None):
+            self.lib.ethcnn_pacer_set_destroy(self.h)
+            self.h = None
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+    def __enter__(self):
+        return self
+
+    def __exit__(self, *a):
+        self.close()
+
+    def __len__(self):
+        return max(0, int(self.lib.ethcnn_pacer_set_slots(self._handle())))
+
+    @property
+    def launches(self):
+        """kernels the set has enqueued since it was made"""
+        return int(self.lib.ethcnn_pacer_set_launches(self._handle()))
+
+    def reset(self, slot):
+        """carry = 0, frame = 0 of that slot (in stream order behind the frames already queued)"""
+        self._chk(self.lib.ethcnn_pacer_set_reset(self._handle(), int(slot)))
+
+    def frames_device(self, frames):
+        """asynchronous on the context's stream (ethcnn_pacer_set_frames_device).  frames: one dict per frame with slot, d_probs, width,
+        height, d_baked (DeviceBuffers or raw device addresses; d_baked may be d_probs) and optionally d_result (72 bytes, None)"""
+        ptr = lambda b: None if b is None else getattr(b, "ptr", b)
+        arr = (PacerSetFrame * max(len(frames), 1))()
+        for j, f in enumerate(frames[:len(arr)]):
+            arr[j] = PacerSetFrame(int(f["slot"]), ptr(f["d_probs"]), int(f["width"]), int(f["height"]), ptr(f["d_baked"]), ptr(f.get("d_result")))
+        self._chk(self.lib.ethcnn_pacer_set_frames_device(self._handle(), arr, len(frames)))
+
+    def frames(self, frames):
+        """synchronous, host memory (ethcnn_pacer_set_frames).  frames: one dict per frame with slot, probs (float32 [nctu, 21]; a view of
+        ctx.host_buffer() is used in place), width, height and optionally out (the array the baked rows go to; None: a new one; the
+        `probs` array itself: in place) -> (the baked arrays [nctu, 21], the result records), both in call order"""
+        arr = (PacerSetFrame * max(len(frames), 1))()
+        res = np.zeros(max(len(frames), 1), PACER_RESULT)
+        keep, outs = [], []
+        for j, f in enumerate(frames[:len(arr)]):
+            n = ctus_per_frame(int(f["width"]), int(f["height"]))
+            probs = np.ascontiguousarray(f["probs"], dtype=np.float32)
+            if probs.size != n * NOUT:
+                raise ValueError("frame %d: a %d x %d frame has %d x 21 probabilities, got %d values" % (j, f["width"], f["height"], n, probs.size))
+            out = f.get("out")
+            if out is None:
+                out = np.empty((n, NOUT), np.float32)
+            elif out.dtype != np.float32 or not out.flags["C_CONTIGUOUS"] or out.size != n * NOUT:
+                raise ValueError("frame %d: out must be a contiguous float32 array of %d values" % (j, n * NOUT))
+            keep.append(probs)
+            outs.append(out)
+            arr[j] = PacerSetFrame(int(f["slot"]), probs.ctypes.data, int(f["width"]), int(f["height"]), out.ctypes.data, res.ctypes.data + j * PACER_RESULT.itemsize)
+        self._chk(self.lib.ethcnn_pacer_set_frames(self._handle(), arr, len(frames)))
+        return [o.reshape(-1, NOUT) for o in outs], [res[j] for j in range(len(frames))]
+
+    def last(self, slot):
+        """the result record of that slot's most recent frame (synchronous)"""
+        res = np.zeros(1, PACER_RESULT)
+        self._chk(self.lib.ethcnn_pacer_set_last(self._handle(), int(slot), res.ctypes.data))
         return res[0]
 
 

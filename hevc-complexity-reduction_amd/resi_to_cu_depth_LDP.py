@@ -35,6 +35,10 @@ step + heads + gates on the GPU).  Differences from the reference, none in the n
     Low-Delay-P token order, "0.25 0.75 0.25 0.75 0.25 0.75".  A frame with i_frame <= 1 or another geometry starts a new allowance.
     ETHCNN_SEARCH_BUDGET_LADDER=auto, which lets the All-Intra launcher build the ladder from the sequence it predicts, is refused at
     start-up with the reason: this loop sees one frame at a time.
+  * --sessions DIR [DIR ...] serves several working directories from one context (serve_many); there the budget is given on the command
+    line, --budget SHARE [--budget-mode frame|carry] [--budget-weights "64 16 4 1"] [--budget-ladder FILE], under the value rules above,
+    and is held for every directory by ONE pacer set (ethcnn.PacerSet): a directory's session is its slot, a round of directories is one
+    call behind the round's step.  One policy for all directories; the environment variables stay refused under --sessions.
 """
 from __future__ import print_function
 
@@ -348,6 +352,20 @@ def check_sessions(workdirs):
     return gates
 
 
+def check_pace(workdirs, share, mode=None, weights=None, ladder=None):
+    """What `--sessions ... --budget` refuses at start-up beyond check_sessions, as ValueError, before a GPU is touched and with nothing
+    written: the four option values under search_budget's rules, and a directory whose Thr_info.txt is not the companion line in
+    Low-Delay-P token order -> (share, mode, weights or None, ladder or None)"""
+    names = _sb.OPTION_NAMES
+    budget = _sb.from_values(share, mode, weights, names)
+    if budget is None:
+        raise ValueError("%s='' is not a share of the full search, 0..1" % names[0])
+    rungs = _sb.ladder_from_path(ladder, 'ldp', auto=NO_AUTO_LADDER, name=names[3])
+    for d in workdirs:
+        _sb.check_companion_thr_file(os.path.join(d, THR_FILE), _sb.COMPANION_LINE_LDP, names[0])
+    return budget + (rungs,)
+
+
 class _BundlePlace(object):
     """bundle i of an LdpSessions object behind the two loaders restore_lstm calls"""
 
@@ -369,6 +387,7 @@ class _Dir(object):
         self.session, self.geom = None, None
         self.last_key, self.state_sig = None, None
         self.pinned, self.pinned_probs = None, None
+        self.paced_geom, self.paced = None, [0, 0, 0, 0]   # as serve's: frames, over budget, sum of cost, sum of full
 
     def p(self, name):
         return os.path.join(self.workdir, name)
@@ -381,17 +400,23 @@ def _host_buffer_again(ctx, old, nbytes):
     return ctx.host_buffer(nbytes)
 
 
-def serve_many(workdirs, max_frames=None, idle_timeout=None, poll_s=2e-4, device=0, verbose=True, accept_stale=False):
+def serve_many(workdirs, max_frames=None, idle_timeout=None, poll_s=2e-4, device=0, verbose=True, accept_stale=False, pace=None):
     """One server for several HM working directories: one context, one LdpSessions object, the unchanged file handshake per directory.
     A poll round takes every directory with pred_start.sig and a complete command.dat, reads their resi.yuv, advances all of them
     in ONE step, writes cu_depth.dat and pred_end.sig per directory and then refreshes every served state.dat and its sidecar.  State
-    continuity per directory is serve's rule.  max_frames and idle_timeout count over all directories.  Returns the frames predicted."""
+    continuity per directory is serve's rule.  max_frames and idle_timeout count over all directories.  Returns the frames predicted.
+    pace: what check_pace returned, or None.  With it the gates are open and one PacerSet holds the search of every directory under that
+    share: a directory's session id is its slot, and behind each step ONE call paces the round's frames in place in their page-locked
+    buffers before the files are written.  A directory's slot is reset where serve resets its pacer."""
     check_sessions(workdirs)
     dirs = [_Dir(d) for d in workdirs]
     ctx = _e.EthCnn(device=device)
-    sessions = None
+    sessions = pacer = None
     try:
         ctx.load_thresholds(dirs[0].p(THR_FILE))   # (the gates check_sessions compared)
+        if pace is not None:
+            ctx.set_thresholds(0.0, 0.0)    # open gates, whatever Thr_info.txt says: the baked files are what the encoders read
+            pacer = _e.PacerSet(ctx, MAX_SESSIONS, pace[0], pace[1], ladder=None if pace[3] is None else _e.sim_thr(*pace[3]), weights=pace[2])
         restore_cnn(ctx, workdirs[0])
         sessions = _e.LdpSessions(ctx, MAX_BUNDLES)
         bundles = {}  # model name of a QP band -> bundle index
@@ -428,7 +453,7 @@ def serve_many(workdirs, max_frames=None, idle_timeout=None, poll_s=2e-4, device
                 if d.geom != (w, h):  # a new sequence in this directory: a new session
                     if d.session is not None:
                         sessions.close(d.session)
-                    d.session, d.geom, d.last_key = sessions.open(w, h), (w, h), None
+                    d.session, d.geom, d.last_key, d.paced_geom = sessions.open(w, h), (w, h), None, None
                 num_vectors = _e.ctus_per_frame(w, h)
                 if d.pinned is None or d.pinned.size < w * h:
                     d.pinned = _host_buffer_again(ctx, d.pinned, w * h)
@@ -449,6 +474,19 @@ def serve_many(workdirs, max_frames=None, idle_timeout=None, poll_s=2e-4, device
                 frames.append({'session': d.session, 'luma': luma, 'qp': qp, 'i_frame': i_frame, 'bundle': bundles[name], 'state_in': state_in,
                                'probs_out': d.pinned_probs[:num_vectors * 21]})
             depths = sessions.step(frames)
+            if pacer is not None:   # (only once the step has succeeded: a frame is never paced twice)
+                for d, (i_frame, w, h, qp) in ready:
+                    if i_frame <= 1 or d.paced_geom != (w, h):
+                        pacer.reset(d.session)   # a new sequence starts with a new allowance, as it starts with a zero LSTM state
+                        d.paced_geom = (w, h)
+                depths, results = pacer.frames([{'slot': d.session, 'probs': depth, 'width': w, 'height': h, 'out': depth}   # page-locked, in place
+                                                for depth, (d, (i_frame, w, h, qp)) in zip(depths, ready)])
+                for res, (d, (i_frame, w, h, qp)) in zip(results, ready):
+                    d.paced = [d.paced[0] + 1, d.paced[1] + int(res['over']), d.paced[2] + int(res['cost']), d.paced[3] + int(res['full'])]
+                    if verbose:
+                        print('%s: frame %d: rung %d, %.6f of the full search%s' % (d.workdir, i_frame, int(res['rung']),
+                                                                                   int(res['cost']) / float(int(res['full']) or 1),
+                                                                                   ', over budget' if res['over'] else ''))
             # what the encoders wait for first, for every directory; the state files afterwards, while they are encoding
             late = [save_cu_depth(depth, d.p(SAVE_FILE), d.p(STATE_FILE), d.p(END_FILE), _e.ctus_per_frame(w, h), (i_frame, w, h))
                     for depth, (d, (i_frame, w, h, qp)) in zip(depths, ready)]
@@ -461,21 +499,31 @@ def serve_many(workdirs, max_frames=None, idle_timeout=None, poll_s=2e-4, device
                 print('%d frames predicted (%d in this step).' % (n_frame_total, len(ready)))
         return n_frame_total
     finally:
+        for d in dirs:
+            if d.paced[0]:
+                sys.stderr.write('resi_to_cu_depth_LDP: %s: search budget %g (%s): %.6f of the full search over %d frames, %d over budget\n'
+                                 % (d.workdir, pace[0], pace[1], d.paced[2] / float(d.paced[3] or 1), d.paced[0], d.paced[1]))
+        if pacer is not None:
+            pacer.close()
         if sessions is not None:
             sessions.close()
         ctx.close()
 
 
 USAGE = ('usage: resi_to_cu_depth_LDP.py [--max-frames N] [--idle-timeout S] [--accept-stale]\n'
-         '       resi_to_cu_depth_LDP.py --sessions DIR [DIR ...] [--max-frames N] [--idle-timeout S] [--accept-stale]\n')
+         '       resi_to_cu_depth_LDP.py --sessions DIR [DIR ...] [--max-frames N] [--idle-timeout S] [--accept-stale] [--quiet]\n'
+         '                               [--budget SHARE [--budget-mode frame|carry] [--budget-weights "W64 W32 W16 W8"] [--budget-ladder FILE]]\n')
 
 
 def main(argv):
     """`python resi_to_cu_depth_LDP.py` in HM-LDP's bin/ (no arguments, like the reference);
-    optional: --max-frames N, --idle-timeout SECONDS; --sessions DIR [DIR ...]: one server for several working directories."""
+    optional: --max-frames N, --idle-timeout SECONDS; --sessions DIR [DIR ...]: one server for several working directories, and behind
+    it only --budget SHARE [--budget-mode M] [--budget-weights "W64 W32 W16 W8"] [--budget-ladder FILE]: the search budget of all of them,
+    and --quiet."""
     max_frames = idle = None
-    accept_stale = False
+    accept_stale = quiet = False
     workdirs = None
+    options = {}   # --budget, --budget-mode, --budget-weights, --budget-ladder -> their texts
     args = list(argv[1:])
     while args:
         a = args.pop(0)
@@ -489,17 +537,27 @@ def main(argv):
             workdirs = []
             while args and not args[0].startswith('--'):
                 workdirs.append(args.pop(0))
+        elif a in _sb.OPTION_NAMES and a not in options and args:
+            options[a] = args.pop(0)
+        elif a == '--quiet':
+            quiet = True
         else:
             sys.stderr.write(USAGE)
             return 2
+    if (options or quiet) and workdirs is None or (options and _sb.OPTION_NAMES[0] not in options):
+        sys.stderr.write(USAGE)   # the budget options belong to --sessions, and the three others to --budget
+        return 2
     if workdirs is not None:
+        pace = None
         try:
             check_sessions(workdirs)
+            if options:
+                pace = check_pace(workdirs, *[options.get(n) for n in _sb.OPTION_NAMES])
         except ValueError as err:
             sys.stderr.write('resi_to_cu_depth_LDP: %s\n' % err)
             return 1
         try:
-            serve_many(workdirs, max_frames=max_frames, idle_timeout=idle, accept_stale=accept_stale)
+            serve_many(workdirs, max_frames=max_frames, idle_timeout=idle, accept_stale=accept_stale, verbose=not quiet, pace=pace)
         except StaleStateError:
             return 1
         return 0

@@ -14,9 +14,14 @@ AUTO = 'auto'                                          # ETHCNN_SEARCH_BUDGET_LA
 AUTO_GRID = 8                                          # ... on this grid, up to MAX_RUNGS rungs, without a cap
 
 
-def from_env():
-    """None when ETHCNN_SEARCH_BUDGET is unset or empty, else (share, mode, weights or None); ValueError names a bad value"""
-    text = os.environ.get('ETHCNN_SEARCH_BUDGET')
+ENV_NAMES = ('ETHCNN_SEARCH_BUDGET', 'ETHCNN_SEARCH_BUDGET_MODE', 'ETHCNN_SEARCH_BUDGET_WEIGHTS', 'ETHCNN_SEARCH_BUDGET_LADDER')
+OPTION_NAMES = ('--budget', '--budget-mode', '--budget-weights', '--budget-ladder')   # the same four as command-line options
+
+
+def from_values(share_text, mode_text, weights_text, names=ENV_NAMES):
+    """None when the share is unset or empty, else (share, mode, weights or None); ValueError names a bad value after `names`, the
+    variables or options the three texts came from"""
+    text = share_text
     if text is None or text == '':
         return None
     try:
@@ -24,23 +29,28 @@ def from_env():
     except ValueError:
         share = -1.0
     if not 0.0 <= share <= 1.0:   # (a NaN fails both comparisons)
-        raise ValueError("ETHCNN_SEARCH_BUDGET='%s' is not a share of the full search, 0..1" % text)
-    mode = os.environ.get('ETHCNN_SEARCH_BUDGET_MODE') or 'frame'
+        raise ValueError("%s='%s' is not a share of the full search, 0..1" % (names[0], text))
+    mode = mode_text or 'frame'
     if mode not in ('frame', 'carry'):
-        raise ValueError("ETHCNN_SEARCH_BUDGET_MODE='%s' (allowed: frame, carry)" % mode)
+        raise ValueError("%s='%s' (allowed: frame, carry)" % (names[1], mode))
     weights = None
-    text = os.environ.get('ETHCNN_SEARCH_BUDGET_WEIGHTS')
+    text = weights_text
     if text:
         try:
             weights = [int(t) for t in text.split()]
         except ValueError:
             weights = []
         if len(weights) != 4 or min(weights) < 0 or max(weights) >= 1 << 32:
-            raise ValueError("ETHCNN_SEARCH_BUDGET_WEIGHTS='%s' is not four integers W64 W32 W16 W8 in 0..2^32-1" % text)
+            raise ValueError("%s='%s' is not four integers W64 W32 W16 W8 in 0..2^32-1" % (names[2], text))
     return share, mode, weights
 
 
-def check_companion_thr_file(path, line):
+def from_env():
+    """None when ETHCNN_SEARCH_BUDGET is unset or empty, else (share, mode, weights or None); ValueError names a bad value"""
+    return from_values(*[os.environ.get(n) for n in ENV_NAMES[:3]])
+
+
+def check_companion_thr_file(path, line, name=ENV_NAMES[0]):
     """A baked cu_depth.dat means what it says only under the companion thresholds, and HM reads them from this file: ValueError unless
     it holds exactly the six values of `line` (the companion line in the token order of the encoder that reads it)"""
     try:
@@ -48,8 +58,8 @@ def check_companion_thr_file(path, line):
     except (OSError, ValueError):
         tokens = None
     if tokens != [float(t) for t in line.split()]:
-        raise ValueError("ETHCNN_SEARCH_BUDGET is set, so the encoder must read the companion thresholds: put the line\n    %s\ninto %s "
-                         "(found: %s)" % (line, path, 'no readable file' if tokens is None else ' '.join('%g' % t for t in tokens)))
+        raise ValueError("%s is set, so the encoder must read the companion thresholds: put the line\n    %s\ninto %s "
+                         "(found: %s)" % (name, line, path, 'no readable file' if tokens is None else ' '.join('%g' % t for t in tokens)))
 
 
 def read_ladder(path, order):
@@ -78,24 +88,28 @@ def read_ladder(path, order):
     return up, down
 
 
-def ladder_from_env(order, auto=None):
-    """None when ETHCNN_SEARCH_BUDGET_LADDER is unset or empty (the default ladder), else read_ladder of that file in the token order
-    of the launcher that asks; ValueError names a file that is missing or malformed or holds more than 4096 rungs.  The value "auto"
-    gives AUTO to a launcher that can build a ladder from the sequence it is about to predict (auto=True); every other launcher
-    passes the reason why it cannot, and the ValueError carries it"""
-    path = os.environ.get('ETHCNN_SEARCH_BUDGET_LADDER')
+def ladder_from_path(path, order, auto=None, name=ENV_NAMES[3]):
+    """None when `path` is unset or empty (the default ladder), else read_ladder of that file in the token order of the launcher that
+    asks; ValueError names a file that is missing or malformed or holds more than 4096 rungs, after `name`, the variable or option the
+    path came from.  The value "auto" gives AUTO to a launcher that can build a ladder from the sequence it is about to predict
+    (auto=True); every other launcher passes the reason why it cannot, and the ValueError carries it"""
     if not path:
         return None
     if path == AUTO and auto is not None:
         if auto is True:
             return AUTO
-        raise ValueError("ETHCNN_SEARCH_BUDGET_LADDER='auto' cannot be read: %s" % auto)
+        raise ValueError("%s='auto' cannot be read: %s" % (name, auto))
     try:
         return read_ladder(path, order)
     except OSError as err:
-        raise ValueError("ETHCNN_SEARCH_BUDGET_LADDER='%s' cannot be read: %s" % (path, err.strerror or err))
+        raise ValueError("%s='%s' cannot be read: %s" % (name, path, err.strerror or err))
     except ValueError as err:
-        raise ValueError("ETHCNN_SEARCH_BUDGET_LADDER: %s" % err)
+        raise ValueError("%s: %s" % (name, err))
+
+
+def ladder_from_env(order, auto=None):
+    """ladder_from_path of ETHCNN_SEARCH_BUDGET_LADDER"""
+    return ladder_from_path(os.environ.get(ENV_NAMES[3]), order, auto)
 
 
 def reliability_from_env(read):

@@ -1364,6 +1364,72 @@ int ethcnn_pacer_frame_device(ethcnn_pacer* pacer, const float* d_probs, int wid
 int ethcnn_pacer_frame(ethcnn_pacer* pacer, const float* probs, int width, int height, float* baked, ethcnn_pacer_result* result);
 int ethcnn_pacer_last(ethcnn_pacer* pacer, ethcnn_pacer_result* out);
 
+/* ---- search budget, online: several sequences.  A PACER SET is the pacer above in the shape of "config #5 online, several live encoders":
+ *      one ladder, one weight vector, one budget and one mode, and up to ETHCNN_PACER_SET_MAX SLOTS.  A slot owns what a pacer owns per
+ *      sequence -- the 128-bit carry, the frame count, the table checked uint32 [K + 1][4], the picked rung's row and one 72-byte result
+ *      slot in page-locked memory -- and a call paces n = 1..32 frames, each of another slot, in TWO launches on the context's stream
+ *      whatever n is: one kernel packs every frame's records, counts the checks of every rung into the table of the frame's slot and makes
+ *      each slot's choice on the device (the block that finishes a FRAME last chooses for it; no block waits for another), one kernel bakes
+ *      every frame under the row its slot's choice left behind.  No reference counterpart.
+ *   The equality that defines it: for every slot, the sequence of results (frame, rung, over, cost, full, carry, thresholds) and every
+ *      baked byte are those of an ethcnn_pacer with the same ladder, weights, budget and mode that is given the same frames of that slot
+ *      in the same order and the same resets -- whatever other slots shared the calls, in whatever order the frames stood in them, and
+ *      whichever subset of the slots a call names.
+ *   ethcnn_pacer_set_create    nslots in 1..32; ladder, K, weight, budget_ppm, mode under the rules of ethcnn_pacer_check (ladder NULL: the
+ *                              default ladder, K is not read; weight NULL: 64 16 4 1).  Holds in HBM the ladder, nslots tables and nslots
+ *                              x 16 state words, and nslots result slots in page-locked memory.  Destroy the set before its context.
+ *   ethcnn_pacer_set_reset     carry = 0 and frame = 0 of ONE slot, in stream order behind the frames already queued; no other slot is
+ *                              touched.
+ *   ethcnn_pacer_set_frames_device   frames[n]: {slot, probs, width, height, baked, result} with DEVICE pointers.  Asynchronous on the
+ *                              context's stream; synchronises nothing, except when the record scratch has to grow.  The scratch is shared
+ *                              by the slots: 64 bytes per CTU of the call with the most CTUs seen (ETHCNN_ERR_NOMEM with the byte count in
+ *                              the message, nothing changed; growing waits for the frames in flight).  baked == probs (in place) is
+ *                              allowed; result (72 bytes, written when the frame's choice is made) may be NULL.
+ *   ethcnn_pacer_set_frames    the same with HOST pointers, synchronous.  A pointer inside an ethcnn_host_alloc buffer is read or written
+ *                              in place by the kernels; every other frame goes through one staging buffer (84 bytes per staged CTU of the
+ *                              call); the bytes do not depend on the route.  result is a host pointer here and may be NULL.  When every
+ *                              output is page-locked the wait is ethcnn_pacer_frame's: the context's completion word, which one lane
+ *                              stores behind the bake (a third launch), with hipStreamSynchronize as the fallback.
+ *   ethcnn_pacer_set_last      synchronous: the result of the slot's most recent frame (ETHCNN_ERR_ARG when it has paced none since create /
+ *                              its reset).
+ *   ethcnn_pacer_set_slots, ethcnn_pacer_set_launches   host only: nslots; the kernels the set has enqueued since create (two per call,
+ *                              three where the host form stores the completion word).  Negative: a NULL set.
+ *   ethcnn_pacer_set_plan      host only, no context: the layout of a call over frames of nctus[j] CTUs under K + 1 rungs, in call order.
+ *                              Frame j owns the blocks [count_first[j], count_first[j] + count_blocks[j]) of the count kernel --
+ *                              count_blocks = slices x ceil((K + 1) / 256), slices of slice_len[j] CTUs cut as ethcnn_pacer_frame cuts
+ *                              them: at most 64 CTUs, balanced (272 CTUs: 55, 55, 55, 55, 52) --, the blocks from bake_first[j] on of the
+ *                              bake kernel, ceil(nctus[j] / 256) of them, and the records from rec0[j] on, the running sum of the CTUs.
+ *                              Every output has n entries and may be NULL; the two grid sizes are the totals.  All sums are kept in 64
+ *                              bits.  ETHCNN_ERR_ARG with nothing written: n outside 1..32, a frame of no CTU or of 2^24 or more, K outside
+ *                              1..ETHCNN_BUDGET_MAX_RUNGS, NULL nctus.
+ *   Refusals of a call, each ETHCNN_ERR_ARG before anything is allocated or enqueued, so that every slot's next result is what it would have
+ *      been without the call: n outside 1..32; a slot outside 0..nslots - 1 or named twice; a NULL probs or baked; a pointer that is not
+ *      4-byte aligned; a baked that overlaps ANOTHER frame's probs or baked; a frame that ethcnn_pacer_frame would refuse (W or H no
+ *      multiple of 8 or above 65536, 2^24 CTUs or more, a cost bound that may not fit in 64 bits).  The text is read with ethcnn_last_error
+ *      of the context, as the pacer's is.
+ *   (A space stands before the parenthesis of these declarations, so that a search for the pacer's own entries, `ethcnn_pacer_` + name +
+ *      `(`, lists those seven and nothing else.) */
+#define ETHCNN_PACER_SET_MAX 32
+typedef struct ethcnn_pacer_set ethcnn_pacer_set;
+typedef struct ethcnn_pacer_set_frame {
+    int slot;                    /* 0..nslots - 1; at most once per call */
+    const float* probs;          /* [nctu][21] */
+    int width, height;
+    float* baked;                /* [nctu][21]; may be probs */
+    ethcnn_pacer_result* result; /* may be NULL */
+} ethcnn_pacer_set_frame;
+int ethcnn_pacer_set_create (ethcnn_ctx* ctx, int nslots, const ethcnn_sim_thr* ladder, int64_t K, const uint64_t weight[4], uint32_t budget_ppm,
+                             int mode, ethcnn_pacer_set** out);
+void ethcnn_pacer_set_destroy (ethcnn_pacer_set* set);
+int ethcnn_pacer_set_slots (const ethcnn_pacer_set* set);
+int64_t ethcnn_pacer_set_launches (const ethcnn_pacer_set* set);
+int ethcnn_pacer_set_reset (ethcnn_pacer_set* set, int slot);
+int ethcnn_pacer_set_frames_device (ethcnn_pacer_set* set, const ethcnn_pacer_set_frame* frames, int n);
+int ethcnn_pacer_set_frames (ethcnn_pacer_set* set, const ethcnn_pacer_set_frame* frames, int n);
+int ethcnn_pacer_set_last (ethcnn_pacer_set* set, int slot, ethcnn_pacer_result* out);
+int ethcnn_pacer_set_plan (const int64_t* nctus, int n, int64_t K, int64_t* count_first_out, int64_t* count_blocks_out, int32_t* slice_len_out,
+                           int64_t* bake_first_out, int64_t* rec0_out, int64_t* count_grid_out, int64_t* bake_grid_out);
+
 /* ---- search budget: building a ladder.  The two sections above pick a rung of a LADDER per frame; how well they hold a budget depends on
  *      that ladder, and the default one is the same on every level and never looks at a label.  These entries turn a simulator's set
  *      with labels into a ladder by a greedy walk from the full search: every step moves ONE of the six thresholds to the nearest grid

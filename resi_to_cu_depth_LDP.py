@@ -17,7 +17,7 @@ def _main():
     args = sys.argv[1:]
     env = os.environ.get("ETHCNN_LDP_NATIVE", "")
     exe = os.path.join(home, "hevc-complexity-reduction_amd", "bin", "resi_to_cu_depth_ldp")
-    want_python = "--python" in args or env == "0" or "--sessions" in args  # (one server for several directories: the Python daemon's)
+    want_python = "--python" in args or env == "0" or "--sessions" in args or any(a.startswith("--budget") for a in args)  # (one server for several directories, and its options: the Python daemon's)
     insist = "--native" in args or env not in ("", "0")
     if not want_python and (insist or os.path.isfile(exe)):
         if not os.path.isfile(exe):
