@@ -73,11 +73,15 @@ class Set(object):
             truth[:, 5:] = d == 3
             labelled = has & ok
             truth &= labelled[:, None]
-        for s in np.unique(sub[sub >= 0]):             # new sub-batches, in order
-            sel = (sub == s) & ok
-            assert s == len(self.m1)
-            self.m1.append(int(bins[sel, 0].max(initial=0)))
-            self.m2.append(int(bins[sel, 1:5].max(initial=0)))
+        new = np.unique(sub[sub >= 0])                 # new sub-batches, in order
+        if new.size:
+            assert np.array_equal(new, len(self.m1) + np.arange(new.size))
+            sel = (sub >= 0) & ok
+            m1, m2 = np.zeros(new.size, np.int64), np.zeros(new.size, np.int64)
+            np.maximum.at(m1, sub[sel] - new[0], bins[sel, 0])
+            np.maximum.at(m2, sub[sel] - new[0], bins[sel, 1:5].max(axis=1))
+            self.m1 += [int(x) for x in m1]
+            self.m2 += [int(x) for x in m2]
         inside, edge = inside & ok[:, None], edge & ok[:, None]  # a rejected CTU counts nowhere
         self.bins = np.concatenate([self.bins, bins])
         self.inside, self.edge = np.concatenate([self.inside, inside]), np.concatenate([self.edge, edge])
