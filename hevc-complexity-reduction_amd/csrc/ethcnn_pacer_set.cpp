@@ -1,6 +1,7 @@
 // ethcnn_pacer_set.cpp -- host side of the pacer set (include/ethcnn.h "search budget, online: several sequences"): up to 32 slots, each
-// what a solo pacer (ethcnn_pacer.cpp) keeps per sequence, behind one ladder, one weight vector, one budget and one mode; a call over n
-// frames is k_pacer_table and k_pacer_bake_table (ethcnn_pacer_set.hip), two launches on the context's stream whatever n is.
+// what a solo pacer (ethcnn_pacer.cpp) keeps per sequence and bound to one of up to 32 POLICIES {ladder, weights, budget, mode}; a call over n
+// frames is k_pacer_table and k_pacer_bake_table (ethcnn_pacer_set.hip), two launches on the context's stream whatever n is and whatever
+// policies its slots have.  ethcnn_pacer_set_create makes a set of one policy bound to every slot.
 #include "ethcnn_analysis.h"
 #include "ethcnn_budget.h"
 #include "ethcnn_pacer_set.h"
@@ -11,12 +12,13 @@ using ethcnn::budget::kNout;
 struct ethcnn_pacer_set {
     ethcnn_ctx* c = nullptr;
     int nslots = 0;
-    int64_t K = 0;
-    uint64_t weight[4] = {};  // (set by ethcnn_pacer_set_create)
-    uint32_t budget_ppm = 0;
-    int mode = 0;
-    int* d_thr = nullptr;           // [K + 1][6]: the ladder, then the full search
-    unsigned* d_checked = nullptr;  // [nslots][K + 1][4]
+    int npolicies = 0;
+    PolicyRec policy[kPacerSetMaxPolicies] = {};  // (set by create; the device holds a copy)
+    int slot_policy[kPacerSetMax] = {};
+    int stride = 0;                 // the most rungs of any policy: rows of a slot's table
+    int* d_thr = nullptr;           // [sum of rungs][6]: every policy's ladder, then its full search
+    PolicyRec* d_policy = nullptr;  // [npolicies]
+    unsigned* d_checked = nullptr;  // [nslots][stride][4]
     unsigned* d_state = nullptr;    // [nslots][kStateWords]
     unsigned* d_recs = nullptr;     // record scratch of a call, 64 bytes a CTU
     int64_t cap_recs = 0;           // in CTUs
@@ -29,7 +31,7 @@ struct ethcnn_pacer_set {
 
 namespace {
 struct Checked {
-    int64_t per[kPacerSetMax];
+    int64_t per[kPacerSetMax], K[kPacerSetMax];
     PacerSetSeg seg[kPacerSetMax];
     int64_t total, count_grid, bake_grid;
 };
@@ -48,7 +50,10 @@ int check_call(ethcnn_pacer_set* p, const ethcnn_pacer_set_frame* f, int n, bool
         if (!f[j].probs || !f[j].baked) return set_err(c, ETHCNN_ERR_ARG, "frame %d: null probabilities or output buffer", j);
         if ((uintptr_t)f[j].probs % 4 || (uintptr_t)f[j].baked % 4 || (device && (uintptr_t)f[j].result % 4))
             return set_err(c, ETHCNN_ERR_ARG, "frame %d: a pointer is not 4-byte aligned", j);
-        if (int rc = check_frame(c, p->weight, f[j].width, f[j].height, &k->per[j])) return rc;
+        const PolicyRec& pr = p->policy[p->slot_policy[f[j].slot]];
+        const uint64_t weight[4] = {pr.weight[0], pr.weight[1], pr.weight[2], pr.weight[3]};
+        if (int rc = check_frame(c, weight, f[j].width, f[j].height, &k->per[j])) return rc;  // (the bound under the weights of ITS slot's policy)
+        k->K[j] = pr.rungs - 1;
     }
     // an output may be its own frame's input (in place); it may not touch another frame's input or output
     for (int i = 0; i < n; ++i)
@@ -59,7 +64,7 @@ int check_call(ethcnn_pacer_set* p, const ethcnn_pacer_set_frame* f, int n, bool
             if ((b < q + bytes && q < be) || (i < j && b < o + bytes && o < be))
                 return set_err(c, ETHCNN_ERR_ARG, "the output of frame %d overlaps a buffer of frame %d", i, j);
         }
-    if (pacer_set_layout(k->per, n, p->K, k->seg, &k->count_grid, &k->bake_grid))
+    if (pacer_set_layout_rungs(k->per, k->K, n, k->seg, &k->count_grid, &k->bake_grid))
         return set_err(c, ETHCNN_ERR_ARG, "ethcnn_pacer_set: no layout for these frames");  // (every rule was checked above)
     k->total = k->seg[n - 1].rec0 + k->per[n - 1];
     return 0;
@@ -72,27 +77,26 @@ int enqueue(ethcnn_pacer_set* p, const ethcnn_pacer_set_frame* f, int n, const C
     FrameTable t;
     BakeTable b;
     t.nseg = b.nseg = n;
-    t.rungs = (int)(p->K + 1);
-    t.rung_blocks = (t.rungs + kPacerSetThreads - 1) / kPacerSetThreads;
-    t.carry_mode = p->mode == ETHCNN_BUDGET_CARRY;
+    t.stride = p->stride;
+    t.policy = p->d_policy;
+    t.one = p->policy[0];
     t.thr = p->d_thr;
     t.checked = p->d_checked;
     t.state = p->d_state;
     t.recs = p->d_recs;
     t.h_result = p->h_result;
-    for (int d = 0; d < 4; ++d) t.weight[d] = p->weight[d];
-    t.budget_ppm = p->budget_ppm;
     b.recs = p->d_recs;
     b.state = p->d_state;
     for (int j = 0; j < n; ++j) {
         const PacerSetSeg& s = k.seg[j];
         t.seg[j] = TableSeg{f[j].probs, f[j].result, (long)s.rec0, f[j].width, f[j].height, (f[j].width + 63) / 64, (int)k.per[j],
-                            (int)s.count_first, (int)s.count_blocks, s.slice_len, f[j].slot};
+                            (int)s.count_first, (int)s.count_blocks, s.slice_len, f[j].slot, p->slot_policy[f[j].slot],
+                            (int)((k.K[j] + 1 + kPacerSetThreads - 1) / kPacerSetThreads)};
         b.seg[j] = BakeSeg{reinterpret_cast<unsigned*>(f[j].baked), (long)s.rec0, (int)k.per[j], (int)s.bake_first, f[j].slot, 0};
     }
     for (int j = n; j < kPacerSetMax; ++j) t.seg[j] = TableSeg{}, b.seg[j] = BakeSeg{};
     (void)hipGetLastError();
-    launch_table(c->stream, t, (unsigned)k.count_grid);
+    launch_table(c->stream, t, (unsigned)k.count_grid, p->npolicies > 1);
     launch_bake_table(c->stream, b, (unsigned)k.bake_grid);
     HIPCHK(c, hipGetLastError());
     p->launches += 2;
@@ -101,27 +105,64 @@ int enqueue(ethcnn_pacer_set* p, const ethcnn_pacer_set_frame* f, int n, const C
 }
 }  // namespace
 
-extern "C" int ethcnn_pacer_set_create(ethcnn_ctx* c, int nslots, const ethcnn_sim_thr* ladder, int64_t K, const uint64_t weight[4], uint32_t budget_ppm,
-                                       int mode, ethcnn_pacer_set** out) {
+// the rules of a policy list and of a binding; c may be NULL (the message then goes where ethcnn_last_error(NULL) reads)
+static int check_policies(ethcnn_ctx* c, const ethcnn_pacer_policy* policies, int npolicies, const int* slot_policy, int nslots) {
+    if (npolicies < 1 || npolicies > kPacerSetMaxPolicies) return set_err(c, ETHCNN_ERR_ARG, "ethcnn_pacer_set: %d policies (1..%d)", npolicies, kPacerSetMaxPolicies);
+    if (!policies) return set_err(c, ETHCNN_ERR_ARG, "ethcnn_pacer_set: null policies");
+    if (nslots < 0 || nslots > kPacerSetMax) return set_err(c, ETHCNN_ERR_ARG, "ethcnn_pacer_set: %d slots (1..%d)", nslots, kPacerSetMax);
+    for (int i = 0; i < npolicies; ++i) {
+        const ethcnn_pacer_policy& q = policies[i];
+        if (check_rules(c, q.ladder, q.K, q.weight, q.budget_ppm, q.mode)) {
+            const std::string why = ethcnn_last_error(c);
+            return set_err(c, ETHCNN_ERR_ARG, "policy %d: %s", i, why.c_str());
+        }
+    }
+    if (slot_policy)
+        for (int s = 0; s < nslots; ++s)
+            if (slot_policy[s] < 0 || slot_policy[s] >= npolicies)
+                return set_err(c, ETHCNN_ERR_ARG, "slot %d: policy %d is outside 0..%d", s, slot_policy[s], npolicies - 1);
+    return 0;
+}
+
+extern "C" int ethcnn_pacer_policies_check(const ethcnn_pacer_policy* policies, int npolicies, const int* slot_policy, int nslots) {
+    return check_policies(nullptr, policies, npolicies, slot_policy, nslots);
+}
+
+extern "C" int ethcnn_pacer_policies_create(ethcnn_ctx* c, int nslots, const ethcnn_pacer_policy* policies, int npolicies, const int* slot_policy,
+                                                ethcnn_pacer_set** out) {
     if (!c) return ETHCNN_ERR_ARG;
     if (!out) return set_err(c, ETHCNN_ERR_ARG, "ethcnn_pacer_set_create: null output");
     if (nslots < 1 || nslots > kPacerSetMax) return set_err(c, ETHCNN_ERR_ARG, "ethcnn_pacer_set_create: %d slots (1..%d)", nslots, kPacerSetMax);
-    if (int rc = check_rules(c, ladder, K, weight, budget_ppm, mode)) return rc;
-    const std::vector<int> rows = ladder_rows(ladder, K);
+    if (int rc = check_policies(c, policies, npolicies, slot_policy, nslots)) return rc;
     HIPCHK(c, hipSetDevice(c->device));
+    // every ladder with its full search appended, one after another; a record per policy
+    std::vector<int> rows;
     ethcnn_pacer_set* p = new ethcnn_pacer_set;
     p->c = c;
     p->nslots = nslots;
-    p->K = (int64_t)rows.size() / 6 - 1;
-    for (int d = 0; d < 4; ++d) p->weight[d] = (weight ? weight : sim::kDefaultWeight)[d];
-    p->budget_ppm = budget_ppm;
-    p->mode = mode;
-    const size_t n = rows.size() / 6, tables = (size_t)nslots * n * 16, states = (size_t)nslots * kStateWords * 4;
+    p->npolicies = npolicies;
+    for (int i = 0; i < npolicies; ++i) {
+        const ethcnn_pacer_policy& q = policies[i];
+        const std::vector<int> mine = ladder_rows(q.ladder, q.K);
+        PolicyRec& r = p->policy[i];
+        r.first_row = (int)(rows.size() / 6);
+        r.rungs = (int)(mine.size() / 6);
+        r.carry_mode = q.mode == ETHCNN_BUDGET_CARRY;
+        r.budget_ppm = q.budget_ppm;
+        for (int d = 0; d < 4; ++d) r.weight[d] = (q.weight ? q.weight : sim::kDefaultWeight)[d];
+        rows.insert(rows.end(), mine.begin(), mine.end());
+        p->stride = r.rungs > p->stride ? r.rungs : p->stride;
+    }
+    for (int s = 0; s < nslots; ++s) p->slot_policy[s] = slot_policy ? slot_policy[s] : 0;
+    const size_t n = rows.size() / 6, recs = (size_t)npolicies * sizeof(PolicyRec), tables = (size_t)nslots * p->stride * 16,
+                 states = (size_t)nslots * kStateWords * 4;
     hipError_t e = hipMalloc((void**)&p->d_thr, n * 24);
+    if (e == hipSuccess) e = hipMalloc((void**)&p->d_policy, recs);
     if (e == hipSuccess) e = hipMalloc((void**)&p->d_checked, tables);
     if (e == hipSuccess) e = hipMalloc((void**)&p->d_state, states);
     if (e == hipSuccess) e = hipHostMalloc((void**)&p->h_result, (size_t)nslots * sizeof(ethcnn_pacer_result), hipHostMallocDefault);
     if (e == hipSuccess) e = hipMemcpyAsync(p->d_thr, rows.data(), n * 24, hipMemcpyHostToDevice, c->stream);
+    if (e == hipSuccess) e = hipMemcpyAsync(p->d_policy, p->policy, recs, hipMemcpyHostToDevice, c->stream);
     if (e == hipSuccess) e = hipMemsetAsync(p->d_checked, 0, tables, c->stream);
     if (e == hipSuccess) e = hipMemsetAsync(p->d_state, 0, states, c->stream);
     if (e == hipSuccess) e = hipStreamSynchronize(c->stream);  // (rows is a temporary)
@@ -129,17 +170,28 @@ extern "C" int ethcnn_pacer_set_create(ethcnn_ctx* c, int nslots, const ethcnn_s
         (void)hipGetLastError();
         ethcnn_pacer_set_destroy(p);
         return set_err(c, e == hipErrorOutOfMemory ? ETHCNN_ERR_NOMEM : ETHCNN_ERR_DEVICE, "ethcnn_pacer_set_create: %s (%llu bytes of tables)", hipGetErrorString(e),
-                       (unsigned long long)(n * 24 + tables + states));
+                       (unsigned long long)(n * 24 + recs + tables + states));
     }
     std::memset(p->h_result, 0, (size_t)nslots * sizeof *p->h_result);
     *out = p;
     return ETHCNN_OK;
 }
 
+extern "C" int ethcnn_pacer_set_create(ethcnn_ctx* c, int nslots, const ethcnn_sim_thr* ladder, int64_t K, const uint64_t weight[4], uint32_t budget_ppm,
+                                       int mode, ethcnn_pacer_set** out) {
+    if (!c) return ETHCNN_ERR_ARG;
+    if (!out) return set_err(c, ETHCNN_ERR_ARG, "ethcnn_pacer_set_create: null output");
+    if (nslots < 1 || nslots > kPacerSetMax) return set_err(c, ETHCNN_ERR_ARG, "ethcnn_pacer_set_create: %d slots (1..%d)", nslots, kPacerSetMax);
+    if (int rc = check_rules(c, ladder, K, weight, budget_ppm, mode)) return rc;  // (its messages without a policy index, as before)
+    const ethcnn_pacer_policy one = {ladder, K, weight, budget_ppm, mode};
+    return ethcnn_pacer_policies_create(c, nslots, &one, 1, nullptr, out);
+}
+
 extern "C" void ethcnn_pacer_set_destroy(ethcnn_pacer_set* p) {
     if (!p) return;
     if (p->c && p->c->stream) (void)hipStreamSynchronize(p->c->stream);
     if (p->d_thr) (void)hipFree(p->d_thr);
+    if (p->d_policy) (void)hipFree(p->d_policy);
     if (p->d_checked) (void)hipFree(p->d_checked);
     if (p->d_state) (void)hipFree(p->d_state);
     if (p->d_recs) (void)hipFree(p->d_recs);
@@ -152,16 +204,39 @@ extern "C" int ethcnn_pacer_set_slots(const ethcnn_pacer_set* p) { return p ? p-
 
 extern "C" int64_t ethcnn_pacer_set_launches(const ethcnn_pacer_set* p) { return p ? p->launches : ETHCNN_ERR_ARG; }
 
-extern "C" int ethcnn_pacer_set_reset(ethcnn_pacer_set* p, int slot) {
+extern "C" int ethcnn_pacer_policies_count(const ethcnn_pacer_set* p) { return p ? p->npolicies : ETHCNN_ERR_ARG; }
+
+extern "C" int ethcnn_pacer_policies_of(const ethcnn_pacer_set* p, int slot) {
     if (!p) return ETHCNN_ERR_ARG;
+    if (slot < 0 || slot >= p->nslots) return set_err(p->c, ETHCNN_ERR_ARG, "ethcnn_pacer_policies_of: slot %d is outside 0..%d", slot, p->nslots - 1);
+    return p->slot_policy[slot];
+}
+
+// carry = 0, frame = 0 and an all-zero table of one slot, in stream order behind the frames already queued
+static int reset_slot(ethcnn_pacer_set* p, int slot) {
     ethcnn_ctx* c = p->c;
-    if (slot < 0 || slot >= p->nslots) return set_err(c, ETHCNN_ERR_ARG, "ethcnn_pacer_set_reset: slot %d is outside 0..%d", slot, p->nslots - 1);
     HIPCHK(c, hipSetDevice(c->device));
     c->done_armed = 0;
-    // stream-ordered behind the frames already queued; the slot's table and ticket are zero between calls anyway
+    // (the slot's table and ticket are zero between calls anyway; the whole stride, whatever policy the slot had)
     HIPCHK(c, hipMemsetAsync(p->d_state + (size_t)slot * kStateWords, 0, kStateWords * 4, c->stream));
-    HIPCHK(c, hipMemsetAsync(p->d_checked + (size_t)slot * (p->K + 1) * 4, 0, (size_t)(p->K + 1) * 16, c->stream));
+    HIPCHK(c, hipMemsetAsync(p->d_checked + (size_t)slot * p->stride * 4, 0, (size_t)p->stride * 16, c->stream));
     p->queued[slot] = 0;
+    return ETHCNN_OK;
+}
+
+extern "C" int ethcnn_pacer_set_reset(ethcnn_pacer_set* p, int slot) {
+    if (!p) return ETHCNN_ERR_ARG;
+    if (slot < 0 || slot >= p->nslots) return set_err(p->c, ETHCNN_ERR_ARG, "ethcnn_pacer_set_reset: slot %d is outside 0..%d", slot, p->nslots - 1);
+    return reset_slot(p, slot);
+}
+
+extern "C" int ethcnn_pacer_policies_bind(ethcnn_pacer_set* p, int slot, int policy) {
+    if (!p) return ETHCNN_ERR_ARG;
+    if (slot < 0 || slot >= p->nslots) return set_err(p->c, ETHCNN_ERR_ARG, "ethcnn_pacer_policies_bind: slot %d is outside 0..%d", slot, p->nslots - 1);
+    if (policy < 0 || policy >= p->npolicies) return set_err(p->c, ETHCNN_ERR_ARG, "ethcnn_pacer_policies_bind: policy %d is outside 0..%d", policy, p->npolicies - 1);
+    if (int rc = reset_slot(p, slot)) return rc;
+    // the frames already queued carry the old policy in their kernel argument: the binding is the host's, from the next call on
+    p->slot_policy[slot] = policy;
     return ETHCNN_OK;
 }
 

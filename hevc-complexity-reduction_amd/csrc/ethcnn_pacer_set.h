@@ -13,7 +13,17 @@
 //   k_pacer_bake_table  k_budget_bake (ethcnn_budget.h) over the same table: a block is 256 consecutive CTUs of ONE segment, a lane a CTU,
 //                       the thresholds are the row the slot's choice left in its state words.
 // Per slot, in HBM: the state words of ethcnn_pacer.h (unsigned [nslots][kStateWords]) and checked uint32 [nslots][rungs][4], both zero
-// between calls but for carry, frame count and the last picked row.  The ladder int [rungs][6] is shared.
+// between calls but for carry, frame count and the last picked row.
+//
+// POLICIES.  A set holds 1..kPacerSetMaxPolicies policies {ladder, weights, budget, mode}; every slot is bound to one of them.  In HBM,
+// written once at create: all ladders concatenated in one int [sum of rungs][6], each with its full-search row appended, and one
+// PolicyRec per policy.  A segment names its policy and its own rung_blocks = ceil(rungs of that policy / 256), so one launch mixes
+// segments of 1 and of 17 rung blocks: nblocks = slices x rung_blocks is the ticket target of THAT segment, the lane -> rung mapping, the
+// dead-lane clamp (rungs - 1 of that policy's rows), the choice loop, the weights, the allowance, the carry rule and the zeroing all
+// come from the policy record, which the block reads once (the index is block-uniform: scalar loads).  A set of ONE policy runs the
+// same kernel source in a second form that takes the record from the kernel argument instead, as before there were policies.  checked is
+// [nslots][stride][4] with stride = the most rungs of any policy, so that binding a slot to another policy reallocates nothing.  A set
+// made by ethcnn_pacer_set_create is a set of one policy bound to every slot.
 #pragma once
 #include <cstdint>
 
@@ -25,6 +35,8 @@
 namespace ethcnn {
 namespace pacer {
 
+constexpr int kPacerSetMaxPolicies = 32;  // ETHCNN_PACER_SET_MAX_POLICIES
+
 struct TableSeg {
     const float* probs;             // [per][21]
     ethcnn_pacer_result* d_result;  // may be NULL
@@ -34,20 +46,29 @@ struct TableSeg {
     int first_block, nblocks;       // of k_pacer_table
     int slice_len;                  // CTUs of a slice (the same under every rung block)
     int slot;
+    int policy;                     // of the slot when the call was made
+    int rung_blocks;                // ceil(rungs of that policy / 256)
+};
+
+struct PolicyRec {                  // 48 bytes
+    int first_row;                  // of its ladder in thr
+    int rungs;                      // K + 1
+    int carry_mode;                 // 1: ETHCNN_BUDGET_CARRY
+    unsigned budget_ppm;
+    unsigned long long weight[4];
 };
 
 struct FrameTable {
     TableSeg seg[kPacerSetMax];
     int nseg;
-    int rungs, rung_blocks;         // K + 1 and ceil(rungs / 256)
-    int carry_mode;                 // 1: ETHCNN_BUDGET_CARRY
-    const int* thr;                 // [rungs][6]
-    unsigned* checked;              // [nslots][rungs][4]
+    int stride;                     // rows of a slot's table: the most rungs of any policy
+    const PolicyRec* policy;        // [npolicies]
+    PolicyRec one;                  // policy 0 itself: what the kernel reads when the set holds no other (first_row = 0)
+    const int* thr;                 // [sum of rungs][6]: the ladders one after another
+    unsigned* checked;              // [nslots][stride][4]
     unsigned* state;                // [nslots][kStateWords]
     unsigned* recs;                 // scratch [sum of per][16]
     ethcnn_pacer_result* h_result;  // [nslots], page-locked
-    unsigned long long weight[4];
-    unsigned budget_ppm;
 };
 static_assert(sizeof(FrameTable) < 4096, "the frame table is a kernel argument");
 
@@ -68,7 +89,8 @@ struct BakeTable {
 };
 static_assert(sizeof(BakeTable) < 4096, "the bake table is a kernel argument");
 
-void launch_table(hipStream_t s, const FrameTable& t, unsigned blocks);
+// many: the set holds more than one policy (the kernel form that reads the policy table); else policy 0 from the argument
+void launch_table(hipStream_t s, const FrameTable& t, unsigned blocks, bool many);
 void launch_bake_table(hipStream_t s, const BakeTable& t, unsigned blocks);
 
 }  // namespace pacer

@@ -2,7 +2,9 @@
 // "search budget, online: several sequences").  k_pacer_table is k_pacer_frame (ethcnn_pacer.hip) over a table of frames, each with the
 // table, the ticket, the carry and the result slot of its own SLOT; k_pacer_bake_table is k_budget_bake (ethcnn_budget.hip) over the same
 // table, each frame under the row its slot's choice left behind.  The rule on a record is shared with k_decide, k_budget_* and
-// k_pacer_frame through ethcnn_node_masks.h.  Integers and bit masks only.
+// k_pacer_frame through ethcnn_node_masks.h.  Integers and bit masks only.  Ladder, weights, budget and mode are those of the POLICY the
+// segment's slot is bound to (ethcnn_pacer_set.h "POLICIES"): k_pacer_table<true> reads its record from the policy table in HBM,
+// k_pacer_table<false>, for a set of one policy, from the kernel argument.
 //
 // The packing arithmetic, the 64-bit state accessors and the bake arithmetic are RESTATED here rather than shared through a header with
 // ethcnn_pacer.hip and ethcnn_budget.hip: those two files compile to what they compiled to before this one existed.
@@ -71,6 +73,9 @@ __device__ __forceinline__ void store64(unsigned* p, u64 v) {
     __hip_atomic_store(p + 1, (unsigned)(v >> 32), PACER_AGENT);
 }
 
+// kMany: the set holds several policies and the segment's record is read from the policy table in HBM; otherwise the set's one policy
+// stands in the kernel argument, as ladder, weights, budget and mode did before there were policies, and the block loads nothing for it
+template <bool kMany>
 __global__ __launch_bounds__(kThreads) void k_pacer_table(const FrameTable tb) {
     __shared__ uint4 s_rec[kSliceCtus * 4];
     __shared__ float s_p[kSliceCtus * kNout];
@@ -84,8 +89,11 @@ __global__ __launch_bounds__(kThreads) void k_pacer_table(const FrameTable tb) {
     for (int i = 1; i < tb.nseg; ++i)
         if (tb.seg[i].first_block <= B) j = i;
     const TableSeg sg = tb.seg[j];
-    const int rungs = tb.rungs, rung_blocks = tb.rung_blocks;
-    unsigned* const checked = tb.checked + (long)sg.slot * rungs * 4;  // the slot's table, state words and result slot
+    // ---- the segment's policy: one record, read once (its index is block-uniform like the segment: scalar loads)
+    const PolicyRec pr = kMany ? tb.policy[sg.policy] : tb.one;
+    const int rungs = pr.rungs, rung_blocks = sg.rung_blocks;
+    const int* const thr = kMany ? tb.thr + (long)pr.first_row * 6 : tb.thr;  // its ladder: rows 0 .. rungs - 1 and no other
+    unsigned* const checked = tb.checked + (long)sg.slot * tb.stride * 4;  // the slot's table, state words and result slot
     unsigned* const state = tb.state + sg.slot * kStateWords;
     const int local = B - sg.first_block;                              // 0 .. nblocks - 1 of the segment
     const int slice = local / rung_blocks, rb = local - slice * rung_blocks;
@@ -118,7 +126,7 @@ __global__ __launch_bounds__(kThreads) void k_pacer_table(const FrameTable tb) {
     {
         const int c = (rb * kWaves + (t >> 6)) * 64 + (t & 63);
         const bool live = c < rungs;
-        const int* th = tb.thr + (long)(live ? c : rungs - 1) * 6;
+        const int* th = thr + (long)(live ? c : rungs - 1) * 6;  // a dead lane reads its OWN policy's last row, counts nothing
         const int up[3] = {th[0], th[1], th[2]}, down[3] = {th[3], th[4], th[5]};
         unsigned n64 = 0u, n32 = 0u, n16 = 0u, n8 = 0u;
         for (int i = 0; i < cur; ++i) {
@@ -166,12 +174,12 @@ __global__ __launch_bounds__(kThreads) void k_pacer_table(const FrameTable tb) {
         const unsigned* row = checked + (long)k * 4;
         u64 v = 0;
 #pragma unroll
-        for (int d = 0; d < 4; ++d) v += tb.weight[d] * (u64)__hip_atomic_load(row + d, PACER_AGENT);
+        for (int d = 0; d < 4; ++d) v += pr.weight[d] * (u64)__hip_atomic_load(row + d, PACER_AGENT);
         return v;
     };
     const u64 full = cost_of(K);
     const u128 carry_in = (u128)load64(state + kStateCarry) | (u128)load64(state + kStateCarry + 2) << 64;
-    const u128 allow = (u128)tb.budget_ppm * full + carry_in;
+    const u128 allow = (u128)pr.budget_ppm * full + carry_in;
     int fit = K, least = K;  // K: none
     u64 least_cost = ~0ull;
     for (int k = t; k < K; k += kThreads) {  // ascending k per lane: the first hit is the lane's smallest
@@ -199,7 +207,7 @@ __global__ __launch_bounds__(kThreads) void k_pacer_table(const FrameTable tb) {
         const bool over = fit == K;
         const int at = over ? least : fit;
         const u64 cost = cost_of(at);
-        const u128 carry = tb.carry_mode && !over ? allow - (u128)cost * 1000000u : (u128)0;
+        const u128 carry = pr.carry_mode && !over ? allow - (u128)cost * 1000000u : (u128)0;
         const u64 frame = load64(state + kStateFrame);
         store64(state + kStateFrame, frame + 1);
         store64(state + kStateCarry, (u64)carry);
@@ -212,7 +220,7 @@ __global__ __launch_bounds__(kThreads) void k_pacer_table(const FrameTable tb) {
         res.full = full;
         res.carry_lo = (u64)carry;
         res.carry_hi = (u64)(carry >> 64);
-        const int* th = tb.thr + (long)at * 6;
+        const int* th = thr + (long)at * 6;
 #pragma unroll
         for (int l = 0; l < 3; ++l) res.up_k[l] = th[l], res.down_k[l] = th[3 + l];
 #pragma unroll
@@ -266,7 +274,10 @@ __global__ __launch_bounds__(kThreads) void k_pacer_bake_table(const BakeTable t
 }
 }  // namespace
 
-void launch_table(hipStream_t s, const FrameTable& t, unsigned blocks) { k_pacer_table<<<blocks, kThreads, 0, s>>>(t); }
+void launch_table(hipStream_t s, const FrameTable& t, unsigned blocks, bool many) {
+    if (many) k_pacer_table<true><<<blocks, kThreads, 0, s>>>(t);
+    else k_pacer_table<false><<<blocks, kThreads, 0, s>>>(t);
+}
 
 void launch_bake_table(hipStream_t s, const BakeTable& t, unsigned blocks) { k_pacer_bake_table<<<blocks, kThreads, 0, s>>>(t); }
 

@@ -19,3 +19,6 @@ struct PacerSetSeg {
 // n frames of nctus[j] CTUs under K + 1 rungs, in call order -> seg[n] and both grid sizes.  0, or ETHCNN_ERR_ARG (n outside 1..32, a
 // frame of no or of 2^24 or more CTUs, K outside 1..4096) with nothing written.
 int pacer_set_layout(const int64_t* nctus, int n, int64_t K, PacerSetSeg* seg, int64_t* count_grid, int64_t* bake_grid);
+// the same with rungs of its own per frame: frame j under K[j] + 1 rungs (the ladder of its slot's policy), so that a frame's count blocks
+// are slices x ceil((K[j] + 1) / 256).  Refuses per frame what pacer_set_layout refuses, and a NULL K.
+int pacer_set_layout_rungs(const int64_t* nctus, const int64_t* K, int n, PacerSetSeg* seg, int64_t* count_grid, int64_t* bake_grid);

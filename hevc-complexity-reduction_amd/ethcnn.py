@@ -334,6 +334,12 @@ SIGNATURES = {
     "ethcnn_pacer_set_frames": (_i, [_vp, _vp, _i]),
     "ethcnn_pacer_set_last": (_i, [_vp, _i, _vp]),
     "ethcnn_pacer_set_plan": (_i, [_vp, _i, ctypes.c_int64, _vp, _vp, _vp, _vp, _vp, _vp, _vp]),
+    "ethcnn_pacer_policies_check": (_i, [_vp, _i, _vp, _i]),
+    "ethcnn_pacer_policies_create": (_i, [_vp, _i, _vp, _i, _vp, ctypes.POINTER(_vp)]),
+    "ethcnn_pacer_policies_count": (_i, [_vp]),
+    "ethcnn_pacer_policies_of": (_i, [_vp, _i]),
+    "ethcnn_pacer_policies_bind": (_i, [_vp, _i, _i]),
+    "ethcnn_pacer_policies_plan": (_i, [_vp, _vp, _i, _vp, _vp, _vp, _vp, _vp, _vp, _vp]),
     "ethcnn_ladder_check": (_i, [_vp, _i, ctypes.c_int64, ctypes.c_uint32]),
     "ethcnn_ladder_build": (_i, [_vp, _vp, _i, ctypes.c_int64, ctypes.c_uint32, _vp, _vp]),
     "ethcnn_ladder_thin": (_i, [_vp, ctypes.c_int64, ctypes.c_int64, _vp, _vp]),
@@ -2804,18 +2810,68 @@ class PacerSetFrame(ctypes.Structure):
                 ("result", ctypes.c_void_p)]
 
 
+PACER_SET_MAX_POLICIES = 32
+
+
+class PacerPolicy(ctypes.Structure):
+    """ethcnn_pacer_policy"""
+    _fields_ = [("ladder", ctypes.c_void_p), ("K", ctypes.c_int64), ("weight", ctypes.c_void_p), ("budget_ppm", ctypes.c_uint32), ("mode", ctypes.c_int32)]
+
+
+def _pacer_policies(policies, ppm=_budget_ppm, mode=_budget_mode):
+    """dicts {budget, mode, ladder, weights} (mode "frame", ladder None and weights None by default) -> (a C array of ethcnn_pacer_policy,
+    the arrays its pointers point into); ppm and mode turn a dict's budget and mode into the numbers of the C struct"""
+    arr = (PacerPolicy * max(len(policies), 1))()
+    keep = []
+    for i, q in enumerate(policies[:len(arr)]):
+        extra = set(q) - {"budget", "mode", "ladder", "weights"}
+        if extra:
+            raise ValueError("policy %d: unknown keys %s" % (i, sorted(extra)))
+        lad = None if q.get("ladder") is None else _sim_cands(q["ladder"])
+        w = None if q.get("weights") is None else (ctypes.c_uint64 * 4)(*[int(x) for x in q["weights"]])
+        keep += [lad, w]
+        arr[i] = PacerPolicy(None if lad is None else lad.ctypes.data, 0 if lad is None else lad.size, None if w is None else ctypes.addressof(w),
+                             ppm(q["budget"]), mode(q.get("mode", "frame")))
+    return arr, keep
+
+
+def _slot_policy(slot_policy):
+    return None if slot_policy is None else (ctypes.c_int * max(len(slot_policy), 1))(*[int(x) for x in slot_policy])
+
+
+def pacer_set_check_policies(policies, slot_policy=None, raw=False, lib=None):
+    """ethcnn_pacer_policies_check (host only): the rules of a PacerSet's policies -- dicts {budget (a share 0..1), mode, ladder,
+    weights} -- and of slot_policy, a policy index per slot (None: none to check); EthCnnError with the policy index in the message
+    where the library says ETHCNN_ERR_ARG.  raw: budget is in parts per million and mode a number, both passed on as they are"""
+    lib = lib or load_library()
+    arr, keep = _pacer_policies(policies, int, int) if raw else _pacer_policies(policies)
+    sp = _slot_policy(slot_policy)
+    rc = lib.ethcnn_pacer_policies_check(arr if len(policies) else None, len(policies), sp, 0 if slot_policy is None else len(slot_policy))
+    if rc:
+        raise EthCnnError(rc, lib.ethcnn_last_error(None).decode())
+
+
 def pacer_set_plan(nctus, K=512, lib=None):
     """ethcnn_pacer_set_plan (host only): the layout of a PacerSet call over frames of these CTU counts, in this order, under K + 1 rungs
     -> {"count_first", "count_blocks", "slice_len", "bake_first", "rec0": one entry per frame, "count_grid", "bake_grid"}; EthCnnError
-    for bad arguments"""
+    for bad arguments.  K may be a list, one entry per frame (ethcnn_pacer_policies_plan): frame j under K[j] + 1 rungs, those of the
+    policy its slot is bound to"""
     lib = lib or load_library()
     n = len(nctus)
     counts = np.array([min(max(int(x), -1), 2 ** 62) for x in nctus], np.int64)
     out = {k: np.zeros(max(n, 1), np.int32 if k == "slice_len" else np.int64) for k in ("count_first", "count_blocks", "slice_len", "bake_first", "rec0")}
     grids = np.zeros(2, np.int64)
-    rc = lib.ethcnn_pacer_set_plan(counts.ctypes.data if n else None, n, _int_arg(K, -1, 2 ** 63 - 1), out["count_first"].ctypes.data,
-                                   out["count_blocks"].ctypes.data, out["slice_len"].ctypes.data, out["bake_first"].ctypes.data, out["rec0"].ctypes.data,
-                                   grids.ctypes.data, grids.ctypes.data + 8)
+    if isinstance(K, (list, tuple, np.ndarray)):
+        if len(K) != n:
+            raise ValueError("%d frames and %d entries of K" % (n, len(K)))
+        each = np.array([_int_arg(x, -1, 2 ** 63 - 1) for x in K], np.int64)
+        rc = lib.ethcnn_pacer_policies_plan(counts.ctypes.data if n else None, each.ctypes.data if n else None, n, out["count_first"].ctypes.data,
+                                             out["count_blocks"].ctypes.data, out["slice_len"].ctypes.data, out["bake_first"].ctypes.data,
+                                             out["rec0"].ctypes.data, grids.ctypes.data, grids.ctypes.data + 8)
+    else:
+        rc = lib.ethcnn_pacer_set_plan(counts.ctypes.data if n else None, n, _int_arg(K, -1, 2 ** 63 - 1), out["count_first"].ctypes.data,
+                                       out["count_blocks"].ctypes.data, out["slice_len"].ctypes.data, out["bake_first"].ctypes.data, out["rec0"].ctypes.data,
+                                       grids.ctypes.data, grids.ctypes.data + 8)
     if rc:
         raise EthCnnError(rc, "ethcnn_pacer_set_plan: bad arguments")
     res = {k: [int(x) for x in v[:n]] for k, v in out.items()}
@@ -2826,15 +2882,30 @@ def pacer_set_plan(nctus, K=512, lib=None):
 class PacerSet(object):
     """Up to 32 paced sequences behind one ladder, one weight vector, one budget (a share 0..1) and one mode (include/ethcnn.h "search
     budget, online: several sequences"): a slot owns the carry, the frame count and the result of one sequence, a call paces any subset
-    of the slots by one frame each in two launches on the context's stream.  Slot by slot the results and the baked rows are a Pacer's."""
+    of the slots by one frame each in two launches on the context's stream.  Slot by slot the results and the baked rows are a Pacer's.
+    PacerSet(ctx, nslots, policies=[{budget, mode, ladder, weights}, ...], slot_policy=None) holds up to 32 policies instead of one:
+    slot s is bound to policies[slot_policy[s]] (None: all to the first) until bind(s, policy), and is a Pacer of that policy."""
 
-    def __init__(self, ctx, nslots, budget, mode="frame", ladder=None, weights=None):
+    def __init__(self, ctx, nslots, budget=None, mode="frame", ladder=None, weights=None, policies=None, slot_policy=None):
         self.ctx, self.lib = ctx, ctx.lib
-        lad = None if ladder is None else _sim_cands(ladder)
-        w = None if weights is None else (ctypes.c_uint64 * 4)(*[int(x) for x in weights])
         h = ctypes.c_void_p()
-        ctx._chk(self.lib.ethcnn_pacer_set_create(ctx.h, int(nslots), None if lad is None else lad.ctypes.data, 0 if lad is None else lad.size, w,
-                                                  _budget_ppm(budget), _budget_mode(mode), ctypes.byref(h)))
+        if policies is not None:
+            if budget is not None or ladder is not None or weights is not None or mode != "frame":
+                raise ValueError("a PacerSet takes either one budget, mode, ladder and weights or a list of policies")
+            if slot_policy is not None and len(slot_policy) != int(nslots):
+                raise ValueError("slot_policy has %d entries for %d slots" % (len(slot_policy), int(nslots)))
+            arr, keep = _pacer_policies(list(policies))
+            ctx._chk(self.lib.ethcnn_pacer_policies_create(ctx.h, int(nslots), arr if len(policies) else None, len(policies), _slot_policy(slot_policy),
+                                                               ctypes.byref(h)))
+        else:
+            if budget is None:
+                raise TypeError("a PacerSet needs a budget or a list of policies")
+            if slot_policy is not None:
+                raise ValueError("slot_policy belongs to a list of policies")
+            lad = None if ladder is None else _sim_cands(ladder)
+            w = None if weights is None else (ctypes.c_uint64 * 4)(*[int(x) for x in weights])
+            ctx._chk(self.lib.ethcnn_pacer_set_create(ctx.h, int(nslots), None if lad is None else lad.ctypes.data, 0 if lad is None else lad.size, w,
+                                                      _budget_ppm(budget), _budget_mode(mode), ctypes.byref(h)))
         self.h = h
         if not hasattr(ctx, "_trainers"):
             ctx._trainers = weakref.WeakSet()
@@ -2876,6 +2947,22 @@ class PacerSet(object):
     def reset(self, slot):
         """carry = 0, frame = 0 of that slot (in stream order behind the frames already queued)"""
         self._chk(self.lib.ethcnn_pacer_set_reset(self._handle(), int(slot)))
+
+    @property
+    def npolicies(self):
+        return max(0, int(self.lib.ethcnn_pacer_policies_count(self._handle())))
+
+    def policy_of(self, slot):
+        """the index of the policy that slot is bound to"""
+        rc = int(self.lib.ethcnn_pacer_policies_of(self._handle(), int(slot)))
+        if rc < 0:
+            self._chk(rc)
+        return rc
+
+    def bind(self, slot, policy):
+        """reset(slot), and from the next call on that slot is paced under policies[policy] (in stream order behind the frames already
+        queued, which keep the policy they were queued under); binding to the policy the slot has is a reset"""
+        self._chk(self.lib.ethcnn_pacer_policies_bind(self._handle(), int(slot), int(policy)))
 
     def frames_device(self, frames):
         """asynchronous on the context's stream (ethcnn_pacer_set_frames_device).  frames: one dict per frame with slot, d_probs, width,

@@ -38,7 +38,13 @@ step + heads + gates on the GPU).  Differences from the reference, none in the n
   * --sessions DIR [DIR ...] serves several working directories from one context (serve_many); there the budget is given on the command
     line, --budget SHARE [--budget-mode frame|carry] [--budget-weights "64 16 4 1"] [--budget-ladder FILE], under the value rules above,
     and is held for every directory by ONE pacer set (ethcnn.PacerSet): a directory's session is its slot, a round of directories is one
-    call behind the round's step.  One policy for all directories; the environment variables stay refused under --sessions.
+    call behind the round's step.  The environment variables stay refused under --sessions.
+  * --sessions ... --budget-policies FILE gives every directory a policy of its own; the --budget options, if any, are the default
+    policy.  One policy per line, `#` starts a comment: SELECTOR SHARE [MODE [LADDER|- [W64 W32 W16 W8]]] with SELECTOR dir=PATH,
+    qp=LO..HI (inclusive) or *; ladder files in Low-Delay-P token order, `-` the default ladder.  Where a directory's slot would be reset
+    (i_frame <= 1 or another picture size) it is bound instead: to the first dir= line whose realpath is the directory's, else the first
+    qp= line that holds the QP of that frame, else the first *, else --budget.  The binding holds until the next start.  Refused at
+    start-up (status 1, nothing written, no GPU touched): what check_policies lists.
 """
 from __future__ import print_function
 
@@ -366,6 +372,28 @@ def check_pace(workdirs, share, mode=None, weights=None, ladder=None):
     return budget + (rungs,)
 
 
+def check_policies(workdirs, path, pace=None):
+    """What `--sessions ... --budget-policies FILE` refuses at start-up beyond check_sessions (and check_pace, which gave `pace`, the
+    default policy of the --budget options, or None), as ValueError, before a GPU is touched and with nothing written: a file that
+    cannot be read or is malformed, a value search_budget refuses, `auto` as a ladder, a dir= line that names no directory of the server
+    or one a second time, more than 32 policies, a directory that could be left without a policy, a rule of the library's own
+    (ethcnn_pacer_policies_check), and a Thr_info.txt that is not the companion line -> search_budget.Policies"""
+    name = _sb.POLICIES_OPTION
+    policies = _sb.Policies(_sb.read_policies(path, 'ldp', auto=NO_AUTO_LADDER), workdirs, pace)
+    try:
+        _e.pacer_set_check_policies(_policy_dicts(policies.policies))
+    except _e.EthCnnError as err:
+        raise ValueError('%s: %s' % (name, err))
+    for d in workdirs:
+        _sb.check_companion_thr_file(os.path.join(d, THR_FILE), _sb.COMPANION_LINE_LDP, name)
+    return policies
+
+
+def _policy_dicts(policies):
+    """search_budget's (share, mode, weights, ladder) tuples as ethcnn.PacerSet takes them"""
+    return [{'budget': p[0], 'mode': p[1], 'weights': p[2], 'ladder': None if p[3] is None else _e.sim_thr(*p[3])} for p in policies]
+
+
 class _BundlePlace(object):
     """bundle i of an LdpSessions object behind the two loaders restore_lstm calls"""
 
@@ -388,6 +416,7 @@ class _Dir(object):
         self.last_key, self.state_sig = None, None
         self.pinned, self.pinned_probs = None, None
         self.paced_geom, self.paced = None, [0, 0, 0, 0]   # as serve's: frames, over budget, sum of cost, sum of full
+        self.policy = None   # under --budget-policies: the (share, mode, weights, ladder) its slot is bound to
 
     def p(self, name):
         return os.path.join(self.workdir, name)
@@ -400,21 +429,27 @@ def _host_buffer_again(ctx, old, nbytes):
     return ctx.host_buffer(nbytes)
 
 
-def serve_many(workdirs, max_frames=None, idle_timeout=None, poll_s=2e-4, device=0, verbose=True, accept_stale=False, pace=None):
+def serve_many(workdirs, max_frames=None, idle_timeout=None, poll_s=2e-4, device=0, verbose=True, accept_stale=False, pace=None, policies=None):
     """One server for several HM working directories: one context, one LdpSessions object, the unchanged file handshake per directory.
     A poll round takes every directory with pred_start.sig and a complete command.dat, reads their resi.yuv, advances all of them
     in ONE step, writes cu_depth.dat and pred_end.sig per directory and then refreshes every served state.dat and its sidecar.  State
     continuity per directory is serve's rule.  max_frames and idle_timeout count over all directories.  Returns the frames predicted.
     pace: what check_pace returned, or None.  With it the gates are open and one PacerSet holds the search of every directory under that
     share: a directory's session id is its slot, and behind each step ONE call paces the round's frames in place in their page-locked
-    buffers before the files are written.  A directory's slot is reset where serve resets its pacer."""
+    buffers before the files are written.  A directory's slot is reset where serve resets its pacer.
+    policies: what check_policies returned, or None.  With it the set holds every policy of the file (and `pace` as the default one), and
+    where a directory's slot would be reset it is BOUND to the policy of that directory and of the QP of the frame that starts the
+    allowance; the binding holds until the next start."""
     check_sessions(workdirs)
     dirs = [_Dir(d) for d in workdirs]
     ctx = _e.EthCnn(device=device)
     sessions = pacer = None
     try:
         ctx.load_thresholds(dirs[0].p(THR_FILE))   # (the gates check_sessions compared)
-        if pace is not None:
+        if policies is not None:
+            ctx.set_thresholds(0.0, 0.0)    # open gates, as below
+            pacer = _e.PacerSet(ctx, MAX_SESSIONS, policies=_policy_dicts(policies.policies))
+        elif pace is not None:
             ctx.set_thresholds(0.0, 0.0)    # open gates, whatever Thr_info.txt says: the baked files are what the encoders read
             pacer = _e.PacerSet(ctx, MAX_SESSIONS, pace[0], pace[1], ladder=None if pace[3] is None else _e.sim_thr(*pace[3]), weights=pace[2])
         restore_cnn(ctx, workdirs[0])
@@ -477,16 +512,21 @@ def serve_many(workdirs, max_frames=None, idle_timeout=None, poll_s=2e-4, device
             if pacer is not None:   # (only once the step has succeeded: a frame is never paced twice)
                 for d, (i_frame, w, h, qp) in ready:
                     if i_frame <= 1 or d.paced_geom != (w, h):
-                        pacer.reset(d.session)   # a new sequence starts with a new allowance, as it starts with a zero LSTM state
+                        if policies is None:
+                            pacer.reset(d.session)   # a new sequence starts with a new allowance, as it starts with a zero LSTM state
+                        else:   # ... and under the policy of this directory and of the QP it starts with, until the next start
+                            d.policy = policies.policies[policies.of(d.workdir, qp)]
+                            pacer.bind(d.session, policies.of(d.workdir, qp))
                         d.paced_geom = (w, h)
                 depths, results = pacer.frames([{'slot': d.session, 'probs': depth, 'width': w, 'height': h, 'out': depth}   # page-locked, in place
                                                 for depth, (d, (i_frame, w, h, qp)) in zip(depths, ready)])
                 for res, (d, (i_frame, w, h, qp)) in zip(results, ready):
                     d.paced = [d.paced[0] + 1, d.paced[1] + int(res['over']), d.paced[2] + int(res['cost']), d.paced[3] + int(res['full'])]
                     if verbose:
-                        print('%s: frame %d: rung %d, %.6f of the full search%s' % (d.workdir, i_frame, int(res['rung']),
-                                                                                   int(res['cost']) / float(int(res['full']) or 1),
-                                                                                   ', over budget' if res['over'] else ''))
+                        print('%s: frame %d: rung %d, %.6f of the full search%s%s' % (d.workdir, i_frame, int(res['rung']),
+                                                                                     int(res['cost']) / float(int(res['full']) or 1),
+                                                                                     ', over budget' if res['over'] else '',
+                                                                                     ' (budget %g, %s)' % d.policy[:2] if d.policy else ''))
             # what the encoders wait for first, for every directory; the state files afterwards, while they are encoding
             late = [save_cu_depth(depth, d.p(SAVE_FILE), d.p(STATE_FILE), d.p(END_FILE), _e.ctus_per_frame(w, h), (i_frame, w, h))
                     for depth, (d, (i_frame, w, h, qp)) in zip(depths, ready)]
@@ -502,7 +542,7 @@ def serve_many(workdirs, max_frames=None, idle_timeout=None, poll_s=2e-4, device
         for d in dirs:
             if d.paced[0]:
                 sys.stderr.write('resi_to_cu_depth_LDP: %s: search budget %g (%s): %.6f of the full search over %d frames, %d over budget\n'
-                                 % (d.workdir, pace[0], pace[1], d.paced[2] / float(d.paced[3] or 1), d.paced[0], d.paced[1]))
+                                 % (d.workdir, (d.policy or pace)[0], (d.policy or pace)[1], d.paced[2] / float(d.paced[3] or 1), d.paced[0], d.paced[1]))
         if pacer is not None:
             pacer.close()
         if sessions is not None:
@@ -512,18 +552,20 @@ def serve_many(workdirs, max_frames=None, idle_timeout=None, poll_s=2e-4, device
 
 USAGE = ('usage: resi_to_cu_depth_LDP.py [--max-frames N] [--idle-timeout S] [--accept-stale]\n'
          '       resi_to_cu_depth_LDP.py --sessions DIR [DIR ...] [--max-frames N] [--idle-timeout S] [--accept-stale] [--quiet]\n'
-         '                               [--budget SHARE [--budget-mode frame|carry] [--budget-weights "W64 W32 W16 W8"] [--budget-ladder FILE]]\n')
+         '                               [--budget SHARE [--budget-mode frame|carry] [--budget-weights "W64 W32 W16 W8"] [--budget-ladder FILE]]\n'
+         '                               [--budget-policies FILE]\n')
 
 
 def main(argv):
     """`python resi_to_cu_depth_LDP.py` in HM-LDP's bin/ (no arguments, like the reference);
     optional: --max-frames N, --idle-timeout SECONDS; --sessions DIR [DIR ...]: one server for several working directories, and behind
     it only --budget SHARE [--budget-mode M] [--budget-weights "W64 W32 W16 W8"] [--budget-ladder FILE]: the search budget of all of them,
-    and --quiet."""
+    --budget-policies FILE: a policy per directory (the --budget options are then the default policy), and --quiet."""
     max_frames = idle = None
     accept_stale = quiet = False
     workdirs = None
     options = {}   # --budget, --budget-mode, --budget-weights, --budget-ladder -> their texts
+    policy_file = None
     args = list(argv[1:])
     while args:
         a = args.pop(0)
@@ -539,25 +581,29 @@ def main(argv):
                 workdirs.append(args.pop(0))
         elif a in _sb.OPTION_NAMES and a not in options and args:
             options[a] = args.pop(0)
+        elif a == _sb.POLICIES_OPTION and policy_file is None and args:
+            policy_file = args.pop(0)
         elif a == '--quiet':
             quiet = True
         else:
             sys.stderr.write(USAGE)
             return 2
-    if (options or quiet) and workdirs is None or (options and _sb.OPTION_NAMES[0] not in options):
+    if (options or quiet or policy_file is not None) and workdirs is None or (options and _sb.OPTION_NAMES[0] not in options):
         sys.stderr.write(USAGE)   # the budget options belong to --sessions, and the three others to --budget
         return 2
     if workdirs is not None:
-        pace = None
+        pace = policies = None
         try:
             check_sessions(workdirs)
             if options:
                 pace = check_pace(workdirs, *[options.get(n) for n in _sb.OPTION_NAMES])
+            if policy_file is not None:
+                policies = check_policies(workdirs, policy_file, pace)
         except ValueError as err:
             sys.stderr.write('resi_to_cu_depth_LDP: %s\n' % err)
             return 1
         try:
-            serve_many(workdirs, max_frames=max_frames, idle_timeout=idle, accept_stale=accept_stale, verbose=not quiet, pace=pace)
+            serve_many(workdirs, max_frames=max_frames, idle_timeout=idle, accept_stale=accept_stale, verbose=not quiet, pace=pace, policies=policies)
         except StaleStateError:
             return 1
         return 0

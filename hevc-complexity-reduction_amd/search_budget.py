@@ -112,6 +112,98 @@ def ladder_from_env(order, auto=None):
     return ladder_from_path(os.environ.get(ENV_NAMES[3]), order, auto)
 
 
+MAX_POLICIES = 32                                      # ETHCNN_PACER_SET_MAX_POLICIES
+POLICIES_OPTION = '--budget-policies'
+
+
+def read_policies(path, order, auto=None, name=POLICIES_OPTION):
+    """a policy file of `--sessions ... --budget-policies`: one policy per line, `#` starts a comment, whitespace-separated fields
+    SELECTOR SHARE [MODE [LADDER|- [W64 W32 W16 W8]]].  SELECTOR is dir=PATH, qp=LO..HI (inclusive) or *; SHARE, MODE and the weights are
+    under from_values' rules, LADDER is a ladder file in the token order `order` (`-`: the default ladder; `auto` is refused with the
+    reason `auto`) -> one (selector, (share, mode, weights or None, ladder or None)) per line, selector one of ('dir', realpath),
+    ('qp', lo, hi), ('*',); ValueError names the file and the line"""
+    try:
+        lines = open(path).read().splitlines()
+    except (OSError, UnicodeDecodeError) as err:
+        raise ValueError("%s='%s' cannot be read: %s" % (name, path, getattr(err, 'strerror', None) or err))
+    out = []
+    for no, line in enumerate(lines, 1):
+        tok = line.split('#', 1)[0].split()
+        if not tok:
+            continue
+        at = '%s, line %d' % (path, no)
+        if len(tok) not in (2, 3, 4, 8):
+            raise ValueError("%s: %s: a policy is SELECTOR SHARE [MODE [LADDER|- [W64 W32 W16 W8]]], got %d fields" % (name, at, len(tok)))
+        sel = tok[0]
+        if sel == '*':
+            selector = ('*',)
+        elif sel.startswith('dir=') and len(sel) > 4:
+            selector = ('dir', os.path.realpath(sel[4:]))
+        elif sel.startswith('qp='):
+            try:
+                lo, hi = [int(t) for t in sel[3:].split('..')]
+            except ValueError:
+                raise ValueError("%s: %s: '%s' is not qp=LO..HI" % (name, at, sel))
+            if lo > hi:
+                raise ValueError("%s: %s: '%s' is an empty range (LO > HI)" % (name, at, sel))
+            selector = ('qp', lo, hi)
+        else:
+            raise ValueError("%s: %s: the selector '%s' is none of dir=PATH, qp=LO..HI and *" % (name, at, sel))
+        try:
+            budget = from_values(tok[1], tok[2] if len(tok) > 2 else None, ' '.join(tok[4:]) if len(tok) > 4 else None,
+                                 (at + ': SHARE', at + ': MODE', at + ': W64 W32 W16 W8'))
+            ladder = ladder_from_path(tok[3] if len(tok) > 3 and tok[3] != '-' else None, order, auto, at + ': LADDER')
+        except ValueError as err:
+            raise ValueError('%s: %s' % (name, err))
+        out.append((selector, budget + (ladder,)))
+    return out
+
+
+class Policies(object):
+    """the policies of one server and the rule that gives a directory its own.  policies: (share, mode, weights or None, ladder or
+    None) each, the lines of the file in file order and then the default of the --budget options, if there is one; at most
+    MAX_POLICIES.  of(directory, qp) is the index of the first match in this order: the first dir= line whose realpath is the
+    directory's, else the first qp= line that holds qp, else the first * line, else the --budget default."""
+
+    def __init__(self, lines, workdirs, default=None, name=POLICIES_OPTION):
+        """lines: what read_policies returned; ValueError for a dir= line that names none of `workdirs` or a directory a second time, for
+        more than MAX_POLICIES policies, and for a directory that may be left without a policy"""
+        self.policies = [p for _, p in lines] + ([default] if default is not None else [])
+        if not self.policies:
+            raise ValueError('%s: the file holds no policy and there is no --budget' % name)
+        if len(self.policies) > MAX_POLICIES:
+            raise ValueError('%s: %d policies%s, one server holds at most %d' % (name, len(self.policies), ', the --budget default among them' if default is not None else '',
+                                                                                MAX_POLICIES))
+        real = [os.path.realpath(d) for d in workdirs]
+        self.by_dir, self.by_qp, self.fallback = {}, [], None
+        for i, (sel, _) in enumerate(lines):
+            if sel[0] == 'dir':
+                if sel[1] not in real:
+                    raise ValueError('%s: dir=%s names none of the --sessions directories' % (name, sel[1]))
+                if sel[1] in self.by_dir:
+                    raise ValueError('%s: two dir= lines for %s' % (name, sel[1]))
+                self.by_dir[sel[1]] = i
+            elif sel[0] == 'qp':
+                self.by_qp.append((sel[1], sel[2], i))
+            elif self.fallback is None:
+                self.fallback = i
+        if self.fallback is None and default is not None:
+            self.fallback = len(self.policies) - 1
+        if self.fallback is None:
+            bare = [d for d, r in zip(workdirs, real) if r not in self.by_dir]
+            if bare:
+                raise ValueError('%s: %s has no dir= line and there is no default (a * line or --budget)' % (name, bare[0]))
+
+    def of(self, directory, qp):
+        real = os.path.realpath(directory)
+        if real in self.by_dir:
+            return self.by_dir[real]
+        for lo, hi, i in self.by_qp:
+            if lo <= qp <= hi:
+                return i
+        return self.fallback   # (never None for a directory of the server: __init__ refused that)
+
+
 def reliability_from_env(read):
     """None when ETHCNN_SEARCH_BUDGET_RELIABILITY is unset or empty (the identity table), else read(path) -- the binding's risk_read,
     host only; ValueError names a file that cannot be read or is no reliability table"""

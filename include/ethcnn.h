@@ -1430,6 +1430,52 @@ int ethcnn_pacer_set_last (ethcnn_pacer_set* set, int slot, ethcnn_pacer_result*
 int ethcnn_pacer_set_plan (const int64_t* nctus, int n, int64_t K, int64_t* count_first_out, int64_t* count_blocks_out, int32_t* slice_len_out,
                            int64_t* bake_first_out, int64_t* rec0_out, int64_t* count_grid_out, int64_t* bake_grid_out);
 
+/* ---- search budget, online: several sequences, a POLICY per slot.  A policy is {ladder, K, weight[4], budget_ppm, mode} under the rules
+ *      of ethcnn_pacer_check, unchanged (ladder NULL: the default ladder, K is not read; weight NULL: 64 16 4 1).  A set holds
+ *      1..ETHCNN_PACER_SET_MAX_POLICIES of them and every slot is BOUND to one: a four-QP evaluation paces each directory under the
+ *      ladder of its own model, a complexity-control curve runs four budgets through one set.  The eight entries above stay as they
+ *      are; a set made by ethcnn_pacer_set_create is a set of one policy bound to every slot.
+ *   The equality that defines it: for every slot, between two binds, the sequence of results and every baked byte are those of an
+ *      ethcnn_pacer created with the slot's policy and given the same frames in the same order -- whatever policies the other slots of
+ *      the calls had, in whatever order the frames stood, and whichever subset a call named.  A call is still two launches, three where
+ *      the host form stores the completion word.
+ *   ethcnn_pacer_policies_check    host only, no context: the rules of every policy (the first broken one, with "policy <index>: " in
+ *                              front of ethcnn_pacer_check's message, read with ethcnn_last_error(NULL)), npolicies in 1..32, and, where
+ *                              slot_policy is not NULL, nslots in 0..32 entries in 0..npolicies - 1.
+ *   ethcnn_pacer_policies_create   ethcnn_pacer_set_create with a policy list; slot_policy [nslots] binds the slots (NULL: all to
+ *                              policy 0).  In HBM, written once: all ladders in one int32 [sum of rungs][6], each with its full search
+ *                              appended, and one 48-byte record per policy.  A slot's table has as many rows as the longest ladder has
+ *                              rungs, so that a bind allocates nothing.
+ *   ethcnn_pacer_policies_count, ethcnn_pacer_policies_of   host only: the number of policies; the policy a slot is bound to.  Negative:
+ *                              a NULL set, a slot outside 0..nslots - 1.
+ *   ethcnn_pacer_policies_bind      ethcnn_pacer_set_reset of that slot plus the new binding, in stream order behind the frames already queued
+ *                              (they keep the policy they were queued under).  No other slot is touched.  Binding a slot to the policy it
+ *                              already has is a reset.  ETHCNN_ERR_ARG with nothing changed: a slot outside 0..nslots - 1, a policy
+ *                              outside 0..npolicies - 1.
+ *   ethcnn_pacer_policies_plan   ethcnn_pacer_set_plan with K[j] + 1 rungs for frame j -- the ladder of its slot's policy --, so that
+ *                              count_blocks[j] = slices x ceil((K[j] + 1) / 256): one call mixes frames of 1 and of 17 rung blocks.
+ *                              Refuses per frame what ethcnn_pacer_set_plan refuses, and a NULL K.
+ *   These six act on an ethcnn_pacer_set; their prefix is ethcnn_pacer_policies_, so that ethcnn_pacer_set_* stays the nine entries above.
+ *   The cost bound of a frame (a cost that may not fit in 64 bits) is taken under the weights of its slot's policy; one refused frame
+ *      still refuses the whole call before anything is allocated or enqueued. */
+#define ETHCNN_PACER_SET_MAX_POLICIES 32
+typedef struct ethcnn_pacer_policy {
+    const ethcnn_sim_thr* ladder; /* NULL: the default ladder */
+    int64_t K;
+    const uint64_t* weight;       /* [4]; NULL: 64 16 4 1 */
+    uint32_t budget_ppm;
+    int32_t mode;
+} ethcnn_pacer_policy;
+int ethcnn_pacer_policies_check (const ethcnn_pacer_policy* policies, int npolicies, const int* slot_policy, int nslots);
+int ethcnn_pacer_policies_create (ethcnn_ctx* ctx, int nslots, const ethcnn_pacer_policy* policies, int npolicies, const int* slot_policy,
+                                      ethcnn_pacer_set** out);
+int ethcnn_pacer_policies_count (const ethcnn_pacer_set* set);
+int ethcnn_pacer_policies_of (const ethcnn_pacer_set* set, int slot);
+int ethcnn_pacer_policies_bind (ethcnn_pacer_set* set, int slot, int policy);
+int ethcnn_pacer_policies_plan (const int64_t* nctus, const int64_t* K, int n, int64_t* count_first_out, int64_t* count_blocks_out,
+                                 int32_t* slice_len_out, int64_t* bake_first_out, int64_t* rec0_out, int64_t* count_grid_out,
+                                 int64_t* bake_grid_out);
+
 /* ---- search budget: building a ladder.  The two sections above pick a rung of a LADDER per frame; how well they hold a budget depends on
  *      that ladder, and the default one is the same on every level and never looks at a label.  These entries turn a simulator's set
  *      with labels into a ladder by a greedy walk from the full search: every step moves ONE of the six thresholds to the nearest grid
