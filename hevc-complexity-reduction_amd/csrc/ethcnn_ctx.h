@@ -337,9 +337,10 @@ int seq_front(ethcnn_ctx* c, const uint8_t* d_luma, const FrameGeom& g, int nf, 
 // front of it (null = zeros); state_out: where the state behind the last one goes (may be state_in).  The state is zeroed in front of
 // every frame with i_frame <= 1, so a row's run of frames that carries its state starts there: a recurrence launch takes the next
 // run of every row that has frames left (uniform rows from frame 1 on: one launch), then one gate launch takes the chunk.
+// thr1 / thr2: the gate pair of every row, k entries each; null (both): the context's pair for all rows, what the solo calls pass.
 // Returns hipGetLastError() behind them: every caller words its own message.
 namespace ethcnn { struct SeqBatchRow; }
-hipError_t seq_launch(ethcnn_ctx* c, const SeqBatchRow* chunk, int k);
+hipError_t seq_launch(ethcnn_ctx* c, const SeqBatchRow* chunk, int k, const float* thr1 = nullptr, const float* thr2 = nullptr);
 // frames per chunk, common to all sequences of a call with sum_nctu CTUs per frame between them: the caller's figure, else what
 // keeps a chunk's vectors within 256 MB, and at least one frame.  A sequence of nframes has min(nframes, this) frames in a chunk.
 inline int64_t seq_chunk_frames(int64_t sum_nctu, int chunk) {

@@ -405,8 +405,9 @@ int seq_front(ethcnn_ctx* c, const uint8_t* d_luma, const FrameGeom& g, int nf, 
 }
 
 // recurrence + heads + gates of a chunk for k sequences (ethcnn_ctx.h): every row has a frame cursor; its next run is one frame if
-// that frame's number is <= 0 and the rest of its chunk otherwise, with no state in front of a frame numbered <= 1
-hipError_t seq_launch(ethcnn_ctx* c, const SeqBatchRow* chunk, int k) {
+// that frame's number is <= 0 and the rest of its chunk otherwise, with no state in front of a frame numbered <= 1.  thr1 / thr2: the
+// gate pair of every row of the chunk, or null for the context's
+hipError_t seq_launch(ethcnn_ctx* c, const SeqBatchRow* chunk, int k, const float* thr1, const float* thr2) {
     int at[kLstmSeqBatchMax] = {};
     for (;;) {
         SeqBatchRow rows[kLstmSeqBatchMax];
@@ -426,7 +427,11 @@ hipError_t seq_launch(ethcnn_ctx* c, const SeqBatchRow* chunk, int k) {
         StageTimer t(c, ETHCNN_STAGE_HEADS, ctu_frames);
         launch_lstm_seq_batch(rows, nr, c->stream);
     }
-    { StageTimer tg(c, ETHCNN_STAGE_GATE); launch_lstm_seq_gates_batch(chunk, k, c->thr1, c->thr2, c->stream); }
+    {
+        StageTimer tg(c, ETHCNN_STAGE_GATE);
+        if (thr1 && thr2) launch_lstm_seq_gates_batch(chunk, k, thr1, thr2, c->stream);
+        else launch_lstm_seq_gates_batch(chunk, k, c->thr1, c->thr2, c->stream);
+    }
     return hipGetLastError();
 }
 

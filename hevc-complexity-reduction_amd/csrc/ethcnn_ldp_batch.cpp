@@ -76,6 +76,15 @@ extern "C" int64_t ethcnn_ldp_batch_state_ctus(ethcnn_ldp_batch* b, int j) { ret
 extern "C" int ethcnn_ldp_batch_get_state(ethcnn_ldp_batch* b, int j, float* out, size_t nfloats) {
     return ldp_set_get_state(b, j, out, nfloats, "ethcnn_ldp_batch_get_state", "sequence index");
 }
+extern "C" int ethcnn_ldp_set_thresholds_batch(ethcnn_ldp_batch* b, int j, float thr_l1_lower, float thr_l2_lower) {
+    return ldp_set_set_gates(b, j, thr_l1_lower, thr_l2_lower, "ethcnn_ldp_set_thresholds_batch", "sequence index");
+}
+extern "C" int ethcnn_ldp_clear_thresholds_batch(ethcnn_ldp_batch* b, int j) {
+    return ldp_set_clear_gates(b, j, "ethcnn_ldp_clear_thresholds_batch", "sequence index");
+}
+extern "C" int ethcnn_ldp_get_thresholds_batch(ethcnn_ldp_batch* b, int j, float* thr_l1_lower, float* thr_l2_lower, int* own) {
+    return ldp_set_get_gates(b, j, thr_l1_lower, thr_l2_lower, own, "ethcnn_ldp_get_thresholds_batch", "sequence index");
+}
 
 extern "C" int ethcnn_ldp_batch_run_device(ethcnn_ldp_batch* b, const ethcnn_ldp_batch_seq* seqs, int nseqs) {
     if (!b) return ETHCNN_ERR_ARG;

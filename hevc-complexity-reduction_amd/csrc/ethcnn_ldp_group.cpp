@@ -34,6 +34,13 @@ extern "C" int64_t ethcnn_ldp_group_state_ctus(ethcnn_ldp_group* g, int m) { ret
 extern "C" int ethcnn_ldp_group_get_state(ethcnn_ldp_group* g, int m, float* out, size_t nfloats) {
     return ldp_set_get_state(g, m, out, nfloats, "ethcnn_ldp_group_get_state", "member");
 }
+extern "C" int ethcnn_ldp_set_thresholds_group(ethcnn_ldp_group* g, int m, float thr_l1_lower, float thr_l2_lower) {
+    return ldp_set_set_gates(g, m, thr_l1_lower, thr_l2_lower, "ethcnn_ldp_set_thresholds_group", "member");
+}
+extern "C" int ethcnn_ldp_clear_thresholds_group(ethcnn_ldp_group* g, int m) { return ldp_set_clear_gates(g, m, "ethcnn_ldp_clear_thresholds_group", "member"); }
+extern "C" int ethcnn_ldp_get_thresholds_group(ethcnn_ldp_group* g, int m, float* thr_l1_lower, float* thr_l2_lower, int* own) {
+    return ldp_set_get_gates(g, m, thr_l1_lower, thr_l2_lower, own, "ethcnn_ldp_get_thresholds_group", "member");
+}
 
 extern "C" int ethcnn_ldp_group_sequence_device(ethcnn_ldp_group* g, const uint8_t* const* d_luma, int w, int h, ptrdiff_t pitch, ptrdiff_t fstride,
                                                 int nframes, const int* qp, int i_first, const float* const* d_state_in, float* const* d_probs) {

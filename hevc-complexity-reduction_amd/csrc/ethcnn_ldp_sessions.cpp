@@ -167,16 +167,18 @@ int sessions_launch(ethcnn_ldp_sessions* s, const Item* items, int n, const Layo
     // front of a frame numbered <= 1, else the resident state.  Every row is one run, so the two launchers are called as they are:
     // seq_launch (ethcnn_ldp.cpp) would zero the state in front of EVERY frame numbered <= 1, the offline calls' rule.
     SeqBatchRow rows[kLdpSessionsMax];
+    float thr1[kLdpSessionsMax], thr2[kLdpSessionsMax];  // by row: the pair follows the session id, not the row position
     long ctu_frames = 0;
     for (int j = 0; j < n; ++j) {
         const Item& it = items[j];
+        ldp_set_gates_of(s, it.session, &thr1[j], &thr2[j]);
         float* const state = s->s[it.session].d_state;
         rows[j] = {s->d_vec + (size_t)first[j] * 16 * kNVec, it.d_state_in ? it.d_state_in : (it.i_frame > 1 ? state : nullptr), state, it.d_lstm, it.d_probs,
                    lstm_seq_efs0(it.qp), it.geom.nctu, 1, it.i_frame};
         ctu_frames += it.geom.nctu;
     }
     { StageTimer t(c, ETHCNN_STAGE_HEADS, ctu_frames); launch_lstm_seq_batch(rows, n, c->stream); }
-    { StageTimer t(c, ETHCNN_STAGE_GATE); launch_lstm_seq_gates_batch(rows, n, c->thr1, c->thr2, c->stream); }
+    { StageTimer t(c, ETHCNN_STAGE_GATE); launch_lstm_seq_gates_batch(rows, n, thr1, thr2, c->stream); }
     const hipError_t e = hipGetLastError();
     if (e != hipSuccess)
         return ldp_set_err(s, ETHCNN_ERR_DEVICE, "launch failed: %s (the resident states of the call's sessions were dropped)", hipGetErrorString(e));
@@ -243,7 +245,24 @@ extern "C" int ethcnn_ldp_sessions_close(ethcnn_ldp_sessions* s, int session) {
     if (int rc = check_session(s, session, "ethcnn_ldp_sessions_close")) return rc;
     s->q[session] = {};
     s->s[session].state_nctu = -1;  // (the buffer stays for the next session of this id)
+    s->s[session].own_gates = false;  // (a reused id starts by inheriting the context's pair)
     return ETHCNN_OK;
+}
+
+extern "C" int ethcnn_ldp_sessions_set_thresholds(ethcnn_ldp_sessions* s, int session, float thr_l1_lower, float thr_l2_lower) {
+    if (!s) return ETHCNN_ERR_ARG;
+    if (int rc = check_session(s, session, "ethcnn_ldp_sessions_set_thresholds")) return rc;
+    return ldp_set_set_gates(s, session, thr_l1_lower, thr_l2_lower, "ethcnn_ldp_sessions_set_thresholds", "session");
+}
+extern "C" int ethcnn_ldp_sessions_clear_thresholds(ethcnn_ldp_sessions* s, int session) {
+    if (!s) return ETHCNN_ERR_ARG;
+    if (int rc = check_session(s, session, "ethcnn_ldp_sessions_clear_thresholds")) return rc;
+    return ldp_set_clear_gates(s, session, "ethcnn_ldp_sessions_clear_thresholds", "session");
+}
+extern "C" int ethcnn_ldp_sessions_get_thresholds(ethcnn_ldp_sessions* s, int session, float* thr_l1_lower, float* thr_l2_lower, int* own) {
+    if (!s) return ETHCNN_ERR_ARG;
+    if (int rc = check_session(s, session, "ethcnn_ldp_sessions_get_thresholds")) return rc;
+    return ldp_set_get_gates(s, session, thr_l1_lower, thr_l2_lower, own, "ethcnn_ldp_sessions_get_thresholds", "session");
 }
 
 extern "C" int64_t ethcnn_ldp_sessions_state_ctus(ethcnn_ldp_sessions* s, int session) {

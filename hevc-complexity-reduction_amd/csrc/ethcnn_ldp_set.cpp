@@ -116,6 +116,37 @@ int ldp_set_get_state(LdpSet* s, int j, float* out, size_t nfloats, const char* 
     return ETHCNN_OK;
 }
 
+namespace {
+int check_gates_call(LdpSet* s, int j, const char* who, const char* what) {
+    if (int rc = check_index(s, j, true, who, what)) return rc;
+    if (s->c->ldp.open || s->c->ai.open) return ldp_set_err(s, ETHCNN_ERR_ARG, "%s: a streamed call has not been ended", who);
+    return 0;
+}
+}  // namespace
+
+int ldp_set_set_gates(LdpSet* s, int j, float thr1, float thr2, const char* who, const char* what) {
+    if (int rc = check_gates_call(s, j, who, what)) return rc;
+    LdpSet::State& S = s->s[j];
+    S.own_gates = true;
+    S.thr1 = thr1;
+    S.thr2 = thr2;
+    return ETHCNN_OK;
+}
+
+int ldp_set_clear_gates(LdpSet* s, int j, const char* who, const char* what) {
+    if (int rc = check_gates_call(s, j, who, what)) return rc;
+    s->s[j].own_gates = false;
+    return ETHCNN_OK;
+}
+
+int ldp_set_get_gates(LdpSet* s, int j, float* thr1, float* thr2, int* own_out, const char* who, const char* what) {
+    if (int rc = check_gates_call(s, j, who, what)) return rc;
+    if (!thr1 || !thr2 || !own_out) return ldp_set_err(s, ETHCNN_ERR_ARG, "%s: null output pointer", who);
+    ldp_set_gates_of(s, j, thr1, thr2);
+    *own_out = s->s[j].own_gates ? 1 : 0;
+    return ETHCNN_OK;
+}
+
 int ldp_set_run(LdpSet* s, const LdpSeq* seqs, int nseqs, const char* who, const char* item, const char* form) {
     ethcnn_ctx* c = s->c;
     // ---- buffers: refused with the whole sum before anything is allocated
@@ -171,10 +202,12 @@ int ldp_set_run(LdpSet* s, const LdpSeq* seqs, int nseqs, const char* who, const
     for (int j = 0; j < nseqs; ++j) s->s[j].state_nctu = -1;  // until every frame has been enqueued
     for (int64_t f0 = 0; f0 < longest; f0 += Fc) {
         SeqBatchRow rows[kLstmSeqBatchMax];
+        float thr1[kLstmSeqBatchMax], thr2[kLstmSeqBatchMax];  // by row: the pair follows the sequence index, not the row position
         int k = 0;
         for (int j = 0; j < nseqs; ++j) {
             const LdpSeq& q = seqs[j];
             if (f0 >= q.nframes) continue;  // this sequence has ended
+            ldp_set_gates_of(s, j, &thr1[k], &thr2[k]);
             const int n = q.geom.nctu, f = (int)std::min<int64_t>(Fc, q.nframes - f0);
             float* const vec = s->d_vec + slice[j];
             if (int rc = seq_front(c, q.d_luma + f0 * q.geom.frame_stride, q.geom, f, vec)) {
@@ -185,7 +218,7 @@ int ldp_set_run(LdpSet* s, const LdpSeq* seqs, int nseqs, const char* who, const
             rows[k++] = {vec, (f0 || !q.d_state_in) ? state : q.d_state_in, state, q.d_lstm, q.d_probs + (size_t)f0 * n * kNOut,
                          lstm_seq_efs0(q.qp), n, f, q.i_frame_first + (int)f0};
         }
-        const hipError_t e = seq_launch(c, rows, k);
+        const hipError_t e = seq_launch(c, rows, k, thr1, thr2);
         if (e != hipSuccess) {
             drop_states(s);
             return ldp_set_err(s, ETHCNN_ERR_DEVICE, "launch failed: %s (the resident states of the %s were dropped)", hipGetErrorString(e), form);

@@ -28,6 +28,8 @@ struct LdpSet {
         float* d_state = nullptr;  // the resident (c, h) state of this sequence index, [cap][2][448], advanced in place
         int cap = 0;               // CTUs, a multiple of 16
         int state_nctu = -1;       // CTU count of the resident state; -1: none
+        bool own_gates = false;    // thr1, thr2 below are this index's gate pair; else it inherits the context's at launch time
+        float thr1 = 0.f, thr2 = 0.f;
     } s[kLstmSeqBatchMax];
     float* d_vec = nullptr;  // the chunk's vectors, sequence after sequence: [min(nframes_j, Fc)][nctu_j][448]
     size_t vec_cap = 0;      // bytes
@@ -47,6 +49,18 @@ int ldp_set_get_blob(LdpSet* s, int i, float* out, size_t nfloats, const char* w
 int ldp_set_chunk(LdpSet* s, int frames, const char* who);
 int64_t ldp_set_state_ctus(LdpSet* s, int j, const char* who, const char* what);
 int ldp_set_get_state(LdpSet* s, int j, float* out, size_t nfloats, const char* who, const char* what);
+// The gate pair of a state index (host-only bookkeeping, nothing touches the stream; refused while a streamed call is open).  Values as
+// ethcnn_set_thresholds takes them: that entry refuses no float, so neither do these.  get: own_out says whether the pair is the
+// index's own or the context's as it stands now; every output pointer is needed.
+int ldp_set_set_gates(LdpSet* s, int j, float thr1, float thr2, const char* who, const char* what);
+int ldp_set_clear_gates(LdpSet* s, int j, const char* who, const char* what);
+int ldp_set_get_gates(LdpSet* s, int j, float* thr1, float* thr2, int* own_out, const char* who, const char* what);
+// the pair state index j runs under in a launch enqueued now: its own if set, else the context's thr1 / thr2 read at this call
+inline void ldp_set_gates_of(const LdpSet* s, int j, float* thr1, float* thr2) {
+    const LdpSet::State& S = s->s[j];
+    *thr1 = S.own_gates ? S.thr1 : s->c->thr1;
+    *thr2 = S.own_gates ? S.thr2 : s->c->thr2;
+}
 void ldp_set_release(LdpSet* s);  // waits for the stream and frees what the set holds on the device (the entry deletes the object)
 
 template <class T>  // T: ethcnn_ldp_group or ethcnn_ldp_batch; what: "members" or "bundles"

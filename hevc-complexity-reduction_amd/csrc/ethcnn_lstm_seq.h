@@ -41,7 +41,9 @@ inline void lstm_seq_blocks(int64_t n, int64_t out[3]) {
 }
 // rows in any order: the launch deals the blocks of a level to the rows with the most frames first (scheduling only)
 void launch_lstm_seq_batch(const SeqBatchRow* rows, int k, hipStream_t s);
-// the gate pass over the rows' probabilities [F][n][21] (reads probs, n and F of a row)
+// the gate pass over the rows' probabilities [F][n][21] (reads probs, n and F of a row): row j under the pair thr1[j], thr2[j] (k
+// entries each).  The scalar form gives every row the same pair.
+void launch_lstm_seq_gates_batch(const SeqBatchRow* rows, int k, const float* thr1, const float* thr2, hipStream_t s);
 void launch_lstm_seq_gates_batch(const SeqBatchRow* rows, int k, float thr1, float thr2, hipStream_t s);
 
 // dependent v_mfma_f32_16x16x4_f32 links per frame of the wave that owns a hidden tile (its four gate chains are interleaved), and of

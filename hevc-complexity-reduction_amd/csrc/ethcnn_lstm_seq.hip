@@ -317,26 +317,37 @@ __device__ __forceinline__ void lstm_seq_gates_body(float* __restrict__ probs, i
     }
 }
 
-// grid (max over rows of frames x mini-batches, rows); a block behind its row's last (frame, mini-batch) returns at once
+// grid (max over rows of frames x mini-batches, rows); a block behind its row's last (frame, mini-batch) returns at once.  Every row
+// has a threshold pair of its own: like n and F it is read by the block-uniform row index, a scalar load from the kernel-argument
+// segment (768 bytes), so no lane indexes the table and nothing of it lives in scratch.
 struct SeqGateBatch {
     float* probs[kLstmSeqBatchMax];
     int n[kLstmSeqBatchMax], F[kLstmSeqBatchMax];
+    float thr1[kLstmSeqBatchMax], thr2[kLstmSeqBatchMax];
 };
-__global__ __launch_bounds__(256) void k_lstm_seq_gates_batch(SeqGateBatch Q, float thr1, float thr2) {
+static_assert(sizeof(SeqGateBatch) == 768, "the gate launch's kernel arguments");
+__global__ __launch_bounds__(256) void k_lstm_seq_gates_batch(SeqGateBatch Q) {
     const int n = Q.n[blockIdx.y], chunks = (n + kSubBatch - 1) / kSubBatch;
     if ((int)blockIdx.x >= chunks * Q.F[blockIdx.y]) return;
-    lstm_seq_gates_body(Q.probs[blockIdx.y], n, chunks, thr1, thr2);
+    lstm_seq_gates_body(Q.probs[blockIdx.y], n, chunks, Q.thr1[blockIdx.y], Q.thr2[blockIdx.y]);
 }
 
-void launch_lstm_seq_gates_batch(const SeqBatchRow* rows, int k, float thr1, float thr2, hipStream_t s) {
+void launch_lstm_seq_gates_batch(const SeqBatchRow* rows, int k, const float* thr1, const float* thr2, hipStream_t s) {
     SeqGateBatch Q;
     unsigned gx = 1;
     for (int j = 0; j < kLstmSeqBatchMax; ++j) {
-        const SeqBatchRow& R = rows[j < k ? j : 0];
-        Q.probs[j] = R.probs, Q.n[j] = R.n, Q.F[j] = R.F;
+        const int r = j < k ? j : 0;
+        const SeqBatchRow& R = rows[r];
+        Q.probs[j] = R.probs, Q.n[j] = R.n, Q.F[j] = R.F, Q.thr1[j] = thr1[r], Q.thr2[j] = thr2[r];
         gx = std::max(gx, (unsigned)((R.n + kSubBatch - 1) / kSubBatch) * (unsigned)R.F);
     }
-    hipLaunchKernelGGL(k_lstm_seq_gates_batch, dim3(gx, (unsigned)k), dim3(256), 0, s, Q, thr1, thr2);
+    hipLaunchKernelGGL(k_lstm_seq_gates_batch, dim3(gx, (unsigned)k), dim3(256), 0, s, Q);
+}
+
+void launch_lstm_seq_gates_batch(const SeqBatchRow* rows, int k, float thr1, float thr2, hipStream_t s) {
+    float t1[kLstmSeqBatchMax], t2[kLstmSeqBatchMax];
+    for (int j = 0; j < k; ++j) t1[j] = thr1, t2[j] = thr2;
+    launch_lstm_seq_gates_batch(rows, k, t1, t2, s);
 }
 
 }  // namespace ethcnn

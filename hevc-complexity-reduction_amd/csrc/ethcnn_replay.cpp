@@ -684,6 +684,12 @@ int batch_replay(ethcnn_replay* p, ethcnn_ldp_batch* b, int nitems, const int* r
 
 template <typename Add>
 int batch_feed(ethcnn_replay* p, ethcnn_ldp_batch* b, int nitems, const int* runs, const int* slots, const int* bundles, Add add) {
+    // the consumers take UNGATED probabilities (open gates on the context): a pair of an index's own would gate them all the same
+    if (b)
+        for (int j = 0; j < kLstmSeqBatchMax; ++j)
+            if (b->s[j].own_gates)
+                return rerr(p, ETHCNN_ERR_ARG, "sequence index %d of the batch holds thresholds of its own (%g, %g): a feed needs open gates (ethcnn_ldp_clear_thresholds_batch)",
+                            j, (double)b->s[j].thr1, (double)b->s[j].thr2);
     BatchLayout L;
     if (int rc = batch_replay(p, b, nitems, runs, slots, bundles, nullptr, nullptr, &L)) return rc;
     for (int j = 0; j < nitems; ++j) {  // in list order: the consumer ends as the per-run feeds in that order leave it

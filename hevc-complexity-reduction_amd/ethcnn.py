@@ -119,6 +119,9 @@ SIGNATURES = {
     "ethcnn_ldp_group_state_ctus": (ctypes.c_int64, [_vp, _i]),
     "ethcnn_ldp_group_set_chunk": (_i, [_vp, _i]),
     "ethcnn_ldp_group_bytes": (ctypes.c_int64, [_i, _i, _i, _i, _i]),
+    "ethcnn_ldp_set_thresholds_group": (_i, [_vp, _i, ctypes.c_float, ctypes.c_float]),
+    "ethcnn_ldp_clear_thresholds_group": (_i, [_vp, _i]),
+    "ethcnn_ldp_get_thresholds_group": (_i, [_vp, _i, _fp, _fp, ctypes.POINTER(_i)]),
     "ethcnn_ldp_batch_create": (_i, [_vp, _i, ctypes.POINTER(_vp)]),
     "ethcnn_ldp_batch_destroy": (None, [_vp]),
     "ethcnn_ldp_batch_last_error": (_cp, [_vp]),
@@ -133,6 +136,9 @@ SIGNATURES = {
     "ethcnn_ldp_batch_set_chunk": (_i, [_vp, _i]),
     "ethcnn_ldp_batch_bytes": (ctypes.c_int64, [ctypes.POINTER(_i), ctypes.POINTER(_i), ctypes.POINTER(_i), _i, _i]),
     "ethcnn_ldp_batch_plan": (_i, [ctypes.POINTER(_i), ctypes.POINTER(_i), _i, _i, ctypes.POINTER(_i), ctypes.POINTER(_i), ctypes.POINTER(_i), _i]),
+    "ethcnn_ldp_set_thresholds_batch": (_i, [_vp, _i, ctypes.c_float, ctypes.c_float]),
+    "ethcnn_ldp_clear_thresholds_batch": (_i, [_vp, _i]),
+    "ethcnn_ldp_get_thresholds_batch": (_i, [_vp, _i, _fp, _fp, ctypes.POINTER(_i)]),
     "ethcnn_ldp_sessions_create": (_i, [_vp, _i, ctypes.POINTER(_vp)]),
     "ethcnn_ldp_sessions_destroy": (None, [_vp]),
     "ethcnn_ldp_sessions_last_error": (_cp, [_vp]),
@@ -149,6 +155,9 @@ SIGNATURES = {
     "ethcnn_ldp_sessions_state_ctus": (ctypes.c_int64, [_vp, _i]),
     "ethcnn_ldp_sessions_bytes": (ctypes.c_int64, [ctypes.POINTER(_i), ctypes.POINTER(_i), _i]),
     "ethcnn_ldp_sessions_plan": (_i, [ctypes.POINTER(_i), _i, _i, ctypes.POINTER(_i), ctypes.POINTER(_i), ctypes.POINTER(_i), _i]),
+    "ethcnn_ldp_sessions_set_thresholds": (_i, [_vp, _i, ctypes.c_float, ctypes.c_float]),
+    "ethcnn_ldp_sessions_clear_thresholds": (_i, [_vp, _i]),
+    "ethcnn_ldp_sessions_get_thresholds": (_i, [_vp, _i, _fp, _fp, ctypes.POINTER(_i)]),
     "ethcnn_ldp_step_begin": (_i, [_vp, _vp, _i, _i, _pd, _i, _i, _vp, _fp]),
     "ethcnn_rows_ready": (_i, [_vp, _i, _i]),
     "ethcnn_predict_luma_begin": (_i, [_vp, _vp, _i, _i, _i, _fp]),
@@ -3018,6 +3027,11 @@ class _LdpSet(object):
     def _fn(self, name):
         return getattr(self.lib, "ethcnn_%s_%s" % (self._PREFIX, name))
 
+    def _gates_fn(self, verb):
+        """ethcnn_ldp_sessions_<verb>_thresholds; for a group and a batch the form comes last: ethcnn_ldp_<verb>_thresholds_group"""
+        form = self._PREFIX[4:]
+        return getattr(self.lib, "ethcnn_ldp_sessions_%s_thresholds" % verb if form == "sessions" else "ethcnn_ldp_%s_thresholds_%s" % (verb, form))
+
     def __init__(self, ctx, count):
         self.ctx, self.lib = ctx, ctx.lib
         h = ctypes.c_void_p()
@@ -3078,12 +3092,27 @@ class _LdpSet(object):
         self._chk(self._fn("get_state")(self.h, int(j), state.ctypes.data_as(_fp), state.size))
         return state
 
+    def set_thresholds(self, j, thr_l1_lower, thr_l2_lower):
+        """a gate pair of its own for member / sequence index / session j: from now on j runs under it, whatever the context's is"""
+        self._chk(self._gates_fn("set")(self.h, int(j), thr_l1_lower, thr_l2_lower))
+
+    def clear_thresholds(self, j):
+        """j inherits the context's pair again (as it stands when a call is made)"""
+        self._chk(self._gates_fn("clear")(self.h, int(j)))
+
+    def thresholds_of(self, j):
+        """-> (thr_l1_lower, thr_l2_lower, own): the pair j runs under now; own = 0: it is the context's"""
+        a, b, own = ctypes.c_float(), ctypes.c_float(), ctypes.c_int()
+        self._chk(self._gates_fn("get")(self.h, int(j), ctypes.byref(a), ctypes.byref(b), ctypes.byref(own)))
+        return a.value, b.value, own.value
+
 
 class LdpGroup(_LdpSet):
     """K = 1..8 Low-Delay-P residual sequences of one geometry through one recurrence launch (include/ethcnn.h "config #5 offline,
     group form"): each member has its own ETH-LSTM bundle, QP, resident state and output, and its result equals
-    EthCnn.ldp_sequence_device on a context that holds its bundle, bit for bit.  The residual CNN and the thresholds are the
-    context's; the context's own LSTM bundle and resident state are not touched."""
+    EthCnn.ldp_sequence_device on a context that holds its bundle, bit for bit.  The residual CNN is the context's, and so are the
+    thresholds of every member that has no pair of its own (set_thresholds); the context's own LSTM bundle and resident state are
+    not touched."""
     _PREFIX = "ldp_group"
 
     def __init__(self, ctx, k):
@@ -3150,7 +3179,8 @@ class LdpBatch(_LdpSet):
     """Up to 32 Low-Delay-P residual sequences of different geometry, length and first frame number through one recurrence launch
     per chunk (include/ethcnn.h "config #5 offline, batch form").  The object holds nbundles = 1..8 ETH-LSTM bundles; a sequence names
     its bundle by index, and its result equals EthCnn.ldp_sequence_device on a context that holds that bundle, bit for bit.  The
-    residual CNN and the thresholds are the context's; the context's own LSTM bundle and resident state are not touched."""
+    residual CNN is the context's, and so are the thresholds of every sequence index that has no pair of its own (set_thresholds);
+    the context's own LSTM bundle and resident state are not touched."""
     _PREFIX = "ldp_batch"
 
     def __init__(self, ctx, nbundles):
@@ -3215,8 +3245,9 @@ class LdpSessions(_LdpSet):
     """Up to 32 live Low-Delay-P encoders on one context (include/ethcnn.h "config #5 online, several live encoders"): a session has a
     picture size and a resident recurrent state, a step advances any subset of the sessions by one frame through one shared front-end
     and one recurrence launch.  The object holds nbundles = 1..8 ETH-LSTM bundles; a frame names its bundle by index, and its result
-    equals EthCnn.ldp_step on a context of its own that holds that bundle, bit for bit.  The residual CNN and the thresholds are the
-    context's; the context's own LSTM bundle and resident state are not touched."""
+    equals EthCnn.ldp_step on a context of its own that holds that bundle, bit for bit.  The residual CNN is the context's, and so
+    are the thresholds of every session that has no pair of its own (set_thresholds; close forgets it); the context's own LSTM bundle
+    and resident state are not touched."""
     _PREFIX = "ldp_sessions"
 
     def __init__(self, ctx, nbundles):

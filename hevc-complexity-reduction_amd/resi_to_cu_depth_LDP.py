@@ -326,9 +326,10 @@ MAX_SESSIONS = 32   # ethcnn_ldp_sessions: sessions open at once
 MAX_BUNDLES = 8     # ... and its bundle places
 
 
-def check_sessions(workdirs):
+def check_sessions(workdirs, gates_per_dir=False):
     """What `--sessions` refuses at start-up, as ValueError, before a GPU is touched and with nothing written -> the gate thresholds
-    all directories share.  The gates are the context's: every Thr_info.txt must give the first directory's gate tokens [1] and [3]."""
+    all directories share.  The gates are the context's: every Thr_info.txt must give the first directory's gate tokens [1] and [3].
+    gates_per_dir (`--gates-per-dir`): the files may differ, each must parse -> the list of every directory's pair, in their order."""
     budget = sorted(k for k in os.environ if k.startswith('ETHCNN_SEARCH_BUDGET'))
     if budget:
         raise ValueError('--sessions does not pace: %s is set, and the search budget is held per sequence (one daemon per encoder does that)'
@@ -343,19 +344,22 @@ def check_sessions(workdirs):
         if real in seen:
             raise ValueError('--sessions: %s is listed twice (as %s and %s)' % (real, seen[real], d))
         seen[real] = d
-    gates = None
+    gates, pairs = None, []
     for d in workdirs:
         path = os.path.join(d, THR_FILE)
         try:
             g = _e.parse_thresholds(path)
         except _e.EthCnnError:
             raise ValueError('--sessions: cannot read the thresholds of %s' % path)
+        pairs.append(g)
+        if gates_per_dir:
+            continue
         if gates is None:
             gates = g
         elif g != gates:
             raise ValueError('--sessions: the gate thresholds of %s (%g %g) differ from those of %s (%g %g); one server has one pair of gates'
                              % (path, g[0], g[1], os.path.join(workdirs[0], THR_FILE), gates[0], gates[1]))
-    return gates
+    return pairs if gates_per_dir else gates
 
 
 def check_pace(workdirs, share, mode=None, weights=None, ladder=None):
@@ -417,6 +421,7 @@ class _Dir(object):
         self.pinned, self.pinned_probs = None, None
         self.paced_geom, self.paced = None, [0, 0, 0, 0]   # as serve's: frames, over budget, sum of cost, sum of full
         self.policy = None   # under --budget-policies: the (share, mode, weights, ladder) its slot is bound to
+        self.gates = None    # under --gates-per-dir: the pair of its own Thr_info.txt, set on every session it opens
 
     def p(self, name):
         return os.path.join(self.workdir, name)
@@ -429,7 +434,8 @@ def _host_buffer_again(ctx, old, nbytes):
     return ctx.host_buffer(nbytes)
 
 
-def serve_many(workdirs, max_frames=None, idle_timeout=None, poll_s=2e-4, device=0, verbose=True, accept_stale=False, pace=None, policies=None):
+def serve_many(workdirs, max_frames=None, idle_timeout=None, poll_s=2e-4, device=0, verbose=True, accept_stale=False, pace=None, policies=None,
+               gates_per_dir=False):
     """One server for several HM working directories: one context, one LdpSessions object, the unchanged file handshake per directory.
     A poll round takes every directory with pred_start.sig and a complete command.dat, reads their resi.yuv, advances all of them
     in ONE step, writes cu_depth.dat and pred_end.sig per directory and then refreshes every served state.dat and its sidecar.  State
@@ -439,9 +445,14 @@ def serve_many(workdirs, max_frames=None, idle_timeout=None, poll_s=2e-4, device
     buffers before the files are written.  A directory's slot is reset where serve resets its pacer.
     policies: what check_policies returned, or None.  With it the set holds every policy of the file (and `pace` as the default one), and
     where a directory's slot would be reset it is BOUND to the policy of that directory and of the QP of the frame that starts the
-    allowance; the binding holds until the next start."""
-    check_sessions(workdirs)
+    allowance; the binding holds until the next start.
+    gates_per_dir: every directory's session runs under the gate pair of that directory's own Thr_info.txt, as read at start-up; the
+    context keeps the first directory's.  Without effect under pace or policies: the gates are then open for every directory."""
+    gates = check_sessions(workdirs, gates_per_dir)
     dirs = [_Dir(d) for d in workdirs]
+    if gates_per_dir and pace is None and policies is None:
+        for d, g in zip(dirs, gates):
+            d.gates = g
     ctx = _e.EthCnn(device=device)
     sessions = pacer = None
     try:
@@ -489,6 +500,8 @@ def serve_many(workdirs, max_frames=None, idle_timeout=None, poll_s=2e-4, device
                     if d.session is not None:
                         sessions.close(d.session)
                     d.session, d.geom, d.last_key, d.paced_geom = sessions.open(w, h), (w, h), None, None
+                    if d.gates is not None:   # (a closed id forgets its pair: every open sets it again)
+                        sessions.set_thresholds(d.session, d.gates[0], d.gates[1])
                 num_vectors = _e.ctus_per_frame(w, h)
                 if d.pinned is None or d.pinned.size < w * h:
                     d.pinned = _host_buffer_again(ctx, d.pinned, w * h)
@@ -553,16 +566,17 @@ def serve_many(workdirs, max_frames=None, idle_timeout=None, poll_s=2e-4, device
 USAGE = ('usage: resi_to_cu_depth_LDP.py [--max-frames N] [--idle-timeout S] [--accept-stale]\n'
          '       resi_to_cu_depth_LDP.py --sessions DIR [DIR ...] [--max-frames N] [--idle-timeout S] [--accept-stale] [--quiet]\n'
          '                               [--budget SHARE [--budget-mode frame|carry] [--budget-weights "W64 W32 W16 W8"] [--budget-ladder FILE]]\n'
-         '                               [--budget-policies FILE]\n')
+         '                               [--budget-policies FILE] [--gates-per-dir]\n')
 
 
 def main(argv):
     """`python resi_to_cu_depth_LDP.py` in HM-LDP's bin/ (no arguments, like the reference);
     optional: --max-frames N, --idle-timeout SECONDS; --sessions DIR [DIR ...]: one server for several working directories, and behind
     it only --budget SHARE [--budget-mode M] [--budget-weights "W64 W32 W16 W8"] [--budget-ladder FILE]: the search budget of all of them,
-    --budget-policies FILE: a policy per directory (the --budget options are then the default policy), and --quiet."""
+    --budget-policies FILE: a policy per directory (the --budget options are then the default policy), --gates-per-dir: every directory
+    under the gate thresholds of its own Thr_info.txt (no effect beside a budget: the gates are then open), and --quiet."""
     max_frames = idle = None
-    accept_stale = quiet = False
+    accept_stale = quiet = gates_per_dir = False
     workdirs = None
     options = {}   # --budget, --budget-mode, --budget-weights, --budget-ladder -> their texts
     policy_file = None
@@ -585,16 +599,18 @@ def main(argv):
             policy_file = args.pop(0)
         elif a == '--quiet':
             quiet = True
+        elif a == '--gates-per-dir':
+            gates_per_dir = True
         else:
             sys.stderr.write(USAGE)
             return 2
-    if (options or quiet or policy_file is not None) and workdirs is None or (options and _sb.OPTION_NAMES[0] not in options):
+    if (options or quiet or gates_per_dir or policy_file is not None) and workdirs is None or (options and _sb.OPTION_NAMES[0] not in options):
         sys.stderr.write(USAGE)   # the budget options belong to --sessions, and the three others to --budget
         return 2
     if workdirs is not None:
         pace = policies = None
         try:
-            check_sessions(workdirs)
+            check_sessions(workdirs, gates_per_dir)
             if options:
                 pace = check_pace(workdirs, *[options.get(n) for n in _sb.OPTION_NAMES])
             if policy_file is not None:
@@ -603,7 +619,8 @@ def main(argv):
             sys.stderr.write('resi_to_cu_depth_LDP: %s\n' % err)
             return 1
         try:
-            serve_many(workdirs, max_frames=max_frames, idle_timeout=idle, accept_stale=accept_stale, verbose=not quiet, pace=pace, policies=policies)
+            serve_many(workdirs, max_frames=max_frames, idle_timeout=idle, accept_stale=accept_stale, verbose=not quiet, pace=pace, policies=policies,
+                       gates_per_dir=gates_per_dir)
         except StaleStateError:
             return 1
         return 0

@@ -2,8 +2,9 @@
 
     resi_video_to_cu_depth_LDP.py <resi.yuv> <width> <height> <qp> [--first-frame 1] [--frames N] [--out cu_depth.dat]
                                   [--state-out state.dat] [--model-dir DIR] [--device 0] [--chunk FRAMES]
-                                  [--also RESI_YUV QP OUT]... [--piece-frames FRAMES]
+                                  [--also RESI_YUV QP OUT]... [--piece-frames FRAMES] [--thr-info-qp QP FILE]...
     resi_video_to_cu_depth_LDP.py --list FILE [--model-dir DIR] [--device 0] [--chunk FRAMES] [--piece-frames FRAMES]
+                                  [--thr-info-qp QP FILE]...
 
 <resi.yuv> is the whole-sequence 4:2:0 residual file HM-16.5_Resi_Pre writes per QP: frame k of the file is POC k.  POC 0 is the intra
 picture and has no residual, so the first frame is 1 unless a later one is asked for (--first-frame > 1 needs the state of the frames
@@ -29,6 +30,12 @@ sequences of that band; all sequences share every recurrence launch (LdpBatch), 
 writes.  Luma is uploaded in pieces of --piece-frames frames of every sequence (default 0: as many as hold 256 MB of luma over all
 sequences).  Outputs are written to temp files and renamed at the end, as with --also.  The positional arguments, --also, --first-frame,
 --frames, --out and --state-out do not go with --list.
+
+--thr-info-qp QP FILE (repeatable) runs every sequence of exactly that QP -- the positional one, an --also, a --list line -- under
+the gate thresholds of FILE (tokens [1] and [3] of its first line, as Thr_info.txt is read): the file a calibration wrote for that
+QP's model.  Every other sequence runs under <model-dir>/Thr_info.txt, as without the option.  The sequences still share every launch,
+and each output is byte for byte what a run of its own writes with FILE as <model-dir>/Thr_info.txt.  A QP given twice, or a FILE that
+cannot be read or parsed, is status 1 before a GPU is opened.
 """
 import argparse
 import os
@@ -51,6 +58,24 @@ else:  # run as a file: the package directory's name is no Python identifier, so
 def _fail(msg):
     sys.stderr.write("resi_video_to_cu_depth_LDP: %s\n" % msg)
     return 1
+
+
+def gates_by_qp(pairs):
+    """--thr-info-qp QP FILE ... -> {qp: (thr1, thr2)}; ValueError for a QP that is no number or given twice and for a FILE that cannot
+    be read or parsed (no GPU is needed)"""
+    gates = {}
+    for qp, path in pairs or []:
+        try:
+            q = int(qp)
+        except ValueError:
+            raise ValueError("--thr-info-qp %s %s: QP is not a number" % (qp, path))
+        if q in gates:
+            raise ValueError("--thr-info-qp: QP %d is given twice" % q)
+        try:
+            gates[q] = _e.parse_thresholds(path)
+        except _e.EthCnnError:
+            raise ValueError("--thr-info-qp %d: cannot read the thresholds of %s" % (q, path))
+    return gates
 
 
 def group_members(a):
@@ -107,10 +132,11 @@ def parse_list(path):
     return seqs
 
 
-def run_list(ctx, a, seqs):
+def run_list(ctx, a, seqs, gates):
     """the sequences of a --list file through one LdpBatch: one bundle per QP band, luma uploaded a piece of frames at a time, the
     resident states carry each sequence from piece to piece.  The sequences go to the batch longest first, so those that still have
-    frames are always the first of the list and each keeps its sequence index (its resident state)."""
+    frames are always the first of the list and each keeps its sequence index (its resident state, and its gate pair where `gates`
+    names its QP)."""
     seqs = sorted(seqs, key=lambda q: -q[5])  # (stable)
     bands = sorted(set(_e.lstm_model_name_for_qp(q[3]) for q in seqs))
     planes = [q[1] * q[2] for q in seqs]
@@ -124,6 +150,9 @@ def run_list(ctx, a, seqs):
                 qp = next(q[3] for q in seqs if _e.lstm_model_name_for_qp(q[3]) == name)
                 print("LSTM model %d (%s): %s" % (i, name, restore_member_lstm(batch, i, qp, a.model_dir)))
             batch.set_chunk(a.chunk)
+            for j, q in enumerate(seqs):
+                if q[3] in gates:
+                    batch.set_thresholds(j, *gates[q[3]])
             maps = [np.memmap(q[0], dtype=np.uint8, mode="r") for q in seqs]
             files = [open(t, "wb") for t in tmps]
             nctu = [_e.ctus_per_frame(q[1], q[2]) for q in seqs]
@@ -177,7 +206,7 @@ def restore_member_lstm(group, m, qp, model_dir):
     return 'synthetic(seed=%s)' % seed
 
 
-def run_group(ctx, a, members, nframes):
+def run_group(ctx, a, members, nframes, gates):
     """several sequences through one LdpGroup: luma is read with numpy a piece of frames at a time, every piece goes through the
     device entry, the resident states carry each sequence on; every output is written to a temp file and renamed at the end"""
     k, n = len(members), _e.ctus_per_frame(a.width, a.height)
@@ -190,6 +219,9 @@ def run_group(ctx, a, members, nframes):
             for m, (_, qp, _) in enumerate(members):
                 print("LSTM model %d (QP %d): %s" % (m, qp, restore_member_lstm(group, m, qp, a.model_dir)))
             group.set_chunk_frames(a.chunk)
+            for m, (_, qp, _) in enumerate(members):
+                if qp in gates:
+                    group.set_thresholds(m, *gates[qp])
             maps = [np.memmap(m[0], dtype=np.uint8, mode="r") for m in members]
             files = [open(t, "wb") for t in tmps]
             d_l = [ctx.alloc(piece * plane) for _ in range(k)]
@@ -237,13 +269,14 @@ def main_list(a):
         return _fail("--piece-frames %d" % a.piece_frames)
     try:
         seqs = parse_list(a.list)
+        gates = gates_by_qp(a.thr_info_qp)
         ctx = _e.EthCnn(device=a.device)
         try:
             print("CNN  model: %s" % restore_cnn(ctx, a.model_dir))
             thr = os.path.join(a.model_dir, "Thr_info.txt")
             if os.path.exists(thr):
                 ctx.load_thresholds(thr)
-            run_list(ctx, a, seqs)
+            run_list(ctx, a, seqs, gates)
         finally:
             ctx.close()
     except (_e.EthCnnError, OSError, ValueError) as e:
@@ -267,6 +300,7 @@ def main(argv):
     ap.add_argument("--chunk", type=int, default=0)
     ap.add_argument("--also", nargs=3, action="append", metavar=("RESI_YUV", "QP", "OUT"))
     ap.add_argument("--piece-frames", type=int, default=0)
+    ap.add_argument("--thr-info-qp", nargs=2, action="append", metavar=("QP", "FILE"))
     try:
         a = ap.parse_args(argv[1:])
         if a.list is None and a.qp is None:
@@ -294,6 +328,7 @@ def main(argv):
         return _fail("--chunk %d" % a.chunk)
     try:
         members = group_members(a)
+        gates = gates_by_qp(a.thr_info_qp)
     except ValueError as e:
         return _fail(str(e))
     for yuv, _, _ in members[1:]:
@@ -312,12 +347,14 @@ def main(argv):
             if os.path.exists(thr):
                 ctx.load_thresholds(thr)
             if len(members) > 1:
-                state = run_group(ctx, a, members, nframes)
+                state = run_group(ctx, a, members, nframes, gates)
                 if a.state_out:
                     tmp = "%s.tmp.%d" % (a.state_out, os.getpid())
                     np.ascontiguousarray(state, dtype="<f4").tofile(tmp)
                     os.replace(tmp, a.state_out)
                 return 0
+            if a.qp in gates:  # a single sequence: its pair is simply the context's
+                ctx.set_thresholds(*gates[a.qp])
             print("LSTM model: %s" % restore_lstm(ctx, a.qp, a.model_dir))
             ctx.ldp_set_sequence_chunk(a.chunk)
             t0 = time.time()

@@ -306,9 +306,10 @@ int64_t ethcnn_ldp_sequence_bytes(int width, int height, int nframes, int chunk_
  *      HM-16.5_Resi_Pre writes one resi_XX.yuv per QP of a sequence and every record of an inter sample file carries four QP slots: the
  *      members of a group are such sequences, each with its own ETH-LSTM bundle, QP, state and output.
  *      DEFINITION: for every member m, d_probs[m] and m's resident state EQUAL what ethcnn_ldp_sequence_device gives on a context that
- *      holds m's bundle, for d_luma[m], qp[m] and the same remaining arguments (d_state_in[m] for d_state_in), bit for bit, gates and
- *      their zero patterns included.  The residual CNN, the thresholds and the stream are the context's; the context's own LSTM bundle,
- *      resident LDP state and sequence buffers are neither used nor changed.
+ *      holds m's bundle and whose thresholds are m's RESOLVED pair, for d_luma[m], qp[m] and the same remaining arguments (d_state_in[m]
+ *      for d_state_in), bit for bit, gates and their zero patterns included.  Member m's resolved pair is its own when
+ *      ethcnn_ldp_set_thresholds_group gave it one, else the context's pair as it stands when the call is made.  The residual CNN and
+ *      the stream are the context's; the context's own LSTM bundle, resident LDP state and sequence buffers are neither used nor changed.
  *      What differs is the schedule: the front-end runs per member and chunk as in the solo call; the recurrence of a run of frames is
  *      ONE launch for all members (level-major block order: every member's long chains first), the gates of a chunk ONE launch.
  *      Geometry, nframes and i_frame_first are common, so all members split into runs at the same frames (i_frame <= 1).
@@ -333,6 +334,8 @@ int64_t ethcnn_ldp_sequence_bytes(int width, int height, int nframes, int chunk_
  *   ethcnn_ldp_group_get_state    member m's resident state, float32 [nctu][2][448]; synchronous
  *   ethcnn_ldp_group_state_ctus   the CTU count of member m's resident state; 0: none; negative: bad arguments
  *   ethcnn_ldp_group_set_chunk    frames per chunk; 0 = default (256 MB of vectors for the whole group).  Results do not depend on it.
+ *   ethcnn_ldp_set_thresholds_group / ethcnn_ldp_clear_thresholds_group / ethcnn_ldp_get_thresholds_group   member m's gate pair, as ethcnn_ldp_set_thresholds_batch
+ *                                 takes sequence index j's.
  *   ethcnn_ldp_group_bytes        host only, no context: the device bytes a call holds, F = min(nframes, chunk or default) frames:
  *                                 k F nctu 448 x 4 (vectors) + k x roundup16(nctu) x 896 x 4 (the resident states); negative for bad
  *                                 arguments.  Beside it, from load time: k bundle images.  A call that cannot get its buffers fails
@@ -353,13 +356,18 @@ int ethcnn_ldp_group_get_state(ethcnn_ldp_group* grp, int m, float* state_out, s
 int64_t ethcnn_ldp_group_state_ctus(ethcnn_ldp_group* grp, int m);
 int ethcnn_ldp_group_set_chunk(ethcnn_ldp_group* grp, int frames);
 int64_t ethcnn_ldp_group_bytes(int width, int height, int nframes, int chunk_frames, int k);
+int ethcnn_ldp_set_thresholds_group(ethcnn_ldp_group* grp, int m, float thr_l1_lower, float thr_l2_lower);
+int ethcnn_ldp_clear_thresholds_group(ethcnn_ldp_group* grp, int m);
+int ethcnn_ldp_get_thresholds_group(ethcnn_ldp_group* grp, int m, float* thr_l1_lower, float* thr_l2_lower, int* own);
 /* ---- config #5 offline, batch form: up to 32 residual sequences of DIFFERENT geometry, length and first frame number through the chain
  *      together (an evaluation set, or the runs of an inter sample file), on one GPU.  The object holds up to 8 ETH-LSTM bundles; every
  *      sequence names its bundle by index, so several sequences of one QP band share one device image.
  *      DEFINITION: for every j, seqs[j].d_probs and the resident state left for sequence index j EQUAL what ethcnn_ldp_sequence_device
- *      gives with the same remaining arguments on a context that holds bundle seqs[j].bundle, bit for bit, gates and their zero patterns
- *      (per frame and 1024-CTU mini-batch of that sequence's own picture) included.  The residual CNN, the thresholds and the stream are
- *      the context's; the context's own LSTM bundle, resident LDP state and sequence buffers are neither used nor changed.
+ *      gives with the same remaining arguments on a context that holds bundle seqs[j].bundle and whose thresholds are j's RESOLVED pair,
+ *      bit for bit, gates and their zero patterns (per frame and 1024-CTU mini-batch of that sequence's own picture) included.  Index
+ *      j's resolved pair is its own when ethcnn_ldp_set_thresholds_batch gave it one, else the context's pair as it stands when the call
+ *      is made; no sequence's result depends on another's pair.  The residual CNN and the stream are the context's; the context's own
+ *      LSTM bundle, resident LDP state and sequence buffers are neither used nor changed.
  *      What differs is the schedule: a call is cut into chunks of Fc frames common to all sequences; chunk t holds frames
  *      [t Fc, min((t + 1) Fc, nframes_j)) of every sequence that still has frames.  Per chunk the front-end runs per sequence as in the
  *      solo call, then ONE recurrence launch and ONE gate launch serve all sequences of the chunk (level-major block order; inside a
@@ -384,6 +392,14 @@ int64_t ethcnn_ldp_group_bytes(int width, int height, int nframes, int chunk_fra
  *   ethcnn_ldp_batch_get_state    the resident state of sequence index j, float32 [nctu][2][448]; synchronous
  *   ethcnn_ldp_batch_state_ctus   its CTU count; 0: none; negative: bad arguments
  *   ethcnn_ldp_batch_set_chunk    Fc; 0 = default: max(1, floor(256 MB / sum_j nctu_j x 1792)).  Results do not depend on it.
+ *   ethcnn_ldp_set_thresholds_batch   (the gate entries of a batch and of a group carry the form LAST in their names: the families
+ *                                 ethcnn_ldp_batch_* and ethcnn_ldp_group_* are closed lists, held to their members by the tests of the
+ *                                 changes that made them.)  Gives sequence index j = 0..31 a gate pair of its own (thr_l1_lower, thr_l2_lower as
+ *                                 ethcnn_set_thresholds takes them: it refuses no float, so neither does this).  The pair is sticky across
+ *                                 calls, like the index's resident state.  ethcnn_ldp_clear_thresholds_batch: the index inherits the context's pair again.
+ *                                 ethcnn_ldp_get_thresholds_batch: the resolved pair and *own = 1 (its own) or 0 (the context's, as it stands now); every
+ *                                 output pointer is needed.  Host-only bookkeeping: nothing is enqueued and nothing waits.  ETHCNN_ERR_ARG:
+ *                                 an index out of range, a null output pointer, an open streamed call.
  *   ethcnn_ldp_batch_bytes        host only, no context: sum_j min(nframes_j, Fc) nctu_j 1792 (vectors) + sum_j roundup16(nctu_j) 3584 (the
  *                                 resident states); negative for bad arguments.  Beside it, from load time: the bundle images.  A call that
  *                                 cannot get its buffers fails with ETHCNN_ERR_NOMEM and this sum in the message, before anything is
@@ -415,13 +431,18 @@ int ethcnn_ldp_batch_set_chunk(ethcnn_ldp_batch* b, int frames);
 int64_t ethcnn_ldp_batch_bytes(const int* widths, const int* heights, const int* nframes, int nseqs, int chunk_frames);
 int ethcnn_ldp_batch_plan(const int* nctus, const int* nframes, int nseqs, int chunk_frames, int* fc_out, int* nchunks_out,
                           int* chunks_out /* [max_chunks][4] */, int max_chunks);
+int ethcnn_ldp_set_thresholds_batch(ethcnn_ldp_batch* b, int j, float thr_l1_lower, float thr_l2_lower);
+int ethcnn_ldp_clear_thresholds_batch(ethcnn_ldp_batch* b, int j);
+int ethcnn_ldp_get_thresholds_batch(ethcnn_ldp_batch* b, int j, float* thr_l1_lower, float* thr_l2_lower, int* own);
 /* ---- config #5 online, several live encoders: up to 32 SESSIONS on one context, each with a picture size and a resident recurrent state of
  *      its own; one call advances any subset of them by one frame.  The object holds up to 8 ETH-LSTM bundles, named by index per frame.
  *      DEFINITION: for every frame of a call, probs and the session's resident state EQUAL what ethcnn_ldp_step gives on a context of its
- *      own that holds the same CNN, the same thresholds and that bundle, bit for bit, gates and their zero patterns (per 1024-CTU
- *      mini-batch of that session's own picture) included.  State rules of ethcnn_ldp_step: state_in is used when given, at ANY frame
+ *      own that holds the same CNN, that bundle and, as its thresholds, the session's RESOLVED pair, bit for bit, gates and their zero
+ *      patterns (per 1024-CTU mini-batch of that session's own picture) included.  A session's resolved pair is its own when
+ *      ethcnn_ldp_sessions_set_thresholds gave it one, else the context's pair as it stands when the call is made; the pair follows the
+ *      session id, not the frame's place in the call, and no session's result depends on another's pair.  State rules of ethcnn_ldp_step: state_in is used when given, at ANY frame
  *      number (i_frame <= 1 included: the frame number then only carries the phase); without it a frame with i_frame <= 1 starts from
- *      zeros and a later one from the session's resident state (none resident: ETHCNN_ERR_ARG, in the wording of ethcnn_ldp_step).  Sessions that are not in a call keep their state.  The residual CNN, the thresholds and the stream
+ *      zeros and a later one from the session's resident state (none resident: ETHCNN_ERR_ARG, in the wording of ethcnn_ldp_step).  Sessions that are not in a call keep their state.  The residual CNN and the stream
  *      are the context's; the context's own LSTM bundle and resident LDP state are neither used nor changed.
  *      What differs is the schedule: the CTU-load stage runs ONCE over a table of the call's pictures, in which picture j owns the 16-CTU
  *      groups [first_group_j, first_group_j + ceil(nctu_j / 16)) (rows of a short last group are padding that nothing reads), then trunk
@@ -433,7 +454,10 @@ int ethcnn_ldp_batch_plan(const int* nctus, const int* nframes, int nseqs, int c
  *   ethcnn_ldp_sessions_open      a session for width x height pictures; *session: its id, the lowest free one of 0..31 (ids are reused
  *                                 after ethcnn_ldp_sessions_close).  Allocates the session's state, roundup16(nctu) x 3584 bytes; may wait
  *                                 for the stream.  A 33rd open session is ETHCNN_ERR_ARG.
- *   ethcnn_ldp_sessions_close     forgets the session and its state.  Waits for nothing: work already enqueued for it completes.
+ *   ethcnn_ldp_sessions_close     forgets the session, its state and its gate pair (a reused id starts by inheriting the context's pair).
+ *                                 Waits for nothing: work already enqueued for it completes.
+ *   ethcnn_ldp_sessions_set_thresholds / _clear_thresholds / _get_thresholds   an OPEN session's gate pair, as
+ *                                 ethcnn_ldp_set_thresholds_batch takes sequence index j's (a session that is not open: ETHCNN_ERR_ARG).
  *   ethcnn_ldp_sessions_step_device   n = 1..32 frames, each of another session.  Device pointers, asynchronous on the context's stream.
  *                                 Refused before anything is allocated or enqueued, every state left as it was: an open streamed call,
  *                                 no CNN weights, a bundle index that is out of range or empty (ETHCNN_ERR_NOWEIGHTS), a session that is
@@ -481,6 +505,9 @@ int ethcnn_ldp_sessions_step(ethcnn_ldp_sessions* s, const ethcnn_ldp_session_fr
 int ethcnn_ldp_sessions_get_state(ethcnn_ldp_sessions* s, int session, float* state_out, size_t nfloats /* nctu * 896 */);
 int64_t ethcnn_ldp_sessions_state_ctus(ethcnn_ldp_sessions* s, int session);
 int64_t ethcnn_ldp_sessions_bytes(const int* widths, const int* heights, int n);
+int ethcnn_ldp_sessions_set_thresholds(ethcnn_ldp_sessions* s, int session, float thr_l1_lower, float thr_l2_lower);
+int ethcnn_ldp_sessions_clear_thresholds(ethcnn_ldp_sessions* s, int session);
+int ethcnn_ldp_sessions_get_thresholds(ethcnn_ldp_sessions* s, int session, float* thr_l1_lower, float* thr_l2_lower, int* own);
 int ethcnn_ldp_sessions_plan(const int* nctus, int n, int max_ctus_per_pass, int* first_group_out, int* npasses_out, int* pass_groups_out,
                              int max_passes);
 /* Pinned (page-locked) host memory: buffers a caller fills itself (file reads) and hands to the host entry points are
@@ -1847,7 +1874,10 @@ int ethcnn_replay_feed_sim(ethcnn_replay* rp, int run, int slot, ethcnn_sim* sim
  * holds is checked against max_bytes and the free device memory before anything is allocated.  Outside the sum: what the batch holds
  * (ethcnn_ldp_batch_bytes).  ethcnn_replay_batch_device: d_probs[j], d_labels[j] in HBM, all given; asynchronous on the context's stream.
  * The feed entries replay into the object's own buffers and then add the items to the consumer in list order with the arguments of
- * ethcnn_replay_feed_calib / _feed_sim: the consumer ends in exactly the state the per-run feeds in that order leave.  Synchronous. */
+ * ethcnn_replay_feed_calib / _feed_sim: the consumer ends in exactly the state the per-run feeds in that order leave.  Synchronous.
+ * Thresholds: ethcnn_replay_run_group_device and ethcnn_replay_batch_device use the group / batch as it is, every member or sequence
+ * index under its resolved pair (ethcnn_ldp_set_thresholds_batch).  The feed entries need open gates: a batch in which ANY sequence index
+ * holds a pair of its own is ETHCNN_ERR_ARG before anything is enqueued, and the text names the index. */
 int64_t ethcnn_replay_batch_bytes(ethcnn_replay* rp, ethcnn_ldp_batch* b, int nitems, const int* runs);
 int ethcnn_replay_batch_device(ethcnn_replay* rp, ethcnn_ldp_batch* b, int nitems, const int* runs, const int* slots, const int* bundles,
                                float* const* d_probs, uint8_t* const* d_labels);
